@@ -17,10 +17,17 @@ pixels, 24.9 MB / N per peer; the collective is warmed up before the timed regio
 last step on rank 0; the rate without it -- the frame complete in rank 0's HBM, what BENCH_r05.json's `value` was -- is printed beside `value` as
 `frame_in_hbm`, the copy's own time as `host_readback`, and `config.value_definition` names the definition ("survey-8d/r6").
 
+A plain run sets up, warms up, times the K passes, writes the outputs (--dump-outputs DIR) and prints the line: `value`, `ms_per_step`, the
+timed run's own ray counters, `frame_in_hbm`, `host_readback`.  Everything else is measured only with --full:
+
 The roofline block is measured in the run itself: HIP-event launch times from a serial (one batch lane) replay of the same
 passes; `roofline.frac` = HBM-side traffic of the dominant kernel from two `rocprofv3 --pmc` child runs of the same passes
 (FETCH_SIZE, WRITE_SIZE, calibrated per kernel class; separate
-passes, kernel-trace only).  Prints ONE JSON line on rank 0.
+passes, kernel-trace only).  Also with --full: the box / triangle test counters (an instrumented replay), the CPU baseline and (N > 1) the
+check of the gathered frame against a one-GPU replay.  Prints ONE JSON line on rank 0.
+
+  python bench.py --gpus 1 --steps 256 --warmup 16 --full                 (+ roofline, kernel times, intersection counters, cpu_baseline)
+  python bench.py --gpus 1 --steps 20 --warmup 5 --dump-outputs DIR        (DIR/sum_buffer.npy: the frame the timed passes accumulated)
 """
 import argparse
 import ctypes as C
@@ -58,9 +65,13 @@ def parse_args():
     ap.add_argument("--depth", type=int, default=8)
     ap.add_argument("--triangles", type=int, default=262144)
     ap.add_argument("--workload", default="sponza", choices=["sponza", "sponza-textured", "sponza-all", "cornell", "sphere", "zoo", "bdpt-glass"])
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-pmc", action="store_true", help="skip the rocprofv3 --pmc child runs (roofline.traffic = null)")
-    ap.add_argument("--cpu-seconds", type=float, default=20.0, help="budget of the bounded CPU-baseline sample")
+    ap.add_argument("--full", action="store_true", help="also the replays, roofline, kernel times, intersection counters, CPU baseline and (N > 1) the "
+                    "one-GPU frame check; a plain run measures only the headline figure")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the timed path computed (the accumulated frame, float32) as DIR/<name>.npy")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="(--full) skip the CPU baseline")
+    ap.add_argument("--no-pmc", action="store_true", help="(--full) skip the rocprofv3 --pmc child runs (roofline.traffic = null)")
+    ap.add_argument("--cpu-seconds", type=float, default=20.0, help="(--full) budget of the bounded CPU-baseline sample")
     ap.add_argument("--pmc-child", action="store_true", help=argparse.SUPPRESS)   # internal: the profiled child of a bench run
     ap.add_argument("--walk-diag-child", action="store_true", help=argparse.SUPPRESS)   # internal: the instrumented-walk child (RTGPU_WIDE_DIAG=3)
     return ap.parse_args()
@@ -518,6 +529,23 @@ def work_changing_env():
     return {k: os.environ[k] for k in sorted(os.environ) if k.startswith(("BENCH_", "RTGPU_")) or k in ("GPU_MAX_HW_QUEUES",)}
 
 
+INTERSECTION_TEST_COUNTERS = ("numRayBoxTests", "numRayTriangleTests", "numShadowRayBoxTests", "numShadowRayTriangleTests")   # off in the timed region
+DUMP_MAX_BYTES = 64 << 20
+
+
+def dump_outputs(directory, frame):
+    """--dump-outputs: the frame the timed path computed -- the sum buffer after the warm-up and timed passes, as Viewport::GetSumBuffer hands it to
+    the caller -- as DIR/sum_buffer.npy (float32, height x width x 3).  The same arguments give the same scene, seed and passes, so two builds can be
+    compared array for array.  A frame above 64 MB is written as a fixed, seeded sample of its pixels instead (DIR/sum_buffer_sample.npy, n x 3)."""
+    os.makedirs(directory, exist_ok=True)
+    if frame.nbytes <= DUMP_MAX_BYTES:
+        np.save(os.path.join(directory, "sum_buffer.npy"), frame)
+        return
+    pixels = frame.reshape(-1, 3)
+    keep = np.sort(np.random.default_rng(SEED).choice(len(pixels), size=DUMP_MAX_BYTES // pixels[0].nbytes, replace=False))
+    np.save(os.path.join(directory, "sum_buffer_sample.npy"), pixels[keep])
+
+
 def main():
     args = parse_args()
     rank = int(os.environ.get("RANK", "0"))
@@ -642,6 +670,8 @@ def main():
     readback_s = elapsed - elapsed_hbm
     if rank == 0:
         host.rth_viewport_read_sum(vp._h, host_sum.ctypes.data_as(C.POINTER(C.c_float)), None)   # a copy of that bitmap for the checks below
+        if args.dump_outputs:
+            dump_outputs(args.dump_outputs, host_sum)
 
     c1 = vp.counters()
     delta = {k: c1[k] - c0[k] for k in c1}
@@ -677,14 +707,16 @@ def main():
         times = kernel_times(vctx) if timing else None
         return {k: a1[k] - a0[k] for k in a1}, dict(a1), times
 
-    serial, _, ktimes = replay(1, False, True)
-    assert serial["numRays"] == delta["numRays"] and serial["numShadowRays"] == delta["numShadowRays"], "serial replay diverged from the timed run"
-    # instrumented replay for the intersection counters (not timed)
-    counted, counted_totals, _ = replay(1, True, False)
-    assert counted["numRays"] == delta["numRays"] and counted["numShadowRays"] == delta["numShadowRays"], "replay diverged from the timed run"
-    for k in ("numRayBoxTests", "numPassedRayBoxTests", "numRayTriangleTests", "numPassedRayTriangleTests", "numShadowRayBoxTests",
-              "numShadowRayTriangleTests"):
-        delta[k] = counted[k]
+    ktimes = counted_totals = None   # a plain run: no replays, so no kernel times, intersection counters or roofline
+    if args.full:
+        serial, _, ktimes = replay(1, False, True)
+        assert serial["numRays"] == delta["numRays"] and serial["numShadowRays"] == delta["numShadowRays"], "serial replay diverged from the timed run"
+        # instrumented replay for the intersection counters (not timed)
+        counted, counted_totals, _ = replay(1, True, False)
+        assert counted["numRays"] == delta["numRays"] and counted["numShadowRays"] == delta["numShadowRays"], "replay diverged from the timed run"
+        for k in ("numRayBoxTests", "numPassedRayBoxTests", "numRayTriangleTests", "numPassedRayTriangleTests", "numShadowRayBoxTests",
+                  "numShadowRayTriangleTests"):
+            delta[k] = counted[k]
     own_counts = dict(delta)
 
     scaling_report = None
@@ -706,7 +738,7 @@ def main():
             "per_rank_process_group_init_s": [round(r[5], 3) for r in per_rank], "per_rank_gather_warmup_s": [round(r[6], 3) for r in per_rank],
             "exchange": {"mode": gather.mode, "reason": gather.mode_reason, "backend": backend, "backend_fallback": backend_fallback},
         }
-        if rank == 0:
+        if rank == 0 and args.full:
             # the same warm-up + timed passes on ONE device, whole frame: the gathered frame must be that frame, bit for bit
             try:
                 whole = make_viewport(ra, args, scene, local_rank, None)
@@ -753,9 +785,11 @@ def main():
                        "env": work_changing_env(), "emulated_shard": [0, emulate] if emulate > 1 else None,
                        "dist_backend": backend if world > 1 else None},
             "counters": {k: delta[k] for k in ("numRays", "numPrimaryRays", "numShadowRays", "numRayBoxTests", "numRayTriangleTests",
-                                               "numShadowRayBoxTests", "numShadowRayTriangleTests", "numMeshHits", "numAnalyticHits")},
+                                               "numShadowRayBoxTests", "numShadowRayTriangleTests", "numMeshHits", "numAnalyticHits")
+                         if args.full or k not in INTERSECTION_TEST_COUNTERS},
             "mrays_per_s_incl_shadow": (delta["numRays"] + delta["numShadowRays"]) / elapsed / 1e6,
-            "intersection_counters": "off in the timed region (reference default); counts from an identical instrumented replay",
+            "intersection_counters": "off in the timed region (reference default); counts from an identical instrumented replay" if args.full else
+                                     "off in the timed region (reference default); not collected (--full replays the passes with them on)",
             "image": {"finite": image_ok, "mean_per_pass": image_mean},
             # the region without its last step: the frame complete in rank 0's HBM (what BENCH_r05.json called `value`; rounds 1-4 and this round: read-back inside)
             "frame_in_hbm": {"value": delta["numRays"] / elapsed_hbm / 1e6, "ms_per_step": 1000.0 * elapsed_hbm / max(1, args.steps)},
@@ -768,9 +802,11 @@ def main():
         if scaling_report:
             out["multi_gpu"] = scaling_report
         # roofline of the dominant kernel class (rank 0's own launches and rank 0's own counters)
-        abytes = algorithmic_bytes(own_counts)
-        abytes_replay = algorithmic_bytes(counted_totals)   # warm-up + timed passes: what the replay's launches processed
+        # (--full only: a plain run has no kernel times, so no dominant class)
         dom = max(ktimes, key=lambda k: ktimes[k][0]) if ktimes else None
+        if dom:
+            abytes = algorithmic_bytes(own_counts)
+            abytes_replay = algorithmic_bytes(counted_totals)   # warm-up + timed passes: what the replay's launches processed
         if dom and ktimes[dom][0] > 0:
             traffic, traffic_error = (None, "skipped (--no-pmc)") if (args.no_pmc or world > 1) else measure_traffic(args)
             launches = ktimes[dom][1]
@@ -891,7 +927,7 @@ def main():
             tot_bytes = sum(abytes.values())
             out["whole_pass_reference_walk_GBs"] = tot_bytes / elapsed / 1e9
 
-        if world == 1 and not args.no_cpu_baseline:
+        if world == 1 and args.full and not args.no_cpu_baseline:
             out["cpu_baseline"] = cpu_baseline(args, scene, camera, ra)
         line = json.dumps(out)
     else:

@@ -6,8 +6,10 @@ pass.  Build container only (needs oracle/_ref/ref_render).  Regenerate: python 
 File: uint32 magic 'RRF1', width, height, passes, maxRayDepth, samplingAll, dimensions, numSeeds; uint64 numRays, numPrimaryRays,
 numShadowRays, numShadowRaysHit; float32 sampleOffset[2]; uint32 seeds[numSeeds]; float32 image[height][width][3]."""
 import os
+import shutil
 import struct
 import sys
+import tempfile
 
 import numpy as np
 
@@ -17,6 +19,8 @@ sys.path.insert(0, os.path.dirname(HERE))
 sys.path.insert(0, os.path.dirname(os.path.dirname(HERE)))
 import ref_render   # noqa: E402
 import ref_scenes   # noqa: E402
+
+SCRATCH = tempfile.mkdtemp(prefix="ref_fixture_")   # private to this run: two runs at once must not read each other's scene or output files
 
 def write_fixture(name, w, h, passes, depth, sampling_all, dims, out):
     with open(os.path.join(OUT, "ref_render", name + ".bin"), "wb") as f:
@@ -32,7 +36,7 @@ def make_statistical(names=None):
         if names and name not in names:
             continue
         scene, camera = make(w / h)
-        path = "/tmp/ref_fixture_%s.bin" % name
+        path = os.path.join(SCRATCH, name + ".bin")
         ref_render.export_scene(path, scene, camera, w, h, passes, 1, depth, dimensions=dims, light_sampling_all=sampling_all, seed=ref_scenes.SEED)
         stats, out = ref_render.run(path, threads=1)       # one thread: the per-thread generator's light picks are then a function of the seed
         os.remove(path)
@@ -47,10 +51,11 @@ if __name__ == "__main__":
     if which in ("all", "statistical"):
         make_statistical()
     if which == "statistical":
+        shutil.rmtree(SCRATCH, ignore_errors=True)
         sys.exit(0)
     for name, (make, w, h, passes, depth, sampling_all, dims) in ref_scenes.FIXTURES.items():
         scene, camera = make(w / h)
-        path = "/tmp/ref_fixture_%s.bin" % name
+        path = os.path.join(SCRATCH, name + ".bin")
         ref_render.export_scene(path, scene, camera, w, h, passes, 4, depth, dimensions=dims, light_sampling_all=sampling_all, seed=ref_scenes.SEED)
         stats, out = ref_render.run(path)
         again, out2 = ref_render.run(path, threads=1)      # the result must not depend on the thread count
@@ -58,3 +63,4 @@ if __name__ == "__main__":
         os.remove(path)
         write_fixture(name, w, h, passes, depth, sampling_all, dims, out)
         print(name, stats["mean"], out["numRays"], out["numShadowRays"])
+    shutil.rmtree(SCRATCH, ignore_errors=True)

@@ -70,20 +70,22 @@ def test_bench_line_names_every_switch_that_changed_its_work(built):
     RTGPU_* / BENCH_* variable in the environment goes into config.env -- also on the reduced BENCH_TIMED_ONLY line."""
     import json
     import subprocess
-    common = ["--steps", "4", "--warmup", "2", "--width", "640", "--height", "360", "--triangles", "20000", "--no-pmc", "--no-cpu-baseline"]
+    common = ["--steps", "4", "--warmup", "2", "--width", "640", "--height", "360", "--triangles", "20000", "--full", "--no-pmc", "--no-cpu-baseline"]
     env = {k: v for k, v in os.environ.items() if not k.startswith(("BENCH_", "RTGPU_"))}
+    # the HIP runtime's queue count changes the work too (config.env names it): whatever the launching environment sets is reported as it is
+    outer = {k: env[k] for k in ("GPU_MAX_HW_QUEUES",) if k in env}
     r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py")] + common, env=dict(env, BENCH_EMULATE_SHARD="4", RTGPU_PACKET="0"), capture_output=True, text=True, timeout=900, cwd=ROOT)
     assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-2000:]
     d = json.loads([l for l in r.stdout.splitlines() if l.startswith("{")][0])
     assert d["config"]["emulated_shard"] == [0, 4] and "EMULATED SHARD: 1/4 of the frame" in d["metric"] and d["config"]["parallelism"].startswith("emulated shard 0 of 4")
-    assert d["config"]["env"] == {"BENCH_EMULATE_SHARD": "4", "RTGPU_PACKET": "0"} and d["n_gpus"] == 1
+    assert d["config"]["env"] == dict(outer, BENCH_EMULATE_SHARD="4", RTGPU_PACKET="0") and d["n_gpus"] == 1
     r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py")] + common, env=dict(env, BENCH_TIMED_ONLY="1", BENCH_EMULATE_SHARD="2"), capture_output=True, text=True, timeout=900, cwd=ROOT)
     assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-2000:]
     d = json.loads([l for l in r.stdout.splitlines() if l.startswith("{")][0])
-    assert d["timed_only"] and d["config"]["emulated_shard"] == [0, 2] and d["config"]["env"] == {"BENCH_EMULATE_SHARD": "2", "BENCH_TIMED_ONLY": "1"}
+    assert d["timed_only"] and d["config"]["emulated_shard"] == [0, 2] and d["config"]["env"] == dict(outer, BENCH_EMULATE_SHARD="2", BENCH_TIMED_ONLY="1")
     r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py")] + common, env=env, capture_output=True, text=True, timeout=900, cwd=ROOT)
     d = json.loads([l for l in r.stdout.splitlines() if l.startswith("{")][0])
-    assert d["config"]["env"] == {} and d["config"]["emulated_shard"] is None and "EMULATED" not in d["metric"]
+    assert d["config"]["env"] == outer and d["config"]["emulated_shard"] is None and "EMULATED" not in d["metric"]
     # SURVEY 8(d): the timed region ends with the final read_sum (Viewport::GetSumBuffer); the rate with the frame complete in HBM is printed beside `value`
     hr = d["host_readback"]
     assert hr["in_value"] is True and hr["ms"] > 0 and hr["bytes"] == 640 * 360 * 12
@@ -97,6 +99,34 @@ def test_bench_line_names_every_switch_that_changed_its_work(built):
     assert r["roof"] == "hbm" and r["peak"] == 8000.0 and r["unit"] == "GB/s"    # `frac` is always a fraction of THIS roof; `bound` names the nearest measured ceiling
     assert r["frac"] is None and r["achieved"] is None and r["algorithmic_bytes_per_launch"] is None and str(r["algorithmic_model"]).startswith("n/a")
     assert r["request_rate_over_hbm_peak"] is None and r["traffic"] is None and r["reference_walk_bytes_per_launch"] > 0 and "non-physical" in r["reference_walk_note"]
+
+
+def test_plain_bench_run_times_its_steps_and_dumps_its_frame(built, tmp_path):
+    """A plain run (no --full) measures the headline figure only: the result line says what it measured, --steps sets the number of timed passes,
+    nothing of --full's replays is in it, and --dump-outputs writes the frame the passes accumulated -- the same frame, bit for bit, on a second run."""
+    import json
+    import subprocess
+    import numpy as np
+    w, h, steps, warmup = 640, 360, 4, 2
+    common = ["--gpus", "1", "--steps", str(steps), "--warmup", str(warmup), "--width", str(w), "--height", str(h), "--triangles", "20000"]
+    env = {k: v for k, v in os.environ.items() if not k.startswith(("BENCH_", "RTGPU_"))}
+    frames = []
+    for run in ("a", "b"):
+        r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py")] + common + ["--dump-outputs", str(tmp_path / run)], env=env, capture_output=True, text=True,
+                           timeout=900, cwd=ROOT)
+        assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-2000:]
+        lines = [l for l in r.stdout.splitlines() if l.startswith("{")]
+        assert len(lines) == 1
+        d = json.loads(lines[0])
+        assert d["unit"] == "Msamples/s" and d["higher_is_better"] is True and d["dtype"] == "f32" and "Msamples/sec" in d["metric"] and d["value"] > 0
+        assert d["steps"] == steps and d["ms_per_step"] > 0 and d["counters"]["numPrimaryRays"] == w * h * steps
+        assert not {"roofline", "kernel_time_ms", "cpu_baseline"} & set(d) and "numRayBoxTests" not in d["counters"]
+        assert os.listdir(tmp_path / run) == ["sum_buffer.npy"]
+        frame = np.load(tmp_path / run / "sum_buffer.npy")
+        assert frame.dtype == np.float32 and frame.shape == (h, w, 3) and np.isfinite(frame).all()
+        assert float(frame.mean()) / (steps + warmup) == d["image"]["mean_per_pass"]
+        frames.append(frame)
+    assert np.array_equal(frames[0].view(np.uint32), frames[1].view(np.uint32))
 
 
 def _committed_trace_class_average_ms():
@@ -125,7 +155,7 @@ def test_roofline_block_is_a_fraction_of_a_roof(built, steps, warmup):
     import json
     import subprocess
     env = {k: v for k, v in os.environ.items() if not k.startswith(("BENCH_", "RTGPU_"))}
-    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", str(steps), "--warmup", str(warmup), "--no-cpu-baseline"], env=env,
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", str(steps), "--warmup", str(warmup), "--full", "--no-cpu-baseline"], env=env,
                        capture_output=True, text=True, timeout=1800, cwd=ROOT)
     assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-2000:]
     d = json.loads([l for l in r.stdout.splitlines() if l.startswith("{")][0])

@@ -5,7 +5,7 @@ export TMPDIR=/tmp
 ARGS="$1"; shift
 for rep in 1 2; do
 for E in "$@"; do
-  env $E python bench.py $ARGS --no-pmc --no-cpu-baseline 2>/dev/null | tail -1 | python -c "
+  env $E python bench.py --full $ARGS --no-pmc --no-cpu-baseline 2>/dev/null | tail -1 | python -c "
 import sys, json
 d = json.loads(sys.stdin.read())
 kt = d.get('kernel_time_ms', {})

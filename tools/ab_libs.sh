@@ -7,7 +7,7 @@ for rep in 1 2; do
 for name in "$@"; do
   if [ $name = base ]; then cp /tmp/librtgpu_base.so raytracer_amd/lib/librtgpu.so; else cp variants/librtgpu_$name.so raytracer_amd/lib/librtgpu.so; fi
   touch raytracer_amd/lib/librtgpu.so raytracer_amd/lib/libraytracer_amd_host.so raytracer_amd/lib/rt_demo
-  python bench.py $ARGS --no-pmc --no-cpu-baseline 2>/dev/null | tail -1 | python -c "
+  python bench.py --full $ARGS --no-pmc --no-cpu-baseline 2>/dev/null | tail -1 | python -c "
 import sys, json
 d = json.loads(sys.stdin.read())
 kt = d.get('kernel_time_ms', {})

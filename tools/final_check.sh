@@ -7,7 +7,7 @@ mkdir -p $T
 timeout 1800 python -m pytest tests -q -m gpu 2>&1 | grep -v "^$" | grep "passed\|failed\|error\|^\." > $T/pytest_gpu.log
 tail -2 $T/pytest_gpu.log
 python -c "import __graft_entry__ as g; g.smoke()" 2>&1 | grep "^smoke" > $T/smoke.log; cat $T/smoke.log
-python bench.py --steps 20 --warmup 5 > $T/bench_default_steps20.json 2> $T/bench_default_steps20.err
+python bench.py --full --steps 20 --warmup 5 > $T/bench_default_steps20.json 2> $T/bench_default_steps20.err
 tail -1 $T/bench_default_steps20.json | python -c "
 import sys, json
 d = json.loads(sys.stdin.read()); r = d['roofline']

@@ -1,10 +1,11 @@
 # What bounds k_trace / k_shade?  Texture-addresser (TA), L1 (TCP) and data-return (TD) counters of `RTGPU_LANES=1 python bench.py`,
 # one rocprofv3 --pmc pass per counter group (kernel-trace only).  usage: tools/pmc_diag.sh <tag> [bench args]
 cd $GRAFT_REPO_ROOT
+RUNS=${RUNS:-runs}   # where the run records go
 export TMPDIR=/tmp
 T=${1:-diag}; shift
 ARGS=${@:---steps 24 --warmup 8}
-mkdir -p gpurun_out/$T
+mkdir -p $RUNS/$T
 i=0
 for group in \
   "TA_TA_BUSY_sum TA_BUSY_avr TA_ADDR_STALLED_BY_TC_CYCLES_sum TA_DATA_STALLED_BY_TC_CYCLES_sum TA_FLAT_READ_WAVEFRONTS_sum TA_FLAT_WRITE_WAVEFRONTS_sum GRBM_GUI_ACTIVE" \
@@ -17,9 +18,9 @@ for group in \
   "TCC_HIT_sum TCC_MISS_sum TCC_REQ_sum TCC_EA0_RDREQ_sum" \
   ; do
   i=$((i+1))
-  RTGPU_LANES=1 timeout 300 rocprofv3 --kernel-trace --pmc $group -d gpurun_out/$T/p$i -o r -- python bench.py --no-cpu-baseline $ARGS > gpurun_out/$T/bench_p$i.json 2> gpurun_out/$T/err_p$i.txt
-  db=$(find gpurun_out/$T/p$i -name '*.db' | head -1)
-  if [ -n "$db" ]; then python tools/rocpd_summary.py $db > gpurun_out/$T/pmc_$i.txt; else echo "pass $i: no db"; tail -3 gpurun_out/$T/err_p$i.txt; fi
-  rm -rf gpurun_out/$T/p$i
+  RTGPU_LANES=1 timeout 300 rocprofv3 --kernel-trace --pmc $group -d $RUNS/$T/p$i -o r -- python bench.py --full --no-cpu-baseline $ARGS > $RUNS/$T/bench_p$i.json 2> $RUNS/$T/err_p$i.txt
+  db=$(find $RUNS/$T/p$i -name '*.db' | head -1)
+  if [ -n "$db" ]; then python tools/rocpd_summary.py $db > $RUNS/$T/pmc_$i.txt; else echo "pass $i: no db"; tail -3 $RUNS/$T/err_p$i.txt; fi
+  rm -rf $RUNS/$T/p$i
 done
-cat gpurun_out/$T/pmc_*.txt | grep -v "^#" | grep "k_trace<24, false>\|k_shade<true" | grep -v " 256$"
+cat $RUNS/$T/pmc_*.txt | grep -v "^#" | grep "k_trace<24, false>\|k_shade<true" | grep -v " 256$"

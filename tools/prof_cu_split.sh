@@ -9,14 +9,14 @@ mkdir -p $(dirname $OUT)
 run() {   # label, env assignments...
   label=$1; shift
   for rep in 1 2; do
-    env "$@" python bench.py --steps $STEPS --warmup $WARM --no-pmc --no-cpu-baseline 2>/dev/null | tail -1 | python -c "
+    env "$@" python bench.py --full --steps $STEPS --warmup $WARM --no-pmc --no-cpu-baseline 2>/dev/null | tail -1 | python -c "
 import sys, json
 d = json.loads(sys.stdin.read())
 print('%-46s %8.1f Msamples/s  %.3f ms/pass (frame in HBM %.3f)  serial kernel ms %s' % ('$label', d['value'], d['ms_per_step'], d['frame_in_hbm']['ms_per_step'], {k: round(v, 1) for k, v in d['kernel_time_ms'].items() if v}))
 " >> $OUT
   done
 }
-echo "# python bench.py --steps $STEPS --warmup $WARM --no-pmc --no-cpu-baseline; two runs per setting; $(date -u)" >> $OUT
+echo "# python bench.py --full --steps $STEPS --warmup $WARM --no-pmc --no-cpu-baseline; two runs per setting; $(date -u)" >> $OUT
 run "default (no partition)" RTGPU_VERBOSE=0
 for K in 16 32 64; do
   for LAYOUT in 0 1; do

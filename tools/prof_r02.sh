@@ -4,17 +4,17 @@ export TMPDIR=/tmp
 T=gpurun_out/r02
 mkdir -p $T
 # 1. what the driver runs (in-run roofline: HIP events + two --pmc child runs; CPU baseline = the reference's objects)
-python bench.py --steps 20 --warmup 5 > $T/bench_default_steps20.json 2> $T/bench_default_steps20.err
+python bench.py --full --steps 20 --warmup 5 > $T/bench_default_steps20.json 2> $T/bench_default_steps20.err
 # 2. the same passes under rocprofv3 --kernel-trace --stats with serial lanes: the population the roofline's launch time is quoted on
-RTGPU_LANES=1 rocprofv3 --kernel-trace --stats -d $T/prof_serial -o r -- python bench.py --steps 20 --warmup 5 --no-pmc --no-cpu-baseline > $T/bench_serial_profiled.json 2>/dev/null
+RTGPU_LANES=1 rocprofv3 --kernel-trace --stats -d $T/prof_serial -o r -- python bench.py --full --steps 20 --warmup 5 --no-pmc --no-cpu-baseline > $T/bench_serial_profiled.json 2>/dev/null
 python tools/rocpd_summary.py $(find $T/prof_serial -name '*.db' | head -1) > $T/kernel_stats_serial.txt
 rm -rf $T/prof_serial
 # 3. longer streams and the other workloads
-for steps in 64 256; do python bench.py --steps $steps --warmup 5 --no-pmc --cpu-seconds 0 > $T/bench_steps$steps.json 2>/dev/null; done
-python bench.py --workload bdpt-glass --steps 20 --warmup 5 > $T/bench_config5_bdpt_glass.json 2>/dev/null
-python bench.py --workload sponza-textured --steps 64 --warmup 5 --no-pmc --cpu-seconds 0 > $T/bench_sponza_textured.json 2>/dev/null
-python bench.py --workload cornell --width 640 --height 480 --depth 4 --steps 16 --warmup 4 --no-pmc --cpu-seconds 0 > $T/bench_config1_cornell.json 2>/dev/null
-python bench.py --workload sphere --steps 64 --warmup 5 --no-pmc --cpu-seconds 0 > $T/bench_config2_sphere.json 2>/dev/null
+for steps in 64 256; do python bench.py --full --steps $steps --warmup 5 --no-pmc --cpu-seconds 0 > $T/bench_steps$steps.json 2>/dev/null; done
+python bench.py --full --workload bdpt-glass --steps 20 --warmup 5 > $T/bench_config5_bdpt_glass.json 2>/dev/null
+python bench.py --full --workload sponza-textured --steps 64 --warmup 5 --no-pmc --cpu-seconds 0 > $T/bench_sponza_textured.json 2>/dev/null
+python bench.py --full --workload cornell --width 640 --height 480 --depth 4 --steps 16 --warmup 4 --no-pmc --cpu-seconds 0 > $T/bench_config1_cornell.json 2>/dev/null
+python bench.py --full --workload sphere --steps 64 --warmup 5 --no-pmc --cpu-seconds 0 > $T/bench_config2_sphere.json 2>/dev/null
 # 4. what bounds k_trace_wide: SQ / TCP / TCC counters, one --pmc pass per group
 i=0
 for group in \
@@ -24,7 +24,7 @@ for group in \
   "TCC_HIT_sum TCC_MISS_sum TCC_REQ_sum TCC_EA0_RDREQ_sum" \
   ; do
   i=$((i+1))
-  RTGPU_LANES=1 timeout 300 rocprofv3 --kernel-trace --pmc $group -d $T/p$i -o r -- python bench.py --steps 20 --warmup 5 --no-pmc --no-cpu-baseline > /dev/null 2> $T/err_p$i.txt
+  RTGPU_LANES=1 timeout 300 rocprofv3 --kernel-trace --pmc $group -d $T/p$i -o r -- python bench.py --full --steps 20 --warmup 5 --no-pmc --no-cpu-baseline > /dev/null 2> $T/err_p$i.txt
   db=$(find $T/p$i -name '*.db' | head -1)
   if [ -n "$db" ]; then python tools/rocpd_summary.py $db > $T/wide_pmc_$i.txt; else echo "pass $i: no db"; tail -3 $T/err_p$i.txt; fi
   rm -rf $T/p$i $T/err_p$i.txt

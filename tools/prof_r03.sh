@@ -4,9 +4,9 @@ export TMPDIR=/tmp
 T=gpurun_out/r03
 mkdir -p $T
 # 1. what the driver runs (in-run roofline: HIP events + three --pmc child runs; CPU baseline = the reference's objects)
-python bench.py --steps 20 --warmup 5 > $T/bench_default_steps20.json 2> $T/bench_default_steps20.err
+python bench.py --full --steps 20 --warmup 5 > $T/bench_default_steps20.json 2> $T/bench_default_steps20.err
 # 2. the same passes under rocprofv3 --kernel-trace --stats with serial lanes: the population the roofline's launch time is quoted on
-RTGPU_LANES=1 rocprofv3 --kernel-trace --stats -d $T/prof_serial -o r -- python bench.py --steps 20 --warmup 5 --no-pmc --no-cpu-baseline > $T/bench_serial_profiled.json 2>/dev/null
+RTGPU_LANES=1 rocprofv3 --kernel-trace --stats -d $T/prof_serial -o r -- python bench.py --full --steps 20 --warmup 5 --no-pmc --no-cpu-baseline > $T/bench_serial_profiled.json 2>/dev/null
 python tools/rocpd_summary.py $(find $T/prof_serial -name '*.db' | head -1) > $T/kernel_stats_serial.txt
 rm -rf $T/prof_serial
 # 3. the counters behind roofline.traffic and roofline.ceilings, one --pmc pass per group (the same groups bench.py's child runs collect)
@@ -18,22 +18,22 @@ for group in \
   "TCC_HIT_sum TCC_MISS_sum TCC_REQ_sum TCC_EA0_RDREQ_sum" \
   ; do
   i=$((i+1))
-  RTGPU_LANES=1 timeout 300 rocprofv3 --kernel-trace --pmc $group -d $T/p$i -o r -- python bench.py --steps 20 --warmup 5 --no-pmc --no-cpu-baseline > /dev/null 2> $T/err_p$i.txt
+  RTGPU_LANES=1 timeout 300 rocprofv3 --kernel-trace --pmc $group -d $T/p$i -o r -- python bench.py --full --steps 20 --warmup 5 --no-pmc --no-cpu-baseline > /dev/null 2> $T/err_p$i.txt
   db=$(find $T/p$i -name '*.db' | head -1)
   if [ -n "$db" ]; then python tools/rocpd_summary.py $db > $T/pmc_$i.txt; else echo "pass $i: no db"; tail -3 $T/err_p$i.txt; fi
   rm -rf $T/p$i $T/err_p$i.txt
 done
 # 4. longer streams and the other workloads
-for steps in 64 256; do python bench.py --steps $steps --warmup 5 --no-pmc --cpu-seconds 0 > $T/bench_steps$steps.json 2>/dev/null; done
-python bench.py --workload sponza-all --steps 20 --warmup 5 --no-pmc --cpu-seconds 0 > $T/bench_sponza_all.json 2>/dev/null
-python bench.py --workload bdpt-glass --steps 20 --warmup 5 --no-pmc --cpu-seconds 0 > $T/bench_config5_bdpt_glass.json 2>/dev/null
-python bench.py --workload sponza-textured --steps 64 --warmup 5 --no-pmc --cpu-seconds 0 > $T/bench_sponza_textured.json 2>/dev/null
-python bench.py --workload cornell --width 640 --height 480 --depth 4 --steps 16 --warmup 4 --no-pmc --cpu-seconds 0 > $T/bench_config1_cornell.json 2>/dev/null
-python bench.py --workload cornell --steps 32 --warmup 4 --no-pmc --cpu-seconds 0 > $T/bench_cornell_1080p.json 2>/dev/null
-python bench.py --workload zoo --steps 32 --warmup 4 --no-pmc --cpu-seconds 0 > $T/bench_zoo_1080p.json 2>/dev/null
-python bench.py --workload sphere --steps 64 --warmup 5 --no-pmc --cpu-seconds 0 > $T/bench_config2_sphere.json 2>/dev/null
+for steps in 64 256; do python bench.py --full --steps $steps --warmup 5 --no-pmc --cpu-seconds 0 > $T/bench_steps$steps.json 2>/dev/null; done
+python bench.py --full --workload sponza-all --steps 20 --warmup 5 --no-pmc --cpu-seconds 0 > $T/bench_sponza_all.json 2>/dev/null
+python bench.py --full --workload bdpt-glass --steps 20 --warmup 5 --no-pmc --cpu-seconds 0 > $T/bench_config5_bdpt_glass.json 2>/dev/null
+python bench.py --full --workload sponza-textured --steps 64 --warmup 5 --no-pmc --cpu-seconds 0 > $T/bench_sponza_textured.json 2>/dev/null
+python bench.py --full --workload cornell --width 640 --height 480 --depth 4 --steps 16 --warmup 4 --no-pmc --cpu-seconds 0 > $T/bench_config1_cornell.json 2>/dev/null
+python bench.py --full --workload cornell --steps 32 --warmup 4 --no-pmc --cpu-seconds 0 > $T/bench_cornell_1080p.json 2>/dev/null
+python bench.py --full --workload zoo --steps 32 --warmup 4 --no-pmc --cpu-seconds 0 > $T/bench_zoo_1080p.json 2>/dev/null
+python bench.py --full --workload sphere --steps 64 --warmup 5 --no-pmc --cpu-seconds 0 > $T/bench_config2_sphere.json 2>/dev/null
 # 5. what rank 0 of N pays at the driver's step count (the tiles it would own; every rank does the same amount of work in parallel)
-for n in 2 4 8; do BENCH_EMULATE_SHARD=$n python bench.py --steps 20 --warmup 5 --no-pmc --cpu-seconds 0 > $T/bench_emulated_shard_$n.json 2>/dev/null; done
+for n in 2 4 8; do BENCH_EMULATE_SHARD=$n python bench.py --full --steps 20 --warmup 5 --no-pmc --cpu-seconds 0 > $T/bench_emulated_shard_$n.json 2>/dev/null; done
 # 6. the GPU test suite and the smoke test
 python -m pytest tests -q -m gpu 2>&1 | grep -v "^$" | grep "passed\|failed\|error\|^\." > $T/pytest_gpu.log
 python -c "import __graft_entry__ as g; g.smoke()" 2>&1 | grep "^smoke" > $T/smoke.log

@@ -4,7 +4,7 @@ export TMPDIR=/tmp
 T=gpurun_out/r3b
 mkdir -p $T
 tools/microbench/cadence > $T/cadence.txt 2>&1
-RTGPU_LANES=1 rocprofv3 --kernel-trace -d $T/prof_serial -o r -- python bench.py --steps 20 --warmup 5 --no-pmc --no-cpu-baseline > $T/bench_serial_profiled.json 2>/dev/null
+RTGPU_LANES=1 rocprofv3 --kernel-trace -d $T/prof_serial -o r -- python bench.py --full --steps 20 --warmup 5 --no-pmc --no-cpu-baseline > $T/bench_serial_profiled.json 2>/dev/null
 db=$(find $T/prof_serial -name '*.db' | head -1)
 python tools/rocpd_summary.py $db > $T/kernel_stats_serial.txt
 python tools/rocpd_summary.py --timeline $db > $T/timeline_serial.txt

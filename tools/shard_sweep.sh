@@ -1,5 +1,5 @@
 cd $GRAFT_REPO_ROOT
-run() { env $1 python bench.py --steps 20 --warmup 5 --no-pmc --no-cpu-baseline 2>/dev/null | tail -1 | python -c "
+run() { env $1 python bench.py --full --steps 20 --warmup 5 --no-pmc --no-cpu-baseline 2>/dev/null | tail -1 | python -c "
 import sys, json
 d = json.loads(sys.stdin.read())
 print('%-60s %8.1f Msamples/s %7.3f ms/pass' % ('$1', d['value'], d['ms_per_step']))
