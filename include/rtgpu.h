@@ -539,6 +539,70 @@ int rtgpu_set_active_blocks(RtgpuContext* ctx, uint32_t numBlocks, const RtBlock
  * checked against the reference's vectors directly (tests/golden/texture_kat.bin). */
 int rtgpu_evaluate_textures(RtgpuContext* ctx, uint32_t count, const uint32_t* textureIndex, const float* uv, float* out);
 
+/* ---------------------------------------------------------------------------------------------
+ * Batched ray queries: Scene::Traverse (Core/Scene/Scene.h:56), Scene::Traverse_Shadow (:60) and Scene::EvaluateIntersection (:62) of the
+ * uploaded scene.  Closest-hit rays take the walk the context renders with (the 4-wide walks and their re-trace hand-over by default; the
+ * reference's binary walk under rtgpu_set_intersection_counters(ctx, 1)) from +inf, and maxDistance is applied to the result; any-hit rays take
+ * the reference's binary walk with tmax = maxDistance (the 4-wide walks' any-hit decision is not exact for a tmax within an ulp of a hit).
+ *   ray        Ray(origin, direction) as the reference's constructor builds it: the direction is normalised and distances are measured along
+ *              it; no origin offset is applied (offsetting is the caller's job).
+ *   RTGPU_TRACE_CLOSEST  hits[i] = Scene::Traverse with hitPoint.distance = maxDistance (+inf allowed).  Miss: objectId RT_INVALID_OBJECT,
+ *              distance = maxDistance, subObjectId = u = v = 0.  A finite light: subObjectId RT_LIGHT_OBJECT.  u, v are the barycentrics of a mesh
+ *              triangle; 0 on analytic shapes and lights.  surfaces (may be NULL) = Scene::EvaluateIntersection of the hit, normal mapping
+ *              included; on a miss all zeros with material RT_NO_MATERIAL.
+ *   RTGPU_TRACE_ANY      occluded[i] = Scene::Traverse_Shadow with hitPoint.distance = maxDistance, 1 or 0 (no offset: the Light Tracer's 0).
+ *   degenerate rays      a non-finite origin, a zero or non-finite direction (its squared length 0 or not finite), or maxDistance NaN or <= 0:
+ *              closest -> a miss (distance = maxDistance), any -> 0, never an undefined memory access.  rtgpu_trace_rays refuses a call that
+ *              holds one (RTGPU_ERR_INVALID_ARGUMENT); rtgpu_trace_rays_async cannot inspect device memory, and the result rule holds there.
+ *   stats      (may be NULL) the query's own counters, counted as the render counters are (box / triangle tests with the intersection counters
+ *              on: closest-hit tests -- those of the walk from +inf -- in numRay*Tests, any-hit tests in numShadowRay*Tests; numRays = the call's
+ *              closest-hit rays; numMeshHits / numAnalyticHits = evaluated surfaces).  A query never adds to what rtgpu_get_counters reports.
+ *   errors     count == 0 is a no-op; NULL buffers with count > 0, an unknown mode, hits / surfaces with RTGPU_TRACE_ANY or occluded with
+ *              RTGPU_TRACE_CLOSEST: RTGPU_ERR_INVALID_ARGUMENT; before rtgpu_upload_scene: RTGPU_ERR_NOT_READY.
+ * Queries have their own path-state arena (176 bytes per ray, grown on first use up to a chunk of 4 M rays; larger calls run chunk by chunk),
+ * queues and counters, and leave the render state alone.  A multi-device context (rtgpu_create_multi) answers on its first device.
+ * --------------------------------------------------------------------------------------------- */
+#define RTGPU_TRACE_CLOSEST 0u
+#define RTGPU_TRACE_ANY     1u
+
+/* 32 bytes (two 16-byte loads) */
+typedef struct RtQueryRay
+{
+    float origin[3];
+    float maxDistance;
+    float direction[3];
+    float _pad;
+} RtQueryRay;
+
+/* 32 bytes: rt::HitPoint (Core/Traversal/HitPoint.h) and three padding words (two 16-byte stores) */
+typedef struct RtQueryHit
+{
+    float    distance;
+    uint32_t objectId;
+    uint32_t subObjectId;
+    float    u, v;
+    uint32_t _pad[3];
+} RtQueryHit;
+
+/* 48 bytes: what Scene::EvaluateIntersection leaves in IntersectionData -- position = frame[3], normal = frame[2], tangent = frame[0]
+ * (world space), texCoord.xy and the material index */
+typedef struct RtQuerySurface
+{
+    float    position[3];
+    float    normal[3];
+    float    tangent[3];
+    float    texCoord[2];
+    uint32_t material;
+} RtQuerySurface;
+
+/* Host pointers; synchronous (flushes the queued passes first, as rtgpu_read_sum does). */
+int rtgpu_trace_rays(RtgpuContext* ctx, uint32_t mode, const RtQueryRay* rays, uint32_t count, RtQueryHit* hits, RtQuerySurface* surfaces,
+                     uint32_t* occluded, RtCounters* stats);
+/* Device pointers (rays, hits and surfaces 16-byte aligned, stats a device RtCounters) on `stream` (a hipStream_t; NULL: the context's own
+ * stream): ordered after the work already queued there, returns without synchronising. */
+int rtgpu_trace_rays_async(RtgpuContext* ctx, uint32_t mode, const RtQueryRay* rays, uint32_t count, RtQueryHit* hits, RtQuerySurface* surfaces,
+                           uint32_t* occluded, RtCounters* stats, void* stream);
+
 /* Known-answer-test hooks.  They evaluate the DEVICE implementation of one hot-path function (the code the traversal and shading
  * kernels call, rt_device_*.h) on caller-provided records, so that tests can hold the HIP functions directly against vectors produced
  * by the reference's own translation units (tests/golden/) without going through any CPU

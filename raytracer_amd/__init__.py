@@ -7,6 +7,7 @@ Python is plumbing only: ctypes bindings over
 
 There is NO CPU fallback: creating a renderer without the HIP library / a GPU raises.
 """
+import collections
 import ctypes as C
 import os
 
@@ -159,6 +160,26 @@ class RtCounters(C.Structure):
                                           "numPassedRayBoxTests", "numRayTriangleTests", "numPassedRayTriangleTests",
                                           "numMeshHits", "numAnalyticHits", "numShadowRayBoxTests",
                                           "numShadowRayTriangleTests", "numRetracedRays")] + [("_reserved", C.c_uint64 * 3)]
+
+
+class RtQueryRay(C.Structure):
+    _fields_ = [("origin", C.c_float * 3), ("maxDistance", C.c_float), ("direction", C.c_float * 3), ("_pad", C.c_float)]
+
+
+class RtQueryHit(C.Structure):
+    _fields_ = [("distance", C.c_float), ("objectId", C.c_uint32), ("subObjectId", C.c_uint32), ("u", C.c_float), ("v", C.c_float), ("_pad", C.c_uint32 * 3)]
+
+
+class RtQuerySurface(C.Structure):
+    _fields_ = [("position", C.c_float * 3), ("normal", C.c_float * 3), ("tangent", C.c_float * 3), ("texCoord", C.c_float * 2), ("material", C.c_uint32)]
+
+
+TRACE_CLOSEST, TRACE_ANY = 0, 1
+RT_INVALID_OBJECT, RT_LIGHT_OBJECT, RT_NO_MATERIAL = 0xFFFFFFFF, 0xFFFFFFFE, 0xFFFFFFFF
+
+# Viewport.trace_rays: Scene::Traverse (+ Scene::EvaluateIntersection with surfaces=True) per ray; the surface fields are None without surfaces
+RayHits = collections.namedtuple("RayHits", ["distance", "object_id", "sub_object_id", "uv", "position", "normal", "tangent", "tex_coord", "material"],
+                                 defaults=(None,) * 5)
 
 
 COUNTER_NAMES = ("numRays", "numShadowRays", "numShadowRaysHit", "numPrimaryRays", "numRayBoxTests", "numPassedRayBoxTests",
@@ -394,6 +415,12 @@ class Camera:
         self.settings.update(bokeh_shape=int(bokeh_shape), barrel_const=float(barrel_const), barrel_variable=float(barrel_variable))
 
 
+def _u32(torch, words):
+    """int32 tensor of uint32 words -> int64 tensor of their unsigned values"""
+    v = words.to(torch.int64)
+    return torch.where(v < 0, v + (1 << 32), v)
+
+
 class Viewport:
     """rt::Viewport driving the GPU "Path Tracer MIS" renderer (reference: Core/Rendering/Viewport.h)."""
 
@@ -540,6 +567,109 @@ class Viewport:
                 d["numRetracedRays"] = int(raw.numRetracedRays)
                 d["numUntrustedRays"], d["numStackOverflowRays"], d["diag2"] = int(raw._reserved[0]), int(raw._reserved[1]), int(raw._reserved[2])
         return d
+
+    # ---- batched ray queries (include/rtgpu.h: rtgpu_trace_rays / rtgpu_trace_rays_async) -----------------------------------------------
+    def trace_rays(self, origins, directions, max_distance=float("inf"), surfaces=False):
+        """Scene::Traverse of the renderer's scene for every ray (origin, direction): (N, 3) float32 NumPy arrays, or torch tensors on the
+        renderer's ROCm device (then the query runs on torch.cuda.current_stream() without a host copy and the results are tensors on that device).
+        max_distance: a scalar or N values (hitPoint.distance before the walk; +inf: unbounded).  Returns RayHits: distance (N,), object_id,
+        sub_object_id (N,) (RT_INVALID_OBJECT on a miss), uv (N, 2); with surfaces=True also Scene::EvaluateIntersection's position, normal, tangent
+        (N, 3), tex_coord (N, 2) and material (N,).  Ids are uint32 in NumPy and int64 in torch."""
+        q = self._query(TRACE_CLOSEST, origins, directions, max_distance, surfaces)
+        hits, surf, torch = q["hits"], q["surfaces"], q["torch"]
+        if torch is None:
+            f, u = hits.view(np.float32), hits
+            out = dict(distance=f[:, 0].copy(), object_id=u[:, 1].copy(), sub_object_id=u[:, 2].copy(), uv=f[:, 3:5].copy())
+            if surf is not None:
+                sf = surf.view(np.float32)
+                out.update(position=sf[:, 0:3].copy(), normal=sf[:, 3:6].copy(), tangent=sf[:, 6:9].copy(), tex_coord=sf[:, 9:11].copy(), material=surf[:, 11].copy())
+            return RayHits(**out)
+        f = hits.view(torch.float32)
+        out = dict(distance=f[:, 0], object_id=_u32(torch, hits[:, 1]), sub_object_id=_u32(torch, hits[:, 2]), uv=f[:, 3:5])
+        if surf is not None:
+            sf = surf.view(torch.float32)
+            out.update(position=sf[:, 0:3], normal=sf[:, 3:6], tangent=sf[:, 6:9], tex_coord=sf[:, 9:11], material=_u32(torch, surf[:, 11]))
+        return RayHits(**out)
+
+    def occluded(self, origins, directions, max_distance=float("inf")):
+        """Scene::Traverse_Shadow (no origin offset) for every ray: a bool array / tensor of N.  Inputs as trace_rays."""
+        q = self._query(TRACE_ANY, origins, directions, max_distance, False)
+        return q["occluded"] != 0
+
+    def _query(self, mode, origins, directions, max_distance, surfaces):
+        torch = None
+        if type(origins).__module__.split(".")[0] == "torch" or type(directions).__module__.split(".")[0] == "torch":
+            import torch
+        if torch is None:
+            for name, a in (("origins", origins), ("directions", directions)):
+                if not isinstance(a, np.ndarray) or a.dtype != np.float32 or a.ndim != 2 or a.shape[1] != 3:
+                    raise ValueError("%s must be an (N, 3) float32 NumPy array (or a torch tensor)" % name)
+        else:
+            for name, a in (("origins", origins), ("directions", directions)):
+                if not isinstance(a, torch.Tensor) or a.dtype != torch.float32 or a.dim() != 2 or a.shape[1] != 3:
+                    raise ValueError("%s must be an (N, 3) float32 tensor" % name)
+                if not a.is_cuda:
+                    raise ValueError("%s must live on the renderer's ROCm device" % name)
+                if not a.is_contiguous():
+                    raise ValueError("%s must be contiguous" % name)
+        if origins.shape != directions.shape:
+            raise ValueError("origins and directions must have the same shape")
+        n = int(origins.shape[0])
+        if torch is None:
+            md = np.asarray(max_distance, dtype=np.float32)
+            if md.ndim not in (0, 1) or (md.ndim == 1 and md.shape[0] != n):
+                raise ValueError("max_distance must be a scalar or N values")
+        elif isinstance(max_distance, torch.Tensor):
+            if max_distance.dtype != torch.float32 or max_distance.dim() != 1 or max_distance.shape[0] != n or max_distance.device != origins.device:
+                raise ValueError("max_distance must be a scalar or an (N,) float32 tensor on the rays' device")
+        if not self.has_renderer:
+            raise RuntimeError("trace_rays / occluded need a renderer: call set_renderer first")
+        ctx = self.device_context()
+        if not ctx.value or host_lib().rth_viewport_upload_scene(self._h) != 0:
+            raise RuntimeError("the viewport's renderer has no device context or its scene could not be uploaded: %s" % (rtgpu_lib().rtgpu_last_error() or b"").decode())
+        lib = rtgpu_lib()
+        if torch is None:
+            rays = np.zeros((n, 8), dtype=np.float32)
+            rays[:, 0:3], rays[:, 3], rays[:, 4:7] = origins, md, directions
+            hits = np.zeros((n, 8), dtype=np.uint32) if mode == TRACE_CLOSEST else None
+            surf = np.zeros((n, 12), dtype=np.uint32) if surfaces else None
+            occ = np.zeros(n, dtype=np.uint32) if mode == TRACE_ANY else None
+            ptr = lambda a: a.ctypes.data_as(C.c_void_p) if a is not None else None   # noqa: E731
+            r = lib.rtgpu_trace_rays(ctx, C.c_uint32(mode), ptr(rays), C.c_uint32(n), ptr(hits), ptr(surf), ptr(occ), None)
+        else:
+            device = origins.device
+            if directions.device != device:
+                raise ValueError("origins and directions must live on the same device")
+            if (device.index if device.index is not None else torch.cuda.current_device()) != multi_info(ctx)["devices"][0]:
+                raise ValueError("the rays must live on the renderer's device (cuda:%d)" % multi_info(ctx)["devices"][0])
+            rays = torch.empty((n, 8), dtype=torch.float32, device=device)
+            rays[:, 0:3] = origins
+            rays[:, 3] = max_distance
+            rays[:, 4:7] = directions
+            rays[:, 7] = 0.0
+            hits = torch.empty((n, 8), dtype=torch.int32, device=device) if mode == TRACE_CLOSEST else None
+            surf = torch.empty((n, 12), dtype=torch.int32, device=device) if surfaces else None
+            occ = torch.empty(n, dtype=torch.int32, device=device) if mode == TRACE_ANY else None
+            ptr = lambda t: C.c_void_p(t.data_ptr()) if t is not None else None   # noqa: E731
+            current = torch.cuda.current_stream(device)
+            if current.cuda_stream != 0:
+                r = lib.rtgpu_trace_rays_async(ctx, C.c_uint32(mode), ptr(rays), C.c_uint32(n), ptr(hits), ptr(surf), ptr(occ), None, C.c_void_p(current.cuda_stream))
+            else:
+                # torch's default stream is the null stream, and a NULL stream means the context's own to rtgpu_trace_rays_async: the query runs on a
+                # side stream ordered after the current stream's work, and the current stream waits for it
+                if getattr(self, "_query_stream", None) is None or self._query_stream.device != device:
+                    self._query_stream = torch.cuda.Stream(device)
+                side = self._query_stream
+                side.wait_stream(current)
+                r = lib.rtgpu_trace_rays_async(ctx, C.c_uint32(mode), ptr(rays), C.c_uint32(n), ptr(hits), ptr(surf), ptr(occ), None, C.c_void_p(side.cuda_stream))
+                current.wait_stream(side)
+                for t in (rays, hits, surf, occ):
+                    if t is not None:
+                        t.record_stream(side)
+        if r != 0:
+            err = (lib.rtgpu_last_error() or b"").decode()
+            raise (ValueError if r == -1 else RuntimeError)("ray query failed (%d): %s" % (r, err))
+        return dict(hits=hits, surfaces=surf, occluded=occ, torch=torch)
 
     @property
     def passes_finished(self):

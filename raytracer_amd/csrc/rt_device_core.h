@@ -676,8 +676,14 @@ RT_DEV void composeShadingFrame(const M4& transform, V4 worldPosition, V4 localS
 // textures (Cornell box: analytic shapes, area light, all BSDFs).
 #define RT_LEAN(k) ((k) == 1 || (k) == 2 || (k) == 4)
 #define RT_TEXTURED(k) ((k) == 0 || (k) == 2 || (k) == 4)
-template <int kLean>
-__device__ __forceinline__ static void sceneEvaluateIntersection(const RtSceneDesc& d, const Ray& ray, const Hit& hit, Intersection& out, Counters& cnt)
+// CountersT: Counters, or DiscardCounters where the caller tallies the hits itself (k_query_evaluate)
+struct DiscardCounters
+{
+    struct Tally { __device__ __forceinline__ void operator++(int) const {} };
+    struct Array { __device__ __forceinline__ Tally operator[](int) const { return Tally(); } } c;
+};
+template <int kLean, typename CountersT = Counters>
+__device__ __forceinline__ static void sceneEvaluateIntersection(const RtSceneDesc& d, const Ray& ray, const Hit& hit, Intersection& out, CountersT& cnt)
 {
     const RtObject& obj = d.objects[hit.objectId];
     const M4 transform = loadM4(obj.transform);

@@ -250,6 +250,18 @@ struct RtgpuContext
         std::vector<Pending> pending;
     } vcm;
 
+    // batched ray queries (rtgpu_trace_rays): a path-state arena, queues, work counts and counters of their own -- never a lane's, never c->counters
+    struct Query
+    {
+        Paths paths = { nullptr, 0, 0 };          // maxLights = 1; capacity = the rays of one chunk
+        uint32_t* queue = nullptr;                // closest-hit rays or any-hit requests of the chunk
+        uint32_t* exactQueue = nullptr; uint32_t* exactShadowQueue = nullptr;   // what the 4-wide walks hand to the re-trace launch
+        uint32_t* counts = nullptr;               // QC_WORDS work counts (QC_*)
+        unsigned long long* counters = nullptr;   // 16 x u64, the layout of RtCounters
+        float4* stagedRays = nullptr; float4* stagedHits = nullptr; float4* stagedSurfaces = nullptr; uint32_t* stagedOccluded = nullptr;   // rtgpu_trace_rays' device copies
+        hipEvent_t done = nullptr;                // recorded behind every query: the next one (whatever its stream), a new arena and a new scene wait for it
+    } query;
+
     // timing
     bool timing = false;
     struct Timed { int kc; hipEvent_t a, b; };
@@ -336,6 +348,28 @@ struct LaunchTimer
 
 static int flushPending(RtgpuContext* c);
 static void freeVcm(RtgpuContext* c);
+
+static void waitQueries(RtgpuContext* c) { if (c->query.done) (void)hipEventSynchronize(c->query.done); }
+static void freeQueryArena(RtgpuContext* c)
+{
+    RtgpuContext::Query& q = c->query;
+    waitQueries(c);
+    for (void* p : { (void*)q.paths.base, (void*)q.queue, (void*)q.exactQueue, (void*)q.exactShadowQueue, (void*)q.stagedRays, (void*)q.stagedHits,
+                     (void*)q.stagedSurfaces, (void*)q.stagedOccluded })
+        if (p) (void)hipFree(p);
+    q.paths.base = nullptr; q.paths.capacity = 0; q.paths.maxLights = 0;
+    q.queue = q.exactQueue = q.exactShadowQueue = nullptr;
+    q.stagedRays = q.stagedHits = q.stagedSurfaces = nullptr; q.stagedOccluded = nullptr;
+}
+static void freeQuery(RtgpuContext* c)
+{
+    RtgpuContext::Query& q = c->query;
+    freeQueryArena(c);
+    if (q.counts) (void)hipFree(q.counts);
+    if (q.counters) (void)hipFree(q.counters);
+    if (q.done) (void)hipEventDestroy(q.done);
+    q.counts = nullptr; q.counters = nullptr; q.done = nullptr;
+}
 
 template <typename T>
 static int uploadArray(RtgpuContext* c, const T* host, size_t count, const T** outDev)
@@ -573,6 +607,7 @@ RTGPU_API void rtgpu_destroy(RtgpuContext* c)
     (void)hipSetDevice(c->device);
     (void)syncLanes(c);
     if (c->gatherStage) (void)hipFree(c->gatherStage);
+    freeQuery(c);
     freeScene(c); freeFilm(c);
     for (uint32_t i = 0; i < RT_MAX_LANES; ++i)
     {
@@ -603,6 +638,7 @@ RTGPU_API int rtgpu_upload_scene(RtgpuContext* c, const RtSceneDesc* s)
     HIP_TRY(hipSetDevice(c->device));
     { int fr = flushPending(c); if (fr) return fr; }
     HIP_TRY(syncLanes(c));
+    waitQueries(c);   // an asynchronous ray query may still walk the old scene
 
     // validation: indices in range, stacks deep enough
     if (s->numObjects > 1 && s->numTopNodes == 0) return fail(RTGPU_ERR_INVALID_ARGUMENT, "scene with more than one object needs a top-level BVH");
@@ -1074,7 +1110,7 @@ static int ensurePaths(RtgpuContext* c, BatchLane& l, uint32_t maxLights, uint32
 // ray that would need more goes to the binary-tree kernel.
 static bool useWide(const RtgpuContext* c) { return (c->wide.nodes != nullptr || (c->wide2.nodes != nullptr && c->wide2Allowed)) && c->wideAllowed && !c->countIntersections; }
 
-static void launchTraceWide(RtgpuContext* c, hipStream_t stream, const Paths& paths, const uint32_t* tq, const uint32_t* tqc, const uint32_t* tsq, const uint32_t* tsc,
+static void launchTraceWide(RtgpuContext* c, hipStream_t stream, unsigned long long* counters, const Paths& paths, const uint32_t* tq, const uint32_t* tqc, const uint32_t* tsq, const uint32_t* tsc,
                             uint32_t* cursor, uint32_t* exactQueue, uint32_t* exactCount, uint32_t* exactShadowQueue, uint32_t* exactShadowCount, float shadowOffset,
                             const uint32_t* denseCounts, uint32_t denseShardCapacity, bool mayTraceUndecidedRaysItself = true, uint32_t bounce = 0u)
 {
@@ -1115,7 +1151,7 @@ static void launchTraceWide(RtgpuContext* c, hipStream_t stream, const Paths& pa
         // a two-level scene (rt_trace_wide2.inl): held to five waves per SIMD (110 -> 96 VGPRs, 8 bytes of scratch: Cornell box trace -7 %, +2 % end to
         // end), 30 KB of LDS per block
         const dim3 grid2(c->numCUs * (c->travBlocksPerCU ? c->travBlocksPerCU : 5u));
-        hipLaunchKernelGGL((k_trace_wide2<24>), grid2, block, 0, stream, c->sceneDev, c->wide2, paths, tq, tqc, tsq, tsc, cursor, c->counters, tune);
+        hipLaunchKernelGGL((k_trace_wide2<24>), grid2, block, 0, stream, c->sceneDev, c->wide2, paths, tq, tqc, tsq, tsc, cursor, counters, tune);
         return;
     }
     static const bool diag = getenv("RTGPU_WIDE_DIAG") != nullptr;       // walk statistics in the spare counters (tools/wide_diag.py)
@@ -1125,13 +1161,13 @@ static void launchTraceWide(RtgpuContext* c, hipStream_t stream, const Paths& pa
     if (packets && !diag && bounce == 0u && denseCounts != nullptr && tsq == nullptr && tq == nullptr)
     {
         static const uint32_t packetBlocksPerCU = getenv("RTGPU_PACKET_BLOCKS") ? (uint32_t)atoi(getenv("RTGPU_PACKET_BLOCKS")) : 8u;
-        hipLaunchKernelGGL(k_trace_packet, dim3(c->numCUs * packetBlocksPerCU), block, 0, stream, c->sceneDev, c->wide, paths, cursor, c->counters, tune);
+        hipLaunchKernelGGL(k_trace_packet, dim3(c->numCUs * packetBlocksPerCU), block, 0, stream, c->sceneDev, c->wide, paths, cursor, counters, tune);
         return;
     }
     if (diag) tune.localExact = (uint32_t)atoi(getenv("RTGPU_WIDE_DIAG"));   // 2: stack-depth histogram instead of the visit counts (tools/wide_diag.py)
-    if (diag) hipLaunchKernelGGL((k_trace_wide<24, true, false>), grid, block, 0, stream, c->sceneDev, c->wide, paths, tq, tqc, tsq, tsc, cursor, c->counters, tune);
-    else if (localExact) hipLaunchKernelGGL((k_trace_wide<24, false, true>), grid, block, 0, stream, c->sceneDev, c->wide, paths, tq, tqc, tsq, tsc, cursor, c->counters, tune);
-    else hipLaunchKernelGGL((k_trace_wide<24, false, false>), grid, block, 0, stream, c->sceneDev, c->wide, paths, tq, tqc, tsq, tsc, cursor, c->counters, tune);
+    if (diag) hipLaunchKernelGGL((k_trace_wide<24, true, false>), grid, block, 0, stream, c->sceneDev, c->wide, paths, tq, tqc, tsq, tsc, cursor, counters, tune);
+    else if (localExact) hipLaunchKernelGGL((k_trace_wide<24, false, true>), grid, block, 0, stream, c->sceneDev, c->wide, paths, tq, tqc, tsq, tsc, cursor, counters, tune);
+    else hipLaunchKernelGGL((k_trace_wide<24, false, false>), grid, block, 0, stream, c->sceneDev, c->wide, paths, tq, tqc, tsq, tsc, cursor, counters, tune);
 }
 
 // The re-trace launch behind a 4-wide walk: the reference's own walk (k_trace) over the rays the walk handed over (0.1 % of a launch), and -- single-mesh
@@ -1139,12 +1175,12 @@ static void launchTraceWide(RtgpuContext* c, hipStream_t stream, const Paths& pa
 // two of three slab tests into inf - inf and the ray walks most of the tree, alone in its wave (1.0-1.6 ms launches at bounce 1 where an ordinary one
 // takes 0.1-0.2 ms, profiles/r04_timeline_serial.txt); a whole block finds the same hit cooperatively.  `overflowQueue`: a queue of the lane nobody
 // uses during this bounce's trace (dense path state: none of the slot queues is in use; slot-per-pixel: the one the next shade will fill).
-static void launchRetrace(RtgpuContext* c, BatchLane& l, hipStream_t stream, const Paths& paths, uint32_t depth, uint32_t stackClass, uint32_t* overflowQueue)
+// `exactQueue` / `exactCount`, `exactShadowQueue` / `exactShadowCount`: what the 4-wide walk handed over; `exactCursor`: the launch's work cursor;
+// `overflowCount`: the count of `overflowQueue`.
+static void launchRetrace(RtgpuContext* c, hipStream_t stream, unsigned long long* counters, const Paths& paths, const uint32_t* exactQueue, const uint32_t* exactCount,
+                          const uint32_t* exactShadowQueue, const uint32_t* exactShadowCount, uint32_t* exactCursor, uint32_t stackClass, uint32_t* overflowQueue,
+                          uint32_t* overflowCount)
 {
-    uint32_t* exactCounts = l.queueCounts + 4 * l.queueCountCapacity;
-    uint32_t* exactShadowCounts = l.queueCounts + 5 * l.queueCountCapacity;
-    uint32_t* exactCursors = l.queueCounts + 6 * l.queueCountCapacity;
-    uint32_t* overflowCounts = l.queueCounts + 7 * l.queueCountCapacity;
     const char* const abortText = getenv("RTGPU_ABORT_RETRACE_AFTER");   // test hook, read per launch (0: every closest-hit ray in flight when its wave's queue runs dry goes to k_trace_monster)
     const int abortEnv = abortText ? atoi(abortText) : -1;
     // OFF by default since the axis-parallel prune (boxNearDegenerateAxes) made the rays it was built for short: on the benchmark frame no ray is handed over any more,
@@ -1153,9 +1189,9 @@ static void launchRetrace(RtgpuContext* c, BatchLane& l, hipStream_t stream, con
     // (profiles/r05_monsters_under_concurrency_ab.txt).  RTGPU_RETRACE_MONSTERS=1 (or the test hook RTGPU_ABORT_RETRACE_AFTER) switches the hand-over on; read per launch.
     const char* const monstersText = getenv("RTGPU_RETRACE_MONSTERS");
     const bool monstersWanted = monstersText ? atoi(monstersText) != 0 : abortText != nullptr;
-    const bool monsters = monstersWanted && overflowQueue != nullptr && c->wide.nodes != nullptr && c->sceneDev.numObjects == 1u && !c->countIntersections;
+    const bool monsters = monstersWanted && overflowQueue != nullptr && overflowCount != nullptr && c->wide.nodes != nullptr && c->sceneDev.numObjects == 1u && !c->countIntersections;
     TravTuning exactTune = c->tune;
-    exactTune.overflowQueue = monsters ? overflowQueue : nullptr; exactTune.overflowCount = monsters ? overflowCounts + depth : nullptr;
+    exactTune.overflowQueue = monsters ? overflowQueue : nullptr; exactTune.overflowCount = monsters ? overflowCount : nullptr;
     exactTune.abortClosestAfter = abortEnv >= 0 ? (uint32_t)abortEnv : RT_ABORT_RETRACE_AFTER;
     exactTune.denseCounts = nullptr; exactTune.denseShardCapacity = 0u;
     // a re-trace launch's queue is dry after the first claim and its duration is its longest ray: an any-hit ray that slides along a wall it started on (a sun in a
@@ -1173,10 +1209,10 @@ static void launchRetrace(RtgpuContext* c, BatchLane& l, hipStream_t stream, con
     const uint32_t fullBlocks = c->numCUs * (c->travBlocksPerCU ? c->travBlocksPerCU : (stackClass == 24u ? 5u : (stackClass == 32u ? 4u : 2u)));
     exactTune.baseBlocks = adaptiveGrid ? c->numCUs : 0u; exactTune.fullGridAbove = c->numCUs * 256u * 4u;
     const dim3 retraceGrid(adaptiveGrid ? fullBlocks : c->numCUs), block(RT_BLOCK);
-#define RT_LAUNCH_RETRACE(S) hipLaunchKernelGGL((k_trace<S, false>), retraceGrid, block, 0, stream, c->sceneDev, paths, l.exactQueue, exactCounts + depth, l.exactShadowQueue, exactShadowCounts + depth, exactCursors + depth, c->counters, exactTune)
+#define RT_LAUNCH_RETRACE(S) hipLaunchKernelGGL((k_trace<S, false>), retraceGrid, block, 0, stream, c->sceneDev, paths, exactQueue, exactCount, exactShadowQueue, exactShadowCount, exactCursor, counters, exactTune)
     if (stackClass == 24u) RT_LAUNCH_RETRACE(24); else if (stackClass == 32u) RT_LAUNCH_RETRACE(32); else RT_LAUNCH_RETRACE(64);
 #undef RT_LAUNCH_RETRACE
-    if (monsters) hipLaunchKernelGGL(k_trace_monster, dim3(64), dim3(RT_MONSTER_BLOCK), 0, stream, c->sceneDev, paths, overflowQueue, overflowCounts + depth);
+    if (monsters) hipLaunchKernelGGL(k_trace_monster, dim3(64), dim3(RT_MONSTER_BLOCK), 0, stream, c->sceneDev, paths, overflowQueue, overflowCount);
 }
 
 // The bounce at which a dense batch hands its remaining paths to k_tail (0: never).  RTGPU_TAIL_DEPTH=n forces bounce n (0: off).
@@ -1316,9 +1352,11 @@ static int flushBatch(RtgpuContext* c, uint32_t maxPasses)
                     uint32_t* exactCounts = l.queueCounts + 4 * l.queueCountCapacity;
                     uint32_t* exactShadowCounts = l.queueCounts + 5 * l.queueCountCapacity;
                     uint32_t* exactCursors = l.queueCounts + 6 * l.queueCountCapacity;
-                    launchTraceWide(c, l.stream, in, nullptr, nullptr, tsq, tsc, cursors + depth, l.exactQueue, exactCounts + depth, l.exactShadowQueue, exactShadowCounts + depth, 0.0001f,
+                    uint32_t* overflowCounts = l.queueCounts + 7 * l.queueCountCapacity;
+                    launchTraceWide(c, l.stream, c->counters, in, nullptr, nullptr, tsq, tsc, cursors + depth, l.exactQueue, exactCounts + depth, l.exactShadowQueue, exactShadowCounts + depth, 0.0001f,
                                     tune.denseCounts, shardCapacity, true, depth);
-                    launchRetrace(c, l, l.stream, in, depth, stackClass, l.queues[0]);
+                    launchRetrace(c, l.stream, c->counters, in, l.exactQueue, exactCounts + depth, l.exactShadowQueue, exactShadowCounts + depth, exactCursors + depth, stackClass,
+                                  l.queues[0], overflowCounts + depth);
                 }
                 else
                 {
@@ -1374,8 +1412,10 @@ static int flushBatch(RtgpuContext* c, uint32_t maxPasses)
                 uint32_t* exactCounts = l.queueCounts + 4 * l.queueCountCapacity;
                 uint32_t* exactShadowCounts = l.queueCounts + 5 * l.queueCountCapacity;
                 uint32_t* exactCursors = l.queueCounts + 6 * l.queueCountCapacity;
-                launchTraceWide(c, l.stream, l.paths, tq, tqc, tsq, tsc, cursors + launchIndex, l.exactQueue, exactCounts + launchIndex, l.exactShadowQueue, exactShadowCounts + launchIndex, 0.0001f, nullptr, 0u);
-                launchRetrace(c, l, l.stream, l.paths, launchIndex, stackClass, l.queues[(depth + 1u) & 1u]);
+                uint32_t* overflowCounts = l.queueCounts + 7 * l.queueCountCapacity;
+                launchTraceWide(c, l.stream, c->counters, l.paths, tq, tqc, tsq, tsc, cursors + launchIndex, l.exactQueue, exactCounts + launchIndex, l.exactShadowQueue, exactShadowCounts + launchIndex, 0.0001f, nullptr, 0u);
+                launchRetrace(c, l.stream, c->counters, l.paths, l.exactQueue, exactCounts + launchIndex, l.exactShadowQueue, exactShadowCounts + launchIndex, exactCursors + launchIndex,
+                              stackClass, l.queues[(depth + 1u) & 1u], overflowCounts + launchIndex);
             }
             else
             {
@@ -1876,6 +1916,160 @@ RTGPU_API int rtgpu_kat_mesh(RtgpuContext* c, const float* rays, uint32_t n, uin
     return katRoundTrip(c, rays, (size_t)n * 7 * 4, out, (size_t)n * 19 * 4, [&](void* dIn, void* dOut, hipStream_t st) {
         hipLaunchKernelGGL(k_kat_mesh, dim3((n + 63u) / 64u), dim3(64), 0, st, c->sceneDev, (const float*)dIn, n, (uint32_t*)dOut);
     });
+}
+
+// ---- batched ray queries (include/rtgpu.h, rtgpu_trace_rays; kernels: rt_query.inl) ----------------------------------------------------------
+// A chunk of rays goes through k_query_load -> the walk the context renders with -> k_query_store (-> k_query_evaluate), on the query's own arena.
+#define RT_QUERY_CHUNK (1u << 22)   // rays per chunk: 4 M x 176 bytes of path records
+enum { QC_QUEUE = 0, QC_CURSOR, QC_EXACT, QC_EXACT_SHADOW, QC_EXACT_CURSOR, QC_WORDS = 8 };
+
+static int ensureQueryArena(RtgpuContext* c, uint32_t rays)
+{
+    RtgpuContext::Query& q = c->query;
+    if (!q.done) HIP_TRY(hipEventCreateWithFlags(&q.done, hipEventDisableTiming));
+    if (!q.counts) HIP_TRY(hipMalloc((void**)&q.counts, QC_WORDS * sizeof(uint32_t)));
+    if (!q.counters) HIP_TRY(hipMalloc((void**)&q.counters, 16 * sizeof(unsigned long long)));
+    const uint32_t want = rays < RT_QUERY_CHUNK ? rays : RT_QUERY_CHUNK;
+    if (q.paths.base && q.paths.capacity >= want) return RTGPU_OK;
+    // grown in powers of two from 64 K rays up to the chunk: a caller whose batches grow slowly does not reallocate with every call
+    uint32_t cap = 65536u;
+    while (cap < want) cap <<= 1;
+    freeQueryArena(c);   // (waits for the queries still using it)
+    HIP_TRY(hipMalloc((void**)&q.paths.base, ((size_t)R_NUM_BASE + RT_SHADOW_RECORDS) * cap * sizeof(float4)));
+    HIP_TRY(hipMalloc((void**)&q.queue, (size_t)cap * sizeof(uint32_t)));
+    HIP_TRY(hipMalloc((void**)&q.exactQueue, (size_t)cap * sizeof(uint32_t)));
+    HIP_TRY(hipMalloc((void**)&q.exactShadowQueue, (size_t)cap * sizeof(uint32_t)));
+    HIP_TRY(hipMalloc((void**)&q.stagedRays, (size_t)cap * sizeof(RtQueryRay)));
+    HIP_TRY(hipMalloc((void**)&q.stagedHits, (size_t)cap * sizeof(RtQueryHit)));
+    HIP_TRY(hipMalloc((void**)&q.stagedSurfaces, (size_t)cap * sizeof(RtQuerySurface)));
+    HIP_TRY(hipMalloc((void**)&q.stagedOccluded, (size_t)cap * sizeof(uint32_t)));
+    q.paths.capacity = cap; q.paths.maxLights = 1;
+    return RTGPU_OK;
+}
+
+// the launches of one chunk (n <= the arena's capacity), device pointers, on `stream`
+static int launchQueryChunk(RtgpuContext* c, hipStream_t stream, uint32_t mode, const float4* rays, uint32_t n, float4* hits, float4* surfaces, uint32_t* occluded)
+{
+    RtgpuContext::Query& q = c->query;
+    const bool closest = mode == RTGPU_TRACE_CLOSEST;
+    const dim3 block(RT_BLOCK), grid((n + RT_BLOCK - 1u) / RT_BLOCK);
+    HIP_TRY(hipMemsetAsync(q.counts, 0, QC_WORDS * sizeof(uint32_t), stream));
+    hipLaunchKernelGGL(k_query_load, grid, block, 0, stream, rays, n, mode, q.paths, q.queue, q.counts + QC_QUEUE, q.counters);
+    const uint32_t* tq = closest ? q.queue : nullptr; const uint32_t* tqc = closest ? q.counts + QC_QUEUE : nullptr;
+    const uint32_t* tsq = closest ? nullptr : q.queue; const uint32_t* tsc = closest ? nullptr : q.counts + QC_QUEUE;
+    const uint32_t stackClass = c->traversalStackNeed <= 24 ? 24u : (c->traversalStackNeed <= 32 ? 32u : 64u);
+    // Any-hit requests walk the reference's binary tree (k_trace) whatever the setting: the 4-wide walks' any-hit decision is exact for the rays the
+    // integrators ask about (tmax = 0.999 x the light's distance: no triangle within an ulp of it), but a query's maxDistance may sit an ulp below a
+    // hit, and there the conservative leaf gate of the 4-wide walks let 6 % of such rays report an occluder the reference's box test culls (DESIGN.md,
+    // "Ray queries").
+    if (useWide(c) && closest)
+    {
+        // the render path's pair: the 4-wide walk hands the rays it does not decide to the re-trace launch (which alone gives them a result).  No
+        // block-local second walk and no k_trace_monster hand-over: neither changes a result.
+        launchTraceWide(c, stream, q.counters, q.paths, tq, tqc, tsq, tsc, q.counts + QC_CURSOR, q.exactQueue, q.counts + QC_EXACT, q.exactShadowQueue,
+                        q.counts + QC_EXACT_SHADOW, 0.0f, nullptr, 0u, false);
+        launchRetrace(c, stream, q.counters, q.paths, q.exactQueue, q.counts + QC_EXACT, q.exactShadowQueue, q.counts + QC_EXACT_SHADOW, q.counts + QC_EXACT_CURSOR,
+                      stackClass, nullptr, nullptr);
+    }
+    else
+    {
+        TravTuning tune = c->tune;
+        tune.shadowOffset = 0.0f; tune.overflowQueue = nullptr; tune.overflowCount = nullptr; tune.denseCounts = nullptr; tune.denseShardCapacity = 0u;
+        const dim3 travGrid(c->numCUs * (c->travBlocksPerCU ? c->travBlocksPerCU : (stackClass == 24u ? 5u : (stackClass == 32u ? 4u : 2u))));
+#define RT_LAUNCH_QUERY_TRACE(S, C) hipLaunchKernelGGL((k_trace<S, C>), travGrid, block, 0, stream, c->sceneDev, q.paths, tq, tqc, tsq, tsc, q.counts + QC_CURSOR, q.counters, tune)
+        if (stackClass == 24u) { if (c->countIntersections) RT_LAUNCH_QUERY_TRACE(24, true); else RT_LAUNCH_QUERY_TRACE(24, false); }
+        else if (stackClass == 32u) { if (c->countIntersections) RT_LAUNCH_QUERY_TRACE(32, true); else RT_LAUNCH_QUERY_TRACE(32, false); }
+        else { if (c->countIntersections) RT_LAUNCH_QUERY_TRACE(64, true); else RT_LAUNCH_QUERY_TRACE(64, false); }
+#undef RT_LAUNCH_QUERY_TRACE
+    }
+    hipLaunchKernelGGL(k_query_store, grid, block, 0, stream, c->sceneDev, rays, n, mode, q.paths, hits, occluded);
+    if (surfaces) hipLaunchKernelGGL(k_query_evaluate, grid, block, 0, stream, c->sceneDev, rays, n, (const float4*)hits, surfaces, q.counters);
+    HIP_TRY(hipGetLastError());
+    return RTGPU_OK;
+}
+
+// argument rules shared by both entry points (count == 0 passes: the callers return at once)
+static int checkQuery(RtgpuContext* c, uint32_t mode, const void* rays, uint32_t count, const void* hits, const void* surfaces, const void* occluded)
+{
+    if (!c) return fail(RTGPU_ERR_INVALID_ARGUMENT, "NULL context");
+    if (mode != RTGPU_TRACE_CLOSEST && mode != RTGPU_TRACE_ANY) return fail(RTGPU_ERR_INVALID_ARGUMENT, "unknown ray query mode");
+    if (mode == RTGPU_TRACE_ANY && (hits || surfaces)) return fail(RTGPU_ERR_INVALID_ARGUMENT, "RTGPU_TRACE_ANY answers in `occluded` only: hits and surfaces must be NULL");
+    if (mode == RTGPU_TRACE_CLOSEST && occluded) return fail(RTGPU_ERR_INVALID_ARGUMENT, "RTGPU_TRACE_CLOSEST answers in `hits` (and `surfaces`): occluded must be NULL");
+    if (count == 0) return RTGPU_OK;
+    if (!rays || (mode == RTGPU_TRACE_CLOSEST ? !hits : !occluded)) return fail(RTGPU_ERR_INVALID_ARGUMENT, "NULL ray or result buffer");
+    if (!c->sceneReady) return fail(RTGPU_ERR_NOT_READY, "rtgpu_upload_scene has not been called");
+    return RTGPU_OK;
+}
+
+// timing (rtgpu_enable_timing) measures the render passes: the query's launches stay out of the kernel classes
+struct QueryUntimed
+{
+    RtgpuContext* c; bool was;
+    explicit QueryUntimed(RtgpuContext* ctx) : c(ctx), was(ctx->timing) { c->timing = false; }
+    ~QueryUntimed() { c->timing = was; }
+};
+
+RTGPU_API int rtgpu_trace_rays(RtgpuContext* c, uint32_t mode, const RtQueryRay* rays, uint32_t count, RtQueryHit* hits, RtQuerySurface* surfaces,
+                               uint32_t* occluded, RtCounters* stats)
+{
+    int r = checkQuery(c, mode, rays, count, hits, surfaces, occluded); if (r) return r;
+    if (count == 0) return RTGPU_OK;
+    for (uint32_t i = 0; i < count; ++i)
+    {
+        const RtQueryRay& ray = rays[i];
+        if (queryRayIsDegenerate(ray.origin[0], ray.origin[1], ray.origin[2], ray.maxDistance, ray.direction[0], ray.direction[1], ray.direction[2]))
+            return fail(RTGPU_ERR_INVALID_ARGUMENT, "ray " + std::to_string(i) + " is degenerate (non-finite origin, zero or non-finite direction, or maxDistance not > 0)");
+    }
+    HIP_TRY(hipSetDevice(c->device));
+    { int fr = vcmFlush(c); if (fr) return fr; }
+    { int fr = flushPending(c); if (fr) return fr; }
+    r = ensureQueryArena(c, count); if (r) return r;
+    RtgpuContext::Query& q = c->query;
+    const QueryUntimed untimed(c);
+    hipStream_t stream = c->lanes[0].stream;
+    HIP_TRY(hipStreamWaitEvent(stream, q.done, 0));
+    HIP_TRY(hipMemsetAsync(q.counters, 0, 16 * sizeof(unsigned long long), stream));
+    const bool closest = mode == RTGPU_TRACE_CLOSEST;
+    for (uint32_t first = 0; first < count; first += q.paths.capacity)
+    {
+        const uint32_t n = count - first < q.paths.capacity ? count - first : q.paths.capacity;
+        HIP_TRY(rtMemcpy(q.stagedRays, rays + first, (size_t)n * sizeof(RtQueryRay), hipMemcpyHostToDevice));
+        r = launchQueryChunk(c, stream, mode, q.stagedRays, n, closest ? q.stagedHits : nullptr, surfaces ? q.stagedSurfaces : nullptr, closest ? nullptr : q.stagedOccluded);
+        if (r) return r;
+        HIP_TRY(hipStreamSynchronize(stream));
+        if (closest) HIP_TRY(rtMemcpy(hits + first, q.stagedHits, (size_t)n * sizeof(RtQueryHit), hipMemcpyDeviceToHost));
+        if (surfaces) HIP_TRY(rtMemcpy(surfaces + first, q.stagedSurfaces, (size_t)n * sizeof(RtQuerySurface), hipMemcpyDeviceToHost));
+        if (!closest) HIP_TRY(rtMemcpy(occluded + first, q.stagedOccluded, (size_t)n * sizeof(uint32_t), hipMemcpyDeviceToHost));
+    }
+    HIP_TRY(hipEventRecord(q.done, stream));
+    if (stats) HIP_TRY(rtMemcpy(stats, q.counters, sizeof(RtCounters), hipMemcpyDeviceToHost));
+    return RTGPU_OK;
+}
+
+RTGPU_API int rtgpu_trace_rays_async(RtgpuContext* c, uint32_t mode, const RtQueryRay* rays, uint32_t count, RtQueryHit* hits, RtQuerySurface* surfaces,
+                                     uint32_t* occluded, RtCounters* stats, void* streamHandle)
+{
+    int r = checkQuery(c, mode, rays, count, hits, surfaces, occluded); if (r) return r;
+    if (count == 0) return RTGPU_OK;
+    if ((((uintptr_t)rays) | ((uintptr_t)hits) | ((uintptr_t)surfaces)) & 15u || ((uintptr_t)occluded & 3u) || ((uintptr_t)stats & 7u))
+        return fail(RTGPU_ERR_INVALID_ARGUMENT, "rays, hits and surfaces must be 16-byte aligned device buffers (occluded 4, stats 8)");
+    HIP_TRY(hipSetDevice(c->device));
+    r = ensureQueryArena(c, count); if (r) return r;
+    RtgpuContext::Query& q = c->query;
+    const QueryUntimed untimed(c);
+    hipStream_t stream = streamHandle ? (hipStream_t)streamHandle : c->lanes[0].stream;
+    HIP_TRY(hipStreamWaitEvent(stream, q.done, 0));   // the arena is shared with the previous query, whatever its stream
+    HIP_TRY(hipMemsetAsync(q.counters, 0, 16 * sizeof(unsigned long long), stream));
+    for (uint32_t first = 0; first < count; first += q.paths.capacity)
+    {
+        const uint32_t n = count - first < q.paths.capacity ? count - first : q.paths.capacity;
+        r = launchQueryChunk(c, stream, mode, (const float4*)(rays + first), n, hits ? (float4*)(hits + first) : nullptr, surfaces ? (float4*)(surfaces + first) : nullptr,
+                             occluded ? occluded + first : nullptr);
+        if (r) return r;
+    }
+    if (stats) HIP_TRY(hipMemcpyAsync(stats, q.counters, sizeof(RtCounters), hipMemcpyDeviceToDevice, stream));
+    HIP_TRY(hipEventRecord(q.done, stream));
+    return RTGPU_OK;
 }
 
 RTGPU_API int rtgpu_set_concurrency(RtgpuContext* c, uint32_t lanes)

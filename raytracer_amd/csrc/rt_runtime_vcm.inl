@@ -91,7 +91,7 @@ static void launchTrace(RtgpuContext* c, hipStream_t stream, const Paths& paths,
         // k_trace_monster
         const uint32_t k = v.traceSerial++;
         uint32_t* exactCount = v.counts + 10u * RT_VCM_COUNT_PLANE + k; uint32_t* exactShadowCount = v.counts + 12u * RT_VCM_COUNT_PLANE + k;
-        launchTraceWide(c, stream, paths, tq, tqc, tsq, tsc, cursor, v.exactQueue, exactCount, v.exactShadowQueue, exactShadowCount, shadowOffset, nullptr, 0u, false);
+        launchTraceWide(c, stream, c->counters, paths, tq, tqc, tsq, tsc, cursor, v.exactQueue, exactCount, v.exactShadowQueue, exactShadowCount, shadowOffset, nullptr, 0u, false);
         tq = v.exactQueue; tqc = exactCount; tsq = v.exactShadowQueue; tsc = exactShadowCount; cursor = v.counts + 14u * RT_VCM_COUNT_PLANE + k;
         travGrid = dim3(c->numCUs);
     }

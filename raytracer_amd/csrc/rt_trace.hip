@@ -7,6 +7,7 @@
 //   rt_generate.inl       k_generate (camera rays, slot-per-pixel pipeline)
 //   rt_post.inl           post-process, bloom, block errors, texture evaluation
 //   rt_kat.inl            known-answer hooks (rtgpu_kat*)
+//   rt_query.inl          batched ray queries around the walks above (rtgpu_trace_rays)
 // The host side (rt_runtime.hip) launches them through the declarations of rt_trace_kernels.h.
 //
 // Compile: hipcc --offload-arch=gfx950 -O3 -ffp-contract=off
@@ -27,6 +28,7 @@ using namespace rtd;
 #include "rt_trace_packet.inl"
 #include "rt_trace_wide2.inl"
 #include "rt_kat.inl"
+#include "rt_query.inl"
 #include "rt_post.inl"
 
 // the instantiations the host side launches

@@ -23,6 +23,15 @@ struct BlurPlan { uint32_t n, wl, wu; float m; };
 struct BloomLevels { const float* level[5]; };
 struct ErrorRow { uint32_t block, y; };
 
+// The degenerate-ray rule of the ray queries (include/rtgpu.h): a non-finite origin, a direction whose squared length (dot3, the sum Ray() takes the
+// root of) is 0 or not finite, or a maxDistance that is NaN or <= 0.  The host-side check of rtgpu_trace_rays and k_query_load (rt_query.inl) share it.
+__host__ __device__ inline bool queryRayIsDegenerate(float ox, float oy, float oz, float maxDistance, float dx, float dy, float dz)
+{
+    const float lengthSq = (dx * dx + dy * dy) + (dz * dz + 0.0f);
+    const bool originFinite = isfinite(ox) && isfinite(oy) && isfinite(oz);
+    return !originFinite || !(lengthSq > 0.0f && lengthSq <= 3.402823466e+38f) || !(maxDistance > 0.0f);
+}
+
 // one list of the traversal kernels' instantiations: X(stack entries per lane, intersection counters) etc.
 #define RT_TRACE_ATTR(kStack) __launch_bounds__(RT_BLOCK) __attribute__((amdgpu_waves_per_eu(kStack <= 24 ? 5 : 1)))
 #define RT_K_TRACE_ARGS (const RtSceneDesc scene, const Paths paths, const uint32_t* __restrict__ queue, const uint32_t* __restrict__ queueCount, \
@@ -62,5 +71,12 @@ __global__ void __launch_bounds__(64) k_kat(const RtSceneDesc scene, uint32_t fu
 __global__ void __launch_bounds__(64) k_kat_sampler(const uint16_t* __restrict__ blueNoise, const float* __restrict__ in, uint32_t inStride, float* __restrict__ out,
                                                     uint32_t count, uint32_t n);
 __global__ void __launch_bounds__(64) k_kat_mesh(const RtSceneDesc scene, const float* __restrict__ rays, uint32_t n, uint32_t* __restrict__ out);
+// ray queries (rt_query.inl)
+__global__ void __launch_bounds__(RT_BLOCK) k_query_load(const float4* __restrict__ rays, uint32_t count, uint32_t mode, const Paths paths,
+                                                         uint32_t* __restrict__ queue, uint32_t* __restrict__ queueCount, unsigned long long* counters);
+__global__ void __launch_bounds__(RT_BLOCK) k_query_store(const RtSceneDesc scene, const float4* __restrict__ rays, uint32_t count, uint32_t mode, const Paths paths,
+                                                          float4* __restrict__ hits, uint32_t* __restrict__ occluded);
+__global__ void __launch_bounds__(RT_BLOCK) k_query_evaluate(const RtSceneDesc scene, const float4* __restrict__ rays, uint32_t count, const float4* __restrict__ hits,
+                                                             float4* __restrict__ surfaces, unsigned long long* counters);
 __global__ void __launch_bounds__(RT_MONSTER_BLOCK) k_trace_monster(const RtSceneDesc scene, const Paths paths, const uint32_t* __restrict__ queue, const uint32_t* __restrict__ queueCount);
 #endif

@@ -30,6 +30,8 @@ public:
 
     RtgpuContext* GetDeviceContext() const { return mCtx; }
     bool SetShard(uint32 rank, uint32 worldSize);
+    // uploads the scene (if it changed) as the first pass would: what the ray queries of the device context (rtgpu_trace_rays) walk
+    bool UploadScene() { return EnsureSceneUploaded(); }
 
 protected:
     // wholeFrameOnOneDevice: integrators that splat over the frame (Light Tracer, VCM) ignore SetRendererDevices

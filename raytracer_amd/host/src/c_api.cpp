@@ -369,6 +369,12 @@ RTH_API int rth_viewport_set_renderer(void* v, void* sh, const char* name, int d
     if (!vh->renderer) return -2;
     return vh->viewport.SetRenderer(vh->renderer) ? 0 : -1;
 }
+// the scene of the viewport's renderer on its device (uploaded lazily before the first pass; the ray queries need it before any pass)
+RTH_API int rth_viewport_upload_scene(void* v)
+{
+    PathTracerMIS* r = dynamic_cast<PathTracerMIS*>(static_cast<ViewportHandle*>(v)->renderer.get());
+    return r && r->UploadScene() ? 0 : -1;
+}
 // the devices of renderers created afterwards (SetRendererDevices); n == 0: back to one device
 RTH_API void rth_set_renderer_devices(const int* devices, uint32_t n) { SetRendererDevices(std::vector<int>(devices, devices + n)); }
 // the public knobs of the "VCM" renderer (no-op with -3 when the viewport's renderer is not VCM); weights = 5 scalars:
