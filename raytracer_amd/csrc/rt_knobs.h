@@ -1,0 +1,79 @@
+// rt_knobs.h -- every RTGPU_* environment variable the library reads, in one place, ordered by WHEN it is read.  Included by rt_runtime.hip behind
+// rt_runtime_context.h.  DESIGN.md ("Environment knobs") lists them with their defaults; why a default is what it is stands next to the policy
+// that uses it (launchTraceWide, launchRetrace, tailDepthFor, ...), not here.
+//
+//   1. per context   copied into the RtgpuContext by rtgpu_create / rtgpu_create_multi: a later change of the variable reaches new contexts only
+//   2. per process   read once, by the first call that needs the value (a function-local static): a later change is never seen
+//   3. per call      read on every launch (or every scene upload): the tests flip these between two renders of one process
+#pragma once
+
+namespace knobs {
+
+static inline int envInt(const char* name, int fallback) { const char* e = getenv(name); return e ? atoi(e) : fallback; }
+static inline bool envSet(const char* name) { return getenv(name) != nullptr; }
+
+// ---- 1. per context --------------------------------------------------------------------------------------------------------------------------
+// bytes RTGPU_LANE_BUDGET_MB asks for; 0: not set
+static inline size_t laneBudgetBytes() { const char* e = getenv("RTGPU_LANE_BUDGET_MB"); return e ? (size_t)strtoull(e, nullptr, 10) << 20 : 0u; }
+
+// the scheduling and layout knobs of a new context, with their clamps (performance only; results do not depend on them)
+static inline void readContextKnobs(RtgpuContext* c)
+{
+    c->tune.refillMinIdle = (uint32_t)envInt("RTGPU_REFILL_MIN_IDLE", (int)c->tune.refillMinIdle);
+    c->tune.otherMinLanes = (uint32_t)envInt("RTGPU_OTHER_MIN_LANES", (int)c->tune.otherMinLanes);
+    c->travBlocksPerCU = (uint32_t)envInt("RTGPU_TRAV_BLOCKS_PER_CU", (int)c->travBlocksPerCU);
+    c->wideAllowed = envInt("RTGPU_WIDE", 1) != 0;
+    c->wide2Allowed = envInt("RTGPU_WIDE2", 1) != 0;
+    c->denseAllowed = envInt("RTGPU_NO_DENSE", 0) == 0;
+    c->countIntersections = envInt("RTGPU_INTERSECTION_COUNTERS", 0) != 0;
+    if (envSet("RTGPU_PASS_BATCH")) { c->passBatch = (uint32_t)envInt("RTGPU_PASS_BATCH", 0); c->passBatchFromEnv = true; }
+    if (c->passBatch < 1) c->passBatch = 1;
+    if (c->passBatch > RT_SEED_RING / 2) c->passBatch = RT_SEED_RING / 2;
+    if (envSet("RTGPU_LANES")) { c->numLanes = (uint32_t)envInt("RTGPU_LANES", 0); c->lanesChosen = true; }
+    if (c->numLanes < 1) c->numLanes = 1;
+    if (c->numLanes > RT_MAX_LANES) c->numLanes = RT_MAX_LANES;
+    if (c->tune.refillMinIdle < 1) c->tune.refillMinIdle = 1;
+    if (c->tune.otherMinLanes < 1) c->tune.otherMinLanes = 1;
+}
+// rtgpu_create_multi
+static inline bool multiStaged() { return envInt("RTGPU_MULTI_STAGED", 0) != 0; }
+static inline bool verbose() { return envInt("RTGPU_VERBOSE", 0) != 0; }
+
+// ---- 2. per process --------------------------------------------------------------------------------------------------------------------------
+#define RT_KNOB_ONCE(type, name, value) static inline type name() { static const type v = (value); return v; }
+RT_KNOB_ONCE(uint32_t, passBatchBase, (uint32_t)envInt("RTGPU_PASS_BATCH_BASE", 5))
+RT_KNOB_ONCE(uint32_t, smallFrameBatch, (uint32_t)envInt("RTGPU_SMALL_FRAME_BATCH", 20))
+RT_KNOB_ONCE(uint32_t, maxStreamBatch, (uint32_t)envInt("RTGPU_MAX_STREAM_BATCH", 24))
+RT_KNOB_ONCE(uint32_t, shadeBlocksPerCU, (uint32_t)envInt("RTGPU_SHADE_BLOCKS_PER_CU", 8))
+RT_KNOB_ONCE(uint32_t, tailBlocksPerCU, (uint32_t)envInt("RTGPU_TAIL_BLOCKS_PER_CU", 4))
+RT_KNOB_ONCE(uint32_t, packetBlocksPerCU, (uint32_t)envInt("RTGPU_PACKET_BLOCKS", 8))
+RT_KNOB_ONCE(int, tailDepth, envInt("RTGPU_TAIL_DEPTH", -1))                      // -1: policy
+RT_KNOB_ONCE(bool, fullPrimary, envInt("RTGPU_FULL_PRIMARY", 0) != 0)
+RT_KNOB_ONCE(int, localExact, envInt("RTGPU_LOCAL_EXACT", -1))                    // -1: policy
+RT_KNOB_ONCE(uint32_t, localExactFromBounce, (uint32_t)envInt("RTGPU_LOCAL_EXACT_FROM", 255))
+RT_KNOB_ONCE(uint32_t, wideChunkMin, (uint32_t)envInt("RTGPU_WIDE_CHUNK_MIN", 64))
+RT_KNOB_ONCE(bool, wideDiag, envSet("RTGPU_WIDE_DIAG"))                           // (its value is read per launch: wideDiagMode)
+RT_KNOB_ONCE(uint32_t, retraceSplitAfter, (uint32_t)envInt("RTGPU_RETRACE_SPLIT_AFTER", 0))   // 0: RT_RETRACE_SPLIT_AFTER
+RT_KNOB_ONCE(int, retraceFullGrid, envInt("RTGPU_RETRACE_FULL_GRID", -1))         // -1: policy
+RT_KNOB_ONCE(int, abortClosestAfter, envInt("RTGPU_ABORT_CLOSEST_AFTER", -1))     // test hook; -1: the context's value
+RT_KNOB_ONCE(bool, vcmClass, envInt("RTGPU_VCM_CLASS", 1) != 0)
+RT_KNOB_ONCE(bool, vcmWide, envInt("RTGPU_VCM_WIDE", 0) != 0)
+RT_KNOB_ONCE(uint32_t, vcmMergeCooperativeMin, (uint32_t)envInt("RTGPU_VCM_MERGE_COOP", RT_VCM_COOPERATIVE_MERGE_MIN))
+RT_KNOB_ONCE(int, vcmBatch, envInt("RTGPU_VCM_BATCH", 0))                         // <= 0: policy
+#undef RT_KNOB_ONCE
+
+// ---- 3. per call -----------------------------------------------------------------------------------------------------------------------------
+// every launch of a 4-wide walk (and of k_tail, which walks the same tree)
+static inline uint32_t anyHitFarFirst() { return envInt("RTGPU_ANYHIT_FAR_FIRST", 1) != 0 ? 1u : 0u; }
+static inline uint32_t wideReverse() { return (uint32_t)envInt("RTGPU_WIDE_REVERSE", 0); }
+static inline uint32_t wideDrainAbort() { return (uint32_t)envInt("RTGPU_WIDE_DRAIN_ABORT", 0); }   // test hook; 0: off
+static inline uint32_t wideDiagMode() { return (uint32_t)envInt("RTGPU_WIDE_DIAG", 0); }
+static inline bool packets() { return envInt("RTGPU_PACKET", 1) != 0; }
+// every re-trace launch
+static inline int abortRetraceAfter() { return envInt("RTGPU_ABORT_RETRACE_AFTER", -1); }   // test hook; < 0: RT_ABORT_RETRACE_AFTER
+static inline bool retraceMonsters() { return envSet("RTGPU_RETRACE_MONSTERS") ? envInt("RTGPU_RETRACE_MONSTERS", 0) != 0 : envSet("RTGPU_ABORT_RETRACE_AFTER"); }
+// every rtgpu_upload_scene
+static inline bool noLean() { return envInt("RTGPU_NO_LEAN", 0) != 0; }
+static inline bool noSimpleTextures() { return envInt("RTGPU_NO_SIMPLE_TEXTURES", 0) != 0; }
+
+} // namespace knobs

@@ -1,0 +1,344 @@
+// rt_runtime_context.h -- what every part of the host runtime shares: the staging copies, error reporting (HIP_TRY), the context and its batch lanes,
+// the free helpers of their device memory, launch timing and the stream pool.  Included by rt_runtime.hip.
+#pragma once
+#include <mutex>
+
+// =====================================================================================================
+// Host side of the C-ABI
+// =====================================================================================================
+// Synchronous copies between HOST memory the caller owns and the device.  HIP would page-lock a large pageable range on the fly and keep the
+// registration cached; the caller then frees the range (a std::vector of the host mirror, a numpy array) and a later allocation lands on the
+// same addresses -- on some boxes of the pool the HSA runtime aborts the process a few dozen contexts later (no message; it went away with
+// this).  So anything above 64 KB that is not page-locked already (hipHostMalloc / hipHostRegister: the viewport's sum bitmaps) travels
+// through a page-locked staging buffer of the library, 8 MB at a time.
+// one staging buffer (and its lock) per device: contexts on different devices copy side by side (rtgpu_create_multi).  8 MB of page-locked memory
+// per device used, kept for the life of the process (freeing it from an exit handler would race the HIP runtime's own teardown)
+struct Staging { std::mutex mutex; void* buffer = nullptr; };
+static std::mutex gStagingTableMutex;
+static std::unordered_map<int, Staging*> gStaging;
+static const size_t kStagingBytes = (size_t)8 << 20;
+static Staging* stagingOfCurrentDevice()
+{
+    int device = 0;
+    (void)hipGetDevice(&device);
+    std::lock_guard<std::mutex> lock(gStagingTableMutex);
+    Staging*& s = gStaging[device];
+    if (!s) s = new Staging();
+    return s;
+}
+static bool hostRangeIsPageLocked(const void* p)
+{
+    hipPointerAttribute_t attr;
+    if (hipPointerGetAttributes(&attr, p) != hipSuccess) { (void)hipGetLastError(); return false; }   // ordinary pageable memory: "invalid value"
+    return attr.type == hipMemoryTypeHost;
+}
+static hipError_t rtMemcpy(void* dst, const void* src, size_t bytes, hipMemcpyKind kind)
+{
+    if (bytes == 0) return hipSuccess;
+    const bool h2d = kind == hipMemcpyHostToDevice, d2h = kind == hipMemcpyDeviceToHost;
+    if ((!h2d && !d2h) || bytes <= ((size_t)64 << 10) || hostRangeIsPageLocked(h2d ? src : dst)) return hipMemcpy(dst, src, bytes, kind);
+    Staging* const st = stagingOfCurrentDevice();
+    std::lock_guard<std::mutex> lock(st->mutex);
+    if (!st->buffer)
+    {
+        const hipError_t e = hipHostMalloc(&st->buffer, kStagingBytes, hipHostMallocPortable);
+        if (e != hipSuccess) { st->buffer = nullptr; return e; }
+    }
+    for (size_t done = 0; done < bytes; done += kStagingBytes)
+    {
+        const size_t n = bytes - done < kStagingBytes ? bytes - done : kStagingBytes;
+        if (h2d) memcpy(st->buffer, static_cast<const char*>(src) + done, n);
+        const hipError_t e = h2d ? hipMemcpy(static_cast<char*>(dst) + done, st->buffer, n, kind) : hipMemcpy(st->buffer, static_cast<const char*>(src) + done, n, kind);
+        if (e != hipSuccess) return e;
+        if (d2h) memcpy(static_cast<char*>(dst) + done, st->buffer, n);
+    }
+    return hipSuccess;
+}
+
+static thread_local std::string gLastError;
+
+static int fail(int code, const std::string& msg) { gLastError = msg; return code; }
+
+#define HIP_TRY(expr)                                                                                   \
+    do {                                                                                                \
+        hipError_t _e = (expr);                                                                         \
+        if (_e != hipSuccess)                                                                           \
+            return fail(_e == hipErrorOutOfMemory ? RTGPU_ERR_OUT_OF_MEMORY : RTGPU_ERR_DEVICE,          \
+                        std::string(#expr) + ": " + hipGetErrorString(_e));                             \
+    } while (0)
+
+enum KernelClass { KC_GENERATE = 0, KC_TRACE, KC_SHADE, KC_ACCUMULATE, KC_RETRACE, KC_TAIL, KC_COUNT };
+static const char* const kKernelClassNames[RTGPU_NUM_KERNEL_CLASSES] = { "generate", "trace", "shade", "accumulate", "retrace", "tail", "", "" };
+
+#define RT_SEED_RING 128
+
+struct CtxPending { DevPass pass; std::vector<uint32_t> seeds; };
+#define RT_VCM_MAX_BATCH 8
+
+#define RT_MAX_LANES 6
+struct BatchLane
+{
+    hipStream_t stream = nullptr;
+    Paths paths = { nullptr, 0, 0 };
+    uint32_t* queues[2] = { nullptr, nullptr };
+    uint32_t* shadowQueues[2] = { nullptr, nullptr };   // capacity * maxLights NEE ray requests each, ping-pong per bounce
+    uint32_t* exactQueue = nullptr;        // closest-hit rays / any-hit requests the 4-wide walks hand to the binary-tree kernel
+    uint32_t* exactShadowQueue = nullptr;
+    // dense path state (rt_dense.inl, LightSamplingStrategy::Single): the second arena of the ping-pong, the parked radiance of
+    // finished paths, per bounce the live / zombie counts of the arena's regions (2 * RT_DENSE_SHARDS words per bounce)
+    Paths paths2 = { nullptr, 0, 0 };
+    float4* home = nullptr; size_t homeCapacity = 0;
+    uint32_t* denseCounts = nullptr;
+    // per-batch work counters, 8 planes of (maxDepth + 2) uint32, zeroed once per batch (one word of each plane per bounce, so that no
+    // reset ever races with a reader); LaneCounts names the planes
+    uint32_t* queueCounts = nullptr;
+    uint32_t queueCountCapacity = 0;
+    hipEvent_t accumulated = nullptr;   // recorded after the lane's k_accumulate
+};
+
+// the planes of BatchLane::queueCounts, built once per flush; index each with the bounce (plane 3 is unused)
+struct LaneCounts
+{
+    uint32_t* pathCounts; uint32_t* shadowCounts; uint32_t* cursors;              // path queues, next-event request queues, the traversal launches' work cursors
+    uint32_t* exactCounts; uint32_t* exactShadowCounts; uint32_t* exactCursors;   // what the 4-wide walks hand to the re-trace launch, and its cursors
+    uint32_t* overflowCounts;                                                     // closest-hit rays the re-trace launch hands to k_trace_monster
+    explicit LaneCounts(const BatchLane& l)
+        : pathCounts(l.queueCounts), shadowCounts(l.queueCounts + 1 * l.queueCountCapacity), cursors(l.queueCounts + 2 * l.queueCountCapacity),
+          exactCounts(l.queueCounts + 4 * l.queueCountCapacity), exactShadowCounts(l.queueCounts + 5 * l.queueCountCapacity),
+          exactCursors(l.queueCounts + 6 * l.queueCountCapacity), overflowCounts(l.queueCounts + 7 * l.queueCountCapacity) {}
+};
+
+struct RtgpuContext
+{
+    int device = 0;
+    uint32_t numCUs = 256;
+
+    // scene (device copies); sceneDev holds DEVICE pointers
+    RtSceneDesc sceneDev;
+    std::vector<void*> sceneAllocs;
+    bool sceneReady = false;
+    uint32_t numLights = 0;
+
+    // film
+    uint32_t width = 0, height = 0;
+    RtgpuShard shard = { 0, 1 };
+    // rtgpu_create_multi: the context the caller holds renders shard 0 and owns one more context per further device (shards 1..);
+    // every call fans out, the read-back calls gather the peers' tiles into this context's sum buffers first (rt_multi.inl)
+    std::vector<RtgpuContext*> peers;
+    bool isPeer = false;
+    bool stagedGather = false;         // no peer access between the devices (or RTGPU_MULTI_STAGED=1): hipMemcpyPeerAsync into staging buffers, then the gather
+    float* gatherStage = nullptr; size_t gatherStageFloats = 0;
+    bool axisParallelSun = false;      // the scene has a delta directional light along a coordinate plane / axis: its next-event rays fill the re-trace launches (full grid there)
+    RtMultiInfo multiInfo = {};        // rtgpu_get_multi_info: which gather was chosen and why, its timings
+    float* sum = nullptr;
+    float* secondary = nullptr;
+    uint32_t* slotPixel = nullptr;
+    uint32_t numSlots = 0;
+    std::vector<uint8_t> activeMask;   // adaptive rendering: 1 = pixel inside an active block; empty = whole image
+
+    // Batch lanes.  Every batch of passes runs on ONE lane = its own stream, path-state arena, queues and work
+    // counters; consecutive batches alternate lanes, so the drain of a persistent traversal launch (a handful of
+    // rays with thousands of steps keep a few waves busy for milliseconds -- an axis-parallel NEE ray that grazes
+    // a plane of box faces can take 30 000) overlaps with the next batch's kernels instead of idling the chip.
+    // Only k_accumulate is ordered across lanes (an event): the film is summed in pass order.
+    BatchLane lanes[RT_MAX_LANES];
+    uint32_t numLanes = 4;
+    bool lanesChosen = false;          // by RTGPU_LANES or rtgpu_set_concurrency; otherwise shards (< 1.1 M owned pixels) run 4 lanes
+    uint32_t nextLane = 0;
+    int lastAccumulateLane = -1;
+    uint32_t traversalStackNeed = 0;   // deepest top-level + mesh stack the uploaded scene can produce
+    WideBvh wide;                      // 4-wide collapse of the same tree (rt_trace_wide.inl); nodes == nullptr: none
+    WideScene wide2;                   // two-level scenes: 4-wide top-level tree over 4-wide mesh trees (rt_trace_wide2.inl); nodes == nullptr: none
+    bool wide2Allowed = true;          // RTGPU_WIDE2=0: two-level scenes keep the binary walk
+    uint64_t walkNodeBytes[3] = { 0, 0, 0 }, walkLeafBoxBytes[3] = { 0, 0, 0 }, walkTriangleBytes = 0;   // rtgpu_get_walk_info, per RTGPU_WALK_* kernel
+    bool wideAllowed = true;           // RTGPU_WIDE=0: single-mesh scenes walk the binary tree (k_trace) even with the intersection counters off
+    bool denseAllowed = true;          // RTGPU_NO_DENSE=1: path state stays in the pixel's slot for the whole path (the first layout)
+    TravTuning tune = { 28u, 32u, 0.0001f, nullptr, nullptr, RT_ABORT_CLOSEST_AFTER, nullptr, 0u };   // scheduling: measured plateau on MI355X (profiles/r01_tuning_sweep.txt)
+    uint32_t travBlocksPerCU = 0;      // 0 = default
+    int32_t tailBounce = -1;           // rtgpu_set_schedule: the bounce at which a dense batch hands over to k_tail (rt_tail.hip); 0 = never, -1 = policy
+    int32_t localRetrace = -1;         // rtgpu_set_schedule: the 4-wide walks trace their undecided rays themselves; 0 / 1, -1 = policy
+    int leanScene = 0;                 // the scene class of rt_device_core.h (kLean): 0 anything, 1 lean, 2 lean + textures, 3 anything without textures, 4 lean + simple bitmaps only
+    bool countIntersections = false;   // box / triangle test counters: RT_ENABLE_INTERSECTION_COUNTERS of the reference, off by default like there (Core/Config.h:4);
+                                       // rtgpu_set_intersection_counters, or RTGPU_INTERSECTION_COUNTERS=1 for the default of new contexts
+    unsigned long long* counters = nullptr;   // 16 x u64
+    uint32_t* deviceFlags = nullptr;          // page-locked, device-visible: kernels raise [0] when a region of a dense arena overflows; checked by every synchronising call
+
+    // passes queued by rtgpu_render_pass and not yet submitted: up to passBatch of them ride through ONE launch
+    // sequence (their paths are simply more slots), which amortises the per-launch tail of the persistent kernels
+    std::vector<CtxPending> pending;
+    uint32_t passBatch = 8;
+    bool passBatchFromEnv = false;     // otherwise small frames / small shards (< 400 k owned pixels) batch 16 passes
+    // A caller that streams passes (no read-back in between) gets larger batches: after every submitted batch of a full-size frame
+    // the next one grows by 8 passes up to 24 (8 -> 2100, 16 -> 2125-2190, 24 -> 2195-2210 Msamples/s over 256 passes); any
+    // synchronising call starts over at the base size, so a caller that renders few passes between read-backs keeps the small batches.
+    uint32_t passBatchBase = 8;
+    size_t laneBudgetBytes = (size_t)32 << 30;   // device memory one batch lane may take: 32 GB, less on a device that could not hold four such lanes
+    uint32_t batchesAtThisSize = 0;    // full batches submitted at the current passBatch
+    uint32_t batchesSinceSync = 0;     // batches submitted since the last synchronising call (their lanes are busy)
+    DevPass* passRingDev = nullptr;
+    DevPass* passRingHost = nullptr;    // pinned
+
+    // per-pass seed ring
+    uint32_t* seedRingDev = nullptr;
+    uint32_t* seedRingHost = nullptr;   // pinned
+    hipEvent_t seedEvents[RT_SEED_RING];
+    bool seedEventUsed[RT_SEED_RING];
+    uint32_t seedCursor = 0;
+
+    bool plainPathTracer = false;      // RT_INTEGRATOR_PATH_TRACER: k_shade<false, true>
+    bool lightTracer = false;          // RT_INTEGRATOR_LIGHT_TRACER: the light stage of rt_vcm.inl without MIS (k_lt_shade)
+    int debugMode = -1;                // RT_INTEGRATOR_DEBUG: DebugRenderingMode, k_debug_shade after the primary rays' traversal
+    // bidirectional integrator (rt_vcm.inl) on lane 0's stream.  Like PathTracerMIS passes, VCM passes ride through the launch
+    // sequence in batches: the light stages of the batch first (pass j's photons are the merge set of pass j+1, so the hash grids
+    // of passes 1.. are built between the stages), then the camera stages -- the same results as one pass at a time.
+    struct Vcm
+    {
+        bool enabled = false;
+        RtVcmParams params;
+        float mergingRadiusVC = 0.0f, mergingRadiusVM = 0.0f;
+        Paths lightPaths = { nullptr, 0, 0 }, cameraPaths = { nullptr, 0, 0 };
+        VcmArena arena = { nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, 0, 0 };
+        uint32_t* mergeQueue = nullptr; uint32_t* connectQueue = nullptr;
+        uint32_t* overflowQueue = nullptr;   // closest-hit rays k_trace hands to k_trace_monster
+        uint32_t* exactQueue = nullptr; uint32_t* exactShadowQueue = nullptr;   // what the 4-wide walks hand to the binary-tree kernel (as BatchLane's)
+        uint32_t traceSerial = 0;            // trace launches since the counters were zeroed: every launch has its own hand-over counters
+        uint32_t* queues[4] = { nullptr, nullptr, nullptr, nullptr };          // light ping-pong, camera ping-pong
+        uint32_t* shadowQueues[4] = { nullptr, nullptr, nullptr, nullptr };
+        uint32_t* counts = nullptr;                                               // VCP_NUM_PLANES planes of RT_VCM_COUNT_PLANE words (VcmCountPlane, rt_runtime_vcm.inl)
+        DevPass* passDev = nullptr; uint32_t* seedDev = nullptr;                 // RT_VCM_MAX_BATCH entries each
+        VcmDev* devsDev = nullptr; HashGridView* gridsDev = nullptr;
+        VcmPhotonGrid grids[RT_VCM_MAX_BATCH];                                    // merge set of pass j of the batch
+        bool havePhotons = false;     // the arena holds the photons of the pass before the next one ...
+        uint32_t lastPhotonPass = 0;  // ... in the storage of this pass of the last batch
+        uint32_t requestsPerVertex = 0;
+        uint32_t batch = 1, batchCapacity = 0;   // passes per launch sequence; what the arenas were sized for
+        // passes queued by rtgpu_render_pass and not yet submitted
+        struct Pending { RtPassParams params; std::vector<uint32_t> seeds; };
+        std::vector<Pending> pending;
+    } vcm;
+
+    // batched ray queries (rtgpu_trace_rays): a path-state arena, queues, work counts and counters of their own -- never a lane's, never c->counters
+    struct Query
+    {
+        Paths paths = { nullptr, 0, 0 };          // maxLights = 1; capacity = the rays of one chunk
+        uint32_t* queue = nullptr;                // closest-hit rays or any-hit requests of the chunk
+        uint32_t* exactQueue = nullptr; uint32_t* exactShadowQueue = nullptr;   // what the 4-wide walks hand to the re-trace launch
+        uint32_t* counts = nullptr;               // QC_WORDS work counts (QC_*)
+        unsigned long long* counters = nullptr;   // 16 x u64, the layout of RtCounters
+        float4* stagedRays = nullptr; float4* stagedHits = nullptr; float4* stagedSurfaces = nullptr; uint32_t* stagedOccluded = nullptr;   // rtgpu_trace_rays' device copies
+        hipEvent_t done = nullptr;                // recorded behind every query: the next one (whatever its stream), a new arena and a new scene wait for it
+    } query;
+
+    // timing
+    bool timing = false;
+    struct Timed { int kc; hipEvent_t a, b; };
+    std::vector<Timed> pendingTimed;
+    std::vector<hipEvent_t> eventPool;
+    double kernelMs[RTGPU_NUM_KERNEL_CLASSES];
+    uint64_t kernelLaunches[RTGPU_NUM_KERNEL_CLASSES];
+};
+
+// frees a device allocation (or several) and forgets it
+template <class T> static void devFree(T*& p) { if (p) (void)hipFree(p); p = nullptr; }
+template <class T, class... Rest> static void devFree(T*& p, Rest*&... rest) { devFree(p); devFree(rest...); }
+
+static void freeScene(RtgpuContext* c)
+{
+    for (void* p : c->sceneAllocs) (void)hipFree(p);
+    c->sceneAllocs.clear();
+    memset(&c->sceneDev, 0, sizeof(c->sceneDev));
+    c->sceneReady = false;
+}
+
+static void freeFilm(RtgpuContext* c)
+{
+    devFree(c->sum, c->secondary, c->slotPixel);
+    c->numSlots = 0;
+}
+
+static void freePaths(BatchLane& l)
+{
+    devFree(l.paths.base, l.queues[0], l.queues[1], l.shadowQueues[0], l.shadowQueues[1], l.exactQueue, l.exactShadowQueue, l.paths2.base, l.home);
+    l.paths.capacity = 0; l.paths.maxLights = 0; l.paths2.capacity = 0; l.paths2.maxLights = 0; l.homeCapacity = 0;
+}
+
+static hipError_t syncLanes(RtgpuContext* c)
+{
+    hipError_t first = hipSuccess;
+    for (uint32_t i = 0; i < RT_MAX_LANES; ++i)
+        if (c->lanes[i].stream) { const hipError_t e = hipStreamSynchronize(c->lanes[i].stream); if (first == hipSuccess) first = e; }
+    return first;
+}
+
+static int resolveTimed(RtgpuContext* c)
+{
+    for (auto& t : c->pendingTimed)
+    {
+        float ms = 0.0f;
+        HIP_TRY(hipEventElapsedTime(&ms, t.a, t.b));
+        c->kernelMs[t.kc] += ms;
+        c->kernelLaunches[t.kc]++;
+        c->eventPool.push_back(t.a); c->eventPool.push_back(t.b);
+    }
+    c->pendingTimed.clear();
+    return RTGPU_OK;
+}
+
+static hipEvent_t acquireEvent(RtgpuContext* c)
+{
+    if (!c->eventPool.empty()) { hipEvent_t e = c->eventPool.back(); c->eventPool.pop_back(); return e; }
+    hipEvent_t e = nullptr;
+    (void)hipEventCreate(&e);
+    return e;
+}
+
+struct LaunchTimer
+{
+    RtgpuContext* c; hipStream_t stream; int kc; hipEvent_t a = nullptr, b = nullptr;
+    LaunchTimer(RtgpuContext* ctx, hipStream_t st, int k) : c(ctx), stream(st), kc(k)
+    {
+        if (c->timing) { a = acquireEvent(c); b = acquireEvent(c); (void)hipEventRecord(a, stream); }
+    }
+    ~LaunchTimer()
+    {
+        if (c->timing) { (void)hipEventRecord(b, stream); c->pendingTimed.push_back({ kc, a, b }); }
+    }
+};
+
+static void waitQueries(RtgpuContext* c) { if (c->query.done) (void)hipEventSynchronize(c->query.done); }
+static void freeQueryArena(RtgpuContext* c)
+{
+    RtgpuContext::Query& q = c->query;
+    waitQueries(c);
+    devFree(q.paths.base, q.queue, q.exactQueue, q.exactShadowQueue, q.stagedRays, q.stagedHits, q.stagedSurfaces, q.stagedOccluded);
+    q.paths.capacity = 0; q.paths.maxLights = 0;
+}
+static void freeQuery(RtgpuContext* c)
+{
+    RtgpuContext::Query& q = c->query;
+    freeQueryArena(c);
+    devFree(q.counts, q.counters);
+    if (q.done) (void)hipEventDestroy(q.done);
+    q.done = nullptr;
+}
+
+// Streams are recycled through a process-wide pool instead of being created and destroyed with every context: a test session (or an
+// application that opens a renderer per frame size) goes through hundreds of contexts, and on some boxes of the pool the HSA runtime's
+// event thread aborts the process after a few hundred stream (hardware queue) create / destroy cycles (no message; ROCm 7.0.2).  A context
+// returns its idle streams at destruction, after it has synchronised them.
+static std::mutex gStreamPoolMutex;
+static std::unordered_map<int, std::vector<hipStream_t>> gStreamPool;   // device -> idle non-blocking streams
+static hipError_t acquireStream(int device, hipStream_t* out)
+{
+    {
+        std::lock_guard<std::mutex> lock(gStreamPoolMutex);
+        auto& pool = gStreamPool[device];
+        if (!pool.empty()) { *out = pool.back(); pool.pop_back(); return hipSuccess; }
+    }
+    return hipStreamCreateWithFlags(out, hipStreamNonBlocking);
+}
+static void releaseStream(int device, hipStream_t stream)
+{
+    std::lock_guard<std::mutex> lock(gStreamPoolMutex);
+    gStreamPool[device].push_back(stream);
+}

@@ -1,0 +1,149 @@
+// rt_runtime_query.inl -- batched ray queries, host side.  Included by rt_runtime.hip.
+
+// ---- batched ray queries (include/rtgpu.h, rtgpu_trace_rays; kernels: rt_query.inl) ----------------------------------------------------------
+// A chunk of rays goes through k_query_load -> the walk the context renders with -> k_query_store (-> k_query_evaluate), on the query's own arena.
+#define RT_QUERY_CHUNK (1u << 22)   // rays per chunk: 4 M x 176 bytes of path records
+enum { QC_QUEUE = 0, QC_CURSOR, QC_EXACT, QC_EXACT_SHADOW, QC_EXACT_CURSOR, QC_WORDS = 8 };
+
+static int ensureQueryArena(RtgpuContext* c, uint32_t rays)
+{
+    RtgpuContext::Query& q = c->query;
+    if (!q.done) HIP_TRY(hipEventCreateWithFlags(&q.done, hipEventDisableTiming));
+    if (!q.counts) HIP_TRY(hipMalloc((void**)&q.counts, QC_WORDS * sizeof(uint32_t)));
+    if (!q.counters) HIP_TRY(hipMalloc((void**)&q.counters, 16 * sizeof(unsigned long long)));
+    const uint32_t want = rays < RT_QUERY_CHUNK ? rays : RT_QUERY_CHUNK;
+    if (q.paths.base && q.paths.capacity >= want) return RTGPU_OK;
+    // grown in powers of two from 64 K rays up to the chunk: a caller whose batches grow slowly does not reallocate with every call
+    uint32_t cap = 65536u;
+    while (cap < want) cap <<= 1;
+    freeQueryArena(c);   // (waits for the queries still using it)
+    HIP_TRY(hipMalloc((void**)&q.paths.base, ((size_t)R_NUM_BASE + RT_SHADOW_RECORDS) * cap * sizeof(float4)));
+    HIP_TRY(hipMalloc((void**)&q.queue, (size_t)cap * sizeof(uint32_t)));
+    HIP_TRY(hipMalloc((void**)&q.exactQueue, (size_t)cap * sizeof(uint32_t)));
+    HIP_TRY(hipMalloc((void**)&q.exactShadowQueue, (size_t)cap * sizeof(uint32_t)));
+    HIP_TRY(hipMalloc((void**)&q.stagedRays, (size_t)cap * sizeof(RtQueryRay)));
+    HIP_TRY(hipMalloc((void**)&q.stagedHits, (size_t)cap * sizeof(RtQueryHit)));
+    HIP_TRY(hipMalloc((void**)&q.stagedSurfaces, (size_t)cap * sizeof(RtQuerySurface)));
+    HIP_TRY(hipMalloc((void**)&q.stagedOccluded, (size_t)cap * sizeof(uint32_t)));
+    q.paths.capacity = cap; q.paths.maxLights = 1;
+    return RTGPU_OK;
+}
+
+// the launches of one chunk (n <= the arena's capacity), device pointers, on `stream`
+static int launchQueryChunk(RtgpuContext* c, hipStream_t stream, uint32_t mode, const float4* rays, uint32_t n, float4* hits, float4* surfaces, uint32_t* occluded)
+{
+    RtgpuContext::Query& q = c->query;
+    const bool closest = mode == RTGPU_TRACE_CLOSEST;
+    const dim3 block(RT_BLOCK), grid((n + RT_BLOCK - 1u) / RT_BLOCK);
+    HIP_TRY(hipMemsetAsync(q.counts, 0, QC_WORDS * sizeof(uint32_t), stream));
+    hipLaunchKernelGGL(k_query_load, grid, block, 0, stream, rays, n, mode, q.paths, q.queue, q.counts + QC_QUEUE, q.counters);
+    const uint32_t* tq = closest ? q.queue : nullptr; const uint32_t* tqc = closest ? q.counts + QC_QUEUE : nullptr;
+    const uint32_t* tsq = closest ? nullptr : q.queue; const uint32_t* tsc = closest ? nullptr : q.counts + QC_QUEUE;
+    // Any-hit requests walk the reference's binary tree (k_trace) whatever the setting: the 4-wide walks' any-hit decision is exact for the rays the
+    // integrators ask about (tmax = 0.999 x the light's distance: no triangle within an ulp of it), but a query's maxDistance may sit an ulp below a
+    // hit, and there the conservative leaf gate of the 4-wide walks let 6 % of such rays report an occluder the reference's box test culls (DESIGN.md,
+    // "Ray queries").
+    if (useWide(c) && closest)
+    {
+        // the render path's pair: the 4-wide walk hands the rays it does not decide to the re-trace launch (which alone gives them a result).  No
+        // block-local second walk and no k_trace_monster hand-over: neither changes a result.
+        launchTraceWide(c, stream, q.counters, q.paths, tq, tqc, tsq, tsc, q.counts + QC_CURSOR, q.exactQueue, q.counts + QC_EXACT, q.exactShadowQueue,
+                        q.counts + QC_EXACT_SHADOW, 0.0f, nullptr, 0u, false);
+        launchRetrace(c, stream, q.counters, q.paths, q.exactQueue, q.counts + QC_EXACT, q.exactShadowQueue, q.counts + QC_EXACT_SHADOW, q.counts + QC_EXACT_CURSOR,
+                      nullptr, nullptr);
+    }
+    else
+    {
+        TravTuning tune = c->tune;
+        tune.shadowOffset = 0.0f; tune.overflowQueue = nullptr; tune.overflowCount = nullptr; tune.denseCounts = nullptr; tune.denseShardCapacity = 0u;
+        launchTraceBinary(c, stream, dim3(traversalBlocks(c, stackClassOf(c))), q.counters, q.paths, tq, tqc, tsq, tsc, q.counts + QC_CURSOR, tune, c->countIntersections);
+    }
+    hipLaunchKernelGGL(k_query_store, grid, block, 0, stream, c->sceneDev, rays, n, mode, q.paths, hits, occluded);
+    if (surfaces) hipLaunchKernelGGL(k_query_evaluate, grid, block, 0, stream, c->sceneDev, rays, n, (const float4*)hits, surfaces, q.counters);
+    HIP_TRY(hipGetLastError());
+    return RTGPU_OK;
+}
+
+// argument rules shared by both entry points (count == 0 passes: the callers return at once)
+static int checkQuery(RtgpuContext* c, uint32_t mode, const void* rays, uint32_t count, const void* hits, const void* surfaces, const void* occluded)
+{
+    if (!c) return fail(RTGPU_ERR_INVALID_ARGUMENT, "NULL context");
+    if (mode != RTGPU_TRACE_CLOSEST && mode != RTGPU_TRACE_ANY) return fail(RTGPU_ERR_INVALID_ARGUMENT, "unknown ray query mode");
+    if (mode == RTGPU_TRACE_ANY && (hits || surfaces)) return fail(RTGPU_ERR_INVALID_ARGUMENT, "RTGPU_TRACE_ANY answers in `occluded` only: hits and surfaces must be NULL");
+    if (mode == RTGPU_TRACE_CLOSEST && occluded) return fail(RTGPU_ERR_INVALID_ARGUMENT, "RTGPU_TRACE_CLOSEST answers in `hits` (and `surfaces`): occluded must be NULL");
+    if (count == 0) return RTGPU_OK;
+    if (!rays || (mode == RTGPU_TRACE_CLOSEST ? !hits : !occluded)) return fail(RTGPU_ERR_INVALID_ARGUMENT, "NULL ray or result buffer");
+    if (!c->sceneReady) return fail(RTGPU_ERR_NOT_READY, "rtgpu_upload_scene has not been called");
+    return RTGPU_OK;
+}
+
+// timing (rtgpu_enable_timing) measures the render passes: the query's launches stay out of the kernel classes
+struct QueryUntimed
+{
+    RtgpuContext* c; bool was;
+    explicit QueryUntimed(RtgpuContext* ctx) : c(ctx), was(ctx->timing) { c->timing = false; }
+    ~QueryUntimed() { c->timing = was; }
+};
+
+RTGPU_API int rtgpu_trace_rays(RtgpuContext* c, uint32_t mode, const RtQueryRay* rays, uint32_t count, RtQueryHit* hits, RtQuerySurface* surfaces,
+                               uint32_t* occluded, RtCounters* stats)
+{
+    int r = checkQuery(c, mode, rays, count, hits, surfaces, occluded); if (r) return r;
+    if (count == 0) return RTGPU_OK;
+    for (uint32_t i = 0; i < count; ++i)
+    {
+        const RtQueryRay& ray = rays[i];
+        if (queryRayIsDegenerate(ray.origin[0], ray.origin[1], ray.origin[2], ray.maxDistance, ray.direction[0], ray.direction[1], ray.direction[2]))
+            return fail(RTGPU_ERR_INVALID_ARGUMENT, "ray " + std::to_string(i) + " is degenerate (non-finite origin, zero or non-finite direction, or maxDistance not > 0)");
+    }
+    HIP_TRY(hipSetDevice(c->device));
+    { int fr = vcmFlush(c); if (fr) return fr; }
+    { int fr = flushPending(c); if (fr) return fr; }
+    r = ensureQueryArena(c, count); if (r) return r;
+    RtgpuContext::Query& q = c->query;
+    const QueryUntimed untimed(c);
+    hipStream_t stream = c->lanes[0].stream;
+    HIP_TRY(hipStreamWaitEvent(stream, q.done, 0));
+    HIP_TRY(hipMemsetAsync(q.counters, 0, 16 * sizeof(unsigned long long), stream));
+    const bool closest = mode == RTGPU_TRACE_CLOSEST;
+    for (uint32_t first = 0; first < count; first += q.paths.capacity)
+    {
+        const uint32_t n = count - first < q.paths.capacity ? count - first : q.paths.capacity;
+        HIP_TRY(rtMemcpy(q.stagedRays, rays + first, (size_t)n * sizeof(RtQueryRay), hipMemcpyHostToDevice));
+        r = launchQueryChunk(c, stream, mode, q.stagedRays, n, closest ? q.stagedHits : nullptr, surfaces ? q.stagedSurfaces : nullptr, closest ? nullptr : q.stagedOccluded);
+        if (r) return r;
+        HIP_TRY(hipStreamSynchronize(stream));
+        if (closest) HIP_TRY(rtMemcpy(hits + first, q.stagedHits, (size_t)n * sizeof(RtQueryHit), hipMemcpyDeviceToHost));
+        if (surfaces) HIP_TRY(rtMemcpy(surfaces + first, q.stagedSurfaces, (size_t)n * sizeof(RtQuerySurface), hipMemcpyDeviceToHost));
+        if (!closest) HIP_TRY(rtMemcpy(occluded + first, q.stagedOccluded, (size_t)n * sizeof(uint32_t), hipMemcpyDeviceToHost));
+    }
+    HIP_TRY(hipEventRecord(q.done, stream));
+    if (stats) HIP_TRY(rtMemcpy(stats, q.counters, sizeof(RtCounters), hipMemcpyDeviceToHost));
+    return RTGPU_OK;
+}
+
+RTGPU_API int rtgpu_trace_rays_async(RtgpuContext* c, uint32_t mode, const RtQueryRay* rays, uint32_t count, RtQueryHit* hits, RtQuerySurface* surfaces,
+                                     uint32_t* occluded, RtCounters* stats, void* streamHandle)
+{
+    int r = checkQuery(c, mode, rays, count, hits, surfaces, occluded); if (r) return r;
+    if (count == 0) return RTGPU_OK;
+    if ((((uintptr_t)rays) | ((uintptr_t)hits) | ((uintptr_t)surfaces)) & 15u || ((uintptr_t)occluded & 3u) || ((uintptr_t)stats & 7u))
+        return fail(RTGPU_ERR_INVALID_ARGUMENT, "rays, hits and surfaces must be 16-byte aligned device buffers (occluded 4, stats 8)");
+    HIP_TRY(hipSetDevice(c->device));
+    r = ensureQueryArena(c, count); if (r) return r;
+    RtgpuContext::Query& q = c->query;
+    const QueryUntimed untimed(c);
+    hipStream_t stream = streamHandle ? (hipStream_t)streamHandle : c->lanes[0].stream;
+    HIP_TRY(hipStreamWaitEvent(stream, q.done, 0));   // the arena is shared with the previous query, whatever its stream
+    HIP_TRY(hipMemsetAsync(q.counters, 0, 16 * sizeof(unsigned long long), stream));
+    for (uint32_t first = 0; first < count; first += q.paths.capacity)
+    {
+        const uint32_t n = count - first < q.paths.capacity ? count - first : q.paths.capacity;
+        r = launchQueryChunk(c, stream, mode, (const float4*)(rays + first), n, hits ? (float4*)(hits + first) : nullptr, surfaces ? (float4*)(surfaces + first) : nullptr,
+                             occluded ? occluded + first : nullptr);
+        if (r) return r;
+    }
+    if (stats) HIP_TRY(hipMemcpyAsync(stats, q.counters, sizeof(RtCounters), hipMemcpyDeviceToDevice, stream));
+    HIP_TRY(hipEventRecord(q.done, stream));
+    return RTGPU_OK;
+}

@@ -1,26 +1,31 @@
 // rt_runtime_vcm.inl -- host side of the bidirectional integrator (renderer "VCM") and of the Light Tracer: arenas, the per-batch launch sequence of
-// rt_vcm.inl's kernels, PreRender.  Included by rt_runtime.hip (inside its extern "C" block, after the PathTracerMIS launch sequence).
+// rt_vcm.inl's kernels, PreRender.  Included by rt_runtime.hip, after the PathTracerMIS launch sequence (rt_runtime_render.inl).
 // =====================================================================================================
 // Bidirectional integrator: host side (kernels in rt_vcm.inl)
 // =====================================================================================================
 #define RT_VCM_COUNT_PLANE (RT_VCM_MAX_PATH_LENGTH + 4u)
-#define RT_VCM_NUM_COUNT_PLANES 16u   // 0-9 as before; 10-11 / 12-13 / 14-15: per trace launch the hand-over counts (closest, any-hit) and cursor of the 4-wide walks
+// the planes of Vcm::counts, RT_VCM_COUNT_PLANE words each: one word per bounce -- and, in the three double planes at the end, one per trace launch of a
+// batch (Vcm::traceSerial): the hand-over counts (closest, any-hit) and the re-trace cursor of the 4-wide walks
+enum VcmCountPlane
+{
+    VCP_LIGHT_PATHS = 0, VCP_LIGHT_SHADOWS, VCP_LIGHT_CURSORS, VCP_CAMERA_PATHS, VCP_CAMERA_SHADOWS, VCP_CAMERA_CURSORS, VCP_MERGES, VCP_LIGHT_OVERFLOW, VCP_CAMERA_OVERFLOW,
+    VCP_CONNECTS, VCP_EXACT = 10, VCP_EXACT_SHADOWS = 12, VCP_EXACT_CURSORS = 14, VCP_NUM_PLANES = 16
+};
+static uint32_t* vcmCounts(const RtgpuContext::Vcm& v, uint32_t plane) { return v.counts + plane * RT_VCM_COUNT_PLANE; }
 
 // the kernels of rt_vcm.inl that may evaluate textures exist per scene class (rt_shade_kernels.h): a scene without textures takes class 3
 // (RTGPU_VCM_CLASS=0: the generic kernels for every scene)
 #define RT_LAUNCH_VCM(K, ...) { if (vcmUntextured(c)) hipLaunchKernelGGL((K<3>), __VA_ARGS__); else hipLaunchKernelGGL((K<0>), __VA_ARGS__); }
 static bool vcmUntextured(const RtgpuContext* c)
 {
-    static const bool allow = !(getenv("RTGPU_VCM_CLASS") && atoi(getenv("RTGPU_VCM_CLASS")) == 0);
-    return allow && (c->leanScene == 1 || c->leanScene == 3);
+    return knobs::vcmClass() && (c->leanScene == 1 || c->leanScene == 3);
 }
 static void freeVcm(RtgpuContext* c)
 {
     RtgpuContext::Vcm& v = c->vcm;
-    void* ptrs[] = { v.lightPaths.base, v.cameraPaths.base, v.arena.recs, v.arena.lightVertices, v.arena.photonRaw, v.arena.lvCount, v.arena.photonCount, v.arena.cameraVertex, v.mergeQueue, v.connectQueue, v.overflowQueue, v.exactQueue, v.exactShadowQueue,
-                     v.queues[0], v.queues[1], v.queues[2], v.queues[3], v.shadowQueues[0], v.shadowQueues[1], v.shadowQueues[2], v.shadowQueues[3], v.counts,
-                     v.passDev, v.seedDev, v.devsDev, v.gridsDev };
-    for (void* p : ptrs) if (p) (void)hipFree(p);
+    devFree(v.lightPaths.base, v.cameraPaths.base, v.arena.recs, v.arena.lightVertices, v.arena.photonRaw, v.arena.lvCount, v.arena.photonCount, v.arena.cameraVertex, v.mergeQueue,
+            v.connectQueue, v.overflowQueue, v.exactQueue, v.exactShadowQueue, v.queues[0], v.queues[1], v.queues[2], v.queues[3], v.shadowQueues[0], v.shadowQueues[1],
+            v.shadowQueues[2], v.shadowQueues[3], v.counts, v.passDev, v.seedDev, v.devsDev, v.gridsDev);
     for (VcmPhotonGrid& g : v.grids) vcmFreePhotonGrid(g);
     const bool enabled = v.enabled; const RtVcmParams params = v.params; const uint32_t batch = v.batch;
     std::vector<RtgpuContext::Vcm::Pending> pending; pending.swap(v.pending);
@@ -59,7 +64,7 @@ static int ensureVcm(RtgpuContext* c, uint32_t maxLV, uint32_t batch)
     for (int k = 0; k < 4; ++k) HIP_TRY(hipMalloc((void**)&v.queues[k], cap * sizeof(uint32_t)));
     for (int k = 0; k < 2; ++k) HIP_TRY(hipMalloc((void**)&v.shadowQueues[k], cap * sizeof(uint32_t)));
     for (int k = 2; k < 4; ++k) HIP_TRY(hipMalloc((void**)&v.shadowQueues[k], cap * (size_t)(requests ? requests : 1u) * sizeof(uint32_t)));
-    HIP_TRY(hipMalloc((void**)&v.counts, (size_t)RT_VCM_NUM_COUNT_PLANES * RT_VCM_COUNT_PLANE * sizeof(uint32_t)));
+    HIP_TRY(hipMalloc((void**)&v.counts, (size_t)VCP_NUM_PLANES * RT_VCM_COUNT_PLANE * sizeof(uint32_t)));
     HIP_TRY(hipMalloc((void**)&v.passDev, (size_t)RT_VCM_MAX_BATCH * sizeof(DevPass)));
     HIP_TRY(hipMalloc((void**)&v.seedDev, (size_t)RT_VCM_MAX_BATCH * RTGPU_MAX_DIMENSIONS * sizeof(uint32_t)));
     HIP_TRY(hipMalloc((void**)&v.devsDev, (size_t)RT_VCM_MAX_BATCH * sizeof(VcmDev)));
@@ -76,31 +81,24 @@ static void launchTrace(RtgpuContext* c, hipStream_t stream, const Paths& paths,
     TravTuning tune = c->tune; tune.shadowOffset = shadowOffset;
     const bool monsters = overflowQueue && tq && !c->countIntersections && c->sceneDev.numObjects == 1u;
     tune.overflowQueue = monsters ? overflowQueue : nullptr; tune.overflowCount = monsters ? overflowCount : nullptr;
-    static const int abortEnv = getenv("RTGPU_ABORT_CLOSEST_AFTER") ? atoi(getenv("RTGPU_ABORT_CLOSEST_AFTER")) : -1;   // test hook: 0 sends every ray in flight at exhaustion
-    if (abortEnv >= 0) tune.abortClosestAfter = (uint32_t)abortEnv;
-    const uint32_t stackClass = c->traversalStackNeed <= 24 ? 24u : (c->traversalStackNeed <= 32 ? 32u : 64u);
-    dim3 travGrid(c->numCUs * (c->travBlocksPerCU ? c->travBlocksPerCU : (stackClass == 24u ? 5u : (stackClass == 32u ? 4u : 2u)))), block(RT_BLOCK);
+    if (knobs::abortClosestAfter() >= 0) tune.abortClosestAfter = (uint32_t)knobs::abortClosestAfter();   // test hook: 0 sends every ray in flight at exhaustion
+    dim3 travGrid(traversalBlocks(c, stackClassOf(c)));
     RtgpuContext::Vcm& v = c->vcm;
     // RTGPU_VCM_WIDE=1: the 4-wide walks in front of the bidirectional integrator's launches too.  Bit-exact (tests/test_gpu_vcm.py), and measured
     // 2 % SLOWER on the Sponza-class scene (16.2 -> 16.6 ms per pass): this pipeline runs on ONE stream, so nothing hides the forty extra re-trace
     // launches per pass batch, and BASELINE config 5 is three analytic objects, which the wide walk does not serve anyway.  Off by default.
-    static const bool vcmWide = getenv("RTGPU_VCM_WIDE") && atoi(getenv("RTGPU_VCM_WIDE")) != 0;
-    if (vcmWide && useWide(c) && v.exactQueue && v.traceSerial < 2u * RT_VCM_COUNT_PLANE)
+    if (knobs::vcmWide() && useWide(c) && v.exactQueue && v.traceSerial < 2u * RT_VCM_COUNT_PLANE)
     {
         // what the wide walk does not decide goes through the binary-tree kernel below, which keeps its hand-over of degenerate closest-hit rays to
         // k_trace_monster
         const uint32_t k = v.traceSerial++;
-        uint32_t* exactCount = v.counts + 10u * RT_VCM_COUNT_PLANE + k; uint32_t* exactShadowCount = v.counts + 12u * RT_VCM_COUNT_PLANE + k;
+        uint32_t* exactCount = vcmCounts(v, VCP_EXACT) + k; uint32_t* exactShadowCount = vcmCounts(v, VCP_EXACT_SHADOWS) + k;
         launchTraceWide(c, stream, c->counters, paths, tq, tqc, tsq, tsc, cursor, v.exactQueue, exactCount, v.exactShadowQueue, exactShadowCount, shadowOffset, nullptr, 0u, false);
-        tq = v.exactQueue; tqc = exactCount; tsq = v.exactShadowQueue; tsc = exactShadowCount; cursor = v.counts + 14u * RT_VCM_COUNT_PLANE + k;
+        tq = v.exactQueue; tqc = exactCount; tsq = v.exactShadowQueue; tsc = exactShadowCount; cursor = vcmCounts(v, VCP_EXACT_CURSORS) + k;
         travGrid = dim3(c->numCUs);
     }
     LaunchTimer t(c, stream, KC_TRACE);
-#define RT_VCM_TRACE(S, C) hipLaunchKernelGGL((k_trace<S, C>), travGrid, block, 0, stream, c->sceneDev, paths, tq, tqc, tsq, tsc, cursor, c->counters, tune)
-    if (stackClass == 24u) { if (c->countIntersections) RT_VCM_TRACE(24, true); else RT_VCM_TRACE(24, false); }
-    else if (stackClass == 32u) { if (c->countIntersections) RT_VCM_TRACE(32, true); else RT_VCM_TRACE(32, false); }
-    else { if (c->countIntersections) RT_VCM_TRACE(64, true); else RT_VCM_TRACE(64, false); }
-#undef RT_VCM_TRACE
+    launchTraceBinary(c, stream, travGrid, c->counters, paths, tq, tqc, tsq, tsc, cursor, tune, c->countIntersections);
     if (monsters) hipLaunchKernelGGL(k_trace_monster, dim3(64), dim3(RT_MONSTER_BLOCK), 0, stream, c->sceneDev, paths, overflowQueue, overflowCount);
 }
 
@@ -207,11 +205,11 @@ static int vcmFlush(RtgpuContext* c)
     HIP_TRY(hipStreamSynchronize(stream));   // the host vectors and the pending seeds are temporaries
     const VcmBatch batch = { v.passDev, v.devsDev, v.gridsDev, c->numSlots };
 
-    HIP_TRY(hipMemsetAsync(v.counts, 0, (size_t)RT_VCM_NUM_COUNT_PLANES * RT_VCM_COUNT_PLANE * sizeof(uint32_t), stream));
+    HIP_TRY(hipMemsetAsync(v.counts, 0, (size_t)VCP_NUM_PLANES * RT_VCM_COUNT_PLANE * sizeof(uint32_t), stream));
     v.traceSerial = 0u;
-    uint32_t* lpc = v.counts; uint32_t* lsc = v.counts + RT_VCM_COUNT_PLANE; uint32_t* lcur = v.counts + 2 * RT_VCM_COUNT_PLANE;
-    uint32_t* cpc = v.counts + 3 * RT_VCM_COUNT_PLANE; uint32_t* csc = v.counts + 4 * RT_VCM_COUNT_PLANE; uint32_t* ccur = v.counts + 5 * RT_VCM_COUNT_PLANE;
-    uint32_t* cmc = v.counts + 6 * RT_VCM_COUNT_PLANE; uint32_t* ccc = v.counts + 9 * RT_VCM_COUNT_PLANE;
+    uint32_t* lpc = vcmCounts(v, VCP_LIGHT_PATHS); uint32_t* lsc = vcmCounts(v, VCP_LIGHT_SHADOWS); uint32_t* lcur = vcmCounts(v, VCP_LIGHT_CURSORS);
+    uint32_t* cpc = vcmCounts(v, VCP_CAMERA_PATHS); uint32_t* csc = vcmCounts(v, VCP_CAMERA_SHADOWS); uint32_t* ccur = vcmCounts(v, VCP_CAMERA_CURSORS);
+    uint32_t* cmc = vcmCounts(v, VCP_MERGES); uint32_t* ccc = vcmCounts(v, VCP_CONNECTS);
     uint32_t** lq = v.queues; uint32_t** cq = v.queues + 2; uint32_t** lsq = v.shadowQueues; uint32_t** csq = v.shadowQueues + 2;
 
     const uint32_t totalSlots = c->numSlots * numPasses;
@@ -230,7 +228,7 @@ static int vcmFlush(RtgpuContext* c)
     {
         const bool haveShadow = b > 0 && vp.useVertexConnection;
         launchTrace(c, stream, v.lightPaths, lq[b & 1u], lpc + b, haveShadow ? lsq[(b - 1u) & 1u] : nullptr, haveShadow ? lsc + (b - 1u) : nullptr, lcur + b, 0.0001f,
-                    v.overflowQueue, v.counts + 7 * RT_VCM_COUNT_PLANE + b);
+                    v.overflowQueue, vcmCounts(v, VCP_LIGHT_OVERFLOW) + b);
         LaunchTimer t(c, stream, KC_SHADE);
         RT_LAUNCH_VCM(k_vcm_light_shade, grid1, block, 0, stream, c->sceneDev, batch, v.lightPaths, v.arena, lq[b & 1u], lpc + b, lq[(b + 1u) & 1u], lpc + b + 1,
                            lsq[b & 1u], lsc + b, c->sum, c->secondary, c->counters);
@@ -252,12 +250,12 @@ static int vcmFlush(RtgpuContext* c)
     bool anyPhotons = false;
     for (uint32_t j = 0; j < numPasses; ++j) anyPhotons = anyPhotons || (grids[j].numPhotons != 0u && passes[j].passIndex > 0u);
     // camera sub-paths
-    static const uint32_t mergeCooperativeMin = getenv("RTGPU_VCM_MERGE_COOP") ? (uint32_t)atoi(getenv("RTGPU_VCM_MERGE_COOP")) : RT_VCM_COOPERATIVE_MERGE_MIN;   // tuning knob
+    const uint32_t mergeCooperativeMin = knobs::vcmMergeCooperativeMin();   // tuning knob
     for (uint32_t d = 0; d < vp.maxPathLength; ++d)
     {
         const bool haveShadow = d > 0;
         launchTrace(c, stream, v.cameraPaths, cq[d & 1u], cpc + d, haveShadow ? csq[(d - 1u) & 1u] : nullptr, haveShadow ? csc + (d - 1u) : nullptr, ccur + d, 0.0001f,
-                    v.overflowQueue, v.counts + 8 * RT_VCM_COUNT_PLANE + d);
+                    v.overflowQueue, vcmCounts(v, VCP_CAMERA_OVERFLOW) + d);
         LaunchTimer t(c, stream, KC_SHADE);
         RT_LAUNCH_VCM(k_vcm_camera_shade, grid1, block, 0, stream, c->sceneDev, batch, v.cameraPaths, v.arena, cq[d & 1u], cpc + d, cq[(d + 1u) & 1u], cpc + d + 1,
                            csq[d & 1u], csc + d, v.mergeQueue, cmc + d, v.connectQueue, ccc + d, c->counters);
@@ -290,8 +288,7 @@ static int vcmRenderPass(RtgpuContext* c, const RtPassParams* p)
     {
         // passes per launch sequence: enough to keep 256 CUs busy through the tails of every bounce, bounded by the arena footprint
         // (about 2 KB per pixel and pass at path length 10)
-        static const int batchEnv = getenv("RTGPU_VCM_BATCH") ? atoi(getenv("RTGPU_VCM_BATCH")) : 0;
-        uint32_t batch = batchEnv > 0 ? (uint32_t)batchEnv : 8u;
+        uint32_t batch = knobs::vcmBatch() > 0 ? (uint32_t)knobs::vcmBatch() : 8u;
         if (batch > RT_VCM_MAX_BATCH) batch = RT_VCM_MAX_BATCH;
         const uint32_t maxLV = v.params.maxPathLength > 1u ? v.params.maxPathLength - 1u : 1u;
         const size_t perSlot = ((size_t)2 * R_NUM_BASE + RT_SHADOW_RECORDS * (1u + c->numLights + maxLV) + V_NUM + (size_t)maxLV * (RT_VCM_LV_RECORDS + 2u) + RT_VCM_LV_RECORDS) * sizeof(float4)
@@ -328,10 +325,10 @@ static int lightTracerRenderPass(RtgpuContext* c, const RtPassParams* p)
     HIP_TRY(hipMemcpyAsync(v.gridsDev, &noGrid, sizeof(noGrid), hipMemcpyHostToDevice, stream));
     HIP_TRY(hipStreamSynchronize(stream));
     const VcmBatch batch = { v.passDev, v.devsDev, v.gridsDev, c->numSlots };
-    HIP_TRY(hipMemsetAsync(v.counts, 0, (size_t)RT_VCM_NUM_COUNT_PLANES * RT_VCM_COUNT_PLANE * sizeof(uint32_t), stream));
+    HIP_TRY(hipMemsetAsync(v.counts, 0, (size_t)VCP_NUM_PLANES * RT_VCM_COUNT_PLANE * sizeof(uint32_t), stream));
     v.traceSerial = 0u;
-    uint32_t* lpc = v.counts; uint32_t* lsc = v.counts + RT_VCM_COUNT_PLANE; uint32_t* lcur = v.counts + 2 * RT_VCM_COUNT_PLANE;
-    uint32_t* cpc = v.counts + 3 * RT_VCM_COUNT_PLANE;
+    uint32_t* lpc = vcmCounts(v, VCP_LIGHT_PATHS); uint32_t* lsc = vcmCounts(v, VCP_LIGHT_SHADOWS); uint32_t* lcur = vcmCounts(v, VCP_LIGHT_CURSORS);
+    uint32_t* cpc = vcmCounts(v, VCP_CAMERA_PATHS);
     uint32_t** lq = v.queues; uint32_t** lsq = v.shadowQueues;
     const uint32_t maxBlocks = c->numCUs * 8u;
     const uint32_t blocksNeeded = (c->numSlots + RT_BLOCK - 1) / RT_BLOCK;
@@ -346,7 +343,7 @@ static int lightTracerRenderPass(RtgpuContext* c, const RtPassParams* p)
     {
         const bool haveShadow = b > 0;
         launchTrace(c, stream, v.lightPaths, lq[b & 1u], lpc + b, haveShadow ? lsq[(b - 1u) & 1u] : nullptr, haveShadow ? lsc + (b - 1u) : nullptr, lcur + b, 0.0f,
-                    v.overflowQueue, v.counts + 7 * RT_VCM_COUNT_PLANE + b);
+                    v.overflowQueue, vcmCounts(v, VCP_LIGHT_OVERFLOW) + b);
         LaunchTimer t(c, stream, KC_SHADE);
         RT_LAUNCH_VCM(k_lt_shade, grid1, block, 0, stream, c->sceneDev, batch, v.lightPaths, v.arena, lq[b & 1u], lpc + b, lq[(b + 1u) & 1u], lpc + b + 1,
                            lsq[b & 1u], lsc + b, c->sum, c->secondary, c->counters);
