@@ -150,7 +150,7 @@ static void launchTraceWide(RtgpuContext* c, hipStream_t stream, unsigned long l
     // closest-hit ray's 17), and the queue is taken front to back again: trace 47.5 -> 45.5 ms per 25 passes, +1 % at 256 passes, +2 % on a 1/8 shard
     // (profiles/r06_claim_order_ab.txt).  RTGPU_WIDE_REVERSE=1: from the end (read per launch: the tests run both orders)
     tune.reverseOrder = knobs::wideReverse();
-    // any-hit rays walk the FARTHEST child they enter first (rt_trace_wide.inl: occlusion is an OR over the candidates, and the occluders of a ray that starts on a
+    // any-hit rays walk the FARTHEST child they enter first (rt_wide_walk.h, interior step: occlusion is an OR over the candidates, and the occluders of a ray that starts on a
     // surface are far from it); RTGPU_ANYHIT_FAR_FIRST=0: nearest first like closest-hit rays (read per launch: the tests run both orders)
     tune.anyHitFarFirst = knobs::anyHitFarFirst();
     const dim3 grid(traversalBlocks(c, 24u)), block(RT_BLOCK);

@@ -43,6 +43,7 @@ __global__ void __launch_bounds__(RT_BLOCK) k_trace_packet(const RtSceneDesc sce
     const PacketConstF triangles = (PacketConstF)(uintptr_t)(scene.triangles + firstTriangle);
     const float inf = __uint_as_float(0x7f800000u);
     uint32_t numRetraced = 0, numUntrusted = 0, numOverflow = 0;
+    const WideLocal noLists = { nullptr, nullptr, nullptr, nullptr, 0u };   // what the packets do not decide goes to the launch's exact queue
 
     for (;;)
     {
@@ -52,7 +53,7 @@ __global__ void __launch_bounds__(RT_BLOCK) k_trace_packet(const RtSceneDesc sce
         if (base >= count) break;
         for (uint32_t first = base; first < base + 64u * RT_PACKET_CLAIM && first < count; first += 64u)
         {
-            // ---- the packet's rays: k_trace_wide's refill for closest-hit rays, word for word ----
+            // ---- the packet's rays: k_trace_wide's refill for closest-hit rays (the same parts of rt_wide_walk.h) ----
             const uint32_t idx = first + lane;
             const bool valid = idx < count;
             uint32_t slot = 0u;
@@ -63,15 +64,9 @@ __global__ void __launch_bounds__(RT_BLOCK) k_trace_packet(const RtSceneDesc sce
             {
                 slot = denseLiveSlot(sDensePrefix, tune.denseShardCapacity, idx);
                 const float4 origin = ldStream(prec(paths, R_ORIGIN, slot)), dir = ldStream(prec(paths, R_DIR, slot));
-                Ray world = makeRay(V4(origin.x, origin.y, origin.z, 0.0f), V4(dir.x, dir.y, dir.z, 0.0f));
-                if ((ubits(origin.w) & 0xFFu) != 0u) world.origin = world.origin + world.dir * 0.001f;
+                const Ray world = wideWorldRay(origin, dir, false, 0.0f);
                 const Ray local = makeRayUnsafe3(transformPoint(invTransform, world.origin), transformVector(invTransform, world.dir));
-                const float mx = fabsf(local.originDivDir.x) + bvh.bound[0] * fabsf(local.invDir.x);
-                const float my = fabsf(local.originDivDir.y) + bvh.bound[1] * fabsf(local.invDir.y);
-                const float mz = fabsf(local.originDivDir.z) + bvh.bound[2] * fabsf(local.invDir.z);
-                const float fold = 4.76837158203125e-07f;   // 2^-21
-                const bool trusted = rayIsNaNFree(local) &&
-                                     mx * fold < bvh.step[0] * fabsf(local.invDir.x) && my * fold < bvh.step[1] * fabsf(local.invDir.y) && mz * fold < bvh.step[2] * fabsf(local.invDir.z);
+                RT_WIDE_FOLD_TEST(local, bvh)
                 if (!trusted)
                 {
                     tune.exactQueue[atomicAdd(tune.exactCount, 1u)] = slot;
@@ -80,11 +75,8 @@ __global__ void __launch_bounds__(RT_BLOCK) k_trace_packet(const RtSceneDesc sce
                 else
                 {
                     ox = local.origin.x; oy = local.origin.y; oz = local.origin.z; dx = local.dir.x; dy = local.dir.y; dz = local.dir.z;
-                    ax = bvh.step[0] * local.invDir.x; ay = bvh.step[1] * local.invDir.y; az = bvh.step[2] * local.invDir.z;
-                    bx = __fmaf_rn(bvh.base[0], local.invDir.x, -local.originDivDir.x);
-                    by = __fmaf_rn(bvh.base[1], local.invDir.y, -local.originDivDir.y);
-                    bz = __fmaf_rn(bvh.base[2], local.invDir.z, -local.originDivDir.z);
-                    tol = fmaxf(fmaxf(mx, my), mz) * 1.9073486328125e-06f;   // 2^-19: 16 ulps
+                    RT_WIDE_FOLD_SET(local, bvh)
+                    tol = RT_WIDE_FOLD_TOL;
                     act = true;
                 }
             }
@@ -154,19 +146,7 @@ __global__ void __launch_bounds__(RT_BLOCK) k_trace_packet(const RtSceneDesc sce
                             float nearD;
                             const bool pass = intersectBoxRayNoNaN(gateRay, __uint_as_float(gmin.x), __uint_as_float(gmin.y), __uint_as_float(gmin.z),
                                                                    __uint_as_float(gmax.x), __uint_as_float(gmax.y), __uint_as_float(gmax.z), nearD);
-                            if (candidate && pass)
-                            {
-                                const float hi = fmaxf(t0, t1);
-                                if (lo < best)
-                                {
-                                    second = fminf(best, hi);
-                                    best = lo;
-                                    const bool firstWins = t0 <= t1;   // HitPoint written through (an exact tie is retraced anyway)
-                                    prec(paths, R_HIT, slot) = f4(fbits(0u), fbits(firstTri + (firstWins ? 0u : 1u)), lo, firstWins ? u0 : u1);
-                                    prec(paths, R_SAMPLER, slot).x = firstWins ? v0_ : v1;
-                                }
-                                else second = fminf(second, lo);
-                            }
+                            if (candidate && pass) wideAcceptPair(paths, slot, 0u, firstTri, t0, u0, v0_, t1, u1, v1, lo, best, second);
                         }
                     }
                     // (else: an unused child slot whose corner point a ray happened to meet)
@@ -179,21 +159,10 @@ __global__ void __launch_bounds__(RT_BLOCK) k_trace_packet(const RtSceneDesc sce
                 }
             }
             // ---- finished ----
-            if (act)
-            {
-                if (overflow) { tune.exactQueue[atomicAdd(tune.exactCount, 1u)] = slot; numRetraced++; numOverflow++; }
-                else if (best == inf) prec(paths, R_HIT, slot) = f4(fbits(RT_INVALID_OBJECT), fbits(0u), inf, 0.0f);   // HitPoint.h:14-51
-                else if (second <= best + tol) { tune.exactQueue[atomicAdd(tune.exactCount, 1u)] = slot; numRetraced++; }   // a runner-up too close to call
-            }
+            if (act && wideFinishRay(paths, tune, noLists, false, 0u, slot, overflow, false, best, second, tol)) { numRetraced++; if (overflow) numOverflow++; }
         }
     }
-    if (numRetraced) atomicAdd(&sTally[1], numRetraced);
-    if (numUntrusted) atomicAdd(&sTally[2], numUntrusted);
-    if (numOverflow) atomicAdd(&sTally[3], numOverflow);
-    __syncthreads();
-    if (threadIdx.x == 1u && sTally[1]) atomicAdd(&counters[RT_COUNTER_RETRACED], (unsigned long long)sTally[1]);
-    if (threadIdx.x == 2u && sTally[2]) atomicAdd(&counters[RT_COUNTER_RETRACED + 1], (unsigned long long)sTally[2]);
-    if (threadIdx.x == 3u && sTally[3]) atomicAdd(&counters[RT_COUNTER_RETRACED + 2], (unsigned long long)sTally[3]);
+    wideFlushTallies<14u>(sTally, true, true, 0u, numRetraced, numUntrusted, numOverflow, true, counters);   // tallies per LANE (every lane adds), sTally cleared above; no any-hit rays here
 }
 #undef RT_PACKET_CE
 #endif   // RT_DEVICE_KERNELS

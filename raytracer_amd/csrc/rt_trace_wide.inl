@@ -1,6 +1,7 @@
 // rt_trace_wide.inl -- traversal of single-mesh scenes over a 4-WIDE tree collapsed from the reference's binary tree (same SAH splits,
 // same leaves), one ray per lane.  Included by rt_trace.hip (kernels: RT_DEVICE_KERNELS) and rt_runtime.hip (tree builders: RT_HOST_BUILDERS) after rt_wide_grid.inl, whose grid, leaf gates and exactness argument it
-// shares.
+// shares; the device parts it has in common with the other 4-wide walks (slab test, hand-over lists, request ray, fold, interior step, mesh leaf, finish, tallies) are
+// rt_wide_walk.h.
 //
 // Why.  k_trace waits ~0.8 us per dependent node fetch with 20 waves per CU to hide it: the walk is a chain of ~29 round
 // trips per ray.  Two earlier attempts changed what a round trip moves -- half the bytes (k_trace_quant: no gain, the conversions ate
@@ -31,64 +32,7 @@ struct WideBvh
     float base[3], step[3], bound[3];
 };
 
-struct WideTuning
-{
-    uint32_t refillMinIdle, otherMinLanes;
-    float shadowOffset;
-    uint32_t* exactQueue; uint32_t* exactCount;               // closest-hit rays handed to the binary-tree kernel
-    uint32_t* exactShadowQueue; uint32_t* exactShadowCount;   // any-hit requests handed to it
-    const uint32_t* denseCounts; uint32_t denseShardCapacity; // dense path state (TravTuning)
-    uint32_t chunkMin;                                        // smallest piece of the work queue a wave claims at once
-    uint32_t localExact;                                      // != 0: a block traces the rays its walk does not decide itself (k_trace_wide; RTGPU_LOCAL_EXACT=0: off)
-    uint32_t drainAbortAfter;                                 // != 0: a wave whose work queue ran dry this many loop iterations ago hands the rays it still walks to the binary-tree kernel
-    uint32_t reverseOrder;                                    // != 0: the queue is taken from its end (any-hit requests first, closest-hit rays last); 0 (default since round 6): front to back -- the launch's drain is then made of the any-hit rays, the short ones under the far-first order
-    uint32_t anyHitFarFirst;                                  // != 0: an any-hit ray walks the FARTHEST child it enters next (round 6; RTGPU_ANYHIT_FAR_FIRST=0: nearest, as closest-hit rays do)
-};
-
 #ifdef RT_DEVICE_KERNELS
-// slab test of one child record against the ray's folded constants; near is clamped to >= 0 (its bits then order like the float).
-// Which of an axis's two planes the ray meets first is a property of the RAY (the sign of its direction), so three byte permutes with
-// per-ray selectors (v_perm_b32) put {near plane, far plane} of every axis into one word and the six min / max of the textbook slab
-// test disappear: 3 perm + 6 cvt (sub-word select) + 6 fma + max + max3 + min3 per child.
-// Record words: w0 = minx | miny << 16, w1 = minz | maxx << 16, w2 = maxy | maxz << 16.  __builtin_amdgcn_perm(hi, lo, sel): byte i of
-// the result is byte sel[i] of {lo = bytes 0-3, hi = bytes 4-7}.
-#define RT_WIDE_SEL_X_POS 0x07060100u   // perm(w1, w0): minx (bytes 0,1) first, maxx (bytes 6,7) second
-#define RT_WIDE_SEL_X_NEG 0x01000706u
-#define RT_WIDE_SEL_Y_POS 0x05040302u   // perm(w2, w0): miny (bytes 2,3) first, maxy (bytes 4,5) second
-#define RT_WIDE_SEL_Y_NEG 0x03020504u
-#define RT_WIDE_SEL_Z_POS 0x07060100u   // perm(w2, w1): minz (bytes 0,1) first, maxz (bytes 6,7) second
-#define RT_WIDE_SEL_Z_NEG 0x01000706u
-#define RT_WIDE_SLAB(q, nearOut, farOut)                                                                                                          \
-    {                                                                                                                                             \
-        const uint32_t w0 = ubits(q.x), w1 = ubits(q.y), w2 = ubits(q.z);                                                                         \
-        const uint32_t px = __builtin_amdgcn_perm(w1, w0, selX), py = __builtin_amdgcn_perm(w2, w0, selY), pz = __builtin_amdgcn_perm(w2, w1, selZ); \
-        const float nx = __fmaf_rn((float)(px & 0xFFFFu), ax, bx), ny = __fmaf_rn((float)(py & 0xFFFFu), ay, by), nz = __fmaf_rn((float)(pz & 0xFFFFu), az, bz); \
-        const float xx = __fmaf_rn((float)(px >> 16), ax, bx), xy = __fmaf_rn((float)(py >> 16), ay, by), xz = __fmaf_rn((float)(pz >> 16), az, bz);            \
-        nearOut = fmaxf(fmaxf(nx, ny), fmaxf(nz, 0.0f));                                                                                           \
-        farOut = fminf(fminf(xx, xy), xz);                                                                                                        \
-    }
-#define RT_WIDE_IS_LEAF(ref) ((((ref) >> RT_NODE_LEAVES_SHIFT) - 1u) < 2u)   // one or two triangles; not an interior node (0), not RT_WIDE_EMPTY / RT_QUANT_DONE (3)
-
-// The block's own list of the rays its walk does not decide (LDS): they are traced by the reference's walk (traceBinaryLoop) in the same launch
-// when the block's 4-wide walk is done, instead of by a launch of their own behind this one (ten launches of 70 ... 1600 us per batch for 0.1 %
-// of the rays, profiles/r03_timeline_serial_start_of_round.txt).  What does not fit the list goes to the launch's queues as before.
-struct WideLocal
-{
-    uint32_t* exact; uint32_t* exactCount;       // closest-hit rays (path slots)
-    uint32_t* shadow; uint32_t* shadowCount;     // any-hit requests (light * capacity + slot)
-    uint32_t capacity;                           // entries per list; 0: no local lists
-};
-RT_DEV void widePushExact(const WideTuning& tune, const WideLocal& local, bool shadowRequest, uint32_t request)
-{
-    if (local.capacity != 0u)
-    {
-        const uint32_t i = atomicAdd(shadowRequest ? local.shadowCount : local.exactCount, 1u);   // (the consumer clamps the count to the capacity)
-        if (i < local.capacity) { (shadowRequest ? local.shadow : local.exact)[i] = request; return; }
-    }
-    if (tune.exactQueue == nullptr) return;   // k_tail: its lists hold every request a chunk can produce (rt_tail.hip states the invariant)
-    if (shadowRequest) tune.exactShadowQueue[atomicAdd(tune.exactShadowCount, 1u)] = request;
-    else tune.exactQueue[atomicAdd(tune.exactCount, 1u)] = request;
-}
 #define RT_WIDE_STACK 16           // stack entries per lane of the 4-wide walk
 #define RT_WIDE_PARK 6u            // words per lane behind the stack (traceWideLoop's `park`)
 #define RT_WIDE_LOCAL_EXACT 256u   // per block and kind: ~40 x what a block of the benchmark hands over per launch
@@ -163,10 +107,7 @@ RT_DEV void traceWideLoop(const RtSceneDesc& scene, const WideBvh& bvh, const Pa
                 shadow = idx >= numClosest;
                 const uint32_t request = shadow ? shadowQueue[idx - numClosest]
                                                 : (tune.denseCounts ? denseLiveSlot(sDensePrefix, tune.denseShardCapacity, idx) : (queue ? queue[idx] : idx));
-                // one ray construction for both kinds of request (a wave usually refills both at once): Ray::Ray normalises the direction
-                // (PathTracerMIS.cpp:86 / :392), then the origin moves along it -- 1e-4 for an any-hit ray, 1e-3 for a bounce, not at all for
-                // a primary ray
-                float maxDistance = inf, offset;
+                float maxDistance = inf;
                 float4 origin, dir;
                 if (shadow)
                 {
@@ -174,26 +115,17 @@ RT_DEV void traceWideLoop(const RtSceneDesc& scene, const WideBvh& bvh, const Pa
                     if (paths.maxLights == 1u) { light = 0u; slot = request; } else { light = request / paths.capacity; slot = request - light * paths.capacity; }
                     origin = ldStream(prec(paths, R_SH_P, slot)); dir = ldStream(pshadow(paths, light, 0, slot));
                     maxDistance = dir.w;           // hitPoint.distance = illuminateResult.distance * 0.999f
-                    offset = tune.shadowOffset;
                 }
                 else
                 {
                     slot = request; light = 0u;
                     origin = ldStream(prec(paths, R_ORIGIN, slot)); dir = ldStream(prec(paths, R_DIR, slot));
-                    offset = 0.001f;
                 }
-                Ray world = makeRay(V4(origin.x, origin.y, origin.z, 0.0f), V4(dir.x, dir.y, dir.z, 0.0f));
-                if (shadow || (ubits(origin.w) & 0xFFu) != 0u) world.origin = world.origin + world.dir * offset;
+                const Ray world = wideWorldRay(origin, dir, shadow, tune.shadowOffset);   // one ray construction for both kinds of request (a wave usually refills both at once)
                 M4 invTransform;
                 for (int r = 0; r < 4; ++r) invTransform.r[r] = V4(invTransformWords[4 * r], invTransformWords[4 * r + 1], invTransformWords[4 * r + 2], invTransformWords[4 * r + 3]);
                 const Ray local = makeRayUnsafe3(transformPoint(invTransform, world.origin), transformVector(invTransform, world.dir));   // = transformRayUnsafe: MeshShape is entered in object space, Scene.cpp:128-145
-                // largest magnitude a slab test of this ray can produce, per axis; 2^-21 of it bounds the folded test's rounding
-                const float mx = fabsf(local.originDivDir.x) + bvh.bound[0] * fabsf(local.invDir.x);
-                const float my = fabsf(local.originDivDir.y) + bvh.bound[1] * fabsf(local.invDir.y);
-                const float mz = fabsf(local.originDivDir.z) + bvh.bound[2] * fabsf(local.invDir.z);
-                const float fold = 4.76837158203125e-07f;   // 2^-21
-                const bool trusted = rayIsNaNFree(local) &&
-                                     mx * fold < bvh.step[0] * fabsf(local.invDir.x) && my * fold < bvh.step[1] * fabsf(local.invDir.y) && mz * fold < bvh.step[2] * fabsf(local.invDir.z);
+                RT_WIDE_FOLD_TEST(local, bvh)
                 if (!trusted)
                 {
                     // a zero direction component (NaNs in the reference's slab test) or an origin far outside the mesh: the reference's walk only
@@ -203,13 +135,10 @@ RT_DEV void traceWideLoop(const RtSceneDesc& scene, const WideBvh& bvh, const Pa
                 else
                 {
                     ox = local.origin.x; oy = local.origin.y; oz = local.origin.z; dx = local.dir.x; dy = local.dir.y; dz = local.dir.z;
-                    ax = bvh.step[0] * local.invDir.x; ay = bvh.step[1] * local.invDir.y; az = bvh.step[2] * local.invDir.z;
-                    bx = __fmaf_rn(bvh.base[0], local.invDir.x, -local.originDivDir.x);
-                    by = __fmaf_rn(bvh.base[1], local.invDir.y, -local.originDivDir.y);
-                    bz = __fmaf_rn(bvh.base[2], local.invDir.z, -local.originDivDir.z);
+                    RT_WIDE_FOLD_SET(local, bvh)
                     park[0] = local.invDir.x; park[RT_BLOCK] = local.invDir.y; park[2 * RT_BLOCK] = local.invDir.z;
                     park[3 * RT_BLOCK] = local.originDivDir.x; park[4 * RT_BLOCK] = local.originDivDir.y; park[5 * RT_BLOCK] = local.originDivDir.z;
-                    tol = shadow ? 0.0f : fmaxf(fmaxf(mx, my), mz) * 1.9073486328125e-06f;   // 2^-19: 16 ulps
+                    tol = shadow ? 0.0f : RT_WIDE_FOLD_TOL;
                     best = maxDistance; second = inf; occluded = false; overflow = false;
                     sp = 0u; cur = 0u;   // node 0 holds the children of the binary tree's root
                     if (kDiag) diagMaxSp = 0u;
@@ -226,47 +155,16 @@ RT_DEV void traceWideLoop(const RtSceneDesc& scene, const WideBvh& bvh, const Pa
             // ---- interior phase: four conservative slab tests per step, until enough lanes wait at a leaf or are finished ----
             if (kDiag) { diagPhase = 1u; diagRuns[1]++; }
             bool in = interior;
-            const float limit = best + (tol + tol);   // box occlusion with the slack that keeps every candidate within tol of the final hit in the walk
+            const float limit = best + (tol + tol);
             // which plane of an axis the ray meets first: byte selectors of the slab test, rebuilt per phase (three registers less across the leaf and refill phases)
             const uint32_t selX = ax < 0.0f ? RT_WIDE_SEL_X_NEG : RT_WIDE_SEL_X_POS, selY = ay < 0.0f ? RT_WIDE_SEL_Y_NEG : RT_WIDE_SEL_Y_POS, selZ = az < 0.0f ? RT_WIDE_SEL_Z_NEG : RT_WIDE_SEL_Z_POS;
-            // Visiting order (round 6).  A closest-hit ray walks its NEAREST entered child next (hits shorten it).  An any-hit ray has nothing to shorten -- it ends
-            // with the first occluder, wherever that lies -- and nearest-first is the worst order for it: a next-event ray starts ON a surface, so the nearest
-            // boxes hold that surface's neighbours, which never occlude it.  FARTHEST child first finds the walls and roofs that do: the step model over the
-            // benchmark's rays (tools/wide8/walk_model.cpp, profiles/r06_wide8_step_model.txt) gives 9.9 interior + 1.5 leaf visits per any-hit ray instead of
-            // 16.0 + 2.6.  Occlusion is an OR over the same candidates: the result does not depend on the order.  Same instruction count: the sort key
-            // 0x7FFFFFFF - bits(entry) = 0x7FFFFFFF ^ bits(entry) (entry >= 0: no borrow), and an any-hit lane xors with 0 instead.
-            // (The flip is rebuilt in every iteration from `tol`, which is zero for any-hit rays only, behind an optimisation barrier: as a loop-invariant value
-            //  it would be one more vector register live across the loop -- the 97th: 20 bytes of scratch -- for three instructions per visit saved.)
             for (;;)
             {
                 if (kDiag) { diagSlots++; if (in) diagVisits++; }
                 if (in)
                 {
-                    const float4* p = bvh.nodes + 4u * cur;
-                    const float4 q0 = p[0], q1 = p[1], q2 = p[2], q3 = p[3];
-                    float n0, f0, n1, f1, n2, f2, n3, f3;
-                    RT_WIDE_SLAB(q0, n0, f0); RT_WIDE_SLAB(q1, n1, f1); RT_WIDE_SLAB(q2, n2, f2); RT_WIDE_SLAB(q3, n3, f3);
-                        // (key, reference) pairs sorted so that the children the ray enters come first -- farthest first for a closest-hit ray, nearest
-                        // first for an any-hit ray: the LAST entered one is walked next -- and the ones it misses last: key = orderFlip ^ bits(entry
-                        // distance) (the distance is >= 0, so its bits order like the float), miss = all ones
-                        const bool h0 = f0 >= n0 && n0 < limit, h1 = f1 >= n1 && n1 < limit, h2 = f2 >= n2 && n2 < limit, h3 = f3 >= n3 && n3 < limit;
-                        float tolNow = tol;
-                        asm volatile("" : "+v"(tolNow));
-                        const uint32_t orderFlip = (tolNow == 0.0f && tune.anyHitFarFirst != 0u) ? 0u : 0x7FFFFFFFu;
-                        uint32_t k0 = h0 ? orderFlip ^ ubits(n0) : 0xFFFFFFFFu, k1 = h1 ? orderFlip ^ ubits(n1) : 0xFFFFFFFFu;
-                        uint32_t k2 = h2 ? orderFlip ^ ubits(n2) : 0xFFFFFFFFu, k3 = h3 ? orderFlip ^ ubits(n3) : 0xFFFFFFFFu;
-                        uint32_t r0 = ubits(q0.w), r1 = ubits(q1.w), r2 = ubits(q2.w), r3 = ubits(q3.w);
-#define RT_WIDE_CE(ka, ra, kb, rb) { const bool c_ = ka > kb; const uint32_t lo_ = min(ka, kb), hi_ = max(ka, kb), rl_ = c_ ? rb : ra, rh_ = c_ ? ra : rb; ka = lo_; kb = hi_; ra = rl_; rb = rh_; }
-                        RT_WIDE_CE(k0, r0, k1, r1) RT_WIDE_CE(k2, r2, k3, r3) RT_WIDE_CE(k0, r0, k2, r2) RT_WIDE_CE(k1, r1, k3, r3) RT_WIDE_CE(k1, r1, k2, r2)
-#undef RT_WIDE_CE
-                        const uint32_t numHit = (h0 ? 1u : 0u) + (h1 ? 1u : 0u) + (h2 ? 1u : 0u) + (h3 ? 1u : 0u);
-                        // the first numHit - 1 references are deferred, the last one (the nearest child) is walked next.  The three stores are
-                        // unconditional (what lands above the new top is free space; the overflow check keeps three entries in reserve)
-                        uint32_t* const top = stack + sp * RT_BLOCK;
-                        top[0] = r0; top[RT_BLOCK] = r1; top[2 * RT_BLOCK] = r2;
-                        if (numHit != 0u) { cur = numHit == 1u ? r0 : (numHit == 2u ? r1 : (numHit == 3u ? r2 : r3)); sp += numHit - 1u; }
-                        else if (sp == 0u) cur = RT_QUANT_DONE;
-                        else { --sp; cur = stack[sp * RT_BLOCK]; }
+                    const WideStep next = wideInteriorStep(bvh.nodes + 4u * cur, stack, 0u, sp, ax, ay, az, bx, by, bz, selX, selY, selZ, limit, tol, tune);
+                    cur = next.cur; sp = next.sp;
                     if (kDiag && sp > diagMaxSp) diagMaxSp = sp;
                     if (sp + 3u > (uint32_t)kStack) { overflow = true; cur = RT_QUANT_DONE; }   // the next step could not push: the binary-tree kernel takes the ray
                 }
@@ -287,42 +185,26 @@ RT_DEV void traceWideLoop(const RtSceneDesc& scene, const WideBvh& bvh, const Pa
                 const uint32_t leaf = cur;
                 if (!RT_WIDE_IS_LEAF(leaf) || occluded) continue;
                 if (kDiag) diagLeaves++;
-                const uint32_t numLeaves = leaf >> RT_NODE_LEAVES_SHIFT, first = leaf & RT_NODE_CHILD_MASK;
+                const uint32_t first = leaf & RT_NODE_CHILD_MASK;
                 Ray ray; ray.origin = V4(ox, oy, oz, 0.0f); ray.dir = V4(dx, dy, dz, 0.0f);
-                V4 v0, e1, e2, nv0, ne1, ne2;
-                loadTriangle(tris + first, v0, e1, e2);
-                loadTriangle(tris + first + (numLeaves > 1u ? 1u : 0u), nv0, ne1, ne2);   // the second triangle of the leaf rides in the same round trip
-                float u0, v0_, t0, u1 = 0.0f, v1 = 0.0f, t1 = inf;
-                if (!intersectTriangleRay(ray, v0, e1, e2, u0, v0_, t0)) t0 = inf;
-                if (numLeaves > 1u && !intersectTriangleRay(ray, nv0, ne1, ne2, u1, v1, t1)) t1 = inf;
-                const float lo = fminf(t0, t1);
+                float u0, v0_, t0, u1, v1, t1;
+                const float lo = wideLeafPair(tris, leaf, ray, t0, u0, v0_, t1, u1, v1);
                 if (lo < best + tol)
                 {
                     // a hit that matters: it counts only if the ray passes the leaf's exact box, as in the reference's walk
-                    const float4 gmin = bvh.gate[2u * first], gmax = bvh.gate[2u * first + 1u];
                     if (kDiag) diagGates++;
                     Ray gateRay;   // = the ray transformRayUnsafe built at refill (makeRayUnsafe3 of the same origin and direction: its quotients were parked then)
                     gateRay.origin = ray.origin; gateRay.dir = ray.dir;
                     gateRay.invDir = V4(park[0], park[RT_BLOCK], park[2 * RT_BLOCK], 0.0f);
                     gateRay.originDivDir = V4(park[3 * RT_BLOCK], park[4 * RT_BLOCK], park[5 * RT_BLOCK], 0.0f);
-                    float nearD;
-                    const bool pass = intersectBoxRayNoNaN(gateRay, gmin.x, gmin.y, gmin.z, gmax.x, gmax.y, gmax.z, nearD) && (!shadow || nearD < best);
+                    const bool pass = wideLeafGate(bvh.gate, first, gateRay, shadow, best);
                     if (pass)
                     {
                         if (shadow) { if (lo < best) occluded = true; }
                         else
                         {
-                            const float hi = fmaxf(t0, t1);
-                            if (lo < best)
-                            {
-                                second = fminf(best, hi);
-                                best = lo;
-                                const bool firstWins = t0 <= t1;   // HitPoint written through (an exact tie is retraced anyway)
-                                prec(paths, R_HIT, slot) = f4(fbits(0u), fbits(first + (firstWins ? 0u : 1u)), lo, firstWins ? u0 : u1);
-                                prec(paths, R_SAMPLER, slot).x = firstWins ? v0_ : v1;
-                                if (kDiag) diagHitWrites++;
-                            }
-                            else second = fminf(second, lo);
+                            const bool wrote = wideAcceptPair(paths, slot, 0u, first, t0, u0, v0_, t1, u1, v1, lo, best, second);
+                            if (kDiag && wrote) diagHitWrites++;
                         }
                     }
                 }
@@ -337,22 +219,9 @@ RT_DEV void traceWideLoop(const RtSceneDesc& scene, const WideBvh& bvh, const Pa
             {
                 // ---- finished ----
                 if (kDiag) { if (diagMaxSp > 9u) diagDeep[0]++; if (diagMaxSp > 13u) diagDeep[1]++; if (diagMaxSp > 17u) diagDeep[2]++; }
-                if (overflow)
-                {
-                    widePushExact(tune, handOver, shadow, shadow ? light * paths.capacity + slot : slot);
-                    handedOver = true; overflowed = true;
-                    uncountShadow = shadow;   // counted by the kernel that resolves it
-                }
-                else if (shadow)
-                {
-                    if (occluded) pshadow(paths, light, 0, slot).w = -1.0f;   // unoccluded requests are tallied when they are resolved
-                }
-                else if (best == inf) prec(paths, R_HIT, slot) = f4(fbits(RT_INVALID_OBJECT), fbits(0u), inf, 0.0f);   // HitPoint.h:14-51
-                else if (second <= best + tol)
-                {
-                    widePushExact(tune, handOver, false, slot);   // a runner-up too close to call: the reference's own walk decides
-                    handedOver = true;
-                }
+                handedOver = wideFinishRay(paths, tune, handOver, shadow, light, slot, overflow, occluded, best, second, tol);
+                overflowed = overflow;
+                uncountShadow = overflow && shadow;   // counted by the kernel that resolves it
                 have = false;
             }
         }
@@ -361,24 +230,9 @@ RT_DEV void traceWideLoop(const RtSceneDesc& scene, const WideBvh& bvh, const Pa
     }
     // counters: shadow rays traced here, rays handed to the binary-tree kernel
     __shared__ uint32_t sTally[4];
-    if (threadIdx.x < 4u) sTally[threadIdx.x] = 0u;
-    __syncthreads();
-    if ((threadIdx.x & 63u) == 0u)
-    {
-        if (numShadowRays) atomicAdd(&sTally[0], numShadowRays);
-        if (numRetraced) atomicAdd(&sTally[1], numRetraced);
-        if (numUntrusted) atomicAdd(&sTally[2], numUntrusted);
-        if (numOverflow) atomicAdd(&sTally[3], numOverflow);
-    }
-    __syncthreads();
-    if (threadIdx.x == 0u && sTally[0]) atomicAdd(&counters[C_SHADOW], (unsigned long long)sTally[0]);
-    if (threadIdx.x == 1u && sTally[1]) atomicAdd(&counters[RT_COUNTER_RETRACED], (unsigned long long)sTally[1]);
-    if (!kDiag)
-    {
-        if (threadIdx.x == 2u && sTally[2]) atomicAdd(&counters[RT_COUNTER_RETRACED + 1], (unsigned long long)sTally[2]);   // diagnostics: untrusted at refill ...
-        if (threadIdx.x == 3u && sTally[3]) atomicAdd(&counters[RT_COUNTER_RETRACED + 2], (unsigned long long)sTally[3]);   // ... and stack overflows
-    }
-    else
+    // tallies per wave (lane 0 of each adds), sTally not yet cleared; the diagnostic instantiation keeps the two spare counters for its own use below
+    wideFlushTallies<15u>(sTally, false, (threadIdx.x & 63u) == 0u, numShadowRays, numRetraced, numUntrusted, numOverflow, !kDiag, counters);
+    if (kDiag)
     {
         // RTGPU_WIDE_DIAG=1: the three spare counters hold the walk's statistics instead
         const bool deep = tune.localExact == 2u, bytes = tune.localExact == 3u;   // (the diagnostic kernel has no block-local lists: the field carries RTGPU_WIDE_DIAG's mode)

@@ -1,7 +1,7 @@
 // rt_trace_wide2.inl -- the 4-wide walk for TWO-LEVEL scenes (Scene::Traverse over the top-level BVH of the objects, Scene.cpp:219-261, into
 // MeshShape::Traverse for mesh objects, Traverse_Object / Traverse_Object_Shadow for analytic shapes and light objects): a 4-wide collapse
 // of the reference's top-level tree over 4-wide collapses of its mesh trees.  Included by rt_trace.hip (kernels: RT_DEVICE_KERNELS) and rt_runtime.hip (tree builders: RT_HOST_BUILDERS) after rt_trace_wide.inl, whose node
-// format, slab test, sorting network and exactness argument it shares; what is new here is only the second level.
+// format and exactness argument it shares (their device parts: rt_wide_walk.h); what is new here is only the second level.
 //
 // Why.  Round 2's k_trace_wide serves scenes with ONE mesh object; the Cornell box (ten analytic instances), a Sponza with props, every
 // scene with an area light fell back to the binary walk of k_trace.
@@ -51,7 +51,7 @@ __global__ void __launch_bounds__(RT_BLOCK) __attribute__((amdgpu_waves_per_eu(k
     __shared__ uint32_t sStack[kStack * RT_BLOCK];
     __shared__ float sWorld[RT_WIDE2_WORLD_WORDS * RT_BLOCK];
     __shared__ uint32_t sDensePrefix[RT_DENSE_SHARDS + 1u];
-    // the block's own hand-over lists (rt_trace_wide.inl, WideLocal): 64 entries per kind keep five blocks of 30.7 KB on a CU
+    // the block's own hand-over lists (rt_wide_walk.h, WideLocal): 64 entries per kind keep five blocks of 30.7 KB on a CU
     __shared__ uint32_t sLocalExact[RT_WIDE2_LOCAL_EXACT], sLocalShadow[RT_WIDE2_LOCAL_EXACT], sLocalCounts[4];
     if (threadIdx.x < 4u) sLocalCounts[threadIdx.x] = 0u;
     __syncthreads();
@@ -82,28 +82,21 @@ __global__ void __launch_bounds__(RT_BLOCK) __attribute__((amdgpu_waves_per_eu(k
     // along the direction and originDivDir stays what it was)
     auto loadWorldRay = [&]() -> Ray
     {
-        float4 origin, dir; float offset;
-        if (shadow) { origin = ldStream(prec(paths, R_SH_P, slot)); dir = ldStream(pshadow(paths, light, 0, slot)); offset = tune.shadowOffset; }
-        else { origin = ldStream(prec(paths, R_ORIGIN, slot)); dir = ldStream(prec(paths, R_DIR, slot)); offset = 0.001f; }
-        Ray world = makeRay(V4(origin.x, origin.y, origin.z, 0.0f), V4(dir.x, dir.y, dir.z, 0.0f));
-        if (shadow || (ubits(origin.w) & 0xFFu) != 0u) world.origin = world.origin + world.dir * offset;
+        float4 origin, dir;
+        if (shadow) { origin = ldStream(prec(paths, R_SH_P, slot)); dir = ldStream(pshadow(paths, light, 0, slot)); }
+        else { origin = ldStream(prec(paths, R_ORIGIN, slot)); dir = ldStream(prec(paths, R_DIR, slot)); }
+        const Ray world = wideWorldRay(origin, dir, shadow, tune.shadowOffset);
         return world;
     };
     // folded slab constants of `ray` on the grid of `level`; false: the reference's walk only (NaNs in its slab test, or the folded test's rounding
     // could eat the spare grid step).  Raises tol to 16 ulps of the largest slab term of this level.
     auto enterLevel = [&](const Ray& ray, const WideLevel& level) -> bool
     {
-        const float mx = fabsf(ray.originDivDir.x) + level.bound[0] * fabsf(ray.invDir.x);
-        const float my = fabsf(ray.originDivDir.y) + level.bound[1] * fabsf(ray.invDir.y);
-        const float mz = fabsf(ray.originDivDir.z) + level.bound[2] * fabsf(ray.invDir.z);
-        const float fold = 4.76837158203125e-07f;   // 2^-21
-        if (!(rayIsNaNFree(ray) && mx * fold < level.step[0] * fabsf(ray.invDir.x) && my * fold < level.step[1] * fabsf(ray.invDir.y) && mz * fold < level.step[2] * fabsf(ray.invDir.z))) return false;
+        RT_WIDE_FOLD_TEST(ray, level)
+        if (!trusted) return false;
         ox = ray.origin.x; oy = ray.origin.y; oz = ray.origin.z; dx = ray.dir.x; dy = ray.dir.y; dz = ray.dir.z;
-        ax = level.step[0] * ray.invDir.x; ay = level.step[1] * ray.invDir.y; az = level.step[2] * ray.invDir.z;
-        bx = __fmaf_rn(level.base[0], ray.invDir.x, -ray.originDivDir.x);
-        by = __fmaf_rn(level.base[1], ray.invDir.y, -ray.originDivDir.y);
-        bz = __fmaf_rn(level.base[2], ray.invDir.z, -ray.originDivDir.z);
-        if (!shadow) tol = fmaxf(tol, fmaxf(fmaxf(mx, my), mz) * 1.9073486328125e-06f);   // 2^-19
+        RT_WIDE_FOLD_SET(ray, level)
+        if (!shadow) tol = fmaxf(tol, RT_WIDE_FOLD_TOL);
         nodeBase = level.nodeBase;
         return true;
     };
@@ -173,27 +166,8 @@ __global__ void __launch_bounds__(RT_BLOCK) __attribute__((amdgpu_waves_per_eu(k
             {
                 if (in)
                 {
-                    const float4* p = wide.nodes + 4u * (size_t)(nodeBase + cur);
-                    const float4 q0 = p[0], q1 = p[1], q2 = p[2], q3 = p[3];
-                    float n0, f0, n1, f1, n2, f2, n3, f3;
-                    RT_WIDE_SLAB(q0, n0, f0); RT_WIDE_SLAB(q1, n1, f1); RT_WIDE_SLAB(q2, n2, f2); RT_WIDE_SLAB(q3, n3, f3);
-                    const bool h0 = f0 >= n0 && n0 < limit, h1 = f1 >= n1 && n1 < limit, h2 = f2 >= n2 && n2 < limit, h3 = f3 >= n3 && n3 < limit;
-                    // any-hit rays walk the FARTHEST entered child next (rt_trace_wide.inl has the reasoning and the barrier's); `tol` is zero for any-hit rays only
-                    float tolNow = tol;
-                    asm volatile("" : "+v"(tolNow));
-                    const uint32_t orderFlip = (tolNow == 0.0f && tune.anyHitFarFirst != 0u) ? 0u : 0x7FFFFFFFu;
-                    uint32_t k0 = h0 ? orderFlip ^ ubits(n0) : 0xFFFFFFFFu, k1 = h1 ? orderFlip ^ ubits(n1) : 0xFFFFFFFFu;
-                    uint32_t k2 = h2 ? orderFlip ^ ubits(n2) : 0xFFFFFFFFu, k3 = h3 ? orderFlip ^ ubits(n3) : 0xFFFFFFFFu;
-                    uint32_t r0 = ubits(q0.w), r1 = ubits(q1.w), r2 = ubits(q2.w), r3 = ubits(q3.w);
-#define RT_WIDE_CE(ka, ra, kb, rb) { const bool c_ = ka > kb; const uint32_t lo_ = min(ka, kb), hi_ = max(ka, kb), rl_ = c_ ? rb : ra, rh_ = c_ ? ra : rb; ka = lo_; kb = hi_; ra = rl_; rb = rh_; }
-                    RT_WIDE_CE(k0, r0, k1, r1) RT_WIDE_CE(k2, r2, k3, r3) RT_WIDE_CE(k0, r0, k2, r2) RT_WIDE_CE(k1, r1, k3, r3) RT_WIDE_CE(k1, r1, k2, r2)
-#undef RT_WIDE_CE
-                    const uint32_t numHit = (h0 ? 1u : 0u) + (h1 ? 1u : 0u) + (h2 ? 1u : 0u) + (h3 ? 1u : 0u);
-                    uint32_t* const top = stack + sp * RT_BLOCK;
-                    top[0] = r0; top[RT_BLOCK] = r1; top[2 * RT_BLOCK] = r2;
-                    if (numHit != 0u) { cur = numHit == 1u ? r0 : (numHit == 2u ? r1 : (numHit == 3u ? r2 : r3)); sp += numHit - 1u; }
-                    else if (sp == levelBase) cur = RT_QUANT_DONE;
-                    else { --sp; cur = stack[sp * RT_BLOCK]; }
+                    const WideStep next = wideInteriorStep(wide.nodes + 4u * (size_t)(nodeBase + cur), stack, levelBase, sp, ax, ay, az, bx, by, bz, selX, selY, selZ, limit, tol, tune);
+                    cur = next.cur; sp = next.sp;
                     if (sp + 3u > (uint32_t)kStack) { handOver = true; cur = RT_QUANT_DONE; }   // the next step could not push: the binary-tree kernel takes the ray
                 }
                 in = in && (cur >> RT_NODE_LEAVES_SHIFT) == 0u;
@@ -215,37 +189,19 @@ __global__ void __launch_bounds__(RT_BLOCK) __attribute__((amdgpu_waves_per_eu(k
                 {
                     // MeshShape::Traverse_Leaf(_Shadow), MeshShape.cpp:134-207, as in k_trace_wide
                     const WideLevel& level = wide.levels[objectId];
-                    const uint32_t numLeaves = cur >> RT_NODE_LEAVES_SHIFT, first = cur & RT_NODE_CHILD_MASK;
-                    const RtTriangle* const tris = scene.triangles + level.triBase;
+                    const uint32_t first = cur & RT_NODE_CHILD_MASK;
                     Ray ray; ray.origin = V4(ox, oy, oz, 0.0f); ray.dir = V4(dx, dy, dz, 0.0f);
-                    V4 v0, e1, e2, nv0, ne1, ne2;
-                    loadTriangle(tris + first, v0, e1, e2);
-                    loadTriangle(tris + first + (numLeaves > 1u ? 1u : 0u), nv0, ne1, ne2);
-                    float u0, v0_, t0, u1 = 0.0f, v1 = 0.0f, t1 = inf;
-                    if (!intersectTriangleRay(ray, v0, e1, e2, u0, v0_, t0)) t0 = inf;
-                    if (numLeaves > 1u && !intersectTriangleRay(ray, nv0, ne1, ne2, u1, v1, t1)) t1 = inf;
-                    const float lo = fminf(t0, t1);
+                    float u0, v0_, t0, u1, v1, t1;
+                    const float lo = wideLeafPair(scene.triangles + level.triBase, cur, ray, t0, u0, v0_, t1, u1, v1);
                     if (lo < best + tol)
                     {
-                        const float4 gmin = wide.gate[level.gateBase + 2u * first], gmax = wide.gate[level.gateBase + 2u * first + 1u];
-                        const Ray gateRay = makeRayUnsafe3(ray.origin, ray.dir);
-                        float nearD;
-                        const bool pass = intersectBoxRayNoNaN(gateRay, gmin.x, gmin.y, gmin.z, gmax.x, gmax.y, gmax.z, nearD) && (!shadow || nearD < best);
+                        const bool pass = wideLeafGate(wide.gate + level.gateBase, first, makeRayUnsafe3(ray.origin, ray.dir), shadow, best);   // (the ray rebuilt, not parked: this walk's LDS holds the world terms)
                         if (pass)
                         {
                             if (shadow) { if (lo < best) occluded = true; }
                             else
                             {
-                                const float hi = fmaxf(t0, t1);
-                                if (lo < best)
-                                {
-                                    second = fminf(best, hi);
-                                    best = lo;
-                                    const bool firstWins = t0 <= t1;
-                                    prec(paths, R_HIT, slot) = f4(fbits(objectId), fbits(first + (firstWins ? 0u : 1u)), lo, firstWins ? u0 : u1);
-                                    prec(paths, R_SAMPLER, slot).x = firstWins ? v0_ : v1;
-                                }
-                                else second = fminf(second, lo);
+                                wideAcceptPair(paths, slot, objectId, first, t0, u0, v0_, t1, u1, v1, lo, best, second);
                             }
                         }
                     }
@@ -261,10 +217,7 @@ __global__ void __launch_bounds__(RT_BLOCK) __attribute__((amdgpu_waves_per_eu(k
                         const Ray world = loadWorldRay();
                         ox = world.origin.x; oy = world.origin.y; oz = world.origin.z; dx = world.dir.x; dy = world.dir.y; dz = world.dir.z;
                         {
-                            ax = topLevel->step[0] * world.invDir.x; ay = topLevel->step[1] * world.invDir.y; az = topLevel->step[2] * world.invDir.z;
-                            bx = __fmaf_rn(topLevel->base[0], world.invDir.x, -world.originDivDir.x);
-                            by = __fmaf_rn(topLevel->base[1], world.invDir.y, -world.originDivDir.y);
-                            bz = __fmaf_rn(topLevel->base[2], world.invDir.z, -world.originDivDir.z);
+                            RT_WIDE_FOLD_SET(world, (*topLevel))
                             nodeBase = topLevel->nodeBase;
                         }
                         if (leafRest == 0u) { popOrDone(); if (cur == RT_QUANT_DONE) finish = true; }
@@ -339,22 +292,8 @@ __global__ void __launch_bounds__(RT_BLOCK) __attribute__((amdgpu_waves_per_eu(k
             }
             if (finish)
             {
-                if (handOver)
-                {
-                    if (shadow) { widePushExact(tune, localLists, true, light * paths.capacity + slot); uncountShadow = true; }   // counted by the kernel that resolves it
-                    else widePushExact(tune, localLists, false, slot);
-                    handedOver = true;
-                }
-                else if (shadow)
-                {
-                    if (occluded) pshadow(paths, light, 0, slot).w = -1.0f;
-                }
-                else if (best == inf) prec(paths, R_HIT, slot) = f4(fbits(RT_INVALID_OBJECT), fbits(0u), inf, 0.0f);
-                else if (second <= best + tol)
-                {
-                    widePushExact(tune, localLists, false, slot);   // a runner-up too close to call: the reference's own walk decides
-                    handedOver = true;
-                }
+                handedOver = wideFinishRay(paths, tune, localLists, shadow, light, slot, handOver, occluded, best, second, tol);
+                if (handOver && shadow) uncountShadow = true;   // counted by the kernel that resolves it (as a plain `handOver && shadow` the kernel's spills move: 32 bytes of scratch for 40)
                 have = false; cur = RT_QUANT_DONE; leafRest = 0u; inMesh = false;
             }
         }
@@ -362,16 +301,8 @@ __global__ void __launch_bounds__(RT_BLOCK) __attribute__((amdgpu_waves_per_eu(k
         }
     }
     __shared__ uint32_t sTally[2];
-    if (threadIdx.x < 2u) sTally[threadIdx.x] = 0u;
-    __syncthreads();
-    if ((threadIdx.x & 63u) == 0u)
-    {
-        if (numShadowRays) atomicAdd(&sTally[0], numShadowRays);
-        if (numRetraced) atomicAdd(&sTally[1], numRetraced);
-    }
-    __syncthreads();
-    if (threadIdx.x == 0u && sTally[0]) atomicAdd(&counters[C_SHADOW], (unsigned long long)sTally[0]);
-    if (threadIdx.x == 1u && sTally[1]) atomicAdd(&counters[RT_COUNTER_RETRACED], (unsigned long long)sTally[1]);
+    // tallies per wave (lane 0 of each adds), sTally not yet cleared; this kernel has no untrusted / overflow counters
+    wideFlushTallies<3u>(sTally, false, (threadIdx.x & 63u) == 0u, numShadowRays, numRetraced, 0u, 0u, true, counters);
     // the rays this block's walk did not decide, by the reference's own walk (as k_trace_wide)
     __syncthreads();
     if (threadIdx.x < 2u && sLocalCounts[threadIdx.x] > RT_WIDE2_LOCAL_EXACT) sLocalCounts[threadIdx.x] = RT_WIDE2_LOCAL_EXACT;

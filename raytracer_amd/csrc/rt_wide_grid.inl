@@ -1,5 +1,6 @@
 // rt_wide_grid.inl -- what the 4-wide walks (rt_trace_wide.inl, rt_trace_wide2.inl, rt_trace_packet.inl) share: the 16-bit grid of conservative boxes, the
-// per-leaf exact boxes ("gates") and the exactness argument below.  Included by rt_trace.hip / rt_tail.hip (RT_DEVICE_KERNELS) and rt_runtime.hip (tree
+// per-leaf exact boxes ("gates"), the launch parameters (WideTuning) and the exactness argument below; the device code they share -- request ray, fold,
+// interior step, mesh leaf, finish, tallies -- is rt_wide_walk.h.  Included by rt_trace.hip / rt_tail.hip (RT_DEVICE_KERNELS) and rt_runtime.hip (tree
 // builders: RT_HOST_BUILDERS).
 // (Round 2 also had a kernel here, k_trace_quant: the reference's BINARY tree with its child pairs re-encoded in 32 bytes -- two accesses per visit instead
 // of four, no decode step.  Bit-exact, and no faster than k_trace: 182 vs 183 ms, the twelve conversions per visit ate what the L1 gave back.  Removed in
@@ -28,6 +29,21 @@
 
 #define RT_QUANT_DONE 0xFFFFFFFFu   // cur: the ray is finished (same value as RT_LEVEL_EXHAUSTED: the mesh level has no node left)
 #define RT_QUANT_GRID 65535.0f
+
+// what a launch of any of the 4-wide walks is tuned by (the device parts they share, rt_wide_walk.h, read it too)
+struct WideTuning
+{
+    uint32_t refillMinIdle, otherMinLanes;
+    float shadowOffset;
+    uint32_t* exactQueue; uint32_t* exactCount;               // closest-hit rays handed to the binary-tree kernel
+    uint32_t* exactShadowQueue; uint32_t* exactShadowCount;   // any-hit requests handed to it
+    const uint32_t* denseCounts; uint32_t denseShardCapacity; // dense path state (TravTuning)
+    uint32_t chunkMin;                                        // smallest piece of the work queue a wave claims at once
+    uint32_t localExact;                                      // != 0: a block traces the rays its walk does not decide itself (k_trace_wide; RTGPU_LOCAL_EXACT=0: off)
+    uint32_t drainAbortAfter;                                 // != 0: a wave whose work queue ran dry this many loop iterations ago hands the rays it still walks to the binary-tree kernel
+    uint32_t reverseOrder;                                    // != 0: the queue is taken from its end (any-hit requests first, closest-hit rays last); 0 (default since round 6): front to back -- the launch's drain is then made of the any-hit rays, the short ones under the far-first order
+    uint32_t anyHitFarFirst;                                  // != 0: an any-hit ray walks the FARTHEST child it enters next (round 6; RTGPU_ANYHIT_FAR_FIRST=0: nearest, as closest-hit rays do)
+};
 
 #ifdef RT_HOST_BUILDERS
 // ---- host: the reference's binary BVH (BVH::Node, 32 bytes, children adjacent) re-encoded ----

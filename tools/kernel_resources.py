@@ -20,8 +20,8 @@ if len(sys.argv) <= 1:
         s += open(out).read()
 else:
     s = open(path).read()
-for m in re.finditer(r'\.name:\s+(\S+)\n(.*?)\.vgpr_count:\s+(\d+)', s, re.S):
-    name, body = m.group(1), m.group(2)
+for m in re.finditer(r'\.group_segment_fixed_size:\s+(\d+)\n.*?\.name:\s+(\S+)\n(.*?)\.vgpr_count:\s+(\d+)', s, re.S):   # (a kernel's metadata keys are sorted: the LDS size comes before its name)
+    lds, name, body = m.group(1), m.group(2), m.group(3)
     dn = subprocess.run(["c++filt", name], capture_output=True, text=True).stdout.split('(')[0].replace("void ", "")
     g = lambda k: (re.search(r'\.%s:\s+(\d+)' % k, body) or [None, "?"])[1]
-    print('%-60s vgpr %3s sgpr %3s scratch %4s lds %6s' % (dn[:60], m.group(3), g("sgpr_count"), g("private_segment_fixed_size"), g("group_segment_fixed_size")))
+    print('%-60s vgpr %3s sgpr %3s scratch %4s lds %6s' % (dn[:60], m.group(4), g("sgpr_count"), g("private_segment_fixed_size"), lds))
