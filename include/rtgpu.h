@@ -603,6 +603,35 @@ int rtgpu_trace_rays(RtgpuContext* ctx, uint32_t mode, const RtQueryRay* rays, u
 int rtgpu_trace_rays_async(RtgpuContext* ctx, uint32_t mode, const RtQueryRay* rays, uint32_t count, RtQueryHit* hits, RtQuerySurface* surfaces,
                            uint32_t* occluded, RtCounters* stats, void* stream);
 
+/* ---------------------------------------------------------------------------------------------
+ * Path records: the reference's PathDebugData hook (Core/Rendering/PathDebugging.h:27-53, filled by PathTracerMIS::RenderPixel at
+ * PathTracerMIS.cpp:377-410; its Demo draws the picked pixel's path from it).  For each pixel (x, y) -- sum-buffer coordinates, as in
+ * RtBlock; the film row flips inside -- the call traces the path rtgpu_render_pass(ctx, params) would trace for it on this context and
+ * writes its vertices in path order: one per vertex the path goes on from, with the sampled BSDF event, and a closing one where it ends.
+ *   RtPathVertex  28 words: 0-2 ray origin, 3-5 ray direction, 6 objectId, 7 subObjectId (uint32), 8 distance, 9-10 u v, 11-13 position,
+ *              14-16 normal, 17-19 tangent (the evaluated frame, world space), 20-21 texCoord, 22-25 throughput, 26 bsdfEvent (uint32), 27 zero.
+ *              Zero where the reference leaves what an earlier vertex wrote (one HitPoint and one ShadingData live for its whole path):
+ *              on a miss word 7 and words 9..21; on a hit that is not a mesh triangle words 9 and 10; word 26 of the closing record.
+ *   RtPathInfo    numVertices = the path's count; only the first maxVertices are stored, and of a pixel's maxVertices entries in `vertices`
+ *              only those the path has are written.  terminationReason = PathTerminationReason, set at the branches of PathTracerMIS.cpp:
+ *              280-367.  radiance = what the pass would add to the pixel.
+ *   errors     numPixels == 0 is a no-op; NULL buffers with numPixels > 0, a pixel outside the frame, maxVertices == 0 and what
+ *              rtgpu_render_pass refuses in the params: RTGPU_ERR_INVALID_ARGUMENT (and its RTGPU_ERR_UNSUPPORTED); before
+ *              rtgpu_upload_scene / rtgpu_resize: RTGPU_ERR_NOT_READY; any integrator but RT_INTEGRATOR_PATH_TRACER_MIS: RTGPU_ERR_UNSUPPORTED.
+ * Host pointers; synchronous (flushes the queued passes first).  A pixel may repeat; shards and active blocks do not restrict the call, and a
+ * multi-device context answers on its first device.  It traces with the walk the context renders with, on an arena, queues and counters of
+ * its own (sized by numPixels, grown on use, freed with the context), is not a pass, and leaves film, sum buffers, counters and kernel
+ * times alone.
+ * --------------------------------------------------------------------------------------------- */
+typedef enum RtPathTerminationReason
+{
+    RT_PATH_HIT_BACKGROUND = 1, RT_PATH_HIT_LIGHT = 2, RT_PATH_DEPTH = 3, RT_PATH_THROUGHPUT = 4, RT_PATH_NO_SAMPLED_EVENT = 5, RT_PATH_RUSSIAN_ROULETTE = 6
+} RtPathTerminationReason;
+typedef struct RtPathVertex { float w[28]; } RtPathVertex;   /* 112 bytes */
+typedef struct RtPathInfo { uint32_t numVertices, terminationReason; float radiance[3]; uint32_t _pad[3]; } RtPathInfo;   /* 32 bytes */
+int rtgpu_record_paths(RtgpuContext* ctx, const RtPassParams* params, const uint32_t* pixelsXY /* 2 per pixel */, uint32_t numPixels,
+                       uint32_t maxVertices, RtPathVertex* vertices /* [numPixels * maxVertices] */, RtPathInfo* infos /* [numPixels] */);
+
 /* Known-answer-test hooks.  They evaluate the DEVICE implementation of one hot-path function (the code the traversal and shading
  * kernels call, rt_device_*.h) on caller-provided records, so that tests can hold the HIP functions directly against vectors produced
  * by the reference's own translation units (tests/golden/) without going through any CPU

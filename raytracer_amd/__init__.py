@@ -162,6 +162,18 @@ class RtCounters(C.Structure):
                                           "numShadowRayTriangleTests", "numRetracedRays")] + [("_reserved", C.c_uint64 * 3)]
 
 
+class RtPathVertex(C.Structure):
+    _fields_ = [("w", C.c_float * 28)]
+
+
+class RtPathInfo(C.Structure):
+    _fields_ = [("numVertices", C.c_uint32), ("terminationReason", C.c_uint32), ("radiance", C.c_float * 3), ("_pad", C.c_uint32 * 3)]
+
+
+# PathTerminationReason (Core/Rendering/PathDebugging.h:9-18)
+PATH_TERMINATION_REASONS = ("None", "HitBackground", "HitLight", "Depth", "Throughput", "NoSampledEvent", "RussianRoulette")
+
+
 class RtQueryRay(C.Structure):
     _fields_ = [("origin", C.c_float * 3), ("maxDistance", C.c_float), ("direction", C.c_float * 3), ("_pad", C.c_float)]
 
@@ -670,6 +682,44 @@ class Viewport:
             err = (lib.rtgpu_last_error() or b"").decode()
             raise (ValueError if r == -1 else RuntimeError)("ray query failed (%d): %s" % (r, err))
         return dict(hits=hits, surfaces=surf, occluded=occ, torch=torch)
+
+    # ---- path records (include/rtgpu.h: rtgpu_record_paths) ------------------------------------------------------------------------------
+    def record_paths(self, params, pixels, max_vertices=None):
+        """The reference's PathDebugData hook for chosen pixels: the vertices of the path the pass `params` traces for each (x, y) of `pixels`
+        (sum-buffer coordinates; a pixel may repeat).  Returns a list, in the order of `pixels`, of (vertices, termination_reason, radiance):
+        vertices (n, 28) float32 as RtPathVertex lays them out (n = min(the path's vertex count, max_vertices); default: every vertex),
+        termination_reason a PathTerminationReason value (PATH_TERMINATION_REASONS names them), radiance (3,) float32 = what the pass adds to the
+        pixel.  `params` is an RtPassParams from next_pass_params(): recording it renders nothing and is not a pass, so record before or after
+        render_pass_with(params) as you like.  A Camera is not accepted: next_pass_params() is the one place that advances the viewport's sample
+        sequence, and a recording that drew from it would shift every later pass."""
+        if not isinstance(params, RtPassParams):
+            raise TypeError("record_paths takes the RtPassParams of next_pass_params(camera), not %s" % type(params).__name__)
+        px = np.asarray(pixels)
+        if px.size == 0:
+            px = px.reshape(0, 2)
+        if px.ndim != 2 or px.shape[1] != 2 or px.dtype.kind not in "iu":
+            raise ValueError("pixels must be a sequence of integer (x, y) pairs")
+        if (px < 0).any() or (px[:, 0] >= self.width).any() or (px[:, 1] >= self.height).any():
+            raise ValueError("a pixel lies outside the %d x %d frame" % (self.width, self.height))
+        capacity = int(params.maxRayDepth) + 1 if max_vertices is None else int(max_vertices)
+        if capacity < 1:
+            raise ValueError("max_vertices must be at least 1")
+        if not self.has_renderer:
+            raise RuntimeError("record_paths needs a renderer: call set_renderer first")
+        ctx = self.device_context()
+        if not ctx.value or host_lib().rth_viewport_upload_scene(self._h) != 0:
+            raise RuntimeError("the viewport's renderer has no device context or its scene could not be uploaded: %s" % (rtgpu_lib().rtgpu_last_error() or b"").decode())
+        n = int(px.shape[0])
+        xy = np.ascontiguousarray(px, dtype=np.uint32)
+        vertices = np.zeros((max(n, 1), capacity, 28), dtype=np.float32)
+        infos = np.zeros((max(n, 1), 8), dtype=np.uint32)
+        r = rtgpu_lib().rtgpu_record_paths(ctx, C.byref(params), xy.ctypes.data_as(C.c_void_p), C.c_uint32(n), C.c_uint32(capacity),
+                                           vertices.ctypes.data_as(C.c_void_p), infos.ctypes.data_as(C.c_void_p))
+        if r != 0:
+            err = (rtgpu_lib().rtgpu_last_error() or b"").decode()
+            raise (ValueError if r == -1 else RuntimeError)("record_paths failed (%d): %s" % (r, err))
+        radiance = infos[:, 2:5].view(np.float32)
+        return [(vertices[i, :min(int(infos[i, 0]), capacity)].copy(), int(infos[i, 1]), radiance[i].copy()) for i in range(n)]
 
     @property
     def passes_finished(self):

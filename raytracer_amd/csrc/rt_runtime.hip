@@ -27,7 +27,7 @@
 // This file is the translation unit and keeps the contexts, the film and the small entry points; its parts: rt_runtime_context.h (RtgpuContext, BatchLane,
 // staging copies, stream pool, HIP_TRY, LaunchTimer, free helpers), rt_knobs.h (every RTGPU_* environment variable), rt_multi.inl (multi-device contexts),
 // rt_runtime_scene.inl (rtgpu_upload_scene), rt_runtime_render.inl (arena sizing, traversal launchers, batch submission), rt_runtime_vcm.inl (bidirectional
-// integrator, Light Tracer), rt_runtime_kat.inl (known-answer hooks, rtgpu_evaluate_textures), rt_runtime_query.inl (batched ray queries).
+// integrator, Light Tracer), rt_runtime_kat.inl (known-answer hooks, rtgpu_evaluate_textures), rt_runtime_query.inl (batched ray queries), rt_runtime_paths.inl (path records).
 //
 // Compile: hipcc --offload-arch=gfx950 -O3 -ffp-contract=off
 #include "rt_trace_common.h"
@@ -197,6 +197,7 @@ RTGPU_API void rtgpu_destroy(RtgpuContext* c)
     (void)syncLanes(c);
     devFree(c->gatherStage);
     freeQuery(c);
+    freeRecorder(c);
     freeScene(c); freeFilm(c);
     for (uint32_t i = 0; i < RT_MAX_LANES; ++i)
     {
@@ -390,26 +391,23 @@ RTGPU_API int rtgpu_vcm_num_photons(RtgpuContext* c, uint32_t* outCount)
     return RTGPU_OK;
 }
 
-RTGPU_API int rtgpu_render_pass(RtgpuContext* c, const RtPassParams* p)
+// what a pass needs before it can be queued or recorded (rtgpu_render_pass, rtgpu_record_paths)
+static int checkPass(const RtgpuContext* c, const RtPassParams* p)
 {
-    if (!c || !p) return fail(RTGPU_ERR_INVALID_ARGUMENT, "NULL argument");
     if (!c->sceneReady) return fail(RTGPU_ERR_NOT_READY, "rtgpu_upload_scene has not been called");
     if (!c->sum) return fail(RTGPU_ERR_NOT_READY, "rtgpu_resize has not been called");
     if (p->numDimensions > RTGPU_MAX_DIMENSIONS) return fail(RTGPU_ERR_INVALID_ARGUMENT, "numDimensions exceeds RTGPU_MAX_DIMENSIONS");
     if (p->numDimensions > 0 && !p->seed) return fail(RTGPU_ERR_INVALID_ARGUMENT, "seed is NULL");
     if (p->maxRayDepth >= 255u) return fail(RTGPU_ERR_INVALID_ARGUMENT, "maxRayDepth must be < 255");
     if (p->camera.dofEnable && p->camera.bokehShape > 2u) return fail(RTGPU_ERR_UNSUPPORTED, "bokeh shapes: circle, hexagon, square (NGon is a TODO in the reference, texture-shaped bokeh is not implemented)");
-    RT_FAN_OUT(c, rtgpu_render_pass(peer, p));   // asynchronous on every device: the shards render side by side
-    HIP_TRY(hipSetDevice(c->device));
-    if (c->numSlots == 0) return RTGPU_OK;   // this shard owns no pixels
-    if (c->vcm.enabled) return vcmRenderPass(c, p);
-    if (c->lightTracer) return lightTracerRenderPass(c, p);
-
-    CtxPending pd;
-    DevPass& pass = pd.pass;
+    return RTGPU_OK;
+}
+// the device's per-pass constants; `seed` is assigned where the pass is submitted
+static void makeDevPass(const RtgpuContext* c, const RtPassParams* p, DevPass& pass)
+{
     memset(&pass, 0, sizeof(pass));
     pass.camera = p->camera;
-    pass.seed = nullptr;   // assigned when the batch is submitted
+    pass.seed = nullptr;
     pass.numDimensions = p->numDimensions;
     pass.blueNoiseLayers = (c->sceneDev.blueNoise && p->useBlueNoise) ? 4u : 0u;   // GenericSampler.cpp:69-73
     pass.sampleOffset[0] = p->sampleOffset[0]; pass.sampleOffset[1] = p->sampleOffset[1];
@@ -421,6 +419,21 @@ RTGPU_API int rtgpu_render_pass(RtgpuContext* c, const RtPassParams* p)
     memcpy(pass.bsdfSamplingWeight, p->bsdfSamplingWeight, 16);
     pass.rngKey[0] = p->rngKey[0]; pass.rngKey[1] = p->rngKey[1];
     pass.width = c->width; pass.height = c->height;
+}
+
+RTGPU_API int rtgpu_render_pass(RtgpuContext* c, const RtPassParams* p)
+{
+    if (!c || !p) return fail(RTGPU_ERR_INVALID_ARGUMENT, "NULL argument");
+    { const int r = checkPass(c, p); if (r) return r; }
+    RT_FAN_OUT(c, rtgpu_render_pass(peer, p));   // asynchronous on every device: the shards render side by side
+    HIP_TRY(hipSetDevice(c->device));
+    if (c->numSlots == 0) return RTGPU_OK;   // this shard owns no pixels
+    if (c->vcm.enabled) return vcmRenderPass(c, p);
+    if (c->lightTracer) return lightTracerRenderPass(c, p);
+
+    CtxPending pd;
+    DevPass& pass = pd.pass;
+    makeDevPass(c, p, pass);   // (its seed pointer is assigned when the batch is submitted)
     pd.seeds.assign(p->seed, p->seed + p->numDimensions);   // the caller's array may be reused right away
 
     // all passes of a batch share the structural parameters; a change submits what is queued first
@@ -672,6 +685,7 @@ RTGPU_API int rtgpu_postprocess(RtgpuContext* c, const RtPostprocessParams* p, u
 
 #include "rt_runtime_kat.inl"
 #include "rt_runtime_query.inl"
+#include "rt_runtime_paths.inl"
 
 RTGPU_API int rtgpu_set_concurrency(RtgpuContext* c, uint32_t lanes)
 {

@@ -229,6 +229,18 @@ struct RtgpuContext
         hipEvent_t done = nullptr;                // recorded behind every query: the next one (whatever its stream), a new arena and a new scene wait for it
     } query;
 
+    // path records (rtgpu_record_paths): the slot-per-pixel pipeline over caller-chosen pixels, on an arena, queues, work counts, counters and per-pass
+    // constants of its own -- never a lane's, never c->counters, never the seed ring
+    struct Recorder
+    {
+        BatchLane lane;                           // arena, queues and work counts as a batch lane holds them (no second arena, no stream or event of its own)
+        uint32_t* slotPixel = nullptr;            // slot -> pixel of the chunk being recorded
+        float4* records = nullptr; size_t recordCapacity = 0;   // per slot: 7 float4 per stored vertex, then {numVertices, terminationReason} (rt_shade.inl)
+        float4* infos = nullptr;                  // two per slot: RtPathInfo
+        unsigned long long* counters = nullptr;   // 16 x u64
+        DevPass* passDev = nullptr; uint32_t* seedDev = nullptr;   // the recorded pass
+    } recorder;
+
     // timing
     bool timing = false;
     struct Timed { int kc; hipEvent_t a, b; };
@@ -320,6 +332,14 @@ static void freeQuery(RtgpuContext* c)
     devFree(q.counts, q.counters);
     if (q.done) (void)hipEventDestroy(q.done);
     q.done = nullptr;
+}
+
+static void freeRecorder(RtgpuContext* c)
+{
+    RtgpuContext::Recorder& rec = c->recorder;
+    freePaths(rec.lane);
+    devFree(rec.lane.queueCounts, rec.slotPixel, rec.records, rec.infos, rec.counters, rec.passDev, rec.seedDev);
+    rec.lane.queueCountCapacity = 0; rec.recordCapacity = 0;
 }
 
 // Streams are recycled through a process-wide pool instead of being created and destroyed with every context: a test session (or an

@@ -1,5 +1,5 @@
 // rt_shade.hip -- the shading kernels of the library, a translation unit of their own: PathTracerMIS / PathTracer / Debug shading over
-// slot-per-pixel and dense path state (rt_shade.inl, rt_dense.inl) and the bidirectional integrator's kernels (rt_vcm.inl).  The host side
+// slot-per-pixel and dense path state (rt_shade.inl with rt_shade_body.inl, rt_dense.inl) and the bidirectional integrator's kernels (rt_vcm.inl).  The host side
 // (rt_runtime.hip) launches them through the declarations of rt_shade_kernels.h.
 //
 // Why its own unit: it is compiled with -mllvm -simplifycfg-sink-common=false.  SimplifyCFG's common-code sinking merges the stores that
@@ -23,6 +23,7 @@ RT_K_SHADE_DENSE_INSTANCES(RT_X)
 #define RT_X(L, P) template __global__ void __launch_bounds__(RT_BLOCK) k_shade<L, P> RT_K_SHADE_ARGS;
 RT_K_SHADE_INSTANCES(RT_X)
 #undef RT_X
+template __global__ void __launch_bounds__(RT_BLOCK) k_shade_record<false, false> RT_K_SHADE_RECORD_ARGS;
 #define RT_X(C) template __global__ void __launch_bounds__(RT_BLOCK) k_vcm_emit<C> RT_K_VCM_EMIT_ARGS; \
                 template __global__ void __launch_bounds__(RT_BLOCK) k_vcm_light_shade<C> RT_K_VCM_LIGHT_SHADE_ARGS; \
                 template __global__ void __launch_bounds__(RT_BLOCK) k_lt_shade<C> RT_K_LT_SHADE_ARGS; \

@@ -92,213 +92,62 @@ RT_DEV void flushAppendBuffer(const uint32_t* buf, uint32_t& count, uint32_t& ba
 }
 
 #ifndef RT_SHADE_FUNCTIONS_ONLY   // (rt_tail.hip takes the functions above and none of the kernels below)
-// The body of PathTracerMIS::RenderPixel's loop for one path vertex (PathTracerMIS.cpp:276-395).
-// kPlain: the renderer "Path Tracer" instead (PathTracer::RenderPixel, Core/Rendering/PathTracer.cpp:73-171): the same walk without
-// next event estimation, MIS weights and sampling weights.
-template <bool kLean, bool kPlain = false>
-__global__ void __launch_bounds__(RT_BLOCK) k_shade(const RtSceneDesc scene, const DevPass* __restrict__ passes, uint32_t slotsPerPass, const Paths paths,
-                                                    const uint32_t* __restrict__ queueIn, const uint32_t* __restrict__ countIn,
-                                                    uint32_t* __restrict__ queueOut, uint32_t* __restrict__ countOut,
-                                                    uint32_t* __restrict__ shadowQueue, uint32_t* __restrict__ shadowCount,
-                                                    unsigned long long* counters)
+// k_shade, and rtgpu_record_paths' k_shade_record: ONE body (rt_shade_body.inl), compiled twice.  The recording blocks are preprocessor blocks, so
+// k_shade is the token stream it was before the recorder existed.
+#define RT_SHADE_KERNEL k_shade
+#define RT_SHADE_RECORDING 0
+#include "rt_shade_body.inl"
+#undef RT_SHADE_KERNEL
+#undef RT_SHADE_RECORDING
+
+// ---- path records (include/rtgpu.h, rtgpu_record_paths; host side: rt_runtime_paths.inl) ------------------------------------------------------
+// The reference's PathDebugData hook (Core/Rendering/PathDebugging.h:27-53, filled at PathTracerMIS.cpp:377-410).  A slot's records are `stride`
+// float4: seven per vertex (RtPathVertex: 28 words), vertex k of the path at 7 k, and in the last one the vertex count and the termination reason,
+// which the shade launch that ends the path writes.  Vertices the buffer has no room for ((stride - 1) / 7 of them fit) are counted, not stored.
+enum { RT_PATH_END_HIT_BACKGROUND = 1, RT_PATH_END_HIT_LIGHT, RT_PATH_END_DEPTH, RT_PATH_END_THROUGHPUT, RT_PATH_END_NO_SAMPLED_EVENT, RT_PATH_END_RUSSIAN_ROULETTE };   // PathTerminationReason
+// u and v are barycentrics: only MeshShape::Traverse writes them (the reference's HitPoint keeps an earlier vertex's otherwise, the record holds 0)
+RT_DEV bool pathHitIsMeshTriangle(const RtSceneDesc& scene, const Hit& hit)
 {
-    __shared__ uint32_t sPathBuf[RT_APPEND_BUFFER], sShadowBuf[RT_APPEND_BUFFER];
-    __shared__ uint32_t sPathCount, sShadowCount, sPathBase, sShadowBase;
-    if (threadIdx.x == 0) { sPathCount = 0; sShadowCount = 0; }
-    __syncthreads();
+    const RtObject& obj = scene.objects[hit.objectId];
+    return obj.objectKind != RT_OBJECT_LIGHT && obj.shapeKind == RT_SHAPE_MESH;
+}
+// position, normal, tangent, texCoord: the evaluated intersection.  The caller passes zeros on a miss, for them and for the sub-object id: the reference's
+// ShadingData and HitPoint still hold an earlier vertex's there
+RT_DEV void storePathVertex(float4* __restrict__ records, uint32_t stride, uint32_t slot, uint32_t index, const Ray& ray, uint32_t objectId, uint32_t subObjectId, float distance,
+                            float u, float v, V4 position, V4 normal, V4 tangent, V4 texCoord, V4 throughput, uint32_t bsdfEvent)
+{
+    if (7u * index + 7u > stride - 1u) return;
+    float4* rec = records + (size_t)slot * stride + 7u * index;
+    rec[0] = f4(ray.origin.x, ray.origin.y, ray.origin.z, ray.dir.x);
+    rec[1] = f4(ray.dir.y, ray.dir.z, fbits(objectId), fbits(subObjectId));
+    rec[2] = f4(distance, u, v, position.x);
+    rec[3] = f4(position.y, position.z, normal.x, normal.y);
+    rec[4] = f4(normal.z, tangent.x, tangent.y, tangent.z);
+    rec[5] = f4(texCoord.x, texCoord.y, throughput.x, throughput.y);
+    rec[6] = f4(throughput.z, throughput.w, fbits(bsdfEvent), 0.0f);
+}
+#define RT_SHADE_KERNEL k_shade_record
+#define RT_SHADE_RECORDING 1
+#include "rt_shade_body.inl"
+#undef RT_SHADE_KERNEL
+#undef RT_SHADE_RECORDING
+
+// The end of a recording: folds the next-event results of every path's last vertex into its radiance (what k_accumulate does before it adds the
+// pixel) and writes the slot's RtPathInfo {numVertices, terminationReason, radiance[3], 0, 0, 0} as two float4.
+__global__ void __launch_bounds__(RT_BLOCK) k_paths_finish(const Paths paths, uint32_t numSlots, const DevPass* __restrict__ passes, const float4* __restrict__ records,
+                                                           uint32_t recordStride, float4* __restrict__ infos, unsigned long long* counters)
+{
     Counters cnt; zeroCounters(cnt);
-    const uint32_t count = *countIn;
+    const V4 lightSamplingWeight = load4(passes[0].lightSamplingWeight);
     const uint32_t stride = gridDim.x * blockDim.x;
-    // the structural parameters are identical for all passes of a batch (the host flushes when they change);
-    // seeds, camera, anti-aliasing offset and rng keys are per pass
-    const DevPass pass = passes[0];
-    const V4 lightSamplingWeight = load4(pass.lightSamplingWeight), bsdfSamplingWeight = load4(pass.bsdfSamplingWeight);
-    // GetLightPickingProbability, PathTracerMIS.cpp:157-172
-    const float lightPickProbability = pass.lightSamplingStrategy == RT_LIGHT_SAMPLING_SINGLE ? 1.0f / (float)scene.numLights : 1.0f;
-    const uint32_t maxRequestsPerVertex = pass.lightSamplingStrategy == RT_LIGHT_SAMPLING_SINGLE ? 1u : (scene.numLights < 8u ? scene.numLights : 8u);
-
-    // every lane of a wave runs the same number of iterations so that the ballot below sees whole waves
-    const uint32_t rounded = (count + RT_BLOCK - 1) / RT_BLOCK * RT_BLOCK;
-    for (uint32_t i = blockIdx.x * blockDim.x + threadIdx.x; i < rounded; i += stride)
+    for (uint32_t slot = blockIdx.x * blockDim.x + threadIdx.x; slot < numSlots; slot += stride)
     {
-        bool alive = false;
-        uint32_t slot = 0;
-        unsigned long long rayMask = 0ull;   // NEE requests of this vertex that need a shadow ray (bit = request index)
-        if (i < count)
-        {
-            slot = queueIn[i];
-            const float4 rOrigin = prec(paths, R_ORIGIN, slot), rDir = prec(paths, R_DIR, slot), rTp = prec(paths, R_TP, slot);
-            const float4 rResult = prec(paths, R_RESULT, slot), rHit = prec(paths, R_HIT, slot), rSampler = prec(paths, R_SAMPLER, slot);
-            const uint32_t flags = ubits(rOrigin.w);
-            uint32_t depth = flags & 0xFFu;
-            const bool lastSpecular = (flags & 0x100u) != 0;
-            const float lastPdfW = rDir.w;
-            const uint32_t pix = ubits(rResult.w);
-            const Ray ray = makePathRay(rOrigin, rDir, depth);
-            V4 throughput(rTp.x, rTp.y, rTp.z, rTp.w);
-            V4 resultColor(rResult.x, rResult.y, rResult.z, 0.0f);
-            resolvePendingLightSamples(paths, slot, ubits(rSampler.w), lightSamplingWeight, resultColor, cnt);   // NEE of the previous vertex
-            Hit hit;
-            hit.objectId = ubits(rHit.x); hit.subObjectId = ubits(rHit.y); hit.distance = rHit.z; hit.u = rHit.w; hit.v = rSampler.x;
-            bool samplerStored = false;
-
-            do
-            {
-                if (hit.objectId == RT_INVALID_OBJECT)
-                {
-                    // EvaluateGlobalLights, PathTracerMIS.cpp:214-252
-                    V4 result = zero4();
-                    for (uint32_t g = 0; g < scene.numGlobalLights; ++g)
-                    {
-                        const RtLight& light = scene.lights[scene.globalLights[g]];
-                        const Ray lightSpaceRay = transformRayUnsafe(loadM4(light.invTransform), ray);
-                        float directPdfW = 0.0f;
-                        const V4 lightContribution = lightGetRadiance<kLean>(scene, light, lightSpaceRay, zero4(), 1.0f, directPdfW);
-                        if (kPlain) result = result + lightContribution;   // PathTracer::EvaluateGlobalLights, PathTracer.cpp:47-71
-                        else if (!almostZero4(lightContribution))
-                        {
-                            float misWeight = 1.0f;
-                            if (depth > 0 && !lastSpecular) misWeight = CombineMis(lastPdfW, directPdfW * lightPickProbability);
-                            result = mulAdd(lightContribution, misWeight, result);
-                        }
-                    }
-                    if (!kPlain) result = result * bsdfSamplingWeight;
-                    resultColor = mulAdd(throughput, result, resultColor);
-                    break;
-                }
-
-                ShadingData sd;
-                // The reference keeps ONE ShadingData for the whole path (PathTracerMIS.cpp:258) and LightSceneObject::
-                // EvaluateIntersection does not touch `material` (SceneObject_Light.cpp:62-73): when a path hits an area light,
-                // IntersectionData::material is still the PREVIOUS vertex's, and its normal map (if any) is applied to the
-                // light's frame (Scene.cpp:327).  The previous material rides in the flags word: (index + 1) << 9.
-                sd.intersection.material = (flags >> 9) - 1u;   // 0 -> RT_NO_MATERIAL
-                if (hit.distance < FLT_MAX) sceneEvaluateIntersection<kLean>(scene, ray, hit, sd.intersection, cnt);
-
-                if (!kLean && hit.subObjectId == RT_LIGHT_OBJECT)
-                {
-                    // EvaluateLight, PathTracerMIS.cpp:174-212
-                    const RtObject& obj = scene.objects[hit.objectId];
-                    const RtLight& light = scene.lights[obj.lightIndex];
-                    const M4 worldToLight = loadM4(obj.invTransform);
-                    const Ray lightSpaceRay = transformRayUnsafe(worldToLight, ray);
-                    const V4 lightSpaceHitPoint = transformPoint(worldToLight, sd.intersection.frame.r[3]);
-                    const float cosAtLight = -dot3(sd.intersection.frame.r[2], ray.dir);
-                    float directPdfA = 0.0f;
-                    V4 lightContribution = lightGetRadiance<false>(scene, light, lightSpaceRay, lightSpaceHitPoint, cosAtLight, directPdfA);
-                    if (kPlain) resultColor = mulAdd(throughput, lightContribution, resultColor);   // PathTracer::EvaluateLight, PathTracer.cpp:26-45
-                    else if (!almostZero4(lightContribution))
-                    {
-                        float misWeight = 1.0f;
-                        if (depth > 0 && !lastSpecular)
-                        {
-                            const float directPdfW = PdfAtoW(directPdfA, hit.distance, cosAtLight);
-                            misWeight = CombineMis(lastPdfW, directPdfW * lightPickProbability);
-                        }
-                        lightContribution = lightContribution * bsdfSamplingWeight;
-                        resultColor = mulAdd(throughput, lightContribution * misWeight, resultColor);
-                    }
-                    else
-                    {
-                        resultColor = mulAdd(throughput, zero4(), resultColor);
-                    }
-                    break;
-                }
-
-                sd.outgoingDirWorldSpace = neg(ray.dir);
-                const RtMaterial& mat = scene.materials[sd.intersection.material];
-                materialEvaluateShadingData<kLean>(scene, mat, sd);
-
-                // emission, PathTracerMIS.cpp:309-317
-                resultColor = mulAdd(throughput, kPlain ? sd.mp.emission : sd.mp.emission * bsdfSamplingWeight, resultColor);
-
-                Sampler sampler; loadSampler(sampler, paths, slot, pix, rSampler, pass, scene.blueNoise);
-                sampler.seed = passes[slot / slotsPerPass].seed;
-
-                // SampleLights (next event estimation), PathTracerMIS.cpp:125-155
-                uint32_t numRequests = 0;
-                if (!kPlain && scene.numLights != 0)
-                {
-                    if (pass.lightSamplingStrategy == RT_LIGHT_SAMPLING_SINGLE)
-                    {
-                        uint32_t lightIndex = 0;
-                        if (scene.numLights > 1) lightIndex = sampler.fallbackInt() % scene.numLights;
-                        if (prepareLightSample<kLean>(scene, pass, sampler, scene.lights[lightIndex], sd, mat, depth, lightPickProbability, paths, slot, 0)) rayMask = 1ull;
-                        numRequests = 1;
-                    }
-                    else
-                    {
-                        for (uint32_t l = 0; l < scene.numLights; ++l)
-                        {
-                            const bool ray = prepareLightSample<kLean>(scene, pass, sampler, scene.lights[l], sd, mat, depth, lightPickProbability, paths, slot, l);
-                            if (ray)
-                            {
-                                if (l < 8u) rayMask |= 1ull << l;
-                                else shadowQueue[atomicAdd(shadowCount, 1u)] = l * paths.capacity + slot;   // more than 64 lights: per-lane append
-                            }
-                        }
-                        numRequests = scene.numLights;
-                    }
-                    prec(paths, R_SH_P, slot) = f4(sd.intersection.frame.r[3].x, sd.intersection.frame.r[3].y, sd.intersection.frame.r[3].z, 0.0f);
-                    prec(paths, R_SH_TP, slot) = f4(throughput.x, throughput.y, throughput.z, 0.0f);
-                }
-
-                bool cont = true;
-                if (depth >= pass.maxRayDepth) cont = false;
-
-                // Russian roulette, PathTracerMIS.cpp:330-347
-                if (cont && depth >= pass.minRussianRouletteDepth)
-                {
-                    const float minColorValue = 0.125f;
-                    const float threshold = minColorValue + (1.0f - minColorValue) * colorMax(sd.mp.baseColor);
-                    if (sampler.getFloat() > threshold) cont = false;
-                    else throughput = throughput * (1.0f / threshold);
-                }
-
-                // BSDF sampling, PathTracerMIS.cpp:349-395
-                if (cont)
-                {
-                    float pdf = 0.0f; V4 incomingDirWorldSpace = zero4(); uint32_t event = EV_NULL;
-                    float u[3]; u[0] = sampler.getFloat(); u[1] = sampler.getFloat(); u[2] = sampler.getFloat();
-                    const V4 bsdfValue = materialSample<kLean>(mat, sd, u, incomingDirWorldSpace, pdf, event);
-                    if (event == EV_NULL) cont = false;
-                    else
-                    {
-                        throughput = throughput * bsdfValue;
-                        if (almostZero4(throughput)) cont = false;
-                        else
-                        {
-                            prec(paths, R_ORIGIN, slot) = f4(sd.intersection.frame.r[3].x, sd.intersection.frame.r[3].y, sd.intersection.frame.r[3].z,
-                                                             fbits((depth + 1u) | (((event & EV_SPECULAR) != 0) ? 0x100u : 0u) | ((sd.intersection.material + 1u) << 9)));
-                            prec(paths, R_DIR, slot) = f4(incomingDirWorldSpace.x, incomingDirWorldSpace.y, incomingDirWorldSpace.z, pdf);
-                            prec(paths, R_TP, slot) = f4(throughput.x, throughput.y, throughput.z, throughput.w);
-                            alive = true;
-                        }
-                    }
-                }
-                storeSampler(sampler, paths, slot, hit.v, numRequests);
-                samplerStored = true;
-            } while (false);
-
-            if (!samplerStored && ubits(rSampler.w) != 0u) prec(paths, R_SAMPLER, slot).w = fbits(0u);   // the resolved requests are spent
-            prec(paths, R_RESULT, slot) = f4(resultColor.x, resultColor.y, resultColor.z, rResult.w);
-            if (!alive) cnt.c[C_RAYS] += depth + 1u;   // counters.numRays += depth + 1, PathTracerMIS.cpp:412
-        }
-
-        // Queue appends go through per-block LDS buffers: a returning atomic on ONE global word sustains only ~88
-        // operations per microsecond on this chip, so per-wave appends (hundreds of thousands per launch) would
-        // dominate the kernel; a block publishes ~RT_APPEND_BUFFER entries per global atomic instead.
-        for (unsigned long long pending = rayMask; pending != 0ull; pending &= pending - 1ull)
-        {
-            const uint32_t l = (uint32_t)(__ffsll((long long)pending) - 1);
-            sShadowBuf[atomicAdd(&sShadowCount, 1u)] = l * paths.capacity + slot;
-        }
-        if (alive) sPathBuf[atomicAdd(&sPathCount, 1u)] = slot;
-        __syncthreads();
-        // flush when the next iteration could overflow a buffer (wave-uniform decision on block-shared counters)
-        const bool last = (i - threadIdx.x) + stride >= rounded;
-        if (last || sPathCount + RT_BLOCK > RT_APPEND_BUFFER) flushAppendBuffer(sPathBuf, sPathCount, sPathBase, queueOut, countOut);
-        if (last || sShadowCount + RT_BLOCK * maxRequestsPerVertex > RT_APPEND_BUFFER) flushAppendBuffer(sShadowBuf, sShadowCount, sShadowBase, shadowQueue, shadowCount);
+        const float4 rResult = prec(paths, R_RESULT, slot);
+        V4 resultColor(rResult.x, rResult.y, rResult.z, 0.0f);
+        resolvePendingLightSamples(paths, slot, ubits(prec(paths, R_SAMPLER, slot).w), lightSamplingWeight, resultColor, cnt);
+        const float4 end = records[(size_t)slot * recordStride + (recordStride - 1u)];
+        infos[2u * slot] = f4(end.x, end.y, resultColor.x, resultColor.y);
+        infos[2u * slot + 1u] = f4(resultColor.z, 0.0f, 0.0f, 0.0f);
     }
     flushCounters(cnt, counters);
 }

@@ -13,6 +13,11 @@
                          const uint32_t* __restrict__ countIn, uint32_t* __restrict__ queueOut, uint32_t* __restrict__ countOut, uint32_t* __restrict__ shadowQueue, \
                          uint32_t* __restrict__ shadowCount, unsigned long long* counters)
 #define RT_K_SHADE_INSTANCES(X) X(false, false) X(false, true) X(true, false)
+// rtgpu_record_paths' variant of k_shade (rt_shade_body.inl): the same arguments, then the record buffer and a slot's stride in it (float4).  One
+// instantiation, the scene class "anything": a recording covers a handful of slots
+#define RT_K_SHADE_RECORD_ARGS (const RtSceneDesc scene, const DevPass* __restrict__ passes, uint32_t slotsPerPass, const Paths paths, const uint32_t* __restrict__ queueIn, \
+                                const uint32_t* __restrict__ countIn, uint32_t* __restrict__ queueOut, uint32_t* __restrict__ countOut, uint32_t* __restrict__ shadowQueue, \
+                                uint32_t* __restrict__ shadowCount, unsigned long long* counters, float4* __restrict__ records, uint32_t recordStride)
 
 
 // The bidirectional integrator's kernels that evaluate textures (normal maps, textured material parameters, an environment map) come in two scene
@@ -48,6 +53,10 @@ __global__ void __launch_bounds__(RT_BLOCK) k_shade(const RtSceneDesc scene, con
                                                     uint32_t* __restrict__ queueOut, uint32_t* __restrict__ countOut,
                                                     uint32_t* __restrict__ shadowQueue, uint32_t* __restrict__ shadowCount,
                                                     unsigned long long* counters);
+template <bool kLean, bool kPlain = false>
+__global__ void __launch_bounds__(RT_BLOCK) k_shade_record RT_K_SHADE_RECORD_ARGS;
+__global__ void __launch_bounds__(RT_BLOCK) k_paths_finish(const Paths paths, uint32_t numSlots, const DevPass* __restrict__ passes, const float4* __restrict__ records,
+                                                           uint32_t recordStride, float4* __restrict__ infos, unsigned long long* counters);
 __global__ void __launch_bounds__(RT_BLOCK) k_debug_shade(const RtSceneDesc scene, const Paths paths, const uint32_t* __restrict__ queueIn, const uint32_t* __restrict__ countIn,
                                                           uint32_t mode, unsigned long long* counters);
 __global__ void __launch_bounds__(RT_BLOCK) k_accumulate(const Paths paths, uint32_t slotsPerPass, uint32_t numPasses, float* __restrict__ sum,

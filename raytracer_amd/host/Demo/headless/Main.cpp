@@ -1,18 +1,21 @@
 // Headless counterpart of the reference's Demo (Demo/Main.cpp:6-40 takes -w/--width, -h/--height, -s/--scene, --renderer,
 // --data and opens a window): loads a JSON scene with helpers::LoadScene, renders N passes with the device "Path Tracer MIS"
 // through the same rt::Viewport API the window loop uses (Demo.cpp: Resize -> SetRenderer -> Render per frame ->
-// GetFrontBuffer) and writes the tone-mapped front buffer as a BMP.  The extra options are --passes, --depth, --output, --seed;
+// GetFrontBuffer) and writes the tone-mapped front buffer as a BMP.  The extra options are --passes, --depth, --output, --seed and
+// --debug-pixel X,Y (prints the path behind that pixel of pass 0, what the reference's Demo shows for a picked pixel: Demo_UserInterface.cpp:197-272);
 // the environment variable RTGPU_DEVICES ("0,1,2,3" / "all") spreads the frame over several GPUs (Core/Rendering/Renderer.h).
 #include "../Demo.h"
 #include "../SceneLoader.h"
 #include "../../Core/Rendering/Viewport.h"
 #include "../../Core/Rendering/Renderer.h"
+#include "../../Core/Rendering/PathTracerMIS.h"
 
 #include <stdio.h>
 #include <stdlib.h>
 #include <string.h>
 #include <chrono>
 #include <string>
+#include <vector>
 
 using namespace rt;
 
@@ -37,9 +40,40 @@ static bool SaveBMP(const char* path, const Bitmap& front)   // 24-bit, rows bot
     return ok;
 }
 
+// The path of pixel (x, y) of the pass `params` (rtgpu_record_paths), one line per vertex and the reason it ended
+static bool PrintPixelPath(IRenderer* renderer, const RtPassParams& params, uint32 x, uint32 y)
+{
+    static const char* const reasons[] = { "None", "HitBackground", "HitLight", "Depth", "Throughput", "NoSampledEvent", "RussianRoulette" };   // PathTerminationReason
+    PathTracerMIS* pt = dynamic_cast<PathTracerMIS*>(renderer);
+    if (!pt || !pt->UploadScene()) { fprintf(stderr, "--debug-pixel: the renderer has no device context\n"); return false; }
+    const uint32 pixel[2] = { x, y };
+    std::vector<RtPathVertex> vertices(params.maxRayDepth + 1u);
+    RtPathInfo info;
+    if (rtgpu_record_paths(pt->GetDeviceContext(), &params, pixel, 1u, (uint32)vertices.size(), vertices.data(), &info) != RTGPU_OK)
+    {
+        fprintf(stderr, "--debug-pixel: %s\n", rtgpu_last_error());
+        return false;
+    }
+    printf("pixel (%u, %u), pass %u: %u vertices, %s, radiance (%g, %g, %g)\n", x, y, params.passIndex, info.numVertices,
+           info.terminationReason < 7u ? reasons[info.terminationReason] : "?", (double)info.radiance[0], (double)info.radiance[1], (double)info.radiance[2]);
+    for (uint32 i = 0; i < info.numVertices && i < vertices.size(); ++i)
+    {
+        const float* w = vertices[i].w;
+        uint32 object, subObject, event;
+        memcpy(&object, w + 6, 4); memcpy(&subObject, w + 7, 4); memcpy(&event, w + 26, 4);
+        printf("  %u: origin (%g, %g, %g) dir (%g, %g, %g)", i, (double)w[0], (double)w[1], (double)w[2], (double)w[3], (double)w[4], (double)w[5]);
+        if (object == RT_INVALID_OBJECT) printf(" miss");
+        else printf(" object %u sub %s%u distance %g at (%g, %g, %g) normal (%g, %g, %g)", object, subObject == RT_LIGHT_OBJECT ? "light " : "", subObject == RT_LIGHT_OBJECT ? 0u : subObject,
+                    (double)w[8], (double)w[11], (double)w[12], (double)w[13], (double)w[14], (double)w[15], (double)w[16]);
+        printf(" throughput (%g, %g, %g) event %u\n", (double)w[22], (double)w[23], (double)w[24], event);
+    }
+    return true;
+}
+
 int main(int argc, char* argv[])
 {
     uint32 width = 1280, height = 720, passes = 64, depth = 20;
+    bool debugPixel = false; uint32 debugX = 0, debugY = 0;
     std::string scenePath, rendererName = "Path Tracer MIS", output = "out.bmp";
     unsigned long long seed = 0; bool haveSeed = false;
     for (int i = 1; i < argc; ++i)
@@ -55,7 +89,8 @@ int main(int argc, char* argv[])
         else if (a == "--depth") depth = (uint32)atoi(value("--depth"));
         else if (a == "--output") output = value("--output");
         else if (a == "--seed") { seed = strtoull(value("--seed"), nullptr, 10); haveSeed = true; }
-        else { fprintf(stderr, "usage: rt_demo -s scene.json [--data dir/] [-w W] [-h H] [--passes N] [--depth D] [--renderer name] [--output out.bmp] [--seed N]\n"); return 2; }
+        else if (a == "--debug-pixel") { if (sscanf(value("--debug-pixel"), "%u,%u", &debugX, &debugY) != 2) { fprintf(stderr, "--debug-pixel takes X,Y\n"); return 2; } debugPixel = true; }
+        else { fprintf(stderr, "usage: rt_demo -s scene.json [--data dir/] [-w W] [-h H] [--passes N] [--depth D] [--renderer name] [--output out.bmp] [--seed N] [--debug-pixel X,Y]\n"); return 2; }
     }
     if (scenePath.empty()) { fprintf(stderr, "no scene given (-s scene.json)\n"); return 2; }
 
@@ -76,7 +111,15 @@ int main(int argc, char* argv[])
     viewport.Reset();
 
     const auto t0 = std::chrono::steady_clock::now();
-    for (uint32 i = 0; i < passes; ++i) if (!viewport.Render(camera)) return 1;
+    uint32 rendered = 0;
+    if (debugPixel)
+    {
+        // pass 0 with its constants in hand: recorded for the pixel, then rendered as Render() would have
+        RtPassParams first;
+        if (!viewport.NextPassParams(camera, first) || !PrintPixelPath(renderer.get(), first, debugX, debugY)) return 1;
+        if (passes > 0) { if (!renderer->RenderPass(first)) return 1; viewport.FinishPass(); rendered = 1; }
+    }
+    for (uint32 i = rendered; i < passes; ++i) if (!viewport.Render(camera)) return 1;
     const RayTracingCounters counters = viewport.GetTotalCounters();   // synchronises
     const double seconds = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
     printf("%u passes of %ux%u in %.3f s: %.1f Msamples/s (%llu paths x bounces, %llu shadow rays), average error %g\n", passes, width, height, seconds,
