@@ -664,6 +664,11 @@ uint64_t rto_hash_grid_query(const float* points, uint32_t numPoints, float radi
 
 void rto_vcm_destroy(void* h) { delete static_cast<VcmRenderer*>(h); }
 uint32_t rto_vcm_num_photons(void* h) { return (uint32_t)static_cast<VcmRenderer*>(h)->recorded.size(); }
+// Optional per-pixel splat counter (test infrastructure, VcmRenderer::splatCounts): `counts` holds one word per pixel of the frames rendered from now on and
+// is incremented, never cleared; NULL turns it off again.  The light tracer has no handle: its counter is process-wide.
+void rto_vcm_set_splat_counts(void* h, uint32_t* counts) { static_cast<VcmRenderer*>(h)->splatCounts = counts; }
+static uint32_t* g_lightTracerSplatCounts = nullptr;
+void rto_light_tracer_set_splat_counts(uint32_t* counts) { g_lightTracerSplatCounts = counts; }
 
 // One pass over the whole film, pixels in row-major order.  Camera-path radiance goes to sum (+ secondarySum when non-null);
 // light-path splats go to lightSum when it is non-null (so the two estimators can be compared separately), else to sum.
@@ -721,7 +726,7 @@ static int vcmRenderPassImpl(void* h, const RtSceneDesc* scene, const RtPassPara
 int rto_light_tracer_render_pass(const RtSceneDesc* scene, const RtPassParams* params, uint32_t width, uint32_t height, float* sum, float* secondarySum, uint64_t* counters)
 {
     Counters c; memset(&c, 0, sizeof(c));
-    VcmRenderer dummy;
+    VcmRenderer dummy; dummy.splatCounts = g_lightTracerSplatCounts;
     VcmCtx* ctx = new VcmCtx();
     ctx->scene = scene; ctx->params = params; ctx->r = &dummy; ctx->counters = &c;
     ctx->width = width; ctx->height = height; ctx->sum = sum; ctx->secondarySum = secondarySum;

@@ -234,6 +234,10 @@ struct VcmRenderer
     std::vector<Photon> photons;          // mPhotons: what the previous pass recorded
     std::vector<Photon> recorded;         // the per-thread lists, concatenated in pixel order
     HashGrid hashGrid;
+    // test infrastructure (rto_vcm_set_splat_counts / rto_light_tracer_set_splat_counts): when non-null, width x height words; every film splat that lands
+    // on a pixel adds one to that pixel's word.  Says how many float terms a pixel of the light image is the sum of, which bounds what the order of a device's
+    // float atomics can change (two orders of adding n non-negative float32 terms differ by at most about 2 n 2^-24 of their sum).  Changes no result.
+    uint32_t* splatCounts = nullptr;
 
     void preRender(uint32_t passNumber, uint32_t width, uint32_t height)
     {
@@ -364,6 +368,7 @@ static inline void vcmSplat(VcmCtx& ctx, V4 filmPos, V4 value, V4 jitter)
 {
     uint32_t x, y;
     if (!filmSplatPixel(filmPos, ctx.width, ctx.height, jitter, x, y)) return;
+    if (ctx.r->splatCounts) ctx.r->splatCounts[(size_t)y * ctx.width + x]++;
     float* p = ctx.sum + 3 * ((size_t)y * ctx.width + x);
     p[0] = p[0] + value.x; p[1] = p[1] + value.y; p[2] = p[2] + value.z;
     if (ctx.secondarySum) { float* q = ctx.secondarySum + 3 * ((size_t)y * ctx.width + x); q[0] = q[0] + value.x; q[1] = q[1] + value.y; q[2] = q[2] + value.z; }

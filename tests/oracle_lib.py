@@ -109,6 +109,12 @@ class Vcm:
     def num_photons(self):
         return int(lib().rto_vcm_num_photons(self._h))
 
+    def set_splat_counts(self, counts):
+        """counts: (H, W) uint32, kept alive here; every film splat of the passes to come adds one to the pixel it lands on (None: off)."""
+        assert counts is None or (counts.dtype == np.uint32 and counts.flags["C_CONTIGUOUS"])
+        self._splat_counts = counts
+        lib().rto_vcm_set_splat_counts(self._h, counts.ctypes.data_as(C.POINTER(C.c_uint32)) if counts is not None else None)
+
     def render_pass(self, scene_desc_ptr, params, width, height, sum_buf, secondary=None, light_sum=None, counters=None, shard=(0, 1)):
         """shard = (rank, world): only the pixels of the 64x64 tiles with tile % world == rank (exact for the camera paths with merging off)"""
         if counters is None:
@@ -146,6 +152,12 @@ def light_tracer_pass(scene_desc_ptr, params, width, height, sum_buf, secondary=
     if r != 0:
         raise RuntimeError("rto_light_tracer_render_pass failed")
     return counters
+
+
+def light_tracer_set_splat_counts(counts):
+    """The light tracer's per-pixel splat counter ((H, W) uint32, process-wide; the caller keeps the array alive and passes None when done)."""
+    assert counts is None or (counts.dtype == np.uint32 and counts.flags["C_CONTIGUOUS"])
+    lib().rto_light_tracer_set_splat_counts(counts.ctypes.data_as(C.POINTER(C.c_uint32)) if counts is not None else None)
 
 
 def hash_grid_query(points, radius, queries, capacity=1 << 22):
