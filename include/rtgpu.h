@@ -443,7 +443,8 @@ typedef enum RtIntegrator
                                      * convention and whole-frame requirement as VCM */
 } RtIntegrator;
 /* rt::DebugRenderingMode (Core/Rendering/DebugRenderer.h:7-33; the four intersection-counter modes exist in the reference only under
- * RT_ENABLE_INTERSECTION_COUNTERS, which is off, and are not provided) */
+ * RT_ENABLE_INTERSECTION_COUNTERS, which is off: their raw values per pixel are the cost planes of rtgpu_render_aovs, RT_AOV_BOX_TESTS ..
+ * RT_AOV_TRIANGLE_TESTS_PASSED) */
 typedef enum RtDebugRenderingMode
 {
     RT_DEBUG_CAMERA_LIGHT = 0, RT_DEBUG_TRIANGLE_ID, RT_DEBUG_DEPTH, RT_DEBUG_POSITION, RT_DEBUG_NORMALS, RT_DEBUG_TANGENTS, RT_DEBUG_BITANGENTS,
@@ -631,6 +632,51 @@ typedef struct RtPathVertex { float w[28]; } RtPathVertex;   /* 112 bytes */
 typedef struct RtPathInfo { uint32_t numVertices, terminationReason; float radiance[3]; uint32_t _pad[3]; } RtPathInfo;   /* 32 bytes */
 int rtgpu_record_paths(RtgpuContext* ctx, const RtPassParams* params, const uint32_t* pixelsXY /* 2 per pixel */, uint32_t numPixels,
                        uint32_t maxVertices, RtPathVertex* vertices /* [numPixels * maxVertices] */, RtPathInfo* infos /* [numPixels] */);
+
+/* ---------------------------------------------------------------------------------------------
+ * AOVs: what the primary ray of every pixel finds, as raw planes in one call -- first-hit geometry, the evaluated material and the cost of
+ * the traversal.  For every pixel of the frame the call generates the primary ray rtgpu_render_pass(ctx, params) would generate for it (the
+ * same sampler draws: depth of field, bokeh, barrel distortion), traces it (Scene::Traverse from +inf) and evaluates
+ * Scene::EvaluateIntersection and Material::EvaluateShadingData at the hit -- the values the debug modes (RtDebugRenderingMode) squeeze into
+ * a display colour, unsqueezed.
+ *   layout     outputs[k] receives plane planes[k] channel-major: channels x height x width 32-bit words (a (C, H, W) tensor); row y is
+ *              sum-buffer row y, as in RtBlock (the film row flips inside).
+ *   values     on a miss everything is 0 except DEPTH (+inf), OBJECT_ID (RT_INVALID_OBJECT) and MATERIAL (RT_NO_MATERIAL).  On a finite
+ *              light the geometry planes hold what Scene::EvaluateIntersection returns, the material planes 0 and MATERIAL RT_NO_MATERIAL.
+ *              The four cost planes are the reference's ctx.localCounters after that one Traverse, counted as RtCounters::numRayBoxTests ..
+ *              numPassedRayTriangleTests are (they walk the reference's binary tree whatever the context renders with; without them the
+ *              call takes the walk the context renders with).
+ *   errors     numPlanes == 0 is a no-op; NULL arguments with numPlanes > 0, a plane id >= RT_AOV_NUM_PLANES or the same plane twice:
+ *              RTGPU_ERR_INVALID_ARGUMENT; what rtgpu_render_pass refuses in the params gets the status it gets there; before
+ *              rtgpu_upload_scene / rtgpu_resize: RTGPU_ERR_NOT_READY.
+ * It submits the passes queued on the device it answers on first, is not a pass, and leaves film, sum buffers, counters, kernel times and the photon state alone.  It
+ * works whichever integrator is selected; shards and active blocks do not restrict it, and a multi-device context answers on its first
+ * device.  Arena and queues are its own (grown on use, freed with the context); a chunk holds at most 4 M pixels (RTGPU_AOV_CHUNK),
+ * larger frames run chunk by chunk.
+ * --------------------------------------------------------------------------------------------- */
+typedef enum RtAovPlane {            /* words per pixel, type */
+    RT_AOV_DEPTH = 0,                /* 1 f32  HitPoint::distance; +inf on a miss            */
+    RT_AOV_POSITION,                 /* 3 f32  frame[3]                                      */
+    RT_AOV_NORMAL,                   /* 3 f32  frame[2] (normal map applied)                 */
+    RT_AOV_TANGENT,                  /* 3 f32  frame[0]                                      */
+    RT_AOV_BITANGENT,                /* 3 f32  frame[1]                                      */
+    RT_AOV_TEXCOORD,                 /* 2 f32                                                */
+    RT_AOV_BARYCENTRICS,             /* 2 f32  HitPoint u, v (0 off mesh triangles)          */
+    RT_AOV_BASE_COLOR,               /* 3 f32  ShadingData::materialParams after textures    */
+    RT_AOV_EMISSION,                 /* 3 f32                                                */
+    RT_AOV_ROUGHNESS, RT_AOV_METALNESS, RT_AOV_IOR,   /* 1 f32 each                          */
+    RT_AOV_OBJECT_ID,                /* 1 u32  RT_INVALID_OBJECT on a miss                   */
+    RT_AOV_SUB_OBJECT_ID,            /* 1 u32  triangle; RT_LIGHT_OBJECT on a finite light   */
+    RT_AOV_MATERIAL,                 /* 1 u32  global material index; RT_NO_MATERIAL on a miss or a light */
+    RT_AOV_BOX_TESTS, RT_AOV_BOX_TESTS_PASSED, RT_AOV_TRIANGLE_TESTS, RT_AOV_TRIANGLE_TESTS_PASSED,  /* 1 u32 each */
+    RT_AOV_NUM_PLANES
+} RtAovPlane;
+/* Host pointers; synchronous. */
+int rtgpu_render_aovs(RtgpuContext* ctx, const RtPassParams* params, const uint32_t* planes, uint32_t numPlanes, void* const* outputs);
+/* Device pointers (16-byte aligned) on `stream` (a hipStream_t; NULL: the context's own stream): ordered after the work already queued
+ * there, returns without synchronising.  `planes`, `outputs` and `params` themselves are host memory and may be reused on return. */
+int rtgpu_render_aovs_async(RtgpuContext* ctx, const RtPassParams* params, const uint32_t* planes, uint32_t numPlanes, void* const* outputs,
+                            void* stream);
 
 /* Known-answer-test hooks.  They evaluate the DEVICE implementation of one hot-path function (the code the traversal and shading
  * kernels call, rt_device_*.h) on caller-provided records, so that tests can hold the HIP functions directly against vectors produced

@@ -198,6 +198,15 @@ COUNTER_NAMES = ("numRays", "numShadowRays", "numShadowRaysHit", "numPrimaryRays
                  "numRayTriangleTests", "numPassedRayTriangleTests", "numMeshHits", "numAnalyticHits", "numShadowRayBoxTests",
                  "numShadowRayTriangleTests", "numRetracedRays")
 
+# RtAovPlane (include/rtgpu.h): name -> (id, channels, dtype), in the enum's order
+AOV_PLANES = collections.OrderedDict(
+    (name, (i, channels, dtype)) for i, (name, channels, dtype) in enumerate((
+        ("depth", 1, np.float32), ("position", 3, np.float32), ("normal", 3, np.float32), ("tangent", 3, np.float32), ("bitangent", 3, np.float32),
+        ("texcoord", 2, np.float32), ("barycentrics", 2, np.float32), ("base_color", 3, np.float32), ("emission", 3, np.float32),
+        ("roughness", 1, np.float32), ("metalness", 1, np.float32), ("ior", 1, np.float32), ("object_id", 1, np.uint32),
+        ("sub_object_id", 1, np.uint32), ("material", 1, np.uint32), ("box_tests", 1, np.uint32), ("box_tests_passed", 1, np.uint32),
+        ("triangle_tests", 1, np.uint32), ("triangle_tests_passed", 1, np.uint32))))
+
 BSDF_NAMES = ("null", "diffuse", "roughDiffuse", "dielectric", "roughDielectric", "metal", "roughMetal", "plastic", "roughPlastic")
 
 
@@ -720,6 +729,60 @@ class Viewport:
             raise (ValueError if r == -1 else RuntimeError)("record_paths failed (%d): %s" % (r, err))
         radiance = infos[:, 2:5].view(np.float32)
         return [(vertices[i, :min(int(infos[i, 0]), capacity)].copy(), int(infos[i, 1]), radiance[i].copy()) for i in range(n)]
+
+    # ---- AOVs (include/rtgpu.h: rtgpu_render_aovs / rtgpu_render_aovs_async) -------------------------------------------------------------
+    def render_aovs(self, params, planes=("depth", "normal", "base_color"), device=False):
+        """What the primary ray of every pixel finds, as raw planes from one call: `planes` names them (AOV_PLANES: first-hit geometry, the
+        evaluated material, ids, and the box / triangle tests of the traversal).  Returns a dict name -> array, (H, W) for a one-channel plane and
+        (C, H, W) otherwise, row y as in sum_buffer(); float planes are float32, id and cost planes uint32.  device=True: torch tensors on the
+        renderer's ROCm device, produced on torch.cuda.current_stream() without a host copy (ids and costs int64, as trace_rays returns them).
+        `params` is an RtPassParams from next_pass_params(): the rays are those the pass would trace (the same lens samples), the call renders
+        nothing and is not a pass.  A Camera is not accepted, for the reason record_paths gives."""
+        if not isinstance(params, RtPassParams):
+            raise TypeError("render_aovs takes the RtPassParams of next_pass_params(camera), not %s" % type(params).__name__)
+        names = [planes] if isinstance(planes, str) else list(planes)
+        for name in names:
+            if name not in AOV_PLANES:
+                raise ValueError("unknown AOV plane %r (AOV_PLANES lists them)" % (name,))
+        if not self.has_renderer:
+            raise RuntimeError("render_aovs needs a renderer: call set_renderer first")
+        ctx = self.device_context()
+        if not ctx.value or host_lib().rth_viewport_upload_scene(self._h) != 0:
+            raise RuntimeError("the viewport's renderer has no device context or its scene could not be uploaded: %s" % (rtgpu_lib().rtgpu_last_error() or b"").decode())
+        lib = rtgpu_lib()
+        n = len(names)
+        ids = (C.c_uint32 * max(n, 1))(*[AOV_PLANES[name][0] for name in names])
+        h, w = self.height, self.width
+        shape = lambda name: (h, w) if AOV_PLANES[name][1] == 1 else (AOV_PLANES[name][1], h, w)   # noqa: E731
+        if not device:
+            out = collections.OrderedDict((name, np.zeros(shape(name), dtype=AOV_PLANES[name][2])) for name in names)
+            ptrs = (C.c_void_p * max(n, 1))(*[out[name].ctypes.data for name in names])
+            r = lib.rtgpu_render_aovs(ctx, C.byref(params), ids, C.c_uint32(n), ptrs)
+        else:
+            import torch
+            dev = torch.device("cuda", multi_info(ctx)["devices"][0])
+            raw = collections.OrderedDict((name, torch.empty(shape(name), dtype=torch.float32 if AOV_PLANES[name][2] is np.float32 else torch.int32, device=dev))
+                                          for name in names)
+            ptrs = (C.c_void_p * max(n, 1))(*[raw[name].data_ptr() for name in names])
+            current = torch.cuda.current_stream(dev)
+            if current.cuda_stream != 0:
+                r = lib.rtgpu_render_aovs_async(ctx, C.byref(params), ids, C.c_uint32(n), ptrs, C.c_void_p(current.cuda_stream))
+            else:
+                # torch's default stream is the null stream, which means the context's own to the async entry point: a side stream, as in _query
+                if getattr(self, "_query_stream", None) is None or self._query_stream.device != dev:
+                    self._query_stream = torch.cuda.Stream(dev)
+                side = self._query_stream
+                side.wait_stream(current)
+                r = lib.rtgpu_render_aovs_async(ctx, C.byref(params), ids, C.c_uint32(n), ptrs, C.c_void_p(side.cuda_stream))
+                current.wait_stream(side)
+                for t in raw.values():
+                    t.record_stream(side)
+        if r != 0:
+            err = (lib.rtgpu_last_error() or b"").decode()
+            raise (ValueError if r == -1 else RuntimeError)("render_aovs failed (%d): %s" % (r, err))
+        if device:
+            out = collections.OrderedDict((name, t if t.dtype == torch.float32 else _u32(torch, t)) for name, t in raw.items())
+        return out
 
     @property
     def passes_finished(self):

@@ -72,6 +72,8 @@ static inline bool packets() { return envInt("RTGPU_PACKET", 1) != 0; }
 // every re-trace launch
 static inline int abortRetraceAfter() { return envInt("RTGPU_ABORT_RETRACE_AFTER", -1); }   // test hook; < 0: RT_ABORT_RETRACE_AFTER
 static inline bool retraceMonsters() { return envSet("RTGPU_RETRACE_MONSTERS") ? envInt("RTGPU_RETRACE_MONSTERS", 0) != 0 : envSet("RTGPU_ABORT_RETRACE_AFTER"); }
+// every rtgpu_render_aovs: pixels per chunk, 1 .. 4 M (the tests run a small frame in several chunks)
+static inline uint32_t aovChunk() { const int v = envInt("RTGPU_AOV_CHUNK", 1 << 22); return v < 1 ? 1u : (v > (1 << 22) ? (1u << 22) : (uint32_t)v); }
 // every rtgpu_upload_scene
 static inline bool noLean() { return envInt("RTGPU_NO_LEAN", 0) != 0; }
 static inline bool noSimpleTextures() { return envInt("RTGPU_NO_SIMPLE_TEXTURES", 0) != 0; }

@@ -27,7 +27,8 @@
 // This file is the translation unit and keeps the contexts, the film and the small entry points; its parts: rt_runtime_context.h (RtgpuContext, BatchLane,
 // staging copies, stream pool, HIP_TRY, LaunchTimer, free helpers), rt_knobs.h (every RTGPU_* environment variable), rt_multi.inl (multi-device contexts),
 // rt_runtime_scene.inl (rtgpu_upload_scene), rt_runtime_render.inl (arena sizing, traversal launchers, batch submission), rt_runtime_vcm.inl (bidirectional
-// integrator, Light Tracer), rt_runtime_kat.inl (known-answer hooks, rtgpu_evaluate_textures), rt_runtime_query.inl (batched ray queries), rt_runtime_paths.inl (path records).
+// integrator, Light Tracer), rt_runtime_kat.inl (known-answer hooks, rtgpu_evaluate_textures), rt_runtime_query.inl (batched ray queries), rt_runtime_paths.inl (path records),
+// rt_runtime_aov.inl (AOVs).
 //
 // Compile: hipcc --offload-arch=gfx950 -O3 -ffp-contract=off
 #include "rt_trace_common.h"
@@ -198,6 +199,7 @@ RTGPU_API void rtgpu_destroy(RtgpuContext* c)
     devFree(c->gatherStage);
     freeQuery(c);
     freeRecorder(c);
+    freeAov(c);
     freeScene(c); freeFilm(c);
     for (uint32_t i = 0; i < RT_MAX_LANES; ++i)
     {
@@ -686,6 +688,7 @@ RTGPU_API int rtgpu_postprocess(RtgpuContext* c, const RtPostprocessParams* p, u
 #include "rt_runtime_kat.inl"
 #include "rt_runtime_query.inl"
 #include "rt_runtime_paths.inl"
+#include "rt_runtime_aov.inl"
 
 RTGPU_API int rtgpu_set_concurrency(RtgpuContext* c, uint32_t lanes)
 {

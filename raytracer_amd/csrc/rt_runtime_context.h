@@ -241,6 +241,25 @@ struct RtgpuContext
         DevPass* passDev = nullptr; uint32_t* seedDev = nullptr;   // the recorded pass
     } recorder;
 
+    // AOVs (rtgpu_render_aovs): the first bounce of the slot-per-pixel pipeline over a chunk of the frame's pixels, on an arena, queues, work counts and counters
+    // of its own -- never a lane's, never c->counters, never the seed ring
+    struct Aov
+    {
+        Paths paths = { nullptr, 0, 0 };          // maxLights = 1; capacity = the pixels of one chunk
+        uint32_t* queue = nullptr;                // the chunk's primary rays (the identity)
+        uint32_t* exactQueue = nullptr; uint32_t* exactShadowQueue = nullptr;   // what the 4-wide walks hand to the re-trace launch
+        uint32_t* slotPixel = nullptr;            // slot -> pixel of the chunk (k_aov_pixels)
+        uint4* rayCounts = nullptr;               // per slot what the counting walk counted for its ray (TravTuning::rayCounts); allocated with the first cost plane
+        uint32_t* staged = nullptr; size_t stagedWords = 0;   // rtgpu_render_aovs' device copy of a chunk's planes
+        uint32_t* counts = nullptr;               // QC_WORDS work counts (QC_*, rt_runtime_query.inl)
+        unsigned long long* counters = nullptr;   // 16 x u64, never read
+        DevPass* passDev = nullptr; uint32_t* seedDev = nullptr;   // the pass whose primary rays are traced
+        // pass constants and seeds travel through a small ring of page-locked records: an asynchronous call returns before its copy has run
+        static const uint32_t kRing = 4;
+        char* ringHost = nullptr; hipEvent_t ringCopied[kRing] = { nullptr, nullptr, nullptr, nullptr }; uint32_t ringCursor = 0;
+        hipEvent_t done = nullptr;                // recorded behind every call: the next one (whatever its stream) and a new arena wait for it
+    } aov;
+
     // timing
     bool timing = false;
     struct Timed { int kc; hipEvent_t a, b; };
@@ -317,7 +336,11 @@ struct LaunchTimer
     }
 };
 
-static void waitQueries(RtgpuContext* c) { if (c->query.done) (void)hipEventSynchronize(c->query.done); }
+static void waitQueries(RtgpuContext* c)
+{
+    if (c->query.done) (void)hipEventSynchronize(c->query.done);
+    if (c->aov.done) (void)hipEventSynchronize(c->aov.done);   // (an asynchronous AOV call walks the scene as a query does)
+}
 static void freeQueryArena(RtgpuContext* c)
 {
     RtgpuContext::Query& q = c->query;
@@ -332,6 +355,26 @@ static void freeQuery(RtgpuContext* c)
     devFree(q.counts, q.counters);
     if (q.done) (void)hipEventDestroy(q.done);
     q.done = nullptr;
+}
+
+static void freeAovArena(RtgpuContext* c)
+{
+    RtgpuContext::Aov& a = c->aov;
+    if (a.done) (void)hipEventSynchronize(a.done);
+    devFree(a.paths.base, a.queue, a.exactQueue, a.exactShadowQueue, a.slotPixel, a.rayCounts);
+    a.paths.capacity = 0; a.paths.maxLights = 0;
+}
+static void freeAov(RtgpuContext* c)
+{
+    RtgpuContext::Aov& a = c->aov;
+    freeAovArena(c);
+    devFree(a.staged, a.counts, a.counters, a.passDev, a.seedDev);
+    a.stagedWords = 0;
+    if (a.ringHost) (void)hipHostFree(a.ringHost);
+    a.ringHost = nullptr;
+    for (uint32_t i = 0; i < RtgpuContext::Aov::kRing; ++i) { if (a.ringCopied[i]) (void)hipEventDestroy(a.ringCopied[i]); a.ringCopied[i] = nullptr; }
+    if (a.done) (void)hipEventDestroy(a.done);
+    a.done = nullptr;
 }
 
 static void freeRecorder(RtgpuContext* c)

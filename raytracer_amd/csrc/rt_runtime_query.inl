@@ -29,6 +29,25 @@ static int ensureQueryArena(RtgpuContext* c, uint32_t rays)
     return RTGPU_OK;
 }
 
+// The walk over an arena of the library's own (ray queries, AOVs): one queue of closest-hit rays or of any-hit requests, work counts laid out as QC_*.
+// `wide`: the render path's pair -- the 4-wide walk hands the rays it does not decide to the re-trace launch (which alone gives them a result); no
+// block-local second walk and no k_trace_monster hand-over, neither changes a result.  Otherwise the reference's binary walk (k_trace), counting where the
+// context counts or `rayCounts` (TravTuning::rayCounts: every closest-hit ray's own counts) is asked for.  Rays start where the caller put them: no offset.
+static void launchArenaWalk(RtgpuContext* c, hipStream_t stream, unsigned long long* counters, const Paths& paths, const uint32_t* tq, const uint32_t* tqc, const uint32_t* tsq,
+                            const uint32_t* tsc, uint32_t* counts, uint32_t* exactQueue, uint32_t* exactShadowQueue, bool wide, uint4* rayCounts)
+{
+    if (wide)
+    {
+        launchTraceWide(c, stream, counters, paths, tq, tqc, tsq, tsc, counts + QC_CURSOR, exactQueue, counts + QC_EXACT, exactShadowQueue, counts + QC_EXACT_SHADOW, 0.0f, nullptr, 0u, false);
+        launchRetrace(c, stream, counters, paths, exactQueue, counts + QC_EXACT, exactShadowQueue, counts + QC_EXACT_SHADOW, counts + QC_EXACT_CURSOR, nullptr, nullptr);
+        return;
+    }
+    TravTuning tune = c->tune;
+    tune.shadowOffset = 0.0f; tune.overflowQueue = nullptr; tune.overflowCount = nullptr; tune.denseCounts = nullptr; tune.denseShardCapacity = 0u;
+    tune.rayCounts = rayCounts;
+    launchTraceBinary(c, stream, dim3(traversalBlocks(c, stackClassOf(c))), counters, paths, tq, tqc, tsq, tsc, counts + QC_CURSOR, tune, rayCounts != nullptr || c->countIntersections);
+}
+
 // the launches of one chunk (n <= the arena's capacity), device pointers, on `stream`
 static int launchQueryChunk(RtgpuContext* c, hipStream_t stream, uint32_t mode, const float4* rays, uint32_t n, float4* hits, float4* surfaces, uint32_t* occluded)
 {
@@ -43,21 +62,7 @@ static int launchQueryChunk(RtgpuContext* c, hipStream_t stream, uint32_t mode, 
     // integrators ask about (tmax = 0.999 x the light's distance: no triangle within an ulp of it), but a query's maxDistance may sit an ulp below a
     // hit, and there the conservative leaf gate of the 4-wide walks let 6 % of such rays report an occluder the reference's box test culls (DESIGN.md,
     // "Ray queries").
-    if (useWide(c) && closest)
-    {
-        // the render path's pair: the 4-wide walk hands the rays it does not decide to the re-trace launch (which alone gives them a result).  No
-        // block-local second walk and no k_trace_monster hand-over: neither changes a result.
-        launchTraceWide(c, stream, q.counters, q.paths, tq, tqc, tsq, tsc, q.counts + QC_CURSOR, q.exactQueue, q.counts + QC_EXACT, q.exactShadowQueue,
-                        q.counts + QC_EXACT_SHADOW, 0.0f, nullptr, 0u, false);
-        launchRetrace(c, stream, q.counters, q.paths, q.exactQueue, q.counts + QC_EXACT, q.exactShadowQueue, q.counts + QC_EXACT_SHADOW, q.counts + QC_EXACT_CURSOR,
-                      nullptr, nullptr);
-    }
-    else
-    {
-        TravTuning tune = c->tune;
-        tune.shadowOffset = 0.0f; tune.overflowQueue = nullptr; tune.overflowCount = nullptr; tune.denseCounts = nullptr; tune.denseShardCapacity = 0u;
-        launchTraceBinary(c, stream, dim3(traversalBlocks(c, stackClassOf(c))), q.counters, q.paths, tq, tqc, tsq, tsc, q.counts + QC_CURSOR, tune, c->countIntersections);
-    }
+    launchArenaWalk(c, stream, q.counters, q.paths, tq, tqc, tsq, tsc, q.counts, q.exactQueue, q.exactShadowQueue, useWide(c) && closest, nullptr);
     hipLaunchKernelGGL(k_query_store, grid, block, 0, stream, c->sceneDev, rays, n, mode, q.paths, hits, occluded);
     if (surfaces) hipLaunchKernelGGL(k_query_evaluate, grid, block, 0, stream, c->sceneDev, rays, n, (const float4*)hits, surfaces, q.counters);
     HIP_TRY(hipGetLastError());

@@ -105,13 +105,19 @@ static uint32_t traversalBlocks(const RtgpuContext* c, uint32_t stackClass)
 }
 
 // The reference's walk over the binary trees (k_trace): the one place that picks its instantiation.  The caller sets up `tune`, chooses the grid and
-// times the launch; `counting`: with the box / triangle test counters.
+// times the launch; `counting`: with the box / triangle test counters (and, where tune.rayCounts is set, every ray's own counts).
 static void launchTraceBinary(RtgpuContext* c, hipStream_t stream, dim3 grid, unsigned long long* counters, const Paths& paths, const uint32_t* tq, const uint32_t* tqc,
                               const uint32_t* tsq, const uint32_t* tsc, uint32_t* cursor, const TravTuning& tune, bool counting)
 {
     const uint32_t stackClass = stackClassOf(c);
 #define RT_LAUNCH_TRACE(S, C) hipLaunchKernelGGL((k_trace<S, C>), grid, dim3(RT_BLOCK), 0, stream, c->sceneDev, paths, tq, tqc, tsq, tsc, cursor, counters, tune)
-    if (stackClass == 24u) { if (counting) RT_LAUNCH_TRACE(24, true); else RT_LAUNCH_TRACE(24, false); }
+    if (counting && tune.rayCounts)
+    {
+        if (stackClass == 24u) hipLaunchKernelGGL((k_trace<24, true, true>), grid, dim3(RT_BLOCK), 0, stream, c->sceneDev, paths, tq, tqc, tsq, tsc, cursor, counters, tune);
+        else if (stackClass == 32u) hipLaunchKernelGGL((k_trace<32, true, true>), grid, dim3(RT_BLOCK), 0, stream, c->sceneDev, paths, tq, tqc, tsq, tsc, cursor, counters, tune);
+        else hipLaunchKernelGGL((k_trace<64, true, true>), grid, dim3(RT_BLOCK), 0, stream, c->sceneDev, paths, tq, tqc, tsq, tsc, cursor, counters, tune);
+    }
+    else if (stackClass == 24u) { if (counting) RT_LAUNCH_TRACE(24, true); else RT_LAUNCH_TRACE(24, false); }
     else if (stackClass == 32u) { if (counting) RT_LAUNCH_TRACE(32, true); else RT_LAUNCH_TRACE(32, false); }
     else { if (counting) RT_LAUNCH_TRACE(64, true); else RT_LAUNCH_TRACE(64, false); }
 #undef RT_LAUNCH_TRACE

@@ -41,7 +41,7 @@ RTGPU_API int rtgpu_upload_scene(RtgpuContext* c, const RtSceneDesc* s)
     HIP_TRY(hipSetDevice(c->device));
     { int fr = flushPending(c); if (fr) return fr; }
     HIP_TRY(syncLanes(c));
-    waitQueries(c);   // an asynchronous ray query may still walk the old scene
+    waitQueries(c);   // an asynchronous ray query or AOV call may still walk the old scene
 
     // validation: indices in range, stacks deep enough
     if (s->numObjects > 1 && s->numTopNodes == 0) return fail(RTGPU_ERR_INVALID_ARGUMENT, "scene with more than one object needs a top-level BVH");

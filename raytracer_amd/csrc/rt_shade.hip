@@ -1,5 +1,6 @@
 // rt_shade.hip -- the shading kernels of the library, a translation unit of their own: PathTracerMIS / PathTracer / Debug shading over
-// slot-per-pixel and dense path state (rt_shade.inl with rt_shade_body.inl, rt_dense.inl) and the bidirectional integrator's kernels (rt_vcm.inl).  The host side
+// slot-per-pixel and dense path state (rt_shade.inl with rt_shade_body.inl, rt_dense.inl), the bidirectional integrator's kernels (rt_vcm.inl) and the
+// resolve kernel of rtgpu_render_aovs (rt_aov.inl).  The host side
 // (rt_runtime.hip) launches them through the declarations of rt_shade_kernels.h.
 //
 // Why its own unit: it is compiled with -mllvm -simplifycfg-sink-common=false.  SimplifyCFG's common-code sinking merges the stores that
@@ -15,6 +16,7 @@
 #include "rt_shade.inl"
 #include "rt_dense.inl"
 #include "rt_vcm.inl"
+#include "rt_aov.inl"
 
 // the instantiations the host side launches (the lists are in rt_shade_kernels.h)
 #define RT_X(L, P, A) template __global__ void RT_SHADE_DENSE_ATTR(L, A) k_shade_dense<L, P, A> RT_K_SHADE_DENSE_ARGS;
@@ -29,4 +31,7 @@ template __global__ void __launch_bounds__(RT_BLOCK) k_shade_record<false, false
                 template __global__ void __launch_bounds__(RT_BLOCK) k_lt_shade<C> RT_K_LT_SHADE_ARGS; \
                 template __global__ void __launch_bounds__(RT_BLOCK) k_vcm_camera_shade<C> RT_K_VCM_CAMERA_SHADE_ARGS;
 RT_VCM_CLASSES(RT_X)
+#undef RT_X
+#define RT_X(C) template __global__ void __launch_bounds__(RT_BLOCK) k_aov_resolve<C> RT_K_AOV_RESOLVE_ARGS;
+RT_AOV_CLASSES(RT_X)
 #undef RT_X

@@ -34,7 +34,7 @@ using namespace rtd;
 #include "rt_post.inl"
 
 // the instantiations the host side launches
-#define RT_X(S, C) template __global__ void RT_TRACE_ATTR(S) k_trace<S, C> RT_K_TRACE_ARGS;
+#define RT_X(S, C) template __global__ void RT_TRACE_ATTR(S) k_trace<S, C, false> RT_K_TRACE_ARGS;
 RT_K_TRACE_INSTANCES(RT_X)
 #undef RT_X
 #define RT_X(S, D, L) template __global__ void RT_TRACE_ATTR(S) k_trace_wide<S, D, L> RT_K_TRACE_WIDE_ARGS;
@@ -42,4 +42,8 @@ RT_K_TRACE_WIDE_INSTANCES(RT_X)
 #undef RT_X
 #define RT_X(S) template __global__ void RT_TRACE_ATTR(S) k_trace_wide2<S> RT_K_TRACE_WIDE2_ARGS;
 RT_K_TRACE_WIDE2_INSTANCES(RT_X)
+#undef RT_X
+// (last: the kernels above keep the places in the code object that they had before these existed)
+#define RT_X(S) template __global__ void RT_TRACE_ATTR(S) k_trace<S, true, true> RT_K_TRACE_ARGS;
+RT_K_TRACE_PER_RAY_INSTANCES(RT_X)
 #undef RT_X

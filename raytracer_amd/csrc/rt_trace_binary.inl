@@ -12,7 +12,13 @@
 // The loop itself is a device function: k_trace runs it over the launch's queues with its own LDS; k_trace_wide runs it over the block's own
 // list of undecided rays when its walk is done (rt_trace_wide.inl), and k_tail between its block-local trace and shade phases (rt_tail.hip).
 // `queue`, `shadowQueue`, the counts and `cursor` may live in LDS (generic pointers); `sharingWaves` = the waves that claim from `cursor`.
-template <int kStack, bool kCount>
+// kPerRay (a counting walk with TravTuning::rayCounts set, rtgpu_render_aovs' cost planes): the lane's C_BOX .. C_TRI_PASS tallies when it took its current ray.
+// They live in LDS, a column per lane like the stack: four more registers took the 24-entry counting walk from 44 to 100 bytes of scratch per lane, and as an
+// instantiation of its own it leaves the counting walk the renderers use as it was.  The other instantiations have no such array.
+template <bool kPerRay> struct CountsAtRefill { __device__ __forceinline__ static uint32_t* lds() { return nullptr; } };
+template <> struct CountsAtRefill<true> { __device__ __forceinline__ static uint32_t* lds() { __shared__ uint32_t sCountsAtRefill[4 * RT_BLOCK]; return sCountsAtRefill; } };
+
+template <int kStack, bool kCount, bool kPerRay = false>
 RT_DEV void traceBinaryLoop(const RtSceneDesc& scene, const Paths& paths, const uint32_t* queue, const uint32_t* queueCount,
                             const uint32_t* shadowQueue, const uint32_t* shadowCount, uint32_t* cursor, unsigned long long* counters, const TravTuning& tune,
                             uint32_t* sStack, uint32_t* sDensePrefix, uint32_t sharingWaves)
@@ -25,6 +31,7 @@ RT_DEV void traceBinaryLoop(const RtSceneDesc& scene, const Paths& paths, const 
     TravState s; s.mode = TRAV_DONE; s.shadow = false;
     uint32_t slot = 0, light = 0;
     bool have = false, exhausted = false;
+    uint32_t* const countsAtRefill = CountsAtRefill<kPerRay>::lds() + threadIdx.x;   // (kPerRay only)
     // chunk size: large enough to make global atomics rare, small enough to keep the tail of the launch balanced
     uint32_t chunkSize = count / (sharingWaves * 4u);
     chunkSize = chunkSize < 64u ? 64u : (chunkSize > 1024u ? 1024u : chunkSize);
@@ -172,6 +179,11 @@ RT_DEV void traceBinaryLoop(const RtSceneDesc& scene, const Paths& paths, const 
                     maxDistance = pshadow(paths, light, 0, slot).w;   // hitPoint.distance = illuminateResult.distance * 0.999f
                 }
                 have = true;
+                if (kPerRay && !shadowRequest)
+                {
+#pragma unroll
+                    for (int k = 0; k < 4; ++k) countsAtRefill[k * RT_BLOCK] = cnt.c[C_BOX + k];
+                }
                 if (bypassMesh)
                 {
                     // = travBegin + the object step of travStepOther for the one mesh object
@@ -247,6 +259,11 @@ RT_DEV void traceBinaryLoop(const RtSceneDesc& scene, const Paths& paths, const 
                 {
                     // nothing was hit: HitPoint stays {RT_INVALID_OBJECT, distance = FLT_MAX-ish infinity} (HitPoint.h:14-51)
                     if (s.hitDistance == __uint_as_float(0x7f800000u)) prec(paths, R_HIT, slot) = f4(fbits(RT_INVALID_OBJECT), fbits(0u), s.hitDistance, 0.0f);
+                    // what this ray added to the lane's tallies since its refill: the reference's ctx.localCounters after one Scene::Traverse.  A slot has one
+                    // closest-hit ray and the counting walk never splits a ray, so a plain 16-byte store does
+                    if (kPerRay && tune.rayCounts)
+                        tune.rayCounts[slot] = make_uint4(cnt.c[C_BOX] - countsAtRefill[0], cnt.c[C_BOX_PASS] - countsAtRefill[RT_BLOCK], cnt.c[C_TRI] - countsAtRefill[2 * RT_BLOCK],
+                                                          cnt.c[C_TRI_PASS] - countsAtRefill[3 * RT_BLOCK]);
                 }
                 have = false;
             }
@@ -255,7 +272,7 @@ RT_DEV void traceBinaryLoop(const RtSceneDesc& scene, const Paths& paths, const 
     flushCounters(cnt, counters);
 }
 
-template <int kStack, bool kCount>
+template <int kStack, bool kCount, bool kPerRay>
 __global__ void __launch_bounds__(RT_BLOCK) __attribute__((amdgpu_waves_per_eu(kStack <= 24 ? 5 : 1))) k_trace(const RtSceneDesc scene, const Paths paths,
                                                     const uint32_t* __restrict__ queue, const uint32_t* __restrict__ queueCount,
                                                     const uint32_t* __restrict__ shadowQueue, const uint32_t* __restrict__ shadowCount,
@@ -270,7 +287,7 @@ __global__ void __launch_bounds__(RT_BLOCK) __attribute__((amdgpu_waves_per_eu(k
         const uint32_t requests = (queueCount ? *queueCount : 0u) + (shadowCount ? *shadowCount : 0u);
         if (requests <= tune.fullGridAbove) { if (blockIdx.x >= tune.baseBlocks) return; blocks = tune.baseBlocks; }
     }
-    traceBinaryLoop<kStack, kCount>(scene, paths, queue, queueCount, shadowQueue, shadowCount, cursor, counters, tune, sStack, sDensePrefix, blocks * (RT_BLOCK / 64u));
+    traceBinaryLoop<kStack, kCount, kPerRay>(scene, paths, queue, queueCount, shadowQueue, shadowCount, cursor, counters, tune, sStack, sDensePrefix, blocks * (RT_BLOCK / 64u));
 }
 
 #ifndef RT_TRACE_FUNCTIONS_ONLY   // (rt_tail.hip takes the walk above and not this kernel)

@@ -53,6 +53,8 @@ struct TravTuning
     uint32_t baseBlocks;      // re-trace launches: blocks beyond this many leave at once unless the queues hold more than `fullGridAbove` requests
     uint32_t fullGridAbove;   // (0 / 0: every block works).  A re-trace launch usually holds a few thousand rays -- one block per CU --, but a scene whose sun
                               // shines exactly along an axis hands it a fifth of all next-event rays (tests/test_gpu_parity.py, test_axis_parallel_next_event_rays)
+    uint4* rayCounts;         // the counting walk k_trace<*, true, true> only, null everywhere else: per slot the box tests, passed box tests, triangle tests and passed
+                              // triangle tests of the slot's closest-hit ray, stored when the ray completes (the cost planes of rtgpu_render_aovs)
 };
 #define RT_ABORT_CLOSEST_AFTER 768u
 // the same hand-over in the re-trace launches behind the 4-wide walks (PathTracerMIS) and in a block's local second walk: their queues hold a few

@@ -41,11 +41,12 @@ __host__ __device__ inline bool queryRayIsDegenerate(float ox, float oy, float o
 #define RT_K_TRACE_WIDE2_ARGS (const RtSceneDesc scene, const WideScene wide, const Paths paths, const uint32_t* __restrict__ queue, const uint32_t* __restrict__ queueCount, \
                                const uint32_t* __restrict__ shadowQueue, const uint32_t* __restrict__ shadowCount, uint32_t* __restrict__ cursor, unsigned long long* counters, const WideTuning tune)
 #define RT_K_TRACE_INSTANCES(X) X(24, false) X(24, true) X(32, false) X(32, true) X(64, false) X(64, true)
+#define RT_K_TRACE_PER_RAY_INSTANCES(X) X(24) X(32) X(64)   // the counting walk that also stores every ray's own counts (TravTuning::rayCounts)
 #define RT_K_TRACE_WIDE_INSTANCES(X) X(24, false, false) X(24, false, true) X(24, true, false)
 #define RT_K_TRACE_WIDE2_INSTANCES(X) X(24)
 
 #ifndef RT_DEVICE_KERNELS
-template <int kStack, bool kCount> __global__ void RT_TRACE_ATTR(kStack) k_trace RT_K_TRACE_ARGS;
+template <int kStack, bool kCount, bool kPerRay = false> __global__ void RT_TRACE_ATTR(kStack) k_trace RT_K_TRACE_ARGS;
 template <int kStack, bool kDiag = false, bool kLocalExact = false> __global__ void RT_TRACE_ATTR(kStack) k_trace_wide RT_K_TRACE_WIDE_ARGS;
 template <int kStack> __global__ void RT_TRACE_ATTR(kStack) k_trace_wide2 RT_K_TRACE_WIDE2_ARGS;
 __global__ void __launch_bounds__(RT_BLOCK) k_trace_packet(const RtSceneDesc scene, const WideBvh bvh, const Paths paths, uint32_t* __restrict__ cursor, unsigned long long* counters, const WideTuning tune);
