@@ -678,6 +678,68 @@ int rtgpu_render_aovs(RtgpuContext* ctx, const RtPassParams* params, const uint3
 int rtgpu_render_aovs_async(RtgpuContext* ctx, const RtPassParams* params, const uint32_t* planes, uint32_t numPlanes, void* const* outputs,
                             void* stream);
 
+/* ---------------------------------------------------------------------------------------------
+ * Denoise: an edge-avoiding a-trous wavelet filter (Dammertz et al. 2010) over a rendered frame, guided by the first-hit planes
+ * rtgpu_render_aovs writes.  It is this library's own filter, defined here operation by operation; tests/denoise_ref.py is the same text in
+ * NumPy float32 and the device is held to it bit for bit.
+ *   inputs     a W x H frame, rows as the sum buffer's: color H x W x 3 f32 interleaved (the sum buffer's layout); depth 1 x H x W; normal,
+ *              position, albedo 3 x H x W each, channel-major (the DEPTH, NORMAL, POSITION and BASE_COLOR planes).  A pixel is valid iff its
+ *              depth is finite (a miss has +inf).
+ *   arithmetic f32; every a * b + c is a rounded multiply, then a rounded add; sums associate left to right as written.
+ *   constants  invN = 1 / (sigmaNormal * sigmaNormal), invP = 1 / (sigmaPlane * sigmaPlane), invC[0] = 1 / (sigmaColor * sigmaColor),
+ *              invC[s + 1] = invC[s] * 4 (the colour sigma halves per level).
+ *   prepare    c = color * colorScale per channel; with RT_DENOISE_DEMODULATE, per channel k, d_k = albedo_k > 1e-3f ? albedo_k : 1.0f and
+ *              c_k = c_k / d_k; without it d = 1 and albedo may be NULL.
+ *   level s    (s = 0 .. iterations - 1, step = 1 << s; the levels ping-pong between two buffers) an invalid pixel p copies its colour.  A valid
+ *              one: acc = 0, wsum = 0; for j = -2 .. 2 (rows, outermost), i = -2 .. 2 (columns): q = p + step * (i, j), skipped when outside
+ *              the frame or invalid; dn = N_p - N_q, dp = P_q - P_p, dc = c_p - c_q;
+ *                  xn = (dn.x * dn.x + dn.y * dn.y) + dn.z * dn.z
+ *                  t  = (N_p.x * dp.x + N_p.y * dp.y) + N_p.z * dp.z,  xp = t * t
+ *                  xc = (dc.x * dc.x + dc.y * dc.y) + dc.z * dc.z
+ *                  x  = (xn * invN + xp * invP) + xc * invC[s]
+ *                  u  = fmaxf(0, 1 - x * 0.0625f); u = u * u, four times: (1 - x / 16)^16, exactly 0 from x = 16 on and for a NaN x
+ *                  w  = (h[|i|] * h[|j|]) * u with h = {0.375, 0.25, 0.0625};  acc_k = acc_k + w * c_q,k;  wsum = wsum + w
+ *              the result is acc_k / wsum, or c_p when wsum == 0.
+ *   finish     out_k = result_k * d_k, H x W x 3 f32 interleaved.  Non-finite colours are the caller's business.
+ *   errors     a NULL context, params or buffer (albedo only with RT_DENOISE_DEMODULATE), iterations outside 1..8, a sigma or colorScale
+ *              that is not finite or <= 0, a width or height of 0: RTGPU_ERR_INVALID_ARGUMENT; more than 16 Mi pixels: RTGPU_ERR_UNSUPPORTED;
+ *              rtgpu_denoise before rtgpu_upload_scene / rtgpu_resize: RTGPU_ERR_NOT_READY; what rtgpu_render_aovs refuses in guideParams
+ *              gets the status it gets there.
+ * rtgpu_filter_atrous is a pure image filter: it needs a context, but no scene and no rtgpu_resize.  rtgpu_denoise submits the queued passes
+ * (a multi-device context gathers and answers on its first device), renders the DEPTH, NORMAL, POSITION and BASE_COLOR planes of guideParams
+ * through the AOV path into device scratch and filters the context's sum buffer; colorScale is the caller's (normally 1 / numPasses).  It is
+ * not a pass and leaves film, both sum buffers, counters, kernel times, the photon state and the active blocks alone.  The filter's scratch is
+ * 64 bytes per pixel, the call's own, grown on use and freed with the context; the host-pointer entries and rtgpu_denoise's guide planes are
+ * staged in a second buffer of at most as much.
+ * --------------------------------------------------------------------------------------------- */
+#define RT_DENOISE_DEMODULATE 1u
+/* 32 bytes */
+typedef struct RtDenoiseParams
+{
+    uint32_t iterations;   /* 1..8 levels */
+    uint32_t flags;        /* RT_DENOISE_DEMODULATE */
+    float    colorScale;
+    float    sigmaColor;
+    float    sigmaNormal;
+    float    sigmaPlane;
+    uint32_t _pad[2];
+} RtDenoiseParams;
+/* Host pointers; synchronous. */
+int rtgpu_filter_atrous(RtgpuContext* ctx, const RtDenoiseParams* params, uint32_t width, uint32_t height, const float* color, const float* depth,
+                        const float* normal, const float* position, const float* albedo, float* outRGB);
+/* Device pointers (16-byte aligned; outRGB must not overlap an input) on `stream` (a hipStream_t; NULL: the context's own stream): ordered
+ * after the work already queued there, returns without synchronising. */
+int rtgpu_filter_atrous_async(RtgpuContext* ctx, const RtDenoiseParams* params, uint32_t width, uint32_t height, const float* color,
+                              const float* depth, const float* normal, const float* position, const float* albedo, float* outRGB, void* stream);
+/* outRGB: host memory, height x width x 3 floats of the context's size; synchronous. */
+int rtgpu_denoise(RtgpuContext* ctx, const RtDenoiseParams* params, const RtPassParams* guideParams, float* outRGB);
+/* outRGB: device memory, 16-byte aligned; the guide render and the filter are ordered on `stream` as above.  The passes rendered after the
+ * call wait for its read of the sum buffer. */
+int rtgpu_denoise_async(RtgpuContext* ctx, const RtDenoiseParams* params, const RtPassParams* guideParams, float* outRGB, void* stream);
+/* rtgpu_postprocess over a caller's image (host memory, height x width x 3 floats of the context's size) in place of the sum buffer -- a
+ * denoised frame, say: the same kernels, the same restrictions, and the same bits for the same input. */
+int rtgpu_postprocess_from(RtgpuContext* ctx, const RtPostprocessParams* params, const float* rgbHost, uint32_t* frontBufferBGRA);
+
 /* Known-answer-test hooks.  They evaluate the DEVICE implementation of one hot-path function (the code the traversal and shading
  * kernels call, rt_device_*.h) on caller-provided records, so that tests can hold the HIP functions directly against vectors produced
  * by the reference's own translation units (tests/golden/) without going through any CPU

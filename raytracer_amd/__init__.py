@@ -207,6 +207,122 @@ AOV_PLANES = collections.OrderedDict(
         ("sub_object_id", 1, np.uint32), ("material", 1, np.uint32), ("box_tests", 1, np.uint32), ("box_tests_passed", 1, np.uint32),
         ("triangle_tests", 1, np.uint32), ("triangle_tests_passed", 1, np.uint32))))
 
+
+# ---- denoise (include/rtgpu.h: rtgpu_filter_atrous / rtgpu_denoise) --------------------------------------------------------------------------
+class RtDenoiseParams(C.Structure):
+    _fields_ = [("iterations", C.c_uint32), ("flags", C.c_uint32), ("colorScale", C.c_float), ("sigmaColor", C.c_float), ("sigmaNormal", C.c_float),
+                ("sigmaPlane", C.c_float), ("_pad", C.c_uint32 * 2)]
+
+
+RT_DENOISE_DEMODULATE = 1
+# the wrappers' defaults: a wide colour sigma at the first level (it halves per level), normals within about 15 degrees, planes within a tenth of a scene unit
+DENOISE_DEFAULTS = dict(sigma_color=2.0, sigma_normal=0.25, sigma_plane=0.1)
+
+
+def denoise_params(iterations=5, sigma_color=DENOISE_DEFAULTS["sigma_color"], sigma_normal=DENOISE_DEFAULTS["sigma_normal"],
+                   sigma_plane=DENOISE_DEFAULTS["sigma_plane"], color_scale=1.0, demodulate=True):
+    p = RtDenoiseParams()
+    p.iterations, p.flags = int(iterations), RT_DENOISE_DEMODULATE if demodulate else 0
+    p.colorScale, p.sigmaColor, p.sigmaNormal, p.sigmaPlane = float(color_scale), float(sigma_color), float(sigma_normal), float(sigma_plane)
+    return p
+
+
+_filter_contexts = {}
+
+
+def _filter_context(device):
+    """a context of the library for the pure image filter (no scene, no film), one per device, kept until release_filter_contexts()"""
+    if device not in _filter_contexts:
+        ctx = C.c_void_p()
+        r = rtgpu_lib().rtgpu_create(int(device), C.byref(ctx))
+        if r != 0:
+            raise RuntimeError("rtgpu_create(%d) failed (%d): %s" % (device, r, (rtgpu_lib().rtgpu_last_error() or b"").decode()))
+        _filter_contexts[device] = ctx
+    return _filter_contexts[device]
+
+
+def release_filter_contexts():
+    """Destroys the contexts atrous_filter created for itself, with their device scratch (64 bytes per pixel of the largest frame filtered, and as much
+    again for the staged planes of the NumPy path).  Waits for the filter calls still running on them."""
+    while _filter_contexts:
+        _, ctx = _filter_contexts.popitem()
+        rtgpu_lib().rtgpu_destroy(ctx)
+
+
+def _run_on_torch_stream(torch, owner, device, tensors, call):
+    """call(stream handle) on torch.cuda.current_stream(device); torch's default stream is the null stream, which means the context's own to the async
+    entry points: then a side stream ordered behind the current one, which the current one waits for (as Viewport._query)"""
+    current = torch.cuda.current_stream(device)
+    if current.cuda_stream != 0:
+        return call(C.c_void_p(current.cuda_stream))
+    side = owner.get(device)
+    if side is None:
+        side = owner[device] = torch.cuda.Stream(device)
+    side.wait_stream(current)
+    r = call(C.c_void_p(side.cuda_stream))
+    current.wait_stream(side)
+    for t in tensors:
+        if t is not None:
+            t.record_stream(side)
+    return r
+
+
+_filter_streams = {}
+
+
+def atrous_filter(color, depth, normal, position, albedo=None, iterations=5, sigma_color=DENOISE_DEFAULTS["sigma_color"],
+                  sigma_normal=DENOISE_DEFAULTS["sigma_normal"], sigma_plane=DENOISE_DEFAULTS["sigma_plane"], color_scale=1.0, demodulate=True, ctx=None):
+    """The edge-avoiding a-trous filter of include/rtgpu.h over a frame: color (H, W, 3), depth (H, W) or (1, H, W), normal, position and albedo (3, H, W)
+    -- the layouts of Viewport.sum_buffer() and Viewport.render_aovs() -- as float32 NumPy arrays, or as contiguous float32 torch tensors on a ROCm device
+    (then the filter runs on torch.cuda.current_stream() without a host copy and returns a tensor).  Returns the (H, W, 3) image.  albedo is needed with
+    demodulate=True only.  `ctx`: a device context to run on (default: one of the module's own per device, which keeps its scratch -- 64 bytes per pixel,
+    twice that on the NumPy path -- until release_filter_contexts()).  Not thread-safe: the calls on one context share that scratch and are ordered by the
+    library's events from one host thread; callers on several threads serialise their calls or pass contexts of their own."""
+    torch = None
+    planes = dict(color=color, depth=depth, normal=normal, position=position)
+    if demodulate:
+        if albedo is None:
+            raise ValueError("demodulate=True needs the albedo plane")
+        planes["albedo"] = albedo
+    if any(type(a).__module__.split(".")[0] == "torch" for a in planes.values()):
+        import torch
+    if getattr(color, "ndim", 0) != 3 or color.shape[2] != 3:
+        raise ValueError("color must be an (H, W, 3) float32 array or tensor")
+    h, w = int(color.shape[0]), int(color.shape[1])
+    shapes = dict(color=((h, w, 3),), depth=((h, w), (1, h, w)), normal=((3, h, w),), position=((3, h, w),), albedo=((3, h, w),))
+    for name, a in planes.items():
+        if torch is None:
+            ok = isinstance(a, np.ndarray) and a.dtype == np.float32
+        else:
+            ok = isinstance(a, torch.Tensor) and a.dtype == torch.float32 and a.is_cuda and a.device == color.device
+        if not ok or tuple(a.shape) not in shapes[name]:
+            raise ValueError("%s must be a float32 %s of shape %s%s" % (name, "NumPy array" if torch is None else "tensor on the colour's ROCm device",
+                                                                        " or ".join(str(t) for t in shapes[name]), "" if torch is None else " (all arrays or all tensors)"))
+    p = denoise_params(iterations, sigma_color, sigma_normal, sigma_plane, color_scale, demodulate)
+    lib = rtgpu_lib()
+    if torch is None:
+        planes = {name: np.ascontiguousarray(a) for name, a in planes.items()}
+        out = np.zeros((h, w, 3), dtype=np.float32)
+        ptr = lambda name: planes[name].ctypes.data_as(C.c_void_p) if name in planes else None   # noqa: E731
+        r = lib.rtgpu_filter_atrous(ctx if ctx is not None else _filter_context(0), C.byref(p), C.c_uint32(w), C.c_uint32(h), ptr("color"), ptr("depth"), ptr("normal"),
+                                    ptr("position"), ptr("albedo"), out.ctypes.data_as(C.c_void_p))
+    else:
+        device = color.device
+        index = device.index if device.index is not None else torch.cuda.current_device()
+        for name, a in planes.items():
+            if not a.is_contiguous():
+                raise ValueError("%s must be contiguous" % name)
+        out = torch.empty((h, w, 3), dtype=torch.float32, device=device)
+        ptr = lambda name: C.c_void_p(planes[name].data_ptr()) if name in planes else None   # noqa: E731
+        context = ctx if ctx is not None else _filter_context(index)
+        r = _run_on_torch_stream(torch, _filter_streams, device, list(planes.values()) + [out], lambda stream: lib.rtgpu_filter_atrous_async(
+            context, C.byref(p), C.c_uint32(w), C.c_uint32(h), ptr("color"), ptr("depth"), ptr("normal"), ptr("position"), ptr("albedo"), C.c_void_p(out.data_ptr()), stream))
+    if r != 0:
+        err = (lib.rtgpu_last_error() or b"").decode()
+        raise (ValueError if r == -1 else RuntimeError)("atrous_filter failed (%d): %s" % (r, err))
+    return out
+
+
 BSDF_NAMES = ("null", "diffuse", "roughDiffuse", "dielectric", "roughDielectric", "metal", "roughMetal", "plastic", "roughPlastic")
 
 
@@ -782,6 +898,55 @@ class Viewport:
             raise (ValueError if r == -1 else RuntimeError)("render_aovs failed (%d): %s" % (r, err))
         if device:
             out = collections.OrderedDict((name, t if t.dtype == torch.float32 else _u32(torch, t)) for name, t in raw.items())
+        return out
+
+    # ---- denoise (include/rtgpu.h: rtgpu_denoise / rtgpu_denoise_async, rtgpu_postprocess_from) ------------------------------------------------------
+    def denoise(self, params, iterations=5, sigma_color=DENOISE_DEFAULTS["sigma_color"], sigma_normal=DENOISE_DEFAULTS["sigma_normal"],
+                sigma_plane=DENOISE_DEFAULTS["sigma_plane"], color_scale=None, demodulate=True, device=False):
+        """The frame rendered so far through the a-trous filter of include/rtgpu.h, guided by the depth, normal, position and base-colour planes of the pass
+        `params` (an RtPassParams from next_pass_params(), as render_aovs takes it): the (H, W, 3) float32 image, sum_buffer() * color_scale filtered.
+        color_scale defaults to 1 / max(1, passes_finished).  device=True: a torch tensor on the renderer's ROCm device, produced on
+        torch.cuda.current_stream() without a host copy.  The call is not a pass: film, sum buffers and counters stay as they are."""
+        if not isinstance(params, RtPassParams):
+            raise TypeError("denoise takes the RtPassParams of next_pass_params(camera), not %s" % type(params).__name__)
+        if not self.has_renderer:
+            raise RuntimeError("denoise needs a renderer: call set_renderer first")
+        ctx = self.device_context()
+        if not ctx.value or host_lib().rth_viewport_upload_scene(self._h) != 0:
+            raise RuntimeError("the viewport's renderer has no device context or its scene could not be uploaded: %s" % (rtgpu_lib().rtgpu_last_error() or b"").decode())
+        p = denoise_params(iterations, sigma_color, sigma_normal, sigma_plane, 1.0 / max(1, self.passes_finished) if color_scale is None else color_scale, demodulate)
+        lib = rtgpu_lib()
+        if not device:
+            out = np.zeros((self.height, self.width, 3), dtype=np.float32)
+            r = lib.rtgpu_denoise(ctx, C.byref(p), C.byref(params), out.ctypes.data_as(C.c_void_p))
+        else:
+            import torch
+            dev = torch.device("cuda", multi_info(ctx)["devices"][0])
+            out = torch.empty((self.height, self.width, 3), dtype=torch.float32, device=dev)
+            if getattr(self, "_denoise_streams", None) is None:
+                self._denoise_streams = {}
+            r = _run_on_torch_stream(torch, self._denoise_streams, dev, [out],
+                                     lambda stream: lib.rtgpu_denoise_async(ctx, C.byref(p), C.byref(params), C.c_void_p(out.data_ptr()), stream))
+        if r != 0:
+            err = (lib.rtgpu_last_error() or b"").decode()
+            raise (ValueError if r == -1 else RuntimeError)("denoise failed (%d): %s" % (r, err))
+        return out
+
+    def front_buffer_from(self, image, exposure=0.0, contrast=0.8, saturation=0.98, dithering=0.005, tonemapper=3, color_filter=(1.0, 1.0, 1.0, 1.0),
+                          dither_seed=0, bloom=0.0, num_passes=1):
+        """front_buffer() over `image`, an (H, W, 3) float32 array of the viewport's size, in place of the sum buffer: the tone-mapped (H, W) uint32
+        0x00RRGGBB picture of a denoised frame, say.  num_passes scales as front_buffer's pass count does (1: the image is already averaged)."""
+        if not isinstance(image, np.ndarray) or image.dtype != np.float32 or image.shape != (self.height, self.width, 3):
+            raise ValueError("image must be an (H, W, 3) float32 NumPy array of the viewport's size")
+        p = RtPostprocessParams()
+        for k in range(4):
+            p.colorFilter[k] = color_filter[k]
+        p.exposure, p.contrast, p.saturation, p.ditheringStrength, p.bloomFactor = exposure, contrast, saturation, dithering, bloom
+        p.tonemapper, p.numPasses, p.ditherSeed = int(tonemapper), max(1, int(num_passes)), int(dither_seed)
+        image = np.ascontiguousarray(image)
+        out = np.zeros((self.height, self.width), dtype=np.uint32)
+        if rtgpu_lib().rtgpu_postprocess_from(self.device_context(), C.byref(p), image.ctypes.data_as(C.c_void_p), out.ctypes.data_as(C.c_void_p)) != 0:
+            raise RuntimeError("postprocess failed: %s" % (rtgpu_lib().rtgpu_last_error() or b"").decode())
         return out
 
     @property

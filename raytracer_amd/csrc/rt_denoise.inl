@@ -1,0 +1,161 @@
+// rt_denoise.inl -- kernels behind rtgpu_filter_atrous / rtgpu_denoise (include/rtgpu.h; host side: rt_runtime_denoise.inl).  Included by rt_trace.hip.
+// An edge-avoiding a-trous wavelet filter (Dammertz et al. 2010) guided by the first-hit planes of rtgpu_render_aovs.  The definition -- every operation and
+// its order -- stands in include/rtgpu.h and DESIGN.md section 5; tests/denoise_ref.py is the same text in NumPy float32, and the kernels are held to it bit for
+// bit (the unit is compiled with -ffp-contract=off: every a * b + c below is a rounded multiply and a rounded add).
+//
+//   k_denoise_prepare   planes -> three 16-byte records per pixel: {n.xyz, valid}, {p.xyz, 0}, {c.rgb, 0} with c = colour * colorScale (/ albedo)
+//   k_atrous<kLast>     one level: one lane per pixel, a wave = 64 consecutive x of one row, so each of a tap's three 16-byte loads is one coalesced
+//                       kilobyte per wave at every step; 25 taps unrolled, no branch inside (a tap outside the frame or on an invalid pixel loads a
+//                       clamped address and is dropped by a select).  kLast: remodulates and writes the float3 image instead of the next level's records.
+//   k_atrous_tiled<kLast, kStep>   the same level for steps 1 and 2 from LDS: a block of 8 rows x 32 columns stages its tile and the 2 * step halo (three
+//                       records per pixel, 30 KB at step 2) and takes its taps from there.  The per-pixel operations and their order are k_atrous's
+//                       (atrousTap, atrousStore), so both give the same bits.
+
+// d_k of the definition: the albedo channel the colour is divided by before and multiplied with after the filter
+RT_DEV float denoiseAlbedoDivisor(const float* __restrict__ albedo, size_t pixels, uint32_t i, uint32_t k)
+{
+    if (!albedo) return 1.0f;
+    const float a = albedo[(size_t)k * pixels + i];
+    return a > 1e-3f ? a : 1.0f;
+}
+
+__global__ void __launch_bounds__(RT_BLOCK) k_denoise_prepare(const float* __restrict__ color, const float* __restrict__ depth, const float* __restrict__ normal,
+                                                              const float* __restrict__ position, const float* __restrict__ albedo, uint32_t pixels, float colorScale,
+                                                              float4* __restrict__ recN, float4* __restrict__ recP, float4* __restrict__ recC)
+{
+    const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= pixels) return;
+    const size_t n = pixels;
+    const bool valid = (__float_as_uint(depth[i]) & 0x7F800000u) != 0x7F800000u;   // finite: a miss has +inf
+    recN[i] = make_float4(normal[i], normal[n + i], normal[2 * n + i], valid ? 1.0f : 0.0f);
+    recP[i] = make_float4(position[i], position[n + i], position[2 * n + i], 0.0f);
+    float c[3];
+    for (uint32_t k = 0; k < 3u; ++k)
+    {
+        c[k] = color[3 * (size_t)i + k] * colorScale;
+        if (albedo) c[k] = c[k] / denoiseAlbedoDivisor(albedo, n, i, k);
+    }
+    recC[i] = make_float4(c[0], c[1], c[2], 0.0f);
+}
+
+// one tap of the definition: its weight from the three distances, then acc += w * c_q and wsum += w -- unless the tap is skipped (`take` false)
+RT_DEV void atrousTap(const float4& np, const float4& pp, const float4& cp, const float4& nq, const float4& pq, const float4& cq, bool take, float kernelWeight,
+                      const AtrousLevel& level, float& acc0, float& acc1, float& acc2, float& wsum)
+{
+    const float dnx = np.x - nq.x, dny = np.y - nq.y, dnz = np.z - nq.z;
+    const float dpx = pq.x - pp.x, dpy = pq.y - pp.y, dpz = pq.z - pp.z;
+    const float dcx = cp.x - cq.x, dcy = cp.y - cq.y, dcz = cp.z - cq.z;
+    const float xn = (dnx * dnx + dny * dny) + dnz * dnz;
+    const float t = (np.x * dpx + np.y * dpy) + np.z * dpz;
+    const float xp = t * t;
+    const float xc = (dcx * dcx + dcy * dcy) + dcz * dcz;
+    const float xs = (xn * level.invN + xp * level.invP) + xc * level.invC;
+    float u = fmaxf(0.0f, 1.0f - xs * 0.0625f);   // (1 - x / 16)^16: exactly 0 from x = 16 on, and for a NaN x
+    u = u * u; u = u * u; u = u * u; u = u * u;
+    const float wt = kernelWeight * u;
+    acc0 = take ? acc0 + wt * cq.x : acc0;
+    acc1 = take ? acc1 + wt * cq.y : acc1;
+    acc2 = take ? acc2 + wt * cq.z : acc2;
+    wsum = take ? wsum + wt : wsum;
+}
+
+// what a level leaves for pixel p: the next level's colour record, or (kLast) the remodulated float3 pixel
+template <bool kLast>
+RT_DEV void atrousStore(uint32_t p, float r0, float r1, float r2, float4* __restrict__ dst, const float* __restrict__ albedo, float* __restrict__ out, uint32_t width, uint32_t height)
+{
+    if (kLast)
+    {
+        const size_t pixels = (size_t)width * height;
+        out[3 * (size_t)p + 0] = r0 * denoiseAlbedoDivisor(albedo, pixels, p, 0u);
+        out[3 * (size_t)p + 1] = r1 * denoiseAlbedoDivisor(albedo, pixels, p, 1u);
+        out[3 * (size_t)p + 2] = r2 * denoiseAlbedoDivisor(albedo, pixels, p, 2u);
+    }
+    else dst[p] = make_float4(r0, r1, r2, 0.0f);
+}
+
+template <bool kLast>
+__global__ void RT_ATROUS_ATTR k_atrous RT_K_ATROUS_ARGS
+{
+    // the blocks of a frame are numbered row by row along grid.x (a tall, narrow image has more block rows than grid.y may hold)
+    const uint32_t blocksX = (width + RT_DENOISE_BLOCK_X - 1u) / RT_DENOISE_BLOCK_X, blockY = blockIdx.x / blocksX, blockX = blockIdx.x - blockY * blocksX;
+    const int32_t x = (int32_t)(blockX * RT_DENOISE_BLOCK_X + threadIdx.x), y = (int32_t)(blockY * RT_DENOISE_BLOCK_Y + threadIdx.y);
+    if (x >= (int32_t)width || y >= (int32_t)height) return;
+    const int32_t w = (int32_t)width, h = (int32_t)height;
+    const uint32_t p = (uint32_t)y * width + (uint32_t)x;
+    const float4 np = recN[p], pp = recP[p], cp = src[p];
+    float r0 = cp.x, r1 = cp.y, r2 = cp.z;   // an invalid pixel copies its colour
+    if (np.w != 0.0f)
+    {
+        const float kernelWeights[3] = { 0.375f, 0.25f, 0.0625f };
+        float acc0 = 0.0f, acc1 = 0.0f, acc2 = 0.0f, wsum = 0.0f;
+#pragma unroll
+        for (int32_t j = -2; j <= 2; ++j)
+        {
+#pragma unroll
+            for (int32_t i = -2; i <= 2; ++i)
+            {
+                const int32_t qx = x + level.step * i, qy = y + level.step * j;
+                const bool inside = qx >= 0 && qx < w && qy >= 0 && qy < h;
+                const uint32_t q = inside ? (uint32_t)qy * width + (uint32_t)qx : p;
+                const float4 nq = recN[q], pq = recP[q], cq = src[q];
+                atrousTap(np, pp, cp, nq, pq, cq, inside && nq.w != 0.0f, kernelWeights[i < 0 ? -i : i] * kernelWeights[j < 0 ? -j : j], level, acc0, acc1, acc2, wsum);
+            }
+        }
+        if (wsum != 0.0f) { r0 = acc0 / wsum; r1 = acc1 / wsum; r2 = acc2 / wsum; }
+    }
+    atrousStore<kLast>(p, r0, r1, r2, dst, albedo, out, width, height);
+}
+template __global__ void RT_ATROUS_ATTR k_atrous<false> RT_K_ATROUS_ARGS;
+template __global__ void RT_ATROUS_ATTR k_atrous<true> RT_K_ATROUS_ARGS;
+
+template <bool kLast, int kStep>
+__global__ void RT_ATROUS_TILED_ATTR k_atrous_tiled RT_K_ATROUS_ARGS
+{
+    constexpr int32_t kHalo = 2 * kStep, kTileW = RT_DENOISE_TILE_X + 2 * kHalo, kTileH = RT_DENOISE_TILE_Y + 2 * kHalo;
+    __shared__ float4 tileN[kTileH * kTileW], tileP[kTileH * kTileW], tileC[kTileH * kTileW];
+    const int32_t w = (int32_t)width, h = (int32_t)height;
+    const uint32_t blocksX = (width + RT_DENOISE_TILE_X - 1u) / RT_DENOISE_TILE_X, blockY = blockIdx.x / blocksX, blockX = blockIdx.x - blockY * blocksX;   // (as k_atrous numbers them)
+    const int32_t x0 = (int32_t)(blockX * RT_DENOISE_TILE_X), y0 = (int32_t)(blockY * RT_DENOISE_TILE_Y);
+    // the tile and its halo; a record outside the frame is invalid (n.w = 0), which is how its tap is skipped
+    for (int32_t e = (int32_t)(threadIdx.y * RT_DENOISE_TILE_X + threadIdx.x); e < kTileH * kTileW; e += RT_DENOISE_TILE_X * RT_DENOISE_TILE_Y)
+    {
+        const int32_t ty = e / kTileW, tx = e - ty * kTileW;
+        const int32_t gx = x0 - kHalo + tx, gy = y0 - kHalo + ty;
+        const bool inside = gx >= 0 && gx < w && gy >= 0 && gy < h;
+        float4 n = make_float4(0.0f, 0.0f, 0.0f, 0.0f), ps = n, c = n;
+        if (inside)
+        {
+            const uint32_t g = (uint32_t)gy * width + (uint32_t)gx;
+            n = recN[g]; ps = recP[g]; c = src[g];
+        }
+        tileN[e] = n; tileP[e] = ps; tileC[e] = c;
+    }
+    __syncthreads();
+    const int32_t x = x0 + (int32_t)threadIdx.x, y = y0 + (int32_t)threadIdx.y;
+    if (x >= w || y >= h) return;
+    const uint32_t p = (uint32_t)y * width + (uint32_t)x;
+    const int32_t centre = ((int32_t)threadIdx.y + kHalo) * kTileW + (int32_t)threadIdx.x + kHalo;
+    const float4 np = tileN[centre], pp = tileP[centre], cp = tileC[centre];
+    float r0 = cp.x, r1 = cp.y, r2 = cp.z;
+    if (np.w != 0.0f)
+    {
+        const float kernelWeights[3] = { 0.375f, 0.25f, 0.0625f };
+        float acc0 = 0.0f, acc1 = 0.0f, acc2 = 0.0f, wsum = 0.0f;
+#pragma unroll
+        for (int32_t j = -2; j <= 2; ++j)
+        {
+#pragma unroll
+            for (int32_t i = -2; i <= 2; ++i)
+            {
+                const int32_t q = centre + kStep * j * kTileW + kStep * i;
+                const float4 nq = tileN[q], pq = tileP[q], cq = tileC[q];
+                atrousTap(np, pp, cp, nq, pq, cq, nq.w != 0.0f, kernelWeights[i < 0 ? -i : i] * kernelWeights[j < 0 ? -j : j], level, acc0, acc1, acc2, wsum);
+            }
+        }
+        if (wsum != 0.0f) { r0 = acc0 / wsum; r1 = acc1 / wsum; r2 = acc2 / wsum; }
+    }
+    atrousStore<kLast>(p, r0, r1, r2, dst, albedo, out, width, height);
+}
+#define RT_X(L, S) template __global__ void RT_ATROUS_TILED_ATTR k_atrous_tiled<L, S> RT_K_ATROUS_ARGS;
+RT_X(false, 1) RT_X(true, 1) RT_X(false, 2) RT_X(true, 2)
+#undef RT_X

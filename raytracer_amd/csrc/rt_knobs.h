@@ -60,6 +60,7 @@ RT_KNOB_ONCE(bool, vcmClass, envInt("RTGPU_VCM_CLASS", 1) != 0)
 RT_KNOB_ONCE(bool, vcmWide, envInt("RTGPU_VCM_WIDE", 0) != 0)
 RT_KNOB_ONCE(uint32_t, vcmMergeCooperativeMin, (uint32_t)envInt("RTGPU_VCM_MERGE_COOP", RT_VCM_COOPERATIVE_MERGE_MIN))
 RT_KNOB_ONCE(int, vcmBatch, envInt("RTGPU_VCM_BATCH", 0))                         // <= 0: policy
+RT_KNOB_ONCE(bool, denoiseTiled, envInt("RTGPU_DENOISE_TILED", 1) != 0)           // the a-trous levels of steps 1 and 2 from LDS tiles (k_atrous_tiled); 0: every level gathers from memory (k_atrous); same bits either way
 #undef RT_KNOB_ONCE
 
 // ---- 3. per call -----------------------------------------------------------------------------------------------------------------------------

@@ -28,7 +28,7 @@
 // staging copies, stream pool, HIP_TRY, LaunchTimer, free helpers), rt_knobs.h (every RTGPU_* environment variable), rt_multi.inl (multi-device contexts),
 // rt_runtime_scene.inl (rtgpu_upload_scene), rt_runtime_render.inl (arena sizing, traversal launchers, batch submission), rt_runtime_vcm.inl (bidirectional
 // integrator, Light Tracer), rt_runtime_kat.inl (known-answer hooks, rtgpu_evaluate_textures), rt_runtime_query.inl (batched ray queries), rt_runtime_paths.inl (path records),
-// rt_runtime_aov.inl (AOVs).
+// rt_runtime_aov.inl (AOVs), rt_runtime_denoise.inl (the a-trous filter, rtgpu_denoise, rtgpu_postprocess_from).
 //
 // Compile: hipcc --offload-arch=gfx950 -O3 -ffp-contract=off
 #include "rt_trace_common.h"
@@ -200,6 +200,7 @@ RTGPU_API void rtgpu_destroy(RtgpuContext* c)
     freeQuery(c);
     freeRecorder(c);
     freeAov(c);
+    freeDenoise(c);
     freeScene(c); freeFilm(c);
     for (uint32_t i = 0; i < RT_MAX_LANES; ++i)
     {
@@ -275,6 +276,7 @@ static int rebuildSlots(RtgpuContext* c)
 
 static int rebuildFilm(RtgpuContext* c)
 {
+    waitDenoiseRead(c);
     freeFilm(c);
     if (c->width == 0 || c->height == 0) return RTGPU_OK;
     const size_t n = (size_t)c->width * c->height * 3;
@@ -319,6 +321,7 @@ RTGPU_API int rtgpu_reset(RtgpuContext* c)
     HIP_TRY(hipSetDevice(c->device));
     { int fr = flushPending(c); if (fr) return fr; }
     HIP_TRY(syncLanes(c));
+    waitDenoiseRead(c);
     if (c->sum)
     {
         const size_t n = (size_t)c->width * c->height * 3;
@@ -429,6 +432,7 @@ RTGPU_API int rtgpu_render_pass(RtgpuContext* c, const RtPassParams* p)
     { const int r = checkPass(c, p); if (r) return r; }
     RT_FAN_OUT(c, rtgpu_render_pass(peer, p));   // asynchronous on every device: the shards render side by side
     HIP_TRY(hipSetDevice(c->device));
+    waitDenoiseRead(c);
     if (c->numSlots == 0) return RTGPU_OK;   // this shard owns no pixels
     if (c->vcm.enabled) return vcmRenderPass(c, p);
     if (c->lightTracer) return lightTracerRenderPass(c, p);
@@ -464,6 +468,7 @@ RTGPU_API int rtgpu_synchronize(RtgpuContext* c)
     RT_FAN_OUT(c, rtgpu_synchronize(peer));
     HIP_TRY(hipSetDevice(c->device));
     HIP_TRY(syncLanes(c));
+    waitDenoiseRead(c);   // (the read-back calls gather the peers' tiles into the sum buffer next)
     c->batchesSinceSync = 0; c->batchesAtThisSize = 0;
     if (!c->passBatchFromEnv) c->passBatch = c->passBatchBase;
     if (c->deviceFlags && c->deviceFlags[0] != 0u)
@@ -622,9 +627,9 @@ RTGPU_API int rtgpu_set_active_blocks(RtgpuContext* c, uint32_t numBlocks, const
     return rebuildSlots(c);
 }
 
-RTGPU_API int rtgpu_postprocess(RtgpuContext* c, const RtPostprocessParams* p, uint32_t* frontBufferBGRA)
+// rtgpu_postprocess (rgbHost == nullptr: the sum buffer) and rtgpu_postprocess_from (a caller's image of the context's size, rt_runtime_denoise.inl)
+static int postprocessImage(RtgpuContext* c, const RtPostprocessParams* p, const float* rgbHost, uint32_t* frontBufferBGRA)
 {
-    if (!c || !p || !frontBufferBGRA) return fail(RTGPU_ERR_INVALID_ARGUMENT, "NULL argument");
     if (!c->sum) return fail(RTGPU_ERR_NOT_READY, "rtgpu_resize has not been called");
     // bloom: the reference's blur works on 4 columns at a time and on 4096-entry line buffers without bounds checks
     // (Bitmap.cpp:925-931, :941, :978-990): sizes it would read or write out of bounds for are refused here
@@ -651,16 +656,24 @@ RTGPU_API int rtgpu_postprocess(RtgpuContext* c, const RtPostprocessParams* p, u
     if (p->tonemapper > RT_TONEMAPPER_ACES) return fail(RTGPU_ERR_INVALID_ARGUMENT, "unknown tonemapper");
     if (p->numPasses == 0) return fail(RTGPU_ERR_INVALID_ARGUMENT, "numPasses must be > 0");
     int r = rtgpu_synchronize(c); if (r) return r;
-    r = gatherPeers(c); if (r) return r;
+    if (!rgbHost) { r = gatherPeers(c); if (r) return r; }   // (a caller's image: the sum buffer is not read)
     const size_t pixels = (size_t)c->width * c->height;
     uint32_t* dFront = nullptr;
-    HIP_TRY(hipMalloc((void**)&dFront, pixels * sizeof(uint32_t)));
+    float* dImage = nullptr;
+    if (rgbHost)
+    {
+        HIP_TRY(hipMalloc((void**)&dImage, pixels * 3 * sizeof(float)));
+        const hipError_t ce = rtMemcpy(dImage, rgbHost, pixels * 3 * sizeof(float), hipMemcpyHostToDevice);
+        if (ce != hipSuccess) { devFree(dImage); return fail(RTGPU_ERR_DEVICE, std::string("rtgpu_postprocess_from: ") + hipGetErrorString(ce)); }
+    }
+    const float* image = rgbHost ? dImage : c->sum;
+    { const hipError_t fe = hipMalloc((void**)&dFront, pixels * sizeof(uint32_t)); if (fe != hipSuccess) { devFree(dImage); HIP_TRY(fe); } }
     const float exposureScale = powf(2.0f, p->exposure);   // colorScale on the host like the reference (Viewport.cpp:453)
     const PostScale scale = { { p->colorFilter[0] * exposureScale, p->colorFilter[1] * exposureScale, p->colorFilter[2] * exposureScale } };
     hipStream_t stream = c->lanes[0].stream;
     hipError_t e = hipSuccess;
     float* dBlur = nullptr; float* dLines = nullptr;
-    if (!bloom) hipLaunchKernelGGL(k_postprocess, dim3((uint32_t)((pixels + RT_BLOCK - 1) / RT_BLOCK)), dim3(RT_BLOCK), 0, stream, c->sum, dFront, c->width, c->height, *p, scale);
+    if (!bloom) hipLaunchKernelGGL(k_postprocess, dim3((uint32_t)((pixels + RT_BLOCK - 1) / RT_BLOCK)), dim3(RT_BLOCK), 0, stream, image, dFront, c->width, c->height, *p, scale);
     else
     {
         // mBlurredImages[i] = GaussianBlur(copy of (i == 0 ? mSum : mBlurredImages[i - 1]), sigma_i, 8), Viewport.cpp:436-445
@@ -671,24 +684,31 @@ RTGPU_API int rtgpu_postprocess(RtgpuContext* c, const RtPostprocessParams* p, u
         {
             float* img = dBlur + (size_t)l * pixels * 3;
             levels.level[l] = img;
-            e = hipMemcpyAsync(img, l == 0 ? c->sum : dBlur + (size_t)(l - 1) * pixels * 3, pixels * 3 * sizeof(float), hipMemcpyDeviceToDevice, stream);
+            e = hipMemcpyAsync(img, l == 0 ? image : dBlur + (size_t)(l - 1) * pixels * 3, pixels * 3 * sizeof(float), hipMemcpyDeviceToDevice, stream);
             if (e != hipSuccess) break;
             hipLaunchKernelGGL(k_blur_lines, dim3((c->height * 3u + RT_BLOCK - 1) / RT_BLOCK), dim3(RT_BLOCK), 0, stream, img, c->width, c->height, 0u, plans[l], dLines, dLines + pixels * 3);
             hipLaunchKernelGGL(k_blur_lines, dim3((c->width * 3u + RT_BLOCK - 1) / RT_BLOCK), dim3(RT_BLOCK), 0, stream, img, c->width, c->height, 1u, plans[l], dLines, dLines + pixels * 3);
         }
-        if (e == hipSuccess) hipLaunchKernelGGL(k_postprocess_bloom, dim3((uint32_t)((pixels + RT_BLOCK - 1) / RT_BLOCK)), dim3(RT_BLOCK), 0, stream, c->sum, levels, dFront, c->width, c->height, *p, scale);
+        if (e == hipSuccess) hipLaunchKernelGGL(k_postprocess_bloom, dim3((uint32_t)((pixels + RT_BLOCK - 1) / RT_BLOCK)), dim3(RT_BLOCK), 0, stream, image, levels, dFront, c->width, c->height, *p, scale);
     }
     if (e == hipSuccess) e = hipStreamSynchronize(stream);
     if (e == hipSuccess) e = rtMemcpy(frontBufferBGRA, dFront, pixels * sizeof(uint32_t), hipMemcpyDeviceToHost);
-    devFree(dFront, dBlur, dLines);
+    devFree(dFront, dBlur, dLines, dImage);
     if (e != hipSuccess) return fail(RTGPU_ERR_DEVICE, std::string("rtgpu_postprocess: ") + hipGetErrorString(e));
     return RTGPU_OK;
+}
+
+RTGPU_API int rtgpu_postprocess(RtgpuContext* c, const RtPostprocessParams* p, uint32_t* frontBufferBGRA)
+{
+    if (!c || !p || !frontBufferBGRA) return fail(RTGPU_ERR_INVALID_ARGUMENT, "NULL argument");
+    return postprocessImage(c, p, nullptr, frontBufferBGRA);
 }
 
 #include "rt_runtime_kat.inl"
 #include "rt_runtime_query.inl"
 #include "rt_runtime_paths.inl"
 #include "rt_runtime_aov.inl"
+#include "rt_runtime_denoise.inl"
 
 RTGPU_API int rtgpu_set_concurrency(RtgpuContext* c, uint32_t lanes)
 {

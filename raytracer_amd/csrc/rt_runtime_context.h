@@ -260,6 +260,15 @@ struct RtgpuContext
         hipEvent_t done = nullptr;                // recorded behind every call: the next one (whatever its stream) and a new arena wait for it
     } aov;
 
+    // the a-trous filter (rtgpu_filter_atrous, rtgpu_denoise; rt_runtime_denoise.inl): scratch of its own, grown on use, freed with the context
+    struct Denoise
+    {
+        float4* records = nullptr; size_t capacity = 0;   // four planes of `capacity` 16-byte records: normals + valid, positions, two colour buffers (64 bytes per pixel)
+        float* io = nullptr; size_t ioFloats = 0;         // device copies of the host entries' inputs and output; rtgpu_denoise's guide planes
+        hipEvent_t done = nullptr;                        // recorded behind every call: the next one (whatever its stream) and new scratch wait for it
+        hipEvent_t sumRead = nullptr; bool sumReadPending = false;   // recorded behind the one kernel of rtgpu_denoise_async that reads the sum buffer: whatever writes the film next waits for it
+    } denoise;
+
     // timing
     bool timing = false;
     struct Timed { int kc; hipEvent_t a, b; };
@@ -375,6 +384,24 @@ static void freeAov(RtgpuContext* c)
     for (uint32_t i = 0; i < RtgpuContext::Aov::kRing; ++i) { if (a.ringCopied[i]) (void)hipEventDestroy(a.ringCopied[i]); a.ringCopied[i] = nullptr; }
     if (a.done) (void)hipEventDestroy(a.done);
     a.done = nullptr;
+}
+
+// before anything writes or frees the sum buffer: an rtgpu_denoise_async on a caller's stream may still be reading it
+static void waitDenoiseRead(RtgpuContext* c)
+{
+    if (!c->denoise.sumReadPending) return;
+    (void)hipEventSynchronize(c->denoise.sumRead);
+    c->denoise.sumReadPending = false;
+}
+static void freeDenoise(RtgpuContext* c)
+{
+    RtgpuContext::Denoise& d = c->denoise;
+    if (d.done) (void)hipEventSynchronize(d.done);
+    devFree(d.records, d.io);
+    d.capacity = 0; d.ioFloats = 0;
+    if (d.done) (void)hipEventDestroy(d.done);
+    if (d.sumRead) (void)hipEventDestroy(d.sumRead);
+    d.done = nullptr; d.sumRead = nullptr; d.sumReadPending = false;
 }
 
 static void freeRecorder(RtgpuContext* c)

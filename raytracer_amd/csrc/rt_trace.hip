@@ -9,6 +9,7 @@
 //   rt_post.inl           post-process, bloom, block errors, texture evaluation
 //   rt_kat.inl            known-answer hooks (rtgpu_kat*)
 //   rt_query.inl          batched ray queries around the walks above (rtgpu_trace_rays)
+//   rt_denoise.inl        the a-trous filter (rtgpu_filter_atrous, rtgpu_denoise)
 // The host side (rt_runtime.hip) launches them through the declarations of rt_trace_kernels.h.
 //
 // Compile: hipcc --offload-arch=gfx950 -O3 -ffp-contract=off
@@ -47,3 +48,6 @@ RT_K_TRACE_WIDE2_INSTANCES(RT_X)
 #define RT_X(S) template __global__ void RT_TRACE_ATTR(S) k_trace<S, true, true> RT_K_TRACE_ARGS;
 RT_K_TRACE_PER_RAY_INSTANCES(RT_X)
 #undef RT_X
+
+// (behind everything else, for the same reason)
+#include "rt_denoise.inl"

@@ -2,7 +2,8 @@
 // --data and opens a window): loads a JSON scene with helpers::LoadScene, renders N passes with the device "Path Tracer MIS"
 // through the same rt::Viewport API the window loop uses (Demo.cpp: Resize -> SetRenderer -> Render per frame ->
 // GetFrontBuffer) and writes the tone-mapped front buffer as a BMP.  The extra options are --passes, --depth, --output, --seed and
-// --debug-pixel X,Y (prints the path behind that pixel of pass 0, what the reference's Demo shows for a picked pixel: Demo_UserInterface.cpp:197-272);
+// --debug-pixel X,Y (prints the path behind that pixel of pass 0, what the reference's Demo shows for a picked pixel: Demo_UserInterface.cpp:197-272),
+// and --denoise [N] (the frame goes through N levels, default 5, of the a-trous filter before it is tone-mapped: rtgpu_denoise, rtgpu_postprocess_from);
 // the environment variable RTGPU_DEVICES ("0,1,2,3" / "all") spreads the frame over several GPUs (Core/Rendering/Renderer.h).
 #include "../Demo.h"
 #include "../SceneLoader.h"
@@ -70,10 +71,41 @@ static bool PrintPixelPath(IRenderer* renderer, const RtPassParams& params, uint
     return true;
 }
 
+// The front buffer of the frame after `levels` levels of the a-trous filter (rtgpu_denoise guided by the first hits of one more pass's primary rays,
+// then the viewport's post-process over the filtered image)
+static bool DenoisedFrontBuffer(Viewport& viewport, const Camera& camera, IRenderer* renderer, uint32 levels, Bitmap& front)
+{
+    PathTracerMIS* pt = dynamic_cast<PathTracerMIS*>(renderer);
+    if (!pt || !pt->UploadScene()) { fprintf(stderr, "--denoise: the renderer has no device context\n"); return false; }
+    const uint32 w = viewport.GetWidth(), h = viewport.GetHeight(), passes = viewport.GetProgress().passesFinished ? viewport.GetProgress().passesFinished : 1u;
+    RtPassParams guide;
+    if (!viewport.NextPassParams(camera, guide)) return false;
+    RtDenoiseParams dp; memset(&dp, 0, sizeof(dp));
+    dp.iterations = levels; dp.flags = RT_DENOISE_DEMODULATE; dp.colorScale = 1.0f / (float)passes;
+    dp.sigmaColor = 2.0f; dp.sigmaNormal = 0.25f; dp.sigmaPlane = 0.1f;
+    std::vector<float> image((size_t)w * h * 3u);
+    const PostprocessParams& pp = viewport.GetPostprocessParams();
+    RtPostprocessParams p; memset(&p, 0, sizeof(p));
+    memcpy(p.colorFilter, &pp.colorFilter, 16);
+    p.exposure = pp.exposure; p.contrast = pp.contrast; p.saturation = pp.saturation; p.ditheringStrength = pp.ditheringStrength; p.bloomFactor = pp.bloomFactor;
+    p.tonemapper = (uint32)pp.tonemapper; p.numPasses = 1u; p.ditherSeed = passes;   // (the image is averaged already: colorScale)
+    Bitmap::InitData init;
+    init.width = w; init.height = h; init.format = Bitmap::Format::B8G8R8A8_UNorm; init.linearSpace = false;   // as Viewport::GetFrontBuffer makes it
+    if (!front.Init(init)) return false;
+    if (rtgpu_denoise(pt->GetDeviceContext(), &dp, &guide, image.data()) != RTGPU_OK ||
+        rtgpu_postprocess_from(pt->GetDeviceContext(), &p, image.data(), reinterpret_cast<uint32*>(front.GetBytes())) != RTGPU_OK)
+    {
+        fprintf(stderr, "--denoise: %s\n", rtgpu_last_error());
+        return false;
+    }
+    return true;
+}
+
 int main(int argc, char* argv[])
 {
     uint32 width = 1280, height = 720, passes = 64, depth = 20;
     bool debugPixel = false; uint32 debugX = 0, debugY = 0;
+    uint32 denoiseLevels = 0;
     std::string scenePath, rendererName = "Path Tracer MIS", output = "out.bmp";
     unsigned long long seed = 0; bool haveSeed = false;
     for (int i = 1; i < argc; ++i)
@@ -90,7 +122,13 @@ int main(int argc, char* argv[])
         else if (a == "--output") output = value("--output");
         else if (a == "--seed") { seed = strtoull(value("--seed"), nullptr, 10); haveSeed = true; }
         else if (a == "--debug-pixel") { if (sscanf(value("--debug-pixel"), "%u,%u", &debugX, &debugY) != 2) { fprintf(stderr, "--debug-pixel takes X,Y\n"); return 2; } debugPixel = true; }
-        else { fprintf(stderr, "usage: rt_demo -s scene.json [--data dir/] [-w W] [-h H] [--passes N] [--depth D] [--renderer name] [--output out.bmp] [--seed N] [--debug-pixel X,Y]\n"); return 2; }
+        else if (a == "--denoise")
+        {
+            denoiseLevels = 5;   // the level count is optional
+            if (i + 1 < argc && argv[i + 1][0] >= '0' && argv[i + 1][0] <= '9') denoiseLevels = (uint32)atoi(argv[++i]);
+            if (denoiseLevels < 1 || denoiseLevels > 8) { fprintf(stderr, "--denoise takes 1..8 levels\n"); return 2; }
+        }
+        else { fprintf(stderr, "usage: rt_demo -s scene.json [--data dir/] [-w W] [-h H] [--passes N] [--depth D] [--renderer name] [--output out.bmp] [--seed N] [--debug-pixel X,Y] [--denoise [N]]\n"); return 2; }
     }
     if (scenePath.empty()) { fprintf(stderr, "no scene given (-s scene.json)\n"); return 2; }
 
@@ -125,7 +163,10 @@ int main(int argc, char* argv[])
     printf("%u passes of %ux%u in %.3f s: %.1f Msamples/s (%llu paths x bounces, %llu shadow rays), average error %g\n", passes, width, height, seconds,
            (double)counters.numRays / seconds / 1.0e6, (unsigned long long)counters.numRays, (unsigned long long)counters.numShadowRays,
            (double)viewport.GetProgress().averageError);
-    if (!SaveBMP(output.c_str(), viewport.GetFrontBuffer())) { fprintf(stderr, "cannot write %s\n", output.c_str()); return 1; }
+    Bitmap denoised;
+    if (denoiseLevels && !DenoisedFrontBuffer(viewport, camera, renderer.get(), denoiseLevels, denoised)) return 1;
+    if (denoiseLevels) printf("denoised: %u levels of the a-trous filter\n", denoiseLevels);
+    if (!SaveBMP(output.c_str(), denoiseLevels ? denoised : viewport.GetFrontBuffer())) { fprintf(stderr, "cannot write %s\n", output.c_str()); return 1; }
     printf("wrote %s\n", output.c_str());
     return 0;
 }

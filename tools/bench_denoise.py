@@ -1,0 +1,97 @@
+#!/usr/bin/env python3
+"""Time of the denoiser (include/rtgpu.h: rtgpu_denoise_async through Viewport.denoise(device=True)) on the Sponza-class 1920 x 1080 frame
+(raytracer_amd.scenes.sponza_class, 262 176 triangles) after 20 passes: one call with 1 .. 5 levels, the guide render alone (the four planes through
+Viewport.render_aovs(device=True)), the filter alone on those planes (raytracer_amd.atrous_filter on tensors) and -- for scale, same context -- one render
+pass.  Prints one JSON line and, with --output, writes it to a file.
+
+Timing, after a warm-up of every shape (scratch growth, code objects), `--reps` repetitions (median, min, max): device events around the call on a
+stream of the tool's own; the render pass: host wall time around a batch of passes that ends in rtgpu_synchronize, per pass.
+`gbytes_per_s_compulsory`: the 64 bytes per pixel and level that a level cannot avoid (three 16-byte records read, one written) over the filter's time --
+what the 25-tap gather achieves against the traffic a perfect cache would leave, not a share of peak.
+
+The tiled / direct A/B: the same command under RTGPU_DENOISE_TILED=0 and =1 (the knob is read once per process), alternating.
+
+  python tools/bench_denoise.py [--reps 20] [--output profiles/denoise_bench_1080p.json]"""
+import argparse
+import json
+import os
+import sys
+import time
+
+import numpy as np
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+
+
+def time_call(torch, fn, reps):
+    for _ in range(3):
+        fn()
+    torch.cuda.synchronize()
+    ms = []
+    for _ in range(reps):
+        a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        a.record()
+        fn()
+        b.record()
+        b.synchronize()
+        ms.append(a.elapsed_time(b))
+    ms = np.array(ms)
+    return {"ms_median": float(np.median(ms)), "ms_min": float(ms.min()), "ms_max": float(ms.max())}
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--reps", type=int, default=20)
+    ap.add_argument("--width", type=int, default=1920)
+    ap.add_argument("--height", type=int, default=1080)
+    ap.add_argument("--passes", type=int, default=20)
+    ap.add_argument("--depth", type=int, default=8)
+    ap.add_argument("--triangles", type=int, default=262144)
+    ap.add_argument("--output", default=None)
+    args = ap.parse_args()
+    import torch
+    import raytracer_amd as ra
+    from raytracer_amd import scenes
+    w, h = args.width, args.height
+    scene, camera = scenes.sponza_class(w / h, args.triangles)
+    vp = ra.Viewport(w, h, seed=1234, max_ray_depth=args.depth)
+    vp.set_renderer(scene)
+    lib, ctx = ra.rtgpu_lib(), vp.device_context()
+    vp.render(camera, passes=args.passes)
+    assert lib.rtgpu_synchronize(ctx) == 0
+    # a render pass of the same context, for scale: batches of `passes` passes, wall time to the end of the device work
+    per_pass = []
+    for _ in range(3):
+        t0 = time.perf_counter()
+        vp.render(camera, passes=args.passes)
+        assert lib.rtgpu_synchronize(ctx) == 0
+        per_pass.append(1e3 * (time.perf_counter() - t0) / args.passes)
+    guide = vp.next_pass_params(camera)
+    out = {"scene": "sponza_class", "triangles": int(scene.desc.contents.numTriangles), "width": w, "height": h, "passes": vp.passes_finished, "reps": args.reps,
+           "RTGPU_DENOISE_TILED": os.environ.get("RTGPU_DENOISE_TILED"),   # None: the library's default
+           "render_pass_ms": {"median": float(np.median(per_pass)), "min": float(min(per_pass)), "max": float(max(per_pass)), "passes_per_batch": args.passes}}
+    names = ("depth", "normal", "position", "base_color")
+    stream = torch.cuda.Stream()   # (the null stream would send the calls through the wrappers' side stream)
+    with torch.cuda.stream(stream):
+        out["guide_render"] = time_call(torch, lambda: vp.render_aovs(guide, names, device=True), args.reps)
+        planes = vp.render_aovs(guide, names, device=True)
+        color = torch.from_numpy(vp.sum_buffer()).cuda()
+        stream.synchronize()
+        out["denoise"], out["filter_alone"] = {}, {}
+        for iterations in range(1, 6):
+            out["denoise"][str(iterations)] = time_call(torch, lambda: vp.denoise(guide, iterations=iterations, device=True), args.reps)
+            t = time_call(torch, lambda: ra.atrous_filter(color, planes["depth"], planes["normal"], planes["position"], planes["base_color"], iterations=iterations,
+                                                          color_scale=1.0 / vp.passes_finished, ctx=ctx), args.reps)
+            t["compulsory_bytes"] = 64 * w * h * iterations
+            t["gbytes_per_s_compulsory"] = t["compulsory_bytes"] / t["ms_median"] / 1e6
+            out["filter_alone"][str(iterations)] = t
+    line = json.dumps(out)
+    print(line)
+    if args.output:
+        with open(args.output, "w") as f:
+            f.write(line + "\n")
+
+
+if __name__ == "__main__":
+    main()
