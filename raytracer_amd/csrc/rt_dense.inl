@@ -43,8 +43,7 @@ __global__ void __launch_bounds__(RT_BLOCK) k_generate_dense(const RtSceneDesc s
             // (the consumers that do not rebuild a fresh path's other records from its slot: see denseShadeVertex)
             stStream(prec(paths, R_TP, slot), f4(1.0f, 1.0f, 1.0f, 1.0f));
             stStream(prec(paths, R_RESULT, slot), f4(0.0f, 0.0f, 0.0f, fbits(pix)));
-            stStream(prec(paths, R_SH_TP, slot), f4(0.0f, 0.0f, 0.0f, fbits(slot)));                    // .w: the path's home
-            storeSampler(sampler, paths, slot, 0.0f, 0u);
+            storeSampler(sampler, paths, slot, 0.0f, densePack(slot, 0u));   // the path's home; no request is pending
         }
     }
     if (blockIdx.x == 0 && threadIdx.x < RT_DENSE_SHARDS)
@@ -63,11 +62,34 @@ __global__ void __launch_bounds__(RT_BLOCK) k_generate_dense(const RtSceneDesc s
 struct DenseVertex
 {
     uint32_t outcome;
-    float4 oOrigin, oDir, oTp, oResult, oSampler, oRng;
-    bool stagedShTp;     // stage[3][thread] holds R_SH_TP (throughput at the vertex | home); otherwise it is {0, 0, 0, home}
+    float4 oOrigin, oDir, oTp, oResult, oSampler, oRng;   // (oSampler.w: densePack(home, requests); with requests, stage[3][thread] holds R_SH_TP and, for a zombie, stage[2][thread] its R_ORIGIN)
     bool rayNeeded;      // the vertex's next-event request needs its shadow ray
-    uint32_t oHome, rayMask;
+    uint32_t rayMask;
 };
+
+// resolvePendingLightSamples (rt_shade.inl) over a dense arena: the verdict of a request rides in its contribution record (.w < 0: no ray was needed, or
+// the walk found an occluder), and the records -- the contributions and the throughput at the vertex -- are fetched as ONE group: one wait, not three.
+// Same sum, same order, same fma.
+template <bool kAll>
+RT_DEV void denseResolvePending(const Paths& in, uint32_t slot, uint32_t numRequests, V4 lightSamplingWeight, V4& resultColor, Counters& cnt)
+{
+    if (numRequests == 0u) return;
+    const float4 tp = ldStream(prec(in, R_SH_TP, slot));
+    V4 accumulated = zero4();
+    bool any = false;
+    const uint32_t n = kAll ? numRequests : 1u;
+    for (uint32_t l = 0; l < n; ++l)
+    {
+        const float4 c = ldStream(pshadow(in, l, 1, slot));
+        if (c.w < 0.0f) continue;
+        accumulated = accumulated + V4(c.x, c.y, c.z, 0.0f);
+        any = true;
+        cnt.c[C_SHADOW_HIT]++;   // counters.numShadowRaysHit: the shadow ray reached the light (PathTracerMIS.cpp:96-99)
+    }
+    if (!any) return;
+    accumulated = accumulated * lightSamplingWeight;
+    resultColor = mulAdd(V4(tp.x, tp.y, tp.z, 0.0f), accumulated, resultColor);
+}
 
 // The body of PathTracerMIS::RenderPixel's loop for one path vertex (PathTracerMIS.cpp:276-395) over the records of arena `in` at `slot`;
 // kPlain: PathTracer::RenderPixel (Core/Rendering/PathTracer.cpp:73-171).  `stage` = four LDS rows of RT_BLOCK float4 (the next-event request
@@ -80,25 +102,31 @@ __device__ __forceinline__ static void denseShadeVertex(const RtSceneDesc& scene
 {
     // Bounce 0 (primarySlotPixel != null): k_generate_dense stores only what depends on the camera sample -- origin and direction.  The other five
     // records of a fresh path are functions of its slot (radiance 0 | pixel, throughput 1, home = slot, the sampler and the per-pixel generator as
-    // the camera left them) and are rebuilt here instead of being written and read back: 80 of 112 bytes per path in each direction.
+    // the camera left them) and are rebuilt here instead of being written and read back: 64 of 96 bytes per path in each direction.
+    // Two trips to memory before the geometry gather: every record whose address the slot alone decides is requested here, at the top (a zombie has only
+    // the first two); the pending request's records follow as one group (denseResolvePending) as soon as R_SAMPLER.w says there is one.
+    // (The plain path tracer has no requests to resolve, so nothing waits between the top and loadSampler: its R_RNG stays where it was, four registers
+    // the tail's plain instantiation does not have.)
+    constexpr bool kEarlyRng = !kPlain;
     const bool primary = primarySlotPixel != nullptr;
-    float4 rResult, rSampler, rShTp;
+    float4 rResult, rSampler;
+    float4 rOrigin = f4(0.0f, 0.0f, 0.0f, 0.0f), rDir = rOrigin, rHit = rOrigin, rRng = rOrigin, rTp = f4(1.0f, 1.0f, 1.0f, 1.0f);
     if (primary)
     {
         rResult = f4(0.0f, 0.0f, 0.0f, fbits(primarySlotPixel[slot - (slot / slotsPerPass) * slotsPerPass]));
-        rSampler = f4(prec(in, R_SAMPLER, slot).x, 0.0f, 0.0f, fbits(0u));   // .x: the hit's v, written by the traversal; no request is pending
-        rShTp = f4(0.0f, 0.0f, 0.0f, fbits(slot));
+        rSampler = f4(prec(in, R_SAMPLER, slot).x, 0.0f, 0.0f, fbits(densePack(slot, 0u)));   // .x: the hit's v, written by the traversal; no request is pending
     }
-    else { rResult = ldStream(prec(in, R_RESULT, slot)); rSampler = ldStream(prec(in, R_SAMPLER, slot)); rShTp = ldStream(prec(in, R_SH_TP, slot)); }
-    const uint32_t pix = ubits(rResult.w), homeIndex = ubits(rShTp.w);
-    v.oHome = homeIndex;
-    V4 resultColor(rResult.x, rResult.y, rResult.z, 0.0f);
-    resolvePendingLightSamples(in, slot, ubits(rSampler.w), lightSamplingWeight, resultColor, cnt);   // NEE of the previous vertex
+    else { rResult = ldStream(prec(in, R_RESULT, slot)); rSampler = ldStream(prec(in, R_SAMPLER, slot)); }
     if (!zombie)
     {
-        const float4 rOrigin = ldStream(prec(in, R_ORIGIN, slot)), rDir = ldStream(prec(in, R_DIR, slot)), rHit = ldStream(prec(in, R_HIT, slot));
-        float4 rTp = f4(1.0f, 1.0f, 1.0f, 1.0f);
-        if (!primary) rTp = ldStream(prec(in, R_TP, slot));
+        rOrigin = ldStream(prec(in, R_ORIGIN, slot)); rDir = ldStream(prec(in, R_DIR, slot)); rHit = ldStream(prec(in, R_HIT, slot));
+        if (!primary) { rTp = ldStream(prec(in, R_TP, slot)); if (kEarlyRng) rRng = ldStream(prec(in, R_RNG, slot)); }
+    }
+    const uint32_t pix = ubits(rResult.w), homeIndex = denseHome(ubits(rSampler.w));
+    V4 resultColor(rResult.x, rResult.y, rResult.z, 0.0f);
+    denseResolvePending<kAll>(in, slot, densePending(ubits(rSampler.w)), lightSamplingWeight, resultColor, cnt);   // NEE of the previous vertex
+    if (!zombie)
+    {
         const uint32_t flags = ubits(rOrigin.w);
         const uint32_t depth = flags & 0xFFu;
         const bool lastSpecular = (flags & 0x100u) != 0;
@@ -179,7 +207,7 @@ __device__ __forceinline__ static void denseShadeVertex(const RtSceneDesc& scene
                 V4 cameraOrigin, cameraDirection;
                 cameraGenerateRayParts(own.camera, coords, sampler, cameraOrigin, cameraDirection);
             }
-            else { loadSampler(sampler, in, slot, pix, rSampler, pass, scene.blueNoise); sampler.seed = passes[homeIndex / slotsPerPass].seed; }
+            else { if (!kEarlyRng) rRng = ldStream(prec(in, R_RNG, slot)); loadSampler(sampler, pix, rSampler, rRng, pass, scene.blueNoise); sampler.seed = passes[homeIndex / slotsPerPass].seed; }
 
             // SampleLights (next event estimation), PathTracerMIS.cpp:125-155
             if (!kPlain && kAll && scene.numLights != 0)
@@ -188,13 +216,13 @@ __device__ __forceinline__ static void denseShadeVertex(const RtSceneDesc& scene
                 {
                     float4 dirTmax, contribution;
                     if (computeLightSample<kLean>(scene, pass, sampler, scene.lights[l], sd, mat, depth, lightPickProbability, dirTmax, contribution)) v.rayMask |= 1u << l;
+                    else contribution.w = -1.0f;   // a request without a ray: the mark the walks leave on an occluded one (verdictRecord)
                     pshadow(in, l, 0, slot) = dirTmax; pshadow(in, l, 1, slot) = contribution;
                 }
                 v.rayNeeded = v.rayMask != 0u;
                 numRequests = v.rayNeeded ? scene.numLights : 0u;
                 stage[2][threadIdx.x] = f4(sd.intersection.frame.r[3].x, sd.intersection.frame.r[3].y, sd.intersection.frame.r[3].z, 0.0f);
-                stage[3][threadIdx.x] = f4(throughput.x, throughput.y, throughput.z, fbits(homeIndex));
-                v.stagedShTp = true;
+                stage[3][threadIdx.x] = f4(throughput.x, throughput.y, throughput.z, 0.0f);
             }
             else if (!kPlain && scene.numLights != 0)
             {
@@ -205,8 +233,7 @@ __device__ __forceinline__ static void denseShadeVertex(const RtSceneDesc& scene
                 numRequests = v.rayNeeded ? 1u : 0u;   // a request without a ray contributes nothing (resolvePendingLightSamples skips it): not kept
                 stage[0][threadIdx.x] = oShadow0; stage[1][threadIdx.x] = oShadow1;
                 stage[2][threadIdx.x] = f4(sd.intersection.frame.r[3].x, sd.intersection.frame.r[3].y, sd.intersection.frame.r[3].z, 0.0f);
-                stage[3][threadIdx.x] = f4(throughput.x, throughput.y, throughput.z, fbits(homeIndex));
-                v.stagedShTp = true;
+                stage[3][threadIdx.x] = f4(throughput.x, throughput.y, throughput.z, 0.0f);
             }
             bool cont = depth < pass.maxRayDepth;
             if (cont && depth >= pass.minRussianRouletteDepth)   // Russian roulette, :330-347
@@ -236,15 +263,14 @@ __device__ __forceinline__ static void denseShadeVertex(const RtSceneDesc& scene
             }
             if (v.outcome == 1)
             {
-                v.oSampler = f4(0.0f, fbits(sampler.salt), fbits(sampler.generated), fbits(numRequests));
+                v.oSampler = f4(0.0f, fbits(sampler.salt), fbits(sampler.generated), fbits(densePack(homeIndex, numRequests)));
                 v.oRng = f4(fbits((uint32_t)sampler.fallback.s[0]), fbits((uint32_t)(sampler.fallback.s[0] >> 32)),
                           fbits((uint32_t)sampler.fallback.s[1]), fbits((uint32_t)(sampler.fallback.s[1] >> 32)));
-                if (numRequests == 0u) v.stagedShTp = false;
             }
             else if (v.rayNeeded)
             {
                 v.outcome = 2;   // the path ends here, its last next-event sample still needs its shadow ray
-                v.oSampler = f4(0.0f, 0.0f, 0.0f, fbits(numRequests));
+                v.oSampler = f4(0.0f, 0.0f, 0.0f, fbits(densePack(homeIndex, numRequests)));
             }
         } while (false);
         if (v.outcome != 1) cnt.c[C_RAYS] += depth + 1u;   // counters.numRays += depth + 1, PathTracerMIS.cpp:412
@@ -308,7 +334,7 @@ __global__ void RT_SHADE_DENSE_ATTR(kLean, kAll) k_shade_dense(const RtSceneDesc
         const uint32_t i = first + threadIdx.x;
         // what this vertex leaves behind: 0 nothing (radiance parked), 1 a live path, 2 a zombie (radiance + one pending request)
         DenseVertex v;
-        v.outcome = 0; v.stagedShTp = false; v.rayNeeded = false; v.oHome = 0u; v.rayMask = 0u;
+        v.outcome = 0; v.rayNeeded = false; v.rayMask = 0u;
         uint32_t inSlot = 0u;
         if (i < count)
         {
@@ -339,18 +365,18 @@ __global__ void RT_SHADE_DENSE_ATTR(kLean, kAll) k_shade_dense(const RtSceneDesc
             // the vertex is dropped and the frame is invalid until the next reset (every synchronising call reports the flag); its home still gets what
             // the path had gathered, so that k_accumulate_home never adds a previous batch's value
             dense.errorFlags[0] = 1u; outcome = 0;
-            stStream(home[v.oHome], f4(v.oResult.x, v.oResult.y, v.oResult.z, 0.0f));
+            stStream(home[denseHome(ubits(v.oSampler.w))], f4(v.oResult.x, v.oResult.y, v.oResult.z, 0.0f));
         }
         if (outcome != 0)
         {
             const uint32_t slot = outcome == 1 ? shard * dense.shardCapacity + sLiveBase + rank : (shard + 1u) * dense.shardCapacity - 1u - (sZombieBase + rank);
             stStream(prec(out, R_RESULT, slot), v.oResult);
             stStream(prec(out, R_SAMPLER, slot), v.oSampler);
-            stStream(prec(out, R_SH_TP, slot), v.stagedShTp ? sStage[3][threadIdx.x] : f4(0.0f, 0.0f, 0.0f, fbits(v.oHome)));
             if (outcome == 1) { stStream(prec(out, R_ORIGIN, slot), v.oOrigin); stStream(prec(out, R_DIR, slot), v.oDir); stStream(prec(out, R_TP, slot), v.oTp); stStream(prec(out, R_RNG, slot), v.oRng); }
-            if (ubits(v.oSampler.w) != 0u)
+            else stStream(prec(out, R_ORIGIN, slot), sStage[2][threadIdx.x]);   // a zombie: the origin of its any-hit rays (a live path's R_ORIGIN is that point already)
+            if (densePending(ubits(v.oSampler.w)) != 0u)
             {
-                stStream(prec(out, R_SH_P, slot), sStage[2][threadIdx.x]);
+                stStream(prec(out, R_SH_TP, slot), sStage[3][threadIdx.x]);
                 if (kAll)
                 {
                     for (uint32_t l = 0; l < scene.numLights; ++l)

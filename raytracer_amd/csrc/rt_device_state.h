@@ -15,17 +15,19 @@ using namespace rtd;
 enum PathRecord : uint32_t
 {
     R_ORIGIN,    // ray origin xyz BEFORE the 1e-3 offset | flags: depth (bits 0-7), lastSpecular << 8, (previous vertex's material + 1) << 9
+                 // (dense arenas: also the origin of the vertex's any-hit rays -- the same point -- and, for a zombie, nothing else; shadowOriginRecord)
     R_DIR,       // ray direction xyz as passed to Ray()   | lastPdfW
     R_TP,        // throughput (4 lanes: RayColor::AlmostZero tests all four)
     R_RESULT,    // accumulated radiance rgb of this path  | pixel: x | y << 16
     R_HIT,       // objectId, subObjectId, distance, u
-    R_SAMPLER,   // hit v | GenericSampler salt, generated | number of NEE requests pending for this vertex
+    R_SAMPLER,   // hit v | GenericSampler salt, generated | number of NEE requests pending for this vertex (dense arenas: | home index << 3, densePending)
     R_RNG,       // per-pixel xoroshiro128+ state (2 x 64 bit)
-    R_SH_P,      // shading point xyz (shadow ray origin before the 1e-4 offset)
-    R_SH_TP,     // throughput at the vertex (the NEE fma uses it)
+    R_SH_P,      // shading point xyz (shadow ray origin before the 1e-4 offset); the dense arenas do not use it (R_ORIGIN holds the same point)
+    R_SH_TP,     // throughput at the vertex (the NEE fma uses it); dense arenas: written and read only while a request is pending
     R_NUM_BASE
 };
-// per NEE request two records, light-major: {direction xyz, tmax (< 0: no ray / occluded)}, {contribution rgb, -}
+// per NEE request two records, light-major: {direction xyz, tmax (< 0: no ray / occluded)}, {contribution rgb, -}.  Dense arenas (verdictRecord = 1):
+// {direction xyz, tmax (< 0: no ray)}, {contribution rgb, < 0: no ray / occluded} -- the resolving vertex reads one record per request, not two
 #define RT_SHADOW_RECORDS 2
 
 struct Paths
@@ -33,7 +35,16 @@ struct Paths
     float4* base;       // (R_NUM_BASE + maxLights * RT_SHADOW_RECORDS) * capacity records
     uint32_t capacity;
     uint32_t maxLights; // NEE requests per vertex (1 for LightSamplingStrategy::Single)
+    // Launch-uniform layout choices the shared any-hit walks follow.  The defaults are the first layout's (slot-per-pixel k_shade, the ray queries, VCM, the
+    // recorder); the two dense arenas and k_tail's in-place arena use denseLayout().
+    // ONE word for both (0: first layout, 1: dense): the walks have no scalar register to spare for a second one.
+    uint32_t dense = 0u;
 };
+__host__ __device__ inline static Paths denseLayout(Paths p) { p.dense = 1u; return p; }
+// the record whose xyz is the origin of the slot's any-hit rays: R_SH_P, or -- dense -- R_ORIGIN, which holds the same point
+RT_DEV uint32_t shadowOriginRecord(const Paths& p) { return p.dense != 0u ? (uint32_t)R_ORIGIN : (uint32_t)R_SH_P; }
+// which record of a request (pshadow's k) gets .w = -1 when its ray is occluded: the direction record, or -- dense -- the contribution record
+RT_DEV uint32_t verdictRecord(const Paths& p) { return p.dense; }
 
 RT_DEV float4& prec(const Paths& p, uint32_t record, uint32_t slot) { return p.base[(size_t)record * p.capacity + slot]; }
 RT_DEV float4& pshadow(const Paths& p, uint32_t light, uint32_t k, uint32_t slot)
@@ -103,15 +114,18 @@ RT_DEV void zeroCounters(Counters& c) {
     for (int k = 0; k < RT_NUM_COUNTERS; ++k) c.c[k] = 0;
 }
 
-// GenericSampler + per-pixel RNG state of a path (R_SAMPLER.yz, R_RNG); `sampler` is the record already loaded
-RT_DEV void loadSampler(Sampler& s, const Paths& p, uint32_t slot, uint32_t pix, const float4& sampler, const DevPass& pass, const uint16_t* blueNoise)
+// GenericSampler + per-pixel RNG state of a path (R_SAMPLER.yz, R_RNG); `sampler` and `rng` are the records already loaded
+RT_DEV void loadSampler(Sampler& s, uint32_t pix, const float4& sampler, const float4& rng, const DevPass& pass, const uint16_t* blueNoise)
 {
     s.seed = pass.seed; s.numDims = pass.numDimensions; s.blueNoiseLayers = pass.blueNoiseLayers; s.blueNoise = blueNoise;
     s.bx = (pix & 0xFFFFu) & 127u; s.by = (pix >> 16) & 127u;
     s.salt = ubits(sampler.y); s.generated = ubits(sampler.z);
-    const float4 rng = prec(p, R_RNG, slot);
     s.fallback.s[0] = (uint64_t)ubits(rng.x) | ((uint64_t)ubits(rng.y) << 32);
     s.fallback.s[1] = (uint64_t)ubits(rng.z) | ((uint64_t)ubits(rng.w) << 32);
+}
+RT_DEV void loadSampler(Sampler& s, const Paths& p, uint32_t slot, uint32_t pix, const float4& sampler, const DevPass& pass, const uint16_t* blueNoise)
+{
+    loadSampler(s, pix, sampler, prec(p, R_RNG, slot), pass, blueNoise);
 }
 RT_DEV void storeSampler(const Sampler& s, const Paths& p, uint32_t slot, float hitV, uint32_t pendingRequests)
 {
@@ -168,6 +182,13 @@ RT_DEV uint32_t denseLiveSlot(const uint32_t* sPrefix, uint32_t shardCapacity, u
 }
 
 #define RT_DENSE_MAX_LIGHTS 7u   // 256 vertices x 7 requests fit the block's append buffer between two flushes (k_shade_dense)
+// R_SAMPLER.w of a dense arena: the pending-request count in the low bits, the path's home index (pass in batch * slotsPerPass + pixel slot) above
+#define RT_DENSE_PENDING_BITS 3u
+#define RT_DENSE_MAX_HOME (1u << (32u - RT_DENSE_PENDING_BITS))   // home indices of a batch stay below this (flushBatch bounds the batch)
+static_assert(RT_DENSE_MAX_LIGHTS < (1u << RT_DENSE_PENDING_BITS), "the pending-request count of a dense vertex has RT_DENSE_PENDING_BITS bits");
+RT_DEV uint32_t densePack(uint32_t home, uint32_t pending) { return (home << RT_DENSE_PENDING_BITS) | pending; }
+RT_DEV uint32_t densePending(uint32_t packed) { return packed & ((1u << RT_DENSE_PENDING_BITS) - 1u); }
+RT_DEV uint32_t denseHome(uint32_t packed) { return packed >> RT_DENSE_PENDING_BITS; }
 
 // Occupancy the register allocator is held to per scene class: "lean + simple bitmaps" needs 135 VGPRs on its own and fits four waves per SIMD with
 // 8-16 bytes of scratch (measured +4 % end to end on the textured Sponza-class scene); "lean + textures" 173 -> 168 = three waves (+8 %), "anything"

@@ -26,6 +26,7 @@ static inline void readContextKnobs(RtgpuContext* c)
     c->wide2Allowed = envInt("RTGPU_WIDE2", 1) != 0;
     c->denseAllowed = envInt("RTGPU_NO_DENSE", 0) == 0;
     c->countIntersections = envInt("RTGPU_INTERSECTION_COUNTERS", 0) != 0;
+    c->anyHitFarFirst = envInt("RTGPU_ANYHIT_FAR_FIRST", 1) != 0 ? 1u : 0u;   // test hook: every 4-wide walk of the context, k_tail's included
     if (envSet("RTGPU_PASS_BATCH")) { c->passBatch = (uint32_t)envInt("RTGPU_PASS_BATCH", 0); c->passBatchFromEnv = true; }
     if (c->passBatch < 1) c->passBatch = 1;
     if (c->passBatch > RT_SEED_RING / 2) c->passBatch = RT_SEED_RING / 2;
@@ -64,8 +65,7 @@ RT_KNOB_ONCE(bool, denoiseTiled, envInt("RTGPU_DENOISE_TILED", 1) != 0)         
 #undef RT_KNOB_ONCE
 
 // ---- 3. per call -----------------------------------------------------------------------------------------------------------------------------
-// every launch of a 4-wide walk (and of k_tail, which walks the same tree)
-static inline uint32_t anyHitFarFirst() { return envInt("RTGPU_ANYHIT_FAR_FIRST", 1) != 0 ? 1u : 0u; }
+// every launch of a 4-wide walk
 static inline uint32_t wideReverse() { return (uint32_t)envInt("RTGPU_WIDE_REVERSE", 0); }
 static inline uint32_t wideDrainAbort() { return (uint32_t)envInt("RTGPU_WIDE_DRAIN_ABORT", 0); }   // test hook; 0: off
 static inline uint32_t wideDiagMode() { return (uint32_t)envInt("RTGPU_WIDE_DIAG", 0); }

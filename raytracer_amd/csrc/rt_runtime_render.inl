@@ -157,8 +157,8 @@ static void launchTraceWide(RtgpuContext* c, hipStream_t stream, unsigned long l
     // (profiles/r06_claim_order_ab.txt).  RTGPU_WIDE_REVERSE=1: from the end (read per launch: the tests run both orders)
     tune.reverseOrder = knobs::wideReverse();
     // any-hit rays walk the FARTHEST child they enter first (rt_wide_walk.h, interior step: occlusion is an OR over the candidates, and the occluders of a ray that starts on a
-    // surface are far from it); RTGPU_ANYHIT_FAR_FIRST=0: nearest first like closest-hit rays (read per launch: the tests run both orders)
-    tune.anyHitFarFirst = knobs::anyHitFarFirst();
+    // surface are far from it); RTGPU_ANYHIT_FAR_FIRST=0: nearest first like closest-hit rays (read when the context is created: the tests run both orders)
+    tune.anyHitFarFirst = c->anyHitFarFirst;
     const dim3 grid(traversalBlocks(c, 24u)), block(RT_BLOCK);
     LaunchTimer t(c, stream, KC_TRACE);
     if (c->wide.nodes == nullptr)
@@ -260,12 +260,13 @@ static int submitDenseBatch(RtgpuContext* c, BatchLane& l, const LaneCounts& cou
     const uint32_t tailDepth = tailDepthFor(c, maxRayDepth, denseAll);
     for (uint32_t depth = 0; depth <= maxRayDepth + 1u; ++depth)
     {
-        const Paths& in = (depth & 1u) ? l.paths2 : l.paths;
-        const Paths& out = (depth & 1u) ? l.paths : l.paths2;
+        // (the dense record layout: any-hit origins in R_ORIGIN, verdicts in the contribution record -- rt_device_state.h)
+        const Paths in = denseLayout((depth & 1u) ? l.paths2 : l.paths);
+        const Paths out = denseLayout((depth & 1u) ? l.paths : l.paths2);
         if (tailDepth != 0u && depth == tailDepth)
         {
             const TailArgs args = { l.denseCounts + (size_t)plane * depth, shardCapacity, counts.cursors + depth, c->tune.refillMinIdle, c->tune.otherMinLanes, c->deviceFlags,
-                                    knobs::anyHitFarFirst() };
+                                    c->anyHitFarFirst };
             uint32_t tailBlocks = (totalSlots + RT_TAIL_PATHS - 1u) / RT_TAIL_PATHS;   // never more blocks than chunks of the whole batch
             if (tailBlocks > c->numCUs * knobs::tailBlocksPerCU()) tailBlocks = c->numCUs * knobs::tailBlocksPerCU();   // tuning knob
             const dim3 tailGrid(tailBlocks ? tailBlocks : 1u);
@@ -379,11 +380,17 @@ static int flushBatch(RtgpuContext* c, uint32_t maxPasses)
     // is what the lane's allocation holds, the rest stays queued for the next flush.
     {
         const size_t perPass = c->numSlots ? c->numSlots : 1u;
-        while (numPasses > 1u && (arenaCapacityFor(perPass * numPasses) > l.paths.capacity || (l.paths2.base && perPass * numPasses > l.homeCapacity))) --numPasses;
+        // (dense path state: a path's home index shares a word with its pending-request count, rt_device_state.h -- whatever the lane budget allowed)
+        while (numPasses > 1u && (arenaCapacityFor(perPass * numPasses) > l.paths.capacity || (l.paths2.base && (perPass * numPasses > l.homeCapacity || perPass * numPasses > RT_DENSE_MAX_HOME)))) --numPasses;
         if (arenaCapacityFor(perPass * numPasses) > l.paths.capacity || (l.paths2.base && perPass * numPasses > l.homeCapacity))
         {
             c->pending.clear();
             return fail(RTGPU_ERR_OUT_OF_MEMORY, "a batch lane's path-state arena does not hold one pass of this frame");
+        }
+        if (l.paths2.base && perPass * numPasses > RT_DENSE_MAX_HOME)
+        {
+            c->pending.clear();
+            return fail(RTGPU_ERR_UNSUPPORTED, "one pass of this frame exceeds the home index range of dense path state");
         }
     }
 

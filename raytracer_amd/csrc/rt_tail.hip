@@ -106,7 +106,7 @@ __global__ void RT_TAIL_ATTR(kLean, kPlain) k_tail RT_K_TAIL_ARGS
             const uint32_t slot = vertexSlot(idx, zombie);
             if (zombie) sLists[2u + cur][atomicAdd(&sN[TN_ZOMBIES], 1u)] = slot; else sLists[cur][atomicAdd(&sN[TN_LIVE], 1u)] = slot;
             // the next-event request the previous bounce's shade left with the vertex: its shadow ray has not been traced yet (request index = light 0 * capacity + slot)
-            if (ubits(prec(paths, R_SAMPLER, slot).w) != 0u && pshadow(paths, 0, 0, slot).w >= 0.0f) sLists[4][atomicAdd(&sN[TN_SHADOW], 1u)] = slot;
+            if (densePending(ubits(prec(paths, R_SAMPLER, slot).w)) != 0u && pshadow(paths, 0, 0, slot).w >= 0.0f) sLists[4][atomicAdd(&sN[TN_SHADOW], 1u)] = slot;
         }
         __syncthreads();
         while (sN[TN_LIVE] + sN[TN_ZOMBIES] != 0u)
@@ -138,21 +138,24 @@ __global__ void RT_TAIL_ATTR(kLean, kPlain) k_tail RT_K_TAIL_ARGS
                 const bool zombie = k >= nLive;
                 const uint32_t slot = zombie ? zombies[k - nLive] : live[k];
                 DenseVertex v;
-                v.outcome = 0; v.stagedShTp = false; v.rayNeeded = false; v.oHome = 0u; v.rayMask = 0u;
+                v.outcome = 0; v.rayNeeded = false; v.rayMask = 0u;
                 denseShadeVertex<kLean, kPlain, false>(scene, passes, slotsPerPass, pass, paths, slot, zombie, lightSamplingWeight, bsdfSamplingWeight, lightPickProbability, stage, home, cnt, v);
                 if (v.outcome == 0) continue;   // its radiance is parked
                 prec(paths, R_RESULT, slot) = v.oResult;
                 prec(paths, R_SAMPLER, slot) = v.oSampler;
-                prec(paths, R_SH_TP, slot) = v.stagedShTp ? stage[3][threadIdx.x] : f4(0.0f, 0.0f, 0.0f, fbits(v.oHome));
                 if (v.outcome == 1)
                 {
                     prec(paths, R_ORIGIN, slot) = v.oOrigin; prec(paths, R_DIR, slot) = v.oDir; prec(paths, R_TP, slot) = v.oTp; prec(paths, R_RNG, slot) = v.oRng;
                     nextLive[atomicAdd(&sN[TN_NEXT_LIVE], 1u)] = slot;
                 }
-                else nextZombies[atomicAdd(&sN[TN_NEXT_ZOMBIES], 1u)] = slot;
-                if (ubits(v.oSampler.w) != 0u)
+                else
                 {
-                    prec(paths, R_SH_P, slot) = stage[2][threadIdx.x];
+                    prec(paths, R_ORIGIN, slot) = stage[2][threadIdx.x];   // a zombie: the origin of its any-hit ray (a live path's R_ORIGIN is that point already)
+                    nextZombies[atomicAdd(&sN[TN_NEXT_ZOMBIES], 1u)] = slot;
+                }
+                if (densePending(ubits(v.oSampler.w)) != 0u)
+                {
+                    prec(paths, R_SH_TP, slot) = stage[3][threadIdx.x];
                     pshadow(paths, 0, 0, slot) = stage[0][threadIdx.x];
                     pshadow(paths, 0, 1, slot) = stage[1][threadIdx.x];
                     if (v.rayNeeded) sLists[4][atomicAdd(&sN[TN_SHADOW], 1u)] = slot;

@@ -41,7 +41,7 @@ RT_DEV void traceBinaryLoop(const RtSceneDesc& scene, const Paths& paths, const 
     {
         if (s.shadow)
         {
-            const float4 origin = prec(paths, R_SH_P, slot), dirTmax = pshadow(paths, light, 0, slot);
+            const float4 origin = prec(paths, shadowOriginRecord(paths), slot), dirTmax = pshadow(paths, light, 0, slot);
             Ray shadowRay = makeRay(V4(origin.x, origin.y, origin.z, 0.0f), V4(dirTmax.x, dirTmax.y, dirTmax.z, 0.0f));
             shadowRay.origin = shadowRay.origin + shadowRay.dir * tune.shadowOffset;   // PathTracerMIS.cpp:86
             return shadowRay;
@@ -253,7 +253,7 @@ RT_DEV void traceBinaryLoop(const RtSceneDesc& scene, const Paths& paths, const 
             {
                 if (s.shadow)
                 {
-                    if (s.occluded) pshadow(paths, light, 0, slot).w = -1.0f;   // unoccluded requests are tallied when they are resolved
+                    if (s.occluded) pshadow(paths, light, verdictRecord(paths), slot).w = -1.0f;   // unoccluded requests are tallied when they are resolved
                 }
                 else
                 {

@@ -113,7 +113,7 @@ RT_DEV void traceWideLoop(const RtSceneDesc& scene, const WideBvh& bvh, const Pa
                 {
                     // request = light * capacity + slot; one request per vertex (LightSamplingStrategy::Single: the arena holds one light's records) needs no division
                     if (paths.maxLights == 1u) { light = 0u; slot = request; } else { light = request / paths.capacity; slot = request - light * paths.capacity; }
-                    origin = ldStream(prec(paths, R_SH_P, slot)); dir = ldStream(pshadow(paths, light, 0, slot));
+                    origin = ldStream(prec(paths, shadowOriginRecord(paths), slot)); dir = ldStream(pshadow(paths, light, 0, slot));
                     maxDistance = dir.w;           // hitPoint.distance = illuminateResult.distance * 0.999f
                 }
                 else

@@ -83,7 +83,7 @@ __global__ void __launch_bounds__(RT_BLOCK) __attribute__((amdgpu_waves_per_eu(k
     auto loadWorldRay = [&]() -> Ray
     {
         float4 origin, dir;
-        if (shadow) { origin = ldStream(prec(paths, R_SH_P, slot)); dir = ldStream(pshadow(paths, light, 0, slot)); }
+        if (shadow) { origin = ldStream(prec(paths, shadowOriginRecord(paths), slot)); dir = ldStream(pshadow(paths, light, 0, slot)); }
         else { origin = ldStream(prec(paths, R_ORIGIN, slot)); dir = ldStream(prec(paths, R_DIR, slot)); }
         const Ray world = wideWorldRay(origin, dir, shadow, tune.shadowOffset);
         return world;

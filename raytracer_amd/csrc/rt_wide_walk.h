@@ -55,7 +55,7 @@ RT_DEV void widePushExact(const WideTuning& tune, const WideLocal& local, bool s
 }
 
 // ---- request ray ------------------------------------------------------------------------------------------------------------------------
-// The reference's world ray of a request from its records (closest-hit: R_ORIGIN, R_DIR; any-hit: R_SH_P and the light's shadow record): Ray::Ray
+// The reference's world ray of a request from its records (closest-hit: R_ORIGIN, R_DIR; any-hit: the record shadowOriginRecord names and the light's shadow record): Ray::Ray
 // normalises the direction (PathTracerMIS.cpp:86 / :392), then the origin moves along it -- shadowOffset (1e-4) for an any-hit ray, 1e-3 for a
 // bounce, not at all for a primary ray (bounce 0: the origin record's low byte) -- and originDivDir stays what Ray::Ray made it, STALE by that
 // offset (PathTracerMIS.cpp:392-393): that is what the reference's top-level box tests see, and what k_trace_wide2 parks for its top-level gates.
@@ -185,7 +185,7 @@ RT_DEV bool wideFinishRay(const Paths& paths, const WideTuning& tune, const Wide
 {
     const float inf = __uint_as_float(0x7f800000u);
     if (handOver) { widePushExact(tune, lists, shadow, shadow ? light * paths.capacity + slot : slot); return true; }
-    if (shadow) { if (occluded) pshadow(paths, light, 0, slot).w = -1.0f; return false; }
+    if (shadow) { if (occluded) pshadow(paths, light, verdictRecord(paths), slot).w = -1.0f; return false; }
     if (best == inf) { prec(paths, R_HIT, slot) = f4(fbits(RT_INVALID_OBJECT), fbits(0u), inf, 0.0f); return false; }   // HitPoint.h:14-51
     if (!(second <= best + tol)) return false;
     widePushExact(tune, lists, false, slot);   // a runner-up too close to call: the reference's own walk decides
