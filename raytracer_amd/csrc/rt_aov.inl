@@ -29,7 +29,7 @@ __global__ void __launch_bounds__(RT_BLOCK) k_aov_resolve RT_K_AOV_RESOLVE_ARGS
     const uint32_t i = blockIdx.x * RT_BLOCK + threadIdx.x;
     if (i >= count) return;
     const float4 rHit = prec(paths, R_HIT, i);
-    Hit hit; hit.objectId = ubits(rHit.x); hit.subObjectId = ubits(rHit.y); hit.distance = rHit.z; hit.u = rHit.w; hit.v = prec(paths, R_SAMPLER, i).x;
+    const Hit hit = unpackHit(rHit, prec(paths, R_SAMPLER, i).x);
     const bool isHit = hit.objectId != RT_INVALID_OBJECT;
     const bool isLight = isHit && hit.subObjectId == RT_LIGHT_OBJECT;
 

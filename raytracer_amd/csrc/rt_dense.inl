@@ -14,7 +14,9 @@
 //   * Finished paths park their radiance at home[pass * slotsPerPass + pixelSlot]; k_accumulate_home adds the passes of a batch to the
 //     film per pixel in pass order -- the float sums are those of the reference's pass-after-pass accumulation, whatever order the
 //     paths were compacted in.
-// Arithmetic and consumption order of the samples are those of k_shade (same functions, same sequence): the images are bit-identical.
+// Arithmetic and consumption order of the samples are those of k_shade: denseShadeVertex calls the same vertex stages in the same sequence (misGlobalLights,
+// misHitLight, misRoulette, misSampleBsdf, computeLightSample: rt_shade.inl) and keeps only what the layout decides -- record loads and stores, the pending
+// request's resolution, next-event staging, zombies and home[].  The images are bit-identical.
 #ifndef RT_SHADE_FUNCTIONS_ONLY
 // k_generate for dense state: slot i = home i; the regions of the first arena are simply filled one after the other
 __global__ void __launch_bounds__(RT_BLOCK) k_generate_dense(const RtSceneDesc scene, const DevPass* __restrict__ passes, uint32_t slotsPerPass, const Paths paths,
@@ -133,31 +135,14 @@ __device__ __forceinline__ static void denseShadeVertex(const RtSceneDesc& scene
         const float lastPdfW = rDir.w;
         const Ray ray = makePathRay(rOrigin, rDir, depth);
         V4 throughput(rTp.x, rTp.y, rTp.z, rTp.w);
-        Hit hit;
-        hit.objectId = ubits(rHit.x); hit.subObjectId = ubits(rHit.y); hit.distance = rHit.z; hit.u = rHit.w; hit.v = rSampler.x;
+        const Hit hit = unpackHit(rHit, rSampler.x);
         uint32_t numRequests = 0;
         do
         {
             if (hit.objectId == RT_INVALID_OBJECT)
             {
-                // EvaluateGlobalLights, PathTracerMIS.cpp:214-252
-                V4 result = zero4();
-                for (uint32_t g = 0; g < scene.numGlobalLights; ++g)
-                {
-                    const RtLight& light = scene.lights[scene.globalLights[g]];
-                    const Ray lightSpaceRay = transformRayUnsafe(loadM4(light.invTransform), ray);
-                    float directPdfW = 0.0f;
-                    const V4 lightContribution = lightGetRadiance<kLean>(scene, light, lightSpaceRay, zero4(), 1.0f, directPdfW);
-                    if (kPlain) result = result + lightContribution;   // PathTracer::EvaluateGlobalLights, PathTracer.cpp:47-71
-                    else if (!almostZero4(lightContribution))
-                    {
-                        float misWeight = 1.0f;
-                        if (depth > 0 && !lastSpecular) misWeight = CombineMis(lastPdfW, directPdfW * lightPickProbability);
-                        result = mulAdd(lightContribution, misWeight, result);
-                    }
-                }
-                if (!kPlain) result = result * bsdfSamplingWeight;
-                resultColor = mulAdd(throughput, result, resultColor);
+                // EvaluateGlobalLights
+                resultColor = mulAdd(throughput, misGlobalLights<kLean, kPlain>(scene, ray, depth, lastSpecular, lastPdfW, lightPickProbability, bsdfSamplingWeight), resultColor);
                 break;
             }
             ShadingData sd;
@@ -165,28 +150,8 @@ __device__ __forceinline__ static void denseShadeVertex(const RtSceneDesc& scene
             if (hit.distance < FLT_MAX) sceneEvaluateIntersection<kLean>(scene, ray, hit, sd.intersection, cnt);
             if (!RT_LEAN(kLean) && hit.subObjectId == RT_LIGHT_OBJECT)
             {
-                // EvaluateLight, PathTracerMIS.cpp:174-212
-                const RtObject& obj = scene.objects[hit.objectId];
-                const RtLight& light = scene.lights[obj.lightIndex];
-                const M4 worldToLight = loadM4(obj.invTransform);
-                const Ray lightSpaceRay = transformRayUnsafe(worldToLight, ray);
-                const V4 lightSpaceHitPoint = transformPoint(worldToLight, sd.intersection.frame.r[3]);
-                const float cosAtLight = -dot3(sd.intersection.frame.r[2], ray.dir);
-                float directPdfA = 0.0f;
-                V4 lightContribution = lightGetRadiance<false>(scene, light, lightSpaceRay, lightSpaceHitPoint, cosAtLight, directPdfA);
-                if (kPlain) resultColor = mulAdd(throughput, lightContribution, resultColor);   // PathTracer::EvaluateLight, PathTracer.cpp:26-45
-                else if (!almostZero4(lightContribution))
-                {
-                    float misWeight = 1.0f;
-                    if (depth > 0 && !lastSpecular)
-                    {
-                        const float directPdfW = PdfAtoW(directPdfA, hit.distance, cosAtLight);
-                        misWeight = CombineMis(lastPdfW, directPdfW * lightPickProbability);
-                    }
-                    lightContribution = lightContribution * bsdfSamplingWeight;
-                    resultColor = mulAdd(throughput, lightContribution * misWeight, resultColor);
-                }
-                else resultColor = mulAdd(throughput, zero4(), resultColor);
+                // EvaluateLight
+                misHitLight<kPlain>(scene, hit, ray, sd.intersection, throughput, depth, lastSpecular, lastPdfW, lightPickProbability, bsdfSamplingWeight, resultColor);
                 break;
             }
             sd.outgoingDirWorldSpace = neg(ray.dir);
@@ -236,36 +201,16 @@ __device__ __forceinline__ static void denseShadeVertex(const RtSceneDesc& scene
                 stage[3][threadIdx.x] = f4(throughput.x, throughput.y, throughput.z, 0.0f);
             }
             bool cont = depth < pass.maxRayDepth;
-            if (cont && depth >= pass.minRussianRouletteDepth)   // Russian roulette, :330-347
+            if (cont && depth >= pass.minRussianRouletteDepth) cont = misRoulette(sampler, sd.mp.baseColor, throughput);
+            if (cont)   // BSDF sampling; the next ray's records
             {
-                const float minColorValue = 0.125f;
-                const float threshold = minColorValue + (1.0f - minColorValue) * colorMax(sd.mp.baseColor);
-                if (sampler.getFloat() > threshold) cont = false;
-                else throughput = throughput * (1.0f / threshold);
-            }
-            if (cont)   // BSDF sampling, :349-395
-            {
-                float pdf = 0.0f; V4 incomingDirWorldSpace = zero4(); uint32_t event = EV_NULL;
-                float u[3]; u[0] = sampler.getFloat(); u[1] = sampler.getFloat(); u[2] = sampler.getFloat();
-                const V4 bsdfValue = materialSample<kLean>(mat, sd, u, incomingDirWorldSpace, pdf, event);
-                if (event != EV_NULL)
-                {
-                    throughput = throughput * bsdfValue;
-                    if (!almostZero4(throughput))
-                    {
-                        v.oOrigin = f4(sd.intersection.frame.r[3].x, sd.intersection.frame.r[3].y, sd.intersection.frame.r[3].z,
-                                     fbits((depth + 1u) | (((event & EV_SPECULAR) != 0) ? 0x100u : 0u) | ((sd.intersection.material + 1u) << 9)));
-                        v.oDir = f4(incomingDirWorldSpace.x, incomingDirWorldSpace.y, incomingDirWorldSpace.z, pdf);
-                        v.oTp = f4(throughput.x, throughput.y, throughput.z, throughput.w);
-                        v.outcome = 1;
-                    }
-                }
+                uint32_t event;
+                if (misSampleBsdf<kLean>(sampler, mat, sd, depth, throughput, event, v.oOrigin, v.oDir, v.oTp)) v.outcome = 1;
             }
             if (v.outcome == 1)
             {
                 v.oSampler = f4(0.0f, fbits(sampler.salt), fbits(sampler.generated), fbits(densePack(homeIndex, numRequests)));
-                v.oRng = f4(fbits((uint32_t)sampler.fallback.s[0]), fbits((uint32_t)(sampler.fallback.s[0] >> 32)),
-                          fbits((uint32_t)sampler.fallback.s[1]), fbits((uint32_t)(sampler.fallback.s[1] >> 32)));
+                v.oRng = packRng(sampler);
             }
             else if (v.rayNeeded)
             {
@@ -302,16 +247,7 @@ __global__ void RT_SHADE_DENSE_ATTR(kLean, kAll) k_shade_dense(const RtSceneDesc
     __shared__ uint32_t sLivePrefix[RT_DENSE_SHARDS + 1u], sZombiePrefix[RT_DENSE_SHARDS + 1u];
     if (threadIdx.x == 0) { sShadowCount = 0; sLive = 0; sZombies = 0; }
     denseLoadPrefix(dense.in, sLivePrefix);
-    if (threadIdx.x == 64)
-    {
-        uint32_t sum = 0;
-        for (uint32_t s = 0; s < RT_DENSE_SHARDS; ++s)
-        {
-            sZombiePrefix[s] = sum; sum += dense.in[RT_DENSE_SHARDS + s];
-            if (blockIdx.x == 0 && dense.in[s] + dense.in[RT_DENSE_SHARDS + s] > dense.shardCapacity) dense.errorFlags[0] = 1u;   // the launch before this one overfilled region s
-        }
-        sZombiePrefix[RT_DENSE_SHARDS] = sum;
-    }
+    denseLoadZombiePrefix(dense.in, dense.shardCapacity, dense.errorFlags, sZombiePrefix);
     __syncthreads();
     Counters cnt; zeroCounters(cnt);
     const uint32_t numLive = sLivePrefix[RT_DENSE_SHARDS], count = numLive + sZombiePrefix[RT_DENSE_SHARDS];
@@ -321,14 +257,6 @@ __global__ void RT_SHADE_DENSE_ATTR(kLean, kAll) k_shade_dense(const RtSceneDesc
     const float lightPickProbability = kAll ? 1.0f : 1.0f / (float)(scene.numLights ? scene.numLights : 1u);   // GetLightPickingProbability, PathTracerMIS.cpp:157-172
 
     const uint32_t rounded = (count + RT_BLOCK - 1) / RT_BLOCK * RT_BLOCK;
-    // the i-th vertex of the launch: live paths first (region by region), then the zombies (from the top of their regions)
-    auto vertexSlot = [&](uint32_t idx, bool& zombie) -> uint32_t
-    {
-        zombie = idx >= numLive;
-        if (!zombie) return denseLiveSlot(sLivePrefix, dense.shardCapacity, idx);
-        const uint32_t z = idx - numLive, s = denseRegionOf(sZombiePrefix, z);
-        return (s + 1u) * dense.shardCapacity - 1u - (z - sZombiePrefix[s]);
-    };
     for (uint32_t first = blockIdx.x * blockDim.x; first < rounded; first += stride)
     {
         const uint32_t i = first + threadIdx.x;
@@ -339,7 +267,7 @@ __global__ void RT_SHADE_DENSE_ATTR(kLean, kAll) k_shade_dense(const RtSceneDesc
         if (i < count)
         {
             bool zombie;
-            const uint32_t slot = vertexSlot(i, zombie);
+            const uint32_t slot = denseVertexSlot(sLivePrefix, sZombiePrefix, numLive, dense.shardCapacity, i, zombie);
             inSlot = slot;
             denseShadeVertex<kLean, kPlain, kAll>(scene, passes, slotsPerPass, pass, in, slot, zombie, lightSamplingWeight, bsdfSamplingWeight, lightPickProbability, sStage, home, cnt, v,
                                                   dense.primarySlotPixel);

@@ -127,11 +127,22 @@ RT_DEV void loadSampler(Sampler& s, const Paths& p, uint32_t slot, uint32_t pix,
 {
     loadSampler(s, pix, sampler, prec(p, R_RNG, slot), pass, blueNoise);
 }
+// R_RNG: the four words of the per-pixel generator, as loadSampler reads them back
+RT_DEV float4 packRng(const Sampler& s)
+{
+    return f4(fbits((uint32_t)s.fallback.s[0]), fbits((uint32_t)(s.fallback.s[0] >> 32)), fbits((uint32_t)s.fallback.s[1]), fbits((uint32_t)(s.fallback.s[1] >> 32)));
+}
 RT_DEV void storeSampler(const Sampler& s, const Paths& p, uint32_t slot, float hitV, uint32_t pendingRequests)
 {
     prec(p, R_SAMPLER, slot) = f4(hitV, fbits(s.salt), fbits(s.generated), fbits(pendingRequests));
-    prec(p, R_RNG, slot) = f4(fbits((uint32_t)s.fallback.s[0]), fbits((uint32_t)(s.fallback.s[0] >> 32)),
-                              fbits((uint32_t)s.fallback.s[1]), fbits((uint32_t)(s.fallback.s[1] >> 32)));
+    prec(p, R_RNG, slot) = packRng(s);
+}
+// the Hit a closest-hit walk left in R_HIT; its v rides in R_SAMPLER.x
+RT_DEV Hit unpackHit(const float4& rHit, float v)
+{
+    Hit hit;
+    hit.objectId = ubits(rHit.x); hit.subObjectId = ubits(rHit.y); hit.distance = rHit.z; hit.u = rHit.w; hit.v = v;
+    return hit;
 }
 
 // The path's current ray exactly as the reference holds it: Ray(origin, direction) -- which normalises and
@@ -179,6 +190,32 @@ RT_DEV uint32_t denseLiveSlot(const uint32_t* sPrefix, uint32_t shardCapacity, u
 {
     const uint32_t s = denseRegionOf(sPrefix, idx);
     return s * shardCapacity + (idx - sPrefix[s]);
+}
+// The same prefix sums for the zombie counts (counts[16, 32)), by thread 64 while thread 0 sums the live ones; all threads of the block call it and
+// synchronise afterwards.  Block 0 also checks the final counts of the launch before: it overfilled region s if the live paths growing up met the
+// zombies growing down.
+RT_DEV void denseLoadZombiePrefix(const uint32_t* counts, uint32_t shardCapacity, uint32_t* errorFlags, uint32_t* sZombiePrefix)
+{
+    if (threadIdx.x == 64)
+    {
+        uint32_t sum = 0;
+        for (uint32_t s = 0; s < RT_DENSE_SHARDS; ++s)
+        {
+            sZombiePrefix[s] = sum; sum += counts[RT_DENSE_SHARDS + s];
+            if (blockIdx.x == 0 && counts[s] + counts[RT_DENSE_SHARDS + s] > shardCapacity) errorFlags[0] = 1u;
+        }
+        sZombiePrefix[RT_DENSE_SHARDS] = sum;
+    }
+}
+// slot of the idx-th vertex of a launch: the live paths first (region by region), then the zombies (from the top of their regions).  numLive is
+// sLivePrefix[RT_DENSE_SHARDS], which both callers hold in a register: read from LDS again here, it moves the register allocation of the kernels
+// the benchmark runs (k_shade_dense<1, false, false> 116 -> 115 VGPRs, k_tail<1, false> 84 -> 76 bytes of scratch).
+RT_DEV uint32_t denseVertexSlot(const uint32_t* sLivePrefix, const uint32_t* sZombiePrefix, uint32_t numLive, uint32_t shardCapacity, uint32_t idx, bool& zombie)
+{
+    zombie = idx >= numLive;
+    if (!zombie) return denseLiveSlot(sLivePrefix, shardCapacity, idx);
+    const uint32_t z = idx - numLive, s = denseRegionOf(sZombiePrefix, z);
+    return (s + 1u) * shardCapacity - 1u - (z - sZombiePrefix[s]);
 }
 
 #define RT_DENSE_MAX_LIGHTS 7u   // 256 vertices x 7 requests fit the block's append buffer between two flushes (k_shade_dense)

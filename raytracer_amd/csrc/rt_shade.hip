@@ -1,5 +1,6 @@
 // rt_shade.hip -- the shading kernels of the library, a translation unit of their own: PathTracerMIS / PathTracer / Debug shading over
-// slot-per-pixel and dense path state (rt_shade.inl with rt_shade_body.inl, rt_dense.inl), the bidirectional integrator's kernels (rt_vcm.inl) and the
+// slot-per-pixel and dense path state (rt_shade.inl with rt_shade_body.inl, rt_dense.inl: two layouts around ONE set of vertex stages, the mis* functions
+// of rt_shade.inl), the bidirectional integrator's kernels (rt_vcm.inl) and the
 // resolve kernel of rtgpu_render_aovs (rt_aov.inl).  The host side
 // (rt_runtime.hip) launches them through the declarations of rt_shade_kernels.h.
 //

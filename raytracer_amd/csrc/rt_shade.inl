@@ -1,5 +1,6 @@
 // rt_shade.inl -- PathTracerMIS / PathTracer / Debug shading over slot-per-pixel path state, and Film::AccumulateColor (k_accumulate).
-// Included by rt_shade.hip.
+// Its functions-only part also holds the vertex stages that every PathTracerMIS shading kernel shares, whatever its path state: misGlobalLights,
+// misHitLight, misRoulette, misSampleBsdf and computeLightSample.  Included by rt_shade.hip, and by rt_tail.hip for those functions.
 RT_DEV float CombineMis(float samplePdf, float otherPdf) { return FastDivide(samplePdf, samplePdf + otherPdf); }        // PathTracerMIS.cpp:16-24
 RT_DEV float PdfAtoW(float pdfA, float distance, float cosThere) { return FastDivide(pdfA * Sqr(distance), Abs(cosThere)); }   // :26-29
 
@@ -70,6 +71,100 @@ RT_DEV void resolvePendingLightSamples(const Paths& paths, uint32_t slot, uint32
     accumulated = accumulated * lightSamplingWeight;
     const float4 tp = prec(paths, R_SH_TP, slot);
     resultColor = mulAdd(V4(tp.x, tp.y, tp.z, 0.0f), accumulated, resultColor);
+}
+
+// ---- The stages of one vertex of PathTracerMIS::RenderPixel's loop (PathTracerMIS.cpp:276-395) that do not depend on where the path's records live:
+// the slot-per-pixel body (rt_shade_body.inl) and denseShadeVertex (rt_dense.inl) call them in the same order around their own loads, stores and
+// next-event code.  kPlain: the renderer "Path Tracer" (PathTracer::RenderPixel, Core/Rendering/PathTracer.cpp:73-171), the same walk without MIS
+// weights and sampling weights. ----
+
+// EvaluateGlobalLights, PathTracerMIS.cpp:214-252: what a ray that left the scene sees; the caller multiplies it into the throughput
+template <int kLean, bool kPlain>
+__device__ __forceinline__ static V4 misGlobalLights(const RtSceneDesc& scene, const Ray& ray, uint32_t depth, bool lastSpecular, float lastPdfW,
+                                                     float lightPickProbability, V4 bsdfSamplingWeight)
+{
+    V4 result = zero4();
+    for (uint32_t g = 0; g < scene.numGlobalLights; ++g)
+    {
+        const RtLight& light = scene.lights[scene.globalLights[g]];
+        const Ray lightSpaceRay = transformRayUnsafe(loadM4(light.invTransform), ray);
+        float directPdfW = 0.0f;
+        const V4 lightContribution = lightGetRadiance<kLean>(scene, light, lightSpaceRay, zero4(), 1.0f, directPdfW);
+        if (kPlain) result = result + lightContribution;   // PathTracer::EvaluateGlobalLights, PathTracer.cpp:47-71
+        else if (!almostZero4(lightContribution))
+        {
+            float misWeight = 1.0f;
+            if (depth > 0 && !lastSpecular) misWeight = CombineMis(lastPdfW, directPdfW * lightPickProbability);
+            result = mulAdd(lightContribution, misWeight, result);
+        }
+    }
+    if (!kPlain) result = result * bsdfSamplingWeight;
+    return result;
+}
+
+// EvaluateLight, PathTracerMIS.cpp:174-212: the path hit an area light (hit.subObjectId == RT_LIGHT_OBJECT) and ends there
+template <bool kPlain>
+__device__ __forceinline__ static void misHitLight(const RtSceneDesc& scene, const Hit& hit, const Ray& ray, const Intersection& intersection, V4 throughput,
+                                                   uint32_t depth, bool lastSpecular, float lastPdfW, float lightPickProbability, V4 bsdfSamplingWeight, V4& resultColor)
+{
+    const RtObject& obj = scene.objects[hit.objectId];
+    const RtLight& light = scene.lights[obj.lightIndex];
+    const M4 worldToLight = loadM4(obj.invTransform);
+    const Ray lightSpaceRay = transformRayUnsafe(worldToLight, ray);
+    const V4 lightSpaceHitPoint = transformPoint(worldToLight, intersection.frame.r[3]);
+    const float cosAtLight = -dot3(intersection.frame.r[2], ray.dir);
+    float directPdfA = 0.0f;
+    V4 lightContribution = lightGetRadiance<false>(scene, light, lightSpaceRay, lightSpaceHitPoint, cosAtLight, directPdfA);
+    if (kPlain) resultColor = mulAdd(throughput, lightContribution, resultColor);   // PathTracer::EvaluateLight, PathTracer.cpp:26-45
+    else if (!almostZero4(lightContribution))
+    {
+        float misWeight = 1.0f;
+        if (depth > 0 && !lastSpecular)
+        {
+            const float directPdfW = PdfAtoW(directPdfA, hit.distance, cosAtLight);
+            misWeight = CombineMis(lastPdfW, directPdfW * lightPickProbability);
+        }
+        lightContribution = lightContribution * bsdfSamplingWeight;
+        resultColor = mulAdd(throughput, lightContribution * misWeight, resultColor);
+    }
+    else resultColor = mulAdd(throughput, zero4(), resultColor);   // (the reference's fma with a zero contribution: kept for the bits of resultColor)
+}
+
+// Russian roulette, PathTracerMIS.cpp:330-347: false = the path ends here; else the throughput is divided by the survival probability
+__device__ __forceinline__ static bool misRoulette(Sampler& sampler, V4 baseColor, V4& throughput)
+{
+    bool cont = true;
+    const float minColorValue = 0.125f;
+    const float threshold = minColorValue + (1.0f - minColorValue) * colorMax(baseColor);
+    if (sampler.getFloat() > threshold) cont = false;
+    else throughput = throughput * (1.0f / threshold);
+    return cont;
+}
+
+// BSDF sampling, PathTracerMIS.cpp:349-395: true = the path goes on, and oOrigin / oDir / oTp are the next ray's R_ORIGIN, R_DIR and R_TP.
+// `event` is the sampled event either way: EV_NULL tells a path that ended without one from one whose throughput went to zero.
+template <int kLean>
+__device__ __forceinline__ static bool misSampleBsdf(Sampler& sampler, const RtMaterial& mat, const ShadingData& sd, uint32_t depth, V4& throughput, uint32_t& event,
+                                                     float4& oOrigin, float4& oDir, float4& oTp)
+{
+    bool alive = false;
+    float pdf = 0.0f; V4 incomingDirWorldSpace = zero4(); event = EV_NULL;
+    float u[3]; u[0] = sampler.getFloat(); u[1] = sampler.getFloat(); u[2] = sampler.getFloat();
+    const V4 bsdfValue = materialSample<kLean>(mat, sd, u, incomingDirWorldSpace, pdf, event);
+    if (event != EV_NULL)
+    {
+        throughput = throughput * bsdfValue;
+        if (!almostZero4(throughput))
+        {
+            // flags of the next vertex: depth, lastSpecular, and the material it leaves (see PathRecord, rt_device_state.h)
+            oOrigin = f4(sd.intersection.frame.r[3].x, sd.intersection.frame.r[3].y, sd.intersection.frame.r[3].z,
+                         fbits((depth + 1u) | (((event & EV_SPECULAR) != 0) ? 0x100u : 0u) | ((sd.intersection.material + 1u) << 9)));
+            oDir = f4(incomingDirWorldSpace.x, incomingDirWorldSpace.y, incomingDirWorldSpace.z, pdf);
+            oTp = f4(throughput.x, throughput.y, throughput.z, throughput.w);
+            alive = true;
+        }
+    }
+    return alive;
 }
 
 #define RT_APPEND_BUFFER 2048u
@@ -163,7 +258,7 @@ __global__ void __launch_bounds__(RT_BLOCK) k_debug_shade(const RtSceneDesc scen
         const uint32_t slot = queueIn[i];
         const float4 rOrigin = prec(paths, R_ORIGIN, slot), rDir = prec(paths, R_DIR, slot), rHit = prec(paths, R_HIT, slot);
         const Ray ray = makePathRay(rOrigin, rDir, 0u);
-        Hit hit; hit.objectId = ubits(rHit.x); hit.subObjectId = ubits(rHit.y); hit.distance = rHit.z; hit.u = rHit.w; hit.v = prec(paths, R_SAMPLER, slot).x;
+        const Hit hit = unpackHit(rHit, prec(paths, R_SAMPLER, slot).x);
         V4 color = zero4();
         if (hit.objectId != RT_INVALID_OBJECT)
         {

@@ -1,7 +1,9 @@
 // rt_shade_body.inl -- the shading kernel of the slot-per-pixel pipeline.  rt_shade.inl includes it twice: as k_shade (RT_SHADE_RECORDING 0: the blocks
 // under that switch are not there), and as k_shade_record (RT_SHADE_RECORDING 1), rtgpu_record_paths' variant, which also writes the path's vertices.
 //
-// The body of PathTracerMIS::RenderPixel's loop for one path vertex (PathTracerMIS.cpp:276-395).
+// The body of PathTracerMIS::RenderPixel's loop for one path vertex (PathTracerMIS.cpp:276-395).  What does not depend on where a path's records live
+// -- the lights a ray hits, Russian roulette, BSDF sampling with the packing of the next ray -- are the mis* stages of rt_shade.inl, which
+// denseShadeVertex (rt_dense.inl) calls too; here are the slot's loads and stores, next event estimation into the slot's request records, and the recorder.
 // kPlain: the renderer "Path Tracer" instead (PathTracer::RenderPixel, Core/Rendering/PathTracer.cpp:73-171): the same walk without
 // next event estimation, MIS weights and sampling weights.
 template <bool kLean, bool kPlain = false>
@@ -51,8 +53,7 @@ __global__ void __launch_bounds__(RT_BLOCK) RT_SHADE_KERNEL(const RtSceneDesc sc
             V4 throughput(rTp.x, rTp.y, rTp.z, rTp.w);
             V4 resultColor(rResult.x, rResult.y, rResult.z, 0.0f);
             resolvePendingLightSamples(paths, slot, ubits(rSampler.w), lightSamplingWeight, resultColor, cnt);   // NEE of the previous vertex
-            Hit hit;
-            hit.objectId = ubits(rHit.x); hit.subObjectId = ubits(rHit.y); hit.distance = rHit.z; hit.u = rHit.w; hit.v = rSampler.x;
+            const Hit hit = unpackHit(rHit, rSampler.x);
             bool samplerStored = false;
 #if RT_SHADE_RECORDING
             uint32_t reason = 0u;   // PathTerminationReason, set where PathTracerMIS.cpp:280-367 sets it
@@ -63,24 +64,8 @@ __global__ void __launch_bounds__(RT_BLOCK) RT_SHADE_KERNEL(const RtSceneDesc sc
             {
                 if (hit.objectId == RT_INVALID_OBJECT)
                 {
-                    // EvaluateGlobalLights, PathTracerMIS.cpp:214-252
-                    V4 result = zero4();
-                    for (uint32_t g = 0; g < scene.numGlobalLights; ++g)
-                    {
-                        const RtLight& light = scene.lights[scene.globalLights[g]];
-                        const Ray lightSpaceRay = transformRayUnsafe(loadM4(light.invTransform), ray);
-                        float directPdfW = 0.0f;
-                        const V4 lightContribution = lightGetRadiance<kLean>(scene, light, lightSpaceRay, zero4(), 1.0f, directPdfW);
-                        if (kPlain) result = result + lightContribution;   // PathTracer::EvaluateGlobalLights, PathTracer.cpp:47-71
-                        else if (!almostZero4(lightContribution))
-                        {
-                            float misWeight = 1.0f;
-                            if (depth > 0 && !lastSpecular) misWeight = CombineMis(lastPdfW, directPdfW * lightPickProbability);
-                            result = mulAdd(lightContribution, misWeight, result);
-                        }
-                    }
-                    if (!kPlain) result = result * bsdfSamplingWeight;
-                    resultColor = mulAdd(throughput, result, resultColor);
+                    // EvaluateGlobalLights
+                    resultColor = mulAdd(throughput, misGlobalLights<kLean, kPlain>(scene, ray, depth, lastSpecular, lastPdfW, lightPickProbability, bsdfSamplingWeight), resultColor);
 #if RT_SHADE_RECORDING
                     reason = RT_PATH_END_HIT_BACKGROUND;
                     storePathVertex(records, recordStride, slot, depth, ray, hit.objectId, 0u, hit.distance, 0.0f, 0.0f, zero4(), zero4(), zero4(), zero4(), throughput, 0u);
@@ -98,31 +83,8 @@ __global__ void __launch_bounds__(RT_BLOCK) RT_SHADE_KERNEL(const RtSceneDesc sc
 
                 if (!kLean && hit.subObjectId == RT_LIGHT_OBJECT)
                 {
-                    // EvaluateLight, PathTracerMIS.cpp:174-212
-                    const RtObject& obj = scene.objects[hit.objectId];
-                    const RtLight& light = scene.lights[obj.lightIndex];
-                    const M4 worldToLight = loadM4(obj.invTransform);
-                    const Ray lightSpaceRay = transformRayUnsafe(worldToLight, ray);
-                    const V4 lightSpaceHitPoint = transformPoint(worldToLight, sd.intersection.frame.r[3]);
-                    const float cosAtLight = -dot3(sd.intersection.frame.r[2], ray.dir);
-                    float directPdfA = 0.0f;
-                    V4 lightContribution = lightGetRadiance<false>(scene, light, lightSpaceRay, lightSpaceHitPoint, cosAtLight, directPdfA);
-                    if (kPlain) resultColor = mulAdd(throughput, lightContribution, resultColor);   // PathTracer::EvaluateLight, PathTracer.cpp:26-45
-                    else if (!almostZero4(lightContribution))
-                    {
-                        float misWeight = 1.0f;
-                        if (depth > 0 && !lastSpecular)
-                        {
-                            const float directPdfW = PdfAtoW(directPdfA, hit.distance, cosAtLight);
-                            misWeight = CombineMis(lastPdfW, directPdfW * lightPickProbability);
-                        }
-                        lightContribution = lightContribution * bsdfSamplingWeight;
-                        resultColor = mulAdd(throughput, lightContribution * misWeight, resultColor);
-                    }
-                    else
-                    {
-                        resultColor = mulAdd(throughput, zero4(), resultColor);
-                    }
+                    // EvaluateLight
+                    misHitLight<kPlain>(scene, hit, ray, sd.intersection, throughput, depth, lastSpecular, lastPdfW, lightPickProbability, bsdfSamplingWeight, resultColor);
 #if RT_SHADE_RECORDING
                     reason = RT_PATH_END_HIT_LIGHT;
                     storePathVertex(records, recordStride, slot, depth, ray, hit.objectId, hit.subObjectId, hit.distance, 0.0f, 0.0f, sd.intersection.frame.r[3], sd.intersection.frame.r[2],
@@ -175,38 +137,19 @@ __global__ void __launch_bounds__(RT_BLOCK) RT_SHADE_KERNEL(const RtSceneDesc sc
                 if (!cont) reason = RT_PATH_END_DEPTH;
 #endif
 
-                // Russian roulette, PathTracerMIS.cpp:330-347
-                if (cont && depth >= pass.minRussianRouletteDepth)
+                if (cont && depth >= pass.minRussianRouletteDepth)   // Russian roulette
                 {
-                    const float minColorValue = 0.125f;
-                    const float threshold = minColorValue + (1.0f - minColorValue) * colorMax(sd.mp.baseColor);
-                    if (sampler.getFloat() > threshold) cont = false;
-                    else throughput = throughput * (1.0f / threshold);
+                    cont = misRoulette(sampler, sd.mp.baseColor, throughput);
 #if RT_SHADE_RECORDING
                     if (!cont) reason = RT_PATH_END_RUSSIAN_ROULETTE;
 #endif
                 }
 
-                // BSDF sampling, PathTracerMIS.cpp:349-395
-                if (cont)
+                if (cont)   // BSDF sampling; the next ray's records
                 {
-                    float pdf = 0.0f; V4 incomingDirWorldSpace = zero4(); uint32_t event = EV_NULL;
-                    float u[3]; u[0] = sampler.getFloat(); u[1] = sampler.getFloat(); u[2] = sampler.getFloat();
-                    const V4 bsdfValue = materialSample<kLean>(mat, sd, u, incomingDirWorldSpace, pdf, event);
-                    if (event == EV_NULL) cont = false;
-                    else
-                    {
-                        throughput = throughput * bsdfValue;
-                        if (almostZero4(throughput)) cont = false;
-                        else
-                        {
-                            prec(paths, R_ORIGIN, slot) = f4(sd.intersection.frame.r[3].x, sd.intersection.frame.r[3].y, sd.intersection.frame.r[3].z,
-                                                             fbits((depth + 1u) | (((event & EV_SPECULAR) != 0) ? 0x100u : 0u) | ((sd.intersection.material + 1u) << 9)));
-                            prec(paths, R_DIR, slot) = f4(incomingDirWorldSpace.x, incomingDirWorldSpace.y, incomingDirWorldSpace.z, pdf);
-                            prec(paths, R_TP, slot) = f4(throughput.x, throughput.y, throughput.z, throughput.w);
-                            alive = true;
-                        }
-                    }
+                    // (straight into the slot's records: through locals, k_shade<false, true> and <true, false> each need ~15 VGPRs more and lose a wave per SIMD)
+                    uint32_t event;
+                    alive = misSampleBsdf<kLean>(sampler, mat, sd, depth, throughput, event, prec(paths, R_ORIGIN, slot), prec(paths, R_DIR, slot), prec(paths, R_TP, slot));
 #if RT_SHADE_RECORDING
                     if (!alive) reason = event == EV_NULL ? RT_PATH_END_NO_SAMPLED_EVENT : RT_PATH_END_THROUGHPUT;
                     else recordedEvent = event;

@@ -59,28 +59,9 @@ __global__ void RT_TAIL_ATTR(kLean, kPlain) k_tail RT_K_TAIL_ARGS
     float4 (*stage)[RT_BLOCK] = reinterpret_cast<float4 (*)[RT_BLOCK]>(sStack);
 
     denseLoadPrefix(args.denseCounts, sLivePrefix);
-    if (threadIdx.x == 64)
-    {
-        uint32_t sum = 0;
-        for (uint32_t s = 0; s < RT_DENSE_SHARDS; ++s)
-        {
-            sZombiePrefix[s] = sum; sum += args.denseCounts[RT_DENSE_SHARDS + s];
-            // the launch before this one overfilled region s (live paths growing up met the zombies growing down): k_shade_dense's prologue check, which the
-            // hand-over bounce would otherwise lose
-            if (blockIdx.x == 0 && args.denseCounts[s] + args.denseCounts[RT_DENSE_SHARDS + s] > args.shardCapacity) args.errorFlags[0] = 1u;
-        }
-        sZombiePrefix[RT_DENSE_SHARDS] = sum;
-    }
+    denseLoadZombiePrefix(args.denseCounts, args.shardCapacity, args.errorFlags, sZombiePrefix);   // (with k_shade_dense's overflow check, which the hand-over bounce would otherwise lose)
     __syncthreads();
     const uint32_t numLive = sLivePrefix[RT_DENSE_SHARDS], total = numLive + sZombiePrefix[RT_DENSE_SHARDS];
-    // the i-th vertex of the hand-over bounce: live paths first (region by region), then the zombies (from the top of their regions), as k_shade_dense
-    auto vertexSlot = [&](uint32_t idx, bool& zombie) -> uint32_t
-    {
-        zombie = idx >= numLive;
-        if (!zombie) return denseLiveSlot(sLivePrefix, args.shardCapacity, idx);
-        const uint32_t z = idx - numLive, s = denseRegionOf(sZombiePrefix, z);
-        return (s + 1u) * args.shardCapacity - 1u - (z - sZombiePrefix[s]);
-    };
     Counters cnt; zeroCounters(cnt);
     const DevPass pass = passes[0];   // the structural parameters are those of every pass of the batch
     const V4 lightSamplingWeight = load4(pass.lightSamplingWeight), bsdfSamplingWeight = load4(pass.bsdfSamplingWeight);
@@ -103,7 +84,7 @@ __global__ void RT_TAIL_ATTR(kLean, kPlain) k_tail RT_K_TAIL_ARGS
             const uint32_t idx = base + k;
             if (idx >= total) continue;
             bool zombie;
-            const uint32_t slot = vertexSlot(idx, zombie);
+            const uint32_t slot = denseVertexSlot(sLivePrefix, sZombiePrefix, numLive, args.shardCapacity, idx, zombie);
             if (zombie) sLists[2u + cur][atomicAdd(&sN[TN_ZOMBIES], 1u)] = slot; else sLists[cur][atomicAdd(&sN[TN_LIVE], 1u)] = slot;
             // the next-event request the previous bounce's shade left with the vertex: its shadow ray has not been traced yet (request index = light 0 * capacity + slot)
             if (densePending(ubits(prec(paths, R_SAMPLER, slot).w)) != 0u && pshadow(paths, 0, 0, slot).w >= 0.0f) sLists[4][atomicAdd(&sN[TN_SHADOW], 1u)] = slot;

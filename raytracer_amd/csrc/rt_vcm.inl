@@ -238,7 +238,7 @@ __global__ void RT_VCM_ATTR(k_vcm_light_shade) k_vcm_light_shade(const RtSceneDe
             float dVC = rMis.x, dVM = rMis.y, dVCM = rMis.z;
             const uint32_t length = ubits(rMis.w) & 0xFFu;
             const bool isFiniteLight = (ubits(rMis.w) & 0x200u) != 0u;
-            Hit hit; hit.objectId = ubits(rHit.x); hit.subObjectId = ubits(rHit.y); hit.distance = rHit.z; hit.u = rHit.w; hit.v = rSampler.x;
+            const Hit hit = unpackHit(rHit, rSampler.x);
             cnt.c[C_RAYS]++;
             if (hit.objectId != RT_INVALID_OBJECT && hit.subObjectId != RT_LIGHT_OBJECT)
             {
@@ -364,7 +364,7 @@ __global__ void RT_VCM_ATTR(k_lt_shade) k_lt_shade(const RtSceneDesc scene, cons
             const uint32_t depth = ubits(rOrigin.w) & 0xFFu;
             const Ray ray = makePathRay(rOrigin, rDir, depth);
             V4 throughput(rTp.x, rTp.y, rTp.z, rTp.w);
-            Hit hit; hit.objectId = ubits(rHit.x); hit.subObjectId = ubits(rHit.y); hit.distance = rHit.z; hit.u = rHit.w; hit.v = rSampler.x;
+            const Hit hit = unpackHit(rHit, rSampler.x);
             cnt.c[C_RAYS]++;
             if (hit.objectId != RT_INVALID_OBJECT && hit.subObjectId != RT_LIGHT_OBJECT)
             {
@@ -583,7 +583,7 @@ __global__ void RT_VCM_ATTR(k_vcm_camera_shade) k_vcm_camera_shade(const RtScene
                 dVC = 0.0f; dVM = 0.0f; dVCM = 1.0f / cameraPdf;
             }
             else { const float4 rMis = vrec(a, V_MIS, slot); dVC = rMis.x; dVM = rMis.y; dVCM = rMis.z; }
-            Hit hit; hit.objectId = ubits(rHit.x); hit.subObjectId = ubits(rHit.y); hit.distance = rHit.z; hit.u = rHit.w; hit.v = rSampler.x;
+            const Hit hit = unpackHit(rHit, rSampler.x);
             cnt.c[C_RAYS]++;
             uint32_t pendingBits = 0u;
             bool samplerStored = false;
