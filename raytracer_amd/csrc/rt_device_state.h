@@ -114,24 +114,31 @@ RT_DEV void zeroCounters(Counters& c) {
     for (int k = 0; k < RT_NUM_COUNTERS; ++k) c.c[k] = 0;
 }
 
+// a generator's pair of 64-bit words as the four lanes of a record (low word first), and back
+RT_DEV float4 packPair(const uint64_t s[2])
+{
+    return f4(fbits((uint32_t)s[0]), fbits((uint32_t)(s[0] >> 32)), fbits((uint32_t)s[1]), fbits((uint32_t)(s[1] >> 32)));
+}
+RT_DEV void unpackPair(const float4& r, uint64_t s[2])
+{
+    s[0] = (uint64_t)ubits(r.x) | ((uint64_t)ubits(r.y) << 32);
+    s[1] = (uint64_t)ubits(r.z) | ((uint64_t)ubits(r.w) << 32);
+}
+
 // GenericSampler + per-pixel RNG state of a path (R_SAMPLER.yz, R_RNG); `sampler` and `rng` are the records already loaded
 RT_DEV void loadSampler(Sampler& s, uint32_t pix, const float4& sampler, const float4& rng, const DevPass& pass, const uint16_t* blueNoise)
 {
     s.seed = pass.seed; s.numDims = pass.numDimensions; s.blueNoiseLayers = pass.blueNoiseLayers; s.blueNoise = blueNoise;
     s.bx = (pix & 0xFFFFu) & 127u; s.by = (pix >> 16) & 127u;
     s.salt = ubits(sampler.y); s.generated = ubits(sampler.z);
-    s.fallback.s[0] = (uint64_t)ubits(rng.x) | ((uint64_t)ubits(rng.y) << 32);
-    s.fallback.s[1] = (uint64_t)ubits(rng.z) | ((uint64_t)ubits(rng.w) << 32);
+    unpackPair(rng, s.fallback.s);
 }
 RT_DEV void loadSampler(Sampler& s, const Paths& p, uint32_t slot, uint32_t pix, const float4& sampler, const DevPass& pass, const uint16_t* blueNoise)
 {
     loadSampler(s, pix, sampler, prec(p, R_RNG, slot), pass, blueNoise);
 }
 // R_RNG: the four words of the per-pixel generator, as loadSampler reads them back
-RT_DEV float4 packRng(const Sampler& s)
-{
-    return f4(fbits((uint32_t)s.fallback.s[0]), fbits((uint32_t)(s.fallback.s[0] >> 32)), fbits((uint32_t)s.fallback.s[1]), fbits((uint32_t)(s.fallback.s[1] >> 32)));
-}
+RT_DEV float4 packRng(const Sampler& s) { return packPair(s.fallback.s); }
 RT_DEV void storeSampler(const Sampler& s, const Paths& p, uint32_t slot, float hitV, uint32_t pendingRequests)
 {
     prec(p, R_SAMPLER, slot) = f4(hitV, fbits(s.salt), fbits(s.generated), fbits(pendingRequests));

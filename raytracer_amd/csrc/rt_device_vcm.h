@@ -1,8 +1,9 @@
 // rt_device_vcm.h -- device functions of the bidirectional integrator (reference: Core/Rendering/VertexConnectionAndMerging.cpp)
 // beyond what the PathTracerMIS path already has: ILight::Emit, Illuminate / GetRadiance without solid-angle sampling and
-// their emission pdfs, BSDF::Pdf, Camera::WorldToFilm / PdfW, the film splat, the packed photon fields, the photon hash
-// grid query and Random::GetVector4.  Same arithmetic, same operation order as the reference's functions; every function
-// cites the lines it follows.
+// their emission pdfs, BSDF::Pdf, Camera::WorldToFilm / PdfW, the film splat, the packed photon fields, the view of
+// the photon hash grid (its cell hash: rt_vcm_photons.h; its range query: mergeCellRanges, rt_vcm.inl) and
+// Random::GetVector4.  Same arithmetic, same operation order as the reference's functions; every function cites the lines
+// it follows.
 #pragma once
 #include "rt_device_core.h"
 
@@ -133,44 +134,6 @@ struct HashGridView
     const Photon* photons; const uint32_t* cellEnds;
     float boxMin[3]; float radiusSqr, invCellSize; uint32_t hashTableMask, numPhotons;
 };
-RT_DEV int32_t cvtT(float f) { return (f >= 2147483648.0f || f < -2147483648.0f || f != f) ? (int32_t)0x80000000 : (int32_t)f; }   // _mm_cvttps_epi32
-RT_DEV uint32_t hashCellIndex(uint32_t x, uint32_t y, uint32_t z, uint32_t mask) { return ((x * 73856093u) ^ (y * 19349663u) ^ (z * 83492791u)) & mask; }   // :148-152
-RT_DEV uint32_t hashCellOfPoint(const float boxMin[3], float invCellSize, uint32_t mask, float px, float py, float pz)   // :160-167
-{
-    const float cx = invCellSize * (px - boxMin[0]), cy = invCellSize * (py - boxMin[1]), cz = invCellSize * (pz - boxMin[2]);
-    return hashCellIndex((uint32_t)cvtT(cx), (uint32_t)cvtT(cy), (uint32_t)cvtT(cz), mask);
-}
-// HashGrid::Process, :73-143: calls query(photonIndex) for every photon within the radius, cells and photons in the reference's order
-template <typename Query>
-RT_DEV void hashGridProcess(const HashGridView& g, V4 queryPos, Query& query)
-{
-    if (g.numPhotons == 0u) return;
-    const V4 distMin = queryPos - V4(g.boxMin[0], g.boxMin[1], g.boxMin[2], 0.0f);
-    const V4 cellCoords = mulSub(distMin, splat(g.invCellSize), splat(0.5f));
-    const int32_t cx = cvtT(cellCoords.x), cy = cvtT(cellCoords.y), cz = cvtT(cellCoords.z);
-    uint32_t numVisitedCells = 0, visitedCells[8];
-#pragma unroll
-    for (uint32_t i = 0; i < 8; ++i)
-    {
-        const uint32_t x = (uint32_t)cx + (i & 1), y = (uint32_t)cy + ((i >> 1) & 1), z = (uint32_t)cz + (i >> 2);
-        const uint32_t ci = hashCellIndex(x, y, z, g.hashTableMask);
-        bool visited = false;
-#pragma unroll
-        for (uint32_t j = 0; j < 8; ++j) if (j < numVisitedCells && visitedCells[j] == ci) visited = true;
-        if (!visited) visitedCells[numVisitedCells++] = ci;
-    }
-    for (uint32_t i = 0; i < numVisitedCells; ++i)
-    {
-        const uint32_t ci = visitedCells[i];
-        const uint32_t rangeStart = ci == 0 ? 0 : g.cellEnds[ci - 1], rangeEnd = g.cellEnds[ci];
-        for (uint32_t j = rangeStart; j < rangeEnd; ++j)
-        {
-            const Photon& ph = g.photons[j];
-            const float distSqr = sqrLength3(queryPos - V4(ph.px, ph.py, ph.pz, 0.0f));
-            if (distSqr <= g.radiusSqr) query(j);
-        }
-    }
-}
 
 // ---- lights ------------------------------------------------------------------------------------------------------------
 #define kSceneRadius (30.0f)   // BackgroundLight.cpp:16, DirectionalLight.cpp:14

@@ -37,16 +37,16 @@ static void freeVcm(RtgpuContext* c)
 static int ensureVcm(RtgpuContext* c, uint32_t maxLV, uint32_t batch)
 {
     RtgpuContext::Vcm& v = c->vcm;
-    const uint32_t requests = c->numLights + maxLV;
+    const uint32_t requests = (c->numLights + maxLV) ? c->numLights + maxLV : 1u;   // shadow requests per camera vertex: the arenas hold at least one
     const size_t cap = (size_t)(c->numSlots ? c->numSlots : 1) * batch;
     if (v.arena.recs && v.arena.capacity >= cap && v.arena.maxLV >= maxLV && v.requestsPerVertex >= requests && v.batchCapacity >= batch) return RTGPU_OK;
     HIP_TRY(syncLanes(c));
     freeVcm(c);
-    if ((unsigned long long)cap * (requests ? requests : 1u) >= 0xFFFFFFFFull) return fail(RTGPU_ERR_UNSUPPORTED, "pixels x passes x shadow requests per vertex exceeds the request index range");
+    if ((unsigned long long)cap * requests >= 0xFFFFFFFFull) return fail(RTGPU_ERR_UNSUPPORTED, "pixels x passes x shadow requests per vertex exceeds the request index range");
     HIP_TRY(hipMalloc((void**)&v.lightPaths.base, ((size_t)R_NUM_BASE + RT_SHADOW_RECORDS) * cap * sizeof(float4)));
     v.lightPaths.capacity = (uint32_t)cap; v.lightPaths.maxLights = 1;
-    HIP_TRY(hipMalloc((void**)&v.cameraPaths.base, ((size_t)R_NUM_BASE + (size_t)(requests ? requests : 1u) * RT_SHADOW_RECORDS) * cap * sizeof(float4)));
-    v.cameraPaths.capacity = (uint32_t)cap; v.cameraPaths.maxLights = requests ? requests : 1u;
+    HIP_TRY(hipMalloc((void**)&v.cameraPaths.base, ((size_t)R_NUM_BASE + (size_t)requests * RT_SHADOW_RECORDS) * cap * sizeof(float4)));
+    v.cameraPaths.capacity = (uint32_t)cap; v.cameraPaths.maxLights = requests;
     HIP_TRY(hipMalloc((void**)&v.arena.recs, (size_t)V_NUM * cap * sizeof(float4)));
     HIP_TRY(hipMalloc((void**)&v.arena.lightVertices, (size_t)maxLV * RT_VCM_LV_RECORDS * cap * sizeof(float4)));
     HIP_TRY(hipMalloc((void**)&v.arena.photonRaw, (size_t)maxLV * 2 * cap * sizeof(float4)));
@@ -55,7 +55,7 @@ static int ensureVcm(RtgpuContext* c, uint32_t maxLV, uint32_t batch)
     HIP_TRY(hipMalloc((void**)&v.connectQueue, cap * sizeof(uint32_t)));
     HIP_TRY(hipMalloc((void**)&v.overflowQueue, cap * sizeof(uint32_t)));
     HIP_TRY(hipMalloc((void**)&v.exactQueue, cap * sizeof(uint32_t)));
-    HIP_TRY(hipMalloc((void**)&v.exactShadowQueue, cap * (size_t)(requests ? requests : 1u) * sizeof(uint32_t)));
+    HIP_TRY(hipMalloc((void**)&v.exactShadowQueue, cap * (size_t)requests * sizeof(uint32_t)));
     HIP_TRY(hipMalloc((void**)&v.arena.lvCount, cap * sizeof(uint32_t)));
     HIP_TRY(hipMalloc((void**)&v.arena.photonCount, cap * sizeof(uint32_t)));
     HIP_TRY(hipMemset(v.arena.photonCount, 0, cap * sizeof(uint32_t)));
@@ -63,7 +63,7 @@ static int ensureVcm(RtgpuContext* c, uint32_t maxLV, uint32_t batch)
     v.arena.capacity = (uint32_t)cap; v.arena.maxLV = maxLV;
     for (int k = 0; k < 4; ++k) HIP_TRY(hipMalloc((void**)&v.queues[k], cap * sizeof(uint32_t)));
     for (int k = 0; k < 2; ++k) HIP_TRY(hipMalloc((void**)&v.shadowQueues[k], cap * sizeof(uint32_t)));
-    for (int k = 2; k < 4; ++k) HIP_TRY(hipMalloc((void**)&v.shadowQueues[k], cap * (size_t)(requests ? requests : 1u) * sizeof(uint32_t)));
+    for (int k = 2; k < 4; ++k) HIP_TRY(hipMalloc((void**)&v.shadowQueues[k], cap * (size_t)requests * sizeof(uint32_t)));
     HIP_TRY(hipMalloc((void**)&v.counts, (size_t)VCP_NUM_PLANES * RT_VCM_COUNT_PLANE * sizeof(uint32_t)));
     HIP_TRY(hipMalloc((void**)&v.passDev, (size_t)RT_VCM_MAX_BATCH * sizeof(DevPass)));
     HIP_TRY(hipMalloc((void**)&v.seedDev, (size_t)RT_VCM_MAX_BATCH * RTGPU_MAX_DIMENSIONS * sizeof(uint32_t)));
@@ -161,6 +161,23 @@ static int vcmBuildGrid(RtgpuContext* c, hipStream_t stream, uint32_t photonPass
     return RTGPU_OK;
 }
 
+// Both renderers work on the whole frame; `renderer` opens the message
+static int refusePartialFrame(RtgpuContext* c, const char* renderer)
+{
+    if (c->shard.rank != 0 || c->shard.worldSize != 1) return fail(RTGPU_ERR_UNSUPPORTED, std::string(renderer) + " needs the whole frame on one device (shard {0, 1})");
+    if (!c->activeMask.empty()) return fail(RTGPU_ERR_UNSUPPORTED, std::string(renderer) + " does not support active-block restriction");
+    return RTGPU_OK;
+}
+// the light vertices a sub-path can store: TraceLightPath's loop (.cpp:334) runs up to maxPathLength - 1; the arenas hold at least one
+static uint32_t vcmMaxLightVertices(const RtVcmParams& vp) { return vp.maxPathLength > 1u ? vp.maxPathLength - 1u : 1u; }
+// what a VCM pass needs of the frame and of the scene: a camera vertex's shadow requests are the bits of one 64-bit mask (k_vcm_camera_shade, k_vcm_connect)
+static int vcmRefusals(RtgpuContext* c)
+{
+    if (const int r = refusePartialFrame(c, "VCM")) return r;
+    if (c->numLights + vcmMaxLightVertices(c->vcm.params) > 64u) return fail(RTGPU_ERR_UNSUPPORTED, "VCM: lights + light vertices per pixel must not exceed 64");
+    return RTGPU_OK;
+}
+
 // Submits the queued VertexConnectionAndMerging passes as one batch (launch sequence: rt_vcm.inl)
 static int vcmFlush(RtgpuContext* c)
 {
@@ -168,13 +185,11 @@ static int vcmFlush(RtgpuContext* c)
     if (v.pending.empty()) return RTGPU_OK;
     const RtVcmParams& vp = v.params;
     const uint32_t numPasses = (uint32_t)v.pending.size();
-    const uint32_t maxLV = vp.maxPathLength > 1u ? vp.maxPathLength - 1u : 1u;
+    const uint32_t maxLV = vcmMaxLightVertices(vp);
     int r = RTGPU_OK;
     do
     {
-        if (c->shard.rank != 0 || c->shard.worldSize != 1) { r = fail(RTGPU_ERR_UNSUPPORTED, "VCM needs the whole frame on one device (shard {0, 1})"); break; }
-        if (!c->activeMask.empty()) { r = fail(RTGPU_ERR_UNSUPPORTED, "VCM does not support active-block restriction"); break; }
-        if (c->numLights + maxLV > 64u) { r = fail(RTGPU_ERR_UNSUPPORTED, "VCM: lights + light vertices per pixel must not exceed 64"); break; }
+        if ((r = vcmRefusals(c)) != RTGPU_OK) break;
         if ((r = flushPending(c)) != RTGPU_OK) break;
         { const hipError_t e = syncLanes(c); if (e != hipSuccess) { r = fail(RTGPU_ERR_DEVICE, hipGetErrorString(e)); break; } }
         if ((r = ensureVcm(c, maxLV, v.batch > numPasses ? v.batch : numPasses)) != RTGPU_OK) break;
@@ -280,9 +295,7 @@ static int vcmFlush(RtgpuContext* c)
 static int vcmRenderPass(RtgpuContext* c, const RtPassParams* p)
 {
     RtgpuContext::Vcm& v = c->vcm;
-    if (c->shard.rank != 0 || c->shard.worldSize != 1) return fail(RTGPU_ERR_UNSUPPORTED, "VCM needs the whole frame on one device (shard {0, 1})");
-    if (!c->activeMask.empty()) return fail(RTGPU_ERR_UNSUPPORTED, "VCM does not support active-block restriction");
-    if (c->numLights + (v.params.maxPathLength > 1u ? v.params.maxPathLength - 1u : 1u) > 64u) return fail(RTGPU_ERR_UNSUPPORTED, "VCM: lights + light vertices per pixel must not exceed 64");
+    if (const int r = vcmRefusals(c)) return r;
     if (p->passIndex == 0u && !v.pending.empty()) { const int r = vcmFlush(c); if (r) return r; }   // a restart begins its own batch
     if (v.pending.empty())
     {
@@ -290,7 +303,7 @@ static int vcmRenderPass(RtgpuContext* c, const RtPassParams* p)
         // (about 2 KB per pixel and pass at path length 10)
         uint32_t batch = knobs::vcmBatch() > 0 ? (uint32_t)knobs::vcmBatch() : 8u;
         if (batch > RT_VCM_MAX_BATCH) batch = RT_VCM_MAX_BATCH;
-        const uint32_t maxLV = v.params.maxPathLength > 1u ? v.params.maxPathLength - 1u : 1u;
+        const uint32_t maxLV = vcmMaxLightVertices(v.params);
         const size_t perSlot = ((size_t)2 * R_NUM_BASE + RT_SHADOW_RECORDS * (1u + c->numLights + maxLV) + V_NUM + (size_t)maxLV * (RT_VCM_LV_RECORDS + 2u) + RT_VCM_LV_RECORDS) * sizeof(float4)
                                + (size_t)(10u + c->numLights + maxLV) * 2u * sizeof(uint32_t);
         while (batch > 1u && perSlot * c->numSlots * batch > ((size_t)48 << 30)) --batch;
@@ -308,8 +321,7 @@ static int vcmRenderPass(RtgpuContext* c, const RtPassParams* p)
 static int lightTracerRenderPass(RtgpuContext* c, const RtPassParams* p)
 {
     RtgpuContext::Vcm& v = c->vcm;
-    if (c->shard.rank != 0 || c->shard.worldSize != 1) return fail(RTGPU_ERR_UNSUPPORTED, "the Light Tracer needs the whole frame on one device (shard {0, 1})");
-    if (!c->activeMask.empty()) return fail(RTGPU_ERR_UNSUPPORTED, "the Light Tracer does not support active-block restriction");
+    if (const int r = refusePartialFrame(c, "the Light Tracer")) return r;
     if (p->maxRayDepth + 2u > RT_VCM_COUNT_PLANE) return fail(RTGPU_ERR_UNSUPPORTED, "Light Tracer: maxRayDepth must be <= 18");
     { int r = flushPending(c); if (r) return r; }
     HIP_TRY(syncLanes(c));

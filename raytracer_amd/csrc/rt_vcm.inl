@@ -9,7 +9,7 @@
 //   for vertex = 1 .. maxPathLength-1:                                         TraceLightPath,         :320-426
 //       trace                    closest hit of the light sub-paths + the camera-connection shadow rays of the previous vertex
 //       vcm_light_shade          splat the previous vertex's connection if visible; store the light vertex and the photon;
-//                                ConnectToCamera (:908-966) up to the shadow ray; AdvancePath (:493-578)
+//                                ConnectToCamera (:908-966, connectToCamera) up to the shadow ray; AdvancePath (:493-578)
 //   trace + vcm_light_finish     the connections of each path's last vertex
 //   for vertex = 1 .. maxPathLength:                                            camera sub-path,        :184-314
 //       trace                    closest hit + the shadow rays queued by the previous vertex
@@ -21,6 +21,11 @@
 // Shadow-ray results arrive one kernel after the terms that need them are computed; the terms are stored per request and
 // folded in afterwards IN THE REFERENCE'S ORDER (lights, then light vertices, then merging), so the camera-path radiance is
 // independent of the schedule (bit-identical to a scalar evaluation of the same pixel).  Film splats are float atomics.
+//
+// What the kernels share exists once: the stored path vertex (storeVertex / fetchVertex / decodeVertex: light vertices and the pending camera
+// vertex, layout in rt_vcm_state.h), connectToCamera (k_vcm_light_shade and the Light Tracer's k_lt_shade), blockReserve and pushShadowRequests
+// (queue space), vcmAdvancePath, vcmResolvePending and vcmEvaluateLight; generator states are packed by packPair / unpackPair (rt_device_state.h)
+// and a photon's cell is hashed by hashCellIndex (rt_vcm_photons.h), the builder's own.
 
 #include "rt_vcm_state.h"
 
@@ -29,13 +34,12 @@ RT_DEV float vcmPdfWtoA(float pdfW, float distance, float cosThere) { return pdf
 RT_DEV void loadSimd(RandomSimd& r, const VcmArena& a, uint32_t slot)
 {
     const float4 s0 = vrec(a, V_SIMD0, slot), s1 = vrec(a, V_SIMD1, slot);
-    r.seed0[0] = (uint64_t)ubits(s0.x) | ((uint64_t)ubits(s0.y) << 32); r.seed0[1] = (uint64_t)ubits(s0.z) | ((uint64_t)ubits(s0.w) << 32);
-    r.seed1[0] = (uint64_t)ubits(s1.x) | ((uint64_t)ubits(s1.y) << 32); r.seed1[1] = (uint64_t)ubits(s1.z) | ((uint64_t)ubits(s1.w) << 32);
+    unpackPair(s0, r.seed0); unpackPair(s1, r.seed1);
 }
 RT_DEV void storeSimd(const RandomSimd& r, const VcmArena& a, uint32_t slot)
 {
-    vrec(a, V_SIMD0, slot) = f4(fbits((uint32_t)r.seed0[0]), fbits((uint32_t)(r.seed0[0] >> 32)), fbits((uint32_t)r.seed0[1]), fbits((uint32_t)(r.seed0[1] >> 32)));
-    vrec(a, V_SIMD1, slot) = f4(fbits((uint32_t)r.seed1[0]), fbits((uint32_t)(r.seed1[0] >> 32)), fbits((uint32_t)r.seed1[1]), fbits((uint32_t)(r.seed1[1] >> 32)));
+    vrec(a, V_SIMD0, slot) = packPair(r.seed0);
+    vrec(a, V_SIMD1, slot) = packPair(r.seed1);
 }
 
 // Queue space for a whole block with ONE global atomic (a returning atomic on one word sustains only ~88 operations per
@@ -50,16 +54,37 @@ RT_DEV uint32_t blockReserve(uint32_t n, uint32_t* __restrict__ globalCount, uin
     return *sBase + local;
 }
 
-// ShadingData of a stored light vertex: fetch and decode are separate so that a loop can fetch the next vertex while it works on this one
-struct LightVertexRecords { float4 r0, r1, r2, r3, r4, r5; };
-RT_DEV LightVertexRecords fetchLightVertex(const VcmArena& a, uint32_t vertex, uint32_t slot)
+// The shadow requests of one vertex (bit r of rayMask: request r needs a ray; at most 64 per vertex, checked by the host) go to the queue as
+// r * capacity + slot, in request order.  Called like blockReserve, which it uses.
+RT_DEV void pushShadowRequests(unsigned long long rayMask, uint32_t capacity, uint32_t slot, uint32_t* __restrict__ shadowQueue, uint32_t* __restrict__ shadowCount,
+                               uint32_t* sCount, uint32_t* sBase)
 {
-    LightVertexRecords v;
-    v.r0 = lvrec(a, vertex, 0, slot); v.r1 = lvrec(a, vertex, 1, slot); v.r2 = lvrec(a, vertex, 2, slot);
-    v.r3 = lvrec(a, vertex, 3, slot); v.r4 = lvrec(a, vertex, 4, slot); v.r5 = lvrec(a, vertex, 5, slot);
+    uint32_t shadowAt = blockReserve((uint32_t)__popcll(rayMask), shadowCount, sCount, sBase);
+    for (; rayMask != 0ull; rayMask &= rayMask - 1ull) shadowQueue[shadowAt++] = (uint32_t)(__ffsll((long long)rayMask) - 1) * capacity + slot;
+}
+
+// A stored path vertex (layout: rt_vcm_state.h).  `base` is the vertex's record 0 -- &lvrec(a, k, 0, slot) for light vertex k, &cvrec(a, 0, slot) for
+// the pending camera vertex -- and `stride` the arena's capacity.  w3 is dVC for a light vertex and dVM for a camera vertex; tag is the path length
+// of a light vertex, 0 for a camera vertex.  Fetch and decode are separate so that a loop can fetch the next vertex while it works on this one.
+struct VertexRecords { float4 r0, r1, r2, r3, r4, r5; };
+RT_DEV void storeVertex(float4* base, uint32_t stride, const ShadingData& sd, uint32_t tag, V4 throughput, float w3, float dVCM)
+{
+    const V4 pos = sd.intersection.frame.r[3], tg = sd.intersection.frame.r[0], nr = sd.intersection.frame.r[2], og = sd.outgoingDirWorldSpace;
+    base[0 * (size_t)stride] = f4(pos.x, pos.y, pos.z, fbits(sd.intersection.material | (tag << 24)));
+    base[1 * (size_t)stride] = f4(tg.x, tg.y, tg.z, sd.mp.roughness);
+    base[2 * (size_t)stride] = f4(nr.x, nr.y, nr.z, sd.mp.metalness);
+    base[3 * (size_t)stride] = f4(og.x, og.y, og.z, w3);
+    base[4 * (size_t)stride] = f4(sd.mp.baseColor.x, sd.mp.baseColor.y, sd.mp.baseColor.z, sd.mp.baseColor.w);
+    base[5 * (size_t)stride] = f4(throughput.x, throughput.y, throughput.z, dVCM);
+}
+RT_DEV VertexRecords fetchVertex(const float4* base, uint32_t stride)
+{
+    VertexRecords v;
+    v.r0 = base[0 * (size_t)stride]; v.r1 = base[1 * (size_t)stride]; v.r2 = base[2 * (size_t)stride];
+    v.r3 = base[3 * (size_t)stride]; v.r4 = base[4 * (size_t)stride]; v.r5 = base[5 * (size_t)stride];
     return v;
 }
-RT_DEV void decodeLightVertex(const RtSceneDesc& scene, const LightVertexRecords& v, ShadingData& sd, V4& throughput, float& dVC, float& dVCM, uint32_t& pathLength)
+RT_DEV void decodeVertex(const RtSceneDesc& scene, const VertexRecords& v, ShadingData& sd, V4& throughput, float& w3, float& dVCM, uint32_t& tag)
 {
     const float4 r0 = v.r0, r1 = v.r1, r2 = v.r2, r3 = v.r3, r4 = v.r4, r5 = v.r5;
     sd.intersection.frame.r[0] = V4(r1.x, r1.y, r1.z, 0.0f);
@@ -68,16 +93,18 @@ RT_DEV void decodeLightVertex(const RtSceneDesc& scene, const LightVertexRecords
     sd.intersection.frame.r[3] = V4(r0.x, r0.y, r0.z, 0.0f);
     sd.intersection.texCoord = zero4();
     sd.intersection.material = ubits(r0.w) & 0x00FFFFFFu;
-    pathLength = ubits(r0.w) >> 24;
+    tag = ubits(r0.w) >> 24;
     sd.outgoingDirWorldSpace = V4(r3.x, r3.y, r3.z, 0.0f);
     sd.mp.baseColor = V4(r4.x, r4.y, r4.z, r4.w); sd.mp.emission = zero4();
     sd.mp.roughness = r1.w; sd.mp.metalness = r2.w; sd.mp.IoR = scene.materials[sd.intersection.material].IoR;
     throughput = V4(r5.x, r5.y, r5.z, 0.0f);
-    dVC = r3.w; dVCM = r5.w;
+    w3 = r3.w; dVCM = r5.w;
 }
-RT_DEV void loadLightVertex(const RtSceneDesc& scene, const VcmArena& a, uint32_t vertex, uint32_t slot, ShadingData& sd, V4& throughput, float& dVC, float& dVCM, uint32_t& pathLength)
+// the pending camera vertex of a slot, for k_vcm_connect and k_vcm_merge
+RT_DEV void loadCameraVertex(const RtSceneDesc& scene, const VcmArena& a, uint32_t slot, ShadingData& sd, V4& throughput, float& dVM, float& dVCM)
 {
-    decodeLightVertex(scene, fetchLightVertex(a, vertex, slot), sd, throughput, dVC, dVCM, pathLength);
+    uint32_t tag;
+    decodeVertex(scene, fetchVertex(&cvrec(a, 0, slot), a.capacity), sd, throughput, dVM, dVCM, tag);
 }
 
 // ---- light stage ---------------------------------------------------------------------------------------------------------
@@ -85,7 +112,7 @@ RT_DEV void loadLightVertex(const RtSceneDesc& scene, const VcmArena& a, uint32_
 // GenerateLightSample, :428-491.  The scalar generator (Random::GetInt) is the pixel's Sampler::fallback stream, which lives in
 // the CAMERA arena's R_RNG record (k_generate has reset it for this pass).
 template <int kClass>
-__global__ void RT_VCM_ATTR(k_vcm_emit) k_vcm_emit(const RtSceneDesc scene, const VcmBatch b, const Paths lp, const Paths cp,
+__global__ void __launch_bounds__(RT_BLOCK) k_vcm_emit(const RtSceneDesc scene, const VcmBatch b, const Paths lp, const Paths cp,
                                                        const VcmArena a, const uint32_t* __restrict__ slotPixel, uint32_t numSlots,
                                                        uint32_t* __restrict__ queue, uint32_t* __restrict__ queueCount)
 {
@@ -110,11 +137,10 @@ __global__ void RT_VCM_ATTR(k_vcm_emit) k_vcm_emit(const RtSceneDesc scene, cons
             if (scene.numLights != 0u)
             {
                 const float4 rng = prec(cp, R_RNG, slot);
-                Xoroshiro fb;
-                fb.s[0] = (uint64_t)ubits(rng.x) | ((uint64_t)ubits(rng.y) << 32); fb.s[1] = (uint64_t)ubits(rng.z) | ((uint64_t)ubits(rng.w) << 32);
+                Xoroshiro fb; unpackPair(rng, fb.s);
                 const float lightPickProbability = 1.0f / (float)scene.numLights;
                 const uint32_t lightIndex = (uint32_t)xoroshiroNext(fb) % scene.numLights;
-                prec(cp, R_RNG, slot) = f4(fbits((uint32_t)fb.s[0]), fbits((uint32_t)(fb.s[0] >> 32)), fbits((uint32_t)fb.s[1]), fbits((uint32_t)(fb.s[1] >> 32)));
+                prec(cp, R_RNG, slot) = packPair(fb.s);
                 const RtLight& light = scene.lights[lightIndex];
                 const V4 ps = simd.getVector4(); const V4 ds = simd.getVector4();
                 const float up[3] = { ps.x, ps.y, ps.z }, ud[2] = { ds.x, ds.y };
@@ -203,9 +229,59 @@ RT_DEV bool vcmAdvancePath(const RtSceneDesc& scene, const VcmDev& vcm, const Pa
     return true;
 }
 
+// The camera connection of a light-path vertex, up to its shadow ray: ConnectToCamera, VertexConnectionAndMerging.cpp:908-966 (kMis), and the same
+// step of LightTracer::RenderPixel, LightTracer.cpp:117-150 (!kMis: no MIS weight, no cosine test, and the shadow ray starts 1e-4 along the normal, :138).
+// Stores the request (resolveSplat reads it back once the ray is traced); true: the request needs its ray.  The film projection, which needs the
+// position alone, stands in front of the BSDF evaluation on purpose (the reference projects behind it, and only where the BSDF is not black):
+// behind it, k_lt_shade<3> needs 130 VGPRs and loses its fourth wave per SIMD.
+template <bool kMis>
+RT_DEV bool connectToCamera(const DevPass& pass, const VcmDev& vcm, const Paths& lp, uint32_t slot, const RtMaterial& mat, const ShadingData& sd, RandomSimd& simd,
+                            V4 throughput, float dVC, float dVCM)
+{
+    const RtCamera& cam = pass.camera;
+    const V4 pos = sd.intersection.frame.r[3], nr = sd.intersection.frame.r[2];
+    V4 dirToCamera = load4(cam.localToWorld + 12) - pos;
+    const float cameraDistanceSqr = sqrLength3(dirToCamera);
+    const float cameraDistance = sqrtf(cameraDistanceSqr);
+    dirToCamera = dirToCamera / cameraDistance;
+    V4 filmPos;
+    const bool onFilm = cameraWorldToFilm(cam, pos, filmPos);
+    float bsdfPdfW = 0.0f, bsdfRevPdfW = 0.0f;
+    const V4 cameraFactor = materialEvaluate<false>(mat, sd, neg(dirToCamera), bsdfPdfW, kMis ? &bsdfRevPdfW : nullptr);
+    float tmax = -1.0f; V4 contribution = zero4(); uint32_t target = 0xFFFFFFFFu;
+    if (onFilm && !almostZero4(cameraFactor))
+    {
+        // the jitter is drawn when the connection is set up (the reference draws it inside Film::AccumulateColor, i.e. only for visible connections;
+        // its stream is per-thread and entropy-seeded, so the position carries no meaning)
+        const V4 jitter = simd.getVector4();
+        tmax = cameraDistance * 0.999f;
+        const float cosToCamera = dot3(dirToCamera, nr);
+        if (!kMis || cosToCamera > FLT_EPSILON)
+        {
+            const float cameraPdfW = cameraDirectionPdfW(cam, neg(dirToCamera));
+            if (kMis)
+            {
+                const float cameraPdfA = cameraPdfW * cosToCamera / cameraDistanceSqr;
+                const float wLight = cameraPdfA * (vcm.misVertexMergingWeightFactorVC + dVCM + dVC * bsdfRevPdfW);
+                const float misWeight = 1.0f / (wLight + 1.0f);
+                contribution = (cameraFactor * throughput) * (misWeight * cameraPdfA / (cosToCamera));
+                contribution = contribution * load4(vcm.cameraConnectingWeight);
+            }
+            else contribution = (cameraFactor * throughput) * (cameraPdfW / cameraDistanceSqr);
+            uint32_t fx, fy;
+            if (filmSplatPixel(filmPos, pass.width, pass.height, jitter, fx, fy)) target = fy * pass.width + fx;
+        }
+    }
+    const V4 shadowOrigin = kMis ? pos : pos + nr * 0.0001f;
+    pshadow(lp, 0, 0, slot) = f4(dirToCamera.x, dirToCamera.y, dirToCamera.z, tmax);
+    pshadow(lp, 0, 1, slot) = f4(contribution.x, contribution.y, contribution.z, fbits(target));
+    prec(lp, R_SH_P, slot) = f4(shadowOrigin.x, shadowOrigin.y, shadowOrigin.z, 0.0f);
+    return tmax >= 0.0f;
+}
+
 // One vertex of TraceLightPath's loop, :334-425
 template <int kClass>
-__global__ void RT_VCM_ATTR(k_vcm_light_shade) k_vcm_light_shade(const RtSceneDesc scene, const VcmBatch b, const Paths lp, const VcmArena a,
+__global__ void __launch_bounds__(RT_BLOCK) k_vcm_light_shade(const RtSceneDesc scene, const VcmBatch b, const Paths lp, const VcmArena a,
                                                               const uint32_t* __restrict__ queueIn, const uint32_t* __restrict__ countIn,
                                                               uint32_t* __restrict__ queueOut, uint32_t* __restrict__ countOut,
                                                               uint32_t* __restrict__ shadowQueue, uint32_t* __restrict__ shadowCount,
@@ -260,47 +336,10 @@ __global__ void RT_VCM_ATTR(k_vcm_light_shade) k_vcm_light_shade(const RtSceneDe
                     {
                         const uint32_t k = a.lvCount[slot];
                         a.lvCount[slot] = k + 1u;
-                        const V4 pos = sd.intersection.frame.r[3], tg = sd.intersection.frame.r[0], nr = sd.intersection.frame.r[2], og = sd.outgoingDirWorldSpace;
-                        lvrec(a, k, 0, slot) = f4(pos.x, pos.y, pos.z, fbits(sd.intersection.material | (length << 24)));
-                        lvrec(a, k, 1, slot) = f4(tg.x, tg.y, tg.z, sd.mp.roughness);
-                        lvrec(a, k, 2, slot) = f4(nr.x, nr.y, nr.z, sd.mp.metalness);
-                        lvrec(a, k, 3, slot) = f4(og.x, og.y, og.z, dVC);
-                        lvrec(a, k, 4, slot) = f4(sd.mp.baseColor.x, sd.mp.baseColor.y, sd.mp.baseColor.z, sd.mp.baseColor.w);
-                        lvrec(a, k, 5, slot) = f4(throughput.x, throughput.y, throughput.z, dVCM);
+                        storeVertex(&lvrec(a, k, 0, slot), a.capacity, sd, length, throughput, dVC, dVCM);
 
-                        // ConnectToCamera, :908-966
-                        const RtCamera& cam = pass.camera;
-                        V4 dirToCamera = load4(cam.localToWorld + 12) - pos;
-                        const float cameraDistanceSqr = sqrLength3(dirToCamera);
-                        const float cameraDistance = sqrtf(cameraDistanceSqr);
-                        dirToCamera = dirToCamera / cameraDistance;
-                        float bsdfPdfW = 0.0f, bsdfRevPdfW = 0.0f;
-                        const V4 cameraFactor = materialEvaluate<false>(mat, sd, neg(dirToCamera), bsdfPdfW, &bsdfRevPdfW);
-                        float tmax = -1.0f; V4 contribution = zero4(); uint32_t target = 0xFFFFFFFFu;
-                        V4 filmPos;
-                        if (!almostZero4(cameraFactor) && cameraWorldToFilm(cam, pos, filmPos))
-                        {
-                            const V4 jitter = simd.getVector4();   // drawn when the connection is set up (the reference draws it inside Film::AccumulateColor,
-                                                                    // i.e. only for visible connections; its stream is per-thread and entropy-seeded, so the position carries no meaning)
-                            tmax = cameraDistance * 0.999f;
-                            const float cosToCamera = dot3(dirToCamera, nr);
-                            if (cosToCamera > FLT_EPSILON)
-                            {
-                                const float cameraPdfW = cameraDirectionPdfW(cam, neg(dirToCamera));
-                                const float cameraPdfA = cameraPdfW * cosToCamera / cameraDistanceSqr;
-                                const float wLight = cameraPdfA * (vcm.misVertexMergingWeightFactorVC + dVCM + dVC * bsdfRevPdfW);
-                                const float misWeight = 1.0f / (wLight + 1.0f);
-                                contribution = (cameraFactor * throughput) * (misWeight * cameraPdfA / (cosToCamera));
-                                contribution = contribution * load4(vcm.cameraConnectingWeight);
-                                uint32_t fx, fy;
-                                if (filmSplatPixel(filmPos, pass.width, pass.height, jitter, fx, fy)) target = fy * pass.width + fx;
-                            }
-                        }
-                        pshadow(lp, 0, 0, slot) = f4(dirToCamera.x, dirToCamera.y, dirToCamera.z, tmax);
-                        pshadow(lp, 0, 1, slot) = f4(contribution.x, contribution.y, contribution.z, fbits(target));
-                        prec(lp, R_SH_P, slot) = f4(pos.x, pos.y, pos.z, 0.0f);
+                        needRay = connectToCamera<true>(pass, vcm, lp, slot, mat, sd, simd, throughput, dVC, dVCM);
                         pending = 1u;
-                        needRay = tmax >= 0.0f;
                     }
                     if (vcm.useVertexMerging)
                     {
@@ -331,10 +370,10 @@ __global__ void RT_VCM_ATTR(k_vcm_light_shade) k_vcm_light_shade(const RtSceneDe
 }
 
 // One vertex of LightTracer::RenderPixel's loop (Core/Rendering/LightTracer.cpp:69-181; renderer "Light Tracer"): like k_vcm_light_shade
-// without MIS quantities, light vertices and photons; every vertex below maxRayDepth is connected to the camera with
-// contribution = bsdf * throughput * PdfW / distance^2, and the shadow ray starts at samplePos + normal * 1e-4 (:138).
+// without MIS quantities, light vertices and photons; every vertex below maxRayDepth is connected to the camera (connectToCamera<false>:
+// contribution = bsdf * throughput * PdfW / distance^2, and the shadow ray starts at samplePos + normal * 1e-4, :138).
 template <int kClass>
-__global__ void RT_VCM_ATTR(k_lt_shade) k_lt_shade(const RtSceneDesc scene, const VcmBatch b, const Paths lp, const VcmArena a,
+__global__ void __launch_bounds__(RT_BLOCK) k_lt_shade(const RtSceneDesc scene, const VcmBatch b, const Paths lp, const VcmArena a,
                                                        const uint32_t* __restrict__ queueIn, const uint32_t* __restrict__ countIn,
                                                        uint32_t* __restrict__ queueOut, uint32_t* __restrict__ countOut,
                                                        uint32_t* __restrict__ shadowQueue, uint32_t* __restrict__ shadowCount,
@@ -379,33 +418,8 @@ __global__ void RT_VCM_ATTR(k_lt_shade) k_lt_shade(const RtSceneDesc scene, cons
                 {
                     const RtMaterial& mat = scene.materials[sd.intersection.material];
                     RandomSimd simd; loadSimd(simd, a, slot);
-                    {
-                        const RtCamera& cam = pass.camera;
-                        const V4 samplePos = sd.intersection.frame.r[3];
-                        V4 dirToCamera = load4(cam.localToWorld + 12) - samplePos;
-                        const float cameraDistanceSqr = sqrLength3(dirToCamera);
-                        const float cameraDistance = sqrtf(cameraDistanceSqr);
-                        dirToCamera = dirToCamera / cameraDistance;
-                        float bsdfPdfW = 0.0f;
-                        const V4 cameraFactor = materialEvaluate<false>(mat, sd, neg(dirToCamera), bsdfPdfW);
-                        float tmax = -1.0f; V4 contribution = zero4(); uint32_t target = 0xFFFFFFFFu;
-                        V4 filmPos;
-                        if (!almostZero4(cameraFactor) && cameraWorldToFilm(cam, samplePos, filmPos))
-                        {
-                            const V4 jitter = simd.getVector4();
-                            tmax = cameraDistance * 0.999f;
-                            const float cameraPdfA = cameraDirectionPdfW(cam, neg(dirToCamera)) / cameraDistanceSqr;
-                            contribution = (cameraFactor * throughput) * cameraPdfA;
-                            uint32_t fx, fy;
-                            if (filmSplatPixel(filmPos, pass.width, pass.height, jitter, fx, fy)) target = fy * pass.width + fx;
-                        }
-                        const V4 shadowOrigin = samplePos + sd.intersection.frame.r[2] * 0.0001f;
-                        pshadow(lp, 0, 0, slot) = f4(dirToCamera.x, dirToCamera.y, dirToCamera.z, tmax);
-                        pshadow(lp, 0, 1, slot) = f4(contribution.x, contribution.y, contribution.z, fbits(target));
-                        prec(lp, R_SH_P, slot) = f4(shadowOrigin.x, shadowOrigin.y, shadowOrigin.z, 0.0f);
-                        pending = 1u;
-                        needRay = tmax >= 0.0f;
-                    }
+                    needRay = connectToCamera<false>(pass, b.vcms[0], lp, slot, mat, sd, simd, throughput, 0.0f, 0.0f);
+                    pending = 1u;
                     const V4 sv = simd.getVector4();
                     const float sample[3] = { sv.x, sv.y, sv.z };
                     V4 incomingDirWorldSpace = zero4(); float pdf = 0.0f; uint32_t event = EV_NULL;
@@ -540,7 +554,7 @@ RT_DEV V4 vcmEvaluateLight(const RtSceneDesc& scene, const VcmDev& vcm, const Rt
 
 // One vertex of RenderPixel's loop, :201-314
 template <int kClass>
-__global__ void RT_VCM_ATTR(k_vcm_camera_shade) k_vcm_camera_shade(const RtSceneDesc scene, const VcmBatch b, const Paths cp, const VcmArena a,
+__global__ void __launch_bounds__(RT_BLOCK) k_vcm_camera_shade(const RtSceneDesc scene, const VcmBatch b, const Paths cp, const VcmArena a,
                                                                const uint32_t* __restrict__ queueIn, const uint32_t* __restrict__ countIn,
                                                                uint32_t* __restrict__ queueOut, uint32_t* __restrict__ countOut,
                                                                uint32_t* __restrict__ shadowQueue, uint32_t* __restrict__ shadowCount,
@@ -674,16 +688,7 @@ __global__ void RT_VCM_ATTR(k_vcm_camera_shade) k_vcm_camera_shade(const RtScene
                 // MergeVertices, :823-906: the range query runs in k_vcm_merge (wave-cooperative for long photon lists); this
                 // vertex is handed over as a record.  With no photons HashGrid::Process returns at once and the term is +0.
                 const bool mergeHere = !isDeltaBsdf && vcm.useVertexMerging && vcm.iteration > 0u && gridPhotons != 0u;
-                if (mergeHere || wantConnect)
-                {
-                    const V4 tg = sd.intersection.frame.r[0], nr = sd.intersection.frame.r[2], og = sd.outgoingDirWorldSpace;
-                    cvrec(a, 0, slot) = f4(pos.x, pos.y, pos.z, fbits(sd.intersection.material));
-                    cvrec(a, 1, slot) = f4(tg.x, tg.y, tg.z, sd.mp.roughness);
-                    cvrec(a, 2, slot) = f4(nr.x, nr.y, nr.z, sd.mp.metalness);
-                    cvrec(a, 3, slot) = f4(og.x, og.y, og.z, dVM);
-                    cvrec(a, 4, slot) = f4(sd.mp.baseColor.x, sd.mp.baseColor.y, sd.mp.baseColor.z, sd.mp.baseColor.w);
-                    cvrec(a, 5, slot) = f4(throughput.x, throughput.y, throughput.z, dVCM);
-                }
+                if (mergeHere || wantConnect) storeVertex(&cvrec(a, 0, slot), a.capacity, sd, 0u, throughput, dVM, dVCM);
                 if (mergeHere) { wantMerge = true; pendingBits |= 0x10000u; }
                 pendingBits |= numLightRequests;
                 if (pendingBits != 0u || wantConnect)
@@ -704,9 +709,7 @@ __global__ void RT_VCM_ATTR(k_vcm_camera_shade) k_vcm_camera_shade(const RtScene
             prec(cp, R_RESULT, slot) = f4(resultColor.x, resultColor.y, resultColor.z, rResult.w);
         }
         // the shadow requests of this vertex, then the surviving path
-        uint32_t shadowAt = blockReserve((uint32_t)__popcll(rayMask), shadowCount, &sCount, &sBase);
-        for (unsigned long long pendingMask = rayMask; pendingMask != 0ull; pendingMask &= pendingMask - 1ull)
-            shadowQueue[shadowAt++] = (uint32_t)(__ffsll((long long)pendingMask) - 1) * cp.capacity + slot;
+        pushShadowRequests(rayMask, cp.capacity, slot, shadowQueue, shadowCount, &sCount, &sBase);
         const uint32_t pathAt = blockReserve(alive ? 1u : 0u, countOut, &sCount, &sBase);
         if (alive) queueOut[pathAt] = slot;
         const uint32_t mergeAt = blockReserve(wantMerge ? 1u : 0u, mergeCount, &sCount, &sBase);
@@ -775,26 +778,11 @@ RT_DEV bool mergePhoton(const RtSceneDesc& scene, const VcmDev& vcm, const HashG
 }
 RT_DEV float laneValue(float v, int lane) { return __uint_as_float((uint32_t)__builtin_amdgcn_readlane((int)__float_as_uint(v), lane)); }   // lane: wave-uniform
 RT_DEV V4 shfl3(V4 v, int lane) { return V4(__shfl(v.x, lane), __shfl(v.y, lane), __shfl(v.z, lane), 0.0f); }
-RT_DEV void loadCameraVertex(const RtSceneDesc& scene, const VcmArena& a, uint32_t slot, ShadingData& sd, V4& throughput, float& dVM, float& dVCM)
-{
-    const float4 r0 = cvrec(a, 0, slot), r1 = cvrec(a, 1, slot), r2 = cvrec(a, 2, slot), r3 = cvrec(a, 3, slot), r4 = cvrec(a, 4, slot), r5 = cvrec(a, 5, slot);
-    sd.intersection.frame.r[0] = V4(r1.x, r1.y, r1.z, 0.0f);
-    sd.intersection.frame.r[2] = V4(r2.x, r2.y, r2.z, 0.0f);
-    sd.intersection.frame.r[1] = cross3(sd.intersection.frame.r[0], sd.intersection.frame.r[2]);
-    sd.intersection.frame.r[3] = V4(r0.x, r0.y, r0.z, 0.0f);
-    sd.intersection.texCoord = zero4();
-    sd.intersection.material = ubits(r0.w);
-    sd.outgoingDirWorldSpace = V4(r3.x, r3.y, r3.z, 0.0f);
-    sd.mp.baseColor = V4(r4.x, r4.y, r4.z, r4.w); sd.mp.emission = zero4();
-    sd.mp.roughness = r1.w; sd.mp.metalness = r2.w; sd.mp.IoR = scene.materials[sd.intersection.material].IoR;
-    throughput = V4(r5.x, r5.y, r5.z, 0.0f);
-    dVM = r3.w; dVCM = r5.w;
-}
 // ConnectVertices, :746-821, for the camera vertices k_vcm_camera_shade queued: every light vertex of the pixel's light path is one
 // request (direction | tmax, contribution | vertex) after the vertex's next-event requests; the visibility rays ride in the next k_trace
 // launch and vcmResolvePending folds the visible ones in.  Reads the 96-byte vertex record the merge kernel uses, plus dVC and the path
 // length from the spare lanes of R_SH_P / R_SH_TP.
-__global__ void RT_VCM_CONNECT_ATTR k_vcm_connect(const RtSceneDesc scene, const VcmBatch b, const Paths cp, const VcmArena a,
+__global__ void __launch_bounds__(RT_BLOCK) k_vcm_connect(const RtSceneDesc scene, const VcmBatch b, const Paths cp, const VcmArena a,
                                                           const uint32_t* __restrict__ queue, const uint32_t* __restrict__ queueCount,
                                                           uint32_t* __restrict__ shadowQueue, uint32_t* __restrict__ shadowCount)
 {
@@ -822,13 +810,13 @@ __global__ void RT_VCM_CONNECT_ATTR k_vcm_connect(const RtSceneDesc scene, const
             const V4 pos = sd.intersection.frame.r[3];
             uint32_t numConnections = 0u;
             const uint32_t numLightVertices = a.lvCount[slot];
-            LightVertexRecords next = fetchLightVertex(a, 0u, slot);   // (numLightVertices >= 1 for a queued vertex)
+            VertexRecords next = fetchVertex(&lvrec(a, 0u, 0, slot), a.capacity);   // (numLightVertices >= 1 for a queued vertex)
             for (uint32_t v = 0; v < numLightVertices; ++v)
             {
                 ShadingData lsd; V4 lvThroughput; float lvVC, lvVCM; uint32_t lvLength;
-                const LightVertexRecords cur = next;
-                next = fetchLightVertex(a, v + 1u < numLightVertices ? v + 1u : v, slot);   // in flight during this vertex's two BSDF evaluations
-                decodeLightVertex(scene, cur, lsd, lvThroughput, lvVC, lvVCM, lvLength);
+                const VertexRecords cur = next;
+                next = fetchVertex(&lvrec(a, v + 1u < numLightVertices ? v + 1u : v, 0, slot), a.capacity);   // in flight during this vertex's two BSDF evaluations
+                decodeVertex(scene, cur, lsd, lvThroughput, lvVC, lvVCM, lvLength);
                 if (lvLength + length + 1u > vcm.maxPathLength) break;
                 V4 lightDir = lsd.intersection.frame.r[3] - pos;
                 const float distanceSqr = sqrLength3(lightDir);
@@ -870,9 +858,7 @@ __global__ void RT_VCM_CONNECT_ATTR k_vcm_connect(const RtSceneDesc scene, const
             pendingBits |= (numConnections << 8) | 0x2000000u;
             prec(cp, R_SAMPLER, slot).w = fbits(pendingBits);
         }
-        uint32_t shadowAt = blockReserve((uint32_t)__popcll(rayMask), shadowCount, &sCount, &sBase);
-        for (unsigned long long pendingMask = rayMask; pendingMask != 0ull; pendingMask &= pendingMask - 1ull)
-            shadowQueue[shadowAt++] = (uint32_t)(__ffsll((long long)pendingMask) - 1) * cp.capacity + slot;
+        pushShadowRequests(rayMask, cp.capacity, slot, shadowQueue, shadowCount, &sCount, &sBase);
     }
 }
 

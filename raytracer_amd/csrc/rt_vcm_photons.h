@@ -28,6 +28,10 @@ struct VcmPhotonGrid
     size_t photonCapacity = 0, pixelCapacity = 0, cellCapacity = 0;
 };
 
+// the cell of a photon, for the builder (k_photon_cells) and the range query (mergeCellRanges, rt_vcm.inl) alike
+__device__ __forceinline__ int32_t cvtT(float f) { return (f >= 2147483648.0f || f < -2147483648.0f || f != f) ? (int32_t)0x80000000 : (int32_t)f; }   // _mm_cvttps_epi32
+__device__ __forceinline__ uint32_t hashCellIndex(uint32_t x, uint32_t y, uint32_t z, uint32_t mask) { return ((x * 73856093u) ^ (y * 19349663u) ^ (z * 83492791u)) & mask; }   // HashGrid.h:148-152
+
 // HashGrid::Build over the photons of `in` (radius = mMergingRadiusVM).  Synchronises the stream once (the photon count sizes
 // the table).  Returns a hipError_t as int.
 int vcmBuildPhotonGrid(const VcmPhotonInput& in, float radius, hipStream_t stream, VcmPhotonGrid& grid);

@@ -51,8 +51,6 @@ __global__ void __launch_bounds__(VP_BLOCK) k_photon_compact(VcmPhotonInput in, 
     if (threadIdx.x < 3 && sMin[threadIdx.x] != FLT_MAX) atomicMinFloat(&boxMin[threadIdx.x], sMin[threadIdx.x]);
 }
 
-__device__ __forceinline__ int32_t cvtT(float f) { return (f >= 2147483648.0f || f < -2147483648.0f || f != f) ? (int32_t)0x80000000 : (int32_t)f; }
-
 __global__ void __launch_bounds__(VP_BLOCK) k_photon_cells(const float4* __restrict__ photons, uint32_t numPhotons, const float* __restrict__ boxMin, float invCellSize,
                                                            uint32_t mask, uint32_t* __restrict__ keys, uint32_t* __restrict__ values, uint32_t* __restrict__ cellCounts)
 {
@@ -60,7 +58,7 @@ __global__ void __launch_bounds__(VP_BLOCK) k_photon_cells(const float4* __restr
     if (i >= numPhotons) return;
     const float4 p = photons[2 * (size_t)i];
     const float cx = invCellSize * (p.x - boxMin[0]), cy = invCellSize * (p.y - boxMin[1]), cz = invCellSize * (p.z - boxMin[2]);
-    const uint32_t cell = (((uint32_t)cvtT(cx) * 73856093u) ^ ((uint32_t)cvtT(cy) * 19349663u) ^ ((uint32_t)cvtT(cz) * 83492791u)) & mask;
+    const uint32_t cell = hashCellIndex((uint32_t)cvtT(cx), (uint32_t)cvtT(cy), (uint32_t)cvtT(cz), mask);   // HashGrid.h:160-167
     keys[i] = cell; values[i] = i;
     atomicAdd(&cellCounts[cell], 1u);
 }

@@ -13,16 +13,23 @@ enum VcmRecord : uint32_t
     V_MERGE,    // camera stage: throughput * vertexMergingColor (rgb) of the vertex whose terms are pending | 1 = present
     V_NUM
 };
-#define RT_VCM_LV_RECORDS 6u   // light vertex: {pos | material, pathLength << 24}, {tangent | roughness}, {normal | metalness},
-                               //               {outgoing dir | dVC}, {baseColor}, {throughput | dVCM}
+// A stored path vertex is six records, `capacity` apart, for both of its uses (storeVertex / fetchVertex / decodeVertex, rt_vcm.inl):
+//   0  position         | material (bits 0-23), tag << 24: the path length of a light vertex, 0 for a camera vertex
+//   1  tangent          | roughness
+//   2  normal           | metalness
+//   3  outgoing dir     | dVC of a light vertex, dVM of a camera vertex
+//   4  baseColor (four lanes)
+//   5  throughput       | dVCM
+// lvrec: vertex k of the slot's light sub-path; cvrec: the camera vertex whose connections and merge query are pending.
+#define RT_VCM_LV_RECORDS 6u
 struct VcmArena
 {
     float4* recs;            // V_NUM x capacity
-    float4* lightVertices;   // maxLV x RT_VCM_LV_RECORDS x capacity
+    float4* lightVertices;   // maxLV x RT_VCM_LV_RECORDS x capacity (vertex records, above)
     float4* photonRaw;       // maxLV x 2 x capacity (this pass's photons, per slot)
     uint32_t* lvCount;       // light vertices of the slot's light sub-path
     uint32_t* photonCount;
-    float4* cameraVertex;    // RT_VCM_LV_RECORDS x capacity: the camera vertex whose merge query is pending (w of record 3 = dVM)
+    float4* cameraVertex;    // RT_VCM_LV_RECORDS x capacity (one vertex record)
     uint32_t capacity, maxLV;
 };
 RT_DEV float4& vrec(const VcmArena& a, uint32_t record, uint32_t slot) { return a.recs[(size_t)record * a.capacity + slot]; }
