@@ -11,9 +11,10 @@ static const size_t kAovRingRecord = sizeof(DevPass) + (size_t)RTGPU_MAX_DIMENSI
 static int ensureAovArena(RtgpuContext* c, uint32_t pixels, bool cost, size_t stagedWordsPerPixel)
 {
     RtgpuContext::Aov& a = c->aov;
+    WalkArena& w = a.arena;
     if (!a.done) HIP_TRY(hipEventCreateWithFlags(&a.done, hipEventDisableTiming));
-    if (!a.counts) HIP_TRY(hipMalloc((void**)&a.counts, QC_WORDS * sizeof(uint32_t)));
-    if (!a.counters) { HIP_TRY(hipMalloc((void**)&a.counters, 16 * sizeof(unsigned long long))); HIP_TRY(hipMemset(a.counters, 0, 16 * sizeof(unsigned long long))); }
+    if (!w.counts) HIP_TRY(hipMalloc((void**)&w.counts, QC_WORDS * sizeof(uint32_t)));
+    if (!w.counters) { HIP_TRY(hipMalloc((void**)&w.counters, 16 * sizeof(unsigned long long))); HIP_TRY(hipMemset(w.counters, 0, 16 * sizeof(unsigned long long))); }
     if (!a.passDev) HIP_TRY(hipMalloc((void**)&a.passDev, sizeof(DevPass)));
     if (!a.seedDev) HIP_TRY(hipMalloc((void**)&a.seedDev, (size_t)RTGPU_MAX_DIMENSIONS * sizeof(uint32_t)));
     if (!a.ringHost)
@@ -21,22 +22,15 @@ static int ensureAovArena(RtgpuContext* c, uint32_t pixels, bool cost, size_t st
         HIP_TRY(hipHostMalloc((void**)&a.ringHost, RtgpuContext::Aov::kRing * kAovRingRecord, hipHostMallocDefault));
         for (uint32_t i = 0; i < RtgpuContext::Aov::kRing; ++i) HIP_TRY(hipEventCreateWithFlags(&a.ringCopied[i], hipEventDisableTiming));
     }
-    if (!a.paths.base || a.paths.capacity < pixels)
+    if (!w.paths.base || w.paths.capacity < pixels)
     {
-        // grown in powers of two from 64 K pixels up to the chunk, as the query arena is
-        uint32_t cap = 65536u;
-        while (cap < pixels) cap <<= 1;
         freeAovArena(c);   // (waits for the calls still using it)
         devFree(a.staged); a.stagedWords = 0;
-        HIP_TRY(hipMalloc((void**)&a.paths.base, ((size_t)R_NUM_BASE + RT_SHADOW_RECORDS) * cap * sizeof(float4)));
-        HIP_TRY(hipMalloc((void**)&a.queue, (size_t)cap * sizeof(uint32_t)));
-        HIP_TRY(hipMalloc((void**)&a.exactQueue, (size_t)cap * sizeof(uint32_t)));
-        HIP_TRY(hipMalloc((void**)&a.exactShadowQueue, (size_t)cap * sizeof(uint32_t)));
-        HIP_TRY(hipMalloc((void**)&a.slotPixel, (size_t)cap * sizeof(uint32_t)));
-        a.paths.capacity = cap; a.paths.maxLights = 1;
+        { const int r = growWalkArena(w, pixels); if (r) return r; }   // (`pixels` is a chunk at most)
+        HIP_TRY(hipMalloc((void**)&a.slotPixel, (size_t)w.paths.capacity * sizeof(uint32_t)));
     }
-    if (cost && !a.rayCounts) HIP_TRY(hipMalloc((void**)&a.rayCounts, (size_t)a.paths.capacity * sizeof(uint4)));
-    const size_t stagedWords = stagedWordsPerPixel * a.paths.capacity;
+    if (cost && !a.rayCounts) HIP_TRY(hipMalloc((void**)&a.rayCounts, (size_t)w.paths.capacity * sizeof(uint4)));
+    const size_t stagedWords = stagedWordsPerPixel * w.paths.capacity;
     if (a.stagedWords < stagedWords)
     {
         if (a.done) HIP_TRY(hipEventSynchronize(a.done));
@@ -51,17 +45,18 @@ static int ensureAovArena(RtgpuContext* c, uint32_t pixels, bool cost, size_t st
 static int launchAovChunk(RtgpuContext* c, hipStream_t stream, unsigned long long firstPixel, uint32_t n, uint32_t mask, const AovOutputs& out, size_t channelStride, size_t firstOut)
 {
     RtgpuContext::Aov& a = c->aov;
+    const WalkArena& w = a.arena;
     const bool cost = (mask & RT_AOV_COST_PLANES) != 0u;
     const dim3 block(RT_BLOCK), grid((n + RT_BLOCK - 1u) / RT_BLOCK);
-    HIP_TRY(hipMemsetAsync(a.counts, 0, QC_WORDS * sizeof(uint32_t), stream));
+    HIP_TRY(hipMemsetAsync(w.counts, 0, QC_WORDS * sizeof(uint32_t), stream));
     hipLaunchKernelGGL(k_aov_pixels, grid, block, 0, stream, a.slotPixel, n, firstPixel, c->width);
     // one pass, so a pass holds all `n` slots: slot / slotsPerPass = 0 for every slot
-    hipLaunchKernelGGL(k_generate, grid, block, 0, stream, c->sceneDev, a.passDev, n, a.paths, a.slotPixel, n, a.queue, a.counts + QC_QUEUE, a.counters);
+    hipLaunchKernelGGL(k_generate, grid, block, 0, stream, c->sceneDev, a.passDev, n, w.paths, a.slotPixel, n, w.queue, w.counts + QC_QUEUE, w.counters);
     // a cost plane takes the counting binary walk; otherwise the walk the context renders with, as the ray queries take it (launchArenaWalk, rt_runtime_query.inl)
-    launchArenaWalk(c, stream, a.counters, a.paths, a.queue, a.counts + QC_QUEUE, nullptr, nullptr, a.counts, a.exactQueue, a.exactShadowQueue, useWide(c) && !cost, cost ? a.rayCounts : nullptr);
+    launchArenaWalk(c, stream, w, true, useWide(c) && !cost, cost ? a.rayCounts : nullptr);
     const uint4* rayCounts = cost ? a.rayCounts : nullptr;
-    if (c->leanScene == 1 || c->leanScene == 3) hipLaunchKernelGGL((k_aov_resolve<3>), grid, block, 0, stream, c->sceneDev, a.paths, n, mask, out, channelStride, firstOut, rayCounts);
-    else hipLaunchKernelGGL((k_aov_resolve<0>), grid, block, 0, stream, c->sceneDev, a.paths, n, mask, out, channelStride, firstOut, rayCounts);
+    if (c->leanScene == 1 || c->leanScene == 3) hipLaunchKernelGGL((k_aov_resolve<3>), grid, block, 0, stream, c->sceneDev, w.paths, n, mask, out, channelStride, firstOut, rayCounts);
+    else hipLaunchKernelGGL((k_aov_resolve<0>), grid, block, 0, stream, c->sceneDev, w.paths, n, mask, out, channelStride, firstOut, rayCounts);
     HIP_TRY(hipGetLastError());
     return RTGPU_OK;
 }
@@ -129,7 +124,7 @@ RTGPU_API int rtgpu_render_aovs(RtgpuContext* c, const RtPassParams* p, const ui
     uint32_t chunk = 0u;
     r = beginAovs(c, p, stream, mask, channels, chunk); if (r) return r;
     RtgpuContext::Aov& a = c->aov;
-    const size_t pixels = (size_t)c->width * c->height, capacity = a.paths.capacity;
+    const size_t pixels = (size_t)c->width * c->height, capacity = a.arena.paths.capacity;
     AovOutputs out;
     for (uint32_t id = 0; id < RT_AOV_NUM_PLANES; ++id) out.plane[id] = nullptr;
     for (uint32_t k = 0; k < numPlanes; ++k) out.plane[planes[k]] = a.staged + (size_t)firstChannel[k] * capacity;

@@ -89,23 +89,67 @@ struct BatchLane
     Paths paths2 = { nullptr, 0, 0 };
     float4* home = nullptr; size_t homeCapacity = 0;
     uint32_t* denseCounts = nullptr;
-    // per-batch work counters, 8 planes of (maxDepth + 2) uint32, zeroed once per batch (one word of each plane per bounce, so that no
+    // per-batch work counters, RT_LANE_COUNT_PLANES planes of (maxDepth + 2) uint32, zeroed once per batch (one word of each plane per bounce, so that no
     // reset ever races with a reader); LaneCounts names the planes
     uint32_t* queueCounts = nullptr;
     uint32_t queueCountCapacity = 0;
     hipEvent_t accumulated = nullptr;   // recorded after the lane's k_accumulate
 };
 
+// One trace step of a launch sequence, carried out by launchTraceStep (rt_runtime_render.inl); LaneCounts fills the first two groups for a bounce of a lane
+struct TraceStep
+{
+    // the work: closest-hit rays and any-hit requests (either queue may be null) over `paths`, taken through `cursor`
+    hipStream_t stream; unsigned long long* counters; Paths paths;
+    const uint32_t* queue = nullptr; const uint32_t* queueCount = nullptr; const uint32_t* shadowQueue = nullptr; const uint32_t* shadowCount = nullptr; uint32_t* cursor = nullptr;
+    // the hand-over of the 4-wide walks: what they leave to the re-trace launch, its work cursor, and -- optional -- where that launch leaves rays for k_trace_monster
+    uint32_t* exactQueue = nullptr; uint32_t* exactCount = nullptr; uint32_t* exactShadowQueue = nullptr; uint32_t* exactShadowCount = nullptr; uint32_t* exactCursor = nullptr;
+    uint32_t* overflowQueue = nullptr; uint32_t* overflowCount = nullptr;
+    // the call's policy
+    float shadowOffset = 0.0001f;              // any-hit rays start this far along their direction (TravTuning::shadowOffset)
+    const uint32_t* denseCounts = nullptr; uint32_t denseShardCapacity = 0u;   // dense path state: the closest-hit rays are the live paths of the arena's regions (no queue)
+    bool mayTraceUndecidedRaysItself = true;   // a 4-wide walk may trace what it does not decide in its own blocks (launchTraceWide's policy decides whether it does)
+    uint32_t bounce = 0u;                      // for the policies that depend on it (the block-local second walk, the packet walk of camera rays)
+    uint4* rayCounts = nullptr;                // binary walk only: every closest-hit ray's own test counts (TravTuning::rayCounts); makes the walk a counting one
+};
+
+#define RT_LANE_COUNT_PLANES 8u
+static size_t laneCountBytes(const BatchLane& l) { return (size_t)RT_LANE_COUNT_PLANES * l.queueCountCapacity * sizeof(uint32_t); }
+
 // the planes of BatchLane::queueCounts, built once per flush; index each with the bounce (plane 3 is unused)
 struct LaneCounts
 {
+    const BatchLane& lane;
     uint32_t* pathCounts; uint32_t* shadowCounts; uint32_t* cursors;              // path queues, next-event request queues, the traversal launches' work cursors
     uint32_t* exactCounts; uint32_t* exactShadowCounts; uint32_t* exactCursors;   // what the 4-wide walks hand to the re-trace launch, and its cursors
     uint32_t* overflowCounts;                                                     // closest-hit rays the re-trace launch hands to k_trace_monster
     explicit LaneCounts(const BatchLane& l)
-        : pathCounts(l.queueCounts), shadowCounts(l.queueCounts + 1 * l.queueCountCapacity), cursors(l.queueCounts + 2 * l.queueCountCapacity),
+        : lane(l), pathCounts(l.queueCounts), shadowCounts(l.queueCounts + 1 * l.queueCountCapacity), cursors(l.queueCounts + 2 * l.queueCountCapacity),
           exactCounts(l.queueCounts + 4 * l.queueCountCapacity), exactShadowCounts(l.queueCounts + 5 * l.queueCountCapacity),
           exactCursors(l.queueCounts + 6 * l.queueCountCapacity), overflowCounts(l.queueCounts + 7 * l.queueCountCapacity) {}
+    // the work of bounce d: {closest-hit rays of bounce d, next-event requests of bounce d - 1}, whichever exist, and the bounce's work cursor
+    void queuesOf(TraceStep& s, uint32_t d, bool haveClosest, bool haveShadow) const
+    {
+        s.queue = haveClosest ? lane.queues[d & 1u] : nullptr; s.queueCount = haveClosest ? pathCounts + d : nullptr;
+        s.shadowQueue = haveShadow ? lane.shadowQueues[(d - 1u) & 1u] : nullptr; s.shadowCount = haveShadow ? shadowCounts + (d - 1u) : nullptr;
+        s.cursor = cursors + d;
+    }
+    // the hand-over of bounce d; `overflowQueue`: a queue of the lane nobody uses during this bounce's trace (launchRetrace)
+    void handOverOf(TraceStep& s, uint32_t d, uint32_t* overflowQueue) const
+    {
+        s.exactQueue = lane.exactQueue; s.exactCount = exactCounts + d; s.exactShadowQueue = lane.exactShadowQueue; s.exactShadowCount = exactShadowCounts + d;
+        s.exactCursor = exactCursors + d; s.overflowQueue = overflowQueue; s.overflowCount = overflowCounts + d;
+    }
+};
+
+// The arena of a walk over the library's own rays (ray queries, AOVs); `counts` and `counters` are allocated once by the owner and outlive a growth
+struct WalkArena
+{
+    Paths paths = { nullptr, 0, 0 };          // maxLights = 1; capacity = the rays of one chunk
+    uint32_t* queue = nullptr;                // the chunk's closest-hit rays or any-hit requests
+    uint32_t* exactQueue = nullptr; uint32_t* exactShadowQueue = nullptr;   // what the 4-wide walks hand to the re-trace launch
+    uint32_t* counts = nullptr;               // QC_WORDS work counts (QC_*, rt_runtime_query.inl)
+    unsigned long long* counters = nullptr;   // 16 x u64, the layout of RtCounters
 };
 
 struct RtgpuContext
@@ -221,11 +265,7 @@ struct RtgpuContext
     // batched ray queries (rtgpu_trace_rays): a path-state arena, queues, work counts and counters of their own -- never a lane's, never c->counters
     struct Query
     {
-        Paths paths = { nullptr, 0, 0 };          // maxLights = 1; capacity = the rays of one chunk
-        uint32_t* queue = nullptr;                // closest-hit rays or any-hit requests of the chunk
-        uint32_t* exactQueue = nullptr; uint32_t* exactShadowQueue = nullptr;   // what the 4-wide walks hand to the re-trace launch
-        uint32_t* counts = nullptr;               // QC_WORDS work counts (QC_*)
-        unsigned long long* counters = nullptr;   // 16 x u64, the layout of RtCounters
+        WalkArena arena;
         float4* stagedRays = nullptr; float4* stagedHits = nullptr; float4* stagedSurfaces = nullptr; uint32_t* stagedOccluded = nullptr;   // rtgpu_trace_rays' device copies
         hipEvent_t done = nullptr;                // recorded behind every query: the next one (whatever its stream), a new arena and a new scene wait for it
     } query;
@@ -246,14 +286,10 @@ struct RtgpuContext
     // of its own -- never a lane's, never c->counters, never the seed ring
     struct Aov
     {
-        Paths paths = { nullptr, 0, 0 };          // maxLights = 1; capacity = the pixels of one chunk
-        uint32_t* queue = nullptr;                // the chunk's primary rays (the identity)
-        uint32_t* exactQueue = nullptr; uint32_t* exactShadowQueue = nullptr;   // what the 4-wide walks hand to the re-trace launch
+        WalkArena arena;                          // capacity = the pixels of one chunk; the queue is the chunk's primary rays (the identity); the counters are never read
         uint32_t* slotPixel = nullptr;            // slot -> pixel of the chunk (k_aov_pixels)
         uint4* rayCounts = nullptr;               // per slot what the counting walk counted for its ray (TravTuning::rayCounts); allocated with the first cost plane
         uint32_t* staged = nullptr; size_t stagedWords = 0;   // rtgpu_render_aovs' device copy of a chunk's planes
-        uint32_t* counts = nullptr;               // QC_WORDS work counts (QC_*, rt_runtime_query.inl)
-        unsigned long long* counters = nullptr;   // 16 x u64, never read
         DevPass* passDev = nullptr; uint32_t* seedDev = nullptr;   // the pass whose primary rays are traced
         // pass constants and seeds travel through a small ring of page-locked records: an asynchronous call returns before its copy has run
         static const uint32_t kRing = 4;
@@ -351,18 +387,32 @@ static void waitQueries(RtgpuContext* c)
     if (c->query.done) (void)hipEventSynchronize(c->query.done);
     if (c->aov.done) (void)hipEventSynchronize(c->aov.done);   // (an asynchronous AOV call walks the scene as a query does)
 }
+// A freed walk arena for `want` rays, in powers of two from 64 K: a caller whose batches grow slowly does not reallocate with every call
+static int growWalkArena(WalkArena& w, uint32_t want)
+{
+    uint32_t cap = 65536u;
+    while (cap < want) cap <<= 1;
+    HIP_TRY(hipMalloc((void**)&w.paths.base, ((size_t)R_NUM_BASE + RT_SHADOW_RECORDS) * cap * sizeof(float4)));
+    HIP_TRY(hipMalloc((void**)&w.queue, (size_t)cap * sizeof(uint32_t)));
+    HIP_TRY(hipMalloc((void**)&w.exactQueue, (size_t)cap * sizeof(uint32_t)));
+    HIP_TRY(hipMalloc((void**)&w.exactShadowQueue, (size_t)cap * sizeof(uint32_t)));
+    w.paths.capacity = cap; w.paths.maxLights = 1;
+    return RTGPU_OK;
+}
+static void freeWalkArena(WalkArena& w) { devFree(w.paths.base, w.queue, w.exactQueue, w.exactShadowQueue); w.paths.capacity = 0; w.paths.maxLights = 0; }
+
 static void freeQueryArena(RtgpuContext* c)
 {
     RtgpuContext::Query& q = c->query;
     waitQueries(c);
-    devFree(q.paths.base, q.queue, q.exactQueue, q.exactShadowQueue, q.stagedRays, q.stagedHits, q.stagedSurfaces, q.stagedOccluded);
-    q.paths.capacity = 0; q.paths.maxLights = 0;
+    freeWalkArena(q.arena);
+    devFree(q.stagedRays, q.stagedHits, q.stagedSurfaces, q.stagedOccluded);
 }
 static void freeQuery(RtgpuContext* c)
 {
     RtgpuContext::Query& q = c->query;
     freeQueryArena(c);
-    devFree(q.counts, q.counters);
+    devFree(q.arena.counts, q.arena.counters);
     if (q.done) (void)hipEventDestroy(q.done);
     q.done = nullptr;
 }
@@ -371,14 +421,14 @@ static void freeAovArena(RtgpuContext* c)
 {
     RtgpuContext::Aov& a = c->aov;
     if (a.done) (void)hipEventSynchronize(a.done);
-    devFree(a.paths.base, a.queue, a.exactQueue, a.exactShadowQueue, a.slotPixel, a.rayCounts);
-    a.paths.capacity = 0; a.paths.maxLights = 0;
+    freeWalkArena(a.arena);
+    devFree(a.slotPixel, a.rayCounts);
 }
 static void freeAov(RtgpuContext* c)
 {
     RtgpuContext::Aov& a = c->aov;
     freeAovArena(c);
-    devFree(a.staged, a.counts, a.counters, a.passDev, a.seedDev);
+    devFree(a.staged, a.arena.counts, a.arena.counters, a.passDev, a.seedDev);
     a.stagedWords = 0;
     if (a.ringHost) (void)hipHostFree(a.ringHost);
     a.ringHost = nullptr;

@@ -20,19 +20,11 @@ static int ensureRecorder(RtgpuContext* c, uint32_t slots, uint32_t maxLights, u
         uint32_t cap = 1024u;
         while (cap < slots) cap <<= 1;
         if (cap < l.paths.capacity) cap = l.paths.capacity;
-        if ((unsigned long long)cap * maxLights >= 0xFFFFFFFFull) return fail(RTGPU_ERR_UNSUPPORTED, "pixels x lights exceeds the NEE request index range");
         freePaths(l);
         devFree(rec.slotPixel, rec.infos);
-        HIP_TRY(hipMalloc((void**)&l.paths.base, ((size_t)R_NUM_BASE + (size_t)maxLights * RT_SHADOW_RECORDS) * cap * sizeof(float4)));
-        HIP_TRY(hipMalloc((void**)&l.queues[0], (size_t)cap * sizeof(uint32_t)));
-        HIP_TRY(hipMalloc((void**)&l.queues[1], (size_t)cap * sizeof(uint32_t)));
-        HIP_TRY(hipMalloc((void**)&l.shadowQueues[0], (size_t)cap * maxLights * sizeof(uint32_t)));
-        HIP_TRY(hipMalloc((void**)&l.shadowQueues[1], (size_t)cap * maxLights * sizeof(uint32_t)));
-        HIP_TRY(hipMalloc((void**)&l.exactQueue, (size_t)cap * sizeof(uint32_t)));
-        HIP_TRY(hipMalloc((void**)&l.exactShadowQueue, (size_t)cap * maxLights * sizeof(uint32_t)));
+        { const int r = allocLanePaths(l, cap, maxLights); if (r) return r; }
         HIP_TRY(hipMalloc((void**)&rec.slotPixel, (size_t)cap * sizeof(uint32_t)));
         HIP_TRY(hipMalloc((void**)&rec.infos, (size_t)cap * 2u * sizeof(float4)));
-        l.paths.capacity = cap; l.paths.maxLights = maxLights;
     }
     if (rec.recordCapacity < (size_t)slots * recordStride)
     {
@@ -45,44 +37,26 @@ static int ensureRecorder(RtgpuContext* c, uint32_t slots, uint32_t maxLights, u
     {
         devFree(l.queueCounts);
         l.queueCountCapacity = maxDepth + 2u;
-        HIP_TRY(hipMalloc((void**)&l.queueCounts, (size_t)8 * l.queueCountCapacity * sizeof(uint32_t)));
+        HIP_TRY(hipMalloc((void**)&l.queueCounts, laneCountBytes(l)));
     }
     return RTGPU_OK;
 }
 
-// the launches of one chunk of `n` slots (rec.slotPixel holds their pixels), on `stream`: submitSlotBatch's sequence with the recording shade kernel
+// the launches of one chunk of `n` slots (rec.slotPixel holds their pixels), on `stream`: submitSlotBatch's bounces (launchSlotBounces) with the recording shade kernel
 static int launchRecordChunk(RtgpuContext* c, hipStream_t stream, uint32_t n, uint32_t maxRayDepth, uint32_t recordStride)
 {
     RtgpuContext::Recorder& rec = c->recorder;
     BatchLane& l = rec.lane;
     const LaneCounts counts(l);
     const dim3 block(RT_BLOCK), grid((n + RT_BLOCK - 1u) / RT_BLOCK);
-    HIP_TRY(hipMemsetAsync(l.queueCounts, 0, (size_t)8 * l.queueCountCapacity * sizeof(uint32_t), stream));
+    HIP_TRY(hipMemsetAsync(l.queueCounts, 0, laneCountBytes(l), stream));
     // one pass, so a pass holds all `n` slots: slot / slotsPerPass = 0 for every slot
     hipLaunchKernelGGL(k_generate, grid, block, 0, stream, c->sceneDev, rec.passDev, n, l.paths, rec.slotPixel, n, l.queues[0], counts.pathCounts + 0, rec.counters);
-    for (uint32_t depth = 0; depth <= maxRayDepth + 1u; ++depth)
+    launchSlotBounces(c, stream, rec.counters, l, counts, maxRayDepth, maxRayDepth + 1u, c->numLights != 0, [&](uint32_t depth)
     {
-        const bool haveClosest = depth <= maxRayDepth;
-        const bool haveShadow = depth > 0 && c->numLights != 0;
-        if (haveClosest || haveShadow)
-        {
-            const uint32_t* tq = haveClosest ? l.queues[depth & 1u] : nullptr;
-            const uint32_t* tqc = haveClosest ? counts.pathCounts + depth : nullptr;
-            const uint32_t* tsq = haveShadow ? l.shadowQueues[(depth - 1u) & 1u] : nullptr;
-            const uint32_t* tsc = haveShadow ? counts.shadowCounts + (depth - 1u) : nullptr;
-            if (useWide(c))
-            {
-                launchTraceWide(c, stream, rec.counters, l.paths, tq, tqc, tsq, tsc, counts.cursors + depth, l.exactQueue, counts.exactCounts + depth, l.exactShadowQueue,
-                                counts.exactShadowCounts + depth, 0.0001f, nullptr, 0u);
-                launchRetrace(c, stream, rec.counters, l.paths, l.exactQueue, counts.exactCounts + depth, l.exactShadowQueue, counts.exactShadowCounts + depth, counts.exactCursors + depth,
-                              l.queues[(depth + 1u) & 1u], counts.overflowCounts + depth);
-            }
-            else launchTraceBinary(c, stream, dim3(traversalBlocks(c, stackClassOf(c))), rec.counters, l.paths, tq, tqc, tsq, tsc, counts.cursors + depth, c->tune, c->countIntersections);
-        }
-        if (haveClosest)
-            hipLaunchKernelGGL((k_shade_record<false, false>), grid, block, 0, stream, c->sceneDev, rec.passDev, n, l.paths, l.queues[depth & 1u], counts.pathCounts + depth,
-                               l.queues[(depth + 1u) & 1u], counts.pathCounts + depth + 1, l.shadowQueues[depth & 1u], counts.shadowCounts + depth, rec.counters, rec.records, recordStride);
-    }
+        hipLaunchKernelGGL((k_shade_record<false, false>), grid, block, 0, stream, c->sceneDev, rec.passDev, n, l.paths, l.queues[depth & 1u], counts.pathCounts + depth,
+                           l.queues[(depth + 1u) & 1u], counts.pathCounts + depth + 1, l.shadowQueues[depth & 1u], counts.shadowCounts + depth, rec.counters, rec.records, recordStride);
+    });
     hipLaunchKernelGGL(k_paths_finish, grid, block, 0, stream, l.paths, n, rec.passDev, rec.records, recordStride, rec.infos, rec.counters);
     HIP_TRY(hipGetLastError());
     return RTGPU_OK;

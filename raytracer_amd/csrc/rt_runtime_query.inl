@@ -8,63 +8,50 @@ enum { QC_QUEUE = 0, QC_CURSOR, QC_EXACT, QC_EXACT_SHADOW, QC_EXACT_CURSOR, QC_W
 static int ensureQueryArena(RtgpuContext* c, uint32_t rays)
 {
     RtgpuContext::Query& q = c->query;
+    WalkArena& w = q.arena;
     if (!q.done) HIP_TRY(hipEventCreateWithFlags(&q.done, hipEventDisableTiming));
-    if (!q.counts) HIP_TRY(hipMalloc((void**)&q.counts, QC_WORDS * sizeof(uint32_t)));
-    if (!q.counters) HIP_TRY(hipMalloc((void**)&q.counters, 16 * sizeof(unsigned long long)));
-    const uint32_t want = rays < RT_QUERY_CHUNK ? rays : RT_QUERY_CHUNK;
-    if (q.paths.base && q.paths.capacity >= want) return RTGPU_OK;
-    // grown in powers of two from 64 K rays up to the chunk: a caller whose batches grow slowly does not reallocate with every call
-    uint32_t cap = 65536u;
-    while (cap < want) cap <<= 1;
+    if (!w.counts) HIP_TRY(hipMalloc((void**)&w.counts, QC_WORDS * sizeof(uint32_t)));
+    if (!w.counters) HIP_TRY(hipMalloc((void**)&w.counters, 16 * sizeof(unsigned long long)));
+    const uint32_t want = rays < RT_QUERY_CHUNK ? rays : RT_QUERY_CHUNK;   // (the arena grows up to the chunk)
+    if (w.paths.base && w.paths.capacity >= want) return RTGPU_OK;
     freeQueryArena(c);   // (waits for the queries still using it)
-    HIP_TRY(hipMalloc((void**)&q.paths.base, ((size_t)R_NUM_BASE + RT_SHADOW_RECORDS) * cap * sizeof(float4)));
-    HIP_TRY(hipMalloc((void**)&q.queue, (size_t)cap * sizeof(uint32_t)));
-    HIP_TRY(hipMalloc((void**)&q.exactQueue, (size_t)cap * sizeof(uint32_t)));
-    HIP_TRY(hipMalloc((void**)&q.exactShadowQueue, (size_t)cap * sizeof(uint32_t)));
-    HIP_TRY(hipMalloc((void**)&q.stagedRays, (size_t)cap * sizeof(RtQueryRay)));
-    HIP_TRY(hipMalloc((void**)&q.stagedHits, (size_t)cap * sizeof(RtQueryHit)));
-    HIP_TRY(hipMalloc((void**)&q.stagedSurfaces, (size_t)cap * sizeof(RtQuerySurface)));
-    HIP_TRY(hipMalloc((void**)&q.stagedOccluded, (size_t)cap * sizeof(uint32_t)));
-    q.paths.capacity = cap; q.paths.maxLights = 1;
+    { const int r = growWalkArena(w, want); if (r) return r; }
+    HIP_TRY(hipMalloc((void**)&q.stagedRays, (size_t)w.paths.capacity * sizeof(RtQueryRay)));
+    HIP_TRY(hipMalloc((void**)&q.stagedHits, (size_t)w.paths.capacity * sizeof(RtQueryHit)));
+    HIP_TRY(hipMalloc((void**)&q.stagedSurfaces, (size_t)w.paths.capacity * sizeof(RtQuerySurface)));
+    HIP_TRY(hipMalloc((void**)&q.stagedOccluded, (size_t)w.paths.capacity * sizeof(uint32_t)));
     return RTGPU_OK;
 }
 
-// The walk over an arena of the library's own (ray queries, AOVs): one queue of closest-hit rays or of any-hit requests, work counts laid out as QC_*.
-// `wide`: the render path's pair -- the 4-wide walk hands the rays it does not decide to the re-trace launch (which alone gives them a result); no
+// The walk over an arena of the library's own (ray queries, AOVs), whose queue holds closest-hit rays (`closest`) or any-hit requests.  `wide`: the render path's pair -- the 4-wide walk hands the rays it does not decide to the re-trace launch (which alone gives them a result); no
 // block-local second walk and no k_trace_monster hand-over, neither changes a result.  Otherwise the reference's binary walk (k_trace), counting where the
 // context counts or `rayCounts` (TravTuning::rayCounts: every closest-hit ray's own counts) is asked for.  Rays start where the caller put them: no offset.
-static void launchArenaWalk(RtgpuContext* c, hipStream_t stream, unsigned long long* counters, const Paths& paths, const uint32_t* tq, const uint32_t* tqc, const uint32_t* tsq,
-                            const uint32_t* tsc, uint32_t* counts, uint32_t* exactQueue, uint32_t* exactShadowQueue, bool wide, uint4* rayCounts)
+static void launchArenaWalk(RtgpuContext* c, hipStream_t stream, const WalkArena& w, bool closest, bool wide, uint4* rayCounts)
 {
-    if (wide)
-    {
-        launchTraceWide(c, stream, counters, paths, tq, tqc, tsq, tsc, counts + QC_CURSOR, exactQueue, counts + QC_EXACT, exactShadowQueue, counts + QC_EXACT_SHADOW, 0.0f, nullptr, 0u, false);
-        launchRetrace(c, stream, counters, paths, exactQueue, counts + QC_EXACT, exactShadowQueue, counts + QC_EXACT_SHADOW, counts + QC_EXACT_CURSOR, nullptr, nullptr);
-        return;
-    }
-    TravTuning tune = c->tune;
-    tune.shadowOffset = 0.0f; tune.overflowQueue = nullptr; tune.overflowCount = nullptr; tune.denseCounts = nullptr; tune.denseShardCapacity = 0u;
-    tune.rayCounts = rayCounts;
-    launchTraceBinary(c, stream, dim3(traversalBlocks(c, stackClassOf(c))), counters, paths, tq, tqc, tsq, tsc, counts + QC_CURSOR, tune, rayCounts != nullptr || c->countIntersections);
+    TraceStep s = { stream, w.counters, w.paths };
+    if (closest) { s.queue = w.queue; s.queueCount = w.counts + QC_QUEUE; } else { s.shadowQueue = w.queue; s.shadowCount = w.counts + QC_QUEUE; }
+    s.cursor = w.counts + QC_CURSOR;
+    s.exactQueue = w.exactQueue; s.exactCount = w.counts + QC_EXACT; s.exactShadowQueue = w.exactShadowQueue; s.exactShadowCount = w.counts + QC_EXACT_SHADOW; s.exactCursor = w.counts + QC_EXACT_CURSOR;
+    s.shadowOffset = 0.0f; s.mayTraceUndecidedRaysItself = false; s.rayCounts = rayCounts;
+    launchTraceStep(c, s, wide);
 }
 
 // the launches of one chunk (n <= the arena's capacity), device pointers, on `stream`
 static int launchQueryChunk(RtgpuContext* c, hipStream_t stream, uint32_t mode, const float4* rays, uint32_t n, float4* hits, float4* surfaces, uint32_t* occluded)
 {
     RtgpuContext::Query& q = c->query;
+    const WalkArena& w = q.arena;
     const bool closest = mode == RTGPU_TRACE_CLOSEST;
     const dim3 block(RT_BLOCK), grid((n + RT_BLOCK - 1u) / RT_BLOCK);
-    HIP_TRY(hipMemsetAsync(q.counts, 0, QC_WORDS * sizeof(uint32_t), stream));
-    hipLaunchKernelGGL(k_query_load, grid, block, 0, stream, rays, n, mode, q.paths, q.queue, q.counts + QC_QUEUE, q.counters);
-    const uint32_t* tq = closest ? q.queue : nullptr; const uint32_t* tqc = closest ? q.counts + QC_QUEUE : nullptr;
-    const uint32_t* tsq = closest ? nullptr : q.queue; const uint32_t* tsc = closest ? nullptr : q.counts + QC_QUEUE;
+    HIP_TRY(hipMemsetAsync(w.counts, 0, QC_WORDS * sizeof(uint32_t), stream));
+    hipLaunchKernelGGL(k_query_load, grid, block, 0, stream, rays, n, mode, w.paths, w.queue, w.counts + QC_QUEUE, w.counters);
     // Any-hit requests walk the reference's binary tree (k_trace) whatever the setting: the 4-wide walks' any-hit decision is exact for the rays the
     // integrators ask about (tmax = 0.999 x the light's distance: no triangle within an ulp of it), but a query's maxDistance may sit an ulp below a
     // hit, and there the conservative leaf gate of the 4-wide walks let 6 % of such rays report an occluder the reference's box test culls (DESIGN.md,
     // "Ray queries").
-    launchArenaWalk(c, stream, q.counters, q.paths, tq, tqc, tsq, tsc, q.counts, q.exactQueue, q.exactShadowQueue, useWide(c) && closest, nullptr);
-    hipLaunchKernelGGL(k_query_store, grid, block, 0, stream, c->sceneDev, rays, n, mode, q.paths, hits, occluded);
-    if (surfaces) hipLaunchKernelGGL(k_query_evaluate, grid, block, 0, stream, c->sceneDev, rays, n, (const float4*)hits, surfaces, q.counters);
+    launchArenaWalk(c, stream, w, closest, useWide(c) && closest, nullptr);
+    hipLaunchKernelGGL(k_query_store, grid, block, 0, stream, c->sceneDev, rays, n, mode, w.paths, hits, occluded);
+    if (surfaces) hipLaunchKernelGGL(k_query_evaluate, grid, block, 0, stream, c->sceneDev, rays, n, (const float4*)hits, surfaces, w.counters);
     HIP_TRY(hipGetLastError());
     return RTGPU_OK;
 }
@@ -109,11 +96,11 @@ RTGPU_API int rtgpu_trace_rays(RtgpuContext* c, uint32_t mode, const RtQueryRay*
     const QueryUntimed untimed(c);
     hipStream_t stream = c->lanes[0].stream;
     HIP_TRY(hipStreamWaitEvent(stream, q.done, 0));
-    HIP_TRY(hipMemsetAsync(q.counters, 0, 16 * sizeof(unsigned long long), stream));
+    HIP_TRY(hipMemsetAsync(q.arena.counters, 0, 16 * sizeof(unsigned long long), stream));
     const bool closest = mode == RTGPU_TRACE_CLOSEST;
-    for (uint32_t first = 0; first < count; first += q.paths.capacity)
+    for (uint32_t first = 0; first < count; first += q.arena.paths.capacity)
     {
-        const uint32_t n = count - first < q.paths.capacity ? count - first : q.paths.capacity;
+        const uint32_t n = count - first < q.arena.paths.capacity ? count - first : q.arena.paths.capacity;
         HIP_TRY(rtMemcpy(q.stagedRays, rays + first, (size_t)n * sizeof(RtQueryRay), hipMemcpyHostToDevice));
         r = launchQueryChunk(c, stream, mode, q.stagedRays, n, closest ? q.stagedHits : nullptr, surfaces ? q.stagedSurfaces : nullptr, closest ? nullptr : q.stagedOccluded);
         if (r) return r;
@@ -123,7 +110,7 @@ RTGPU_API int rtgpu_trace_rays(RtgpuContext* c, uint32_t mode, const RtQueryRay*
         if (!closest) HIP_TRY(rtMemcpy(occluded + first, q.stagedOccluded, (size_t)n * sizeof(uint32_t), hipMemcpyDeviceToHost));
     }
     HIP_TRY(hipEventRecord(q.done, stream));
-    if (stats) HIP_TRY(rtMemcpy(stats, q.counters, sizeof(RtCounters), hipMemcpyDeviceToHost));
+    if (stats) HIP_TRY(rtMemcpy(stats, q.arena.counters, sizeof(RtCounters), hipMemcpyDeviceToHost));
     return RTGPU_OK;
 }
 
@@ -140,15 +127,15 @@ RTGPU_API int rtgpu_trace_rays_async(RtgpuContext* c, uint32_t mode, const RtQue
     const QueryUntimed untimed(c);
     hipStream_t stream = streamHandle ? (hipStream_t)streamHandle : c->lanes[0].stream;
     HIP_TRY(hipStreamWaitEvent(stream, q.done, 0));   // the arena is shared with the previous query, whatever its stream
-    HIP_TRY(hipMemsetAsync(q.counters, 0, 16 * sizeof(unsigned long long), stream));
-    for (uint32_t first = 0; first < count; first += q.paths.capacity)
+    HIP_TRY(hipMemsetAsync(q.arena.counters, 0, 16 * sizeof(unsigned long long), stream));
+    for (uint32_t first = 0; first < count; first += q.arena.paths.capacity)
     {
-        const uint32_t n = count - first < q.paths.capacity ? count - first : q.paths.capacity;
+        const uint32_t n = count - first < q.arena.paths.capacity ? count - first : q.arena.paths.capacity;
         r = launchQueryChunk(c, stream, mode, (const float4*)(rays + first), n, hits ? (float4*)(hits + first) : nullptr, surfaces ? (float4*)(surfaces + first) : nullptr,
                              occluded ? occluded + first : nullptr);
         if (r) return r;
     }
-    if (stats) HIP_TRY(hipMemcpyAsync(stats, q.counters, sizeof(RtCounters), hipMemcpyDeviceToDevice, stream));
+    if (stats) HIP_TRY(hipMemcpyAsync(stats, q.arena.counters, sizeof(RtCounters), hipMemcpyDeviceToDevice, stream));
     HIP_TRY(hipEventRecord(q.done, stream));
     return RTGPU_OK;
 }

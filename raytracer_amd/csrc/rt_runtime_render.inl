@@ -31,6 +31,19 @@ static uint32_t maxBatchFor(const RtgpuContext* c, uint32_t maxLights)
 // roughly a sixteenth: blocks take turns)
 static size_t arenaCapacityFor(size_t slots) { return (size_t)RT_DENSE_SHARDS * ((slots + RT_DENSE_SHARDS - 1u) / RT_DENSE_SHARDS + 65536u); }
 
+// The seven buffers of a slot-per-pixel lane (freed before: freePaths) for `capacity` slots with `maxLights` next-event requests per vertex
+static int allocLanePaths(BatchLane& l, size_t capacity, uint32_t maxLights)
+{
+    if ((unsigned long long)capacity * maxLights >= 0xFFFFFFFFull) return fail(RTGPU_ERR_UNSUPPORTED, "pixels x lights exceeds the NEE request index range");
+    HIP_TRY(hipMalloc((void**)&l.paths.base, ((size_t)R_NUM_BASE + (size_t)maxLights * RT_SHADOW_RECORDS) * capacity * sizeof(float4)));
+    for (int k = 0; k < 2; ++k) HIP_TRY(hipMalloc((void**)&l.queues[k], capacity * sizeof(uint32_t)));
+    for (int k = 0; k < 2; ++k) HIP_TRY(hipMalloc((void**)&l.shadowQueues[k], capacity * maxLights * sizeof(uint32_t)));
+    HIP_TRY(hipMalloc((void**)&l.exactQueue, capacity * sizeof(uint32_t)));
+    HIP_TRY(hipMalloc((void**)&l.exactShadowQueue, capacity * maxLights * sizeof(uint32_t)));
+    l.paths.capacity = (uint32_t)capacity; l.paths.maxLights = maxLights;
+    return RTGPU_OK;
+}
+
 static int ensurePaths(RtgpuContext* c, BatchLane& l, uint32_t maxLights, uint32_t maxDepth)
 {
     if (maxLights == 0) maxLights = 1;
@@ -65,19 +78,10 @@ static int ensurePaths(RtgpuContext* c, BatchLane& l, uint32_t maxLights, uint32
         }
         const size_t cap = arenaCapacityFor(wanted);
         if (cap >= 0xFFFFFFFFull) return fail(RTGPU_ERR_UNSUPPORTED, "pixels x pass batch exceeds the slot index range");
-        const size_t records = ((size_t)R_NUM_BASE + (size_t)maxLights * RT_SHADOW_RECORDS) * cap;
-        HIP_TRY(hipMalloc((void**)&l.paths.base, records * sizeof(float4)));
-        HIP_TRY(hipMalloc((void**)&l.queues[0], cap * sizeof(uint32_t)));
-        HIP_TRY(hipMalloc((void**)&l.queues[1], cap * sizeof(uint32_t)));
-        if ((unsigned long long)cap * maxLights >= 0xFFFFFFFFull) return fail(RTGPU_ERR_UNSUPPORTED, "pixels x lights exceeds the NEE request index range");
-        HIP_TRY(hipMalloc((void**)&l.shadowQueues[0], cap * maxLights * sizeof(uint32_t)));
-        HIP_TRY(hipMalloc((void**)&l.shadowQueues[1], cap * maxLights * sizeof(uint32_t)));
-        HIP_TRY(hipMalloc((void**)&l.exactQueue, cap * sizeof(uint32_t)));
-        HIP_TRY(hipMalloc((void**)&l.exactShadowQueue, cap * maxLights * sizeof(uint32_t)));
-        l.paths.capacity = (uint32_t)cap; l.paths.maxLights = maxLights;
+        { const int r = allocLanePaths(l, cap, maxLights); if (r) return r; }
         if (wantDense)
         {
-            HIP_TRY(hipMalloc((void**)&l.paths2.base, records * sizeof(float4)));
+            HIP_TRY(hipMalloc((void**)&l.paths2.base, ((size_t)R_NUM_BASE + (size_t)maxLights * RT_SHADOW_RECORDS) * cap * sizeof(float4)));
             HIP_TRY(hipMalloc((void**)&l.home, wanted * sizeof(float4)));
             l.homeCapacity = wanted;
             l.paths2.capacity = (uint32_t)cap; l.paths2.maxLights = maxLights;
@@ -89,7 +93,7 @@ static int ensurePaths(RtgpuContext* c, BatchLane& l, uint32_t maxLights, uint32
         HIP_TRY(hipStreamSynchronize(l.stream));
         devFree(l.queueCounts, l.denseCounts);
         l.queueCountCapacity = maxDepth + 2;
-        HIP_TRY(hipMalloc((void**)&l.queueCounts, (size_t)8 * l.queueCountCapacity * sizeof(uint32_t)));
+        HIP_TRY(hipMalloc((void**)&l.queueCounts, laneCountBytes(l)));
         HIP_TRY(hipMalloc((void**)&l.denseCounts, (size_t)2 * RT_DENSE_SHARDS * (l.queueCountCapacity + 1u) * sizeof(uint32_t)));
     }
     return RTGPU_OK;
@@ -104,22 +108,15 @@ static uint32_t traversalBlocks(const RtgpuContext* c, uint32_t stackClass)
     return c->numCUs * (c->travBlocksPerCU ? c->travBlocksPerCU : (stackClass == 24u ? 5u : (stackClass == 32u ? 4u : 2u)));
 }
 
-// The reference's walk over the binary trees (k_trace): the one place that picks its instantiation.  The caller sets up `tune`, chooses the grid and
-// times the launch; `counting`: with the box / triangle test counters (and, where tune.rayCounts is set, every ray's own counts).
-static void launchTraceBinary(RtgpuContext* c, hipStream_t stream, dim3 grid, unsigned long long* counters, const Paths& paths, const uint32_t* tq, const uint32_t* tqc,
-                              const uint32_t* tsq, const uint32_t* tsc, uint32_t* cursor, const TravTuning& tune, bool counting)
+// The reference's walk over the binary trees (k_trace) over the work of `s`: the one place that picks its instantiation.  The caller sets up `tune`, chooses the
+// grid and times the launch; `counting`: with the box / triangle test counters (and, where tune.rayCounts is set, every ray's own counts).
+static void launchTraceBinary(RtgpuContext* c, const TraceStep& s, dim3 grid, const TravTuning& tune, bool counting)
 {
     const uint32_t stackClass = stackClassOf(c);
-#define RT_LAUNCH_TRACE(S, C) hipLaunchKernelGGL((k_trace<S, C>), grid, dim3(RT_BLOCK), 0, stream, c->sceneDev, paths, tq, tqc, tsq, tsc, cursor, counters, tune)
-    if (counting && tune.rayCounts)
-    {
-        if (stackClass == 24u) hipLaunchKernelGGL((k_trace<24, true, true>), grid, dim3(RT_BLOCK), 0, stream, c->sceneDev, paths, tq, tqc, tsq, tsc, cursor, counters, tune);
-        else if (stackClass == 32u) hipLaunchKernelGGL((k_trace<32, true, true>), grid, dim3(RT_BLOCK), 0, stream, c->sceneDev, paths, tq, tqc, tsq, tsc, cursor, counters, tune);
-        else hipLaunchKernelGGL((k_trace<64, true, true>), grid, dim3(RT_BLOCK), 0, stream, c->sceneDev, paths, tq, tqc, tsq, tsc, cursor, counters, tune);
-    }
-    else if (stackClass == 24u) { if (counting) RT_LAUNCH_TRACE(24, true); else RT_LAUNCH_TRACE(24, false); }
-    else if (stackClass == 32u) { if (counting) RT_LAUNCH_TRACE(32, true); else RT_LAUNCH_TRACE(32, false); }
-    else { if (counting) RT_LAUNCH_TRACE(64, true); else RT_LAUNCH_TRACE(64, false); }
+#define RT_LAUNCH_TRACE(S, C, R) hipLaunchKernelGGL((k_trace<S, C, R>), grid, dim3(RT_BLOCK), 0, s.stream, c->sceneDev, s.paths, s.queue, s.queueCount, s.shadowQueue, s.shadowCount, s.cursor, s.counters, tune)
+#define RT_LAUNCH_TRACE_STACK(S) { if (counting && tune.rayCounts) RT_LAUNCH_TRACE(S, true, true); else if (counting) RT_LAUNCH_TRACE(S, true, false); else RT_LAUNCH_TRACE(S, false, false); }
+    if (stackClass == 24u) RT_LAUNCH_TRACE_STACK(24) else if (stackClass == 32u) RT_LAUNCH_TRACE_STACK(32) else RT_LAUNCH_TRACE_STACK(64)
+#undef RT_LAUNCH_TRACE_STACK
 #undef RT_LAUNCH_TRACE
 }
 
@@ -127,9 +124,7 @@ static void launchTraceBinary(RtgpuContext* c, hipStream_t stream, dim3 grid, un
 // ray that would need more goes to the binary-tree kernel.
 static bool useWide(const RtgpuContext* c) { return (c->wide.nodes != nullptr || (c->wide2.nodes != nullptr && c->wide2Allowed)) && c->wideAllowed && !c->countIntersections; }
 
-static void launchTraceWide(RtgpuContext* c, hipStream_t stream, unsigned long long* counters, const Paths& paths, const uint32_t* tq, const uint32_t* tqc, const uint32_t* tsq, const uint32_t* tsc,
-                            uint32_t* cursor, uint32_t* exactQueue, uint32_t* exactCount, uint32_t* exactShadowQueue, uint32_t* exactShadowCount, float shadowOffset,
-                            const uint32_t* denseCounts, uint32_t denseShardCapacity, bool mayTraceUndecidedRaysItself = true, uint32_t bounce = 0u)
+static void launchTraceWide(RtgpuContext* c, const TraceStep& s)
 {
     // A block traces the rays its walk does not decide itself (rt_trace_wide.inl) where launches are short: a 1/8 shard of a full-HD frame gains 10 %
     // (ten launches per batch less to wait for), a full frame loses 1.4 % (a block holds its slot of the CU while one wave walks; the separate launch
@@ -142,10 +137,10 @@ static void launchTraceWide(RtgpuContext* c, hipStream_t stream, unsigned long l
     //  axis -- which walk alone for milliseconds and would hold a whole block's slot of the CU meanwhile: 16.5 -> 26 ms per pass, profiles/r04_vcm_wide_ab.txt, measured
     //  when the separate launch still handed them on to k_trace_monster; that hand-over is opt-in since round 5 (launchRetrace), the separate launch stays: it
     //  holds one block per CU instead of the traversal grid)
-    const bool localExact = mayTraceUndecidedRaysItself && c->traversalStackNeed <= 24u && (localExactEnv >= 0 ? localExactEnv != 0 : (c->localRetrace >= 0 ? c->localRetrace != 0 : (c->numSlots < 400000u || bounce >= localExactFromBounce)));   // (round 5, with re-trace launches that hand long rays on and share subtrees early: a 1/8 shard still gains 3 % from it, a 1/4 shard (518 k pixels) now LOSES 2 %, halves 0: profiles/r05_shard_policy.txt)
+    const bool localExact = s.mayTraceUndecidedRaysItself && c->traversalStackNeed <= 24u && (localExactEnv >= 0 ? localExactEnv != 0 : (c->localRetrace >= 0 ? c->localRetrace != 0 : (c->numSlots < 400000u || s.bounce >= localExactFromBounce)));   // (round 5, with re-trace launches that hand long rays on and share subtrees early: a 1/8 shard still gains 3 % from it, a 1/4 shard (518 k pixels) now LOSES 2 %, halves 0: profiles/r05_shard_policy.txt)
     const uint32_t chunkMin = knobs::wideChunkMin();   // tuning knob
-    WideTuning tune = { c->tune.refillMinIdle, c->tune.otherMinLanes, shadowOffset, exactQueue, exactCount, exactShadowQueue, exactShadowCount, denseCounts, denseShardCapacity,
-                        chunkMin < 64u ? 64u : chunkMin, localExact ? 1u : 0u, 0u };
+    WideTuning tune = { c->tune.refillMinIdle, c->tune.otherMinLanes, s.shadowOffset, s.exactQueue, s.exactCount, s.exactShadowQueue, s.exactShadowCount, s.denseCounts,
+                        s.denseShardCapacity, chunkMin < 64u ? 64u : chunkMin, localExact ? 1u : 0u, 0u };
     // test hook, read per launch: a wave whose work queue ran dry N loop iterations ago hands the rays it still walks -- hits half found, written through -- to the
     // re-trace launch (the stack-overflow path, which the benchmark frame never takes).  As a schedule it moves time, it does not save any: what k_trace_wide's drain
     // loses (-5.6 % at N = 8) the re-trace launches gain, with or without k_trace_monster behind them (profiles/r05_drain_abort_ab.txt)
@@ -160,26 +155,33 @@ static void launchTraceWide(RtgpuContext* c, hipStream_t stream, unsigned long l
     // surface are far from it); RTGPU_ANYHIT_FAR_FIRST=0: nearest first like closest-hit rays (read when the context is created: the tests run both orders)
     tune.anyHitFarFirst = c->anyHitFarFirst;
     const dim3 grid(traversalBlocks(c, 24u)), block(RT_BLOCK);
-    LaunchTimer t(c, stream, KC_TRACE);
+    LaunchTimer t(c, s.stream, KC_TRACE);
     if (c->wide.nodes == nullptr)
     {
         // a two-level scene (rt_trace_wide2.inl): held to five waves per SIMD (110 -> 96 VGPRs, 8 bytes of scratch: Cornell box trace -7 %, +2 % end to
         // end), 30 KB of LDS per block
-        hipLaunchKernelGGL((k_trace_wide2<24>), grid, block, 0, stream, c->sceneDev, c->wide2, paths, tq, tqc, tsq, tsc, cursor, counters, tune);
+        hipLaunchKernelGGL((k_trace_wide2<24>), grid, block, 0, s.stream, c->sceneDev, c->wide2, s.paths, s.queue, s.queueCount, s.shadowQueue, s.shadowCount, s.cursor, s.counters, tune);
         return;
     }
     const bool diag = knobs::wideDiag();       // walk statistics in the spare counters (tools/wide_diag.py)
     // the camera rays of a dense batch walk the tree as packets (rt_trace_packet.inl: a wave = an 8 x 8 pixel block, the node is uniform); RTGPU_PACKET=0: off
     const bool packets = knobs::packets();   // (read per launch: the tests switch it)
-    if (packets && !diag && bounce == 0u && denseCounts != nullptr && tsq == nullptr && tq == nullptr)
+    if (packets && !diag && s.bounce == 0u && s.denseCounts != nullptr && s.shadowQueue == nullptr && s.queue == nullptr)
     {
-        hipLaunchKernelGGL(k_trace_packet, dim3(c->numCUs * knobs::packetBlocksPerCU()), block, 0, stream, c->sceneDev, c->wide, paths, cursor, counters, tune);
+        hipLaunchKernelGGL(k_trace_packet, dim3(c->numCUs * knobs::packetBlocksPerCU()), block, 0, s.stream, c->sceneDev, c->wide, s.paths, s.cursor, s.counters, tune);
         return;
     }
     if (diag) tune.localExact = knobs::wideDiagMode();   // 2: stack-depth histogram instead of the visit counts (tools/wide_diag.py)
-    if (diag) hipLaunchKernelGGL((k_trace_wide<24, true, false>), grid, block, 0, stream, c->sceneDev, c->wide, paths, tq, tqc, tsq, tsc, cursor, counters, tune);
-    else if (localExact) hipLaunchKernelGGL((k_trace_wide<24, false, true>), grid, block, 0, stream, c->sceneDev, c->wide, paths, tq, tqc, tsq, tsc, cursor, counters, tune);
-    else hipLaunchKernelGGL((k_trace_wide<24, false, false>), grid, block, 0, stream, c->sceneDev, c->wide, paths, tq, tqc, tsq, tsc, cursor, counters, tune);
+#define RT_LAUNCH_TRACE_WIDE(D, L) hipLaunchKernelGGL((k_trace_wide<24, D, L>), grid, block, 0, s.stream, c->sceneDev, c->wide, s.paths, s.queue, s.queueCount, s.shadowQueue, s.shadowCount, s.cursor, s.counters, tune)
+    if (diag) RT_LAUNCH_TRACE_WIDE(true, false); else if (localExact) RT_LAUNCH_TRACE_WIDE(false, true); else RT_LAUNCH_TRACE_WIDE(false, false);
+#undef RT_LAUNCH_TRACE_WIDE
+}
+
+// what a 4-wide walk handed over, as the work of a step of its own
+static TraceStep handedOver(TraceStep s)
+{
+    s.queue = s.exactQueue; s.queueCount = s.exactCount; s.shadowQueue = s.exactShadowQueue; s.shadowCount = s.exactShadowCount; s.cursor = s.exactCursor;
+    return s;
 }
 
 // The re-trace launch behind a 4-wide walk: the reference's own walk (k_trace) over the rays the walk handed over (0.1 % of a launch), and -- single-mesh
@@ -187,26 +189,24 @@ static void launchTraceWide(RtgpuContext* c, hipStream_t stream, unsigned long l
 // two of three slab tests into inf - inf and the ray walks most of the tree, alone in its wave (1.0-1.6 ms launches at bounce 1 where an ordinary one
 // takes 0.1-0.2 ms, profiles/r04_timeline_serial.txt); a whole block finds the same hit cooperatively.  `overflowQueue`: a queue of the lane nobody
 // uses during this bounce's trace (dense path state: none of the slot queues is in use; slot-per-pixel: the one the next shade will fill).
-// `exactQueue` / `exactCount`, `exactShadowQueue` / `exactShadowCount`: what the 4-wide walk handed over; `exactCursor`: the launch's work cursor;
-// `overflowCount`: the count of `overflowQueue`.
-static void launchRetrace(RtgpuContext* c, hipStream_t stream, unsigned long long* counters, const Paths& paths, const uint32_t* exactQueue, const uint32_t* exactCount,
-                          const uint32_t* exactShadowQueue, const uint32_t* exactShadowCount, uint32_t* exactCursor, uint32_t* overflowQueue, uint32_t* overflowCount)
+// Its work is the hand-over of `s`; `s.overflowQueue` / `s.overflowCount`: null, or that queue and its count.
+static void launchRetrace(RtgpuContext* c, const TraceStep& s)
 {
     const int abortEnv = knobs::abortRetraceAfter();   // test hook, read per launch (0: every closest-hit ray in flight when its wave's queue runs dry goes to k_trace_monster)
     // OFF by default since the axis-parallel prune (boxNearDegenerateAxes) made the rays it was built for short: on the benchmark frame no ray is handed over any more,
     // and the EMPTY k_trace_monster launch behind every re-trace launch is not free under concurrency -- its 64 blocks of 512 threads / 33 KB LDS wait for CU slots that the other
     // lanes' persistent traversal kernels hold: 27.7 ms summed over the 40 launches of the driver's timed region (profiles/r05_concurrency.txt), 2 % end to end
     // (profiles/r05_monsters_under_concurrency_ab.txt).  RTGPU_RETRACE_MONSTERS=1 (or the test hook RTGPU_ABORT_RETRACE_AFTER) switches the hand-over on; read per launch.
-    const bool monsters = knobs::retraceMonsters() && overflowQueue != nullptr && overflowCount != nullptr && c->wide.nodes != nullptr && c->sceneDev.numObjects == 1u && !c->countIntersections;
+    const bool monsters = knobs::retraceMonsters() && s.overflowQueue != nullptr && s.overflowCount != nullptr && c->wide.nodes != nullptr && c->sceneDev.numObjects == 1u && !c->countIntersections;
     TravTuning exactTune = c->tune;
-    exactTune.overflowQueue = monsters ? overflowQueue : nullptr; exactTune.overflowCount = monsters ? overflowCount : nullptr;
+    exactTune.overflowQueue = monsters ? s.overflowQueue : nullptr; exactTune.overflowCount = monsters ? s.overflowCount : nullptr;
     exactTune.abortClosestAfter = abortEnv >= 0 ? (uint32_t)abortEnv : RT_ABORT_RETRACE_AFTER;
     exactTune.denseCounts = nullptr; exactTune.denseShardCapacity = 0u;
     // a re-trace launch's queue is dry after the first claim and its duration is its longest ray: an any-hit ray that slides along a wall it started on (a sun in a
     // coordinate plane: the ray lies IN the wall's plane, Moeller-Trumbore never accepts the coplanar triangles) walks ~170 nodes = 250 us alone.  Idle lanes take its
     // deferred subtrees after RT_RETRACE_SPLIT_AFTER drain iterations instead of the 32 of a full launch.
     exactTune.splitAfter = knobs::retraceSplitAfter() ? knobs::retraceSplitAfter() : RT_RETRACE_SPLIT_AFTER;   // tuning knob
-    LaunchTimer t(c, stream, KC_RETRACE);
+    LaunchTimer t(c, s.stream, KC_RETRACE);
     // one block per CU serves the usual few thousand requests; above 1024 requests per CU (exactTune.fullGridAbove = numCUs * 1024) the whole traversal grid works
     // (decided on the device from the counts)
     // (only where the scene can produce such queues -- a delta sun with an exactly-zero direction component, c->axisParallelSun: the 1024 extra blocks that read two
@@ -215,8 +215,19 @@ static void launchRetrace(RtgpuContext* c, hipStream_t stream, unsigned long lon
     const bool adaptiveGrid = gridEnv >= 0 ? gridEnv != 0 : c->axisParallelSun;
     exactTune.baseBlocks = adaptiveGrid ? c->numCUs : 0u; exactTune.fullGridAbove = c->numCUs * 256u * 4u;
     const dim3 retraceGrid(adaptiveGrid ? traversalBlocks(c, stackClassOf(c)) : c->numCUs);
-    launchTraceBinary(c, stream, retraceGrid, counters, paths, exactQueue, exactCount, exactShadowQueue, exactShadowCount, exactCursor, exactTune, false);
-    if (monsters) hipLaunchKernelGGL(k_trace_monster, dim3(64), dim3(RT_MONSTER_BLOCK), 0, stream, c->sceneDev, paths, overflowQueue, overflowCount);
+    launchTraceBinary(c, handedOver(s), retraceGrid, exactTune, false);
+    if (monsters) hipLaunchKernelGGL(k_trace_monster, dim3(64), dim3(RT_MONSTER_BLOCK), 0, s.stream, c->sceneDev, s.paths, s.overflowQueue, s.overflowCount);
+}
+
+// One trace step of a launch sequence.  `wide` (the render sequences: useWide(c)): the 4-wide tree serves the launch; what it does not trust goes through the
+// binary-tree kernel right behind it (a small grid: few rays).  Otherwise the reference's binary walk on the full traversal grid, counting where the context
+// counts or s.rayCounts is asked for.
+static void launchTraceStep(RtgpuContext* c, const TraceStep& s, bool wide)
+{
+    if (wide) { launchTraceWide(c, s); launchRetrace(c, s); return; }
+    TravTuning tune = c->tune; tune.shadowOffset = s.shadowOffset; tune.denseCounts = s.denseCounts; tune.denseShardCapacity = s.denseShardCapacity; tune.rayCounts = s.rayCounts;
+    LaunchTimer t(c, s.stream, KC_TRACE);
+    launchTraceBinary(c, s, dim3(traversalBlocks(c, stackClassOf(c))), tune, s.rayCounts != nullptr || c->countIntersections);
 }
 
 // The bounce at which a dense batch hands its remaining paths to k_tail (0: never).  RTGPU_TAIL_DEPTH=n forces bounce n (0: off).
@@ -279,23 +290,11 @@ static int submitDenseBatch(RtgpuContext* c, BatchLane& l, const LaneCounts& cou
         const bool haveClosest = depth <= maxRayDepth, haveShadow = depth > 0 && haveNee;
         if (haveClosest || haveShadow)
         {
-            TravTuning tune = c->tune;
-            tune.denseCounts = haveClosest ? l.denseCounts + (size_t)plane * depth : nullptr; tune.denseShardCapacity = shardCapacity;
-            const uint32_t* tsq = haveShadow ? l.shadowQueues[(depth - 1u) & 1u] : nullptr;
-            const uint32_t* tsc = haveShadow ? counts.shadowCounts + (depth - 1u) : nullptr;
-            if (useWide(c))
-            {
-                // the 4-wide tree serves the launch; what it does not trust goes through the binary-tree kernel right behind it (a small grid: few rays)
-                launchTraceWide(c, l.stream, c->counters, in, nullptr, nullptr, tsq, tsc, counts.cursors + depth, l.exactQueue, counts.exactCounts + depth, l.exactShadowQueue,
-                                counts.exactShadowCounts + depth, 0.0001f, tune.denseCounts, shardCapacity, true, depth);
-                launchRetrace(c, l.stream, c->counters, in, l.exactQueue, counts.exactCounts + depth, l.exactShadowQueue, counts.exactShadowCounts + depth, counts.exactCursors + depth,
-                              l.queues[0], counts.overflowCounts + depth);
-            }
-            else
-            {
-                LaunchTimer t(c, l.stream, KC_TRACE);
-                launchTraceBinary(c, l.stream, dim3(traversalBlocks(c, stackClassOf(c))), c->counters, in, nullptr, nullptr, tsq, tsc, counts.cursors + depth, tune, c->countIntersections);
-            }
+            TraceStep s = { l.stream, c->counters, in };
+            counts.queuesOf(s, depth, false, haveShadow);   // (the closest-hit rays are the arena's live paths: no queue)
+            counts.handOverOf(s, depth, l.queues[0]);       // (none of the slot queues is in use)
+            s.denseCounts = haveClosest ? l.denseCounts + (size_t)plane * depth : nullptr; s.denseShardCapacity = shardCapacity; s.bounce = depth;
+            launchTraceStep(c, s, useWide(c));
         }
         // bounce `depth`: shades the live paths; folds the visibility results of the previous bounce's zombies in (the last round does only that)
         const DenseCounts dc = { l.denseCounts + (size_t)plane * depth, l.denseCounts + (size_t)plane * (depth + 1u), shardCapacity, c->deviceFlags,
@@ -311,6 +310,26 @@ static int submitDenseBatch(RtgpuContext* c, BatchLane& l, const LaneCounts& cou
 #undef RT_LAUNCH_SHADE_DENSE
 #undef RT_LAUNCH_TAIL
 
+// The bounces of a slot-per-pixel sequence on lane `l` (a batch lane or the recorder's), after its k_generate.  Bounce k: trace {closest-hit rays of bounce k,
+// next-event rays of bounce k - 1} -> shade(k); one last trace for the next-event rays of the final bounce.  A bounce's overflow queue: the one its shade will fill.
+template <class Shade>
+static void launchSlotBounces(RtgpuContext* c, hipStream_t stream, unsigned long long* counters, const BatchLane& l, const LaneCounts& counts, uint32_t maxRayDepth, uint32_t lastDepth,
+                              bool haveNee, Shade shade)
+{
+    for (uint32_t depth = 0; depth <= lastDepth; ++depth)
+    {
+        const bool haveClosest = depth <= maxRayDepth, haveShadow = depth > 0 && haveNee;
+        if (haveClosest || haveShadow)
+        {
+            TraceStep s = { stream, counters, l.paths };
+            counts.queuesOf(s, depth, haveClosest, haveShadow);
+            counts.handOverOf(s, depth, l.queues[(depth + 1u) & 1u]);
+            launchTraceStep(c, s, useWide(c));
+        }
+        if (haveClosest) shade(depth);
+    }
+}
+
 #define RT_LAUNCH_SHADE(...) hipLaunchKernelGGL((k_shade<__VA_ARGS__>), grid, block, 0, l.stream, c->sceneDev, passesDev, c->numSlots, l.paths, l.queues[depth & 1u], counts.pathCounts + depth, \
                                              l.queues[(depth + 1u) & 1u], counts.pathCounts + depth + 1, l.shadowQueues[depth & 1u], counts.shadowCounts + depth, c->counters)
 
@@ -322,42 +341,14 @@ static void submitSlotBatch(RtgpuContext* c, BatchLane& l, const LaneCounts& cou
         LaunchTimer t(c, l.stream, KC_GENERATE);
         hipLaunchKernelGGL(k_generate, grid, block, 0, l.stream, c->sceneDev, passesDev, c->numSlots, l.paths, c->slotPixel, totalSlots, l.queues[0], counts.pathCounts + 0, c->counters);
     }
-    // bounce k: trace {closest rays of bounce k, NEE rays of bounce k-1} -> shade k; one last trace for the NEE rays of
-    // the final bounce
-    const uint32_t lastDepth = c->debugMode >= 0 ? 0u : maxRayDepth + 1u;
-    for (uint32_t depth = 0; depth <= lastDepth; ++depth)
+    launchSlotBounces(c, l.stream, c->counters, l, counts, maxRayDepth, c->debugMode >= 0 ? 0u : maxRayDepth + 1u, c->numLights != 0 && !c->plainPathTracer, [&](uint32_t depth)
     {
-        const bool haveClosest = depth <= maxRayDepth;
-        const bool haveShadow = depth > 0 && c->numLights != 0 && !c->plainPathTracer;
-        if (haveClosest || haveShadow)
-        {
-            const uint32_t* tq = haveClosest ? l.queues[depth & 1u] : nullptr;
-            const uint32_t* tqc = haveClosest ? counts.pathCounts + depth : nullptr;
-            const uint32_t* tsq = haveShadow ? l.shadowQueues[(depth - 1u) & 1u] : nullptr;
-            const uint32_t* tsc = haveShadow ? counts.shadowCounts + (depth - 1u) : nullptr;
-            if (useWide(c))
-            {
-                // the re-encoded tree serves the launch; what it does not trust goes through the binary-tree kernel right behind it
-                launchTraceWide(c, l.stream, c->counters, l.paths, tq, tqc, tsq, tsc, counts.cursors + depth, l.exactQueue, counts.exactCounts + depth, l.exactShadowQueue,
-                                counts.exactShadowCounts + depth, 0.0001f, nullptr, 0u);
-                launchRetrace(c, l.stream, c->counters, l.paths, l.exactQueue, counts.exactCounts + depth, l.exactShadowQueue, counts.exactShadowCounts + depth, counts.exactCursors + depth,
-                              l.queues[(depth + 1u) & 1u], counts.overflowCounts + depth);
-            }
-            else
-            {
-                LaunchTimer t(c, l.stream, KC_TRACE);
-                launchTraceBinary(c, l.stream, dim3(traversalBlocks(c, stackClassOf(c))), c->counters, l.paths, tq, tqc, tsq, tsc, counts.cursors + depth, c->tune, c->countIntersections);
-            }
-        }
-        if (haveClosest)
-        {
-            LaunchTimer t(c, l.stream, KC_SHADE);
-            if (c->debugMode >= 0)
-                hipLaunchKernelGGL(k_debug_shade, grid, block, 0, l.stream, c->sceneDev, l.paths, l.queues[0], counts.pathCounts + 0, (uint32_t)c->debugMode, c->counters);
-            else if (c->plainPathTracer) RT_LAUNCH_SHADE(false, true);
-            else if (c->leanScene == 1) RT_LAUNCH_SHADE(true); else RT_LAUNCH_SHADE(false);
-        }
-    }
+        LaunchTimer t(c, l.stream, KC_SHADE);
+        if (c->debugMode >= 0)
+            hipLaunchKernelGGL(k_debug_shade, grid, block, 0, l.stream, c->sceneDev, l.paths, l.queues[0], counts.pathCounts + 0, (uint32_t)c->debugMode, c->counters);
+        else if (c->plainPathTracer) RT_LAUNCH_SHADE(false, true);
+        else if (c->leanScene == 1) RT_LAUNCH_SHADE(true); else RT_LAUNCH_SHADE(false);
+    });
 }
 #undef RT_LAUNCH_SHADE
 
@@ -422,7 +413,7 @@ static int flushBatch(RtgpuContext* c, uint32_t maxPasses)
     const dim3 grid(blocksNeeded < maxBlocks ? blocksNeeded : maxBlocks), pixelGrid(pixelBlocks < maxBlocks ? pixelBlocks : maxBlocks), block(RT_BLOCK);
     const LaneCounts counts(l);
 
-    HIP_TRY(hipMemsetAsync(l.queueCounts, 0, (size_t)8 * l.queueCountCapacity * sizeof(uint32_t), l.stream));
+    HIP_TRY(hipMemsetAsync(l.queueCounts, 0, laneCountBytes(l), l.stream));
     const bool dense = c->denseAllowed && c->debugMode < 0 && maxLights <= RT_DENSE_MAX_LIGHTS && l.paths2.base != nullptr;
     const bool denseAll = dense && first.lightSamplingStrategy == RT_LIGHT_SAMPLING_ALL && !c->plainPathTracer;
     if (dense) { r = submitDenseBatch(c, l, counts, passesDev, totalSlots, first.maxRayDepth, denseAll, grid); if (r) return r; }

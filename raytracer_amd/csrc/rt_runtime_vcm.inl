@@ -78,6 +78,7 @@ static int ensureVcm(RtgpuContext* c, uint32_t maxLV, uint32_t batch)
 static void launchTrace(RtgpuContext* c, hipStream_t stream, const Paths& paths, const uint32_t* tq, const uint32_t* tqc, const uint32_t* tsq, const uint32_t* tsc, uint32_t* cursor,
                         float shadowOffset = 0.0001f, uint32_t* overflowQueue = nullptr, uint32_t* overflowCount = nullptr)
 {
+    TraceStep s = { stream, c->counters, paths, tq, tqc, tsq, tsc, cursor }; s.shadowOffset = shadowOffset; s.mayTraceUndecidedRaysItself = false;
     TravTuning tune = c->tune; tune.shadowOffset = shadowOffset;
     const bool monsters = overflowQueue && tq && !c->countIntersections && c->sceneDev.numObjects == 1u;
     tune.overflowQueue = monsters ? overflowQueue : nullptr; tune.overflowCount = monsters ? overflowCount : nullptr;
@@ -92,13 +93,13 @@ static void launchTrace(RtgpuContext* c, hipStream_t stream, const Paths& paths,
         // what the wide walk does not decide goes through the binary-tree kernel below, which keeps its hand-over of degenerate closest-hit rays to
         // k_trace_monster
         const uint32_t k = v.traceSerial++;
-        uint32_t* exactCount = vcmCounts(v, VCP_EXACT) + k; uint32_t* exactShadowCount = vcmCounts(v, VCP_EXACT_SHADOWS) + k;
-        launchTraceWide(c, stream, c->counters, paths, tq, tqc, tsq, tsc, cursor, v.exactQueue, exactCount, v.exactShadowQueue, exactShadowCount, shadowOffset, nullptr, 0u, false);
-        tq = v.exactQueue; tqc = exactCount; tsq = v.exactShadowQueue; tsc = exactShadowCount; cursor = vcmCounts(v, VCP_EXACT_CURSORS) + k;
+        s.exactQueue = v.exactQueue; s.exactCount = vcmCounts(v, VCP_EXACT) + k; s.exactShadowQueue = v.exactShadowQueue; s.exactShadowCount = vcmCounts(v, VCP_EXACT_SHADOWS) + k; s.exactCursor = vcmCounts(v, VCP_EXACT_CURSORS) + k;
+        launchTraceWide(c, s);
+        s = handedOver(s);
         travGrid = dim3(c->numCUs);
     }
     LaunchTimer t(c, stream, KC_TRACE);
-    launchTraceBinary(c, stream, travGrid, c->counters, paths, tq, tqc, tsq, tsc, cursor, tune, c->countIntersections);
+    launchTraceBinary(c, s, travGrid, tune, c->countIntersections);
     if (monsters) hipLaunchKernelGGL(k_trace_monster, dim3(64), dim3(RT_MONSTER_BLOCK), 0, stream, c->sceneDev, paths, overflowQueue, overflowCount);
 }
 

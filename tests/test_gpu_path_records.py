@@ -10,6 +10,7 @@ import time
 import numpy as np
 import pytest
 
+import oracle_lib
 import path_records_ref as ref
 import raytracer_amd as ra
 from raytracer_amd import scenes
@@ -67,6 +68,35 @@ def test_device_records_equal_the_oracles(built, walk, name):
         compared += v.size
         masked += int(mask.sum())
     assert masked * 2 < compared, "the mask covers %d of %d words" % (masked, compared)
+
+
+@pytest.mark.parametrize("name", ["sponza_class", "cornell_box"])
+def test_device_records_equal_the_oracles_on_the_binary_walk_without_counters(built, monkeypatch, name):
+    """RTGPU_WIDE=0 / RTGPU_WIDE2=0 with the intersection counters off: the recorder's trace steps take the reference's binary walk (k_trace) without the
+    counting code -- the one walk the `walk` cases above do not reach (they take the 4-wide walks or the counting k_trace).  Two passes, every pixel, depth 3;
+    the bar of the test above."""
+    monkeypatch.setenv("RTGPU_WIDE", "0")
+    monkeypatch.setenv("RTGPU_WIDE2", "0")
+    w, h = (96, 54) if name == "sponza_class" else (64, 48)
+    scene, camera = scenes.sponza_class(w / h, 6000) if name == "sponza_class" else scenes.cornell_box(w / h)
+    bn = ra.load_blue_noise()
+    scene.desc.contents.blueNoise = bn.ctypes.data
+    vp = ra.Viewport(w, h, seed=4242, max_ray_depth=3)
+    vp.set_renderer(scene)
+    desc = scene.desc.contents
+    pixels = ref.all_pixels(w, h)
+    for _ in range(2):
+        p = vp.next_pass_params(camera)
+        got = vp.record_paths(p, pixels)
+        assert len(got) == w * h
+        for (x, y), (v, reason, radiance) in zip(pixels, got):
+            ov = oracle_lib.render_pixel_paths(scene.desc, p, w, h, x, y, capacity=5)
+            assert len(v) == len(ov), "pixel (%d, %d): %d vertices, the oracle has %d" % (x, y, len(v), len(ov))
+            mask = ref.stale_mask(ov, desc)
+            assert not ((v.view(np.uint32) != ov.view(np.uint32)) & ~mask).any(), "pixel (%d, %d): a record differs from the oracle's" % (x, y)
+            assert not v[mask].view(np.uint32).any(), "pixel (%d, %d): a stale field is not zero" % (x, y)
+            assert same_words(radiance, oracle_lib.render_pixel(scene.desc, p, w, h, x, y)[:3]), "pixel (%d, %d): radiance" % (x, y)
+            assert 1 <= reason <= 6 and reason_agrees_with_last_record(v, reason), "pixel (%d, %d): reason %d" % (x, y, reason)
 
 
 # ---- 2. recording against rendering --------------------------------------------------------------------------------------------------------
