@@ -736,6 +736,59 @@ int rtgpu_denoise(RtgpuContext* ctx, const RtDenoiseParams* params, const RtPass
 /* outRGB: device memory, 16-byte aligned; the guide render and the filter are ordered on `stream` as above.  The passes rendered after the
  * call wait for its read of the sum buffer. */
 int rtgpu_denoise_async(RtgpuContext* ctx, const RtDenoiseParams* params, const RtPassParams* guideParams, float* outRGB, void* stream);
+
+/* ---------------------------------------------------------------------------------------------
+ * Variance-guided denoise: the a-trous filter above with the luminance edge-stop of SVGF (Schied et al. 2017) in place of the colour one.  The
+ * film's two sums -- every pass, and every second pass -- give two estimates of a pixel, a = sum / n and b = 2 * secondary / n, and (a - b)^2 is the
+ * variance of the mean (the quantity rtgpu_compute_block_errors takes the root of).  A tap's luminance distance is measured against the local
+ * standard deviation, and the variance is filtered alongside the colour: a converged pixel keeps its shadow edges, a noisy one gives its fireflies
+ * away.  Everything not restated here is as in rtgpu_filter_atrous: validity, invN, invP, xn, xp, h, the tap order, the f32 arithmetic with every
+ * multiply and add rounded on its own, sums left to right as written.  tests/denoise_var_ref.py is the same text in NumPy float32.
+ *   inputs     as above, and colorHalf: H x W x 3 f32 interleaved, the sum over half of the samples (the film's secondary buffer).
+ *   constants  sL2 = sigmaLum * sigmaLum.
+ *   luminance  lum(c) = ((c0 + 2 * c1) + c2) * 0.25f
+ *   prepare    c_k = color_k * colorScale and b_k = colorHalf_k * (2 * colorScale), both divided by d_k under RT_DENOISE_DEMODULATE as above;
+ *              e = lum(c) - lum(b), v = e * e (exact for an even number of passes); an invalid pixel gets v = 0.
+ *   level s    (step = 1 << s) an invalid pixel copies c and v.  A valid pixel p:
+ *              the local variance: gsum = 0, gw = 0; for j = -1 .. 1 (outermost), i = -1 .. 1: q = p + (i, j) -- NOT spread by step --, skipped when
+ *                  outside the frame or invalid; k = gk[|i|] * gk[|j|] with gk = {0.5, 0.25}; gsum = gsum + k * v_q; gw = gw + k.
+ *                  g = gsum / gw (the centre is always taken); denom = g * sL2 + varianceFloor.
+ *              the 25 taps, spread by step, as above, with
+ *                  dl = lum(c_p) - lum(c_q);  xc = (dl * dl) / denom
+ *                  x  = (xn * invN + xp * invP) + xc
+ *                  u and w as above;  acc_k = acc_k + w * c_q,k;  vacc = vacc + (w * w) * v_q;  wsum = wsum + w
+ *              the result: c_k = acc_k / wsum, v = vacc / (wsum * wsum); both stay as they are when wsum == 0.
+ *              There is no per-level schedule of sigmaLum: the variance shrinks from level to level, and that does its job.
+ *   finish     out_k = c_k * d_k; outVariance = v, H x W f32 (optional: may be NULL).
+ *   NaN, inf   follow from the operations: a NaN denom or xc gives the tap weight 0 through fmaxf.
+ *   errors     as above, and a sigmaLum or varianceFloor that is not finite or <= 0, or a NULL colorHalf: RTGPU_ERR_INVALID_ARGUMENT.
+ * The four entries mirror the four above: the same stream, alignment (outVariance too) and overlap rules (no output overlaps an input or the other
+ * output).  rtgpu_denoise_var filters the context's sum and secondary buffers (a multi-device context: the gathered ones); it is not a pass either,
+ * and the passes rendered after an _async call wait for its read of both buffers.  The variance travels in the fourth lane of the colour records:
+ * the scratch stays at 64 bytes per pixel.
+ * --------------------------------------------------------------------------------------------- */
+/* 32 bytes */
+typedef struct RtDenoiseVarParams
+{
+    uint32_t iterations;     /* 1..8 levels */
+    uint32_t flags;          /* RT_DENOISE_DEMODULATE */
+    float    colorScale;
+    float    sigmaLum;       /* luminance distance in standard deviations; the wrappers' default is 4 */
+    float    sigmaNormal;
+    float    sigmaPlane;
+    float    varianceFloor;  /* added to g * sL2: what a distance is measured against where the two halves agree; default 1e-10 */
+    uint32_t _pad;
+} RtDenoiseVarParams;
+int rtgpu_filter_atrous_var(RtgpuContext* ctx, const RtDenoiseVarParams* params, uint32_t width, uint32_t height, const float* color,
+                            const float* colorHalf, const float* depth, const float* normal, const float* position, const float* albedo,
+                            float* outRGB, float* outVariance);
+int rtgpu_filter_atrous_var_async(RtgpuContext* ctx, const RtDenoiseVarParams* params, uint32_t width, uint32_t height, const float* color,
+                                  const float* colorHalf, const float* depth, const float* normal, const float* position, const float* albedo,
+                                  float* outRGB, float* outVariance, void* stream);
+int rtgpu_denoise_var(RtgpuContext* ctx, const RtDenoiseVarParams* params, const RtPassParams* guideParams, float* outRGB, float* outVariance);
+int rtgpu_denoise_var_async(RtgpuContext* ctx, const RtDenoiseVarParams* params, const RtPassParams* guideParams, float* outRGB,
+                            float* outVariance, void* stream);
+
 /* rtgpu_postprocess over a caller's image (host memory, height x width x 3 floats of the context's size) in place of the sum buffer -- a
  * denoised frame, say: the same kernels, the same restrictions, and the same bits for the same input. */
 int rtgpu_postprocess_from(RtgpuContext* ctx, const RtPostprocessParams* params, const float* rgbHost, uint32_t* frontBufferBGRA);

@@ -227,6 +227,23 @@ def denoise_params(iterations=5, sigma_color=DENOISE_DEFAULTS["sigma_color"], si
     return p
 
 
+class RtDenoiseVarParams(C.Structure):
+    _fields_ = [("iterations", C.c_uint32), ("flags", C.c_uint32), ("colorScale", C.c_float), ("sigmaLum", C.c_float), ("sigmaNormal", C.c_float),
+                ("sigmaPlane", C.c_float), ("varianceFloor", C.c_float), ("_pad", C.c_uint32)]
+
+
+# the variance-guided filter's own defaults: luminance within four standard deviations; a floor far below any variance a render produces
+DENOISE_VAR_DEFAULTS = dict(sigma_lum=4.0, variance_floor=1e-10)
+
+
+def denoise_var_params(iterations=5, sigma_lum=DENOISE_VAR_DEFAULTS["sigma_lum"], sigma_normal=DENOISE_DEFAULTS["sigma_normal"],
+                       sigma_plane=DENOISE_DEFAULTS["sigma_plane"], variance_floor=DENOISE_VAR_DEFAULTS["variance_floor"], color_scale=1.0, demodulate=True):
+    p = RtDenoiseVarParams()
+    p.iterations, p.flags = int(iterations), RT_DENOISE_DEMODULATE if demodulate else 0
+    p.colorScale, p.sigmaLum, p.sigmaNormal, p.sigmaPlane, p.varianceFloor = float(color_scale), float(sigma_lum), float(sigma_normal), float(sigma_plane), float(variance_floor)
+    return p
+
+
 _filter_contexts = {}
 
 
@@ -271,15 +288,24 @@ _filter_streams = {}
 
 
 def atrous_filter(color, depth, normal, position, albedo=None, iterations=5, sigma_color=DENOISE_DEFAULTS["sigma_color"],
-                  sigma_normal=DENOISE_DEFAULTS["sigma_normal"], sigma_plane=DENOISE_DEFAULTS["sigma_plane"], color_scale=1.0, demodulate=True, ctx=None):
+                  sigma_normal=DENOISE_DEFAULTS["sigma_normal"], sigma_plane=DENOISE_DEFAULTS["sigma_plane"], color_scale=1.0, demodulate=True, ctx=None,
+                  color_half=None, sigma_lum=DENOISE_VAR_DEFAULTS["sigma_lum"], variance_floor=DENOISE_VAR_DEFAULTS["variance_floor"], return_variance=False):
     """The edge-avoiding a-trous filter of include/rtgpu.h over a frame: color (H, W, 3), depth (H, W) or (1, H, W), normal, position and albedo (3, H, W)
     -- the layouts of Viewport.sum_buffer() and Viewport.render_aovs() -- as float32 NumPy arrays, or as contiguous float32 torch tensors on a ROCm device
     (then the filter runs on torch.cuda.current_stream() without a host copy and returns a tensor).  Returns the (H, W, 3) image.  albedo is needed with
     demodulate=True only.  `ctx`: a device context to run on (default: one of the module's own per device, which keeps its scratch -- 64 bytes per pixel,
     twice that on the NumPy path -- until release_filter_contexts()).  Not thread-safe: the calls on one context share that scratch and are ordered by the
-    library's events from one host thread; callers on several threads serialise their calls or pass contexts of their own."""
+    library's events from one host thread; callers on several threads serialise their calls or pass contexts of their own.
+
+    color_half (H, W, 3), the sum over half of the samples (Viewport.sum_buffer(secondary=True)[1]), selects the variance-guided filter
+    (rtgpu_filter_atrous_var): sigma_lum and variance_floor take sigma_color's place, and return_variance=True returns (image, the (H, W) variance)."""
     torch = None
+    variance = color_half is not None
+    if return_variance and not variance:
+        raise ValueError("return_variance=True needs color_half")
     planes = dict(color=color, depth=depth, normal=normal, position=position)
+    if variance:
+        planes["color_half"] = color_half
     if demodulate:
         if albedo is None:
             raise ValueError("demodulate=True needs the albedo plane")
@@ -289,7 +315,7 @@ def atrous_filter(color, depth, normal, position, albedo=None, iterations=5, sig
     if getattr(color, "ndim", 0) != 3 or color.shape[2] != 3:
         raise ValueError("color must be an (H, W, 3) float32 array or tensor")
     h, w = int(color.shape[0]), int(color.shape[1])
-    shapes = dict(color=((h, w, 3),), depth=((h, w), (1, h, w)), normal=((3, h, w),), position=((3, h, w),), albedo=((3, h, w),))
+    shapes = dict(color=((h, w, 3),), color_half=((h, w, 3),), depth=((h, w), (1, h, w)), normal=((3, h, w),), position=((3, h, w),), albedo=((3, h, w),))
     for name, a in planes.items():
         if torch is None:
             ok = isinstance(a, np.ndarray) and a.dtype == np.float32
@@ -298,14 +324,24 @@ def atrous_filter(color, depth, normal, position, albedo=None, iterations=5, sig
         if not ok or tuple(a.shape) not in shapes[name]:
             raise ValueError("%s must be a float32 %s of shape %s%s" % (name, "NumPy array" if torch is None else "tensor on the colour's ROCm device",
                                                                         " or ".join(str(t) for t in shapes[name]), "" if torch is None else " (all arrays or all tensors)"))
-    p = denoise_params(iterations, sigma_color, sigma_normal, sigma_plane, color_scale, demodulate)
+    if variance:
+        p = denoise_var_params(iterations, sigma_lum, sigma_normal, sigma_plane, variance_floor, color_scale, demodulate)
+    else:
+        p = denoise_params(iterations, sigma_color, sigma_normal, sigma_plane, color_scale, demodulate)
     lib = rtgpu_lib()
+    out_variance = None
     if torch is None:
         planes = {name: np.ascontiguousarray(a) for name, a in planes.items()}
         out = np.zeros((h, w, 3), dtype=np.float32)
         ptr = lambda name: planes[name].ctypes.data_as(C.c_void_p) if name in planes else None   # noqa: E731
-        r = lib.rtgpu_filter_atrous(ctx if ctx is not None else _filter_context(0), C.byref(p), C.c_uint32(w), C.c_uint32(h), ptr("color"), ptr("depth"), ptr("normal"),
-                                    ptr("position"), ptr("albedo"), out.ctypes.data_as(C.c_void_p))
+        context = ctx if ctx is not None else _filter_context(0)
+        if variance:
+            out_variance = np.zeros((h, w), dtype=np.float32) if return_variance else None
+            r = lib.rtgpu_filter_atrous_var(context, C.byref(p), C.c_uint32(w), C.c_uint32(h), ptr("color"), ptr("color_half"), ptr("depth"), ptr("normal"), ptr("position"),
+                                            ptr("albedo"), out.ctypes.data_as(C.c_void_p), out_variance.ctypes.data_as(C.c_void_p) if return_variance else None)
+        else:
+            r = lib.rtgpu_filter_atrous(context, C.byref(p), C.c_uint32(w), C.c_uint32(h), ptr("color"), ptr("depth"), ptr("normal"),
+                                        ptr("position"), ptr("albedo"), out.ctypes.data_as(C.c_void_p))
     else:
         device = color.device
         index = device.index if device.index is not None else torch.cuda.current_device()
@@ -315,12 +351,18 @@ def atrous_filter(color, depth, normal, position, albedo=None, iterations=5, sig
         out = torch.empty((h, w, 3), dtype=torch.float32, device=device)
         ptr = lambda name: C.c_void_p(planes[name].data_ptr()) if name in planes else None   # noqa: E731
         context = ctx if ctx is not None else _filter_context(index)
-        r = _run_on_torch_stream(torch, _filter_streams, device, list(planes.values()) + [out], lambda stream: lib.rtgpu_filter_atrous_async(
-            context, C.byref(p), C.c_uint32(w), C.c_uint32(h), ptr("color"), ptr("depth"), ptr("normal"), ptr("position"), ptr("albedo"), C.c_void_p(out.data_ptr()), stream))
+        if variance:
+            out_variance = torch.empty((h, w), dtype=torch.float32, device=device) if return_variance else None
+            r = _run_on_torch_stream(torch, _filter_streams, device, list(planes.values()) + [out, out_variance], lambda stream: lib.rtgpu_filter_atrous_var_async(
+                context, C.byref(p), C.c_uint32(w), C.c_uint32(h), ptr("color"), ptr("color_half"), ptr("depth"), ptr("normal"), ptr("position"), ptr("albedo"),
+                C.c_void_p(out.data_ptr()), C.c_void_p(out_variance.data_ptr()) if return_variance else None, stream))
+        else:
+            r = _run_on_torch_stream(torch, _filter_streams, device, list(planes.values()) + [out], lambda stream: lib.rtgpu_filter_atrous_async(
+                context, C.byref(p), C.c_uint32(w), C.c_uint32(h), ptr("color"), ptr("depth"), ptr("normal"), ptr("position"), ptr("albedo"), C.c_void_p(out.data_ptr()), stream))
     if r != 0:
         err = (lib.rtgpu_last_error() or b"").decode()
         raise (ValueError if r == -1 else RuntimeError)("atrous_filter failed (%d): %s" % (r, err))
-    return out
+    return (out, out_variance) if return_variance else out
 
 
 BSDF_NAMES = ("null", "diffuse", "roughDiffuse", "dielectric", "roughDielectric", "metal", "roughMetal", "plastic", "roughPlastic")
@@ -902,11 +944,16 @@ class Viewport:
 
     # ---- denoise (include/rtgpu.h: rtgpu_denoise / rtgpu_denoise_async, rtgpu_postprocess_from) ------------------------------------------------------
     def denoise(self, params, iterations=5, sigma_color=DENOISE_DEFAULTS["sigma_color"], sigma_normal=DENOISE_DEFAULTS["sigma_normal"],
-                sigma_plane=DENOISE_DEFAULTS["sigma_plane"], color_scale=None, demodulate=True, device=False):
+                sigma_plane=DENOISE_DEFAULTS["sigma_plane"], color_scale=None, demodulate=True, device=False, variance=False,
+                sigma_lum=DENOISE_VAR_DEFAULTS["sigma_lum"], variance_floor=DENOISE_VAR_DEFAULTS["variance_floor"], return_variance=False):
         """The frame rendered so far through the a-trous filter of include/rtgpu.h, guided by the depth, normal, position and base-colour planes of the pass
         `params` (an RtPassParams from next_pass_params(), as render_aovs takes it): the (H, W, 3) float32 image, sum_buffer() * color_scale filtered.
         color_scale defaults to 1 / max(1, passes_finished).  device=True: a torch tensor on the renderer's ROCm device, produced on
-        torch.cuda.current_stream() without a host copy.  The call is not a pass: film, sum buffers and counters stay as they are."""
+        torch.cuda.current_stream() without a host copy.  The call is not a pass: film, sum buffers and counters stay as they are.
+        variance=True: the variance-guided filter (rtgpu_denoise_var) over the sum and the secondary sum buffer, with sigma_lum and variance_floor in
+        sigma_color's place; return_variance=True then returns (image, the (H, W) variance of the filtered luminance)."""
+        if return_variance and not variance:
+            raise ValueError("return_variance=True needs variance=True")
         if not isinstance(params, RtPassParams):
             raise TypeError("denoise takes the RtPassParams of next_pass_params(camera), not %s" % type(params).__name__)
         if not self.has_renderer:
@@ -914,23 +961,37 @@ class Viewport:
         ctx = self.device_context()
         if not ctx.value or host_lib().rth_viewport_upload_scene(self._h) != 0:
             raise RuntimeError("the viewport's renderer has no device context or its scene could not be uploaded: %s" % (rtgpu_lib().rtgpu_last_error() or b"").decode())
-        p = denoise_params(iterations, sigma_color, sigma_normal, sigma_plane, 1.0 / max(1, self.passes_finished) if color_scale is None else color_scale, demodulate)
+        scale = 1.0 / max(1, self.passes_finished) if color_scale is None else color_scale
+        if variance:
+            p = denoise_var_params(iterations, sigma_lum, sigma_normal, sigma_plane, variance_floor, scale, demodulate)
+        else:
+            p = denoise_params(iterations, sigma_color, sigma_normal, sigma_plane, scale, demodulate)
         lib = rtgpu_lib()
+        out_variance = None
         if not device:
             out = np.zeros((self.height, self.width, 3), dtype=np.float32)
-            r = lib.rtgpu_denoise(ctx, C.byref(p), C.byref(params), out.ctypes.data_as(C.c_void_p))
+            if variance:
+                out_variance = np.zeros((self.height, self.width), dtype=np.float32) if return_variance else None
+                r = lib.rtgpu_denoise_var(ctx, C.byref(p), C.byref(params), out.ctypes.data_as(C.c_void_p), out_variance.ctypes.data_as(C.c_void_p) if return_variance else None)
+            else:
+                r = lib.rtgpu_denoise(ctx, C.byref(p), C.byref(params), out.ctypes.data_as(C.c_void_p))
         else:
             import torch
             dev = torch.device("cuda", multi_info(ctx)["devices"][0])
             out = torch.empty((self.height, self.width, 3), dtype=torch.float32, device=dev)
             if getattr(self, "_denoise_streams", None) is None:
                 self._denoise_streams = {}
-            r = _run_on_torch_stream(torch, self._denoise_streams, dev, [out],
-                                     lambda stream: lib.rtgpu_denoise_async(ctx, C.byref(p), C.byref(params), C.c_void_p(out.data_ptr()), stream))
+            if variance:
+                out_variance = torch.empty((self.height, self.width), dtype=torch.float32, device=dev) if return_variance else None
+                r = _run_on_torch_stream(torch, self._denoise_streams, dev, [out, out_variance], lambda stream: lib.rtgpu_denoise_var_async(
+                    ctx, C.byref(p), C.byref(params), C.c_void_p(out.data_ptr()), C.c_void_p(out_variance.data_ptr()) if return_variance else None, stream))
+            else:
+                r = _run_on_torch_stream(torch, self._denoise_streams, dev, [out],
+                                         lambda stream: lib.rtgpu_denoise_async(ctx, C.byref(p), C.byref(params), C.c_void_p(out.data_ptr()), stream))
         if r != 0:
             err = (lib.rtgpu_last_error() or b"").decode()
             raise (ValueError if r == -1 else RuntimeError)("denoise failed (%d): %s" % (r, err))
-        return out
+        return (out, out_variance) if return_variance else out
 
     def front_buffer_from(self, image, exposure=0.0, contrast=0.8, saturation=0.98, dithering=0.005, tonemapper=3, color_filter=(1.0, 1.0, 1.0, 1.0),
                           dither_seed=0, bloom=0.0, num_passes=1):

@@ -303,7 +303,7 @@ struct RtgpuContext
         float4* records = nullptr; size_t capacity = 0;   // four planes of `capacity` 16-byte records: normals + valid, positions, two colour buffers (64 bytes per pixel)
         float* io = nullptr; size_t ioFloats = 0;         // device copies of the host entries' inputs and output; rtgpu_denoise's guide planes
         hipEvent_t done = nullptr;                        // recorded behind every call: the next one (whatever its stream) and new scratch wait for it
-        hipEvent_t sumRead = nullptr; bool sumReadPending = false;   // recorded behind the one kernel of rtgpu_denoise_async that reads the sum buffer: whatever writes the film next waits for it
+        hipEvent_t sumRead = nullptr; bool sumReadPending = false;   // recorded behind the one kernel of rtgpu_denoise_async that reads the sum buffer (rtgpu_denoise_var_async: both sum buffers): whatever writes the film next waits for it
     } denoise;
 
     // timing

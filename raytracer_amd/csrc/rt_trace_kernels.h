@@ -48,14 +48,14 @@ __host__ __device__ inline bool queryRayIsDegenerate(float ox, float oy, float o
 // the a-trous filter (rt_denoise.inl): a block is RT_DENOISE_BLOCK_Y rows of 64 consecutive x, one wave per row; a level's constants
 #define RT_DENOISE_BLOCK_X 64
 #define RT_DENOISE_BLOCK_Y 4
-struct AtrousLevel { int32_t step; float invN, invP, invC; };
+struct AtrousLevel { int32_t step; float invN, invP, invC, varianceFloor; };   // (the variance-guided kernels: invC holds sigmaLum^2)
 #define RT_ATROUS_ATTR __launch_bounds__(RT_DENOISE_BLOCK_X * RT_DENOISE_BLOCK_Y)
 // the LDS-tiled variant for steps 1 and 2: a block is a tile of 8 rows x 32 columns (with its 2 * step halo: 30 KB of LDS at step 2)
 #define RT_DENOISE_TILE_X 32
 #define RT_DENOISE_TILE_Y 8
 #define RT_ATROUS_TILED_ATTR __launch_bounds__(RT_DENOISE_TILE_X * RT_DENOISE_TILE_Y) __attribute__((amdgpu_waves_per_eu(1, 3)))   /* (at 4 waves per SIMD, 128 VGPRs, the compiler spills) */
 #define RT_K_ATROUS_ARGS (const float4* __restrict__ recN, const float4* __restrict__ recP, const float4* __restrict__ src, float4* __restrict__ dst, \
-                          const float* __restrict__ albedo, float* __restrict__ out, uint32_t width, uint32_t height, const AtrousLevel level)
+                          const float* __restrict__ albedo, float* __restrict__ out, float* __restrict__ outVariance, uint32_t width, uint32_t height, const AtrousLevel level)
 
 #ifndef RT_DEVICE_KERNELS
 template <int kStack, bool kCount, bool kPerRay = false> __global__ void RT_TRACE_ATTR(kStack) k_trace RT_K_TRACE_ARGS;
@@ -95,7 +95,10 @@ __global__ void __launch_bounds__(RT_BLOCK) k_query_evaluate(const RtSceneDesc s
 __global__ void __launch_bounds__(RT_BLOCK) k_denoise_prepare(const float* __restrict__ color, const float* __restrict__ depth, const float* __restrict__ normal,
                                                               const float* __restrict__ position, const float* __restrict__ albedo, uint32_t pixels, float colorScale,
                                                               float4* __restrict__ recN, float4* __restrict__ recP, float4* __restrict__ recC);
-template <bool kLast> __global__ void RT_ATROUS_ATTR k_atrous RT_K_ATROUS_ARGS;
-template <bool kLast, int kStep> __global__ void RT_ATROUS_TILED_ATTR k_atrous_tiled RT_K_ATROUS_ARGS;
+__global__ void __launch_bounds__(RT_BLOCK) k_denoise_prepare_var(const float* __restrict__ color, const float* __restrict__ colorHalf, const float* __restrict__ depth,
+                                                                  const float* __restrict__ normal, const float* __restrict__ position, const float* __restrict__ albedo,
+                                                                  uint32_t pixels, float colorScale, float4* __restrict__ recN, float4* __restrict__ recP, float4* __restrict__ recC);
+template <bool kLast, bool kVar = false> __global__ void RT_ATROUS_ATTR k_atrous RT_K_ATROUS_ARGS;
+template <bool kLast, int kStep, bool kVar = false> __global__ void RT_ATROUS_TILED_ATTR k_atrous_tiled RT_K_ATROUS_ARGS;
 __global__ void __launch_bounds__(RT_MONSTER_BLOCK) k_trace_monster(const RtSceneDesc scene, const Paths paths, const uint32_t* __restrict__ queue, const uint32_t* __restrict__ queueCount);
 #endif

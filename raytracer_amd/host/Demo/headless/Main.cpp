@@ -3,7 +3,8 @@
 // through the same rt::Viewport API the window loop uses (Demo.cpp: Resize -> SetRenderer -> Render per frame ->
 // GetFrontBuffer) and writes the tone-mapped front buffer as a BMP.  The extra options are --passes, --depth, --output, --seed and
 // --debug-pixel X,Y (prints the path behind that pixel of pass 0, what the reference's Demo shows for a picked pixel: Demo_UserInterface.cpp:197-272),
-// and --denoise [N] (the frame goes through N levels, default 5, of the a-trous filter before it is tone-mapped: rtgpu_denoise, rtgpu_postprocess_from);
+// --denoise [N] (the frame goes through N levels, default 5, of the a-trous filter before it is tone-mapped: rtgpu_denoise, rtgpu_postprocess_from)
+// and --denoise-variance [N] (the same through the variance-guided filter over the film's two sum buffers: rtgpu_denoise_var);
 // the environment variable RTGPU_DEVICES ("0,1,2,3" / "all") spreads the frame over several GPUs (Core/Rendering/Renderer.h).
 #include "../Demo.h"
 #include "../SceneLoader.h"
@@ -72,8 +73,8 @@ static bool PrintPixelPath(IRenderer* renderer, const RtPassParams& params, uint
 }
 
 // The front buffer of the frame after `levels` levels of the a-trous filter (rtgpu_denoise guided by the first hits of one more pass's primary rays,
-// then the viewport's post-process over the filtered image)
-static bool DenoisedFrontBuffer(Viewport& viewport, const Camera& camera, IRenderer* renderer, uint32 levels, Bitmap& front)
+// then the viewport's post-process over the filtered image).  `variance`: rtgpu_denoise_var, the variance-guided filter
+static bool DenoisedFrontBuffer(Viewport& viewport, const Camera& camera, IRenderer* renderer, uint32 levels, bool variance, Bitmap& front)
 {
     PathTracerMIS* pt = dynamic_cast<PathTracerMIS*>(renderer);
     if (!pt || !pt->UploadScene()) { fprintf(stderr, "--denoise: the renderer has no device context\n"); return false; }
@@ -83,6 +84,9 @@ static bool DenoisedFrontBuffer(Viewport& viewport, const Camera& camera, IRende
     RtDenoiseParams dp; memset(&dp, 0, sizeof(dp));
     dp.iterations = levels; dp.flags = RT_DENOISE_DEMODULATE; dp.colorScale = 1.0f / (float)passes;
     dp.sigmaColor = 2.0f; dp.sigmaNormal = 0.25f; dp.sigmaPlane = 0.1f;
+    RtDenoiseVarParams dv; memset(&dv, 0, sizeof(dv));
+    dv.iterations = levels; dv.flags = RT_DENOISE_DEMODULATE; dv.colorScale = dp.colorScale;
+    dv.sigmaLum = 4.0f; dv.sigmaNormal = dp.sigmaNormal; dv.sigmaPlane = dp.sigmaPlane; dv.varianceFloor = 1e-10f;
     std::vector<float> image((size_t)w * h * 3u);
     const PostprocessParams& pp = viewport.GetPostprocessParams();
     RtPostprocessParams p; memset(&p, 0, sizeof(p));
@@ -92,7 +96,7 @@ static bool DenoisedFrontBuffer(Viewport& viewport, const Camera& camera, IRende
     Bitmap::InitData init;
     init.width = w; init.height = h; init.format = Bitmap::Format::B8G8R8A8_UNorm; init.linearSpace = false;   // as Viewport::GetFrontBuffer makes it
     if (!front.Init(init)) return false;
-    if (rtgpu_denoise(pt->GetDeviceContext(), &dp, &guide, image.data()) != RTGPU_OK ||
+    if ((variance ? rtgpu_denoise_var(pt->GetDeviceContext(), &dv, &guide, image.data(), nullptr) : rtgpu_denoise(pt->GetDeviceContext(), &dp, &guide, image.data())) != RTGPU_OK ||
         rtgpu_postprocess_from(pt->GetDeviceContext(), &p, image.data(), reinterpret_cast<uint32*>(front.GetBytes())) != RTGPU_OK)
     {
         fprintf(stderr, "--denoise: %s\n", rtgpu_last_error());
@@ -105,7 +109,7 @@ int main(int argc, char* argv[])
 {
     uint32 width = 1280, height = 720, passes = 64, depth = 20;
     bool debugPixel = false; uint32 debugX = 0, debugY = 0;
-    uint32 denoiseLevels = 0;
+    uint32 denoiseLevels = 0; bool denoiseVariance = false;
     std::string scenePath, rendererName = "Path Tracer MIS", output = "out.bmp";
     unsigned long long seed = 0; bool haveSeed = false;
     for (int i = 1; i < argc; ++i)
@@ -122,13 +126,14 @@ int main(int argc, char* argv[])
         else if (a == "--output") output = value("--output");
         else if (a == "--seed") { seed = strtoull(value("--seed"), nullptr, 10); haveSeed = true; }
         else if (a == "--debug-pixel") { if (sscanf(value("--debug-pixel"), "%u,%u", &debugX, &debugY) != 2) { fprintf(stderr, "--debug-pixel takes X,Y\n"); return 2; } debugPixel = true; }
-        else if (a == "--denoise")
+        else if (a == "--denoise" || a == "--denoise-variance")
         {
             denoiseLevels = 5;   // the level count is optional
+            denoiseVariance = a == "--denoise-variance";
             if (i + 1 < argc && argv[i + 1][0] >= '0' && argv[i + 1][0] <= '9') denoiseLevels = (uint32)atoi(argv[++i]);
-            if (denoiseLevels < 1 || denoiseLevels > 8) { fprintf(stderr, "--denoise takes 1..8 levels\n"); return 2; }
+            if (denoiseLevels < 1 || denoiseLevels > 8) { fprintf(stderr, "%s takes 1..8 levels\n", a.c_str()); return 2; }
         }
-        else { fprintf(stderr, "usage: rt_demo -s scene.json [--data dir/] [-w W] [-h H] [--passes N] [--depth D] [--renderer name] [--output out.bmp] [--seed N] [--debug-pixel X,Y] [--denoise [N]]\n"); return 2; }
+        else { fprintf(stderr, "usage: rt_demo -s scene.json [--data dir/] [-w W] [-h H] [--passes N] [--depth D] [--renderer name] [--output out.bmp] [--seed N] [--debug-pixel X,Y] [--denoise [N]] [--denoise-variance [N]]\n"); return 2; }
     }
     if (scenePath.empty()) { fprintf(stderr, "no scene given (-s scene.json)\n"); return 2; }
 
@@ -164,8 +169,8 @@ int main(int argc, char* argv[])
            (double)counters.numRays / seconds / 1.0e6, (unsigned long long)counters.numRays, (unsigned long long)counters.numShadowRays,
            (double)viewport.GetProgress().averageError);
     Bitmap denoised;
-    if (denoiseLevels && !DenoisedFrontBuffer(viewport, camera, renderer.get(), denoiseLevels, denoised)) return 1;
-    if (denoiseLevels) printf("denoised: %u levels of the a-trous filter\n", denoiseLevels);
+    if (denoiseLevels && !DenoisedFrontBuffer(viewport, camera, renderer.get(), denoiseLevels, denoiseVariance, denoised)) return 1;
+    if (denoiseLevels) printf("denoised: %u levels of the %sa-trous filter\n", denoiseLevels, denoiseVariance ? "variance-guided " : "");
     if (!SaveBMP(output.c_str(), denoiseLevels ? denoised : viewport.GetFrontBuffer())) { fprintf(stderr, "cannot write %s\n", output.c_str()); return 1; }
     printf("wrote %s\n", output.c_str());
     return 0;

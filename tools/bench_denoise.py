@@ -2,7 +2,10 @@
 """Time of the denoiser (include/rtgpu.h: rtgpu_denoise_async through Viewport.denoise(device=True)) on the Sponza-class 1920 x 1080 frame
 (raytracer_amd.scenes.sponza_class, 262 176 triangles) after 20 passes: one call with 1 .. 5 levels, the guide render alone (the four planes through
 Viewport.render_aovs(device=True)), the filter alone on those planes (raytracer_amd.atrous_filter on tensors) and -- for scale, same context -- one render
-pass.  Prints one JSON line and, with --output, writes it to a file.
+pass; and the same two for the variance-guided filter (rtgpu_denoise_var_async through Viewport.denoise(variance=True, device=True), rtgpu_filter_atrous_var_async
+through atrous_filter(color_half=...)), both with the variance plane written, interleaved with the plain ones level count by level count, with their
+ratios to them (`var_over_plain`).  A build without the variance-guided filter reports the plain figures alone.  Prints one JSON line and, with --output,
+writes it to a file.
 
 Timing, after a warm-up of every shape (scratch growth, code objects), `--reps` repetitions (median, min, max): device events around the call on a
 stream of the tool's own; the render pass: host wall time around a batch of passes that ends in rtgpu_synchronize, per pass.
@@ -76,9 +79,13 @@ def main():
     with torch.cuda.stream(stream):
         out["guide_render"] = time_call(torch, lambda: vp.render_aovs(guide, names, device=True), args.reps)
         planes = vp.render_aovs(guide, names, device=True)
-        color = torch.from_numpy(vp.sum_buffer()).cuda()
+        has_var = hasattr(lib, "rtgpu_denoise_var_async")
+        sums = vp.sum_buffer(secondary=True)
+        color, color_half = torch.from_numpy(sums[0]).cuda(), torch.from_numpy(sums[1]).cuda()
         stream.synchronize()
         out["denoise"], out["filter_alone"] = {}, {}
+        if has_var:
+            out["denoise_var"], out["filter_var_alone"], out["var_over_plain"] = {}, {}, {}
         for iterations in range(1, 6):
             out["denoise"][str(iterations)] = time_call(torch, lambda: vp.denoise(guide, iterations=iterations, device=True), args.reps)
             t = time_call(torch, lambda: ra.atrous_filter(color, planes["depth"], planes["normal"], planes["position"], planes["base_color"], iterations=iterations,
@@ -86,6 +93,15 @@ def main():
             t["compulsory_bytes"] = 64 * w * h * iterations
             t["gbytes_per_s_compulsory"] = t["compulsory_bytes"] / t["ms_median"] / 1e6
             out["filter_alone"][str(iterations)] = t
+            if has_var:
+                out["denoise_var"][str(iterations)] = time_call(torch, lambda: vp.denoise(guide, iterations=iterations, device=True, variance=True, return_variance=True), args.reps)
+                tv = time_call(torch, lambda: ra.atrous_filter(color, planes["depth"], planes["normal"], planes["position"], planes["base_color"], iterations=iterations,
+                                                               color_scale=1.0 / vp.passes_finished, ctx=ctx, color_half=color_half, return_variance=True), args.reps)
+                tv["compulsory_bytes"] = 64 * w * h * iterations
+                tv["gbytes_per_s_compulsory"] = tv["compulsory_bytes"] / tv["ms_median"] / 1e6
+                out["filter_var_alone"][str(iterations)] = tv
+                out["var_over_plain"][str(iterations)] = {"denoise": out["denoise_var"][str(iterations)]["ms_median"] / out["denoise"][str(iterations)]["ms_median"],
+                                                          "filter_alone": tv["ms_median"] / t["ms_median"]}
     line = json.dumps(out)
     print(line)
     if args.output:
