@@ -771,7 +771,7 @@ int rtgpu_denoise_async(RtgpuContext* ctx, const RtDenoiseParams* params, const 
 typedef struct RtDenoiseVarParams
 {
     uint32_t iterations;     /* 1..8 levels */
-    uint32_t flags;          /* RT_DENOISE_DEMODULATE */
+    uint32_t flags;          /* RT_DENOISE_DEMODULATE, RT_DENOISE_INPUT_PREPARED (defined below, with temporal accumulation) */
     float    colorScale;
     float    sigmaLum;       /* luminance distance in standard deviations; the wrappers' default is 4 */
     float    sigmaNormal;
@@ -788,6 +788,96 @@ int rtgpu_filter_atrous_var_async(RtgpuContext* ctx, const RtDenoiseVarParams* p
 int rtgpu_denoise_var(RtgpuContext* ctx, const RtDenoiseVarParams* params, const RtPassParams* guideParams, float* outRGB, float* outVariance);
 int rtgpu_denoise_var_async(RtgpuContext* ctx, const RtDenoiseVarParams* params, const RtPassParams* guideParams, float* outRGB,
                             float* outVariance, void* stream);
+
+/* ---------------------------------------------------------------------------------------------
+ * Temporal accumulation: the other half of SVGF.  The scene is static between uploads, so reprojection is exact geometry: the world position of a
+ * pixel's first hit goes through the previous frame's worldToScreen, the previous frame's accumulated estimates are fetched bilinearly around that
+ * point -- each of the four taps tested against the pixel's own surface -- and blended with this frame's.  The half-sample estimate b is accumulated
+ * beside the full estimate a with the same weights: the accumulated error lum(A) - lum(B) = sum w_i e_i has E[e^2] = sum w_i^2 Var(mean_i), the
+ * variance of the accumulated mean, so the variance-guided filter above takes the accumulated pair as it stands (RT_DENOISE_INPUT_PREPARED).
+ * Everything not restated here is as in rtgpu_filter_atrous_var: the frame layout and row order, validity (a finite depth), d_k, the f32 arithmetic
+ * with every multiply and add rounded on its own, sums left to right as written.  tests/temporal_ref.py is the same text in NumPy float32.
+ *   inputs     this frame: color, colorHalf H x W x 3; depth 1 x H x W; normal, position, albedo 3 x H x W (albedo only under RT_DENOISE_DEMODULATE);
+ *              objectId 1 x H x W u32, optional (the OBJECT_ID plane).
+ *              the previous frame: prevA, prevB H x W x 3 and prevLength H x W f32 -- the outputs outA, outB, outLength of the previous call --,
+ *              prevDepth, prevNormal, prevPosition, that frame's guide planes, and prevObjectId, optional.  The object test is skipped unless both
+ *              id planes are given.  All previous pointers NULL: there is no history, and every pixel starts.
+ *   outputs    outA, outB H x W x 3: the accumulated full and half-sample estimates of the mean, in history space (divided by d under
+ *              RT_DENOISE_DEMODULATE and never multiplied back); outLength H x W f32; outMotion 2 x H x W f32, optional.
+ *   prepare    c_k = color_k * colorScale, b_k = colorHalf_k * (2 * colorScale), both divided by d_k under RT_DENOISE_DEMODULATE.
+ *   start      means outA = c, outB = b, outLength = 1, outMotion = (0, 0).  An invalid pixel starts.
+ *   project    M = prevWorldToScreen (rows of four, as RtCamera holds it), P = position_p; for each lane j = 0 .. 3
+ *                  t_j = P.x * M[0][j] + M[3][j];  t_j = P.y * M[1][j] + t_j;  t_j = P.z * M[2][j] + t_j
+ *              start unless t_2 > 0.  u = (t_0 / t_3) * 0.5f + 0.5f, v likewise from t_1;
+ *                  fx = u * (float)W - prevSampleOffset[0];  fr = v * (float)H - prevSampleOffset[1];  fy = (float)(H - 1) - fr
+ *              (the generator's convention: the primary ray of pixel x goes through film coordinate (x + sampleOffset) / W, film rows run bottom-up).
+ *              Start unless fx > -1 && fx < W && fy > -1 && fy < H (false for a NaN; tested before any conversion to integer).
+ *              outMotion = (fx - x, fy - y).
+ *   taps       x0 = floorf(fx), tx = fx - x0, likewise y0, ty.  For (a, b) in (0,0), (1,0), (0,1), (1,1): q = (x0 + a, y0 + b),
+ *              k = (a ? tx : 1 - tx) * (b ? ty : 1 - ty).  A tap is taken iff q is inside the frame, prevDepth_q is finite, the ids are equal (when
+ *              both id planes are given), (N_p.x * N_q.x + N_p.y * N_q.y) + N_p.z * N_q.z >= normalThreshold and, with dp = P_q - P_p,
+ *              fabsf((N_p.x * dp.x + N_p.y * dp.y) + N_p.z * dp.z) <= planeTolerance * depth_p.  A taken tap adds
+ *                  hA_k = hA_k + k * prevA_q,k;  hB_k likewise;  ln = ln + k * prevLength_q;  ks = ks + k
+ *              start unless ks > 0.
+ *   blend      hA = hA / ks, hB = hB / ks;  n = fminf(ln / ks + 1, maxHistory);  alpha = fmaxf(1 / n, alphaMin);
+ *                  outA_k = hA_k + alpha * (c_k - hA_k);  outB_k likewise;  outLength = n.
+ *   scope      SVGF's 3 x 3 fallback search where no tap is taken, feeding the first filtered level back into the history, and reprojecting the
+ *              background by direction are not part of it: a pixel whose four taps fail starts, the history is the unfiltered pair, a miss starts.
+ *              A frame needs an even number of passes, at least 2, for a - b to mean anything (as rtgpu_denoise_var).  Non-finite colours are the
+ *              caller's business.
+ *   errors     a NULL context, params or required buffer (albedo only with RT_DENOISE_DEMODULATE), previous pointers only partly given, exactly one
+ *              id plane beside a history, a parameter outside its stated range or not finite (colorScale: finite and > 0), a width or height of 0:
+ *              RTGPU_ERR_INVALID_ARGUMENT; more than 16 Mi pixels: RTGPU_ERR_UNSUPPORTED; the _async entry: a buffer that is not 16-byte aligned, an
+ *              output that overlaps an input or another output: RTGPU_ERR_INVALID_ARGUMENT.
+ * RT_DENOISE_INPUT_PREPARED, for rtgpu_filter_atrous_var and its three siblings: color and colorHalf are taken as c and b themselves -- no colorScale
+ * multiply, no doubling, no division; the finish still multiplies by d under RT_DENOISE_DEMODULATE.  (outA, outB) go straight into the filter with it.
+ *
+ * rtgpu_temporal_accumulate is a pure image operation like rtgpu_filter_atrous_var, with its rules: a context, but no scene and no rtgpu_resize.
+ * rtgpu_denoise_temporal keeps the history in the context.  It submits the queued passes and gathers peers as rtgpu_denoise_var does, renders the DEPTH,
+ * NORMAL, POSITION, BASE_COLOR and OBJECT_ID planes of guideParams through the AOV path, accumulates the sum and secondary buffers against the stored
+ * history (none: every pixel starts), stores the new history with these guides and guideParams' worldToScreen and sampleOffset, and filters (outA, outB)
+ * with `filter`, its flags | RT_DENOISE_INPUT_PREPARED and its colorScale taken as 1; filter == NULL: no spatial filter, outRGB_k = outA_k * d_k and
+ * outVariance is not written.  params->prevWorldToScreen and prevSampleOffset are ignored: the context remembers its own (guideParams' worldToScreen must
+ * therefore be the matrix of guideParams' own localToWorld: the host mirror's Camera computes it in SetPerspective, not in SetTransform).  The result is by definition
+ * the composition of the two pure entries on the same planes.  rtgpu_temporal_reset drops the history, and so do rtgpu_resize, rtgpu_set_shard and
+ * rtgpu_upload_scene; rtgpu_reset does not -- resetting the film every frame is the use case.  Like the other denoise calls these are not passes: film,
+ * both sum buffers, counters, kernel times, the photon state and the active blocks stay as they are, and the passes rendered after an _async call wait
+ * for its read of both sum buffers.  The history is 128 bytes per pixel (this frame's and the previous one's, four 16-byte records each: {A, length},
+ * {B, id}, {N, valid}, {P, 0}), the call's own, grown on use and freed with the context; guides and the accumulated pair are staged in the filter's
+ * second buffer (at most 84 bytes per pixel), and the pure entries pack the caller's history into the filter's 64-byte records.
+ * --------------------------------------------------------------------------------------------- */
+#define RT_DENOISE_INPUT_PREPARED 2u
+/* 96 bytes */
+typedef struct RtTemporalParams
+{
+    uint32_t flags;                /* RT_DENOISE_DEMODULATE */
+    float    colorScale;           /* normally 1 / passes of this frame */
+    float    alphaMin;             /* floor of the blend factor, (0, 1]; the wrappers' default is 0.1 */
+    float    maxHistory;           /* cap of the history length, >= 1; default 64 */
+    float    normalThreshold;      /* a tap needs N_p . N_q >= this; [-1, 1]; default 0.9 */
+    float    planeTolerance;       /* a tap needs |N_p . (P_q - P_p)| <= this * depth_p; > 0; default 0.01 */
+    float    prevSampleOffset[2];  /* RtPassParams::sampleOffset of the pass the previous guides were rendered with */
+    float    prevWorldToScreen[16];/* RtCamera::worldToScreen of that pass */
+} RtTemporalParams;
+/* Host pointers; synchronous. */
+int rtgpu_temporal_accumulate(RtgpuContext* ctx, const RtTemporalParams* params, uint32_t width, uint32_t height, const float* color,
+                              const float* colorHalf, const float* depth, const float* normal, const float* position, const float* albedo,
+                              const uint32_t* objectId, const float* prevA, const float* prevB, const float* prevLength, const float* prevDepth,
+                              const float* prevNormal, const float* prevPosition, const uint32_t* prevObjectId, float* outA, float* outB,
+                              float* outLength, float* outMotion);
+/* Device pointers on `stream`, as rtgpu_filter_atrous_var_async. */
+int rtgpu_temporal_accumulate_async(RtgpuContext* ctx, const RtTemporalParams* params, uint32_t width, uint32_t height, const float* color,
+                                    const float* colorHalf, const float* depth, const float* normal, const float* position, const float* albedo,
+                                    const uint32_t* objectId, const float* prevA, const float* prevB, const float* prevLength,
+                                    const float* prevDepth, const float* prevNormal, const float* prevPosition, const uint32_t* prevObjectId,
+                                    float* outA, float* outB, float* outLength, float* outMotion, void* stream);
+/* outRGB (and outVariance, optional): host memory of the context's size; synchronous. */
+int rtgpu_denoise_temporal(RtgpuContext* ctx, const RtTemporalParams* params, const RtDenoiseVarParams* filter /* NULL: no spatial filter */,
+                           const RtPassParams* guideParams, float* outRGB, float* outVariance);
+/* outRGB, outVariance: device memory, 16-byte aligned, on `stream` as rtgpu_denoise_var_async. */
+int rtgpu_denoise_temporal_async(RtgpuContext* ctx, const RtTemporalParams* params, const RtDenoiseVarParams* filter, const RtPassParams* guideParams,
+                                 float* outRGB, float* outVariance, void* stream);
+int rtgpu_temporal_reset(RtgpuContext* ctx);
 
 /* rtgpu_postprocess over a caller's image (host memory, height x width x 3 floats of the context's size) in place of the sum buffer -- a
  * denoised frame, say: the same kernels, the same restrictions, and the same bits for the same input. */

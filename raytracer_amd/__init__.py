@@ -215,6 +215,7 @@ class RtDenoiseParams(C.Structure):
 
 
 RT_DENOISE_DEMODULATE = 1
+RT_DENOISE_INPUT_PREPARED = 2   # (the variance-guided filter: the inputs are the accumulated pair of temporal_accumulate)
 # the wrappers' defaults: a wide colour sigma at the first level (it halves per level), normals within about 15 degrees, planes within a tenth of a scene unit
 DENOISE_DEFAULTS = dict(sigma_color=2.0, sigma_normal=0.25, sigma_plane=0.1)
 
@@ -289,7 +290,8 @@ _filter_streams = {}
 
 def atrous_filter(color, depth, normal, position, albedo=None, iterations=5, sigma_color=DENOISE_DEFAULTS["sigma_color"],
                   sigma_normal=DENOISE_DEFAULTS["sigma_normal"], sigma_plane=DENOISE_DEFAULTS["sigma_plane"], color_scale=1.0, demodulate=True, ctx=None,
-                  color_half=None, sigma_lum=DENOISE_VAR_DEFAULTS["sigma_lum"], variance_floor=DENOISE_VAR_DEFAULTS["variance_floor"], return_variance=False):
+                  color_half=None, sigma_lum=DENOISE_VAR_DEFAULTS["sigma_lum"], variance_floor=DENOISE_VAR_DEFAULTS["variance_floor"], return_variance=False,
+                  prepared=False):
     """The edge-avoiding a-trous filter of include/rtgpu.h over a frame: color (H, W, 3), depth (H, W) or (1, H, W), normal, position and albedo (3, H, W)
     -- the layouts of Viewport.sum_buffer() and Viewport.render_aovs() -- as float32 NumPy arrays, or as contiguous float32 torch tensors on a ROCm device
     (then the filter runs on torch.cuda.current_stream() without a host copy and returns a tensor).  Returns the (H, W, 3) image.  albedo is needed with
@@ -298,9 +300,13 @@ def atrous_filter(color, depth, normal, position, albedo=None, iterations=5, sig
     library's events from one host thread; callers on several threads serialise their calls or pass contexts of their own.
 
     color_half (H, W, 3), the sum over half of the samples (Viewport.sum_buffer(secondary=True)[1]), selects the variance-guided filter
-    (rtgpu_filter_atrous_var): sigma_lum and variance_floor take sigma_color's place, and return_variance=True returns (image, the (H, W) variance)."""
+    (rtgpu_filter_atrous_var): sigma_lum and variance_floor take sigma_color's place, and return_variance=True returns (image, the (H, W) variance).
+    prepared=True (RT_DENOISE_INPUT_PREPARED, with color_half): color and color_half are the accumulated pair (a, b) of temporal_accumulate, taken as they
+    are -- no color_scale, no doubling, no division by the albedo; the result is still multiplied by it under demodulate."""
     torch = None
     variance = color_half is not None
+    if prepared and not variance:
+        raise ValueError("prepared=True needs color_half")
     if return_variance and not variance:
         raise ValueError("return_variance=True needs color_half")
     planes = dict(color=color, depth=depth, normal=normal, position=position)
@@ -326,6 +332,8 @@ def atrous_filter(color, depth, normal, position, albedo=None, iterations=5, sig
                                                                         " or ".join(str(t) for t in shapes[name]), "" if torch is None else " (all arrays or all tensors)"))
     if variance:
         p = denoise_var_params(iterations, sigma_lum, sigma_normal, sigma_plane, variance_floor, color_scale, demodulate)
+        if prepared:
+            p.flags |= RT_DENOISE_INPUT_PREPARED
     else:
         p = denoise_params(iterations, sigma_color, sigma_normal, sigma_plane, color_scale, demodulate)
     lib = rtgpu_lib()
@@ -363,6 +371,115 @@ def atrous_filter(color, depth, normal, position, albedo=None, iterations=5, sig
         err = (lib.rtgpu_last_error() or b"").decode()
         raise (ValueError if r == -1 else RuntimeError)("atrous_filter failed (%d): %s" % (r, err))
     return (out, out_variance) if return_variance else out
+
+
+# ---- temporal accumulation (include/rtgpu.h: rtgpu_temporal_accumulate / rtgpu_denoise_temporal) ------------------------------------------------
+class RtTemporalParams(C.Structure):
+    _fields_ = [("flags", C.c_uint32), ("colorScale", C.c_float), ("alphaMin", C.c_float), ("maxHistory", C.c_float), ("normalThreshold", C.c_float),
+                ("planeTolerance", C.c_float), ("prevSampleOffset", C.c_float * 2), ("prevWorldToScreen", C.c_float * 16)]
+
+
+# a history of at most 64 frames that never weighs the new frame below a tenth; normals within about 25 degrees; planes within a hundredth of the depth
+TEMPORAL_DEFAULTS = dict(alpha_min=0.1, max_history=64.0, normal_threshold=0.9, plane_tolerance=0.01)
+
+
+def temporal_params(alpha_min=TEMPORAL_DEFAULTS["alpha_min"], max_history=TEMPORAL_DEFAULTS["max_history"], normal_threshold=TEMPORAL_DEFAULTS["normal_threshold"],
+                    plane_tolerance=TEMPORAL_DEFAULTS["plane_tolerance"], color_scale=1.0, demodulate=True, prev_world_to_screen=None, prev_sample_offset=(0.0, 0.0)):
+    p = RtTemporalParams()
+    p.flags = RT_DENOISE_DEMODULATE if demodulate else 0
+    p.colorScale, p.alphaMin, p.maxHistory, p.normalThreshold, p.planeTolerance = float(color_scale), float(alpha_min), float(max_history), float(normal_threshold), float(plane_tolerance)
+    p.prevSampleOffset[0], p.prevSampleOffset[1] = float(prev_sample_offset[0]), float(prev_sample_offset[1])
+    if prev_world_to_screen is not None:
+        m = np.asarray(prev_world_to_screen, dtype=np.float32).reshape(-1)
+        if m.size != 16:
+            raise ValueError("prev_world_to_screen must hold 16 values (RtCamera.worldToScreen)")
+        for i in range(16):
+            p.prevWorldToScreen[i] = float(m[i])
+    return p
+
+
+HISTORY_KEYS = ("a", "b", "length", "depth", "normal", "position", "object_id")
+
+
+def temporal_accumulate(color, color_half, depth, normal, position, albedo=None, object_id=None, history=None, prev_world_to_screen=None, prev_sample_offset=(0.0, 0.0),
+                        alpha_min=TEMPORAL_DEFAULTS["alpha_min"], max_history=TEMPORAL_DEFAULTS["max_history"], normal_threshold=TEMPORAL_DEFAULTS["normal_threshold"],
+                        plane_tolerance=TEMPORAL_DEFAULTS["plane_tolerance"], color_scale=1.0, demodulate=True, return_motion=False, ctx=None):
+    """Temporal accumulation of include/rtgpu.h over a frame: color, color_half (H, W, 3) -- Viewport.sum_buffer(secondary=True) --, depth (H, W) or (1, H, W),
+    normal, position, albedo (3, H, W) float32 and object_id (H, W) or (1, H, W) uint32 (optional) -- Viewport.render_aovs() --, as NumPy arrays or as
+    contiguous torch tensors on a ROCm device (object_id: the int64 tensor render_aovs(device=True) returns, or int32 words), then on
+    torch.cuda.current_stream() without a host copy, as atrous_filter.  `history`: None (every pixel starts) or the dict a previous call returned, with
+    prev_world_to_screen and prev_sample_offset of the pass its guides were rendered with (RtPassParams.camera.worldToScreen, .sampleOffset).  Returns the
+    history dict of this frame -- a, b (H, W, 3): the accumulated full and half-sample estimates in history space; length (H, W); and this frame's depth,
+    normal, position and object_id (the words the device reads) -- which the next call takes back and whose (a, b) go into atrous_filter(prepared=True);
+    return_motion=True: (history, the (2, H, W) motion plane).  albedo is needed with demodulate=True only; the object test needs the ids of both frames."""
+    torch = None
+    planes = dict(color=color, color_half=color_half, depth=depth, normal=normal, position=position)
+    if demodulate:
+        if albedo is None:
+            raise ValueError("demodulate=True needs the albedo plane")
+        planes["albedo"] = albedo
+    if object_id is not None:
+        planes["object_id"] = object_id
+    if history is not None:
+        if prev_world_to_screen is None:
+            raise ValueError("a history needs prev_world_to_screen")
+        for key in HISTORY_KEYS:
+            if key not in history:
+                raise ValueError("history must be the dict a previous call returned (no %r)" % key)
+            if history[key] is not None:
+                planes["prev_" + key] = history[key]
+        if ("object_id" in planes) != ("prev_object_id" in planes):
+            raise ValueError("the object test needs both id planes: give object_id and a history with one, or neither")
+    if any(type(a).__module__.split(".")[0] == "torch" for a in planes.values()):
+        import torch
+    if getattr(color, "ndim", 0) != 3 or color.shape[2] != 3:
+        raise ValueError("color must be an (H, W, 3) float32 array or tensor")
+    h, w = int(color.shape[0]), int(color.shape[1])
+    one, three, image = ((h, w), (1, h, w)), ((3, h, w),), ((h, w, 3),)
+    shapes = dict(color=image, color_half=image, depth=one, normal=three, position=three, albedo=three, object_id=one, prev_a=image, prev_b=image, prev_length=one,
+                  prev_depth=one, prev_normal=three, prev_position=three, prev_object_id=one)
+    for name, a in list(planes.items()):
+        ids = name.endswith("object_id")
+        if torch is None:
+            ok = isinstance(a, np.ndarray) and a.dtype == (np.uint32 if ids else np.float32)
+        else:
+            ok = isinstance(a, torch.Tensor) and a.dtype in ((torch.int32, torch.int64) if ids else (torch.float32,)) and a.is_cuda and a.device == color.device
+            if ok and ids and a.dtype == torch.int64:
+                planes[name] = a.to(torch.int32)   # (the low words: ids are below 2^32)
+        if not ok or tuple(a.shape) not in shapes[name]:
+            raise ValueError("%s must be a %s %s of shape %s%s" % (name, "uint32" if ids else "float32", "NumPy array" if torch is None else "tensor on the colour's ROCm device",
+                                                                   " or ".join(str(t) for t in shapes[name]), "" if torch is None else " (all arrays or all tensors)"))
+    p = temporal_params(alpha_min, max_history, normal_threshold, plane_tolerance, color_scale, demodulate, prev_world_to_screen if history is not None else None,
+                        prev_sample_offset)
+    lib = rtgpu_lib()
+    order = ("color", "color_half", "depth", "normal", "position", "albedo", "object_id", "prev_a", "prev_b", "prev_length", "prev_depth", "prev_normal", "prev_position",
+             "prev_object_id")
+    if torch is None:
+        planes = {name: np.ascontiguousarray(a) for name, a in planes.items()}
+        out = dict(a=np.zeros((h, w, 3), dtype=np.float32), b=np.zeros((h, w, 3), dtype=np.float32), length=np.zeros((h, w), dtype=np.float32))
+        motion = np.zeros((2, h, w), dtype=np.float32) if return_motion else None
+        ptr = lambda a: a.ctypes.data_as(C.c_void_p) if a is not None else None   # noqa: E731
+        context = ctx if ctx is not None else _filter_context(0)
+        r = lib.rtgpu_temporal_accumulate(context, C.byref(p), C.c_uint32(w), C.c_uint32(h), *([ptr(planes.get(name)) for name in order] +
+                                          [ptr(out["a"]), ptr(out["b"]), ptr(out["length"]), ptr(motion)]))
+    else:
+        device = color.device
+        index = device.index if device.index is not None else torch.cuda.current_device()
+        for name, a in planes.items():
+            if not a.is_contiguous():
+                raise ValueError("%s must be contiguous" % name)
+        out = dict(a=torch.empty((h, w, 3), dtype=torch.float32, device=device), b=torch.empty((h, w, 3), dtype=torch.float32, device=device),
+                   length=torch.empty((h, w), dtype=torch.float32, device=device))
+        motion = torch.empty((2, h, w), dtype=torch.float32, device=device) if return_motion else None
+        ptr = lambda a: C.c_void_p(a.data_ptr()) if a is not None else None   # noqa: E731
+        context = ctx if ctx is not None else _filter_context(index)
+        r = _run_on_torch_stream(torch, _filter_streams, device, list(planes.values()) + list(out.values()) + [motion], lambda stream: lib.rtgpu_temporal_accumulate_async(
+            context, C.byref(p), C.c_uint32(w), C.c_uint32(h), *([ptr(planes.get(name)) for name in order] + [ptr(out["a"]), ptr(out["b"]), ptr(out["length"]), ptr(motion), stream])))
+    if r != 0:
+        err = (lib.rtgpu_last_error() or b"").decode()
+        raise (ValueError if r == -1 else RuntimeError)("temporal_accumulate failed (%d): %s" % (r, err))
+    out.update(depth=planes["depth"], normal=planes["normal"], position=planes["position"], object_id=planes.get("object_id"))
+    return (out, motion) if return_motion else out
 
 
 BSDF_NAMES = ("null", "diffuse", "roughDiffuse", "dielectric", "roughDielectric", "metal", "roughMetal", "plastic", "roughPlastic")
@@ -945,13 +1062,24 @@ class Viewport:
     # ---- denoise (include/rtgpu.h: rtgpu_denoise / rtgpu_denoise_async, rtgpu_postprocess_from) ------------------------------------------------------
     def denoise(self, params, iterations=5, sigma_color=DENOISE_DEFAULTS["sigma_color"], sigma_normal=DENOISE_DEFAULTS["sigma_normal"],
                 sigma_plane=DENOISE_DEFAULTS["sigma_plane"], color_scale=None, demodulate=True, device=False, variance=False,
-                sigma_lum=DENOISE_VAR_DEFAULTS["sigma_lum"], variance_floor=DENOISE_VAR_DEFAULTS["variance_floor"], return_variance=False):
+                sigma_lum=DENOISE_VAR_DEFAULTS["sigma_lum"], variance_floor=DENOISE_VAR_DEFAULTS["variance_floor"], return_variance=False, temporal=False,
+                alpha_min=TEMPORAL_DEFAULTS["alpha_min"], max_history=TEMPORAL_DEFAULTS["max_history"], normal_threshold=TEMPORAL_DEFAULTS["normal_threshold"],
+                plane_tolerance=TEMPORAL_DEFAULTS["plane_tolerance"]):
         """The frame rendered so far through the a-trous filter of include/rtgpu.h, guided by the depth, normal, position and base-colour planes of the pass
         `params` (an RtPassParams from next_pass_params(), as render_aovs takes it): the (H, W, 3) float32 image, sum_buffer() * color_scale filtered.
         color_scale defaults to 1 / max(1, passes_finished).  device=True: a torch tensor on the renderer's ROCm device, produced on
         torch.cuda.current_stream() without a host copy.  The call is not a pass: film, sum buffers and counters stay as they are.
         variance=True: the variance-guided filter (rtgpu_denoise_var) over the sum and the secondary sum buffer, with sigma_lum and variance_floor in
-        sigma_color's place; return_variance=True then returns (image, the (H, W) variance of the filtered luminance)."""
+        sigma_color's place; return_variance=True then returns (image, the (H, W) variance of the filtered luminance).
+        temporal=True (rtgpu_denoise_temporal): the frame is first accumulated against the history the renderer keeps from the previous such call --
+        reprojected through that call's camera, with alpha_min, max_history, normal_threshold and plane_tolerance -- and becomes the next call's history;
+        variance=True then filters the accumulated pair, variance=False returns the accumulated frame unfiltered.  reset() keeps the history (a moving
+        camera resets the film every frame); reset_history(), a resize and a new scene drop it.  The reprojection reads params.camera.worldToScreen, which
+        Camera.set_perspective computes from the transform of the moment (as the reference's Camera does): after Camera.set_transform call set_perspective again,
+        or the history is looked up through the camera's old place."""
+        if temporal:
+            return self._denoise_temporal(params, iterations, sigma_normal, sigma_plane, color_scale, demodulate, device, variance, sigma_lum, variance_floor, return_variance,
+                                          alpha_min, max_history, normal_threshold, plane_tolerance)
         if return_variance and not variance:
             raise ValueError("return_variance=True needs variance=True")
         if not isinstance(params, RtPassParams):
@@ -992,6 +1120,47 @@ class Viewport:
             err = (lib.rtgpu_last_error() or b"").decode()
             raise (ValueError if r == -1 else RuntimeError)("denoise failed (%d): %s" % (r, err))
         return (out, out_variance) if return_variance else out
+
+    def _denoise_temporal(self, params, iterations, sigma_normal, sigma_plane, color_scale, demodulate, device, variance, sigma_lum, variance_floor, return_variance,
+                          alpha_min, max_history, normal_threshold, plane_tolerance):
+        if return_variance and not variance:
+            raise ValueError("return_variance=True needs variance=True")
+        if not isinstance(params, RtPassParams):
+            raise TypeError("denoise takes the RtPassParams of next_pass_params(camera), not %s" % type(params).__name__)
+        if not self.has_renderer:
+            raise RuntimeError("denoise needs a renderer: call set_renderer first")
+        ctx = self.device_context()
+        if not ctx.value or host_lib().rth_viewport_upload_scene(self._h) != 0:
+            raise RuntimeError("the viewport's renderer has no device context or its scene could not be uploaded: %s" % (rtgpu_lib().rtgpu_last_error() or b"").decode())
+        scale = 1.0 / max(1, self.passes_finished) if color_scale is None else color_scale
+        t = temporal_params(alpha_min, max_history, normal_threshold, plane_tolerance, scale, demodulate)
+        v = denoise_var_params(iterations, sigma_lum, sigma_normal, sigma_plane, variance_floor, 1.0, demodulate) if variance else None
+        vref = C.byref(v) if variance else None
+        lib = rtgpu_lib()
+        out_variance = None
+        if not device:
+            out = np.zeros((self.height, self.width, 3), dtype=np.float32)
+            out_variance = np.zeros((self.height, self.width), dtype=np.float32) if return_variance else None
+            r = lib.rtgpu_denoise_temporal(ctx, C.byref(t), vref, C.byref(params), out.ctypes.data_as(C.c_void_p), out_variance.ctypes.data_as(C.c_void_p) if return_variance else None)
+        else:
+            import torch
+            dev = torch.device("cuda", multi_info(ctx)["devices"][0])
+            out = torch.empty((self.height, self.width, 3), dtype=torch.float32, device=dev)
+            out_variance = torch.empty((self.height, self.width), dtype=torch.float32, device=dev) if return_variance else None
+            if getattr(self, "_denoise_streams", None) is None:
+                self._denoise_streams = {}
+            r = _run_on_torch_stream(torch, self._denoise_streams, dev, [out, out_variance], lambda stream: lib.rtgpu_denoise_temporal_async(
+                ctx, C.byref(t), vref, C.byref(params), C.c_void_p(out.data_ptr()), C.c_void_p(out_variance.data_ptr()) if return_variance else None, stream))
+        if r != 0:
+            err = (lib.rtgpu_last_error() or b"").decode()
+            raise (ValueError if r == -1 else RuntimeError)("denoise failed (%d): %s" % (r, err))
+        return (out, out_variance) if return_variance else out
+
+    def reset_history(self):
+        """Drops the history of denoise(temporal=True) (rtgpu_temporal_reset): the next such call starts every pixel."""
+        ctx = self.device_context()
+        if ctx.value and rtgpu_lib().rtgpu_temporal_reset(ctx) != 0:
+            raise RuntimeError("reset_history failed: %s" % (rtgpu_lib().rtgpu_last_error() or b"").decode())
 
     def front_buffer_from(self, image, exposure=0.0, contrast=0.8, saturation=0.98, dithering=0.005, tonemapper=3, color_filter=(1.0, 1.0, 1.0, 1.0),
                           dither_seed=0, bloom=0.0, num_passes=1):

@@ -26,8 +26,9 @@ RT_DEV float denoiseAlbedoDivisor(const float* __restrict__ albedo, size_t pixel
 // lum(c) of the variance-guided definition
 RT_DEV float denoiseLum(float c0, float c1, float c2) { return ((c0 + 2.0f * c1) + c2) * 0.25f; }
 
-// pixel i of k_denoise_prepare (kVar: of k_denoise_prepare_var, whose colour record carries the variance of the mean's luminance)
-template <bool kVar>
+// pixel i of k_denoise_prepare (kVar: of k_denoise_prepare_var, whose colour record carries the variance of the mean's luminance; kPrepared: of
+// k_denoise_prepare_accumulated, RT_DENOISE_INPUT_PREPARED: colour and colorHalf are c and b themselves -- no scale, no doubling, no division)
+template <bool kVar, bool kPrepared = false>
 RT_DEV void denoisePrepare(uint32_t i, const float* __restrict__ color, const float* __restrict__ colorHalf, const float* __restrict__ depth, const float* __restrict__ normal,
                            const float* __restrict__ position, const float* __restrict__ albedo, uint32_t pixels, float colorScale,
                            float4* __restrict__ recN, float4* __restrict__ recP, float4* __restrict__ recC)
@@ -39,6 +40,12 @@ RT_DEV void denoisePrepare(uint32_t i, const float* __restrict__ color, const fl
     float c[3], b[3];
     for (uint32_t k = 0; k < 3u; ++k)
     {
+        if (kPrepared)
+        {
+            c[k] = color[3 * (size_t)i + k];
+            b[k] = colorHalf[3 * (size_t)i + k];
+            continue;
+        }
         c[k] = color[3 * (size_t)i + k] * colorScale;
         if (kVar) b[k] = colorHalf[3 * (size_t)i + k] * (2.0f * colorScale);
         if (albedo)
@@ -73,6 +80,15 @@ __global__ void __launch_bounds__(RT_BLOCK) k_denoise_prepare_var(const float* _
     const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= pixels) return;
     denoisePrepare<true>(i, color, colorHalf, depth, normal, position, albedo, pixels, colorScale, recN, recP, recC);
+}
+
+__global__ void __launch_bounds__(RT_BLOCK) k_denoise_prepare_accumulated(const float* __restrict__ color, const float* __restrict__ colorHalf, const float* __restrict__ depth,
+                                                                          const float* __restrict__ normal, const float* __restrict__ position, uint32_t pixels,
+                                                                          float4* __restrict__ recN, float4* __restrict__ recP, float4* __restrict__ recC)
+{
+    const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= pixels) return;
+    denoisePrepare<true, true>(i, color, colorHalf, depth, normal, position, nullptr, pixels, 1.0f, recN, recP, recC);
 }
 
 // one tap of the definition: its weight from the three distances, then acc += w * c_q and wsum += w -- unless the tap is skipped (`take` false).

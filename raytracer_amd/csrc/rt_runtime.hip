@@ -28,7 +28,8 @@
 // staging copies, stream pool, HIP_TRY, LaunchTimer, free helpers), rt_knobs.h (every RTGPU_* environment variable), rt_multi.inl (multi-device contexts),
 // rt_runtime_scene.inl (rtgpu_upload_scene), rt_runtime_render.inl (arena sizing, traversal launchers, batch submission), rt_runtime_vcm.inl (bidirectional
 // integrator, Light Tracer), rt_runtime_kat.inl (known-answer hooks, rtgpu_evaluate_textures), rt_runtime_query.inl (batched ray queries), rt_runtime_paths.inl (path records),
-// rt_runtime_aov.inl (AOVs), rt_runtime_denoise.inl (the a-trous filter, rtgpu_denoise, rtgpu_postprocess_from).
+// rt_runtime_aov.inl (AOVs), rt_runtime_denoise.inl (the a-trous filter, rtgpu_denoise, rtgpu_postprocess_from),
+// rt_runtime_temporal.inl (temporal accumulation).
 //
 // Compile: hipcc --offload-arch=gfx950 -O3 -ffp-contract=off
 #include "rt_trace_common.h"
@@ -287,6 +288,7 @@ static int rebuildFilm(RtgpuContext* c)
     HIP_TRY(hipStreamSynchronize(nullptr));   // the batch lanes are non-blocking streams: they do not wait for the null stream's memsets
     c->activeMask.clear();   // a new film starts with the whole image active
     c->vcm.havePhotons = false;   // recorded per slot of the old film
+    c->temporal.have = false;     // (and the history of rtgpu_denoise_temporal: another frame size, another film)
     return rebuildSlots(c);
 }
 
@@ -709,6 +711,7 @@ RTGPU_API int rtgpu_postprocess(RtgpuContext* c, const RtPostprocessParams* p, u
 #include "rt_runtime_paths.inl"
 #include "rt_runtime_aov.inl"
 #include "rt_runtime_denoise.inl"
+#include "rt_runtime_temporal.inl"
 
 RTGPU_API int rtgpu_set_concurrency(RtgpuContext* c, uint32_t lanes)
 {

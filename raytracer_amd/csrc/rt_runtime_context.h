@@ -306,6 +306,14 @@ struct RtgpuContext
         hipEvent_t sumRead = nullptr; bool sumReadPending = false;   // recorded behind the one kernel of rtgpu_denoise_async that reads the sum buffer (rtgpu_denoise_var_async: both sum buffers): whatever writes the film next waits for it
     } denoise;
 
+    // temporal accumulation (rtgpu_denoise_temporal; rt_runtime_temporal.inl): the previous frame and the one being written, ordered by denoise.done
+    struct Temporal
+    {
+        float4* records = nullptr; size_t capacity = 0;   // two sets of four planes of `capacity` 16-byte records: {A, length}, {B, id}, {N, valid}, {P, 0} (128 bytes per pixel)
+        uint32_t current = 0; bool have = false;          // the set that holds the previous frame; false: no history (every pixel starts)
+        float worldToScreen[16] = {}, sampleOffset[2] = {};   // of the pass that frame's guides were rendered with
+    } temporal;
+
     // timing
     bool timing = false;
     struct Timed { int kc; hipEvent_t a, b; };
@@ -448,8 +456,8 @@ static void freeDenoise(RtgpuContext* c)
 {
     RtgpuContext::Denoise& d = c->denoise;
     if (d.done) (void)hipEventSynchronize(d.done);
-    devFree(d.records, d.io);
-    d.capacity = 0; d.ioFloats = 0;
+    devFree(d.records, d.io, c->temporal.records);
+    d.capacity = 0; d.ioFloats = 0; c->temporal.capacity = 0; c->temporal.have = false;
     if (d.done) (void)hipEventDestroy(d.done);
     if (d.sumRead) (void)hipEventDestroy(d.sumRead);
     d.done = nullptr; d.sumRead = nullptr; d.sumReadPending = false;

@@ -48,6 +48,19 @@ static int ensureDenoiseIo(RtgpuContext* c, size_t floats)
     return RTGPU_OK;
 }
 
+// the record scratch for `pixels` pixels (four planes of 16-byte records), and the event every call on it is ordered by
+static int ensureAtrousRecords(RtgpuContext* c, size_t pixels)
+{
+    RtgpuContext::Denoise& d = c->denoise;
+    if (!d.done) HIP_TRY(hipEventCreateWithFlags(&d.done, hipEventDisableTiming));
+    if (d.capacity >= pixels) return RTGPU_OK;
+    HIP_TRY(hipEventSynchronize(d.done));   // (a fresh event is complete)
+    devFree(d.records); d.capacity = 0;
+    HIP_TRY(hipMalloc((void**)&d.records, 4u * pixels * sizeof(float4)));
+    d.capacity = pixels;
+    return RTGPU_OK;
+}
+
 // the launches of one call on `stream`; every pointer is device memory.  `colorIsSum`: the colour is the context's sum buffer (and colorHalf its secondary one), whose
 // next writer waits for sumRead.  colorHalf and outVariance (may be NULL) belong to the variance-guided filter
 static int launchAtrous(RtgpuContext* c, const AtrousPlan& plan, uint32_t width, uint32_t height, const float* color, const float* colorHalf, const float* depth, const float* normal,
@@ -56,19 +69,13 @@ static int launchAtrous(RtgpuContext* c, const AtrousPlan& plan, uint32_t width,
     const AtrousPlan* const p = &plan;
     RtgpuContext::Denoise& d = c->denoise;
     const size_t pixels = (size_t)width * height;
-    if (!d.done) HIP_TRY(hipEventCreateWithFlags(&d.done, hipEventDisableTiming));
-    if (d.capacity < pixels)
-    {
-        HIP_TRY(hipEventSynchronize(d.done));   // (a fresh event is complete)
-        devFree(d.records); d.capacity = 0;
-        HIP_TRY(hipMalloc((void**)&d.records, 4u * pixels * sizeof(float4)));
-        d.capacity = pixels;
-    }
+    { int r = ensureAtrousRecords(c, pixels); if (r) return r; }
     HIP_TRY(hipStreamWaitEvent(stream, d.done, 0));   // the scratch is shared with the previous call, whatever its stream
     float4* const recN = d.records; float4* const recP = recN + d.capacity; float4* const buffers[2] = { recP + d.capacity, recP + 2u * d.capacity };
     if (!(p->flags & RT_DENOISE_DEMODULATE)) albedo = nullptr;
     const dim3 prepareGrid((uint32_t)((pixels + RT_BLOCK - 1u) / RT_BLOCK));
-    if (p->variance) hipLaunchKernelGGL(k_denoise_prepare_var, prepareGrid, dim3(RT_BLOCK), 0, stream, color, colorHalf, depth, normal, position, albedo, (uint32_t)pixels, p->colorScale, recN, recP, buffers[0]);
+    if (p->variance && (p->flags & RT_DENOISE_INPUT_PREPARED)) hipLaunchKernelGGL(k_denoise_prepare_accumulated, prepareGrid, dim3(RT_BLOCK), 0, stream, color, colorHalf, depth, normal, position, (uint32_t)pixels, recN, recP, buffers[0]);
+    else if (p->variance) hipLaunchKernelGGL(k_denoise_prepare_var, prepareGrid, dim3(RT_BLOCK), 0, stream, color, colorHalf, depth, normal, position, albedo, (uint32_t)pixels, p->colorScale, recN, recP, buffers[0]);
     else hipLaunchKernelGGL(k_denoise_prepare, prepareGrid, dim3(RT_BLOCK), 0, stream, color, depth, normal, position, albedo, (uint32_t)pixels, p->colorScale, recN, recP, buffers[0]);
     if (colorIsSum)
     {

@@ -42,6 +42,7 @@ RTGPU_API int rtgpu_upload_scene(RtgpuContext* c, const RtSceneDesc* s)
     { int fr = flushPending(c); if (fr) return fr; }
     HIP_TRY(syncLanes(c));
     waitQueries(c);   // an asynchronous ray query or AOV call may still walk the old scene
+    c->temporal.have = false;   // rtgpu_denoise_temporal's history shows the old scene
 
     // validation: indices in range, stacks deep enough
     if (s->numObjects > 1 && s->numTopNodes == 0) return fail(RTGPU_ERR_INVALID_ARGUMENT, "scene with more than one object needs a top-level BVH");

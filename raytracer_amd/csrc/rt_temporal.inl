@@ -1,0 +1,140 @@
+// rt_temporal.inl -- kernels behind rtgpu_temporal_accumulate / rtgpu_denoise_temporal (include/rtgpu.h; host side: rt_runtime_temporal.inl).  Included by
+// rt_trace.hip behind rt_denoise.inl, whose helpers it uses and whose -ffp-contract=off it shares: every a * b + c below is a rounded multiply and a rounded add.
+// Temporal accumulation, the other half of SVGF: the world position of a pixel's first hit goes through the previous frame's worldToScreen, the previous
+// frame's accumulated pair (A, B) and history length are fetched bilinearly from the four pixels around that point -- each tap tested against the pixel's own
+// surface -- and blended with this frame's pair.  The definition stands in include/rtgpu.h; tests/temporal_ref.py is the same text in NumPy float32.
+//
+//   k_temporal_pack   planar history of a caller (the pure entries) -> the four 16-byte records per pixel the context keeps its own history in:
+//                     {A.rgb, length}, {B.rgb, object id}, {N.xyz, valid}, {P.xyz, 0}
+//   k_temporal        one lane per pixel, a wave = 64 consecutive x of one row.  The current planes are coalesced loads; a tap is four 16-byte gathers, no
+//                     branch around it (a tap outside the frame loads the pixel's own address and is dropped by a select, as atrousTap does).  Neighbours
+//                     share three of their four taps under coherent motion: the caches do what an LDS tile would.  It writes the planar outputs and,
+//                     where asked, the records of the next frame's history and the remodulated image; every per-pixel operation exists once.
+
+__global__ void __launch_bounds__(RT_BLOCK) k_temporal_pack(const float* __restrict__ prevA, const float* __restrict__ prevB, const float* __restrict__ prevLength,
+                                                            const float* __restrict__ prevDepth, const float* __restrict__ prevNormal, const float* __restrict__ prevPosition,
+                                                            const uint32_t* __restrict__ prevObjectId, uint32_t pixels, float4* __restrict__ recA, float4* __restrict__ recB,
+                                                            float4* __restrict__ recN, float4* __restrict__ recP)
+{
+    const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= pixels) return;
+    const size_t n = pixels;
+    const bool valid = (__float_as_uint(prevDepth[i]) & 0x7F800000u) != 0x7F800000u;
+    recA[i] = make_float4(prevA[3 * (size_t)i], prevA[3 * (size_t)i + 1], prevA[3 * (size_t)i + 2], prevLength[i]);
+    recB[i] = make_float4(prevB[3 * (size_t)i], prevB[3 * (size_t)i + 1], prevB[3 * (size_t)i + 2], __uint_as_float(prevObjectId ? prevObjectId[i] : 0u));
+    recN[i] = make_float4(prevNormal[i], prevNormal[n + i], prevNormal[2 * n + i], valid ? 1.0f : 0.0f);
+    recP[i] = make_float4(prevPosition[i], prevPosition[n + i], prevPosition[2 * n + i], 0.0f);
+}
+
+// a history record in one 16-byte load (as atrousColour)
+RT_DEV float4 temporalRecord(const float4* __restrict__ src, uint32_t q)
+{
+    const AtrousLanes lanes = *reinterpret_cast<const AtrousLanes*>(src + q);
+    return make_float4(lanes.x, lanes.y, lanes.z, lanes.w);
+}
+
+__global__ void RT_ATROUS_ATTR k_temporal RT_K_TEMPORAL_ARGS
+{
+    // (blocks numbered row by row along grid.x, as k_atrous numbers them)
+    const uint32_t blocksX = (width + RT_DENOISE_BLOCK_X - 1u) / RT_DENOISE_BLOCK_X, blockY = blockIdx.x / blocksX, blockX = blockIdx.x - blockY * blocksX;
+    const int32_t x = (int32_t)(blockX * RT_DENOISE_BLOCK_X + threadIdx.x), y = (int32_t)(blockY * RT_DENOISE_BLOCK_Y + threadIdx.y);
+    if (x >= (int32_t)width || y >= (int32_t)height) return;
+    const int32_t w = (int32_t)width, h = (int32_t)height;
+    const uint32_t p = (uint32_t)y * width + (uint32_t)x;
+    const size_t pixels = (size_t)width * height;
+    const float depthP = in.depth[p];
+    const bool valid = (__float_as_uint(depthP) & 0x7F800000u) != 0x7F800000u;
+    const float4 np = make_float4(in.normal[p], in.normal[pixels + p], in.normal[2 * pixels + p], valid ? 1.0f : 0.0f);
+    const float4 pp = make_float4(in.position[p], in.position[pixels + p], in.position[2 * pixels + p], 0.0f);
+    const uint32_t idP = in.objectId ? in.objectId[p] : 0u;
+    // prepare
+    float c[3], b[3], d[3];
+#pragma unroll
+    for (uint32_t k = 0; k < 3u; ++k)
+    {
+        c[k] = in.color[3 * (size_t)p + k] * frame.colorScale;
+        b[k] = in.colorHalf[3 * (size_t)p + k] * (2.0f * frame.colorScale);
+        d[k] = denoiseAlbedoDivisor(in.albedo, pixels, p, k);
+        if (in.albedo)
+        {
+            c[k] = c[k] / d[k];
+            b[k] = b[k] / d[k];
+        }
+    }
+    float a0 = c[0], a1 = c[1], a2 = c[2], b0 = b[0], b1 = b[1], b2 = b[2], length = 1.0f, motionX = 0.0f, motionY = 0.0f;   // a pixel that starts
+    if (in.recA)   // (uniform: NULL without history)
+    {
+        // project: transformPoint's operations, lane by lane
+        float t[4];
+#pragma unroll
+        for (uint32_t j = 0; j < 4u; ++j)
+        {
+            t[j] = pp.x * frame.m[j] + frame.m[12u + j];
+            t[j] = pp.y * frame.m[4u + j] + t[j];
+            t[j] = pp.z * frame.m[8u + j] + t[j];
+        }
+        const float u = (t[0] / t[3]) * 0.5f + 0.5f, v = (t[1] / t[3]) * 0.5f + 0.5f;
+        const float fw = (float)w, fh = (float)h;
+        const float fx = u * fw - frame.prevSampleOffset[0];
+        const float fr = v * fh - frame.prevSampleOffset[1];
+        const float fy = (float)(h - 1) - fr;
+        const bool reaches = valid && t[2] > 0.0f && fx > -1.0f && fx < fw && fy > -1.0f && fy < fh;   // (false for a NaN; before any conversion to integer)
+        // taps: a pixel that does not reach the previous frame takes them around (0, 0) and drops the lot
+        const float sx = reaches ? fx : 0.0f, sy = reaches ? fy : 0.0f;
+        const float flx = floorf(sx), fly = floorf(sy);
+        const float tx = sx - flx, ty = sy - fly;
+        const int32_t x0 = (int32_t)flx, y0 = (int32_t)fly;
+        const float limit = frame.planeTolerance * depthP;
+        float hA0 = 0.0f, hA1 = 0.0f, hA2 = 0.0f, hB0 = 0.0f, hB1 = 0.0f, hB2 = 0.0f, ln = 0.0f, ks = 0.0f;
+#pragma unroll
+        for (int32_t tb = 0; tb < 2; ++tb)
+        {
+#pragma unroll
+            for (int32_t ta = 0; ta < 2; ++ta)
+            {
+                const int32_t qx = x0 + ta, qy = y0 + tb;
+                const bool inside = qx >= 0 && qx < w && qy >= 0 && qy < h;
+                const uint32_t q = inside ? (uint32_t)qy * width + (uint32_t)qx : p;
+                const float4 aq = temporalRecord(in.recA, q), bq = temporalRecord(in.recB, q), nq = temporalRecord(in.recN, q), pq = temporalRecord(in.recP, q);
+                const float k = (ta ? tx : 1.0f - tx) * (tb ? ty : 1.0f - ty);
+                const float dpx = pq.x - pp.x, dpy = pq.y - pp.y, dpz = pq.z - pp.z;
+                const float cosine = (np.x * nq.x + np.y * nq.y) + np.z * nq.z;
+                const float offset = fabsf((np.x * dpx + np.y * dpy) + np.z * dpz);
+                const bool sameObject = !frame.useIds || __float_as_uint(bq.w) == idP;
+                const bool take = reaches && inside && nq.w != 0.0f && sameObject && cosine >= frame.normalThreshold && offset <= limit;
+                hA0 = take ? hA0 + k * aq.x : hA0;
+                hA1 = take ? hA1 + k * aq.y : hA1;
+                hA2 = take ? hA2 + k * aq.z : hA2;
+                hB0 = take ? hB0 + k * bq.x : hB0;
+                hB1 = take ? hB1 + k * bq.y : hB1;
+                hB2 = take ? hB2 + k * bq.z : hB2;
+                ln = take ? ln + k * aq.w : ln;
+                ks = take ? ks + k : ks;
+            }
+        }
+        if (ks > 0.0f)
+        {
+            // blend
+            hA0 = hA0 / ks; hA1 = hA1 / ks; hA2 = hA2 / ks;
+            hB0 = hB0 / ks; hB1 = hB1 / ks; hB2 = hB2 / ks;
+            const float n = fminf(ln / ks + 1.0f, frame.maxHistory);
+            const float alpha = fmaxf(1.0f / n, frame.alphaMin);
+            a0 = hA0 + alpha * (c[0] - hA0); a1 = hA1 + alpha * (c[1] - hA1); a2 = hA2 + alpha * (c[2] - hA2);
+            b0 = hB0 + alpha * (b[0] - hB0); b1 = hB1 + alpha * (b[1] - hB1); b2 = hB2 + alpha * (b[2] - hB2);
+            length = n;
+            motionX = fx - (float)x; motionY = fy - (float)y;
+        }
+    }
+    out.a[3 * (size_t)p + 0] = a0; out.a[3 * (size_t)p + 1] = a1; out.a[3 * (size_t)p + 2] = a2;
+    out.b[3 * (size_t)p + 0] = b0; out.b[3 * (size_t)p + 1] = b1; out.b[3 * (size_t)p + 2] = b2;
+    out.length[p] = length;
+    if (out.motion) { out.motion[p] = motionX; out.motion[pixels + p] = motionY; }
+    if (out.recA)   // the context's next history: this frame's pair beside this frame's guides
+    {
+        out.recA[p] = make_float4(a0, a1, a2, length);
+        out.recB[p] = make_float4(b0, b1, b2, __uint_as_float(idP));
+        out.recN[p] = np;
+        out.recP[p] = pp;
+    }
+    if (out.image) { out.image[3 * (size_t)p + 0] = a0 * d[0]; out.image[3 * (size_t)p + 1] = a1 * d[1]; out.image[3 * (size_t)p + 2] = a2 * d[2]; }
+}

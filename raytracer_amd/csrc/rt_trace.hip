@@ -10,6 +10,7 @@
 //   rt_kat.inl            known-answer hooks (rtgpu_kat*)
 //   rt_query.inl          batched ray queries around the walks above (rtgpu_trace_rays)
 //   rt_denoise.inl        the a-trous filter (rtgpu_filter_atrous, rtgpu_denoise)
+//   rt_temporal.inl       temporal accumulation (rtgpu_temporal_accumulate, rtgpu_denoise_temporal)
 // The host side (rt_runtime.hip) launches them through the declarations of rt_trace_kernels.h.
 //
 // Compile: hipcc --offload-arch=gfx950 -O3 -ffp-contract=off
@@ -51,3 +52,4 @@ RT_K_TRACE_PER_RAY_INSTANCES(RT_X)
 
 // (behind everything else, for the same reason)
 #include "rt_denoise.inl"
+#include "rt_temporal.inl"

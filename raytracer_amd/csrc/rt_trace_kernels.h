@@ -57,6 +57,14 @@ struct AtrousLevel { int32_t step; float invN, invP, invC, varianceFloor; };   /
 #define RT_K_ATROUS_ARGS (const float4* __restrict__ recN, const float4* __restrict__ recP, const float4* __restrict__ src, float4* __restrict__ dst, \
                           const float* __restrict__ albedo, float* __restrict__ out, float* __restrict__ outVariance, uint32_t width, uint32_t height, const AtrousLevel level)
 
+// temporal accumulation (rt_temporal.inl): k_atrous's block.  What k_temporal reads, what it writes (motion, image and the four records: where asked) and the
+// call's constants (m: prevWorldToScreen)
+struct TemporalIn { const float* color; const float* colorHalf; const float* depth; const float* normal; const float* position; const float* albedo; const uint32_t* objectId;
+                    const float4* recA; const float4* recB; const float4* recN; const float4* recP; };   // (the records: the previous frame; NULL without history)
+struct TemporalOut { float* a; float* b; float* length; float* motion; float* image; float4* recA; float4* recB; float4* recN; float4* recP; };
+struct TemporalFrame { float colorScale, alphaMin, maxHistory, normalThreshold, planeTolerance, prevSampleOffset[2]; uint32_t useIds; float m[16]; };
+#define RT_K_TEMPORAL_ARGS (const TemporalIn in, const TemporalOut out, uint32_t width, uint32_t height, const TemporalFrame frame)
+
 #ifndef RT_DEVICE_KERNELS
 template <int kStack, bool kCount, bool kPerRay = false> __global__ void RT_TRACE_ATTR(kStack) k_trace RT_K_TRACE_ARGS;
 template <int kStack, bool kDiag = false, bool kLocalExact = false> __global__ void RT_TRACE_ATTR(kStack) k_trace_wide RT_K_TRACE_WIDE_ARGS;
@@ -98,7 +106,16 @@ __global__ void __launch_bounds__(RT_BLOCK) k_denoise_prepare(const float* __res
 __global__ void __launch_bounds__(RT_BLOCK) k_denoise_prepare_var(const float* __restrict__ color, const float* __restrict__ colorHalf, const float* __restrict__ depth,
                                                                   const float* __restrict__ normal, const float* __restrict__ position, const float* __restrict__ albedo,
                                                                   uint32_t pixels, float colorScale, float4* __restrict__ recN, float4* __restrict__ recP, float4* __restrict__ recC);
+__global__ void __launch_bounds__(RT_BLOCK) k_denoise_prepare_accumulated(const float* __restrict__ color, const float* __restrict__ colorHalf, const float* __restrict__ depth,
+                                                                          const float* __restrict__ normal, const float* __restrict__ position, uint32_t pixels,
+                                                                          float4* __restrict__ recN, float4* __restrict__ recP, float4* __restrict__ recC);
 template <bool kLast, bool kVar = false> __global__ void RT_ATROUS_ATTR k_atrous RT_K_ATROUS_ARGS;
 template <bool kLast, int kStep, bool kVar = false> __global__ void RT_ATROUS_TILED_ATTR k_atrous_tiled RT_K_ATROUS_ARGS;
+// temporal accumulation (rt_temporal.inl)
+__global__ void __launch_bounds__(RT_BLOCK) k_temporal_pack(const float* __restrict__ prevA, const float* __restrict__ prevB, const float* __restrict__ prevLength,
+                                                            const float* __restrict__ prevDepth, const float* __restrict__ prevNormal, const float* __restrict__ prevPosition,
+                                                            const uint32_t* __restrict__ prevObjectId, uint32_t pixels, float4* __restrict__ recA, float4* __restrict__ recB,
+                                                            float4* __restrict__ recN, float4* __restrict__ recP);
+__global__ void RT_ATROUS_ATTR k_temporal RT_K_TEMPORAL_ARGS;
 __global__ void __launch_bounds__(RT_MONSTER_BLOCK) k_trace_monster(const RtSceneDesc scene, const Paths paths, const uint32_t* __restrict__ queue, const uint32_t* __restrict__ queueCount);
 #endif
