@@ -377,6 +377,42 @@ uint32_t rtgpu_abi_version(void);
 /* --- scene: replaces Scene::BuildBVH's pointer graph; copies everything, host memory may be freed */
 int rtgpu_upload_scene(RtgpuContext* ctx, const RtSceneDesc* scene);
 
+/* --- moving objects: what the reference's demo does when the selected object is dragged -- ISceneObject::SetTransform
+ *     (Demo_UserInterface.cpp:659), then Scene::BuildBVH (:701), which rebuilds only the top-level tree over the objects' boxes; the mesh
+ *     trees belong to the shapes.  rtgpu_update_objects replaces the object table, the top-level nodes and (optionally) the light table of
+ *     the uploaded scene in place, and nothing else.
+ *   contract   numObjects and numLights equal the uploaded scene's; previousIndex is a permutation of 0 .. numObjects - 1; objects[i] equals
+ *              the device's objects[previousIndex[i]] in every field but transform and invTransform (kind, shape, both parameter vectors,
+ *              material, mesh and light index; the padding words too); lights[k] equals the device's lights[k] in every field but its two
+ *              matrices (lights are never reordered).  invTransform is the caller's, as in RtObject.
+ *   errors     a NULL argument, an abiVersion mismatch, a violated contract, a malformed top-level tree (a child or a leaf's objects out of
+ *              range, more nodes than a tree over numObjects leaves can have): RTGPU_ERR_INVALID_ARGUMENT; a leaf of more than 3 objects, or
+ *              the new top-level depth plus the deepest mesh tree beyond the 64-entry stack: RTGPU_ERR_UNSUPPORTED; before
+ *              rtgpu_upload_scene: RTGPU_ERR_NOT_READY.  A refused update leaves the scene on the device exactly as it was.
+ *   ordering   as rtgpu_upload_scene: the queued passes are submitted and every lane, ray query and AOV call is waited for first, so passes
+ *              queued before the call render the old scene and passes after it the new one.  A multi-device context updates every peer.
+ *   refreshes  the device's object table, top-level nodes and light table; the stack need; the axis-parallel-sun flag (a directional light's
+ *              direction lives in its transform); the 4-wide top level of a two-level scene (rebuilt on the host: it lies in a slab of its
+ *              own behind the mesh levels, so a top level of another size moves nothing) and the per-object level table, permuted.  The
+ *              photons of the bidirectional integrator are dropped: they show the old scene.  The history of rtgpu_denoise_temporal is kept, with each
+ *              object's motion beside it ("Temporal accumulation that follows moving objects", below).
+ *   keeps      mesh nodes, triangles, shading records, textures, materials, the mesh levels of the 4-wide trees, the 4-wide tree of a
+ *              single-mesh scene (its one object only changes its transform), the traversal kernel chosen at upload and the scene class.
+ *              Nothing whose size grows with the triangle count is read, rebuilt or copied: RtUpdateInfo::bytesUploaded states what was.
+ * rtgpu_get_update_info: the last successful update since rtgpu_upload_scene (all zero before the first): bytes copied to one device,
+ * updates so far, the depth of the new top-level tree and the RTGPU_WALK_* kernel that serves the scene. */
+typedef struct RtSceneUpdate
+{
+    uint32_t abiVersion, numObjects, numTopNodes, numLights;
+    const RtNode*   topNodes;       /* [numTopNodes] the rebuilt Scene::mTraceableObjectsBVH */
+    const RtObject* objects;        /* [numObjects]  in the NEW leaf order */
+    const uint32_t* previousIndex;  /* [numObjects]  objects[i] was objects[previousIndex[i]] of the scene as it stands on the device */
+    const RtLight*  lights;         /* [numLights]   Scene::mLights order, or NULL: the lights are unchanged */
+} RtSceneUpdate;
+int rtgpu_update_objects(RtgpuContext* ctx, const RtSceneUpdate* update);
+typedef struct RtUpdateInfo { uint64_t bytesUploaded; uint32_t numUpdates, topDepth; uint32_t walk; uint32_t _pad[3]; } RtUpdateInfo;   /* 32 bytes */
+int rtgpu_get_update_info(RtgpuContext* ctx, RtUpdateInfo* out);
+
 /* --- film: Viewport::Resize (Viewport.cpp:52-107) / Viewport::Reset (:120-138) ------------------*/
 int rtgpu_resize(RtgpuContext* ctx, uint32_t width, uint32_t height);
 int rtgpu_set_shard(RtgpuContext* ctx, RtgpuShard shard);
@@ -790,7 +826,7 @@ int rtgpu_denoise_var_async(RtgpuContext* ctx, const RtDenoiseVarParams* params,
                             float* outVariance, void* stream);
 
 /* ---------------------------------------------------------------------------------------------
- * Temporal accumulation: the other half of SVGF.  The scene is static between uploads, so reprojection is exact geometry: the world position of a
+ * Temporal accumulation: the other half of SVGF.  The scene is static between uploads and updates (objects moved by rtgpu_update_objects: the next section), so reprojection is exact geometry: the world position of a
  * pixel's first hit goes through the previous frame's worldToScreen, the previous frame's accumulated estimates are fetched bilinearly around that
  * point -- each of the four taps tested against the pixel's own surface -- and blended with this frame's.  The half-sample estimate b is accumulated
  * beside the full estimate a with the same weights: the accumulated error lum(A) - lum(B) = sum w_i e_i has E[e^2] = sum w_i^2 Var(mean_i), the
@@ -840,7 +876,7 @@ int rtgpu_denoise_var_async(RtgpuContext* ctx, const RtDenoiseVarParams* params,
  * outVariance is not written.  params->prevWorldToScreen and prevSampleOffset are ignored: the context remembers its own (guideParams' worldToScreen must
  * therefore be the matrix of guideParams' own localToWorld: the host mirror's Camera computes it in SetPerspective, not in SetTransform).  The result is by definition
  * the composition of the two pure entries on the same planes.  rtgpu_temporal_reset drops the history, and so do rtgpu_resize, rtgpu_set_shard and
- * rtgpu_upload_scene; rtgpu_reset does not -- resetting the film every frame is the use case.  Like the other denoise calls these are not passes: film,
+ * rtgpu_upload_scene (rtgpu_update_objects does not: the next section); rtgpu_reset does not -- resetting the film every frame is the use case.  Like the other denoise calls these are not passes: film,
  * both sum buffers, counters, kernel times, the photon state and the active blocks stay as they are, and the passes rendered after an _async call wait
  * for its read of both sum buffers.  The history is 128 bytes per pixel (this frame's and the previous one's, four 16-byte records each: {A, length},
  * {B, id}, {N, valid}, {P, 0}), the call's own, grown on use and freed with the context; guides and the accumulated pair are staged in the filter's
@@ -878,6 +914,50 @@ int rtgpu_denoise_temporal(RtgpuContext* ctx, const RtTemporalParams* params, co
 int rtgpu_denoise_temporal_async(RtgpuContext* ctx, const RtTemporalParams* params, const RtDenoiseVarParams* filter, const RtPassParams* guideParams,
                                  float* outRGB, float* outVariance, void* stream);
 int rtgpu_temporal_reset(RtgpuContext* ctx);
+
+/* ---------------------------------------------------------------------------------------------
+ * Temporal accumulation that follows moving objects.  Between two frames rtgpu_update_objects may have moved objects; a pixel's surface point then was
+ * somewhere else in the previous frame, and perhaps under another object id (the update reorders the object table).  For every CURRENT object id o there is
+ * a record RtObjectMotion: m takes a current world position to the world position the same surface point had in the previous frame (rows of four, the row
+ * convention of `project` above); prevId is the id the object had in the previous frame's planes; moved == 0: the object stood still.
+ * Everything not restated here is rtgpu_temporal_accumulate.
+ *   per pixel  with a valid hit and id o = objectId_p < numObjects: if moved[o] == 0, P' = P_p and N' = N_p (a select: the bits of the static call); otherwise
+ *              for lanes j = 0 .. 2
+ *                  P'_j = P.x * m[0][j] + m[3][j];  P'_j = P.y * m[1][j] + P'_j;  P'_j = P.z * m[2][j] + P'_j
+ *                  N'_j = N.x * m[0][j];            N'_j = N.y * m[1][j] + N'_j;  N'_j = N.z * m[2][j] + N'_j      (not renormalised)
+ *              every multiply and add rounded on its own.  A pixel whose id is >= numObjects starts; the table is never read out of range.
+ *   project    uses P'.
+ *   taps       a tap is taken iff q is inside the frame, prevDepth_q is finite, prevObjectId_q == prevId[o], (N'.x * N_q.x + N'.y * N_q.y) + N'.z * N_q.z >=
+ *              normalThreshold and, with dp = P_q - P', fabsf((N'.x * dp.x + N'.y * dp.y) + N'.z * dp.z) <= planeTolerance * depth_p.
+ *   the rest   outMotion, blend and start rules are unchanged; what the caller keeps as the next history are the CURRENT N, P and ids.
+ *   scope      rigid motions.  Under a scale N' is no unit normal and the plane distance is measured in the previous frame's units: the two surface tests
+ *              are then approximate, but defined.  Lighting that changed because a light or an occluder moved is not reprojected: the history lags behind
+ *              it by what alphaMin allows.
+ *   errors     as rtgpu_temporal_accumulate, and: objects NULL or numObjects == 0, objectId NULL, prevObjectId NULL beside a history:
+ *              RTGPU_ERR_INVALID_ARGUMENT; the _async entry: a table that is not 16-byte aligned device memory.
+ * The table is host memory for the synchronous entry and device memory for the _async one.
+ *
+ * rtgpu_denoise_temporal builds the table itself.  With the history it keeps, per current object, the id and the transform the object had when the history was
+ * stored; rtgpu_update_objects carries them through its previousIndex (through several updates, if there are several between two frames) and no longer
+ * drops the history.  At the next call moved[o] = 0 when the 16 words of the transform are bit-equal to the stored ones; otherwise
+ * m = invTransform_now * transform_then (row convention: world now -> local -> world then), every element computed in double, the four products of a dot
+ * product summed left to right, and rounded to float once.  A product of two floats is exact in double, so neither a contraction into fused multiply-adds
+ * nor NumPy's float64 arithmetic can round the sum differently: tests/temporal_moving_ref.py builds the same table.  When no update happened since the
+ * history was stored the call launches what it launched before objects could move, with the same arguments.
+ * --------------------------------------------------------------------------------------------- */
+/* 80 bytes (five 16-byte loads) */
+typedef struct RtObjectMotion { float m[16]; uint32_t prevId; uint32_t moved; uint32_t _pad[2]; } RtObjectMotion;
+int rtgpu_temporal_accumulate_moving(RtgpuContext* ctx, const RtTemporalParams* params, uint32_t width, uint32_t height, const float* color,
+                                     const float* colorHalf, const float* depth, const float* normal, const float* position, const float* albedo,
+                                     const uint32_t* objectId, const float* prevA, const float* prevB, const float* prevLength, const float* prevDepth,
+                                     const float* prevNormal, const float* prevPosition, const uint32_t* prevObjectId, float* outA, float* outB,
+                                     float* outLength, float* outMotion, const RtObjectMotion* objects, uint32_t numObjects);
+int rtgpu_temporal_accumulate_moving_async(RtgpuContext* ctx, const RtTemporalParams* params, uint32_t width, uint32_t height, const float* color,
+                                           const float* colorHalf, const float* depth, const float* normal, const float* position, const float* albedo,
+                                           const uint32_t* objectId, const float* prevA, const float* prevB, const float* prevLength,
+                                           const float* prevDepth, const float* prevNormal, const float* prevPosition, const uint32_t* prevObjectId,
+                                           float* outA, float* outB, float* outLength, float* outMotion, const RtObjectMotion* objects, uint32_t numObjects,
+                                           void* stream);
 
 /* rtgpu_postprocess over a caller's image (host memory, height x width x 3 floats of the context's size) in place of the sum buffer -- a
  * denoised frame, say: the same kernels, the same restrictions, and the same bits for the same input. */

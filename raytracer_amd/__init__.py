@@ -114,6 +114,25 @@ class RtSceneDesc(C.Structure):
                 ("texelBytes", C.c_uint64)]
 
 
+class RtSceneUpdate(C.Structure):
+    _fields_ = [("abiVersion", C.c_uint32), ("numObjects", C.c_uint32), ("numTopNodes", C.c_uint32), ("numLights", C.c_uint32),
+                ("topNodes", C.POINTER(RtNode)), ("objects", C.POINTER(RtObject)), ("previousIndex", C.POINTER(C.c_uint32)),
+                ("lights", C.POINTER(RtLight))]
+
+
+class RtUpdateInfo(C.Structure):
+    _fields_ = [("bytesUploaded", C.c_uint64), ("numUpdates", C.c_uint32), ("topDepth", C.c_uint32), ("walk", C.c_uint32), ("_pad", C.c_uint32 * 3)]
+
+
+def update_info(ctx):
+    """rtgpu_get_update_info as a dict: what the last rtgpu_update_objects copied to the device, and the walk that serves the scene."""
+    info = RtUpdateInfo()
+    if rtgpu_lib().rtgpu_get_update_info(ctx, C.byref(info)) != 0:
+        raise RuntimeError("rtgpu_get_update_info failed")
+    return {"bytesUploaded": int(info.bytesUploaded), "numUpdates": int(info.numUpdates), "topDepth": int(info.topDepth),
+            "walk": ["binary", "wide", "wide2"][info.walk]}
+
+
 class RtPostprocessParams(C.Structure):
     _fields_ = [("colorFilter", C.c_float * 4), ("exposure", C.c_float), ("contrast", C.c_float), ("saturation", C.c_float),
                 ("ditheringStrength", C.c_float), ("bloomFactor", C.c_float), ("tonemapper", C.c_uint32), ("numPasses", C.c_uint32),
@@ -401,9 +420,27 @@ def temporal_params(alpha_min=TEMPORAL_DEFAULTS["alpha_min"], max_history=TEMPOR
 HISTORY_KEYS = ("a", "b", "length", "depth", "normal", "position", "object_id")
 
 
+class RtObjectMotion(C.Structure):
+    _fields_ = [("m", C.c_float * 16), ("prevId", C.c_uint32), ("moved", C.c_uint32), ("_pad", C.c_uint32 * 2)]
+
+
+def object_motion_table(object_motion):
+    """(matrices (n, 4, 4), prev_ids (n,), moved (n,)) as the (n, 20) word array of RtObjectMotion records"""
+    matrices, prev_ids, moved = object_motion
+    m = np.ascontiguousarray(matrices, dtype=np.float32).reshape(-1, 16)
+    ids, flags = np.asarray(prev_ids).reshape(-1), np.asarray(moved).reshape(-1)
+    if m.shape[0] == 0 or ids.shape != (m.shape[0],) or flags.shape != (m.shape[0],):
+        raise ValueError("object_motion must be (matrices (n, 4, 4), prev_ids (n,), moved (n,)) with n >= 1")
+    table = np.zeros((m.shape[0], 20), dtype=np.uint32)
+    table[:, :16] = m.view(np.uint32)
+    table[:, 16] = ids.astype(np.uint32)
+    table[:, 17] = (flags != 0).astype(np.uint32)
+    return table
+
+
 def temporal_accumulate(color, color_half, depth, normal, position, albedo=None, object_id=None, history=None, prev_world_to_screen=None, prev_sample_offset=(0.0, 0.0),
                         alpha_min=TEMPORAL_DEFAULTS["alpha_min"], max_history=TEMPORAL_DEFAULTS["max_history"], normal_threshold=TEMPORAL_DEFAULTS["normal_threshold"],
-                        plane_tolerance=TEMPORAL_DEFAULTS["plane_tolerance"], color_scale=1.0, demodulate=True, return_motion=False, ctx=None):
+                        plane_tolerance=TEMPORAL_DEFAULTS["plane_tolerance"], color_scale=1.0, demodulate=True, return_motion=False, ctx=None, object_motion=None):
     """Temporal accumulation of include/rtgpu.h over a frame: color, color_half (H, W, 3) -- Viewport.sum_buffer(secondary=True) --, depth (H, W) or (1, H, W),
     normal, position, albedo (3, H, W) float32 and object_id (H, W) or (1, H, W) uint32 (optional) -- Viewport.render_aovs() --, as NumPy arrays or as
     contiguous torch tensors on a ROCm device (object_id: the int64 tensor render_aovs(device=True) returns, or int32 words), then on
@@ -411,8 +448,16 @@ def temporal_accumulate(color, color_half, depth, normal, position, albedo=None,
     prev_world_to_screen and prev_sample_offset of the pass its guides were rendered with (RtPassParams.camera.worldToScreen, .sampleOffset).  Returns the
     history dict of this frame -- a, b (H, W, 3): the accumulated full and half-sample estimates in history space; length (H, W); and this frame's depth,
     normal, position and object_id (the words the device reads) -- which the next call takes back and whose (a, b) go into atrous_filter(prepared=True);
-    return_motion=True: (history, the (2, H, W) motion plane).  albedo is needed with demodulate=True only; the object test needs the ids of both frames."""
+    return_motion=True: (history, the (2, H, W) motion plane).  albedo is needed with demodulate=True only; the object test needs the ids of both frames.
+    object_motion=(matrices (n, 4, 4), prev_ids (n,), moved (n,)): the objects moved between the two frames (rtgpu_temporal_accumulate_moving) -- per current
+    object id the matrix that takes a world position to where that surface point was in the previous frame, the id the object had there, and whether it
+    moved at all; NumPy arrays whichever way the frame comes.  Both id planes are required with it."""
     torch = None
+    table = None
+    if object_motion is not None:
+        table = object_motion_table(object_motion)
+        if object_id is None or (history is not None and history.get("object_id") is None):
+            raise ValueError("object_motion follows objects by their ids: it needs object_id and a history with one")
     planes = dict(color=color, color_half=color_half, depth=depth, normal=normal, position=position)
     if demodulate:
         if albedo is None:
@@ -460,8 +505,11 @@ def temporal_accumulate(color, color_half, depth, normal, position, albedo=None,
         motion = np.zeros((2, h, w), dtype=np.float32) if return_motion else None
         ptr = lambda a: a.ctypes.data_as(C.c_void_p) if a is not None else None   # noqa: E731
         context = ctx if ctx is not None else _filter_context(0)
-        r = lib.rtgpu_temporal_accumulate(context, C.byref(p), C.c_uint32(w), C.c_uint32(h), *([ptr(planes.get(name)) for name in order] +
-                                          [ptr(out["a"]), ptr(out["b"]), ptr(out["length"]), ptr(motion)]))
+        buffers = [ptr(planes.get(name)) for name in order] + [ptr(out["a"]), ptr(out["b"]), ptr(out["length"]), ptr(motion)]
+        if table is None:
+            r = lib.rtgpu_temporal_accumulate(context, C.byref(p), C.c_uint32(w), C.c_uint32(h), *buffers)
+        else:
+            r = lib.rtgpu_temporal_accumulate_moving(context, C.byref(p), C.c_uint32(w), C.c_uint32(h), *(buffers + [ptr(table), C.c_uint32(table.shape[0])]))
     else:
         device = color.device
         index = device.index if device.index is not None else torch.cuda.current_device()
@@ -473,8 +521,16 @@ def temporal_accumulate(color, color_half, depth, normal, position, albedo=None,
         motion = torch.empty((2, h, w), dtype=torch.float32, device=device) if return_motion else None
         ptr = lambda a: C.c_void_p(a.data_ptr()) if a is not None else None   # noqa: E731
         context = ctx if ctx is not None else _filter_context(index)
-        r = _run_on_torch_stream(torch, _filter_streams, device, list(planes.values()) + list(out.values()) + [motion], lambda stream: lib.rtgpu_temporal_accumulate_async(
-            context, C.byref(p), C.c_uint32(w), C.c_uint32(h), *([ptr(planes.get(name)) for name in order] + [ptr(out["a"]), ptr(out["b"]), ptr(out["length"]), ptr(motion), stream])))
+        buffers = [ptr(planes.get(name)) for name in order] + [ptr(out["a"]), ptr(out["b"]), ptr(out["length"]), ptr(motion)]
+        if table is None:
+            r = _run_on_torch_stream(torch, _filter_streams, device, list(planes.values()) + list(out.values()) + [motion], lambda stream: lib.rtgpu_temporal_accumulate_async(
+                context, C.byref(p), C.c_uint32(w), C.c_uint32(h), *(buffers + [stream])))
+        else:
+            with torch.cuda.device(device):
+                table_dev = torch.from_numpy(table.view(np.int32)).to(device)     # (ordered on the current stream, which the side stream waits for)
+            r = _run_on_torch_stream(torch, _filter_streams, device, list(planes.values()) + list(out.values()) + [motion, table_dev],
+                                     lambda stream: lib.rtgpu_temporal_accumulate_moving_async(context, C.byref(p), C.c_uint32(w), C.c_uint32(h), *(
+                                         buffers + [C.c_void_p(table_dev.data_ptr()), C.c_uint32(table.shape[0]), stream])))
     if r != 0:
         err = (lib.rtgpu_last_error() or b"").decode()
         raise (ValueError if r == -1 else RuntimeError)("temporal_accumulate failed (%d): %s" % (r, err))
@@ -671,6 +727,34 @@ class Scene:
         self.built = True
         return self
 
+    # ---- moving objects (ISceneObject::SetTransform + the top-level half of Scene::BuildBVH) ----------------------------------------
+    _OBJECT_CALLS = ("sphere", "box", "rect", "mesh", "area_light", "background_light", "directional_light", "point_light", "spot_light")
+
+    def object_count(self):
+        """Objects added so far, shapes and lights alike: the range of set_object_transform's index."""
+        return int(host_lib().rth_scene_object_count(self._h))
+
+    def set_object_transform(self, index, transform):
+        """ISceneObject::SetTransform of the object the index-th add_* call made (lights count).  Takes effect with update() (or build())."""
+        if host_lib().rth_scene_object_set_transform(self._h, C.c_uint32(index), transform) != 0:
+            raise IndexError("no object %r" % (index,))
+        added = [args for kind, args in self.calls if kind in self._OBJECT_CALLS]
+        if len(added) == self.object_count() and "transform" in added[index]:   # (objects of load_json are not in `calls`)
+            added[index]["transform"] = list(transform)
+
+    def update(self):
+        """Scene::UpdateBVH: rebuilds the top-level tree over the objects' current boxes and rewrites the flat objects, top nodes and light
+        matrices; meshes, materials and textures keep their numbering.  Viewport.update_scene() sends the result to the device."""
+        if host_lib().rth_scene_update(self._h) != 0:
+            raise RuntimeError("Scene::UpdateBVH failed (it needs a build() first)")
+        return self
+
+    def update_desc(self):
+        """The RtSceneUpdate of the last update() (pointers into the scene, valid until the next build / update)."""
+        u = RtSceneUpdate()
+        host_lib().rth_scene_update_desc(self._h, C.byref(u))
+        return u
+
     @property
     def desc(self):
         """Pointer to the flat RtSceneDesc (valid until the scene is rebuilt / destroyed)."""
@@ -792,6 +876,13 @@ class Viewport:
 
     def reset(self):
         host_lib().rth_viewport_reset(self._h)
+
+    def update_scene(self):
+        """Viewport::UpdateScene: after Scene.update(), sends the moved objects and the rebuilt top level to the renderer's device
+        (rtgpu_update_objects) -- no triangle is uploaded again.  Passes queued before the call render the scene as it was.  The accumulated
+        frame is the caller's to reset()."""
+        if host_lib().rth_viewport_update_scene(self._h) != 0:
+            raise RuntimeError("Viewport::UpdateScene failed: %s" % (rtgpu_lib().rtgpu_last_error() or b"").decode())
 
     def render(self, camera, passes=1):
         if host_lib().rth_viewport_render(self._h, camera._h, C.c_uint32(passes)) != 0:

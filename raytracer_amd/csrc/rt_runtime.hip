@@ -26,7 +26,7 @@
 //
 // This file is the translation unit and keeps the contexts, the film and the small entry points; its parts: rt_runtime_context.h (RtgpuContext, BatchLane,
 // staging copies, stream pool, HIP_TRY, LaunchTimer, free helpers), rt_knobs.h (every RTGPU_* environment variable), rt_multi.inl (multi-device contexts),
-// rt_runtime_scene.inl (rtgpu_upload_scene), rt_runtime_render.inl (arena sizing, traversal launchers, batch submission), rt_runtime_vcm.inl (bidirectional
+// rt_runtime_scene.inl (rtgpu_upload_scene, rtgpu_update_objects), rt_runtime_render.inl (arena sizing, traversal launchers, batch submission), rt_runtime_vcm.inl (bidirectional
 // integrator, Light Tracer), rt_runtime_kat.inl (known-answer hooks, rtgpu_evaluate_textures), rt_runtime_query.inl (batched ray queries), rt_runtime_paths.inl (path records),
 // rt_runtime_aov.inl (AOVs), rt_runtime_denoise.inl (the a-trous filter, rtgpu_denoise, rtgpu_postprocess_from),
 // rt_runtime_temporal.inl (temporal accumulation).
@@ -748,6 +748,14 @@ RTGPU_API int rtgpu_get_walk_info(RtgpuContext* c, RtWalkInfo* out)
     const uint32_t kernel = !useWide(c) ? RTGPU_WALK_BINARY : (c->wide.nodes ? RTGPU_WALK_WIDE : RTGPU_WALK_WIDE2);
     out->kernel = kernel; out->reserved = 0u;
     out->nodeBytes = c->walkNodeBytes[kernel]; out->leafBoxBytes = c->walkLeafBoxBytes[kernel]; out->triangleBytes = c->walkTriangleBytes;
+    return RTGPU_OK;
+}
+
+RTGPU_API int rtgpu_get_update_info(RtgpuContext* c, RtUpdateInfo* out)
+{
+    if (!c || !out) return fail(RTGPU_ERR_INVALID_ARGUMENT, "NULL argument");
+    *out = c->updatable.info;
+    out->walk = !useWide(c) ? RTGPU_WALK_BINARY : (c->wide.nodes ? RTGPU_WALK_WIDE : RTGPU_WALK_WIDE2);
     return RTGPU_OK;
 }
 

@@ -162,6 +162,17 @@ struct RtgpuContext
     std::vector<void*> sceneAllocs;
     bool sceneReady = false;
     uint32_t numLights = 0;
+    // rtgpu_update_objects: host copies of what an update is checked against and permutes, and the room the upload left for a top level of another size
+    struct Updatable
+    {
+        std::vector<RtObject> objects; std::vector<RtLight> lights;   // as they stand on the device
+        std::vector<WideLevel> levels;                                // WideScene::levels as they stand on the device (empty: the scene has no two-level 4-wide trees)
+        WideScene wide2 = {};                                         // the device arrays of those trees (RtgpuContext::wide2 is this, or empty while the top level could not be built)
+        uint32_t maxMeshDepth = 0, topNodeCapacity = 0;               // deepest mesh tree; nodes the device's top-level array holds
+        uint32_t topWideNodeCapacity = 0;                             // 4-wide nodes the top level's slab behind the mesh levels holds
+        uint64_t meshNodeBytes = 0, meshGateBytes = 0;                // the mesh levels' share of walkNodeBytes / walkLeafBoxBytes[RTGPU_WALK_WIDE2]
+        RtUpdateInfo info = {};                                       // rtgpu_get_update_info
+    } updatable;
 
     // film
     uint32_t width = 0, height = 0;
@@ -312,6 +323,11 @@ struct RtgpuContext
         float4* records = nullptr; size_t capacity = 0;   // two sets of four planes of `capacity` 16-byte records: {A, length}, {B, id}, {N, valid}, {P, 0} (128 bytes per pixel)
         uint32_t current = 0; bool have = false;          // the set that holds the previous frame; false: no history (every pixel starts)
         float worldToScreen[16] = {}, sampleOffset[2] = {};   // of the pass that frame's guides were rendered with
+        // moving objects: per CURRENT object the id and transform it had when the history was stored (rtgpu_update_objects carries them through its
+        // permutations and raises movedSince); the device copy of the RtObjectMotion table built from them
+        struct Then { uint32_t id; float transform[16]; };
+        std::vector<Then> then; bool movedSince = false;
+        RtObjectMotion* motion = nullptr; size_t motionCapacity = 0;
     } temporal;
 
     // timing
@@ -456,8 +472,8 @@ static void freeDenoise(RtgpuContext* c)
 {
     RtgpuContext::Denoise& d = c->denoise;
     if (d.done) (void)hipEventSynchronize(d.done);
-    devFree(d.records, d.io, c->temporal.records);
-    d.capacity = 0; d.ioFloats = 0; c->temporal.capacity = 0; c->temporal.have = false;
+    devFree(d.records, d.io, c->temporal.records, c->temporal.motion);
+    d.capacity = 0; d.ioFloats = 0; c->temporal.capacity = 0; c->temporal.have = false; c->temporal.motionCapacity = 0;
     if (d.done) (void)hipEventDestroy(d.done);
     if (d.sumRead) (void)hipEventDestroy(d.sumRead);
     d.done = nullptr; d.sumRead = nullptr; d.sumReadPending = false;

@@ -1,13 +1,14 @@
-// rt_runtime_scene.inl -- rtgpu_upload_scene: validation, the device copies of the scene, the 4-wide trees, the scene class.  Included by rt_runtime.hip.
+// rt_runtime_scene.inl -- rtgpu_upload_scene: validation, the device copies of the scene, the 4-wide trees, the scene class; rtgpu_update_objects: new transforms
+// and a new top level in place.  Included by rt_runtime.hip.
 
 template <typename T>
-static int uploadArray(RtgpuContext* c, const T* host, size_t count, const T** outDev)
+static int uploadArray(RtgpuContext* c, const T* host, size_t count, const T** outDev, size_t capacity = 0)   // capacity: elements to allocate, where more than count
 {
     *outDev = nullptr;
-    if (count == 0) return RTGPU_OK;
-    if (!host) return fail(RTGPU_ERR_INVALID_ARGUMENT, "scene array pointer is NULL but its count is not zero");
+    if (count == 0 && capacity == 0) return RTGPU_OK;
+    if (!host && count) return fail(RTGPU_ERR_INVALID_ARGUMENT, "scene array pointer is NULL but its count is not zero");
     void* dev = nullptr;
-    HIP_TRY(hipMalloc(&dev, count * sizeof(T)));
+    HIP_TRY(hipMalloc(&dev, (capacity > count ? capacity : count) * sizeof(T)));
     c->sceneAllocs.push_back(dev);
     HIP_TRY(rtMemcpy(dev, host, count * sizeof(T), hipMemcpyHostToDevice));
     *outDev = static_cast<const T*>(dev);
@@ -31,6 +32,14 @@ static uint32_t bvhDepth(const RtNode* nodes, uint32_t numNodes)
         stack.push_back({ n.childIndex, depth + 1 }); stack.push_back({ n.childIndex + 1, depth + 1 });
     }
     return maxDepth;
+}
+
+// a delta directional light whose direction has an exactly-zero component: EVERY next-event ray towards it is axis-parallel and goes through the re-trace launches (launchRetrace)
+static bool hasAxisParallelSun(const RtLight* lights, uint32_t numLights)
+{
+    for (uint32_t i = 0; i < numLights; ++i)
+        if (lights[i].type == RT_LIGHT_DIRECTIONAL && lights[i].isDelta && (lights[i].transform[8] == 0.0f || lights[i].transform[9] == 0.0f || lights[i].transform[10] == 0.0f)) return true;
+    return false;
 }
 
 RTGPU_API int rtgpu_upload_scene(RtgpuContext* c, const RtSceneDesc* s)
@@ -148,7 +157,10 @@ RTGPU_API int rtgpu_upload_scene(RtgpuContext* c, const RtSceneDesc* s)
     freeScene(c);
     RtSceneDesc d = *s;
     int r;
-    if ((r = uploadArray(c, s->topNodes, s->numTopNodes, &d.topNodes))) return r;
+    // (room for the largest tree over numObjects leaves -- 2 n - 1 nodes and the unused node 1 --: rtgpu_update_objects replaces the top level in place)
+    c->updatable = RtgpuContext::Updatable();
+    c->updatable.topNodeCapacity = s->numTopNodes > 2u * s->numObjects + 2u ? s->numTopNodes : 2u * s->numObjects + 2u;
+    if ((r = uploadArray(c, s->topNodes, s->numTopNodes, &d.topNodes, s->numObjects ? c->updatable.topNodeCapacity : 0u))) return r;
     if ((r = uploadArray(c, s->objects, s->numObjects, &d.objects))) return r;
     if ((r = uploadArray(c, s->lights, s->numLights, &d.lights))) return r;
     if ((r = uploadArray(c, s->globalLights, s->numGlobalLights, &d.globalLights))) return r;
@@ -226,11 +238,6 @@ RTGPU_API int rtgpu_upload_scene(RtgpuContext* c, const RtSceneDesc* s)
             memcpy(level.base, b.base, sizeof(b.base)); memcpy(level.step, b.step, sizeof(b.step)); memcpy(level.bound, b.bound, sizeof(b.bound));
             allNodes.insert(allNodes.end(), b.nodes.begin(), b.nodes.end()); allGates.insert(allGates.end(), b.gate.begin(), b.gate.end());
         };
-        if (s->numObjects > 1u)
-        {
-            const WideLevelBuild top = buildWideLevel(s->topNodes, s->numTopNodes, s->numObjects, topDepth);
-            if (top.ok) append(top, levels[s->numObjects], 0u); else ok = false;
-        }
         std::unordered_map<uint32_t, uint32_t> builtMesh;   // mesh index -> the first object whose level holds its tree (instances share it)
         for (uint32_t o = 0; o < s->numObjects && ok; ++o)
         {
@@ -245,6 +252,21 @@ RTGPU_API int rtgpu_upload_scene(RtgpuContext* c, const RtSceneDesc* s)
             append(b, levels[o], mesh.firstTriangle);
             builtMesh[obj.meshIndex] = o;
         }
+        // the top level goes BEHIND the mesh levels, into a slab that holds the largest one numObjects leaves can have (fewer 4-wide nodes than the binary
+        // tree has interior ones; two gate records per object whatever the tree): rtgpu_update_objects rebuilds it there and no mesh base moves
+        const size_t meshNodes = allNodes.size(), meshGates = allGates.size();
+        size_t usedNodes = meshNodes;
+        if (ok)
+        {
+            const WideLevelBuild top = buildWideLevel(s->topNodes, s->numTopNodes, s->numObjects, topDepth);
+            if (top.ok && top.nodes.size() / 4u <= s->numObjects && top.gate.size() == 2u * (size_t)s->numObjects)
+            {
+                append(top, levels[s->numObjects], 0u);
+                usedNodes = allNodes.size();
+                allNodes.resize(meshNodes + 4u * (size_t)s->numObjects, make_float4(0.0f, 0.0f, 0.0f, 0.0f));
+            }
+            else ok = false;
+        }
         if (ok && (allNodes.size() / 4u) < RT_NODE_CHILD_MASK && allGates.size() < 0xFFFFFFFFull)
         {
             const float4* devNodes = nullptr; const float4* devGates = nullptr; const WideLevel* devLevels = nullptr;
@@ -252,7 +274,9 @@ RTGPU_API int rtgpu_upload_scene(RtgpuContext* c, const RtSceneDesc* s)
             if ((r = uploadArray(c, allGates.data(), allGates.size(), &devGates))) return r;
             if ((r = uploadArray(c, levels.data(), levels.size(), &devLevels))) return r;
             c->wide2.nodes = devNodes; c->wide2.gate = devGates; c->wide2.levels = devLevels; c->wide2.numObjects = s->numObjects;
-            c->walkNodeBytes[RTGPU_WALK_WIDE2] = allNodes.size() * sizeof(float4); c->walkLeafBoxBytes[RTGPU_WALK_WIDE2] = allGates.size() * sizeof(float4);
+            c->walkNodeBytes[RTGPU_WALK_WIDE2] = usedNodes * sizeof(float4); c->walkLeafBoxBytes[RTGPU_WALK_WIDE2] = allGates.size() * sizeof(float4);
+            c->updatable.levels = levels; c->updatable.wide2 = c->wide2; c->updatable.topWideNodeCapacity = s->numObjects;
+            c->updatable.meshNodeBytes = meshNodes * sizeof(float4); c->updatable.meshGateBytes = meshGates * sizeof(float4);
         }
     }
     if (singleMesh)
@@ -278,6 +302,8 @@ RTGPU_API int rtgpu_upload_scene(RtgpuContext* c, const RtSceneDesc* s)
     c->walkNodeBytes[RTGPU_WALK_BINARY] = ((uint64_t)s->numTopNodes + s->numMeshNodes) * sizeof(RtNode); c->walkTriangleBytes = (uint64_t)s->numTriangles * sizeof(RtTriangle);
     c->numLights = s->numLights;
     c->traversalStackNeed = topDepth + maxMeshDepth;
+    c->updatable.maxMeshDepth = maxMeshDepth;
+    c->updatable.objects.assign(s->objects, s->objects + s->numObjects); c->updatable.lights.assign(s->lights, s->lights + s->numLights);
     bool lean = !knobs::noLean();
     for (uint32_t i = 0; i < s->numObjects && lean; ++i) lean = s->objects[i].objectKind == RT_OBJECT_SHAPE && s->objects[i].shapeKind == RT_SHAPE_MESH;
     for (uint32_t i = 0; i < s->numMaterials && lean; ++i) lean = s->materials[i].bsdf == RT_BSDF_DIFFUSE;
@@ -294,11 +320,109 @@ RTGPU_API int rtgpu_upload_scene(RtgpuContext* c, const RtSceneDesc* s)
         for (uint32_t i = 0; i < s->numTextures && simple; ++i) simple = s->textures[i].kind == RT_TEXTURE_BITMAP && RT_FORMAT_IS_SIMPLE(s->textures[i].format);
         if (simple) c->leanScene = 4;
     }
-    // a delta directional light whose direction has an exactly-zero component: EVERY next-event ray towards it is axis-parallel and goes through the re-trace launches (launchRetrace)
-    c->axisParallelSun = false;
-    for (uint32_t i = 0; i < s->numLights; ++i)
-        if (s->lights[i].type == RT_LIGHT_DIRECTIONAL && s->lights[i].isDelta && (s->lights[i].transform[8] == 0.0f || s->lights[i].transform[9] == 0.0f || s->lights[i].transform[10] == 0.0f)) c->axisParallelSun = true;
+    c->axisParallelSun = hasAxisParallelSun(s->lights, s->numLights);
     c->sceneReady = true;
     c->vcm.havePhotons = false;   // photons of another scene
+    return RTGPU_OK;
+}
+
+// ---- rtgpu_update_objects (include/rtgpu.h): new transforms and a new top level in place ------------------------------------------------------------
+// Everything is checked and built on the host first -- against the host copies RtgpuContext::Updatable keeps of the device's tables --, then copied: a refused
+// update has touched nothing.  The device arrays keep their addresses (the top-level nodes and the 4-wide top level were allocated with room for the largest
+// tree over numObjects leaves), so kernels launched afterwards read the new scene through the same RtSceneDesc / WideScene pointers.
+template <class T> static bool sameBut2Matrices(const T& a, const T& b)   // RtObject / RtLight: transform and invTransform come first
+{
+    return memcmp((const char*)&a + 128, (const char*)&b + 128, sizeof(T) - 128u) == 0;
+}
+
+RTGPU_API int rtgpu_update_objects(RtgpuContext* c, const RtSceneUpdate* u)
+{
+    if (!c || !u) return fail(RTGPU_ERR_INVALID_ARGUMENT, "NULL argument");
+    RT_FAN_OUT(c, rtgpu_update_objects(peer, u));   // every device traverses its own copy (a refusal is the same on each: the first peer returns it)
+    if (u->abiVersion != RTGPU_ABI_VERSION) return fail(RTGPU_ERR_INVALID_ARGUMENT, "RtSceneUpdate::abiVersion mismatch");
+    if (!c->sceneReady) return fail(RTGPU_ERR_NOT_READY, "rtgpu_upload_scene has not been called");
+    HIP_TRY(hipSetDevice(c->device));
+    { int fr = flushPending(c); if (fr) return fr; }
+    HIP_TRY(syncLanes(c));
+    waitQueries(c);
+    RtgpuContext::Updatable& up = c->updatable;
+    const uint32_t n = u->numObjects;
+    if (n != c->sceneDev.numObjects || u->numLights != c->sceneDev.numLights) return fail(RTGPU_ERR_INVALID_ARGUMENT, "an update keeps the scene's object and light counts");
+    if ((n && (!u->objects || !u->previousIndex)) || (u->numTopNodes && !u->topNodes)) return fail(RTGPU_ERR_INVALID_ARGUMENT, "update array pointer is NULL but its count is not zero");
+    if (n > 1u && u->numTopNodes == 0u) return fail(RTGPU_ERR_INVALID_ARGUMENT, "scene with more than one object needs a top-level BVH");
+    if (u->numTopNodes > up.topNodeCapacity) return fail(RTGPU_ERR_INVALID_ARGUMENT, "more top-level nodes than a tree over the scene's objects can have");
+    {
+        std::vector<uint8_t> seen(n, 0u);
+        for (uint32_t i = 0; i < n; ++i)
+        {
+            const uint32_t p = u->previousIndex[i];
+            if (p >= n || seen[p]) return fail(RTGPU_ERR_INVALID_ARGUMENT, "previousIndex is not a permutation");
+            seen[p] = 1u;
+            if (!sameBut2Matrices(u->objects[i], up.objects[p])) return fail(RTGPU_ERR_INVALID_ARGUMENT, "an update changes transforms only: an object differs from its predecessor in another field");
+        }
+    }
+    for (uint32_t i = 0; u->lights && i < u->numLights; ++i)
+        if (!sameBut2Matrices(u->lights[i], up.lights[i])) return fail(RTGPU_ERR_INVALID_ARGUMENT, "an update changes transforms only: a light differs from its predecessor in another field");
+    const uint32_t topDepth = bvhDepth(u->topNodes, u->numTopNodes);
+    if (topDepth == 0xFFFFFFFFu) return fail(RTGPU_ERR_INVALID_ARGUMENT, "malformed top-level BVH");
+    for (uint32_t i = 0; i < u->numTopNodes; ++i)
+    {
+        const uint32_t leaves = u->topNodes[i].leaves & 0x3FFFFFFFu;
+        if (leaves > RT_MAX_PACKED_LEAVES) return fail(RTGPU_ERR_UNSUPPORTED, "BVH leaves with more than 3 items are not supported");
+        if (leaves && (uint64_t)u->topNodes[i].childIndex + leaves > n) return fail(RTGPU_ERR_INVALID_ARGUMENT, "a top-level leaf holds objects out of range");
+    }
+    if (topDepth + up.maxMeshDepth > 64) return fail(RTGPU_ERR_UNSUPPORTED, "BVH deeper than the 64-entry traversal stack");
+
+    // the 4-wide top level and the level table in the new order (two-level scenes)
+    WideLevelBuild top;
+    std::vector<WideLevel> levels;
+    bool topFits = false;
+    if (!up.levels.empty())
+    {
+        levels.resize((size_t)n + 1u);
+        for (uint32_t i = 0; i < n; ++i) levels[i] = up.levels[u->previousIndex[i]];
+        levels[n] = up.levels[n];
+        top = buildWideLevel(u->topNodes, u->numTopNodes, n, topDepth);
+        topFits = top.ok && top.nodes.size() / 4u <= up.topWideNodeCapacity && top.gate.size() == 2u * (size_t)n;
+        if (topFits)
+        {
+            memcpy(levels[n].base, top.base, sizeof(top.base)); memcpy(levels[n].step, top.step, sizeof(top.step)); memcpy(levels[n].bound, top.bound, sizeof(top.bound));
+        }
+    }
+
+    uint64_t bytes = 0;
+    auto put = [&](const void* dev, const void* host, size_t size) -> hipError_t { bytes += size; return rtMemcpy(const_cast<void*>(dev), host, size, hipMemcpyHostToDevice); };
+    HIP_TRY(put(c->sceneDev.objects, u->objects, (size_t)n * sizeof(RtObject)));
+    HIP_TRY(put(c->sceneDev.topNodes, u->topNodes, (size_t)u->numTopNodes * sizeof(RtNode)));
+    if (u->lights) HIP_TRY(put(c->sceneDev.lights, u->lights, (size_t)u->numLights * sizeof(RtLight)));
+    if (!levels.empty())
+    {
+        if (topFits)
+        {
+            HIP_TRY(put(up.wide2.nodes + 4u * (size_t)levels[n].nodeBase, top.nodes.data(), top.nodes.size() * sizeof(float4)));
+            HIP_TRY(put(up.wide2.gate + levels[n].gateBase, top.gate.data(), top.gate.size() * sizeof(float4)));
+        }
+        HIP_TRY(put(up.wide2.levels, levels.data(), levels.size() * sizeof(WideLevel)));
+        // (a top level that cannot be built leaves the scene to the binary walk, as at upload, until an update brings one that can)
+        if (topFits) c->wide2 = up.wide2; else memset(&c->wide2, 0, sizeof(c->wide2));
+        c->walkNodeBytes[RTGPU_WALK_WIDE2] = up.meshNodeBytes + top.nodes.size() * sizeof(float4);
+        up.levels = levels;
+    }
+    c->sceneDev.numTopNodes = u->numTopNodes;
+    c->walkNodeBytes[RTGPU_WALK_BINARY] = ((uint64_t)u->numTopNodes + c->sceneDev.numMeshNodes) * sizeof(RtNode);
+    up.objects.assign(u->objects, u->objects + n);
+    if (u->lights) { up.lights.assign(u->lights, u->lights + u->numLights); c->axisParallelSun = hasAxisParallelSun(u->lights, u->numLights); }
+    c->traversalStackNeed = topDepth + up.maxMeshDepth;
+    c->vcm.havePhotons = false;   // photons of the scene as it was
+    if (c->temporal.have && c->temporal.then.size() == n)
+    {
+        // rtgpu_denoise_temporal's history stays: current object i is the one that was previousIndex[i], and carries that one's id and transform of then
+        std::vector<RtgpuContext::Temporal::Then> then(n);
+        for (uint32_t i = 0; i < n; ++i) then[i] = c->temporal.then[u->previousIndex[i]];
+        c->temporal.then.swap(then);
+        c->temporal.movedSince = true;
+    }
+    else c->temporal.have = false;
+    up.info.bytesUploaded = bytes; up.info.numUpdates++; up.info.topDepth = topDepth;
     return RTGPU_OK;
 }

@@ -32,10 +32,39 @@ static TemporalFrame temporalFrame(const RtTemporalParams* t, const float* world
     return f;
 }
 
-static void launchTemporalKernel(const TemporalIn& in, const TemporalOut& out, uint32_t width, uint32_t height, const TemporalFrame& frame, hipStream_t stream)
+// motion: the device copy of an RtObjectMotion table (objects moved between the two frames: k_temporal<true>), or NULL: the static kernel, launched as ever
+static void launchTemporalKernel(const TemporalIn& in, const TemporalOut& out, uint32_t width, uint32_t height, const TemporalFrame& frame, hipStream_t stream,
+                                 const RtObjectMotion* motion = nullptr, uint32_t numObjects = 0u)
 {
     const dim3 block(RT_DENOISE_BLOCK_X, RT_DENOISE_BLOCK_Y), grid(((width + RT_DENOISE_BLOCK_X - 1u) / RT_DENOISE_BLOCK_X) * ((height + RT_DENOISE_BLOCK_Y - 1u) / RT_DENOISE_BLOCK_Y));
-    hipLaunchKernelGGL(k_temporal, grid, block, 0, stream, in, out, width, height, frame);
+    if (!motion) { hipLaunchKernelGGL(k_temporal<false>, grid, block, 0, stream, in, out, width, height, frame); return; }
+    static_assert(sizeof(RtObjectMotion) == 5u * sizeof(float4), "k_temporal<true> reads a motion record as five float4");
+    TemporalFrameMoving moving;
+    static_cast<TemporalFrame&>(moving) = frame;
+    moving.objects = reinterpret_cast<const float4*>(motion); moving.numObjects = numObjects;
+    hipLaunchKernelGGL(k_temporal<true>, grid, block, 0, stream, in, out, width, height, moving);
+}
+
+// The motion table of rtgpu_denoise_temporal (include/rtgpu.h): then[o] = the id and transform current object o had when the history was stored.  Doubles, each dot
+// product summed left to right, rounded to float once: products of two floats are exact in double, so this is NumPy's float64 result whatever the compiler contracts.
+typedef RtgpuContext::Temporal::Then ObjectThen;
+static void buildMotionTable(const std::vector<RtObject>& now, const std::vector<ObjectThen>& then, std::vector<RtObjectMotion>& table)
+{
+    table.resize(now.size());
+    for (size_t o = 0; o < now.size(); ++o)
+    {
+        RtObjectMotion& r = table[o];
+        memset(&r, 0, sizeof(r));
+        r.prevId = then[o].id;
+        r.moved = memcmp(now[o].transform, then[o].transform, sizeof(then[o].transform)) != 0 ? 1u : 0u;
+        for (int i = 0; i < 4; ++i)
+            for (int j = 0; j < 4; ++j)
+            {
+                double sum = (double)now[o].invTransform[4 * i] * (double)then[o].transform[j];
+                for (int k = 1; k < 4; ++k) sum = sum + (double)now[o].invTransform[4 * i + k] * (double)then[o].transform[4 * k + j];
+                r.m[4 * i + j] = (float)sum;
+            }
+    }
 }
 
 // the planes of the pure entries, as the caller passed them
@@ -55,9 +84,15 @@ static const void* temporalBuffer(const TemporalPlanes& b, uint32_t k)
     return all[k];
 }
 
-static int checkTemporal(RtgpuContext* c, const RtTemporalParams* t, uint32_t width, uint32_t height, TemporalPlanes& b, bool& history)
+// the motion table of the _moving entries (NULL, 0: the entries without)
+struct TemporalMotion { const RtObjectMotion* objects; uint32_t numObjects; bool given; };
+static const TemporalMotion kNoMotion = { nullptr, 0u, false };
+
+static int checkTemporal(RtgpuContext* c, const RtTemporalParams* t, uint32_t width, uint32_t height, TemporalPlanes& b, bool& history, const TemporalMotion& motion = kNoMotion)
 {
     if (!c) return fail(RTGPU_ERR_INVALID_ARGUMENT, "NULL context");
+    if (motion.given && (!motion.objects || motion.numObjects == 0u)) return fail(RTGPU_ERR_INVALID_ARGUMENT, "the motion table is NULL or empty");
+    if (motion.given && (!b.objectId || (b.prevA && !b.prevObjectId))) return fail(RTGPU_ERR_INVALID_ARGUMENT, "moving objects are followed by their ids: both id planes are required");
     if (!t || !b.color || !b.colorHalf || !b.depth || !b.normal || !b.position || !b.outA || !b.outB || !b.outLength) return fail(RTGPU_ERR_INVALID_ARGUMENT, "NULL argument");
     if (t->flags & RT_DENOISE_DEMODULATE) { if (!b.albedo) return fail(RTGPU_ERR_INVALID_ARGUMENT, "RT_DENOISE_DEMODULATE needs the albedo plane"); }
     else b.albedo = nullptr;
@@ -70,7 +105,8 @@ static int checkTemporal(RtgpuContext* c, const RtTemporalParams* t, uint32_t wi
 }
 
 // the launches of a pure call on `stream`; every pointer is device memory
-static int launchTemporal(RtgpuContext* c, const RtTemporalParams* t, uint32_t width, uint32_t height, const TemporalPlanes& b, bool history, hipStream_t stream)
+static int launchTemporal(RtgpuContext* c, const RtTemporalParams* t, uint32_t width, uint32_t height, const TemporalPlanes& b, bool history, hipStream_t stream,
+                          const TemporalMotion& motion = kNoMotion)
 {
     RtgpuContext::Denoise& d = c->denoise;
     const size_t pixels = (size_t)width * height;
@@ -85,7 +121,8 @@ static int launchTemporal(RtgpuContext* c, const RtTemporalParams* t, uint32_t w
         in.recA = recA; in.recB = recB; in.recN = recN; in.recP = recP;
     }
     const TemporalOut out = { b.outA, b.outB, b.outLength, b.outMotion, nullptr, nullptr, nullptr, nullptr, nullptr };
-    launchTemporalKernel(in, out, width, height, temporalFrame(t, t->prevWorldToScreen, t->prevSampleOffset, history && b.objectId && b.prevObjectId), stream);
+    launchTemporalKernel(in, out, width, height, temporalFrame(t, t->prevWorldToScreen, t->prevSampleOffset, history && b.objectId && b.prevObjectId), stream,
+                         history && motion.given ? motion.objects : nullptr, motion.numObjects);   // (without history every pixel starts: the table has nothing to say)
     const hipError_t launched = hipGetLastError();
     const hipError_t recorded = hipEventRecord(d.done, stream);   // (whatever the launches answered, as launchAtrous)
     HIP_TRY(launched);
@@ -93,17 +130,15 @@ static int launchTemporal(RtgpuContext* c, const RtTemporalParams* t, uint32_t w
     return RTGPU_OK;
 }
 
-RTGPU_API int rtgpu_temporal_accumulate(RtgpuContext* c, const RtTemporalParams* t, uint32_t width, uint32_t height, const float* color, const float* colorHalf, const float* depth,
-                                        const float* normal, const float* position, const float* albedo, const uint32_t* objectId, const float* prevA, const float* prevB,
-                                        const float* prevLength, const float* prevDepth, const float* prevNormal, const float* prevPosition, const uint32_t* prevObjectId,
-                                        float* outA, float* outB, float* outLength, float* outMotion)
+// the host-pointer entries: every plane, and the motion table behind them, staged in the filter's second buffer
+static int temporalAccumulateHost(RtgpuContext* c, const RtTemporalParams* t, uint32_t width, uint32_t height, TemporalPlanes host, const TemporalMotion& motion)
 {
-    TemporalPlanes host = { color, colorHalf, depth, normal, position, albedo, objectId, prevA, prevB, prevLength, prevDepth, prevNormal, prevPosition, prevObjectId, outA, outB, outLength, outMotion };
     bool history = false;
-    int r = checkTemporal(c, t, width, height, host, history); if (r) return r;
+    int r = checkTemporal(c, t, width, height, host, history, motion); if (r) return r;
     HIP_TRY(hipSetDevice(c->device));
     const size_t n = (size_t)width * height, plane = (n + 3u) & ~(size_t)3u;   // (planes start 16-byte aligned)
-    r = ensureDenoiseIo(c, 41u * plane); if (r) return r;   // the floats per pixel of the 18 buffers
+    const size_t tableFloats = motion.given ? (size_t)motion.numObjects * (sizeof(RtObjectMotion) / sizeof(float)) : 0u;
+    r = ensureDenoiseIo(c, 41u * plane + tableFloats); if (r) return r;   // the floats per pixel of the 18 buffers
     hipStream_t stream = c->lanes[0].stream;
     HIP_TRY(hipEventSynchronize(c->denoise.done));   // the staging copies below are not ordered on a stream
     const void* staged[kTemporalBuffers];
@@ -119,21 +154,44 @@ RTGPU_API int rtgpu_temporal_accumulate(RtgpuContext* c, const RtTemporalParams*
                                     (const uint32_t*)staged[6], (const float*)staged[7], (const float*)staged[8], (const float*)staged[9], (const float*)staged[10],
                                     (const float*)staged[11], (const float*)staged[12], (const uint32_t*)staged[13], (float*)staged[14], (float*)staged[15], (float*)staged[16],
                                     (float*)staged[17] };
-    r = launchTemporal(c, t, width, height, device, history, stream); if (r) return r;
+    TemporalMotion staged_motion = motion;
+    if (motion.given)
+    {
+        HIP_TRY(rtMemcpy(cursor, motion.objects, tableFloats * sizeof(float), hipMemcpyHostToDevice));
+        staged_motion.objects = reinterpret_cast<const RtObjectMotion*>(cursor);
+    }
+    r = launchTemporal(c, t, width, height, device, history, stream, staged_motion); if (r) return r;
     HIP_TRY(hipStreamSynchronize(stream));
     for (uint32_t k = kTemporalFirstOutput; k < kTemporalBuffers; ++k)
         if (staged[k]) HIP_TRY(rtMemcpy(const_cast<void*>(temporalBuffer(host, k)), staged[k], kTemporalFloats[k] * n * sizeof(float), hipMemcpyDeviceToHost));
     return RTGPU_OK;
 }
 
-RTGPU_API int rtgpu_temporal_accumulate_async(RtgpuContext* c, const RtTemporalParams* t, uint32_t width, uint32_t height, const float* color, const float* colorHalf,
-                                              const float* depth, const float* normal, const float* position, const float* albedo, const uint32_t* objectId, const float* prevA,
-                                              const float* prevB, const float* prevLength, const float* prevDepth, const float* prevNormal, const float* prevPosition,
-                                              const uint32_t* prevObjectId, float* outA, float* outB, float* outLength, float* outMotion, void* streamHandle)
+RTGPU_API int rtgpu_temporal_accumulate(RtgpuContext* c, const RtTemporalParams* t, uint32_t width, uint32_t height, const float* color, const float* colorHalf, const float* depth,
+                                        const float* normal, const float* position, const float* albedo, const uint32_t* objectId, const float* prevA, const float* prevB,
+                                        const float* prevLength, const float* prevDepth, const float* prevNormal, const float* prevPosition, const uint32_t* prevObjectId,
+                                        float* outA, float* outB, float* outLength, float* outMotion)
 {
-    TemporalPlanes b = { color, colorHalf, depth, normal, position, albedo, objectId, prevA, prevB, prevLength, prevDepth, prevNormal, prevPosition, prevObjectId, outA, outB, outLength, outMotion };
+    const TemporalPlanes host = { color, colorHalf, depth, normal, position, albedo, objectId, prevA, prevB, prevLength, prevDepth, prevNormal, prevPosition, prevObjectId, outA, outB, outLength, outMotion };
+    return temporalAccumulateHost(c, t, width, height, host, kNoMotion);
+}
+
+RTGPU_API int rtgpu_temporal_accumulate_moving(RtgpuContext* c, const RtTemporalParams* t, uint32_t width, uint32_t height, const float* color, const float* colorHalf, const float* depth,
+                                               const float* normal, const float* position, const float* albedo, const uint32_t* objectId, const float* prevA, const float* prevB,
+                                               const float* prevLength, const float* prevDepth, const float* prevNormal, const float* prevPosition, const uint32_t* prevObjectId,
+                                               float* outA, float* outB, float* outLength, float* outMotion, const RtObjectMotion* objects, uint32_t numObjects)
+{
+    const TemporalPlanes host = { color, colorHalf, depth, normal, position, albedo, objectId, prevA, prevB, prevLength, prevDepth, prevNormal, prevPosition, prevObjectId, outA, outB, outLength, outMotion };
+    const TemporalMotion motion = { objects, numObjects, true };
+    return temporalAccumulateHost(c, t, width, height, host, motion);
+}
+
+// the device-pointer entries
+static int temporalAccumulateDevice(RtgpuContext* c, const RtTemporalParams* t, uint32_t width, uint32_t height, TemporalPlanes b, const TemporalMotion& motion, void* streamHandle)
+{
     bool history = false;
-    int r = checkTemporal(c, t, width, height, b, history); if (r) return r;
+    int r = checkTemporal(c, t, width, height, b, history, motion); if (r) return r;
+    if (motion.given && ((uintptr_t)motion.objects & 15u)) return fail(RTGPU_ERR_INVALID_ARGUMENT, "the motion table must be 16-byte aligned device memory");
     const size_t n = (size_t)width * height;
     // every buffer aligned; each output against everything before it
     for (uint32_t o = 0; o < kTemporalBuffers; ++o)
@@ -151,7 +209,27 @@ RTGPU_API int rtgpu_temporal_accumulate_async(RtgpuContext* c, const RtTemporalP
     }
     HIP_TRY(hipSetDevice(c->device));
     hipStream_t stream = streamHandle ? (hipStream_t)streamHandle : c->lanes[0].stream;
-    return launchTemporal(c, t, width, height, b, history, stream);
+    return launchTemporal(c, t, width, height, b, history, stream, motion);
+}
+
+RTGPU_API int rtgpu_temporal_accumulate_async(RtgpuContext* c, const RtTemporalParams* t, uint32_t width, uint32_t height, const float* color, const float* colorHalf,
+                                              const float* depth, const float* normal, const float* position, const float* albedo, const uint32_t* objectId, const float* prevA,
+                                              const float* prevB, const float* prevLength, const float* prevDepth, const float* prevNormal, const float* prevPosition,
+                                              const uint32_t* prevObjectId, float* outA, float* outB, float* outLength, float* outMotion, void* streamHandle)
+{
+    const TemporalPlanes b = { color, colorHalf, depth, normal, position, albedo, objectId, prevA, prevB, prevLength, prevDepth, prevNormal, prevPosition, prevObjectId, outA, outB, outLength, outMotion };
+    return temporalAccumulateDevice(c, t, width, height, b, kNoMotion, streamHandle);
+}
+
+RTGPU_API int rtgpu_temporal_accumulate_moving_async(RtgpuContext* c, const RtTemporalParams* t, uint32_t width, uint32_t height, const float* color, const float* colorHalf,
+                                                     const float* depth, const float* normal, const float* position, const float* albedo, const uint32_t* objectId,
+                                                     const float* prevA, const float* prevB, const float* prevLength, const float* prevDepth, const float* prevNormal,
+                                                     const float* prevPosition, const uint32_t* prevObjectId, float* outA, float* outB, float* outLength, float* outMotion,
+                                                     const RtObjectMotion* objects, uint32_t numObjects, void* streamHandle)
+{
+    const TemporalPlanes b = { color, colorHalf, depth, normal, position, albedo, objectId, prevA, prevB, prevLength, prevDepth, prevNormal, prevPosition, prevObjectId, outA, outB, outLength, outMotion };
+    const TemporalMotion motion = { objects, numObjects, true };
+    return temporalAccumulateDevice(c, t, width, height, b, motion, streamHandle);
 }
 
 RTGPU_API int rtgpu_temporal_reset(RtgpuContext* c)
@@ -206,7 +284,25 @@ static int denoiseTemporalFrame(RtgpuContext* c, const RtTemporalParams* t, cons
     TemporalIn in = { c->sum, c->secondary, dDepth, dNormal, dPosition, (t->flags & RT_DENOISE_DEMODULATE) ? dAlbedo : nullptr, dId, nullptr, nullptr, nullptr, nullptr };
     if (h.have) { in.recA = from; in.recB = from + h.capacity; in.recN = from + 2u * h.capacity; in.recP = from + 3u * h.capacity; }
     const TemporalOut res = { dA, dB, dLength, nullptr, v ? nullptr : out, to, to + h.capacity, to + 2u * h.capacity, to + 3u * h.capacity };
-    launchTemporalKernel(in, res, c->width, c->height, temporalFrame(t, h.worldToScreen, h.sampleOffset, h.have), stream);
+    const RtObjectMotion* motion = nullptr;
+    const std::vector<RtObject>& objects = c->updatable.objects;
+    if (h.have && h.movedSince && !objects.empty() && h.then.size() == objects.size())
+    {
+        // objects were updated since the history was stored: where each was then.  (The table is small and the copy is not ordered on a stream: the kernel
+        // of the previous call may still read the last one.)
+        std::vector<RtObjectMotion> table;
+        buildMotionTable(objects, h.then, table);
+        HIP_TRY(hipEventSynchronize(c->denoise.done));
+        if (h.motionCapacity < table.size())
+        {
+            devFree(h.motion); h.motionCapacity = 0;
+            HIP_TRY(hipMalloc((void**)&h.motion, table.size() * sizeof(RtObjectMotion)));
+            h.motionCapacity = table.size();
+        }
+        HIP_TRY(rtMemcpy(h.motion, table.data(), table.size() * sizeof(RtObjectMotion), hipMemcpyHostToDevice));
+        motion = h.motion;
+    }
+    launchTemporalKernel(in, res, c->width, c->height, temporalFrame(t, h.worldToScreen, h.sampleOffset, h.have), stream, motion, (uint32_t)objects.size());
     const hipError_t launched = hipGetLastError();
     const hipError_t recorded = hipEventRecord(c->denoise.done, stream);
     HIP_TRY(launched);
@@ -217,6 +313,9 @@ static int denoiseTemporalFrame(RtgpuContext* c, const RtTemporalParams* t, cons
     d.sumReadPending = true;
     // this frame is the next call's history
     h.current ^= 1u; h.have = true;
+    h.movedSince = false;
+    h.then.resize(objects.size());
+    for (size_t o = 0; o < objects.size(); ++o) { h.then[o].id = (uint32_t)o; memcpy(h.then[o].transform, objects[o].transform, sizeof(h.then[o].transform)); }
     memcpy(h.worldToScreen, guideParams->camera.worldToScreen, sizeof(h.worldToScreen));
     h.sampleOffset[0] = guideParams->sampleOffset[0]; h.sampleOffset[1] = guideParams->sampleOffset[1];
     if (v)

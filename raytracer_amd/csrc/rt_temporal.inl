@@ -10,6 +10,11 @@
 //                     branch around it (a tap outside the frame loads the pixel's own address and is dropped by a select, as atrousTap does).  Neighbours
 //                     share three of their four taps under coherent motion: the caches do what an LDS tile would.  It writes the planar outputs and,
 //                     where asked, the records of the next frame's history and the remodulated image; every per-pixel operation exists once.
+//   k_temporal<true>  the scene's objects moved between the two frames (rtgpu_update_objects): the pixel's object id selects an 80-byte record of the motion
+//                     table -- one lane-indexed gather of five 16-byte loads; the table holds some hundred objects and neighbours share their object, so it
+//                     is served from the caches, mostly as a broadcast -- whose matrix takes position and normal to where that surface point was in the
+//                     previous frame.  Projection and the tap tests use the moved pair and the id the object had then; the stored history keeps this
+//                     frame's own.  An unmoved object selects its own position and normal: the bits of k_temporal<false>.
 
 __global__ void __launch_bounds__(RT_BLOCK) k_temporal_pack(const float* __restrict__ prevA, const float* __restrict__ prevB, const float* __restrict__ prevLength,
                                                             const float* __restrict__ prevDepth, const float* __restrict__ prevNormal, const float* __restrict__ prevPosition,
@@ -33,7 +38,7 @@ RT_DEV float4 temporalRecord(const float4* __restrict__ src, uint32_t q)
     return make_float4(lanes.x, lanes.y, lanes.z, lanes.w);
 }
 
-__global__ void RT_ATROUS_ATTR k_temporal RT_K_TEMPORAL_ARGS
+template <bool kMoving> __global__ void RT_ATROUS_ATTR k_temporal RT_K_TEMPORAL_ARGS
 {
     // (blocks numbered row by row along grid.x, as k_atrous numbers them)
     const uint32_t blocksX = (width + RT_DENOISE_BLOCK_X - 1u) / RT_DENOISE_BLOCK_X, blockY = blockIdx.x / blocksX, blockX = blockIdx.x - blockY * blocksX;
@@ -64,21 +69,48 @@ __global__ void RT_ATROUS_ATTR k_temporal RT_K_TEMPORAL_ARGS
     float a0 = c[0], a1 = c[1], a2 = c[2], b0 = b[0], b1 = b[1], b2 = b[2], length = 1.0f, motionX = 0.0f, motionY = 0.0f;   // a pixel that starts
     if (in.recA)   // (uniform: NULL without history)
     {
+        // where the pixel's surface point was in the previous frame (pm, nm) and the id its object had there: its own, unless objects moved
+        float4 pm = pp, nm = np;
+        uint32_t idThen = idP;
+        bool known = true;
+        if constexpr (kMoving)
+        {
+            known = idP < frame.numObjects;   // (a miss carries RT_INVALID_OBJECT; the table is never read out of range)
+            const float4* const record = frame.objects + 5u * (size_t)(known ? idP : 0u);
+            const float4 r0 = temporalRecord(record, 0u), r1 = temporalRecord(record, 1u), r2 = temporalRecord(record, 2u), r3 = temporalRecord(record, 3u);
+            const float4 tail = temporalRecord(record, 4u);
+            const bool moved = __float_as_uint(tail.y) != 0u;
+            idThen = __float_as_uint(tail.x);
+            const float rows[3][4] = { { r0.x, r1.x, r2.x, r3.x }, { r0.y, r1.y, r2.y, r3.y }, { r0.z, r1.z, r2.z, r3.z } };   // [lane j] = m[0][j], m[1][j], m[2][j], m[3][j]
+            float pj[3], nj[3];
+#pragma unroll
+            for (uint32_t j = 0; j < 3u; ++j)
+            {
+                pj[j] = pp.x * rows[j][0] + rows[j][3];
+                pj[j] = pp.y * rows[j][1] + pj[j];
+                pj[j] = pp.z * rows[j][2] + pj[j];
+                nj[j] = np.x * rows[j][0];
+                nj[j] = np.y * rows[j][1] + nj[j];
+                nj[j] = np.z * rows[j][2] + nj[j];
+            }
+            pm = make_float4(moved ? pj[0] : pp.x, moved ? pj[1] : pp.y, moved ? pj[2] : pp.z, 0.0f);
+            nm = make_float4(moved ? nj[0] : np.x, moved ? nj[1] : np.y, moved ? nj[2] : np.z, np.w);
+        }
         // project: transformPoint's operations, lane by lane
         float t[4];
 #pragma unroll
         for (uint32_t j = 0; j < 4u; ++j)
         {
-            t[j] = pp.x * frame.m[j] + frame.m[12u + j];
-            t[j] = pp.y * frame.m[4u + j] + t[j];
-            t[j] = pp.z * frame.m[8u + j] + t[j];
+            t[j] = pm.x * frame.m[j] + frame.m[12u + j];
+            t[j] = pm.y * frame.m[4u + j] + t[j];
+            t[j] = pm.z * frame.m[8u + j] + t[j];
         }
         const float u = (t[0] / t[3]) * 0.5f + 0.5f, v = (t[1] / t[3]) * 0.5f + 0.5f;
         const float fw = (float)w, fh = (float)h;
         const float fx = u * fw - frame.prevSampleOffset[0];
         const float fr = v * fh - frame.prevSampleOffset[1];
         const float fy = (float)(h - 1) - fr;
-        const bool reaches = valid && t[2] > 0.0f && fx > -1.0f && fx < fw && fy > -1.0f && fy < fh;   // (false for a NaN; before any conversion to integer)
+        const bool reaches = valid && known && t[2] > 0.0f && fx > -1.0f && fx < fw && fy > -1.0f && fy < fh;   // (false for a NaN; before any conversion to integer)
         // taps: a pixel that does not reach the previous frame takes them around (0, 0) and drops the lot
         const float sx = reaches ? fx : 0.0f, sy = reaches ? fy : 0.0f;
         const float flx = floorf(sx), fly = floorf(sy);
@@ -97,10 +129,10 @@ __global__ void RT_ATROUS_ATTR k_temporal RT_K_TEMPORAL_ARGS
                 const uint32_t q = inside ? (uint32_t)qy * width + (uint32_t)qx : p;
                 const float4 aq = temporalRecord(in.recA, q), bq = temporalRecord(in.recB, q), nq = temporalRecord(in.recN, q), pq = temporalRecord(in.recP, q);
                 const float k = (ta ? tx : 1.0f - tx) * (tb ? ty : 1.0f - ty);
-                const float dpx = pq.x - pp.x, dpy = pq.y - pp.y, dpz = pq.z - pp.z;
-                const float cosine = (np.x * nq.x + np.y * nq.y) + np.z * nq.z;
-                const float offset = fabsf((np.x * dpx + np.y * dpy) + np.z * dpz);
-                const bool sameObject = !frame.useIds || __float_as_uint(bq.w) == idP;
+                const float dpx = pq.x - pm.x, dpy = pq.y - pm.y, dpz = pq.z - pm.z;
+                const float cosine = (nm.x * nq.x + nm.y * nq.y) + nm.z * nq.z;
+                const float offset = fabsf((nm.x * dpx + nm.y * dpy) + nm.z * dpz);
+                const bool sameObject = !frame.useIds || __float_as_uint(bq.w) == idThen;
                 const bool take = reaches && inside && nq.w != 0.0f && sameObject && cosine >= frame.normalThreshold && offset <= limit;
                 hA0 = take ? hA0 + k * aq.x : hA0;
                 hA1 = take ? hA1 + k * aq.y : hA1;
@@ -138,3 +170,6 @@ __global__ void RT_ATROUS_ATTR k_temporal RT_K_TEMPORAL_ARGS
     }
     if (out.image) { out.image[3 * (size_t)p + 0] = a0 * d[0]; out.image[3 * (size_t)p + 1] = a1 * d[1]; out.image[3 * (size_t)p + 2] = a2 * d[2]; }
 }
+
+template __global__ void RT_ATROUS_ATTR k_temporal<false>(const TemporalIn, const TemporalOut, uint32_t, uint32_t, const TemporalFrame);
+template __global__ void RT_ATROUS_ATTR k_temporal<true>(const TemporalIn, const TemporalOut, uint32_t, uint32_t, const TemporalFrameMoving);

@@ -63,7 +63,12 @@ struct TemporalIn { const float* color; const float* colorHalf; const float* dep
                     const float4* recA; const float4* recB; const float4* recN; const float4* recP; };   // (the records: the previous frame; NULL without history)
 struct TemporalOut { float* a; float* b; float* length; float* motion; float* image; float4* recA; float4* recB; float4* recN; float4* recP; };
 struct TemporalFrame { float colorScale, alphaMin, maxHistory, normalThreshold, planeTolerance, prevSampleOffset[2]; uint32_t useIds; float m[16]; };
-#define RT_K_TEMPORAL_ARGS (const TemporalIn in, const TemporalOut out, uint32_t width, uint32_t height, const TemporalFrame frame)
+// k_temporal<true>, moving objects: the frame's constants and the motion table -- five float4 per object, RtObjectMotion's 80 bytes: the rows of m, then
+// {prevId, moved, 0, 0}.  The static instantiation takes TemporalFrame itself: its argument list is what it was before objects could move.
+struct TemporalFrameMoving : TemporalFrame { const float4* objects; uint32_t numObjects; };
+template <bool kMoving> struct TemporalFrameOf { typedef TemporalFrame type; };
+template <> struct TemporalFrameOf<true> { typedef TemporalFrameMoving type; };
+#define RT_K_TEMPORAL_ARGS (const TemporalIn in, const TemporalOut out, uint32_t width, uint32_t height, const typename TemporalFrameOf<kMoving>::type frame)
 
 #ifndef RT_DEVICE_KERNELS
 template <int kStack, bool kCount, bool kPerRay = false> __global__ void RT_TRACE_ATTR(kStack) k_trace RT_K_TRACE_ARGS;
@@ -116,6 +121,6 @@ __global__ void __launch_bounds__(RT_BLOCK) k_temporal_pack(const float* __restr
                                                             const float* __restrict__ prevDepth, const float* __restrict__ prevNormal, const float* __restrict__ prevPosition,
                                                             const uint32_t* __restrict__ prevObjectId, uint32_t pixels, float4* __restrict__ recA, float4* __restrict__ recB,
                                                             float4* __restrict__ recN, float4* __restrict__ recP);
-__global__ void RT_ATROUS_ATTR k_temporal RT_K_TEMPORAL_ARGS;
+template <bool kMoving = false> __global__ void RT_ATROUS_ATTR k_temporal RT_K_TEMPORAL_ARGS;
 __global__ void __launch_bounds__(RT_MONSTER_BLOCK) k_trace_monster(const RtSceneDesc scene, const Paths paths, const uint32_t* __restrict__ queue, const uint32_t* __restrict__ queueCount);
 #endif

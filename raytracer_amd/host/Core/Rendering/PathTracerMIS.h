@@ -32,6 +32,9 @@ public:
     bool SetShard(uint32 rank, uint32 worldSize);
     // uploads the scene (if it changed) as the first pass would: what the ray queries of the device context (rtgpu_trace_rays) walk
     bool UploadScene() { return EnsureSceneUploaded(); }
+    // after Scene::UpdateBVH: sends the moved objects and the new top level alone (rtgpu_update_objects); a scene that was never uploaded, was rebuilt, or
+    // was updated more than once since this renderer saw it goes up whole instead
+    bool UpdateScene() { return EnsureSceneUploaded(); }
 
 protected:
     // wholeFrameOnOneDevice: integrators that splat over the frame (Light Tracer, VCM) ignore SetRendererDevices
@@ -41,6 +44,7 @@ private:
     bool EnsureSceneUploaded();
     RtgpuContext* mCtx = nullptr;
     uint64 mUploadedBuildId = ~0ull;
+    uint64 mUploadedUpdateId = 0;
     std::vector<uint16> mBlueNoise;
 };
 

@@ -32,6 +32,7 @@ public:
     bool SetRenderer(const RendererPtr& renderer);
     bool Render(const Camera& camera);
     void Reset();
+    bool UpdateScene();   // sends what Scene::UpdateBVH changed to the renderer's device (mirror-only, like UpdateBVH)
 
     // Synchronises with the device and returns the accumulated (not tone-mapped) image.
     const Bitmap& GetSumBuffer();

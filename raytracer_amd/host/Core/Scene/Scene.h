@@ -19,6 +19,16 @@ public:
     void AddObject(SceneObjectPtr object);
     bool BuildBVH();
 
+    // Moving objects (mirror-only; what the reference's demo does with ISceneObject::SetTransform and a second BuildBVH, Demo_UserInterface.cpp:659,701, minus
+    // the re-flatten).  SetObjectTransform: the object of the index-th AddObject call.  UpdateBVH: rebuilds mTraceableObjectsBVH over the current boxes, reorders
+    // mTraceableObjects and rewrites only the flat objects, the flat top nodes and the matrices of the flat lights; materials, meshes and textures keep the
+    // numbering of the last BuildBVH (Flatten interns them in leaf order: a re-flatten after a reorder may renumber them).  Needs a BuildBVH before it.
+    bool SetObjectTransform(uint32 index, const math::Matrix4& matrix);
+    bool UpdateBVH();
+    // what rtgpu_update_objects takes after UpdateBVH; previousIndex relates the leaf order to the one before that UpdateBVH
+    void GetUpdate(RtSceneUpdate& out) const;
+    uint64 GetUpdateId() const { return mUpdateId; }   // UpdateBVH calls since the last BuildBVH
+
     uint32 GetNumObjects() const { return (uint32)mAllObjects.size(); }
     const std::vector<const LightSceneObject*>& GetLights() const { return mLights; }
     const std::vector<const LightSceneObject*>& GetGlobalLights() const { return mGlobalLights; }
@@ -54,6 +64,8 @@ private:
     std::vector<uint8> mFlatTexels;
     RtSceneDesc mDesc;
     uint64 mBuildId = 0;
+    std::vector<uint32> mPreviousIndex;
+    uint64 mUpdateId = 0;
 };
 
 } // namespace rt

@@ -439,7 +439,76 @@ bool Scene::Flatten()
     mDesc.vertexShading = mFlatVertexShading.data();
     mDesc.blueNoise = nullptr;
     mBuildId++;
+    mUpdateId = 0;
+    mPreviousIndex.clear();
     return true;
+}
+
+bool Scene::SetObjectTransform(uint32 index, const Matrix4& matrix)
+{
+    if (index >= mAllObjects.size()) return false;
+    mAllObjects[index]->SetTransform(matrix);
+    return true;
+}
+
+bool Scene::UpdateBVH()
+{
+    if (mBuildId == 0 || mFlatObjects.size() != mTraceableObjects.size()) return false;
+    // the flat record each object has, by object: everything but the matrices stays as the last Flatten() wrote it
+    std::map<const ISceneObject*, uint32> previous;
+    for (uint32 i = 0; i < mTraceableObjects.size(); ++i) previous[mTraceableObjects[i]] = i;
+
+    // the builder sees the objects in AddObject order, as in BuildBVH: the tree is the one a fresh scene with these transforms gets
+    std::vector<const ISceneObject*> traceable;
+    for (const auto& object : mAllObjects)
+        if (previous.count(object.get())) traceable.push_back(object.get());
+    if (traceable.size() != mTraceableObjects.size()) return false;
+    std::vector<Box> boxes;
+    boxes.reserve(traceable.size());
+    for (const ISceneObject* obj : traceable) boxes.push_back(obj->GetBoundingBox());
+
+    BVHBuilder::Indices newOrder;
+    BVHBuilder builder(mTraceableObjectsBVH);
+    if (!builder.Build(boxes.data(), (uint32)traceable.size(), BvhBuildingParams(), newOrder)) return false;
+
+    const std::vector<RtObject> oldFlat = mFlatObjects;
+    mPreviousIndex.resize(traceable.size());
+    for (uint32 i = 0; i < traceable.size(); ++i)
+    {
+        const ISceneObject* obj = traceable[newOrder[i]];
+        mTraceableObjects[i] = obj;
+        mPreviousIndex[i] = previous[obj];
+        RtObject& O = mFlatObjects[i];
+        O = oldFlat[mPreviousIndex[i]];
+        obj->GetTransform().Store(O.transform);
+        obj->GetInverseTransform().Store(O.invTransform);
+    }
+    for (size_t i = 0; i < mLights.size() && i < mFlatLights.size(); ++i)
+    {
+        mLights[i]->GetTransform().Store(mFlatLights[i].transform);
+        mLights[i]->GetInverseTransform().Store(mFlatLights[i].invTransform);
+    }
+    mFlatTopNodes.clear();
+    CopyNodes(mTraceableObjectsBVH, mFlatTopNodes);
+    mDesc.numTopNodes = (uint32)mFlatTopNodes.size();
+    mDesc.topNodes = mFlatTopNodes.data();
+    mDesc.objects = mFlatObjects.data();
+    mDesc.lights = mFlatLights.data();
+    mUpdateId++;
+    return true;
+}
+
+void Scene::GetUpdate(RtSceneUpdate& out) const
+{
+    memset(&out, 0, sizeof(out));
+    out.abiVersion = RTGPU_ABI_VERSION;
+    out.numObjects = (uint32)mFlatObjects.size();
+    out.numTopNodes = (uint32)mFlatTopNodes.size();
+    out.numLights = (uint32)mFlatLights.size();
+    out.topNodes = mFlatTopNodes.data();
+    out.objects = mFlatObjects.data();
+    out.previousIndex = mPreviousIndex.data();
+    out.lights = mFlatLights.data();
 }
 
 } // namespace rt

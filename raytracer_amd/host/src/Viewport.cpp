@@ -526,6 +526,14 @@ bool Viewport::SetRenderer(const RendererPtr& renderer)
     return true;
 }
 
+// After Scene::UpdateBVH: the renderer's device takes the moved objects now (passes queued so far render the scene as it was).  The accumulated
+// frame is the caller's to Reset(): it shows the old scene.
+bool Viewport::UpdateScene()
+{
+    PathTracerMIS* renderer = dynamic_cast<PathTracerMIS*>(mRenderer.get());
+    return renderer && renderer->UpdateScene();
+}
+
 bool Viewport::SetRenderingParams(const RenderingParams& params)
 {
     if (params.maxRayDepth >= 255u || params.antiAliasingSpread < 0.0f) return false;
@@ -864,7 +872,20 @@ const char* PathTracerMIS::GetName() const { return "Path Tracer MIS"; }
 bool PathTracerMIS::EnsureSceneUploaded()
 {
     if (!mCtx) return false;
-    if (mUploadedBuildId == mScene.GetBuildId()) return true;
+    if (mUploadedBuildId == mScene.GetBuildId() && mUploadedUpdateId == mScene.GetUpdateId()) return true;
+    if (mUploadedBuildId == mScene.GetBuildId() && mUploadedUpdateId + 1 == mScene.GetUpdateId())
+    {
+        // one Scene::UpdateBVH ahead of the device: its previousIndex relates exactly these two states
+        RtSceneUpdate update;
+        mScene.GetUpdate(update);
+        if (rtgpu_update_objects(mCtx, &update) != RTGPU_OK)
+        {
+            fprintf(stderr, "[rt] ERROR: scene update failed: %s\n", rtgpu_last_error());
+            return false;
+        }
+        mUploadedUpdateId = mScene.GetUpdateId();
+        return true;
+    }
     RtSceneDesc desc = mScene.GetDesc();
     desc.blueNoise = mBlueNoise.empty() ? nullptr : mBlueNoise.data();
     if (rtgpu_upload_scene(mCtx, &desc) != RTGPU_OK)
@@ -873,6 +894,7 @@ bool PathTracerMIS::EnsureSceneUploaded()
         return false;
     }
     mUploadedBuildId = mScene.GetBuildId();
+    mUploadedUpdateId = mScene.GetUpdateId();
     return true;
 }
 

@@ -316,6 +316,15 @@ RTH_API int rth_kat_parse_double(const char* text, double* out) { return helpers
 
 RTH_API int rth_scene_build(void* sh) { return static_cast<SceneHandle*>(sh)->scene.BuildBVH() ? 0 : -1; }
 RTH_API const RtSceneDesc* rth_scene_desc(void* sh) { return &static_cast<SceneHandle*>(sh)->scene.GetDesc(); }
+// moving objects: addIndex = the position among the AddObject calls (shapes and lights alike); rth_scene_update = Scene::UpdateBVH
+RTH_API uint32_t rth_scene_object_count(void* sh) { return static_cast<SceneHandle*>(sh)->scene.GetNumObjects(); }
+RTH_API int rth_scene_object_set_transform(void* sh, uint32_t addIndex, const float m16[16])
+{
+    return m16 && static_cast<SceneHandle*>(sh)->scene.SetObjectTransform(addIndex, LoadMatrix(m16)) ? 0 : -1;
+}
+RTH_API int rth_scene_update(void* sh) { return static_cast<SceneHandle*>(sh)->scene.UpdateBVH() ? 0 : -1; }
+// the RtSceneUpdate of the last rth_scene_update (pointers into the scene, valid until the next build or update)
+RTH_API void rth_scene_update_desc(void* sh, RtSceneUpdate* out) { static_cast<SceneHandle*>(sh)->scene.GetUpdate(*out); }
 
 // ---- camera -----------------------------------------------------------------------------------------
 RTH_API void* rth_camera_create() { return new Camera(); }
@@ -375,6 +384,7 @@ RTH_API int rth_viewport_upload_scene(void* v)
     PathTracerMIS* r = dynamic_cast<PathTracerMIS*>(static_cast<ViewportHandle*>(v)->renderer.get());
     return r && r->UploadScene() ? 0 : -1;
 }
+RTH_API int rth_viewport_update_scene(void* v) { return static_cast<ViewportHandle*>(v)->viewport.UpdateScene() ? 0 : -1; }
 // the devices of renderers created afterwards (SetRendererDevices); n == 0: back to one device
 RTH_API void rth_set_renderer_devices(const int* devices, uint32_t n) { SetRendererDevices(std::vector<int>(devices, devices + n)); }
 // the public knobs of the "VCM" renderer (no-op with -3 when the viewport's renderer is not VCM); weights = 5 scalars:

@@ -1,0 +1,216 @@
+#!/usr/bin/env python3
+"""Cost and worth of moving objects between frames (include/rtgpu.h: rtgpu_update_objects, temporal accumulation that follows moving objects) on the
+Sponza-class 1920 x 1080 frame: the 262 176-triangle mesh (raytracer_amd.scenes.sponza_class_mesh) plus a handful of objects that orbit in front of the camera
+-- two spheres, a box and a small mesh (12 triangles) -- so that the scene takes the two-level 4-wide walk.  `--passes` passes per frame, the film reset
+between frames, the orbit advanced by `--step` degrees per frame.
+
+Times (after a warm-up; `--reps` repetitions: median, min, max):
+  host_update            Scene.update(): the top-level tree rebuilt over the objects' boxes, the flat objects rewritten (host wall time)
+  update_objects         Viewport.update_scene() -> rtgpu_update_objects of that update (host wall time; the call synchronises as rtgpu_upload_scene does)
+  upload_scene           rtgpu_upload_scene of the same scene, for comparison (host wall time), and `bytes_uploaded` by the update (rtgpu_get_update_info)
+  k_temporal_static      rtgpu_temporal_accumulate_async on device tensors with a history: k_temporal_pack + k_temporal<false> (device events)
+  k_temporal_moving      rtgpu_temporal_accumulate_moving_async on the same tensors and a device table: k_temporal_pack + k_temporal<true>
+`k_temporal_motion_table_ms` is the difference of the two medians: what the table costs the kernel.
+
+Worth: the relative MSE, mean((x - ref)^2 / (ref^2 + 0.01)), against a render of `--reference-passes` passes of the scene as it stands after `--frames` frames,
+over the whole frame and over the pixels of the orbiting objects alone, of
+  a  this feature: update_scene() + Viewport.denoise(temporal=True) every frame, the history kept across the moves
+  b  the history dropped at every move (what a caller had to do: every move was a new scene)
+  c  rtgpu_denoise_var on the last frame alone
+The history follows surfaces, not light: where a moved object's shadow was, and on a surface that turned towards or away from a light, it lags by what alphaMin
+allows.  Under the scene's sun (20 000 units through a one-degree cone) that lag dominates a RELATIVE error; --no-sun measures the same frames under the sky alone.
+Prints one JSON line and, with --output, writes it to a file.
+
+  python tools/bench_update.py [--reps 20] [--output profiles/update_bench_1080p.json]"""
+import argparse
+import ctypes as C
+import json
+import math
+import os
+import sys
+import time
+
+import numpy as np
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+sys.path.insert(0, os.path.join(ROOT, "tools"))
+
+from bench_denoise import time_call   # noqa: E402
+
+ORBIT_CENTRE, ORBIT_RADIUS = (-6.0, 2.0, 0.6), 2.2
+NAMES = ("color", "color_half", "depth", "normal", "position", "albedo", "object_id", "prev_a", "prev_b", "prev_length", "prev_depth", "prev_normal", "prev_position",
+         "prev_object_id")
+
+
+def wall(fn, reps):
+    ms = []
+    for _ in range(reps):
+        t0 = time.perf_counter()
+        fn()
+        ms.append(1e3 * (time.perf_counter() - t0))
+    ms = np.array(ms)
+    return {"ms_median": float(np.median(ms)), "ms_min": float(ms.min()), "ms_max": float(ms.max())}
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--reps", type=int, default=20)
+    ap.add_argument("--width", type=int, default=1920)
+    ap.add_argument("--height", type=int, default=1080)
+    ap.add_argument("--passes", type=int, default=2)
+    ap.add_argument("--frames", type=int, default=16)
+    ap.add_argument("--step", type=float, default=3.0, help="degrees of orbit per frame")
+    ap.add_argument("--reference-passes", type=int, default=512)
+    ap.add_argument("--depth", type=int, default=8)
+    ap.add_argument("--triangles", type=int, default=262144)
+    ap.add_argument("--no-sun", action="store_true", help="leave the directional light out: under the sky alone nothing casts a hard shadow that moves with the objects")
+    ap.add_argument("--output", default=None)
+    args = ap.parse_args()
+    import torch
+    import raytracer_amd as ra
+    from raytracer_amd import scenes
+    w, h = args.width, args.height
+    pos, idx, nrm, tan, uv, mat = scenes.sponza_class_mesh(args.triangles, 7, refine=True)
+    scene = ra.Scene()
+    mats = [scene.add_material("diffuse", c) for _, c in scenes.SPONZA_MATERIALS]
+    scene.add_mesh(pos, idx, nrm, tan, uv, mat, mats)
+    orbiters = []      # (object index, phase in degrees, height)
+
+    def pose(k, frame):
+        _, phase, lift = orbiters[k]
+        a = math.radians(phase + args.step * frame)
+        return ra.transform_from_euler((ORBIT_CENTRE[0] + ORBIT_RADIUS * math.cos(a), ORBIT_CENTRE[1] + lift, ORBIT_CENTRE[2] + ORBIT_RADIUS * math.sin(a)),
+                                       (0.0, 2.0 * args.step * frame + phase, 0.0))
+    red, gold = scene.add_material("diffuse", (0.8, 0.15, 0.1)), scene.add_material("roughMetal", (1.0, 0.7, 0.2), roughness=0.3)
+    for phase, lift, add in ((0.0, 0.0, lambda t: scene.add_sphere(0.5, t, red)), (90.0, 0.6, lambda t: scene.add_sphere(0.35, t, gold)),
+                             (180.0, -0.4, lambda t: scene.add_box((0.4, 0.6, 0.4), t, red)),
+                             (270.0, 0.3, lambda t: scene.add_mesh(*scenes.box_mesh(0.45), materials=[gold, red], transform=t))):
+        orbiters.append((scene.object_count(), phase, lift))
+        add(pose(len(orbiters) - 1, 0))
+    scene.add_background_light((1.0, 1.5, 2.0))
+    if not args.no_sun:
+        scene.add_directional_light((20000.0, 19000.0, 18000.0), np.float32(1.0) / np.float32(180.0) * np.float32(3.14159265359),
+                                    ra.transform_from_euler((0.0, 0.0, 0.0), scenes.SPONZA_LIGHT_ORIENTATION))
+    scene.build()
+    camera = ra.Camera((-12.5, 2.2, 0.6), (4.0, 82.0, 0.0), w / h, 65.0)
+    vp = ra.Viewport(w, h, seed=1234, max_ray_depth=args.depth)
+    vp.set_renderer(scene)
+    lib, ctx = ra.rtgpu_lib(), vp.device_context()
+
+    def move_to(frame):
+        for k, (index, _, _) in enumerate(orbiters):
+            scene.set_object_transform(index, pose(k, frame))
+        scene.update()
+        vp.update_scene()
+    vp.render(camera, passes=1)
+    assert lib.rtgpu_synchronize(ctx) == 0
+    out = {"scene": "sponza_class + %d orbiting objects" % len(orbiters), "triangles": int(scene.desc.contents.numTriangles), "objects": int(scene.desc.contents.numObjects),
+           "width": w, "height": h, "passes_per_frame": args.passes, "frames": args.frames, "orbit_deg_per_frame": args.step, "sun": not args.no_sun, "reference_passes": args.reference_passes,
+           "reps": args.reps}
+    # ---- the update against the upload ---------------------------------------------------------------------------------------------------------------
+    counter = [0]
+
+    def advance():
+        counter[0] += 1
+        for k, (index, _, _) in enumerate(orbiters):
+            scene.set_object_transform(index, pose(k, counter[0]))
+    for _ in range(3):
+        advance(); scene.update(); vp.update_scene()
+    host, device = [], []
+    for _ in range(args.reps):
+        advance()
+        t0 = time.perf_counter(); scene.update(); t1 = time.perf_counter(); vp.update_scene(); t2 = time.perf_counter()
+        host.append(1e3 * (t1 - t0)); device.append(1e3 * (t2 - t1))
+    stats = lambda ms: {"ms_median": float(np.median(ms)), "ms_min": float(min(ms)), "ms_max": float(max(ms))}   # noqa: E731
+    out["host_update"], out["update_objects"] = stats(host), stats(device)
+    info = ra.update_info(ctx)
+    out["bytes_uploaded"], out["walk"], out["top_depth"] = info["bytesUploaded"], info["walk"], info["topDepth"]
+    blue_noise = ra.load_blue_noise()                           # (the renderer uploads the scene with the sampler's table: so does this)
+    scene.desc.contents.blueNoise = blue_noise.ctypes.data
+    upload = lambda: lib.rtgpu_upload_scene(ctx, scene.desc)   # noqa: E731  (the same flat scene; the viewport's renderer already holds it)
+    assert upload() == 0
+    out["upload_scene"] = wall(upload, max(3, args.reps // 4))
+    out["update_share_of_upload"] = out["update_objects"]["ms_median"] / out["upload_scene"]["ms_median"]
+
+    # ---- worth: three ways through the same sixteen frames ---------------------------------------------------------------------------------------------
+    names = ("depth", "normal", "position", "base_color", "object_id")
+    stream = torch.cuda.Stream()
+    scale = np.float32(1.0 / args.passes)
+    last = args.frames - 1
+    with torch.cuda.stream(stream):
+        def chain(drop_history):
+            vp.reset_history()
+            for frame in range(args.frames):
+                move_to(frame)
+                vp.reset()
+                vp.render(camera, passes=args.passes)
+                guide = vp.next_pass_params(camera)
+                if drop_history:
+                    vp.reset_history()
+                image = vp.denoise(guide, temporal=True, variance=True, device=True)
+            stream.synchronize()
+            return image.cpu().numpy(), guide
+        followed, guide = chain(False)
+        alone = vp.denoise(guide, variance=True, device=True).cpu().numpy()
+        raw = vp.sum_buffer() * scale
+        planes = vp.render_aovs(guide, names, device=True)
+        dropped, _ = chain(True)
+        # the reference: the scene as it stands now, converged
+        vp.reset()
+        vp.render(camera, passes=args.reference_passes)
+        reference = (vp.sum_buffer() / np.float32(args.reference_passes)).astype(np.float64)
+        ids = planes["object_id"].cpu().numpy().reshape(h, w)
+        d = scene.desc.contents
+        moving_ids = [i for i in range(d.numObjects) if d.objects[i].objectKind == 0 and not (d.objects[i].shapeKind == 3 and d.meshes[d.objects[i].meshIndex].numTriangles > 1000)]
+        on_orbiters = np.isin(ids, moving_ids)
+
+        def rel_mse(image, mask=None):
+            e = (image.astype(np.float64) - reference) ** 2 / (reference ** 2 + 0.01)
+            return float(e.mean() if mask is None else e[mask].mean())
+        out["orbiter_pixels"] = int(on_orbiters.sum())
+        out["rel_mse"] = {"raw_frame": rel_mse(raw), "a_update_and_temporal": rel_mse(followed), "b_history_dropped_at_every_move": rel_mse(dropped),
+                          "c_denoise_var_last_frame_alone": rel_mse(alone)}
+        out["rel_mse_on_orbiters"] = {"raw_frame": rel_mse(raw, on_orbiters), "a_update_and_temporal": rel_mse(followed, on_orbiters),
+                                      "b_history_dropped_at_every_move": rel_mse(dropped, on_orbiters), "c_denoise_var_last_frame_alone": rel_mse(alone, on_orbiters)}
+
+        # ---- the kernel with and without the table: the raw _async entries on tensors made once ----------------------------------------------------------
+        vp.reset()
+        vp.render(camera, passes=args.passes)
+        sums = vp.sum_buffer(secondary=True)
+        t = dict(color=torch.from_numpy(sums[0]).cuda(), color_half=torch.from_numpy(sums[1]).cuda(), depth=planes["depth"], normal=planes["normal"], position=planes["position"],
+                 albedo=planes["base_color"], object_id=planes["object_id"].to(torch.int32))
+        first = ra.temporal_accumulate(t["color"], t["color_half"], t["depth"], t["normal"], t["position"], t["albedo"], t["object_id"], color_scale=float(scale), ctx=ctx)
+        t.update(prev_a=first["a"], prev_b=first["b"], prev_length=first["length"], prev_depth=t["depth"], prev_normal=t["normal"], prev_position=t["position"],
+                 prev_object_id=t["object_id"])
+        outputs = [torch.empty((h, w, 3), dtype=torch.float32, device="cuda"), torch.empty((h, w, 3), dtype=torch.float32, device="cuda"),
+                   torch.empty((h, w), dtype=torch.float32, device="cuda"), torch.empty((2, h, w), dtype=torch.float32, device="cuda")]
+        p = ra.temporal_params(color_scale=float(scale), prev_world_to_screen=list(guide.camera.worldToScreen), prev_sample_offset=tuple(guide.sampleOffset))
+        pointers = [C.c_void_p(t[name].data_ptr()) for name in NAMES] + [C.c_void_p(o.data_ptr()) for o in outputs]
+        n = int(d.numObjects)
+        # every orbiter "moved" by the step of one frame (a rigid motion about the orbit's axis): the table's matrices are used, the ids stand still
+        a = math.radians(args.step)
+        turn = np.array([[math.cos(a), 0.0, -math.sin(a), 0.0], [0.0, 1.0, 0.0, 0.0], [math.sin(a), 0.0, math.cos(a), 0.0], [0.0, 0.0, 0.0, 1.0]])
+        shift = np.eye(4); shift[3, :3] = ORBIT_CENTRE
+        back = np.eye(4); back[3, :3] = [-c for c in ORBIT_CENTRE]
+        matrices = np.stack([(back @ turn @ shift) if i in moving_ids else np.eye(4) for i in range(n)]).astype(np.float32)
+        table = torch.from_numpy(ra.object_motion_table((matrices, np.arange(n), [1 if i in moving_ids else 0 for i in range(n)])).view(np.int32)).cuda()
+        handle = C.c_void_p(stream.cuda_stream)
+        static = lambda: lib.rtgpu_temporal_accumulate_async(ctx, C.byref(p), C.c_uint32(w), C.c_uint32(h), *(pointers + [handle]))   # noqa: E731
+        moving = lambda: lib.rtgpu_temporal_accumulate_moving_async(ctx, C.byref(p), C.c_uint32(w), C.c_uint32(h), *(pointers + [C.c_void_p(table.data_ptr()), C.c_uint32(n), handle]))   # noqa: E731
+        assert static() == 0 and moving() == 0, lib.rtgpu_last_error()
+        # interleaved, so that both see the same clocks
+        out["k_temporal_static"] = time_call(torch, static, args.reps)
+        out["k_temporal_moving"] = time_call(torch, moving, args.reps)
+        out["k_temporal_static_again"] = time_call(torch, static, args.reps)
+        out["k_temporal_motion_table_ms"] = out["k_temporal_moving"]["ms_median"] - 0.5 * (out["k_temporal_static"]["ms_median"] + out["k_temporal_static_again"]["ms_median"])
+        out["history_length_mean_on_orbiters_with_the_table"] = float(outputs[2].cpu().numpy()[on_orbiters].mean()) if on_orbiters.any() else None
+    line = json.dumps(out)
+    print(line)
+    if args.output:
+        with open(args.output, "w") as f:
+            f.write(line + "\n")
+
+
+if __name__ == "__main__":
+    main()
