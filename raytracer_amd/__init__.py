@@ -288,7 +288,7 @@ def release_filter_contexts():
 
 def _run_on_torch_stream(torch, owner, device, tensors, call):
     """call(stream handle) on torch.cuda.current_stream(device); torch's default stream is the null stream, which means the context's own to the async
-    entry points: then a side stream ordered behind the current one, which the current one waits for (as Viewport._query)"""
+    entry points: then a side stream of `owner` (device -> stream, one per device, reused) ordered behind the current one, which the current one waits for"""
     current = torch.cuda.current_stream(device)
     if current.cuda_stream != 0:
         return call(C.c_void_p(current.cuda_stream))
@@ -306,6 +306,59 @@ def _run_on_torch_stream(torch, owner, device, tensors, call):
 
 _filter_streams = {}
 
+def _image_planes(planes, shapes):
+    """The planes (a dict name -> array, "color" first) of atrous_filter / temporal_accumulate held to `shapes` (name -> the shapes allowed): float32 NumPy arrays,
+    or contiguous float32 tensors on the colour's ROCm device; a plane named *object_id holds uint32 words, or int32 / int64 in a tensor.  Returns the planes as the
+    library reads them (contiguous arrays; int64 ids narrowed to int32), ptr(a name of theirs, an array or None), empty(shape) for an output of their kind, the device
+    index (0 for NumPy arrays) and the torch module (None for NumPy arrays)."""
+    torch = None
+    if any(type(a).__module__.split(".")[0] == "torch" for a in planes.values()):
+        import torch
+        on_gpu = isinstance(planes["color"], torch.Tensor) and planes["color"].is_cuda
+        device = planes["color"].device if on_gpu else None
+    for name, a in list(planes.items()):
+        ids = name.endswith("object_id")
+        if torch is None:
+            ok = isinstance(a, np.ndarray) and a.dtype == (np.uint32 if ids else np.float32)
+        elif not ids:
+            ok = on_gpu and isinstance(a, torch.Tensor) and a.dtype == torch.float32 and a.device == device
+        else:
+            ok = on_gpu and isinstance(a, torch.Tensor) and a.dtype in (torch.int32, torch.int64) and a.device == device
+            if ok and a.dtype == torch.int64:
+                planes[name] = a.to(torch.int32)   # (the low words: ids are below 2^32)
+        if not ok or a.shape not in shapes[name]:
+            raise ValueError("%s must be a %s %s of shape %s%s" % (name, "uint32" if ids else "float32", "NumPy array" if torch is None else "tensor on the colour's ROCm device",
+                                                                   " or ".join(str(t) for t in shapes[name]), "" if torch is None else " (all arrays or all tensors)"))
+        if torch is not None and not a.is_contiguous():
+            raise ValueError("%s must be contiguous" % name)
+    if torch is None:
+        planes = {name: np.ascontiguousarray(a) for name, a in planes.items()}
+
+        def ptr(a):
+            a = planes.get(a) if a.__class__ is str else a
+            return None if a is None else C.c_void_p(a.ctypes.data)   # (the arrays outlive the call: in `planes`, or the caller's outputs)
+        return planes, ptr, lambda shape: np.zeros(shape, dtype=np.float32), 0, None
+
+    def ptr(a):
+        a = planes.get(a) if a.__class__ is str else a
+        return None if a is None else C.c_void_p(a.data_ptr())
+    return planes, ptr, lambda shape: torch.empty(shape, dtype=torch.float32, device=device), device.index if device.index is not None else torch.cuda.current_device(), torch
+
+
+def _image_call(torch, index, what, ctx, entry, args, tensors):
+    """entry(context, *args) of the library, or with torch entry_async(context, *args, stream) on torch.cuda.current_stream() (`tensors`: what a side stream would
+    touch); `ctx`: the caller's context, or None: the module's own of device `index`.  Raises as the status says."""
+    lib = rtgpu_lib()
+    context = ctx if ctx is not None else _filter_context(index)
+    if torch is None:
+        r = getattr(lib, entry)(context, *args)
+    else:
+        entry = getattr(lib, entry + "_async")
+        r = _run_on_torch_stream(torch, _filter_streams, index, tensors, lambda stream: entry(context, *args, stream))
+    if r != 0:
+        err = (lib.rtgpu_last_error() or b"").decode()
+        raise (ValueError if r == -1 else RuntimeError)("%s failed (%d): %s" % (what, r, err))
+
 
 def atrous_filter(color, depth, normal, position, albedo=None, iterations=5, sigma_color=DENOISE_DEFAULTS["sigma_color"],
                   sigma_normal=DENOISE_DEFAULTS["sigma_normal"], sigma_plane=DENOISE_DEFAULTS["sigma_plane"], color_scale=1.0, demodulate=True, ctx=None,
@@ -322,7 +375,6 @@ def atrous_filter(color, depth, normal, position, albedo=None, iterations=5, sig
     (rtgpu_filter_atrous_var): sigma_lum and variance_floor take sigma_color's place, and return_variance=True returns (image, the (H, W) variance).
     prepared=True (RT_DENOISE_INPUT_PREPARED, with color_half): color and color_half are the accumulated pair (a, b) of temporal_accumulate, taken as they
     are -- no color_scale, no doubling, no division by the albedo; the result is still multiplied by it under demodulate."""
-    torch = None
     variance = color_half is not None
     if prepared and not variance:
         raise ValueError("prepared=True needs color_half")
@@ -335,60 +387,23 @@ def atrous_filter(color, depth, normal, position, albedo=None, iterations=5, sig
         if albedo is None:
             raise ValueError("demodulate=True needs the albedo plane")
         planes["albedo"] = albedo
-    if any(type(a).__module__.split(".")[0] == "torch" for a in planes.values()):
-        import torch
     if getattr(color, "ndim", 0) != 3 or color.shape[2] != 3:
         raise ValueError("color must be an (H, W, 3) float32 array or tensor")
     h, w = int(color.shape[0]), int(color.shape[1])
-    shapes = dict(color=((h, w, 3),), color_half=((h, w, 3),), depth=((h, w), (1, h, w)), normal=((3, h, w),), position=((3, h, w),), albedo=((3, h, w),))
-    for name, a in planes.items():
-        if torch is None:
-            ok = isinstance(a, np.ndarray) and a.dtype == np.float32
-        else:
-            ok = isinstance(a, torch.Tensor) and a.dtype == torch.float32 and a.is_cuda and a.device == color.device
-        if not ok or tuple(a.shape) not in shapes[name]:
-            raise ValueError("%s must be a float32 %s of shape %s%s" % (name, "NumPy array" if torch is None else "tensor on the colour's ROCm device",
-                                                                        " or ".join(str(t) for t in shapes[name]), "" if torch is None else " (all arrays or all tensors)"))
+    planes, ptr, empty, index, torch = _image_planes(planes, dict(color=((h, w, 3),), color_half=((h, w, 3),), depth=((h, w), (1, h, w)), normal=((3, h, w),),
+                                                                 position=((3, h, w),), albedo=((3, h, w),)))
+    out, out_variance = empty((h, w, 3)), empty((h, w)) if return_variance else None
+    guides = (ptr("depth"), ptr("normal"), ptr("position"), ptr("albedo"), ptr(out))
+    tensors = list(planes.values()) + [out, out_variance]
     if variance:
         p = denoise_var_params(iterations, sigma_lum, sigma_normal, sigma_plane, variance_floor, color_scale, demodulate)
         if prepared:
             p.flags |= RT_DENOISE_INPUT_PREPARED
+        _image_call(torch, index, "atrous_filter", ctx, "rtgpu_filter_atrous_var",
+                    (C.byref(p), C.c_uint32(w), C.c_uint32(h), ptr("color"), ptr("color_half")) + guides + (ptr(out_variance),), tensors)
     else:
         p = denoise_params(iterations, sigma_color, sigma_normal, sigma_plane, color_scale, demodulate)
-    lib = rtgpu_lib()
-    out_variance = None
-    if torch is None:
-        planes = {name: np.ascontiguousarray(a) for name, a in planes.items()}
-        out = np.zeros((h, w, 3), dtype=np.float32)
-        ptr = lambda name: planes[name].ctypes.data_as(C.c_void_p) if name in planes else None   # noqa: E731
-        context = ctx if ctx is not None else _filter_context(0)
-        if variance:
-            out_variance = np.zeros((h, w), dtype=np.float32) if return_variance else None
-            r = lib.rtgpu_filter_atrous_var(context, C.byref(p), C.c_uint32(w), C.c_uint32(h), ptr("color"), ptr("color_half"), ptr("depth"), ptr("normal"), ptr("position"),
-                                            ptr("albedo"), out.ctypes.data_as(C.c_void_p), out_variance.ctypes.data_as(C.c_void_p) if return_variance else None)
-        else:
-            r = lib.rtgpu_filter_atrous(context, C.byref(p), C.c_uint32(w), C.c_uint32(h), ptr("color"), ptr("depth"), ptr("normal"),
-                                        ptr("position"), ptr("albedo"), out.ctypes.data_as(C.c_void_p))
-    else:
-        device = color.device
-        index = device.index if device.index is not None else torch.cuda.current_device()
-        for name, a in planes.items():
-            if not a.is_contiguous():
-                raise ValueError("%s must be contiguous" % name)
-        out = torch.empty((h, w, 3), dtype=torch.float32, device=device)
-        ptr = lambda name: C.c_void_p(planes[name].data_ptr()) if name in planes else None   # noqa: E731
-        context = ctx if ctx is not None else _filter_context(index)
-        if variance:
-            out_variance = torch.empty((h, w), dtype=torch.float32, device=device) if return_variance else None
-            r = _run_on_torch_stream(torch, _filter_streams, device, list(planes.values()) + [out, out_variance], lambda stream: lib.rtgpu_filter_atrous_var_async(
-                context, C.byref(p), C.c_uint32(w), C.c_uint32(h), ptr("color"), ptr("color_half"), ptr("depth"), ptr("normal"), ptr("position"), ptr("albedo"),
-                C.c_void_p(out.data_ptr()), C.c_void_p(out_variance.data_ptr()) if return_variance else None, stream))
-        else:
-            r = _run_on_torch_stream(torch, _filter_streams, device, list(planes.values()) + [out], lambda stream: lib.rtgpu_filter_atrous_async(
-                context, C.byref(p), C.c_uint32(w), C.c_uint32(h), ptr("color"), ptr("depth"), ptr("normal"), ptr("position"), ptr("albedo"), C.c_void_p(out.data_ptr()), stream))
-    if r != 0:
-        err = (lib.rtgpu_last_error() or b"").decode()
-        raise (ValueError if r == -1 else RuntimeError)("atrous_filter failed (%d): %s" % (r, err))
+        _image_call(torch, index, "atrous_filter", ctx, "rtgpu_filter_atrous", (C.byref(p), C.c_uint32(w), C.c_uint32(h), ptr("color")) + guides, tensors)
     return (out, out_variance) if return_variance else out
 
 
@@ -452,7 +467,6 @@ def temporal_accumulate(color, color_half, depth, normal, position, albedo=None,
     object_motion=(matrices (n, 4, 4), prev_ids (n,), moved (n,)): the objects moved between the two frames (rtgpu_temporal_accumulate_moving) -- per current
     object id the matrix that takes a world position to where that surface point was in the previous frame, the id the object had there, and whether it
     moved at all; NumPy arrays whichever way the frame comes.  Both id planes are required with it."""
-    torch = None
     table = None
     if object_motion is not None:
         table = object_motion_table(object_motion)
@@ -475,65 +489,27 @@ def temporal_accumulate(color, color_half, depth, normal, position, albedo=None,
                 planes["prev_" + key] = history[key]
         if ("object_id" in planes) != ("prev_object_id" in planes):
             raise ValueError("the object test needs both id planes: give object_id and a history with one, or neither")
-    if any(type(a).__module__.split(".")[0] == "torch" for a in planes.values()):
-        import torch
     if getattr(color, "ndim", 0) != 3 or color.shape[2] != 3:
         raise ValueError("color must be an (H, W, 3) float32 array or tensor")
     h, w = int(color.shape[0]), int(color.shape[1])
     one, three, image = ((h, w), (1, h, w)), ((3, h, w),), ((h, w, 3),)
+    # (in the order of the entry's arguments)
     shapes = dict(color=image, color_half=image, depth=one, normal=three, position=three, albedo=three, object_id=one, prev_a=image, prev_b=image, prev_length=one,
                   prev_depth=one, prev_normal=three, prev_position=three, prev_object_id=one)
-    for name, a in list(planes.items()):
-        ids = name.endswith("object_id")
-        if torch is None:
-            ok = isinstance(a, np.ndarray) and a.dtype == (np.uint32 if ids else np.float32)
-        else:
-            ok = isinstance(a, torch.Tensor) and a.dtype in ((torch.int32, torch.int64) if ids else (torch.float32,)) and a.is_cuda and a.device == color.device
-            if ok and ids and a.dtype == torch.int64:
-                planes[name] = a.to(torch.int32)   # (the low words: ids are below 2^32)
-        if not ok or tuple(a.shape) not in shapes[name]:
-            raise ValueError("%s must be a %s %s of shape %s%s" % (name, "uint32" if ids else "float32", "NumPy array" if torch is None else "tensor on the colour's ROCm device",
-                                                                   " or ".join(str(t) for t in shapes[name]), "" if torch is None else " (all arrays or all tensors)"))
+    planes, ptr, empty, index, torch = _image_planes(planes, shapes)
     p = temporal_params(alpha_min, max_history, normal_threshold, plane_tolerance, color_scale, demodulate, prev_world_to_screen if history is not None else None,
                         prev_sample_offset)
-    lib = rtgpu_lib()
-    order = ("color", "color_half", "depth", "normal", "position", "albedo", "object_id", "prev_a", "prev_b", "prev_length", "prev_depth", "prev_normal", "prev_position",
-             "prev_object_id")
-    if torch is None:
-        planes = {name: np.ascontiguousarray(a) for name, a in planes.items()}
-        out = dict(a=np.zeros((h, w, 3), dtype=np.float32), b=np.zeros((h, w, 3), dtype=np.float32), length=np.zeros((h, w), dtype=np.float32))
-        motion = np.zeros((2, h, w), dtype=np.float32) if return_motion else None
-        ptr = lambda a: a.ctypes.data_as(C.c_void_p) if a is not None else None   # noqa: E731
-        context = ctx if ctx is not None else _filter_context(0)
-        buffers = [ptr(planes.get(name)) for name in order] + [ptr(out["a"]), ptr(out["b"]), ptr(out["length"]), ptr(motion)]
-        if table is None:
-            r = lib.rtgpu_temporal_accumulate(context, C.byref(p), C.c_uint32(w), C.c_uint32(h), *buffers)
-        else:
-            r = lib.rtgpu_temporal_accumulate_moving(context, C.byref(p), C.c_uint32(w), C.c_uint32(h), *(buffers + [ptr(table), C.c_uint32(table.shape[0])]))
+    out = dict(a=empty((h, w, 3)), b=empty((h, w, 3)), length=empty((h, w)))
+    motion = empty((2, h, w)) if return_motion else None
+    args = [C.byref(p), C.c_uint32(w), C.c_uint32(h)] + [ptr(name) for name in shapes] + [ptr(out["a"]), ptr(out["b"]), ptr(out["length"]), ptr(motion)]
+    tensors = list(planes.values()) + list(out.values()) + [motion]
+    if table is None:
+        _image_call(torch, index, "temporal_accumulate", ctx, "rtgpu_temporal_accumulate", args, tensors)
     else:
-        device = color.device
-        index = device.index if device.index is not None else torch.cuda.current_device()
-        for name, a in planes.items():
-            if not a.is_contiguous():
-                raise ValueError("%s must be contiguous" % name)
-        out = dict(a=torch.empty((h, w, 3), dtype=torch.float32, device=device), b=torch.empty((h, w, 3), dtype=torch.float32, device=device),
-                   length=torch.empty((h, w), dtype=torch.float32, device=device))
-        motion = torch.empty((2, h, w), dtype=torch.float32, device=device) if return_motion else None
-        ptr = lambda a: C.c_void_p(a.data_ptr()) if a is not None else None   # noqa: E731
-        context = ctx if ctx is not None else _filter_context(index)
-        buffers = [ptr(planes.get(name)) for name in order] + [ptr(out["a"]), ptr(out["b"]), ptr(out["length"]), ptr(motion)]
-        if table is None:
-            r = _run_on_torch_stream(torch, _filter_streams, device, list(planes.values()) + list(out.values()) + [motion], lambda stream: lib.rtgpu_temporal_accumulate_async(
-                context, C.byref(p), C.c_uint32(w), C.c_uint32(h), *(buffers + [stream])))
-        else:
-            with torch.cuda.device(device):
-                table_dev = torch.from_numpy(table.view(np.int32)).to(device)     # (ordered on the current stream, which the side stream waits for)
-            r = _run_on_torch_stream(torch, _filter_streams, device, list(planes.values()) + list(out.values()) + [motion, table_dev],
-                                     lambda stream: lib.rtgpu_temporal_accumulate_moving_async(context, C.byref(p), C.c_uint32(w), C.c_uint32(h), *(
-                                         buffers + [C.c_void_p(table_dev.data_ptr()), C.c_uint32(table.shape[0]), stream])))
-    if r != 0:
-        err = (lib.rtgpu_last_error() or b"").decode()
-        raise (ValueError if r == -1 else RuntimeError)("temporal_accumulate failed (%d): %s" % (r, err))
+        if torch is not None:
+            with torch.cuda.device(index):
+                table = torch.from_numpy(table.view(np.int32)).to(color.device)   # (ordered on the current stream, which the side stream waits for)
+        _image_call(torch, index, "temporal_accumulate", ctx, "rtgpu_temporal_accumulate_moving", args + [ptr(table), C.c_uint32(table.shape[0])], tensors + [table])
     out.update(depth=planes["depth"], normal=planes["normal"], position=planes["position"], object_id=planes.get("object_id"))
     return (out, motion) if return_motion else out
 
@@ -810,6 +786,7 @@ class Viewport:
         self.width, self.height = int(width), int(height)
         self._scene = None
         self.has_renderer = False
+        self._query_streams, self._denoise_streams = {}, {}   # the side streams of _run_on_torch_stream: ray queries and AOVs, denoise
         if host_lib().rth_viewport_set_params(self._h, C.c_uint32(dimensions), int(bool(use_blue_noise)), C.c_float(anti_aliasing_spread),
                                               C.c_uint32(max_ray_depth), C.c_uint32(min_russian_roulette_depth), int(bool(light_sampling_all))) != 0:
             raise ValueError("invalid rendering params")
@@ -1038,21 +1015,8 @@ class Viewport:
             surf = torch.empty((n, 12), dtype=torch.int32, device=device) if surfaces else None
             occ = torch.empty(n, dtype=torch.int32, device=device) if mode == TRACE_ANY else None
             ptr = lambda t: C.c_void_p(t.data_ptr()) if t is not None else None   # noqa: E731
-            current = torch.cuda.current_stream(device)
-            if current.cuda_stream != 0:
-                r = lib.rtgpu_trace_rays_async(ctx, C.c_uint32(mode), ptr(rays), C.c_uint32(n), ptr(hits), ptr(surf), ptr(occ), None, C.c_void_p(current.cuda_stream))
-            else:
-                # torch's default stream is the null stream, and a NULL stream means the context's own to rtgpu_trace_rays_async: the query runs on a
-                # side stream ordered after the current stream's work, and the current stream waits for it
-                if getattr(self, "_query_stream", None) is None or self._query_stream.device != device:
-                    self._query_stream = torch.cuda.Stream(device)
-                side = self._query_stream
-                side.wait_stream(current)
-                r = lib.rtgpu_trace_rays_async(ctx, C.c_uint32(mode), ptr(rays), C.c_uint32(n), ptr(hits), ptr(surf), ptr(occ), None, C.c_void_p(side.cuda_stream))
-                current.wait_stream(side)
-                for t in (rays, hits, surf, occ):
-                    if t is not None:
-                        t.record_stream(side)
+            r = _run_on_torch_stream(torch, self._query_streams, device, (rays, hits, surf, occ), lambda stream: lib.rtgpu_trace_rays_async(
+                ctx, C.c_uint32(mode), ptr(rays), C.c_uint32(n), ptr(hits), ptr(surf), ptr(occ), None, stream))
         if r != 0:
             err = (lib.rtgpu_last_error() or b"").decode()
             raise (ValueError if r == -1 else RuntimeError)("ray query failed (%d): %s" % (r, err))
@@ -1130,19 +1094,7 @@ class Viewport:
             raw = collections.OrderedDict((name, torch.empty(shape(name), dtype=torch.float32 if AOV_PLANES[name][2] is np.float32 else torch.int32, device=dev))
                                           for name in names)
             ptrs = (C.c_void_p * max(n, 1))(*[raw[name].data_ptr() for name in names])
-            current = torch.cuda.current_stream(dev)
-            if current.cuda_stream != 0:
-                r = lib.rtgpu_render_aovs_async(ctx, C.byref(params), ids, C.c_uint32(n), ptrs, C.c_void_p(current.cuda_stream))
-            else:
-                # torch's default stream is the null stream, which means the context's own to the async entry point: a side stream, as in _query
-                if getattr(self, "_query_stream", None) is None or self._query_stream.device != dev:
-                    self._query_stream = torch.cuda.Stream(dev)
-                side = self._query_stream
-                side.wait_stream(current)
-                r = lib.rtgpu_render_aovs_async(ctx, C.byref(params), ids, C.c_uint32(n), ptrs, C.c_void_p(side.cuda_stream))
-                current.wait_stream(side)
-                for t in raw.values():
-                    t.record_stream(side)
+            r = _run_on_torch_stream(torch, self._query_streams, dev, raw.values(), lambda stream: lib.rtgpu_render_aovs_async(ctx, C.byref(params), ids, C.c_uint32(n), ptrs, stream))
         if r != 0:
             err = (lib.rtgpu_last_error() or b"").decode()
             raise (ValueError if r == -1 else RuntimeError)("render_aovs failed (%d): %s" % (r, err))
@@ -1168,9 +1120,6 @@ class Viewport:
         camera resets the film every frame); reset_history(), a resize and a new scene drop it.  The reprojection reads params.camera.worldToScreen, which
         Camera.set_perspective computes from the transform of the moment (as the reference's Camera does): after Camera.set_transform call set_perspective again,
         or the history is looked up through the camera's old place."""
-        if temporal:
-            return self._denoise_temporal(params, iterations, sigma_normal, sigma_plane, color_scale, demodulate, device, variance, sigma_lum, variance_floor, return_variance,
-                                          alpha_min, max_history, normal_threshold, plane_tolerance)
         if return_variance and not variance:
             raise ValueError("return_variance=True needs variance=True")
         if not isinstance(params, RtPassParams):
@@ -1181,67 +1130,32 @@ class Viewport:
         if not ctx.value or host_lib().rth_viewport_upload_scene(self._h) != 0:
             raise RuntimeError("the viewport's renderer has no device context or its scene could not be uploaded: %s" % (rtgpu_lib().rtgpu_last_error() or b"").decode())
         scale = 1.0 / max(1, self.passes_finished) if color_scale is None else color_scale
-        if variance:
+        # the entry (its _async sibling with device=True) and the arguments in front of the guide params; rtgpu_denoise alone takes no outVariance behind outRGB
+        if temporal:
+            t = temporal_params(alpha_min, max_history, normal_threshold, plane_tolerance, scale, demodulate)
+            v = denoise_var_params(iterations, sigma_lum, sigma_normal, sigma_plane, variance_floor, 1.0, demodulate) if variance else None
+            entry, leading = "rtgpu_denoise_temporal", (C.byref(t), C.byref(v) if variance else None)
+        elif variance:
             p = denoise_var_params(iterations, sigma_lum, sigma_normal, sigma_plane, variance_floor, scale, demodulate)
+            entry, leading = "rtgpu_denoise_var", (C.byref(p),)
         else:
             p = denoise_params(iterations, sigma_color, sigma_normal, sigma_plane, scale, demodulate)
+            entry, leading = "rtgpu_denoise", (C.byref(p),)
         lib = rtgpu_lib()
-        out_variance = None
         if not device:
-            out = np.zeros((self.height, self.width, 3), dtype=np.float32)
-            if variance:
-                out_variance = np.zeros((self.height, self.width), dtype=np.float32) if return_variance else None
-                r = lib.rtgpu_denoise_var(ctx, C.byref(p), C.byref(params), out.ctypes.data_as(C.c_void_p), out_variance.ctypes.data_as(C.c_void_p) if return_variance else None)
-            else:
-                r = lib.rtgpu_denoise(ctx, C.byref(p), C.byref(params), out.ctypes.data_as(C.c_void_p))
+            empty = lambda *shape: np.zeros(shape, dtype=np.float32)   # noqa: E731
+            ptr = lambda a: a.ctypes.data_as(C.c_void_p) if a is not None else None   # noqa: E731
         else:
             import torch
             dev = torch.device("cuda", multi_info(ctx)["devices"][0])
-            out = torch.empty((self.height, self.width, 3), dtype=torch.float32, device=dev)
-            if getattr(self, "_denoise_streams", None) is None:
-                self._denoise_streams = {}
-            if variance:
-                out_variance = torch.empty((self.height, self.width), dtype=torch.float32, device=dev) if return_variance else None
-                r = _run_on_torch_stream(torch, self._denoise_streams, dev, [out, out_variance], lambda stream: lib.rtgpu_denoise_var_async(
-                    ctx, C.byref(p), C.byref(params), C.c_void_p(out.data_ptr()), C.c_void_p(out_variance.data_ptr()) if return_variance else None, stream))
-            else:
-                r = _run_on_torch_stream(torch, self._denoise_streams, dev, [out],
-                                         lambda stream: lib.rtgpu_denoise_async(ctx, C.byref(p), C.byref(params), C.c_void_p(out.data_ptr()), stream))
-        if r != 0:
-            err = (lib.rtgpu_last_error() or b"").decode()
-            raise (ValueError if r == -1 else RuntimeError)("denoise failed (%d): %s" % (r, err))
-        return (out, out_variance) if return_variance else out
-
-    def _denoise_temporal(self, params, iterations, sigma_normal, sigma_plane, color_scale, demodulate, device, variance, sigma_lum, variance_floor, return_variance,
-                          alpha_min, max_history, normal_threshold, plane_tolerance):
-        if return_variance and not variance:
-            raise ValueError("return_variance=True needs variance=True")
-        if not isinstance(params, RtPassParams):
-            raise TypeError("denoise takes the RtPassParams of next_pass_params(camera), not %s" % type(params).__name__)
-        if not self.has_renderer:
-            raise RuntimeError("denoise needs a renderer: call set_renderer first")
-        ctx = self.device_context()
-        if not ctx.value or host_lib().rth_viewport_upload_scene(self._h) != 0:
-            raise RuntimeError("the viewport's renderer has no device context or its scene could not be uploaded: %s" % (rtgpu_lib().rtgpu_last_error() or b"").decode())
-        scale = 1.0 / max(1, self.passes_finished) if color_scale is None else color_scale
-        t = temporal_params(alpha_min, max_history, normal_threshold, plane_tolerance, scale, demodulate)
-        v = denoise_var_params(iterations, sigma_lum, sigma_normal, sigma_plane, variance_floor, 1.0, demodulate) if variance else None
-        vref = C.byref(v) if variance else None
-        lib = rtgpu_lib()
-        out_variance = None
+            empty = lambda *shape: torch.empty(shape, dtype=torch.float32, device=dev)   # noqa: E731
+            ptr = lambda a: C.c_void_p(a.data_ptr()) if a is not None else None   # noqa: E731
+        out, out_variance = empty(self.height, self.width, 3), empty(self.height, self.width) if return_variance else None
+        args = (ctx,) + leading + (C.byref(params), ptr(out)) + ((ptr(out_variance),) if temporal or variance else ())
         if not device:
-            out = np.zeros((self.height, self.width, 3), dtype=np.float32)
-            out_variance = np.zeros((self.height, self.width), dtype=np.float32) if return_variance else None
-            r = lib.rtgpu_denoise_temporal(ctx, C.byref(t), vref, C.byref(params), out.ctypes.data_as(C.c_void_p), out_variance.ctypes.data_as(C.c_void_p) if return_variance else None)
+            r = getattr(lib, entry)(*args)
         else:
-            import torch
-            dev = torch.device("cuda", multi_info(ctx)["devices"][0])
-            out = torch.empty((self.height, self.width, 3), dtype=torch.float32, device=dev)
-            out_variance = torch.empty((self.height, self.width), dtype=torch.float32, device=dev) if return_variance else None
-            if getattr(self, "_denoise_streams", None) is None:
-                self._denoise_streams = {}
-            r = _run_on_torch_stream(torch, self._denoise_streams, dev, [out, out_variance], lambda stream: lib.rtgpu_denoise_temporal_async(
-                ctx, C.byref(t), vref, C.byref(params), C.c_void_p(out.data_ptr()), C.c_void_p(out_variance.data_ptr()) if return_variance else None, stream))
+            r = _run_on_torch_stream(torch, self._denoise_streams, dev, [out, out_variance], lambda stream: getattr(lib, entry + "_async")(*(args + (stream,))))
         if r != 0:
             err = (lib.rtgpu_last_error() or b"").decode()
             raise (ValueError if r == -1 else RuntimeError)("denoise failed (%d): %s" % (r, err))

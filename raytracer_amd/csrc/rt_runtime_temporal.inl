@@ -67,104 +67,79 @@ static void buildMotionTable(const std::vector<RtObject>& now, const std::vector
     }
 }
 
-// the planes of the pure entries, as the caller passed them
-struct TemporalPlanes
+// the planes of the pure entries, in the order of their arguments
+enum { T_COLOR, T_HALF, T_DEPTH, T_NORMAL, T_POSITION, T_ALBEDO, T_ID, T_PREV_A, T_PREV_B, T_PREV_LENGTH, T_PREV_DEPTH, T_PREV_NORMAL, T_PREV_POSITION, T_PREV_ID,
+       T_OUT_A, T_OUT_B, T_OUT_LENGTH, T_OUT_MOTION };
+static PlaneTable temporalPlanes(const float* color, const float* colorHalf, const float* depth, const float* normal, const float* position, const float* albedo, const uint32_t* objectId,
+                                 const float* prevA, const float* prevB, const float* prevLength, const float* prevDepth, const float* prevNormal, const float* prevPosition,
+                                 const uint32_t* prevObjectId, float* outA, float* outB, float* outLength, float* outMotion)
 {
-    const float* color; const float* colorHalf; const float* depth; const float* normal; const float* position; const float* albedo; const uint32_t* objectId;
-    const float* prevA; const float* prevB; const float* prevLength; const float* prevDepth; const float* prevNormal; const float* prevPosition; const uint32_t* prevObjectId;
-    float* outA; float* outB; float* outLength; float* outMotion;
-};
-static const uint32_t kTemporalBuffers = 18u, kTemporalFirstOutput = 14u;
-// buffer k of the planes (the struct's order) and its floats per pixel
-static const uint32_t kTemporalFloats[kTemporalBuffers] = { 3u, 3u, 1u, 3u, 3u, 3u, 1u, 3u, 3u, 1u, 1u, 3u, 3u, 1u, 3u, 3u, 1u, 2u };
-static const void* temporalBuffer(const TemporalPlanes& b, uint32_t k)
-{
-    const void* const all[kTemporalBuffers] = { b.color, b.colorHalf, b.depth, b.normal, b.position, b.albedo, b.objectId, b.prevA, b.prevB, b.prevLength, b.prevDepth, b.prevNormal,
-                                               b.prevPosition, b.prevObjectId, b.outA, b.outB, b.outLength, b.outMotion };
-    return all[k];
+    return { { { color, 3u, false }, { colorHalf, 3u, false }, { depth, 1u, false }, { normal, 3u, false }, { position, 3u, false }, { albedo, 3u, false }, { objectId, 1u, false },
+               { prevA, 3u, false }, { prevB, 3u, false }, { prevLength, 1u, false }, { prevDepth, 1u, false }, { prevNormal, 3u, false }, { prevPosition, 3u, false },
+               { prevObjectId, 1u, false }, { outA, 3u, true }, { outB, 3u, true }, { outLength, 1u, true }, { outMotion, 2u, true } }, 18u };
 }
 
 // the motion table of the _moving entries (NULL, 0: the entries without)
 struct TemporalMotion { const RtObjectMotion* objects; uint32_t numObjects; bool given; };
 static const TemporalMotion kNoMotion = { nullptr, 0u, false };
 
-static int checkTemporal(RtgpuContext* c, const RtTemporalParams* t, uint32_t width, uint32_t height, TemporalPlanes& b, bool& history, const TemporalMotion& motion = kNoMotion)
+static int checkTemporal(RtgpuContext* c, const RtTemporalParams* t, uint32_t width, uint32_t height, PlaneTable& b, bool& history, const TemporalMotion& motion)
 {
     if (!c) return fail(RTGPU_ERR_INVALID_ARGUMENT, "NULL context");
     if (motion.given && (!motion.objects || motion.numObjects == 0u)) return fail(RTGPU_ERR_INVALID_ARGUMENT, "the motion table is NULL or empty");
-    if (motion.given && (!b.objectId || (b.prevA && !b.prevObjectId))) return fail(RTGPU_ERR_INVALID_ARGUMENT, "moving objects are followed by their ids: both id planes are required");
-    if (!t || !b.color || !b.colorHalf || !b.depth || !b.normal || !b.position || !b.outA || !b.outB || !b.outLength) return fail(RTGPU_ERR_INVALID_ARGUMENT, "NULL argument");
-    if (t->flags & RT_DENOISE_DEMODULATE) { if (!b.albedo) return fail(RTGPU_ERR_INVALID_ARGUMENT, "RT_DENOISE_DEMODULATE needs the albedo plane"); }
-    else b.albedo = nullptr;
-    const uint32_t given = (b.prevA ? 1u : 0u) + (b.prevB ? 1u : 0u) + (b.prevLength ? 1u : 0u) + (b.prevDepth ? 1u : 0u) + (b.prevNormal ? 1u : 0u) + (b.prevPosition ? 1u : 0u);
-    if ((given != 0u && given != 6u) || (given == 0u && b.prevObjectId)) return fail(RTGPU_ERR_INVALID_ARGUMENT, "the previous frame's buffers must be given together or not at all");
+    if (motion.given && (!b.has(T_ID) || (b.has(T_PREV_A) && !b.has(T_PREV_ID)))) return fail(RTGPU_ERR_INVALID_ARGUMENT, "moving objects are followed by their ids: both id planes are required");
+    if (!t || !b.has(T_COLOR) || !b.has(T_HALF) || !b.has(T_DEPTH) || !b.has(T_NORMAL) || !b.has(T_POSITION) || !b.has(T_OUT_A) || !b.has(T_OUT_B) || !b.has(T_OUT_LENGTH))
+        return fail(RTGPU_ERR_INVALID_ARGUMENT, "NULL argument");
+    if (!(t->flags & RT_DENOISE_DEMODULATE)) b.planes[T_ALBEDO].ptr = nullptr;
+    else if (!b.has(T_ALBEDO)) return fail(RTGPU_ERR_INVALID_ARGUMENT, "RT_DENOISE_DEMODULATE needs the albedo plane");
+    uint32_t given = 0u;
+    for (uint32_t k = T_PREV_A; k <= T_PREV_POSITION; ++k) given += b.has(k) ? 1u : 0u;
+    if ((given != 0u && given != 6u) || (given == 0u && b.has(T_PREV_ID))) return fail(RTGPU_ERR_INVALID_ARGUMENT, "the previous frame's buffers must be given together or not at all");
     history = given == 6u;
-    if (history && (b.objectId != nullptr) != (b.prevObjectId != nullptr)) return fail(RTGPU_ERR_INVALID_ARGUMENT, "the object test needs both id planes: give both or neither");
+    if (history && b.has(T_ID) != b.has(T_PREV_ID)) return fail(RTGPU_ERR_INVALID_ARGUMENT, "the object test needs both id planes: give both or neither");
     int r = checkTemporalParams(t, true); if (r) return r;
     return checkFilterSize(width, height);
 }
 
-// the launches of a pure call on `stream`; every pointer is device memory
-static int launchTemporal(RtgpuContext* c, const RtTemporalParams* t, uint32_t width, uint32_t height, const TemporalPlanes& b, bool history, hipStream_t stream,
-                          const TemporalMotion& motion = kNoMotion)
+// the launches of a pure call on `stream`; every plane is device memory
+static int launchTemporal(RtgpuContext* c, const RtTemporalParams* t, uint32_t width, uint32_t height, const PlaneTable& b, bool history, hipStream_t stream, const TemporalMotion& motion)
 {
     RtgpuContext::Denoise& d = c->denoise;
     const size_t pixels = (size_t)width * height;
-    int r = ensureAtrousRecords(c, history ? pixels : 0u); if (r) return r;
+    int r = ensureScratch(c, d.records, d.capacity, history ? pixels : 0u, 4u); if (r) return r;   // (the filter's record scratch, and the event every call is ordered by)
     HIP_TRY(hipStreamWaitEvent(stream, d.done, 0));
-    TemporalIn in = { b.color, b.colorHalf, b.depth, b.normal, b.position, b.albedo, b.objectId, nullptr, nullptr, nullptr, nullptr };
+    TemporalIn in = { b.in(T_COLOR), b.in(T_HALF), b.in(T_DEPTH), b.in(T_NORMAL), b.in(T_POSITION), b.in(T_ALBEDO), b.ids(T_ID), nullptr, nullptr, nullptr, nullptr };
     if (history)
     {
         float4* const recA = d.records; float4* const recB = recA + d.capacity; float4* const recN = recB + d.capacity; float4* const recP = recN + d.capacity;
-        hipLaunchKernelGGL(k_temporal_pack, dim3((uint32_t)((pixels + RT_BLOCK - 1u) / RT_BLOCK)), dim3(RT_BLOCK), 0, stream, b.prevA, b.prevB, b.prevLength, b.prevDepth, b.prevNormal,
-                           b.prevPosition, b.prevObjectId, (uint32_t)pixels, recA, recB, recN, recP);
+        hipLaunchKernelGGL(k_temporal_pack, dim3((uint32_t)((pixels + RT_BLOCK - 1u) / RT_BLOCK)), dim3(RT_BLOCK), 0, stream, b.in(T_PREV_A), b.in(T_PREV_B), b.in(T_PREV_LENGTH),
+                           b.in(T_PREV_DEPTH), b.in(T_PREV_NORMAL), b.in(T_PREV_POSITION), b.ids(T_PREV_ID), (uint32_t)pixels, recA, recB, recN, recP);
         in.recA = recA; in.recB = recB; in.recN = recN; in.recP = recP;
     }
-    const TemporalOut out = { b.outA, b.outB, b.outLength, b.outMotion, nullptr, nullptr, nullptr, nullptr, nullptr };
-    launchTemporalKernel(in, out, width, height, temporalFrame(t, t->prevWorldToScreen, t->prevSampleOffset, history && b.objectId && b.prevObjectId), stream,
+    const TemporalOut out = { b.out(T_OUT_A), b.out(T_OUT_B), b.out(T_OUT_LENGTH), b.out(T_OUT_MOTION), nullptr, nullptr, nullptr, nullptr, nullptr };
+    launchTemporalKernel(in, out, width, height, temporalFrame(t, t->prevWorldToScreen, t->prevSampleOffset, history && b.has(T_ID) && b.has(T_PREV_ID)), stream,
                          history && motion.given ? motion.objects : nullptr, motion.numObjects);   // (without history every pixel starts: the table has nothing to say)
-    const hipError_t launched = hipGetLastError();
-    const hipError_t recorded = hipEventRecord(d.done, stream);   // (whatever the launches answered, as launchAtrous)
-    HIP_TRY(launched);
-    HIP_TRY(recorded);
-    return RTGPU_OK;
+    return recordDone(c, stream);
 }
 
-// the host-pointer entries: every plane, and the motion table behind them, staged in the filter's second buffer
-static int temporalAccumulateHost(RtgpuContext* c, const RtTemporalParams* t, uint32_t width, uint32_t height, TemporalPlanes host, const TemporalMotion& motion)
+// the pure entries over planes (and a motion table) in device memory (onDevice), or in host memory: then staged, the table behind the planes
+static int temporalAccumulate(RtgpuContext* c, const RtTemporalParams* t, uint32_t width, uint32_t height, PlaneTable b, TemporalMotion motion, bool onDevice, void* streamHandle)
 {
     bool history = false;
-    int r = checkTemporal(c, t, width, height, host, history, motion); if (r) return r;
+    int r = checkTemporal(c, t, width, height, b, history, motion); if (r) return r;
+    const size_t n = (size_t)width * height;
+    if (onDevice && motion.given && ((uintptr_t)motion.objects & 15u)) return fail(RTGPU_ERR_INVALID_ARGUMENT, "the motion table must be 16-byte aligned device memory");
+    if (onDevice) { r = checkDevicePlanes(b, n); if (r) return r; }
     HIP_TRY(hipSetDevice(c->device));
-    const size_t n = (size_t)width * height, plane = (n + 3u) & ~(size_t)3u;   // (planes start 16-byte aligned)
-    const size_t tableFloats = motion.given ? (size_t)motion.numObjects * (sizeof(RtObjectMotion) / sizeof(float)) : 0u;
-    r = ensureDenoiseIo(c, 41u * plane + tableFloats); if (r) return r;   // the floats per pixel of the 18 buffers
-    hipStream_t stream = c->lanes[0].stream;
-    HIP_TRY(hipEventSynchronize(c->denoise.done));   // the staging copies below are not ordered on a stream
-    const void* staged[kTemporalBuffers];
-    float* cursor = c->denoise.io;
-    for (uint32_t k = 0; k < kTemporalBuffers; ++k)
-    {
-        const void* const source = temporalBuffer(host, k);
-        staged[k] = source ? cursor : nullptr;
-        if (source && k < kTemporalFirstOutput) HIP_TRY(rtMemcpy(cursor, source, kTemporalFloats[k] * n * sizeof(float), hipMemcpyHostToDevice));
-        cursor += kTemporalFloats[k] * plane;
-    }
-    const TemporalPlanes device = { (const float*)staged[0], (const float*)staged[1], (const float*)staged[2], (const float*)staged[3], (const float*)staged[4], (const float*)staged[5],
-                                    (const uint32_t*)staged[6], (const float*)staged[7], (const float*)staged[8], (const float*)staged[9], (const float*)staged[10],
-                                    (const float*)staged[11], (const float*)staged[12], (const uint32_t*)staged[13], (float*)staged[14], (float*)staged[15], (float*)staged[16],
-                                    (float*)staged[17] };
-    TemporalMotion staged_motion = motion;
-    if (motion.given)
-    {
-        HIP_TRY(rtMemcpy(cursor, motion.objects, tableFloats * sizeof(float), hipMemcpyHostToDevice));
-        staged_motion.objects = reinterpret_cast<const RtObjectMotion*>(cursor);
-    }
-    r = launchTemporal(c, t, width, height, device, history, stream, staged_motion); if (r) return r;
+    hipStream_t stream = streamHandle ? (hipStream_t)streamHandle : c->lanes[0].stream;
+    PlaneTable device = b;
+    const void* table = motion.objects;
+    if (!onDevice) { r = stagePlanes(c, b, n, device, &table, motion.given ? motion.numObjects * sizeof(RtObjectMotion) : 0u); if (r) return r; }
+    motion.objects = (const RtObjectMotion*)table;
+    r = launchTemporal(c, t, width, height, device, history, stream, motion);
+    if (r || onDevice) return r;
     HIP_TRY(hipStreamSynchronize(stream));
-    for (uint32_t k = kTemporalFirstOutput; k < kTemporalBuffers; ++k)
-        if (staged[k]) HIP_TRY(rtMemcpy(const_cast<void*>(temporalBuffer(host, k)), staged[k], kTemporalFloats[k] * n * sizeof(float), hipMemcpyDeviceToHost));
-    return RTGPU_OK;
+    return copyPlanesBack(b, device, n);
 }
 
 RTGPU_API int rtgpu_temporal_accumulate(RtgpuContext* c, const RtTemporalParams* t, uint32_t width, uint32_t height, const float* color, const float* colorHalf, const float* depth,
@@ -172,8 +147,8 @@ RTGPU_API int rtgpu_temporal_accumulate(RtgpuContext* c, const RtTemporalParams*
                                         const float* prevLength, const float* prevDepth, const float* prevNormal, const float* prevPosition, const uint32_t* prevObjectId,
                                         float* outA, float* outB, float* outLength, float* outMotion)
 {
-    const TemporalPlanes host = { color, colorHalf, depth, normal, position, albedo, objectId, prevA, prevB, prevLength, prevDepth, prevNormal, prevPosition, prevObjectId, outA, outB, outLength, outMotion };
-    return temporalAccumulateHost(c, t, width, height, host, kNoMotion);
+    return temporalAccumulate(c, t, width, height, temporalPlanes(color, colorHalf, depth, normal, position, albedo, objectId, prevA, prevB, prevLength, prevDepth, prevNormal,
+                                                                  prevPosition, prevObjectId, outA, outB, outLength, outMotion), kNoMotion, false, nullptr);
 }
 
 RTGPU_API int rtgpu_temporal_accumulate_moving(RtgpuContext* c, const RtTemporalParams* t, uint32_t width, uint32_t height, const float* color, const float* colorHalf, const float* depth,
@@ -181,35 +156,8 @@ RTGPU_API int rtgpu_temporal_accumulate_moving(RtgpuContext* c, const RtTemporal
                                                const float* prevLength, const float* prevDepth, const float* prevNormal, const float* prevPosition, const uint32_t* prevObjectId,
                                                float* outA, float* outB, float* outLength, float* outMotion, const RtObjectMotion* objects, uint32_t numObjects)
 {
-    const TemporalPlanes host = { color, colorHalf, depth, normal, position, albedo, objectId, prevA, prevB, prevLength, prevDepth, prevNormal, prevPosition, prevObjectId, outA, outB, outLength, outMotion };
-    const TemporalMotion motion = { objects, numObjects, true };
-    return temporalAccumulateHost(c, t, width, height, host, motion);
-}
-
-// the device-pointer entries
-static int temporalAccumulateDevice(RtgpuContext* c, const RtTemporalParams* t, uint32_t width, uint32_t height, TemporalPlanes b, const TemporalMotion& motion, void* streamHandle)
-{
-    bool history = false;
-    int r = checkTemporal(c, t, width, height, b, history, motion); if (r) return r;
-    if (motion.given && ((uintptr_t)motion.objects & 15u)) return fail(RTGPU_ERR_INVALID_ARGUMENT, "the motion table must be 16-byte aligned device memory");
-    const size_t n = (size_t)width * height;
-    // every buffer aligned; each output against everything before it
-    for (uint32_t o = 0; o < kTemporalBuffers; ++o)
-    {
-        const uintptr_t pb = (uintptr_t)temporalBuffer(b, o);
-        if (!pb) continue;
-        if (pb & 15u) return fail(RTGPU_ERR_INVALID_ARGUMENT, "the buffers must be 16-byte aligned device memory");
-        if (o < kTemporalFirstOutput) continue;
-        for (uint32_t i = 0; i < o; ++i)
-        {
-            const uintptr_t pa = (uintptr_t)temporalBuffer(b, i);
-            if (pa && pa < pb + kTemporalFloats[o] * n * sizeof(float) && pb < pa + kTemporalFloats[i] * n * sizeof(float))
-                return fail(RTGPU_ERR_INVALID_ARGUMENT, "an output overlaps an input or another output");
-        }
-    }
-    HIP_TRY(hipSetDevice(c->device));
-    hipStream_t stream = streamHandle ? (hipStream_t)streamHandle : c->lanes[0].stream;
-    return launchTemporal(c, t, width, height, b, history, stream, motion);
+    return temporalAccumulate(c, t, width, height, temporalPlanes(color, colorHalf, depth, normal, position, albedo, objectId, prevA, prevB, prevLength, prevDepth, prevNormal,
+                                                                  prevPosition, prevObjectId, outA, outB, outLength, outMotion), { objects, numObjects, true }, false, nullptr);
 }
 
 RTGPU_API int rtgpu_temporal_accumulate_async(RtgpuContext* c, const RtTemporalParams* t, uint32_t width, uint32_t height, const float* color, const float* colorHalf,
@@ -217,8 +165,8 @@ RTGPU_API int rtgpu_temporal_accumulate_async(RtgpuContext* c, const RtTemporalP
                                               const float* prevB, const float* prevLength, const float* prevDepth, const float* prevNormal, const float* prevPosition,
                                               const uint32_t* prevObjectId, float* outA, float* outB, float* outLength, float* outMotion, void* streamHandle)
 {
-    const TemporalPlanes b = { color, colorHalf, depth, normal, position, albedo, objectId, prevA, prevB, prevLength, prevDepth, prevNormal, prevPosition, prevObjectId, outA, outB, outLength, outMotion };
-    return temporalAccumulateDevice(c, t, width, height, b, kNoMotion, streamHandle);
+    return temporalAccumulate(c, t, width, height, temporalPlanes(color, colorHalf, depth, normal, position, albedo, objectId, prevA, prevB, prevLength, prevDepth, prevNormal,
+                                                                  prevPosition, prevObjectId, outA, outB, outLength, outMotion), kNoMotion, true, streamHandle);
 }
 
 RTGPU_API int rtgpu_temporal_accumulate_moving_async(RtgpuContext* c, const RtTemporalParams* t, uint32_t width, uint32_t height, const float* color, const float* colorHalf,
@@ -227,9 +175,8 @@ RTGPU_API int rtgpu_temporal_accumulate_moving_async(RtgpuContext* c, const RtTe
                                                      const float* prevPosition, const uint32_t* prevObjectId, float* outA, float* outB, float* outLength, float* outMotion,
                                                      const RtObjectMotion* objects, uint32_t numObjects, void* streamHandle)
 {
-    const TemporalPlanes b = { color, colorHalf, depth, normal, position, albedo, objectId, prevA, prevB, prevLength, prevDepth, prevNormal, prevPosition, prevObjectId, outA, outB, outLength, outMotion };
-    const TemporalMotion motion = { objects, numObjects, true };
-    return temporalAccumulateDevice(c, t, width, height, b, motion, streamHandle);
+    return temporalAccumulate(c, t, width, height, temporalPlanes(color, colorHalf, depth, normal, position, albedo, objectId, prevA, prevB, prevLength, prevDepth, prevNormal,
+                                                                  prevPosition, prevObjectId, outA, outB, outLength, outMotion), { objects, numObjects, true }, true, streamHandle);
 }
 
 RTGPU_API int rtgpu_temporal_reset(RtgpuContext* c)
@@ -244,46 +191,19 @@ static int denoiseTemporalFrame(RtgpuContext* c, const RtTemporalParams* t, cons
                                 float* outVariance, void* streamHandle)
 {
     if (!c) return fail(RTGPU_ERR_INVALID_ARGUMENT, "NULL context");
-    if (!t || !guideParams || (!outHost && !outDevice)) return fail(RTGPU_ERR_INVALID_ARGUMENT, "NULL argument");
-    if (outDevice && (((uintptr_t)outDevice | (uintptr_t)outVariance) & 15u)) return fail(RTGPU_ERR_INVALID_ARGUMENT, "the output must be a 16-byte aligned device buffer");
+    if (!t) return fail(RTGPU_ERR_INVALID_ARGUMENT, "NULL argument");
     int r = checkTemporalParams(t, false); if (r) return r;
     if (v) { r = checkDenoiseVarParams(v); if (r) return r; }
-    if (!c->sceneReady) return fail(RTGPU_ERR_NOT_READY, "rtgpu_upload_scene has not been called");
-    if (!c->sum) return fail(RTGPU_ERR_NOT_READY, "rtgpu_resize has not been called");
-    r = checkPass(c, guideParams); if (r) return r;
-    r = checkFilterSize(c->width, c->height); if (r) return r;
-    r = rtgpu_synchronize(c); if (r) return r;
-    r = gatherPeers(c); if (r) return r;
-    const size_t n = (size_t)c->width * c->height, plane = (n + 3u) & ~(size_t)3u;
-    if (!v) outVariance = nullptr;
-    if (outDevice && outVariance)
-    {
-        const uintptr_t a = (uintptr_t)outDevice, b = (uintptr_t)outVariance;
-        if (a < b + n * sizeof(float) && b < a + 3u * n * sizeof(float)) return fail(RTGPU_ERR_INVALID_ARGUMENT, "outVariance overlaps outRGB");
-    }
-    // guides: depth 1, normal 3, position 3, albedo 3, object id 1; the accumulated pair 3 + 3 and its length 1; then the host entry's result
-    r = ensureDenoiseIo(c, 18u * plane + (outHost ? 3u * plane + n : 0u)); if (r) return r;
+    FrameStep f;
+    r = beginFrame(c, guideParams, outHost, outDevice, outVariance, v != nullptr, streamHandle, 5u, 7u, f); if (r) return r;   // its own planes: the accumulated pair 3 + 3 and its length 1
+    float* const dA = f.extra; float* const dB = dA + 3u * f.stride; float* const dLength = dB + 3u * f.stride;
     RtgpuContext::Temporal& h = c->temporal;
-    if (h.capacity < n)
-    {
-        HIP_TRY(hipEventSynchronize(c->denoise.done));
-        devFree(h.records); h.capacity = 0; h.have = false;
-        HIP_TRY(hipMalloc((void**)&h.records, 8u * n * sizeof(float4)));
-        h.capacity = n;
-    }
-    hipStream_t stream = streamHandle ? (hipStream_t)streamHandle : c->lanes[0].stream;
-    HIP_TRY(hipStreamWaitEvent(stream, c->denoise.done, 0));   // guide planes and history are shared with the previous call
-    float* const dDepth = c->denoise.io; float* const dNormal = dDepth + plane; float* const dPosition = dNormal + 3u * plane; float* const dAlbedo = dPosition + 3u * plane;
-    uint32_t* const dId = (uint32_t*)(dAlbedo + 3u * plane); float* const dA = (float*)dId + plane; float* const dB = dA + 3u * plane; float* const dLength = dB + 3u * plane;
-    float* const out = outHost ? dLength + plane : outDevice;
-    float* const variance = outHost && outVariance ? out + 3u * plane : outVariance;
-    const uint32_t planes[5] = { RT_AOV_DEPTH, RT_AOV_NORMAL, RT_AOV_POSITION, RT_AOV_BASE_COLOR, RT_AOV_OBJECT_ID };
-    void* const outputs[5] = { dDepth, dNormal, dPosition, dAlbedo, dId };
-    r = rtgpu_render_aovs_async(c, guideParams, planes, 5u, outputs, stream); if (r) return r;
+    if (h.capacity < f.pixels) h.have = false;
+    r = ensureScratch(c, h.records, h.capacity, f.pixels, 8u); if (r) return r;   // two sets of four planes of records
     float4* const from = h.records + (size_t)h.current * 4u * h.capacity; float4* const to = h.records + (size_t)(h.current ^ 1u) * 4u * h.capacity;
-    TemporalIn in = { c->sum, c->secondary, dDepth, dNormal, dPosition, (t->flags & RT_DENOISE_DEMODULATE) ? dAlbedo : nullptr, dId, nullptr, nullptr, nullptr, nullptr };
+    TemporalIn in = { c->sum, c->secondary, f.depth, f.normal, f.position, (t->flags & RT_DENOISE_DEMODULATE) ? f.albedo : nullptr, f.id, nullptr, nullptr, nullptr, nullptr };
     if (h.have) { in.recA = from; in.recB = from + h.capacity; in.recN = from + 2u * h.capacity; in.recP = from + 3u * h.capacity; }
-    const TemporalOut res = { dA, dB, dLength, nullptr, v ? nullptr : out, to, to + h.capacity, to + 2u * h.capacity, to + 3u * h.capacity };
+    const TemporalOut res = { dA, dB, dLength, nullptr, v ? nullptr : f.out, to, to + h.capacity, to + 2u * h.capacity, to + 3u * h.capacity };
     const RtObjectMotion* motion = nullptr;
     const std::vector<RtObject>& objects = c->updatable.objects;
     if (h.have && h.movedSince && !objects.empty() && h.then.size() == objects.size())
@@ -293,24 +213,13 @@ static int denoiseTemporalFrame(RtgpuContext* c, const RtTemporalParams* t, cons
         std::vector<RtObjectMotion> table;
         buildMotionTable(objects, h.then, table);
         HIP_TRY(hipEventSynchronize(c->denoise.done));
-        if (h.motionCapacity < table.size())
-        {
-            devFree(h.motion); h.motionCapacity = 0;
-            HIP_TRY(hipMalloc((void**)&h.motion, table.size() * sizeof(RtObjectMotion)));
-            h.motionCapacity = table.size();
-        }
+        r = ensureScratch(c, h.motion, h.motionCapacity, table.size()); if (r) return r;
         HIP_TRY(rtMemcpy(h.motion, table.data(), table.size() * sizeof(RtObjectMotion), hipMemcpyHostToDevice));
         motion = h.motion;
     }
-    launchTemporalKernel(in, res, c->width, c->height, temporalFrame(t, h.worldToScreen, h.sampleOffset, h.have), stream, motion, (uint32_t)objects.size());
-    const hipError_t launched = hipGetLastError();
-    const hipError_t recorded = hipEventRecord(c->denoise.done, stream);
-    HIP_TRY(launched);
-    HIP_TRY(recorded);
-    RtgpuContext::Denoise& d = c->denoise;
-    if (!d.sumRead) HIP_TRY(hipEventCreateWithFlags(&d.sumRead, hipEventDisableTiming));
-    HIP_TRY(hipEventRecord(d.sumRead, stream));
-    d.sumReadPending = true;
+    launchTemporalKernel(in, res, c->width, c->height, temporalFrame(t, h.worldToScreen, h.sampleOffset, h.have), f.stream, motion, (uint32_t)objects.size());
+    r = recordDone(c, f.stream); if (r) return r;
+    r = markSumRead(c, f.stream); if (r) return r;
     // this frame is the next call's history
     h.current ^= 1u; h.have = true;
     h.movedSince = false;
@@ -322,16 +231,9 @@ static int denoiseTemporalFrame(RtgpuContext* c, const RtTemporalParams* t, cons
     {
         AtrousPlan plan = atrousPlan(v);
         plan.flags |= RT_DENOISE_INPUT_PREPARED; plan.colorScale = 1.0f;
-        r = launchAtrous(c, plan, c->width, c->height, dA, dB, dDepth, dNormal, dPosition, dAlbedo, out, variance, stream, false); if (r) return r;
+        r = launchAtrous(c, plan, c->width, c->height, filterPlanes(dA, dB, f.depth, f.normal, f.position, f.albedo, f.out, f.variance), f.stream, false); if (r) return r;
     }
-    if (outHost)
-    {
-        HIP_TRY(hipStreamSynchronize(stream));
-        d.sumReadPending = false;
-        HIP_TRY(rtMemcpy(outHost, out, 3u * n * sizeof(float), hipMemcpyDeviceToHost));
-        if (outVariance) HIP_TRY(rtMemcpy(outVariance, variance, n * sizeof(float), hipMemcpyDeviceToHost));
-    }
-    return RTGPU_OK;
+    return finishFrame(c, f);
 }
 
 RTGPU_API int rtgpu_denoise_temporal(RtgpuContext* c, const RtTemporalParams* t, const RtDenoiseVarParams* v, const RtPassParams* guideParams, float* outRGB, float* outVariance)

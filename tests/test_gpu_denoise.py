@@ -217,6 +217,11 @@ def test_statuses(built):
         assert raw_filter(ctx, good, 4, 4, (), "rtgpu_filter_atrous_async", dict(device_pointers, depth=C.c_void_p(dev.data_ptr() + 64 * 4 * 3 + 8))) == INVALID_ARGUMENT
         assert raw_filter(ctx, good, 4, 4, (), "rtgpu_filter_atrous_async", dict(device_pointers, out=C.c_void_p(dev.data_ptr() + 4 * 32))) == INVALID_ARGUMENT
         assert b"overlap" in lib.rtgpu_last_error()
+        # the checker is the variance-guided and the temporal entries' too: an output inside an input that is not the colour, a misaligned input that is not the colour
+        inside_position = C.c_void_p(dev.data_ptr() + 64 * 4 * 7 + 4 * 32)
+        assert raw_filter(ctx, good, 4, 4, (), "rtgpu_filter_atrous_async", dict(device_pointers, out=inside_position)) == INVALID_ARGUMENT and b"overlap" in lib.rtgpu_last_error()
+        assert raw_filter(ctx, good, 4, 4, (), "rtgpu_filter_atrous_async", dict(device_pointers, normal=C.c_void_p(dev.data_ptr() + 64 * 4 * 4 + 4))) == INVALID_ARGUMENT
+        assert b"aligned" in lib.rtgpu_last_error()
         assert lib.rtgpu_synchronize(ctx) == OK
         torch.cuda.synchronize()
         # rtgpu_denoise before rtgpu_upload_scene, then before rtgpu_resize
