@@ -21,7 +21,7 @@
 // k_generate for dense state: slot i = home i; the regions of the first arena are simply filled one after the other
 __global__ void __launch_bounds__(RT_BLOCK) k_generate_dense(const RtSceneDesc scene, const DevPass* __restrict__ passes, uint32_t slotsPerPass, const Paths paths,
                                                              const uint32_t* __restrict__ slotPixel, uint32_t numSlots, uint32_t shardCapacity, uint32_t* __restrict__ counts,
-                                                             unsigned long long* counters, uint32_t fullRecords)
+                                                             unsigned long long* counters)
 {
     const uint32_t stride = gridDim.x * blockDim.x;
     for (uint32_t slot = blockIdx.x * blockDim.x + threadIdx.x; slot < numSlots; slot += stride)
@@ -40,13 +40,7 @@ __global__ void __launch_bounds__(RT_BLOCK) k_generate_dense(const RtSceneDesc s
         cameraGenerateRayParts(pass.camera, coords, sampler, origin, direction);
         stStream(prec(paths, R_ORIGIN, slot), f4(origin.x, origin.y, origin.z, fbits(0x100u)));   // depth 0, lastSpecular = true (PathTracerMIS.h:29-34)
         stStream(prec(paths, R_DIR, slot), f4(direction.x, direction.y, direction.z, 1.0f));        // lastPdfW = 1
-        if (fullRecords != 0u)
-        {
-            // (the consumers that do not rebuild a fresh path's other records from its slot: see denseShadeVertex)
-            stStream(prec(paths, R_TP, slot), f4(1.0f, 1.0f, 1.0f, 1.0f));
-            stStream(prec(paths, R_RESULT, slot), f4(0.0f, 0.0f, 0.0f, fbits(pix)));
-            storeSampler(sampler, paths, slot, 0.0f, densePack(slot, 0u));   // the path's home; no request is pending
-        }
+        // (the five other records of a fresh path are functions of its slot: bounce 0's shade rebuilds them, see denseShadeVertex)
     }
     if (blockIdx.x == 0 && threadIdx.x < RT_DENSE_SHARDS)
     {

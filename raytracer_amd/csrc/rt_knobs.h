@@ -1,6 +1,7 @@
 // rt_knobs.h -- every RTGPU_* environment variable the library reads, in one place, ordered by WHEN it is read.  Included by rt_runtime.hip behind
 // rt_runtime_context.h.  DESIGN.md ("Environment knobs") lists them with their defaults; why a default is what it is stands next to the policy
-// that uses it (launchTraceWide, launchRetrace, tailDepthFor, ...), not here.
+// that uses it (launchTraceWide, launchRetrace, tailDepthFor, ...), not here.  A knob scales a policy or forces code that ships anyway (which is how the
+// tests reach it); a path that lost its measurement has none -- it is deleted together with its option, and DESIGN.md keeps the finding.
 //
 //   1. per context   copied into the RtgpuContext by rtgpu_create / rtgpu_create_multi: a later change of the variable reaches new contexts only
 //   2. per process   read once, by the first call that needs the value (a function-local static): a later change is never seen
@@ -26,7 +27,6 @@ static inline void readContextKnobs(RtgpuContext* c)
     c->wide2Allowed = envInt("RTGPU_WIDE2", 1) != 0;
     c->denseAllowed = envInt("RTGPU_NO_DENSE", 0) == 0;
     c->countIntersections = envInt("RTGPU_INTERSECTION_COUNTERS", 0) != 0;
-    c->anyHitFarFirst = envInt("RTGPU_ANYHIT_FAR_FIRST", 1) != 0 ? 1u : 0u;   // test hook: every 4-wide walk of the context, k_tail's included
     if (envSet("RTGPU_PASS_BATCH")) { c->passBatch = (uint32_t)envInt("RTGPU_PASS_BATCH", 0); c->passBatchFromEnv = true; }
     if (c->passBatch < 1) c->passBatch = 1;
     if (c->passBatch > RT_SEED_RING / 2) c->passBatch = RT_SEED_RING / 2;
@@ -48,10 +48,6 @@ RT_KNOB_ONCE(uint32_t, maxStreamBatch, (uint32_t)envInt("RTGPU_MAX_STREAM_BATCH"
 RT_KNOB_ONCE(uint32_t, shadeBlocksPerCU, (uint32_t)envInt("RTGPU_SHADE_BLOCKS_PER_CU", 8))
 RT_KNOB_ONCE(uint32_t, tailBlocksPerCU, (uint32_t)envInt("RTGPU_TAIL_BLOCKS_PER_CU", 4))
 RT_KNOB_ONCE(uint32_t, packetBlocksPerCU, (uint32_t)envInt("RTGPU_PACKET_BLOCKS", 8))
-RT_KNOB_ONCE(int, tailDepth, envInt("RTGPU_TAIL_DEPTH", -1))                      // -1: policy
-RT_KNOB_ONCE(bool, fullPrimary, envInt("RTGPU_FULL_PRIMARY", 0) != 0)
-RT_KNOB_ONCE(int, localExact, envInt("RTGPU_LOCAL_EXACT", -1))                    // -1: policy
-RT_KNOB_ONCE(uint32_t, localExactFromBounce, (uint32_t)envInt("RTGPU_LOCAL_EXACT_FROM", 255))
 RT_KNOB_ONCE(uint32_t, wideChunkMin, (uint32_t)envInt("RTGPU_WIDE_CHUNK_MIN", 64))
 RT_KNOB_ONCE(bool, wideDiag, envSet("RTGPU_WIDE_DIAG"))                           // (its value is read per launch: wideDiagMode)
 RT_KNOB_ONCE(uint32_t, retraceSplitAfter, (uint32_t)envInt("RTGPU_RETRACE_SPLIT_AFTER", 0))   // 0: RT_RETRACE_SPLIT_AFTER
@@ -66,13 +62,9 @@ RT_KNOB_ONCE(bool, denoiseTiled, envInt("RTGPU_DENOISE_TILED", 1) != 0)         
 
 // ---- 3. per call -----------------------------------------------------------------------------------------------------------------------------
 // every launch of a 4-wide walk
-static inline uint32_t wideReverse() { return (uint32_t)envInt("RTGPU_WIDE_REVERSE", 0); }
 static inline uint32_t wideDrainAbort() { return (uint32_t)envInt("RTGPU_WIDE_DRAIN_ABORT", 0); }   // test hook; 0: off
 static inline uint32_t wideDiagMode() { return (uint32_t)envInt("RTGPU_WIDE_DIAG", 0); }
 static inline bool packets() { return envInt("RTGPU_PACKET", 1) != 0; }
-// every re-trace launch
-static inline int abortRetraceAfter() { return envInt("RTGPU_ABORT_RETRACE_AFTER", -1); }   // test hook; < 0: RT_ABORT_RETRACE_AFTER
-static inline bool retraceMonsters() { return envSet("RTGPU_RETRACE_MONSTERS") ? envInt("RTGPU_RETRACE_MONSTERS", 0) != 0 : envSet("RTGPU_ABORT_RETRACE_AFTER"); }
 // every rtgpu_render_aovs: pixels per chunk, 1 .. 4 M (the tests run a small frame in several chunks)
 static inline uint32_t aovChunk() { const int v = envInt("RTGPU_AOV_CHUNK", 1 << 22); return v < 1 ? 1u : (v > (1 << 22) ? (1u << 22) : (uint32_t)v); }
 // every rtgpu_upload_scene

@@ -102,9 +102,8 @@ struct TraceStep
     // the work: closest-hit rays and any-hit requests (either queue may be null) over `paths`, taken through `cursor`
     hipStream_t stream; unsigned long long* counters; Paths paths;
     const uint32_t* queue = nullptr; const uint32_t* queueCount = nullptr; const uint32_t* shadowQueue = nullptr; const uint32_t* shadowCount = nullptr; uint32_t* cursor = nullptr;
-    // the hand-over of the 4-wide walks: what they leave to the re-trace launch, its work cursor, and -- optional -- where that launch leaves rays for k_trace_monster
+    // the hand-over of the 4-wide walks: what they leave to the re-trace launch, and its work cursor
     uint32_t* exactQueue = nullptr; uint32_t* exactCount = nullptr; uint32_t* exactShadowQueue = nullptr; uint32_t* exactShadowCount = nullptr; uint32_t* exactCursor = nullptr;
-    uint32_t* overflowQueue = nullptr; uint32_t* overflowCount = nullptr;
     // the call's policy
     float shadowOffset = 0.0001f;              // any-hit rays start this far along their direction (TravTuning::shadowOffset)
     const uint32_t* denseCounts = nullptr; uint32_t denseShardCapacity = 0u;   // dense path state: the closest-hit rays are the live paths of the arena's regions (no queue)
@@ -113,20 +112,21 @@ struct TraceStep
     uint4* rayCounts = nullptr;                // binary walk only: every closest-hit ray's own test counts (TravTuning::rayCounts); makes the walk a counting one
 };
 
+// LaneCounts names the first six; eight are allocated and zeroed: 32 bytes per bounce are a multiple of 16 at any depth, which the runtime's memset fills with
+// ONE kernel (the 24 bytes of six planes take a second fill kernel per batch at every odd maxDepth: the launch listings of tools/launch_order.py show it)
 #define RT_LANE_COUNT_PLANES 8u
 static size_t laneCountBytes(const BatchLane& l) { return (size_t)RT_LANE_COUNT_PLANES * l.queueCountCapacity * sizeof(uint32_t); }
 
-// the planes of BatchLane::queueCounts, built once per flush; index each with the bounce (plane 3 is unused)
+// the planes of BatchLane::queueCounts in use, built once per flush; index each with the bounce
 struct LaneCounts
 {
     const BatchLane& lane;
     uint32_t* pathCounts; uint32_t* shadowCounts; uint32_t* cursors;              // path queues, next-event request queues, the traversal launches' work cursors
     uint32_t* exactCounts; uint32_t* exactShadowCounts; uint32_t* exactCursors;   // what the 4-wide walks hand to the re-trace launch, and its cursors
-    uint32_t* overflowCounts;                                                     // closest-hit rays the re-trace launch hands to k_trace_monster
     explicit LaneCounts(const BatchLane& l)
         : lane(l), pathCounts(l.queueCounts), shadowCounts(l.queueCounts + 1 * l.queueCountCapacity), cursors(l.queueCounts + 2 * l.queueCountCapacity),
-          exactCounts(l.queueCounts + 4 * l.queueCountCapacity), exactShadowCounts(l.queueCounts + 5 * l.queueCountCapacity),
-          exactCursors(l.queueCounts + 6 * l.queueCountCapacity), overflowCounts(l.queueCounts + 7 * l.queueCountCapacity) {}
+          exactCounts(l.queueCounts + 3 * l.queueCountCapacity), exactShadowCounts(l.queueCounts + 4 * l.queueCountCapacity),
+          exactCursors(l.queueCounts + 5 * l.queueCountCapacity) {}
     // the work of bounce d: {closest-hit rays of bounce d, next-event requests of bounce d - 1}, whichever exist, and the bounce's work cursor
     void queuesOf(TraceStep& s, uint32_t d, bool haveClosest, bool haveShadow) const
     {
@@ -134,11 +134,11 @@ struct LaneCounts
         s.shadowQueue = haveShadow ? lane.shadowQueues[(d - 1u) & 1u] : nullptr; s.shadowCount = haveShadow ? shadowCounts + (d - 1u) : nullptr;
         s.cursor = cursors + d;
     }
-    // the hand-over of bounce d; `overflowQueue`: a queue of the lane nobody uses during this bounce's trace (launchRetrace)
-    void handOverOf(TraceStep& s, uint32_t d, uint32_t* overflowQueue) const
+    // the hand-over of bounce d
+    void handOverOf(TraceStep& s, uint32_t d) const
     {
         s.exactQueue = lane.exactQueue; s.exactCount = exactCounts + d; s.exactShadowQueue = lane.exactShadowQueue; s.exactShadowCount = exactShadowCounts + d;
-        s.exactCursor = exactCursors + d; s.overflowQueue = overflowQueue; s.overflowCount = overflowCounts + d;
+        s.exactCursor = exactCursors + d;
     }
 };
 
@@ -209,7 +209,6 @@ struct RtgpuContext
     bool wideAllowed = true;           // RTGPU_WIDE=0: single-mesh scenes walk the binary tree (k_trace) even with the intersection counters off
     bool denseAllowed = true;          // RTGPU_NO_DENSE=1: path state stays in the pixel's slot for the whole path (the first layout)
     TravTuning tune = { 28u, 32u, 0.0001f, nullptr, nullptr, RT_ABORT_CLOSEST_AFTER, nullptr, 0u };   // scheduling: measured plateau on MI355X (profiles/r01_tuning_sweep.txt)
-    uint32_t anyHitFarFirst = 1u;      // WideTuning::anyHitFarFirst of every launch; RTGPU_ANYHIT_FAR_FIRST=0: any-hit rays walk the nearest child first
     uint32_t travBlocksPerCU = 0;      // 0 = default
     int32_t tailBounce = -1;           // rtgpu_set_schedule: the bounce at which a dense batch hands over to k_tail (rt_tail.hip); 0 = never, -1 = policy
     int32_t localRetrace = -1;         // rtgpu_set_schedule: the 4-wide walks trace their undecided rays themselves; 0 / 1, -1 = policy

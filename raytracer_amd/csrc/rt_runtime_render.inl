@@ -128,32 +128,20 @@ static void launchTraceWide(RtgpuContext* c, const TraceStep& s)
 {
     // A block traces the rays its walk does not decide itself (rt_trace_wide.inl) where launches are short: a 1/8 shard of a full-HD frame gains 10 %
     // (ten launches per batch less to wait for), a full frame loses 1.4 % (a block holds its slot of the CU while one wave walks; the separate launch
-    // ran beside the other lanes' kernels) -- profiles/r04_local_exact_ab.txt.  RTGPU_LOCAL_EXACT=0 / 1 forces it.
-    const int localExactEnv = knobs::localExact();
-    // (larger frames: from this bounce on -- the late launches of a batch are short whatever the frame; 255 = never)
-    const uint32_t localExactFromBounce = knobs::localExactFromBounce();
-    // (the second walk runs on the kernel's 24-entry stacks: scenes whose binary trees need deeper ones keep the separate launch)
-    // (never in front of the bidirectional integrator: its light paths produce degenerate closest-hit rays -- an emitted direction that is exactly a coordinate
-    //  axis -- which walk alone for milliseconds and would hold a whole block's slot of the CU meanwhile: 16.5 -> 26 ms per pass, profiles/r04_vcm_wide_ab.txt, measured
-    //  when the separate launch still handed them on to k_trace_monster; that hand-over is opt-in since round 5 (launchRetrace), the separate launch stays: it
-    //  holds one block per CU instead of the traversal grid)
-    const bool localExact = s.mayTraceUndecidedRaysItself && c->traversalStackNeed <= 24u && (localExactEnv >= 0 ? localExactEnv != 0 : (c->localRetrace >= 0 ? c->localRetrace != 0 : (c->numSlots < 400000u || s.bounce >= localExactFromBounce)));   // (round 5, with re-trace launches that hand long rays on and share subtrees early: a 1/8 shard still gains 3 % from it, a 1/4 shard (518 k pixels) now LOSES 2 %, halves 0: profiles/r05_shard_policy.txt)
+    // ran beside the other lanes' kernels) -- profiles/r04_local_exact_ab.txt; round 5: a 1/8 shard still gains 3 %, a 1/4 shard (518 k pixels) loses 2 %, halves 0
+    // -- profiles/r05_shard_policy.txt.  So: small frames, unless rtgpu_set_schedule says otherwise.  Never on stacks deeper than the kernel's 24 entries (the
+    // second walk runs on them), never where the caller forbids it (the bidirectional integrator: a degenerate closest-hit ray of a light path would hold a whole
+    // block's slot of the CU for milliseconds, 16.5 -> 26 ms per pass, profiles/r04_vcm_wide_ab.txt; its separate launch holds one block per CU instead).
+    const bool localExact = s.mayTraceUndecidedRaysItself && c->traversalStackNeed <= 24u && (c->localRetrace >= 0 ? c->localRetrace != 0 : c->numSlots < 400000u);
     const uint32_t chunkMin = knobs::wideChunkMin();   // tuning knob
+    // drainAbortAfter, a test hook read per launch: a wave whose work queue ran dry N loop iterations ago hands the rays it still walks -- hits half found, written
+    // through -- to the re-trace launch (the stack-overflow path, which the benchmark frame never takes).  As a schedule it moves time, it does not save any: what
+    // k_trace_wide's drain loses (-5.6 % at N = 8) the re-trace launches gain (profiles/r05_drain_abort_ab.txt)
+    // The work queue {closest-hit rays of bounce k, any-hit requests of bounce k - 1} is taken front to back: a launch ends with the drain of its last rays, so the
+    // SHORT rays belong at the end, and under the far-first order of the interior step (rt_wide_walk.h) those are the any-hit rays: 9.9 interior visits against a
+    // closest-hit ray's 17 (profiles/r06_claim_order_ab.txt: against the queue taken from its end, trace 47.5 -> 45.5 ms per 25 passes, +2 % on a 1/8 shard).
     WideTuning tune = { c->tune.refillMinIdle, c->tune.otherMinLanes, s.shadowOffset, s.exactQueue, s.exactCount, s.exactShadowQueue, s.exactShadowCount, s.denseCounts,
-                        s.denseShardCapacity, chunkMin < 64u ? 64u : chunkMin, localExact ? 1u : 0u, 0u };
-    // test hook, read per launch: a wave whose work queue ran dry N loop iterations ago hands the rays it still walks -- hits half found, written through -- to the
-    // re-trace launch (the stack-overflow path, which the benchmark frame never takes).  As a schedule it moves time, it does not save any: what k_trace_wide's drain
-    // loses (-5.6 % at N = 8) the re-trace launches gain, with or without k_trace_monster behind them (profiles/r05_drain_abort_ab.txt)
-    tune.drainAbortAfter = knobs::wideDrainAbort();
-    // The order the work queue {closest-hit rays of bounce k, any-hit requests of bounce k - 1} is taken in: a launch ends with the drain of its last rays, so the
-    // SHORT rays belong at the end.  Round 5 took it from its END (any-hit requests first): unoccluded next-event rays, which no hit ever shortens, were the long
-    // ones (trace -1 %, shards +2 %, profiles/r05_claim_order_ab.txt).  Round 6's far-first order made any-hit rays the short ones (9.9 interior visits against a
-    // closest-hit ray's 17), and the queue is taken front to back again: trace 47.5 -> 45.5 ms per 25 passes, +1 % at 256 passes, +2 % on a 1/8 shard
-    // (profiles/r06_claim_order_ab.txt).  RTGPU_WIDE_REVERSE=1: from the end (read per launch: the tests run both orders)
-    tune.reverseOrder = knobs::wideReverse();
-    // any-hit rays walk the FARTHEST child they enter first (rt_wide_walk.h, interior step: occlusion is an OR over the candidates, and the occluders of a ray that starts on a
-    // surface are far from it); RTGPU_ANYHIT_FAR_FIRST=0: nearest first like closest-hit rays (read when the context is created: the tests run both orders)
-    tune.anyHitFarFirst = c->anyHitFarFirst;
+                        s.denseShardCapacity, chunkMin < 64u ? 64u : chunkMin, localExact ? 1u : 0u, knobs::wideDrainAbort() };
     const dim3 grid(traversalBlocks(c, 24u)), block(RT_BLOCK);
     LaunchTimer t(c, s.stream, KC_TRACE);
     if (c->wide.nodes == nullptr)
@@ -184,23 +172,14 @@ static TraceStep handedOver(TraceStep s)
     return s;
 }
 
-// The re-trace launch behind a 4-wide walk: the reference's own walk (k_trace) over the rays the walk handed over (0.1 % of a launch), and -- single-mesh
-// scenes -- k_trace_monster behind it for the closest-hit rays among them that k_trace gave up on: a direction that is exactly a coordinate axis turns
-// two of three slab tests into inf - inf and the ray walks most of the tree, alone in its wave (1.0-1.6 ms launches at bounce 1 where an ordinary one
-// takes 0.1-0.2 ms, profiles/r04_timeline_serial.txt); a whole block finds the same hit cooperatively.  `overflowQueue`: a queue of the lane nobody
-// uses during this bounce's trace (dense path state: none of the slot queues is in use; slot-per-pixel: the one the next shade will fill).
-// Its work is the hand-over of `s`; `s.overflowQueue` / `s.overflowCount`: null, or that queue and its count.
+// The re-trace launch behind a 4-wide walk: the reference's own walk (k_trace) over the rays the walk handed over (0.1 % of a launch).  It keeps every ray
+// it takes: since the axis-parallel prune (boxNearDegenerateAxes) made degenerate closest-hit rays short, no ray of the benchmark frame would go on to
+// k_trace_monster, and an empty launch of that kernel behind every re-trace launch cost 2 % end to end under concurrency
+// (profiles/r05_monsters_under_concurrency_ab.txt).  The cooperative walker serves the bidirectional integrator's launches (rt_runtime_vcm.inl).
+// Its work is the hand-over of `s`.
 static void launchRetrace(RtgpuContext* c, const TraceStep& s)
 {
-    const int abortEnv = knobs::abortRetraceAfter();   // test hook, read per launch (0: every closest-hit ray in flight when its wave's queue runs dry goes to k_trace_monster)
-    // OFF by default since the axis-parallel prune (boxNearDegenerateAxes) made the rays it was built for short: on the benchmark frame no ray is handed over any more,
-    // and the EMPTY k_trace_monster launch behind every re-trace launch is not free under concurrency -- its 64 blocks of 512 threads / 33 KB LDS wait for CU slots that the other
-    // lanes' persistent traversal kernels hold: 27.7 ms summed over the 40 launches of the driver's timed region (profiles/r05_concurrency.txt), 2 % end to end
-    // (profiles/r05_monsters_under_concurrency_ab.txt).  RTGPU_RETRACE_MONSTERS=1 (or the test hook RTGPU_ABORT_RETRACE_AFTER) switches the hand-over on; read per launch.
-    const bool monsters = knobs::retraceMonsters() && s.overflowQueue != nullptr && s.overflowCount != nullptr && c->wide.nodes != nullptr && c->sceneDev.numObjects == 1u && !c->countIntersections;
-    TravTuning exactTune = c->tune;
-    exactTune.overflowQueue = monsters ? s.overflowQueue : nullptr; exactTune.overflowCount = monsters ? s.overflowCount : nullptr;
-    exactTune.abortClosestAfter = abortEnv >= 0 ? (uint32_t)abortEnv : RT_ABORT_RETRACE_AFTER;
+    TravTuning exactTune = c->tune;   // (no overflow queue: the launch hands nothing on)
     exactTune.denseCounts = nullptr; exactTune.denseShardCapacity = 0u;
     // a re-trace launch's queue is dry after the first claim and its duration is its longest ray: an any-hit ray that slides along a wall it started on (a sun in a
     // coordinate plane: the ray lies IN the wall's plane, Moeller-Trumbore never accepts the coplanar triangles) walks ~170 nodes = 250 us alone.  Idle lanes take its
@@ -216,7 +195,6 @@ static void launchRetrace(RtgpuContext* c, const TraceStep& s)
     exactTune.baseBlocks = adaptiveGrid ? c->numCUs : 0u; exactTune.fullGridAbove = c->numCUs * 256u * 4u;
     const dim3 retraceGrid(adaptiveGrid ? traversalBlocks(c, stackClassOf(c)) : c->numCUs);
     launchTraceBinary(c, handedOver(s), retraceGrid, exactTune, false);
-    if (monsters) hipLaunchKernelGGL(k_trace_monster, dim3(64), dim3(RT_MONSTER_BLOCK), 0, s.stream, c->sceneDev, s.paths, s.overflowQueue, s.overflowCount);
 }
 
 // One trace step of a launch sequence.  `wide` (the render sequences: useWide(c)): the 4-wide tree serves the launch; what it does not trust goes through the
@@ -230,18 +208,16 @@ static void launchTraceStep(RtgpuContext* c, const TraceStep& s, bool wide)
     launchTraceBinary(c, s, dim3(traversalBlocks(c, stackClassOf(c))), tune, s.rayCounts != nullptr || c->countIntersections);
 }
 
-// The bounce at which a dense batch hands its remaining paths to k_tail (0: never).  RTGPU_TAIL_DEPTH=n forces bounce n (0: off).
+// The bounce at which a dense batch hands its remaining paths to k_tail (0: never).  rtgpu_set_schedule forces a bounce (0: off).
 static uint32_t tailDepthFor(const RtgpuContext* c, uint32_t maxRayDepth, bool denseAll)
 {
-    const int env = knobs::tailDepth();
-    if (env == 0 || c->tailBounce == 0 || denseAll || c->wide.nodes == nullptr || !useWide(c) || stackClassOf(c) != 24u || c->debugMode >= 0) return 0u;
+    if (c->tailBounce == 0 || denseAll || c->wide.nodes == nullptr || !useWide(c) || stackClassOf(c) != 24u || c->debugMode >= 0) return 0u;
     // Measured (profiles/r04_tail_sweep.txt, 20 passes): a 1/8 shard of the full-HD benchmark frame gains 6-8 % with the hand-over at bounce 4 or 5 (0.580 ->
     // 0.544 ms per pass, with 20-pass batches 0.575-0.606 -> 0.526-0.558; bounce 2: -20 %, 3: 0), a 1/4 shard +2 % at bounce 5 and +4 % at bounce 6 together with the block-local re-trace, halves and full frames lose 1-5 % at any bounce: the block-local
     // rounds pay a drain each and only beat the launch sequence where that is all floors.  So: small frames only.  Round 5 (faster traversal and re-trace launches,
     // profiles/r05_shard_policy.txt): bounce 6 beats 5 on the 1/8 shard too (0.499 -> 0.488 ms per pass), 4 loses everywhere, halves gain 0.6 % at 6 (left off).
-    uint32_t depth = env > 0 ? (uint32_t)env : (c->tailBounce > 0 ? (uint32_t)c->tailBounce : (c->numSlots < 700000u ? 6u : 0u));
-    if (depth > maxRayDepth + 1u) return 0u;
-    return depth;
+    const uint32_t depth = c->tailBounce > 0 ? (uint32_t)c->tailBounce : (c->numSlots < 700000u ? 6u : 0u);
+    return depth > maxRayDepth + 1u ? 0u : depth;
 }
 
 // The scene-class ladders of the shading kernels and of the fused tail (rt_shade_kernels.h, rt_tail_kernels.h): kLean class, plain path tracer, all lights
@@ -256,14 +232,12 @@ static int submitDenseBatch(RtgpuContext* c, BatchLane& l, const LaneCounts& cou
     const dim3 block(RT_BLOCK);
     const uint32_t shardCapacity = (totalSlots + RT_DENSE_SHARDS - 1u) / RT_DENSE_SHARDS + 65536u;
     const uint32_t plane = 2u * RT_DENSE_SHARDS;
-    // a fresh path's records: only origin and direction are stored, bounce 0's shade rebuilds the rest from the slot (rt_dense.inl); RTGPU_FULL_PRIMARY=1: all seven.
+    // a fresh path's records: only origin and direction are stored, bounce 0's shade rebuilds the rest from the slot (rt_dense.inl)
     // (the tail kernel never sees bounce 0 -- tailDepthFor returns >= 1 -- and the traversal kernels read origin and direction only)
-    const bool leanPrimary = !knobs::fullPrimary();
     HIP_TRY(hipMemsetAsync(l.denseCounts, 0, (size_t)plane * (l.queueCountCapacity + 1u) * sizeof(uint32_t), l.stream));
     {
         LaunchTimer t(c, l.stream, KC_GENERATE);
-        hipLaunchKernelGGL(k_generate_dense, grid, block, 0, l.stream, c->sceneDev, passesDev, c->numSlots, l.paths, c->slotPixel, totalSlots, shardCapacity, l.denseCounts, c->counters,
-                           leanPrimary ? 0u : 1u);
+        hipLaunchKernelGGL(k_generate_dense, grid, block, 0, l.stream, c->sceneDev, passesDev, c->numSlots, l.paths, c->slotPixel, totalSlots, shardCapacity, l.denseCounts, c->counters);
     }
     const bool haveNee = c->numLights != 0 && !c->plainPathTracer;
     // The fused tail (rt_tail.hip): from bounce `tailDepth` on, one persistent launch takes the batch's remaining paths to their end.  Single-mesh
@@ -276,8 +250,7 @@ static int submitDenseBatch(RtgpuContext* c, BatchLane& l, const LaneCounts& cou
         const Paths out = denseLayout((depth & 1u) ? l.paths : l.paths2);
         if (tailDepth != 0u && depth == tailDepth)
         {
-            const TailArgs args = { l.denseCounts + (size_t)plane * depth, shardCapacity, counts.cursors + depth, c->tune.refillMinIdle, c->tune.otherMinLanes, c->deviceFlags,
-                                    c->anyHitFarFirst };
+            const TailArgs args = { l.denseCounts + (size_t)plane * depth, shardCapacity, counts.cursors + depth, c->tune.refillMinIdle, c->tune.otherMinLanes, c->deviceFlags };
             uint32_t tailBlocks = (totalSlots + RT_TAIL_PATHS - 1u) / RT_TAIL_PATHS;   // never more blocks than chunks of the whole batch
             if (tailBlocks > c->numCUs * knobs::tailBlocksPerCU()) tailBlocks = c->numCUs * knobs::tailBlocksPerCU();   // tuning knob
             const dim3 tailGrid(tailBlocks ? tailBlocks : 1u);
@@ -292,13 +265,13 @@ static int submitDenseBatch(RtgpuContext* c, BatchLane& l, const LaneCounts& cou
         {
             TraceStep s = { l.stream, c->counters, in };
             counts.queuesOf(s, depth, false, haveShadow);   // (the closest-hit rays are the arena's live paths: no queue)
-            counts.handOverOf(s, depth, l.queues[0]);       // (none of the slot queues is in use)
+            counts.handOverOf(s, depth);
             s.denseCounts = haveClosest ? l.denseCounts + (size_t)plane * depth : nullptr; s.denseShardCapacity = shardCapacity; s.bounce = depth;
             launchTraceStep(c, s, useWide(c));
         }
         // bounce `depth`: shades the live paths; folds the visibility results of the previous bounce's zombies in (the last round does only that)
         const DenseCounts dc = { l.denseCounts + (size_t)plane * depth, l.denseCounts + (size_t)plane * (depth + 1u), shardCapacity, c->deviceFlags,
-                                 leanPrimary && depth == 0u ? c->slotPixel : nullptr };
+                                 depth == 0u ? c->slotPixel : nullptr };
         LaunchTimer t(c, l.stream, KC_SHADE);
         if (c->plainPathTracer) RT_LAUNCH_SHADE_DENSE(0, true, false);
         else if (denseAll) { if (c->leanScene == 1) RT_LAUNCH_SHADE_DENSE(1, false, true); else if (c->leanScene == 2) RT_LAUNCH_SHADE_DENSE(2, false, true); else if (c->leanScene == 4) RT_LAUNCH_SHADE_DENSE(4, false, true); else RT_LAUNCH_SHADE_DENSE(0, false, true); }
@@ -311,7 +284,7 @@ static int submitDenseBatch(RtgpuContext* c, BatchLane& l, const LaneCounts& cou
 #undef RT_LAUNCH_TAIL
 
 // The bounces of a slot-per-pixel sequence on lane `l` (a batch lane or the recorder's), after its k_generate.  Bounce k: trace {closest-hit rays of bounce k,
-// next-event rays of bounce k - 1} -> shade(k); one last trace for the next-event rays of the final bounce.  A bounce's overflow queue: the one its shade will fill.
+// next-event rays of bounce k - 1} -> shade(k); one last trace for the next-event rays of the final bounce.
 template <class Shade>
 static void launchSlotBounces(RtgpuContext* c, hipStream_t stream, unsigned long long* counters, const BatchLane& l, const LaneCounts& counts, uint32_t maxRayDepth, uint32_t lastDepth,
                               bool haveNee, Shade shade)
@@ -323,7 +296,7 @@ static void launchSlotBounces(RtgpuContext* c, hipStream_t stream, unsigned long
         {
             TraceStep s = { stream, counters, l.paths };
             counts.queuesOf(s, depth, haveClosest, haveShadow);
-            counts.handOverOf(s, depth, l.queues[(depth + 1u) & 1u]);
+            counts.handOverOf(s, depth);
             launchTraceStep(c, s, useWide(c));
         }
         if (haveClosest) shade(depth);

@@ -55,7 +55,7 @@ template <int kLean>
 __global__ void __launch_bounds__(RT_BLOCK) k_aov_resolve RT_K_AOV_RESOLVE_ARGS;
 __global__ void __launch_bounds__(RT_BLOCK) k_generate_dense(const RtSceneDesc scene, const DevPass* __restrict__ passes, uint32_t slotsPerPass, const Paths paths,
                                                              const uint32_t* __restrict__ slotPixel, uint32_t numSlots, uint32_t shardCapacity, uint32_t* __restrict__ counts,
-                                                             unsigned long long* counters, uint32_t fullRecords);
+                                                             unsigned long long* counters);
 template <int kLean, bool kPlain = false, bool kAll = false>
 __global__ void RT_SHADE_DENSE_ATTR(kLean, kAll) k_shade_dense RT_K_SHADE_DENSE_ARGS;
 __global__ void __launch_bounds__(RT_BLOCK) k_accumulate_home(const float4* __restrict__ home, const uint32_t* __restrict__ slotPixel, uint32_t slotsPerPass, uint32_t numPasses,

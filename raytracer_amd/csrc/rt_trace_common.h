@@ -57,9 +57,9 @@ struct TravTuning
                               // triangle tests of the slot's closest-hit ray, stored when the ray completes (the cost planes of rtgpu_render_aovs)
 };
 #define RT_ABORT_CLOSEST_AFTER 768u
-// the same hand-over in the re-trace launches behind the 4-wide walks (PathTracerMIS) and in a block's local second walk: their queues hold a few
-// thousand rays, a wave's queue is dry after its first claim, an ordinary ray is done within ~10 rounds (a round = a run of interior steps + a leaf)
-#define RT_ABORT_RETRACE_AFTER 96u
+// the same hand-over in a block's local second walk (k_trace_wide), whose overflow queue is the launch's exact queue: its lists hold a few hundred
+// rays, a wave's queue is dry after its first claim, an ordinary ray is done within ~10 rounds (a round = a run of interior steps + a leaf)
+#define RT_ABORT_LOCAL_AFTER 96u
 
 #define RT_COUNTER_RETRACED 12   // counters[]: rays the 4-wide walks handed to the binary-tree walk (RtCounters::numRetracedRays)
 #define RT_MONSTER_BLOCK 512

@@ -100,7 +100,6 @@ RT_DEV void traceWideLoop(const RtSceneDesc& scene, const WideBvh& bvh, const Pa
                 if (chunk.next >= chunk.end) { exhausted = true; if (kDiag) diagExhausted = (unsigned long long)clock64(); continue; }
             }
             uint32_t idx = waveTake(!have, chunk);
-            if (tune.reverseOrder != 0u && idx != 0xFFFFFFFFu) idx = count - 1u - idx;
             bool tookUntrusted = false, tookShadow = false;
             if (idx != 0xFFFFFFFFu)
             {
@@ -163,7 +162,7 @@ RT_DEV void traceWideLoop(const RtSceneDesc& scene, const WideBvh& bvh, const Pa
                 if (kDiag) { diagSlots++; if (in) diagVisits++; }
                 if (in)
                 {
-                    const WideStep next = wideInteriorStep(bvh.nodes + 4u * cur, stack, 0u, sp, ax, ay, az, bx, by, bz, selX, selY, selZ, limit, tol, tune);
+                    const WideStep next = wideInteriorStep(bvh.nodes + 4u * cur, stack, 0u, sp, ax, ay, az, bx, by, bz, selX, selY, selZ, limit, tol);
                     cur = next.cur; sp = next.sp;
                     if (kDiag && sp > diagMaxSp) diagMaxSp = sp;
                     if (sp + 3u > (uint32_t)kStack) { overflow = true; cur = RT_QUANT_DONE; }   // the next step could not push: the binary-tree kernel takes the ray
@@ -290,9 +289,9 @@ __global__ void __launch_bounds__(RT_BLOCK) __attribute__((amdgpu_waves_per_eu(k
         __syncthreads();
         if (sLocalCounts[0] + sLocalCounts[1] != 0u)
         {
-            // a degenerate closest-hit ray (an axis-parallel direction: it walks most of the tree) does not keep the block: past RT_ABORT_RETRACE_AFTER rounds
-            // it goes to the launch's exact queue, i.e. to the re-trace launch behind this one, which hands it on to k_trace_monster
-            const TravTuning exactTune = { tune.refillMinIdle, tune.otherMinLanes, tune.shadowOffset, tune.exactQueue, tune.exactCount, RT_ABORT_RETRACE_AFTER, nullptr, 0u, RT_RETRACE_SPLIT_AFTER };
+            // a degenerate closest-hit ray (an axis-parallel direction: it walks most of the tree) does not keep the block: past RT_ABORT_LOCAL_AFTER rounds
+            // it goes to the launch's exact queue, i.e. to the re-trace launch behind this one (one block per CU instead of this block's slot of the traversal grid)
+            const TravTuning exactTune = { tune.refillMinIdle, tune.otherMinLanes, tune.shadowOffset, tune.exactQueue, tune.exactCount, RT_ABORT_LOCAL_AFTER, nullptr, 0u, RT_RETRACE_SPLIT_AFTER };
             traceBinaryLoop<kStack, false>(scene, paths, sLocalExact, &sLocalCounts[0], sLocalShadow, &sLocalCounts[1], &sLocalCounts[2], counters, exactTune, sStack, sDensePrefix,
                                                   (uint32_t)RT_BLOCK / 64u);
         }

@@ -123,7 +123,6 @@ __global__ void __launch_bounds__(RT_BLOCK) __attribute__((amdgpu_waves_per_eu(k
                 if (chunk.next >= chunk.end) { exhausted = true; continue; }
             }
             uint32_t idx = waveTake(!have, chunk);
-            if (tune.reverseOrder != 0u && idx != 0xFFFFFFFFu) idx = count - 1u - idx;   // (as in k_trace_wide: the any-hit requests first)
             bool tookShadow = false;
             if (idx != 0xFFFFFFFFu)
             {
@@ -166,7 +165,7 @@ __global__ void __launch_bounds__(RT_BLOCK) __attribute__((amdgpu_waves_per_eu(k
             {
                 if (in)
                 {
-                    const WideStep next = wideInteriorStep(wide.nodes + 4u * (size_t)(nodeBase + cur), stack, levelBase, sp, ax, ay, az, bx, by, bz, selX, selY, selZ, limit, tol, tune);
+                    const WideStep next = wideInteriorStep(wide.nodes + 4u * (size_t)(nodeBase + cur), stack, levelBase, sp, ax, ay, az, bx, by, bz, selX, selY, selZ, limit, tol);
                     cur = next.cur; sp = next.sp;
                     if (sp + 3u > (uint32_t)kStack) { handOver = true; cur = RT_QUANT_DONE; }   // the next step could not push: the binary-tree kernel takes the ray
                 }

@@ -93,17 +93,18 @@ RT_DEV Ray wideWorldRay(float4 origin, float4 dir, bool shadow, float shadowOffs
 // One visit of the interior node at `node` (four child records) by the ray with the folded constants a, b, the byte selectors, `limit` (= best + 2 tol:
 // box occlusion with the slack that keeps every candidate within tol of the final hit in the walk) and `tol`: four slab tests, the entered children
 // sorted, all but one deferred on the lane's `stack` column from entry `sp` up; returns the reference to walk next and the new stack level.
-// (`tune` by reference, for its anyHitFarFirst: passed as a value, k_tail<1, false> spills two registers more.)  `floor` is the stack level the walk may
-// not pop below (0, or where the mesh level of a two-level walk began).  The overflow check and the diagnostics are the caller's.
+// `floor` is the stack level the walk may not pop below (0, or where the mesh level of a two-level walk began).  The overflow check and the diagnostics
+// are the caller's.
 //
 // Order.  (key, reference) pairs are sorted so that the children the ray enters come first and the ones it misses last (key = all ones); the first
 // numHit - 1 references are deferred and the LAST entered one is walked next: the nearest child for a closest-hit ray (key = 0x7FFFFFFF ^ bits(entry
 // distance): farthest first; the distance is >= 0, so its bits order like the float and there is no borrow), the FARTHEST for an any-hit ray
-// (key = bits(entry distance): nearest first; WideTuning::anyHitFarFirst, round 6).  A closest-hit ray wants its nearest child (hits shorten it).
+// (key = bits(entry distance): nearest first; round 6).  A closest-hit ray wants its nearest child (hits shorten it).
 // An any-hit ray has nothing to shorten -- it ends with the first occluder, wherever that lies -- and nearest-first is the worst order for it: a
 // next-event ray starts ON a surface, so the nearest boxes hold that surface's neighbours, which never occlude it; farthest first finds the walls
 // and roofs that do (step model over the benchmark's rays, tools/wide8/walk_model.cpp, profiles/r06_wide8_step_model.txt: 9.9 interior + 1.5 leaf
-// visits per any-hit ray instead of 16.0 + 2.6).  Occlusion is an OR over the same candidates: the result does not depend on the order.
+// visits per any-hit ray instead of 16.0 + 2.6; 13.6 % end to end against nearest first, profiles/r06_anyhit_order_ab.txt -- that order is no
+// longer selectable).  Occlusion is an OR over the same candidates: the result does not depend on the order.
 // The flip is rebuilt in every visit from `tol` behind an optimisation barrier: as a loop-invariant value it would be one more vector register
 // live across the loop -- the 97th: 20 bytes of scratch -- for three instructions per visit saved.
 // INVARIANT the flip rests on: `tol == 0` stands for "any-hit ray".  Any-hit rays keep tol = 0 (they track no runner-up), and every trusted
@@ -114,7 +115,7 @@ RT_DEV Ray wideWorldRay(float4 origin, float4 dir, bool shadow, float shadowOffs
 #define RT_WIDE_CE(ka, ra, kb, rb) { const bool c_ = ka > kb; const uint32_t lo_ = min(ka, kb), hi_ = max(ka, kb), rl_ = c_ ? rb : ra, rh_ = c_ ? ra : rb; ka = lo_; kb = hi_; ra = rl_; rb = rh_; }
 struct WideStep { uint32_t cur, sp; };
 RT_DEV WideStep wideInteriorStep(const float4* node, uint32_t* stack, uint32_t floor, uint32_t sp, float ax, float ay, float az, float bx, float by, float bz,
-                                 uint32_t selX, uint32_t selY, uint32_t selZ, float limit, float tol, const WideTuning& tune)
+                                 uint32_t selX, uint32_t selY, uint32_t selZ, float limit, float tol)
 {
     const float4 q0 = node[0], q1 = node[1], q2 = node[2], q3 = node[3];
     float n0, f0, n1, f1, n2, f2, n3, f3;
@@ -122,7 +123,7 @@ RT_DEV WideStep wideInteriorStep(const float4* node, uint32_t* stack, uint32_t f
     const bool h0 = f0 >= n0 && n0 < limit, h1 = f1 >= n1 && n1 < limit, h2 = f2 >= n2 && n2 < limit, h3 = f3 >= n3 && n3 < limit;
     float tolNow = tol;
     asm volatile("" : "+v"(tolNow));
-    const uint32_t orderFlip = (tolNow == 0.0f && tune.anyHitFarFirst != 0u) ? 0u : 0x7FFFFFFFu;
+    const uint32_t orderFlip = tolNow == 0.0f ? 0u : 0x7FFFFFFFu;
     uint32_t k0 = h0 ? orderFlip ^ ubits(n0) : 0xFFFFFFFFu, k1 = h1 ? orderFlip ^ ubits(n1) : 0xFFFFFFFFu;
     uint32_t k2 = h2 ? orderFlip ^ ubits(n2) : 0xFFFFFFFFu, k3 = h3 ? orderFlip ^ ubits(n3) : 0xFFFFFFFFu;
     uint32_t r0 = ubits(q0.w), r1 = ubits(q1.w), r2 = ubits(q2.w), r3 = ubits(q3.w);

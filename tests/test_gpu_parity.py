@@ -864,19 +864,14 @@ def assert_quant_identical(img, img2, counters, ref, ref2, ref_counters):
     assert counters["numRayBoxTests"] == 0 and counters["numRayTriangleTests"] == 0   # the reference's counters belong to its own walk
 
 
-@pytest.mark.parametrize("dense", ["0", "1", "back-to-front", "any-hit-nearest-first"])
+@pytest.mark.parametrize("dense", ["0", "1"])
 def test_wide_traversal_bit_exact_on_single_mesh_scenes(built, monkeypatch, dense):
     """k_trace_wide (4-wide collapse of the same tree, conservative 16-bit boxes, exact leaf gate, runner-up tracking, exact re-trace,
     stack-overflow hand-over) gives the reference's hits: images and ray / shadow-ray / hit counters identical to the oracle's binary-tree
     walk, with the dense and with the slot-per-pixel path state, and only a small fraction of the rays needs the exact re-trace.
-    Round 6: any-hit rays walk the FARTHEST child they enter first by default (occlusion is an OR over the candidates: the order cannot
-    change a result); the last case runs them nearest first like closest-hit rays (RTGPU_ANYHIT_FAR_FIRST=0) -- same bits either way."""
+    Round 6: any-hit rays walk the FARTHEST child they enter first (occlusion is an OR over the candidates: the order cannot change a result)."""
     monkeypatch.setenv("RTGPU_WIDE", "1")
     monkeypatch.setenv("RTGPU_NO_DENSE", "1" if dense == "0" else "0")
-    if dense == "back-to-front":
-        monkeypatch.setenv("RTGPU_WIDE_REVERSE", "1")   # (round 5's default: a launch's queue taken from its end; round 6 takes it front to back)
-    if dense == "any-hit-nearest-first":
-        monkeypatch.setenv("RTGPU_ANYHIT_FAR_FIRST", "0")
     w, h = 128, 72
     scene, camera = scene_zoo.mesh_scene(w / h, triangles=8000, with_analytic=False)
     out = run_quant(scene, camera, w, h, passes=3, max_ray_depth=8)
@@ -976,51 +971,6 @@ def test_packet_walk_of_the_camera_rays_gives_the_reference_hits(built, monkeypa
     assert_quant_identical(*out)
 
 
-@pytest.mark.parametrize("abort_after", ["0", "3", None, "monsters"])
-def test_retrace_launch_hands_long_closest_hit_rays_to_the_cooperative_walker(built, monkeypatch, abort_after):
-    """Round 5: the re-trace launch behind k_trace_wide (the reference's own walk over the 0.1 % of the rays the 4-wide walk does not decide) CAN hand
-    closest-hit rays that are still walking RT_ABORT_RETRACE_AFTER scheduling rounds after their wave's queue ran dry to k_trace_monster, which finds
-    the same hit with a whole block (degenerate axis-parallel rays walk most of the tree: 1-1.6 ms alone in a wave).  The hand-over is OFF by default since
-    the axis-parallel prune (rt_runtime.hip launchRetrace); setting RTGPU_ABORT_RETRACE_AFTER switches it on: 0 sends EVERY ray in flight at that moment down
-    that path, 3 the slower ones.  The `None` case is the product default (no hand-over, no k_trace_monster launch) and RTGPU_RETRACE_MONSTERS=1 with the
-    default threshold is covered by the fourth case.  Images and counters are the oracle's in all of them -- separate re-trace launch and block-local second
-    walk (whose aborted rays go to the launch's exact queue, then re-trace launch, then monster), dense and slot-per-pixel path state."""
-    if abort_after == "monsters":
-        monkeypatch.setenv("RTGPU_RETRACE_MONSTERS", "1")
-        abort_after = None
-    if abort_after is not None:
-        monkeypatch.setenv("RTGPU_ABORT_RETRACE_AFTER", abort_after)
-    w, h = 160, 96
-    scene, camera = scenes.sponza_class(w / h, 30000)
-    desc = scene.desc
-    bn = ra.load_blue_noise()
-    desc.contents.blueNoise = bn.ctypes.data
-    lib = ra.rtgpu_lib()
-    reference = None
-    for local_retrace, no_dense in ((0, False), (1, False), (0, True)):
-        if no_dense:
-            monkeypatch.setenv("RTGPU_NO_DENSE", "1")
-        vp = ra.Viewport(w, h, seed=777, max_ray_depth=6)
-        vp.set_renderer(scene)
-        ctx = vp.device_context()
-        assert lib.rtgpu_set_intersection_counters(ctx, 0) == 0
-        assert lib.rtgpu_set_schedule(ctx, C.c_uint32(0), C.c_int32(0)) == 0 and lib.rtgpu_set_schedule(ctx, C.c_uint32(1), C.c_int32(local_retrace)) == 0
-        if reference is None:
-            ref = np.zeros((h, w, 3), dtype=np.float32); ref2 = np.zeros((h, w, 3), dtype=np.float32)
-            cnt = np.zeros(16, dtype=np.uint64)
-            for _ in range(3):
-                p = vp.next_pass_params(camera)
-                vp.render_pass_with(p)
-                oracle_lib.render_pass(desc, p, w, h, ref, ref2, cnt, threads=8)
-            reference = (ref, ref2, {n: int(cnt[i]) for i, n in enumerate(ra.COUNTER_NAMES)})
-        else:
-            vp.render(camera, 3)    # the same seed => the same per-pass constants
-        img, img2 = vp.sum_buffer(secondary=True)
-        counters = vp.counters()
-        assert_quant_identical(img, img2, counters, *reference)
-        assert counters["numRetracedRays"] > 0
-
-
 def test_wide_traversal_hands_over_rays_whose_stack_would_overflow(built, monkeypatch):
     """A pathological mesh -- 64 nested sheets around the camera axis, sizes and distances growing by 1.6 from one to the next: the SAH
     builder peels them off a few at a time (a tree 22 levels deep for 128 triangles), and a ray through the stack of sheets enters every
@@ -1107,10 +1057,8 @@ def test_two_level_scenes_with_the_counters_off(built, monkeypatch):
     the rays it does not decide to the binary-tree kernel; and with RTGPU_WIDE2=0 the binary walk without the counting code, where a wave's
     idle lanes take over subtrees of its longest any-hit rays at the end of a launch.  Images and ray counters are the oracle's either way."""
     w, h = 192, 108
-    for wide2 in ("1", "0", "1 any-hit nearest first"):
-        monkeypatch.setenv("RTGPU_WIDE2", wide2[0])
-        monkeypatch.setenv("RTGPU_ANYHIT_FAR_FIRST", "0" if "nearest" in wide2 else "1")   # (round 6: any-hit rays walk the farthest entered child first by default)
-        wide2 = wide2[0]
+    for wide2 in ("1", "0"):
+        monkeypatch.setenv("RTGPU_WIDE2", wide2)
         scene, camera = scene_zoo.mesh_scene(w / h, triangles=20000)
         out = run_quant(scene, camera, w, h, passes=3, max_ray_depth=6)
         assert_quant_identical(*out)

@@ -4,7 +4,7 @@ store their shading point there), the occlusion verdict in the contribution reco
 
 Bar: as tests/test_gpu_parity.py -- BIT-EXACT sum buffers and IDENTICAL ray counters against the CPU oracle.  Every case renders a
 small frame; a scene's oracle image is computed once and shared by the launch-sequence variants of that scene.  The fused tail is switched
-on through rtgpu_set_schedule: RTGPU_TAIL_DEPTH is read once per process."""
+on through rtgpu_set_schedule, per context."""
 import ctypes as C
 
 import numpy as np

@@ -1,4 +1,4 @@
-"""Walk statistics: the binary tree (reference counters) or the 4-wide tree (RTGPU_WIDE=1 RTGPU_WIDE_DIAG=1 [RTGPU_WIDE_SORT=1])."""
+"""Walk statistics: the binary tree (reference counters) or the 4-wide tree (RTGPU_WIDE=1 RTGPU_WIDE_DIAG=1)."""
 import os, sys
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import raytracer_amd as ra
