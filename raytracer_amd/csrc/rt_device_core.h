@@ -6,6 +6,7 @@
 
 #include "rt_device_math.h"
 #include "../../include/rtgpu.h"
+#include "rt_wide_format.h"
 
 namespace rtd {
 
@@ -368,11 +369,8 @@ RT_DEV bool lightTestRayHit(const RtLight& L, const Ray& ray, float& outDistance
 }
 
 // MeshShape::EvaluateIntersection, MeshShape.cpp:283-328
-// The device copy of the scene holds the shading data DE-INDEXED: one 128-byte record per triangle (its three VertexShadingData and
-// its material), in triangle order, where the C ABI's vertexIndices[] would be (vertexShading[] is not uploaded).  A hit then costs
-// one memory round trip to one aligned 128-byte line instead of the index record followed by three scattered 32-byte vertices.
-struct __attribute__((aligned(16))) TriangleShading { RtVertexShading v[3]; uint32_t materialIndex; uint32_t _pad[7]; };
-static_assert(sizeof(TriangleShading) == 128, "TriangleShading");
+// The device copy of the scene holds the shading data DE-INDEXED: one TriangleShading record per triangle (rt_wide_format.h) where the C ABI's
+// vertexIndices[] would be.
 RT_DEV void meshEvaluateIntersection(const RtSceneDesc& d, const RtMesh& mesh, const Hit& hit, Intersection& out)
 {
     const TriangleShading& tri = reinterpret_cast<const TriangleShading*>(d.vertexIndices)[mesh.firstTriangle + hit.subObjectId];
@@ -424,9 +422,8 @@ RT_DEV float bcGrayscale(const uint8_t* blockData, uint32_t x, uint32_t y)
 }
 // One texel as Bitmap::GetPixel / GetPixelBlock decode it (Bitmap.cpp:335-517, 520-832; loads: Math/Vector4Load.h):
 // every UNorm load is float(integer) * RN(1 / max) -- the SSE paths scale by powers of two around that, exactly.
-// kSimple: the scene holds only RT_FORMAT_IS_SIMPLE bitmaps (scene class 4, below) -- the same decode, three-and-a-half cases instead of 23, small
+// kSimple: the scene holds only RT_FORMAT_IS_SIMPLE bitmaps (rt_wide_format.h; scene class 4, below) -- the same decode, three-and-a-half cases instead of 23, small
 // enough to be inlined at every call site of the shading kernel.
-#define RT_FORMAT_IS_SIMPLE(f) ((f) == RT_FORMAT_B8G8R8_UNORM || (f) == RT_FORMAT_B8G8R8A8_UNORM || (f) == RT_FORMAT_R8G8B8A8_UNORM || (f) == RT_FORMAT_R16G16B16A16_HALF)
 template <bool kSimple = false>
 RT_DEV V4 bitmapTexel(const RtTexture& t, const uint8_t* texels, uint32_t x, uint32_t y)
 {

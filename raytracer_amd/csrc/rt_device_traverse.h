@@ -31,9 +31,7 @@ enum TravMode : uint32_t
     TRAV_MESH = 3       // cur is a node of the current mesh's BVH
 };
 
-#define RT_NODE_LEAVES_SHIFT 30u
-#define RT_NODE_CHILD_MASK 0x3FFFFFFFu
-#define RT_MAX_PACKED_LEAVES 3u    // numLeaves must fit two bits (the reference builds leaves of <= 2, BVHBuilder.h:16)
+// (a packed node is childIndex | numLeaves << RT_NODE_LEAVES_SHIFT: rt_wide_format.h, which the host's tree builders share)
 #define RT_LEVEL_EXHAUSTED 0xFFFFFFFFu   // cur: the current level has no node left (its part of the stack is empty)
 
 RT_DEV uint32_t packNode(uint32_t childIndex, uint32_t leavesWord) { return childIndex | (leavesOf(leavesWord) << RT_NODE_LEAVES_SHIFT); }

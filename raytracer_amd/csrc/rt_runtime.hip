@@ -26,7 +26,7 @@
 //
 // This file is the translation unit and keeps the contexts, the film and the small entry points; its parts: rt_runtime_context.h (RtgpuContext, BatchLane,
 // staging copies, stream pool, HIP_TRY, LaunchTimer, free helpers), rt_knobs.h (every RTGPU_* environment variable), rt_multi.inl (multi-device contexts),
-// rt_runtime_scene.inl (rtgpu_upload_scene, rtgpu_update_objects), rt_runtime_render.inl (arena sizing, traversal launchers, batch submission), rt_runtime_vcm.inl (bidirectional
+// rt_runtime_scene.inl (rtgpu_upload_scene, rtgpu_update_objects: the copies of what rt_scene_prepare.h checks and builds on the host), rt_runtime_render.inl (arena sizing, traversal launchers, batch submission), rt_runtime_vcm.inl (bidirectional
 // integrator, Light Tracer), rt_runtime_kat.inl (known-answer hooks, rtgpu_evaluate_textures), rt_runtime_query.inl (batched ray queries), rt_runtime_paths.inl (path records),
 // rt_runtime_aov.inl (AOVs), rt_runtime_denoise.inl (the a-trous filter, rtgpu_denoise, rtgpu_postprocess_from),
 // rt_runtime_temporal.inl (temporal accumulation).
@@ -46,10 +46,7 @@
 
 using namespace rtd;
 
-#define RT_HOST_BUILDERS 1
-#include "rt_wide_grid.inl"
-#include "rt_trace_wide.inl"
-#include "rt_trace_wide2.inl"
+#include "rt_scene_prepare.h"
 #include "rt_trace_kernels.h"
 #include "rt_shade_kernels.h"
 #include "rt_tail_kernels.h"

@@ -1,6 +1,7 @@
 // rt_trace.hip -- the traversal kernels of the library and the small kernels around them, a translation unit of their own:
 //   rt_trace_binary.inl   k_trace (the reference's walk: binary BVH, near child first), k_trace_monster
-//   rt_wide_grid.inl      the 16-bit grid, the leaf gates, WideTuning and the exactness argument the 4-wide walks share
+//   rt_wide_grid.inl      the exactness argument the 4-wide walks share (their format -- grid, node records, leaf gates, WideTuning -- is rt_wide_format.h,
+//                         which every unit has through rt_device_core.h; the host builds the trees in rt_scene_prepare.h)
 //   rt_wide_walk.h        the device parts the 4-wide walks share: slab test, hand-over lists, request ray, fold, interior step, mesh leaf (pair, gate, acceptance), finish, tallies
 //   rt_trace_wide.inl     k_trace_wide (4-wide tree of a single-mesh scene; the rays it does not decide go through the reference's walk in the same launch)
 //   rt_trace_packet.inl   k_trace_packet (the camera rays of a dense batch: one wave walks the 4-wide tree for an 8 x 8 pixel block, the node is uniform)

@@ -1,7 +1,7 @@
 // rt_trace_wide.inl -- traversal of single-mesh scenes over a 4-WIDE tree collapsed from the reference's binary tree (same SAH splits,
-// same leaves), one ray per lane.  Included by rt_trace.hip (kernels: RT_DEVICE_KERNELS) and rt_runtime.hip (tree builders: RT_HOST_BUILDERS) after rt_wide_grid.inl, whose grid, leaf gates and exactness argument it
+// same leaves), one ray per lane.  Device only; included by rt_trace.hip and rt_tail.hip after rt_wide_grid.inl, whose exactness argument it
 // shares; the device parts it has in common with the other 4-wide walks (slab test, hand-over lists, request ray, fold, interior step, mesh leaf, finish, tallies) are
-// rt_wide_walk.h.
+// rt_wide_walk.h.  The tree's format (WideBvh, node records, gates) is rt_wide_format.h; the host builds it in rt_scene_prepare.h (buildQuantBvh, buildWideBvh).
 //
 // Why.  k_trace waits ~0.8 us per dependent node fetch with 20 waves per CU to hide it: the walk is a chain of ~29 round
 // trips per ray.  Two earlier attempts changed what a round trip moves -- half the bytes (k_trace_quant: no gain, the conversions ate
@@ -14,25 +14,10 @@
 // fat leaves, one gate per ray, deferred children in slot order, one-wave blocks) spilled on the 96-VGPR cliff or lost otherwise; their
 // measurements are in profiles/r02_wide_diag.txt and DESIGN 4, their code is in the history (round 2), not here.
 //
-// Node n = records nodes[4 n .. 4 n + 3], one per child: {min.xyz, max.xyz as 16-bit grid coordinates (rounded outwards, QuantBvh's
-// grid), reference}.  A reference is an interior node's index, a leaf (first triangle | count << 30, the binary tree's own leaves of
-// one or two triangles), or RT_WIDE_EMPTY behind a degenerate box for the unused slots of a node with two or three children.
-//
-// Exactness: k_trace_quant's argument word for word (conservative boxes visit a superset of the reference's leaves in another order;
+// Exactness: the argument of rt_wide_grid.inl word for word (conservative boxes visit a superset of the reference's leaves in another order;
 // a leaf's triangles count only behind the leaf's exact box; runner-up within tol, zero direction components, far origins -> the
 // binary-tree kernel decides), plus one more hand-over: a ray whose stack would overflow.
 
-#define RT_WIDE_EMPTY 0xC0000000u    // leaf count 3 never occurs in the reference's trees (BVHBuilder.h:16): "no child"
-
-struct WideBvh
-{
-    const float4* nodes;
-    const float4* gate;      // QuantBvh::gate
-    uint32_t numNodes;
-    float base[3], step[3], bound[3];
-};
-
-#ifdef RT_DEVICE_KERNELS
 #define RT_WIDE_STACK 16           // stack entries per lane of the 4-wide walk
 #define RT_WIDE_PARK 6u            // words per lane behind the stack (traceWideLoop's `park`)
 #define RT_WIDE_LOCAL_EXACT 256u   // per block and kind: ~40 x what a block of the benchmark hands over per launch
@@ -297,69 +282,3 @@ __global__ void __launch_bounds__(RT_BLOCK) __attribute__((amdgpu_waves_per_eu(k
         }
     }
 }
-#endif   // RT_DEVICE_KERNELS
-
-#ifdef RT_HOST_BUILDERS
-// ---- host: collapse of the reference's binary tree.  A wide node starts as the two children of a binary node; while it has a free
-// slot, its interior child with the largest surface area is replaced by that child's own two children.  Node indices are breadth first.
-struct WideBuild
-{
-    std::vector<float4> nodes;
-    bool ok = false;
-};
-
-static WideBuild buildWideBvh(const RtNode* nodes, uint32_t numNodes, const QuantBuild& q)
-{
-    WideBuild w;
-    if (!q.ok) return w;
-    auto isLeaf = [&](uint32_t n) { return (nodes[n].leaves & 0x3FFFFFFFu) != 0u; };
-    auto area = [&](uint32_t n)
-    {
-        const double ex = (double)nodes[n].max[0] - nodes[n].min[0], ey = (double)nodes[n].max[1] - nodes[n].min[1], ez = (double)nodes[n].max[2] - nodes[n].min[2];
-        return ex * ey + ey * ez + ez * ex;
-    };
-    std::vector<uint32_t> wideOf(numNodes, 0xFFFFFFFFu);   // binary interior node -> wide node
-    std::vector<uint32_t> order;                            // wide node -> binary node
-    order.push_back(0u); wideOf[0] = 0u;
-    std::vector<uint32_t> children;                         // 4 binary node indices per wide node (0xFFFFFFFF: empty)
-    for (size_t i = 0; i < order.size(); ++i)
-    {
-        const uint32_t n = order[i];
-        uint32_t list[4]; uint32_t num = 2;
-        list[0] = nodes[n].childIndex; list[1] = nodes[n].childIndex + 1u;
-        while (num < 4u)
-        {
-            int pick = -1; double bestArea = -1.0;
-            for (uint32_t k = 0; k < num; ++k) if (!isLeaf(list[k]) && area(list[k]) > bestArea) { bestArea = area(list[k]); pick = (int)k; }
-            if (pick < 0) break;
-            const uint32_t c = nodes[list[pick]].childIndex;
-            list[pick] = c; list[num++] = c + 1u;
-        }
-        for (uint32_t k = 0; k < 4u; ++k)
-        {
-            const uint32_t child = k < num ? list[k] : 0xFFFFFFFFu;
-            children.push_back(child);
-            if (child != 0xFFFFFFFFu && !isLeaf(child))
-            {
-                if (order.size() >= RT_NODE_CHILD_MASK) return w;
-                wideOf[child] = (uint32_t)order.size(); order.push_back(child);
-            }
-        }
-    }
-    w.nodes.resize(order.size() * 4u);
-    for (size_t i = 0; i < order.size(); ++i)
-        for (uint32_t k = 0; k < 4u; ++k)
-        {
-            const uint32_t child = children[i * 4u + k];
-            float4 rec = make_float4(0.0f, 0.0f, 0.0f, __builtin_bit_cast(float, (uint32_t)RT_WIDE_EMPTY));   // a point at the grid's corner, outside the mesh's bounds
-            if (child != 0xFFFFFFFFu)
-            {
-                rec = q.pairs[child];   // the child's box on the grid; its packed reference is replaced for interior children
-                if (!isLeaf(child)) rec.w = __builtin_bit_cast(float, wideOf[child]);
-            }
-            w.nodes[i * 4u + k] = rec;
-        }
-    w.ok = true;
-    return w;
-}
-#endif   // RT_HOST_BUILDERS

@@ -1,7 +1,8 @@
 // rt_trace_wide2.inl -- the 4-wide walk for TWO-LEVEL scenes (Scene::Traverse over the top-level BVH of the objects, Scene.cpp:219-261, into
 // MeshShape::Traverse for mesh objects, Traverse_Object / Traverse_Object_Shadow for analytic shapes and light objects): a 4-wide collapse
-// of the reference's top-level tree over 4-wide collapses of its mesh trees.  Included by rt_trace.hip (kernels: RT_DEVICE_KERNELS) and rt_runtime.hip (tree builders: RT_HOST_BUILDERS) after rt_trace_wide.inl, whose node
-// format and exactness argument it shares (their device parts: rt_wide_walk.h); what is new here is only the second level.
+// of the reference's top-level tree over 4-wide collapses of its mesh trees.  Device only; included by rt_trace.hip after rt_trace_wide.inl, whose node
+// format and exactness argument it shares (their device parts: rt_wide_walk.h); what is new here is only the second level.  WideLevel and WideScene are
+// rt_wide_format.h; the host assembles the levels in rt_scene_prepare.h (buildWideLevel, buildTwoLevel).
 //
 // Why.  Round 2's k_trace_wide serves scenes with ONE mesh object; the Cornell box (ten analytic instances), a Sponza with props, every
 // scene with an area light fell back to the binary walk of k_trace.
@@ -21,24 +22,6 @@
 // direction component at either level, origins far outside a grid, and rays whose stack would overflow.  Any-hit rays: an OR over the
 // same candidates with the reference's per-object conditions against the fixed ray length.
 
-struct WideLevel   // 64 bytes
-{
-    uint32_t nodeBase;    // first node of the level in WideScene::nodes, in nodes (a node = four float4)
-    uint32_t gateBase;    // the exact box of the leaf whose first primitive is p: gate[gateBase + 2 p] (min), gate[gateBase + 2 p + 1] (max)
-    uint32_t triBase;     // mesh levels: the mesh's first triangle in RtSceneDesc::triangles
-    uint32_t valid;       // 0: an object without a tree (an empty mesh)
-    float base[3], step[3], bound[3];
-    uint32_t pad[3];
-};
-struct WideScene
-{
-    const float4* nodes;
-    const float4* gate;
-    const WideLevel* levels;   // [numObjects] mesh objects (valid only for those), [numObjects] = the top level
-    uint32_t numObjects;       // >= 2 (one-object scenes are Scene::Traverse's bypass: no top-level tree; k_trace_wide or k_trace serve them)
-};
-
-#ifdef RT_DEVICE_KERNELS
 #define RT_WIDE2_WORLD_WORDS 6u   // per lane in LDS: the world ray's invDir and (stale) originDivDir
 #define RT_WIDE2_LOCAL_EXACT 64u
 
@@ -313,58 +296,3 @@ __global__ void __launch_bounds__(RT_BLOCK) __attribute__((amdgpu_waves_per_eu(k
                                               (uint32_t)RT_BLOCK / 64u);
     }
 }
-
-#endif   // RT_DEVICE_KERNELS
-
-#ifdef RT_HOST_BUILDERS
-// ---- host: the 4-wide trees of a two-level scene --------------------------------------------------------------------------------------
-struct WideLevelBuild
-{
-    std::vector<float4> nodes, gate;   // gate: 2 float4 per primitive index
-    float base[3], step[3], bound[3];
-    bool ok = false;
-};
-
-// One level (the top-level tree over the objects, or a mesh's tree over its triangles).  A tree whose root is a leaf (one or two
-// primitives: a quad, two objects) gets a single wide node with that leaf as its only child.
-static WideLevelBuild buildWideLevel(const RtNode* nodes, uint32_t numNodes, uint32_t numPrimitives, uint32_t depth)
-{
-    WideLevelBuild out;
-    if (numNodes == 0u || numPrimitives == 0u) return out;
-    const uint32_t rootLeaves = nodes[0].leaves & 0x3FFFFFFFu;
-    if (rootLeaves == 0u)
-    {
-        const QuantBuild q = buildQuantBvh(nodes, numNodes, numPrimitives, depth);
-        if (!q.ok) return out;
-        const WideBuild w = buildWideBvh(nodes, numNodes, q);
-        if (!w.ok) return out;
-        out.nodes = w.nodes; out.gate = q.gate;
-        memcpy(out.base, q.base, sizeof(q.base)); memcpy(out.step, q.step, sizeof(q.step)); memcpy(out.bound, q.bound, sizeof(q.bound));
-        out.ok = true;
-        return out;
-    }
-    if (rootLeaves > 2u || (uint64_t)nodes[0].childIndex + rootLeaves > numPrimitives) return out;
-    // the grid of buildQuantBvh over the root's box; the leaf's stored box a full step outside the exact one
-    const RtNode& root = nodes[0];
-    float largest = 0.0f;
-    for (int a = 0; a < 3; ++a) { if (!(root.min[a] <= root.max[a]) || !std::isfinite(root.min[a]) || !std::isfinite(root.max[a])) return out; largest = fmaxf(largest, root.max[a] - root.min[a]); }
-    uint32_t v[6];
-    for (int a = 0; a < 3; ++a)
-    {
-        out.step[a] = fmaxf(root.max[a] - root.min[a], 1e-6f * fmaxf(largest, 1e-30f)) / (RT_QUANT_GRID - 8.0f);
-        out.base[a] = root.min[a] - 4.0f * out.step[a];
-        out.bound[a] = fmaxf(fabsf(root.min[a]), fabsf(root.max[a])) + 8.0f * out.step[a];
-        if (!(out.step[a] > 0.0f) || !std::isfinite(out.step[a])) return out;
-        v[a] = 1u; v[3 + a] = 65534u;    // planes at base + step and base + 65534 step: more than a step outside [min, max] on both sides
-        if ((double)out.base[a] + (double)out.step[a] > (double)root.min[a] - (double)out.step[a] || (double)out.base[a] + 65534.0 * (double)out.step[a] < (double)root.max[a] + (double)out.step[a]) return out;
-    }
-    const uint32_t d0 = v[0] | (v[1] << 16), d1 = v[2] | (v[3] << 16), d2 = v[4] | (v[5] << 16);
-    out.nodes.assign(4u, make_float4(0.0f, 0.0f, 0.0f, __builtin_bit_cast(float, (uint32_t)RT_WIDE_EMPTY)));
-    out.nodes[0] = make_float4(__builtin_bit_cast(float, d0), __builtin_bit_cast(float, d1), __builtin_bit_cast(float, d2), __builtin_bit_cast(float, root.childIndex | (rootLeaves << RT_NODE_LEAVES_SHIFT)));
-    out.gate.assign((size_t)2 * numPrimitives, make_float4(0.0f, 0.0f, 0.0f, 0.0f));
-    out.gate[2u * (size_t)root.childIndex] = make_float4(root.min[0], root.min[1], root.min[2], 0.0f);
-    out.gate[2u * (size_t)root.childIndex + 1u] = make_float4(root.max[0], root.max[1], root.max[2], 0.0f);
-    out.ok = true;
-    return out;
-}
-#endif   // RT_HOST_BUILDERS

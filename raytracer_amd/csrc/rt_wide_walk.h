@@ -1,7 +1,7 @@
 // rt_wide_walk.h -- the device code the 4-wide walks share, each part once: k_trace_wide / k_tail (traceWideLoop, rt_trace_wide.inl), k_trace_wide2
 // (rt_trace_wide2.inl) and k_trace_packet (rt_trace_packet.inl): the node record's slab test, the hand-over lists, the request ray, the fold, the interior
-// step, the mesh leaf, the end of a ray and the tallies.  Included by rt_trace.hip and rt_tail.hip behind rt_wide_grid.inl (the grid, WideTuning and
-// the exactness argument these parts carry out) and before the walk files, which keep what is their own: the loops, the phase scheduling, the refill
+// step, the mesh leaf, the end of a ray and the tallies.  Included by rt_trace.hip and rt_tail.hip behind rt_wide_grid.inl (the exactness argument these
+// parts carry out; the grid, the records and WideTuning are rt_wide_format.h) and before the walk files, which keep what is their own: the loops, the phase scheduling, the refill
 // policy, the tolerance policy, the second level, the packet's uniform node.
 //
 // Form.  k_trace_wide and k_trace_wide2 sit on the 96-VGPR limit (five waves per SIMD, no scratch in the hot instantiation): a part is a force-inlined

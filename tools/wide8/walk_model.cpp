@@ -2,7 +2,7 @@
 //
 // Reads what tools/wide8/dump_walk_inputs.py wrote (the benchmark mesh's binary tree = the reference's BVH::Node array, its triangles in leaf order, a sample of
 // the rays a depth-8 PathTracerMIS pass traces) and walks every ray through
-//   W4   today's tree: 4-wide collapse (rt_trace_wide.inl buildWideBvh), boxes on the 16-bit grid, children visited in order of their entry distance (the
+//   W4   today's tree: 4-wide collapse (rt_scene_prepare.h buildWideBvh), boxes on the 16-bit grid, children visited in order of their entry distance (the
 //        kernel's five-exchange sort);
 //   W8   the 8-wide collapse of the same binary tree (same SAH splits, same leaves), in four flavours: planes on the 16-bit grid or as 8-bit offsets in the
 //        node's own frame (origin on the grid + one power-of-two scale per axis: the 64-byte node of DESIGN 8), children visited by entry distance (a full
@@ -102,7 +102,7 @@ static void optimiseTopology(int sweeps)
     gNodes = out;
 }
 
-// ---- the 16-bit grid of rt_wide_grid.inl (conservative, a step to spare) ----
+// ---- the 16-bit grid of rt_scene_prepare.h, wideGridOver (conservative, a step to spare) ----
 static float gBase[3], gStep[3];
 static void buildGrid()
 {
