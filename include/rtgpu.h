@@ -959,6 +959,61 @@ int rtgpu_temporal_accumulate_moving_async(RtgpuContext* ctx, const RtTemporalPa
                                            float* outA, float* outB, float* outLength, float* outMotion, const RtObjectMotion* objects, uint32_t numObjects,
                                            void* stream);
 
+/* ---------------------------------------------------------------------------------------------
+ * Clipping the history.  Reprojection follows a pixel's surface, not the light on it: when a shadow arrives, the history carries the sunlight on at what alphaMin
+ * allows.  The remedy of the image-space kind (TAA, ReLAX, ReBLUR): the reprojected history is clipped to the mean +- gamma standard deviations of THIS frame's
+ * colours over the pixel's own surface in a small window, and the further it had to be pulled, the shorter its history length becomes.  Where nothing clips the
+ * result is the bits of the call without.  Everything not restated here is rtgpu_temporal_accumulate_moving, and with objects == NULL and numObjects == 0
+ * rtgpu_temporal_accumulate; the rules of every operation are theirs: f32, every multiply and add rounded on its own, sums in the order written, correctly
+ * rounded / and sqrtf.  tests/temporal_clip_ref.py is the same text in NumPy float32.
+ *   moments    for a valid pixel p, over the window pixels q = (x + dx, y + dy), dy = -r .. r outer, dx = -r .. r inner, p itself included.  q counts iff it is
+ *              inside the frame, depth_q is finite, objectId_q == objectId_p (when the objectId plane is given),
+ *              (N_p.x * N_q.x + N_p.y * N_q.y) + N_p.z * N_q.z >= normalThreshold and, with dp = P_q - P_p,
+ *              fabsf((N_p.x * dp.x + N_p.y * dp.y) + N_p.z * dp.z) <= planeTolerance * depth_p -- this frame's guides and the pixel's own N and P, never the
+ *              moved pair.  Each counted q adds   cnt = cnt + 1;  s1_k = s1_k + c_q,k;  s2_k = s2_k + c_q,k * c_q,k   (c: the prepared colour, in history
+ *              space).  Then   mu_k = s1_k / cnt;  var_k = fmaxf(s2_k / cnt - mu_k * mu_k, 0);  g_k = gamma * sqrtf(var_k).
+ *   clip       where the pixel blends (ks > 0) and cnt >= minCount, behind hA = hA / ks, hB = hB / ks:
+ *                  lo_k = mu_k - g_k;  hi_k = mu_k + g_k;  hA'_k = fminf(fmaxf(hA_k, lo_k), hi_k);  hB'_k = hB_k + (hA'_k - hA_k)
+ *              B is shifted, not clipped: clipped into the same box A - B would be zero, and the variance-guided filter would take the pixel for converged
+ *              exactly where its history was just thrown away.  The shift keeps the accumulated variance estimate.
+ *   anti-lag   e = (fabsf(hA'_0 - hA_0) + fabsf(hA'_1 - hA_1)) + fabsf(hA'_2 - hA_2);  wd = (g_0 + g_1) + g_2;  f = e > 0 ? wd / (wd + e) : 1;
+ *                  n = fminf((ln / ks) * f + 1, maxHistory)
+ *              alpha and the blend as before, over hA' and hB'.  With e = 0 the factor is exactly 1 and (ln / ks) * 1 is ln / ks: a pixel that does not clip
+ *              carries the bits of the call without a clip.  A pixel with cnt < minCount, a pixel that starts and an invalid pixel are untouched, with f = 1.
+ *   outputs    those of the call without, and outConfidence, H x W f32, optional: f.
+ *   scope      the statistics are this frame's: a window that straddles a shadow edge is wide and lets a band of r pixels lag on; under heavy-tailed noise the
+ *              sample deviation underestimates, and a small gamma darkens a static image.  Neither is repaired ("History clipping", has their
+ *              size).  Non-finite colours remain the caller's business.
+ *   errors     as rtgpu_temporal_accumulate_moving -- but objects may be NULL with numObjects == 0: then no object moved --, and: clip NULL on the pure entries,
+ *              radius outside 1 .. 3, minCount outside 1 .. 49, gamma not finite or outside [0, 1e6]: RTGPU_ERR_INVALID_ARGUMENT; the _async entry holds
+ *              outConfidence to the alignment and overlap rules of the other outputs.
+ * rtgpu_denoise_temporal_clip is rtgpu_denoise_temporal with the clip: by definition the composition of the pure entries, the motion table built after an update
+ * as that call builds it.  clip == NULL: rtgpu_denoise_temporal itself, word for word and launch for launch (outConfidence is then not written).  outConfidence:
+ * memory of outRGB's kind.  The moments are 32 bytes per pixel of scratch of the clipped calls' own, grown on use and freed with the context.
+ * --------------------------------------------------------------------------------------------- */
+typedef struct RtTemporalClip {   /* 16 bytes */
+    uint32_t radius;     /* window (2r+1)^2 around the pixel in THIS frame; 1, 2 or 3 */
+    float    gamma;      /* half-width of the box in standard deviations; finite, [0, 1e6] */
+    uint32_t minCount;   /* clip only where at least this many window pixels lie on the pixel's surface; 1 .. 49 */
+    uint32_t _pad;
+} RtTemporalClip;
+int rtgpu_temporal_accumulate_clip(RtgpuContext* ctx, const RtTemporalParams* params, uint32_t width, uint32_t height, const float* color,
+                                   const float* colorHalf, const float* depth, const float* normal, const float* position, const float* albedo,
+                                   const uint32_t* objectId, const float* prevA, const float* prevB, const float* prevLength, const float* prevDepth,
+                                   const float* prevNormal, const float* prevPosition, const uint32_t* prevObjectId, float* outA, float* outB,
+                                   float* outLength, float* outMotion, const RtObjectMotion* objects, uint32_t numObjects, const RtTemporalClip* clip,
+                                   float* outConfidence);
+int rtgpu_temporal_accumulate_clip_async(RtgpuContext* ctx, const RtTemporalParams* params, uint32_t width, uint32_t height, const float* color,
+                                         const float* colorHalf, const float* depth, const float* normal, const float* position, const float* albedo,
+                                         const uint32_t* objectId, const float* prevA, const float* prevB, const float* prevLength,
+                                         const float* prevDepth, const float* prevNormal, const float* prevPosition, const uint32_t* prevObjectId,
+                                         float* outA, float* outB, float* outLength, float* outMotion, const RtObjectMotion* objects, uint32_t numObjects,
+                                         const RtTemporalClip* clip, float* outConfidence, void* stream);
+int rtgpu_denoise_temporal_clip(RtgpuContext* ctx, const RtTemporalParams* params, const RtDenoiseVarParams* filter, const RtPassParams* guideParams,
+                                float* outRGB, float* outVariance, const RtTemporalClip* clip, float* outConfidence);
+int rtgpu_denoise_temporal_clip_async(RtgpuContext* ctx, const RtTemporalParams* params, const RtDenoiseVarParams* filter, const RtPassParams* guideParams,
+                                      float* outRGB, float* outVariance, const RtTemporalClip* clip, float* outConfidence, void* stream);
+
 /* rtgpu_postprocess over a caller's image (host memory, height x width x 3 floats of the context's size) in place of the sum buffer -- a
  * denoised frame, say: the same kernels, the same restrictions, and the same bits for the same input. */
 int rtgpu_postprocess_from(RtgpuContext* ctx, const RtPostprocessParams* params, const float* rgbHost, uint32_t* frontBufferBGRA);

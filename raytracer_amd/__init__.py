@@ -453,9 +453,34 @@ def object_motion_table(object_motion):
     return table
 
 
+class RtTemporalClip(C.Structure):
+    _fields_ = [("radius", C.c_uint32), ("gamma", C.c_float), ("minCount", C.c_uint32), ("_pad", C.c_uint32)]
+
+
+# history clipping (include/rtgpu.h, "Clipping the history"): the widest window, a box of one standard deviation ("History clipping", says how it
+# was chosen), and a pixel clips only where a 3 x 3 patch's worth of its window lies on its own surface
+TEMPORAL_CLIP_DEFAULTS = dict(radius=3, gamma=1.0, min_count=9)
+
+
+def temporal_clip(clip):
+    """The RtTemporalClip of a wrapper's `clip` argument: None (no clip: None comes back), True (TEMPORAL_CLIP_DEFAULTS) or a dict with any of radius, gamma and
+    min_count, the rest at their defaults.  The library checks the ranges."""
+    if clip is None or clip is False:
+        return None
+    chosen = dict(TEMPORAL_CLIP_DEFAULTS)
+    if clip is not True:
+        if not isinstance(clip, dict) or set(clip) - set(chosen):
+            raise ValueError("clip must be None, True or a dict with keys among radius, gamma, min_count")
+        chosen.update(clip)
+    c = RtTemporalClip()
+    c.radius, c.gamma, c.minCount = int(chosen["radius"]), float(chosen["gamma"]), int(chosen["min_count"])
+    return c
+
+
 def temporal_accumulate(color, color_half, depth, normal, position, albedo=None, object_id=None, history=None, prev_world_to_screen=None, prev_sample_offset=(0.0, 0.0),
                         alpha_min=TEMPORAL_DEFAULTS["alpha_min"], max_history=TEMPORAL_DEFAULTS["max_history"], normal_threshold=TEMPORAL_DEFAULTS["normal_threshold"],
-                        plane_tolerance=TEMPORAL_DEFAULTS["plane_tolerance"], color_scale=1.0, demodulate=True, return_motion=False, ctx=None, object_motion=None):
+                        plane_tolerance=TEMPORAL_DEFAULTS["plane_tolerance"], color_scale=1.0, demodulate=True, return_motion=False, ctx=None, object_motion=None,
+                        clip=None, return_confidence=False):
     """Temporal accumulation of include/rtgpu.h over a frame: color, color_half (H, W, 3) -- Viewport.sum_buffer(secondary=True) --, depth (H, W) or (1, H, W),
     normal, position, albedo (3, H, W) float32 and object_id (H, W) or (1, H, W) uint32 (optional) -- Viewport.render_aovs() --, as NumPy arrays or as
     contiguous torch tensors on a ROCm device (object_id: the int64 tensor render_aovs(device=True) returns, or int32 words), then on
@@ -466,7 +491,13 @@ def temporal_accumulate(color, color_half, depth, normal, position, albedo=None,
     return_motion=True: (history, the (2, H, W) motion plane).  albedo is needed with demodulate=True only; the object test needs the ids of both frames.
     object_motion=(matrices (n, 4, 4), prev_ids (n,), moved (n,)): the objects moved between the two frames (rtgpu_temporal_accumulate_moving) -- per current
     object id the matrix that takes a world position to where that surface point was in the previous frame, the id the object had there, and whether it
-    moved at all; NumPy arrays whichever way the frame comes.  Both id planes are required with it."""
+    moved at all; NumPy arrays whichever way the frame comes.  Both id planes are required with it.
+    clip=True or a dict (temporal_clip): the reprojected history is clipped to this frame's local colour statistics and its length cut by how far it was pulled
+    (rtgpu_temporal_accumulate_clip), with or without object_motion; return_confidence=True then appends the (H, W) confidence plane -- 1 where nothing clipped
+    -- to what is returned."""
+    clip = temporal_clip(clip)
+    if return_confidence and clip is None:
+        raise ValueError("return_confidence=True needs clip")
     table = None
     if object_motion is not None:
         table = object_motion_table(object_motion)
@@ -502,16 +533,21 @@ def temporal_accumulate(color, color_half, depth, normal, position, albedo=None,
     out = dict(a=empty((h, w, 3)), b=empty((h, w, 3)), length=empty((h, w)))
     motion = empty((2, h, w)) if return_motion else None
     args = [C.byref(p), C.c_uint32(w), C.c_uint32(h)] + [ptr(name) for name in shapes] + [ptr(out["a"]), ptr(out["b"]), ptr(out["length"]), ptr(motion)]
-    tensors = list(planes.values()) + list(out.values()) + [motion]
-    if table is None:
+    confidence = empty((h, w)) if return_confidence else None
+    tensors = list(planes.values()) + list(out.values()) + [motion, confidence]
+    if table is not None and torch is not None:
+        with torch.cuda.device(index):
+            table = torch.from_numpy(table.view(np.int32)).to(color.device)   # (ordered on the current stream, which the side stream waits for)
+    moving = [ptr(table), C.c_uint32(0 if table is None else table.shape[0])]
+    if clip is not None:
+        _image_call(torch, index, "temporal_accumulate", ctx, "rtgpu_temporal_accumulate_clip", args + moving + [C.byref(clip), ptr(confidence)], tensors + [table])
+    elif table is None:
         _image_call(torch, index, "temporal_accumulate", ctx, "rtgpu_temporal_accumulate", args, tensors)
     else:
-        if torch is not None:
-            with torch.cuda.device(index):
-                table = torch.from_numpy(table.view(np.int32)).to(color.device)   # (ordered on the current stream, which the side stream waits for)
-        _image_call(torch, index, "temporal_accumulate", ctx, "rtgpu_temporal_accumulate_moving", args + [ptr(table), C.c_uint32(table.shape[0])], tensors + [table])
+        _image_call(torch, index, "temporal_accumulate", ctx, "rtgpu_temporal_accumulate_moving", args + moving, tensors + [table])
     out.update(depth=planes["depth"], normal=planes["normal"], position=planes["position"], object_id=planes.get("object_id"))
-    return (out, motion) if return_motion else out
+    extras = ((motion,) if return_motion else ()) + ((confidence,) if return_confidence else ())
+    return (out,) + extras if extras else out
 
 
 BSDF_NAMES = ("null", "diffuse", "roughDiffuse", "dielectric", "roughDielectric", "metal", "roughMetal", "plastic", "roughPlastic")
@@ -1107,7 +1143,7 @@ class Viewport:
                 sigma_plane=DENOISE_DEFAULTS["sigma_plane"], color_scale=None, demodulate=True, device=False, variance=False,
                 sigma_lum=DENOISE_VAR_DEFAULTS["sigma_lum"], variance_floor=DENOISE_VAR_DEFAULTS["variance_floor"], return_variance=False, temporal=False,
                 alpha_min=TEMPORAL_DEFAULTS["alpha_min"], max_history=TEMPORAL_DEFAULTS["max_history"], normal_threshold=TEMPORAL_DEFAULTS["normal_threshold"],
-                plane_tolerance=TEMPORAL_DEFAULTS["plane_tolerance"]):
+                plane_tolerance=TEMPORAL_DEFAULTS["plane_tolerance"], clip=None, return_confidence=False):
         """The frame rendered so far through the a-trous filter of include/rtgpu.h, guided by the depth, normal, position and base-colour planes of the pass
         `params` (an RtPassParams from next_pass_params(), as render_aovs takes it): the (H, W, 3) float32 image, sum_buffer() * color_scale filtered.
         color_scale defaults to 1 / max(1, passes_finished).  device=True: a torch tensor on the renderer's ROCm device, produced on
@@ -1119,7 +1155,15 @@ class Viewport:
         variance=True then filters the accumulated pair, variance=False returns the accumulated frame unfiltered.  reset() keeps the history (a moving
         camera resets the film every frame); reset_history(), a resize and a new scene drop it.  The reprojection reads params.camera.worldToScreen, which
         Camera.set_perspective computes from the transform of the moment (as the reference's Camera does): after Camera.set_transform call set_perspective again,
-        or the history is looked up through the camera's old place."""
+        or the history is looked up through the camera's old place.
+        clip=True or a dict (temporal_clip), with temporal=True: the history is clipped to this frame's local colour statistics (rtgpu_denoise_temporal_clip) --
+        the remedy for lighting that changed under a surface; clip=None is the call without, word for word.  return_confidence=True then appends the (H, W)
+        confidence plane to what is returned."""
+        clip = temporal_clip(clip)
+        if clip is not None and not temporal:
+            raise ValueError("clip needs temporal=True")
+        if return_confidence and clip is None:
+            raise ValueError("return_confidence=True needs clip")
         if return_variance and not variance:
             raise ValueError("return_variance=True needs variance=True")
         if not isinstance(params, RtPassParams):
@@ -1151,15 +1195,19 @@ class Viewport:
             empty = lambda *shape: torch.empty(shape, dtype=torch.float32, device=dev)   # noqa: E731
             ptr = lambda a: C.c_void_p(a.data_ptr()) if a is not None else None   # noqa: E731
         out, out_variance = empty(self.height, self.width, 3), empty(self.height, self.width) if return_variance else None
+        out_confidence = empty(self.height, self.width) if return_confidence else None
         args = (ctx,) + leading + (C.byref(params), ptr(out)) + ((ptr(out_variance),) if temporal or variance else ())
+        if clip is not None:
+            entry, args = "rtgpu_denoise_temporal_clip", args + (C.byref(clip), ptr(out_confidence))
         if not device:
             r = getattr(lib, entry)(*args)
         else:
-            r = _run_on_torch_stream(torch, self._denoise_streams, dev, [out, out_variance], lambda stream: getattr(lib, entry + "_async")(*(args + (stream,))))
+            r = _run_on_torch_stream(torch, self._denoise_streams, dev, [out, out_variance, out_confidence], lambda stream: getattr(lib, entry + "_async")(*(args + (stream,))))
         if r != 0:
             err = (lib.rtgpu_last_error() or b"").decode()
             raise (ValueError if r == -1 else RuntimeError)("denoise failed (%d): %s" % (r, err))
-        return (out, out_variance) if return_variance else out
+        extras = ((out_variance,) if return_variance else ()) + ((out_confidence,) if return_confidence else ())
+        return (out,) + extras if extras else out
 
     def reset_history(self):
         """Drops the history of denoise(temporal=True) (rtgpu_temporal_reset): the next such call starts every pixel."""

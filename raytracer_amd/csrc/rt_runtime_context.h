@@ -327,6 +327,8 @@ struct RtgpuContext
         struct Then { uint32_t id; float transform[16]; };
         std::vector<Then> then; bool movedSince = false;
         RtObjectMotion* motion = nullptr; size_t motionCapacity = 0;
+        // history clipping: two planes of `momentsCapacity` 16-byte records, {mu.rgb, cnt} and {g.rgb, 0} (32 bytes per pixel), of the clipped calls, pure or not
+        float4* moments = nullptr; size_t momentsCapacity = 0;
     } temporal;
 
     // timing
@@ -471,8 +473,8 @@ static void freeDenoise(RtgpuContext* c)
 {
     RtgpuContext::Denoise& d = c->denoise;
     if (d.done) (void)hipEventSynchronize(d.done);
-    devFree(d.records, d.io, c->temporal.records, c->temporal.motion);
-    d.capacity = 0; d.ioFloats = 0; c->temporal.capacity = 0; c->temporal.have = false; c->temporal.motionCapacity = 0;
+    devFree(d.records, d.io, c->temporal.records, c->temporal.motion, c->temporal.moments);
+    d.capacity = 0; d.ioFloats = 0; c->temporal.capacity = 0; c->temporal.have = false; c->temporal.motionCapacity = 0; c->temporal.momentsCapacity = 0;
     if (d.done) (void)hipEventDestroy(d.done);
     if (d.sumRead) (void)hipEventDestroy(d.sumRead);
     d.done = nullptr; d.sumRead = nullptr; d.sumReadPending = false;

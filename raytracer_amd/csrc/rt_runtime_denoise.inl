@@ -54,7 +54,7 @@ template <class T> static int ensureScratch(RtgpuContext* c, T*& buffer, size_t&
 struct Plane { const void* ptr; uint32_t floatsPerPixel; bool output; };
 struct PlaneTable
 {
-    Plane planes[18]; uint32_t count;
+    Plane planes[19]; uint32_t count;
     bool has(uint32_t k) const { return planes[k].ptr != nullptr; }
     const float* in(uint32_t k) const { return (const float*)planes[k].ptr; }
     const uint32_t* ids(uint32_t k) const { return (const uint32_t*)planes[k].ptr; }
@@ -232,12 +232,13 @@ struct FrameStep
 
 // The checks of a frame call behind those of its parameter blocks; then every queued pass is in the sum buffer, `stream` stands behind the previous call, and the first
 // `guides` of depth, normal, position, base colour and object id are rendered on it: the first hits of the primary rays `guideParams` generates, through the AOV path
-// (its arena, never a lane's).  outHost or outDevice; outVariance (optional) is memory of the same kind, written with writesVariance only
+// (its arena, never a lane's).  outHost or outDevice; outVariance (optional) is memory of the same kind, written with writesVariance only; outPlane (optional, beside
+// outDevice only): one more device output of a float per pixel, held to the same rules
 static int beginFrame(RtgpuContext* c, const RtPassParams* guideParams, float* outHost, float* outDevice, float* outVariance, bool writesVariance, void* streamHandle,
-                      uint32_t guides, uint32_t extraFloatsPerPixel, FrameStep& f)
+                      uint32_t guides, uint32_t extraFloatsPerPixel, FrameStep& f, float* outPlane = nullptr)
 {
     if (!guideParams || (!outHost && !outDevice)) return fail(RTGPU_ERR_INVALID_ARGUMENT, "NULL argument");
-    if (outDevice && (((uintptr_t)outDevice | (uintptr_t)outVariance) & 15u)) return fail(RTGPU_ERR_INVALID_ARGUMENT, "the output must be a 16-byte aligned device buffer");
+    if (outDevice && (((uintptr_t)outDevice | (uintptr_t)outVariance | (uintptr_t)outPlane) & 15u)) return fail(RTGPU_ERR_INVALID_ARGUMENT, "the output must be a 16-byte aligned device buffer");
     if (!writesVariance) outVariance = nullptr;
     if (!c->sceneReady) return fail(RTGPU_ERR_NOT_READY, "rtgpu_upload_scene has not been called");
     if (!c->sum) return fail(RTGPU_ERR_NOT_READY, "rtgpu_resize has not been called");
@@ -248,6 +249,12 @@ static int beginFrame(RtgpuContext* c, const RtPassParams* guideParams, float* o
     {
         const uintptr_t a = (uintptr_t)outDevice, b = (uintptr_t)outVariance;
         if (a < b + n * sizeof(float) && b < a + 3u * n * sizeof(float)) return fail(RTGPU_ERR_INVALID_ARGUMENT, "outVariance overlaps outRGB");
+    }
+    if (outDevice && outPlane)
+    {
+        const uintptr_t a = (uintptr_t)outDevice, b = (uintptr_t)outVariance, p = (uintptr_t)outPlane;
+        if ((p < a + 3u * n * sizeof(float) && a < p + n * sizeof(float)) || (b && p < b + n * sizeof(float) && b < p + n * sizeof(float)))
+            return fail(RTGPU_ERR_INVALID_ARGUMENT, "an output overlaps another output");
     }
     // every queued pass is in the sum buffer, and a multi-device context's tiles are gathered on the first device, as for rtgpu_read_sum
     r = rtgpu_synchronize(c); if (r) return r;

@@ -1,7 +1,7 @@
 // rt_runtime_temporal.inl -- temporal accumulation, host side.  Included by rt_runtime.hip behind rt_runtime_denoise.inl.
 
 // ---- temporal accumulation (include/rtgpu.h, rtgpu_temporal_accumulate / rtgpu_denoise_temporal; kernels: k_temporal_pack and k_temporal, rt_temporal.inl) ------
-// One call is one k_temporal launch on the call's stream.  The previous frame reaches it as four planes of 16-byte records: the context-level call keeps two sets
+// One call is one k_temporal launch on the call's stream (a clipped call with a history: k_temporal_moments in front of it).  The previous frame reaches it as four planes of 16-byte records: the context-level call keeps two sets
 // of them (the previous frame's and the one being written, 128 bytes per pixel, RtgpuContext::Temporal), the pure entries pack the caller's planes into the
 // a-trous filter's record scratch first (k_temporal_pack).  The calls share the filter's events: `done` orders them behind each other and behind the filter
 // calls whatever their streams, `sumRead` stands behind the read of the sum buffers.
@@ -22,6 +22,15 @@ static int checkTemporalParams(const RtTemporalParams* t, bool withCamera)
     return RTGPU_OK;
 }
 
+// RtTemporalClip (history clipping): every field inside its stated range
+static int checkTemporalClip(const RtTemporalClip* clip)
+{
+    if (clip->radius < 1u || clip->radius > 3u) return fail(RTGPU_ERR_INVALID_ARGUMENT, "clip radius must be 1, 2 or 3");
+    if (!(clip->gamma >= 0.0f && clip->gamma <= 1e6f)) return fail(RTGPU_ERR_INVALID_ARGUMENT, "clip gamma must be finite and in [0, 1e6]");
+    if (clip->minCount < 1u || clip->minCount > 49u) return fail(RTGPU_ERR_INVALID_ARGUMENT, "clip minCount must be 1..49");
+    return RTGPU_OK;
+}
+
 static TemporalFrame temporalFrame(const RtTemporalParams* t, const float* worldToScreen, const float* sampleOffset, bool useIds)
 {
     TemporalFrame f;
@@ -32,17 +41,57 @@ static TemporalFrame temporalFrame(const RtTemporalParams* t, const float* world
     return f;
 }
 
-// motion: the device copy of an RtObjectMotion table (objects moved between the two frames: k_temporal<true>), or NULL: the static kernel, launched as ever
+// history clipping of one launch: the clip, two planes of `capacity` moment records for k_temporal_moments to fill, and the confidence plane (may be NULL)
+struct TemporalClipLaunch { const RtTemporalClip* clip; float4* moments; size_t capacity; float* confidence; };
+
+// motion: the device copy of an RtObjectMotion table (objects moved between the two frames: k_temporal<true>), or NULL: the static kernel, launched as ever.
+// clipped (or NULL): k_temporal_moments over this frame's planes first -- only with a history: without one nothing blends, and nothing is there to clip --, then
+// the clipping variant of either kernel
 static void launchTemporalKernel(const TemporalIn& in, const TemporalOut& out, uint32_t width, uint32_t height, const TemporalFrame& frame, hipStream_t stream,
-                                 const RtObjectMotion* motion = nullptr, uint32_t numObjects = 0u)
+                                 const RtObjectMotion* motion = nullptr, uint32_t numObjects = 0u, const TemporalClipLaunch* clipped = nullptr)
 {
     const dim3 block(RT_DENOISE_BLOCK_X, RT_DENOISE_BLOCK_Y), grid(((width + RT_DENOISE_BLOCK_X - 1u) / RT_DENOISE_BLOCK_X) * ((height + RT_DENOISE_BLOCK_Y - 1u) / RT_DENOISE_BLOCK_Y));
-    if (!motion) { hipLaunchKernelGGL(k_temporal<false>, grid, block, 0, stream, in, out, width, height, frame); return; }
+    if (!motion && !clipped) { hipLaunchKernelGGL(k_temporal<false>, grid, block, 0, stream, in, out, width, height, frame); return; }
     static_assert(sizeof(RtObjectMotion) == 5u * sizeof(float4), "k_temporal<true> reads a motion record as five float4");
     TemporalFrameMoving moving;
     static_cast<TemporalFrame&>(moving) = frame;
     moving.objects = reinterpret_cast<const float4*>(motion); moving.numObjects = numObjects;
-    hipLaunchKernelGGL(k_temporal<true>, grid, block, 0, stream, in, out, width, height, moving);
+    if (!clipped) { hipLaunchKernelGGL(k_temporal<true>, grid, block, 0, stream, in, out, width, height, moving); return; }
+    float4* const mu = clipped->moments; float4* const g = mu + clipped->capacity;
+    if (in.recA)
+    {
+        const dim3 tile(RT_DENOISE_TILE_X, RT_DENOISE_TILE_Y), tiles(((width + RT_DENOISE_TILE_X - 1u) / RT_DENOISE_TILE_X) * ((height + RT_DENOISE_TILE_Y - 1u) / RT_DENOISE_TILE_Y));
+        const TemporalMomentsFrame moments = { frame.colorScale, frame.normalThreshold, frame.planeTolerance, clipped->clip->gamma };
+        typedef void (*MomentsKernel) RT_K_TEMPORAL_MOMENTS_ARGS;
+        static const MomentsKernel kernels[3] = { k_temporal_moments<1>, k_temporal_moments<2>, k_temporal_moments<3> };
+        hipLaunchKernelGGL(kernels[clipped->clip->radius - 1u], tiles, tile, 0, stream, in, width, height, moments, mu, g);
+    }
+    if (!motion)
+    {
+        TemporalFrameClip<TemporalFrame> f;
+        static_cast<TemporalFrame&>(f) = frame;
+        f.momentMu = mu; f.momentG = g; f.confidence = clipped->confidence; f.minCount = (float)clipped->clip->minCount;
+        hipLaunchKernelGGL((k_temporal<false, true>), grid, block, 0, stream, in, out, width, height, f);
+    }
+    else
+    {
+        TemporalFrameClip<TemporalFrameMoving> f;
+        static_cast<TemporalFrameMoving&>(f) = moving;
+        f.momentMu = mu; f.momentG = g; f.confidence = clipped->confidence; f.minCount = (float)clipped->clip->minCount;
+        hipLaunchKernelGGL((k_temporal<true, true>), grid, block, 0, stream, in, out, width, height, f);
+    }
+}
+
+// the moment records of a clipped call over `pixels` pixels: scratch of the clipped calls' own, ordered like the rest by denoise.done.  Without a history no
+// moments are taken and none are read: nothing is allocated
+static int temporalClipLaunch(RtgpuContext* c, const RtTemporalClip* clip, size_t pixels, bool history, float* confidence, TemporalClipLaunch& launch)
+{
+    RtgpuContext::Temporal& h = c->temporal;
+    launch = { clip, nullptr, 0u, confidence };
+    if (!history) return RTGPU_OK;
+    int r = ensureScratch(c, h.moments, h.momentsCapacity, pixels, 2u); if (r) return r;
+    launch.moments = h.moments; launch.capacity = h.momentsCapacity;
+    return RTGPU_OK;
 }
 
 // The motion table of rtgpu_denoise_temporal (include/rtgpu.h): then[o] = the id and transform current object o had when the history was stored.  Doubles, each dot
@@ -69,14 +118,14 @@ static void buildMotionTable(const std::vector<RtObject>& now, const std::vector
 
 // the planes of the pure entries, in the order of their arguments
 enum { T_COLOR, T_HALF, T_DEPTH, T_NORMAL, T_POSITION, T_ALBEDO, T_ID, T_PREV_A, T_PREV_B, T_PREV_LENGTH, T_PREV_DEPTH, T_PREV_NORMAL, T_PREV_POSITION, T_PREV_ID,
-       T_OUT_A, T_OUT_B, T_OUT_LENGTH, T_OUT_MOTION };
+       T_OUT_A, T_OUT_B, T_OUT_LENGTH, T_OUT_MOTION, T_OUT_CONFIDENCE };
 static PlaneTable temporalPlanes(const float* color, const float* colorHalf, const float* depth, const float* normal, const float* position, const float* albedo, const uint32_t* objectId,
                                  const float* prevA, const float* prevB, const float* prevLength, const float* prevDepth, const float* prevNormal, const float* prevPosition,
-                                 const uint32_t* prevObjectId, float* outA, float* outB, float* outLength, float* outMotion)
+                                 const uint32_t* prevObjectId, float* outA, float* outB, float* outLength, float* outMotion, float* outConfidence = nullptr)
 {
     return { { { color, 3u, false }, { colorHalf, 3u, false }, { depth, 1u, false }, { normal, 3u, false }, { position, 3u, false }, { albedo, 3u, false }, { objectId, 1u, false },
                { prevA, 3u, false }, { prevB, 3u, false }, { prevLength, 1u, false }, { prevDepth, 1u, false }, { prevNormal, 3u, false }, { prevPosition, 3u, false },
-               { prevObjectId, 1u, false }, { outA, 3u, true }, { outB, 3u, true }, { outLength, 1u, true }, { outMotion, 2u, true } }, 18u };
+               { prevObjectId, 1u, false }, { outA, 3u, true }, { outB, 3u, true }, { outLength, 1u, true }, { outMotion, 2u, true }, { outConfidence, 1u, true } }, 19u };
 }
 
 // the motion table of the _moving entries (NULL, 0: the entries without)
@@ -102,11 +151,14 @@ static int checkTemporal(RtgpuContext* c, const RtTemporalParams* t, uint32_t wi
 }
 
 // the launches of a pure call on `stream`; every plane is device memory
-static int launchTemporal(RtgpuContext* c, const RtTemporalParams* t, uint32_t width, uint32_t height, const PlaneTable& b, bool history, hipStream_t stream, const TemporalMotion& motion)
+static int launchTemporal(RtgpuContext* c, const RtTemporalParams* t, uint32_t width, uint32_t height, const PlaneTable& b, bool history, hipStream_t stream, const TemporalMotion& motion,
+                          const RtTemporalClip* clip)
 {
     RtgpuContext::Denoise& d = c->denoise;
     const size_t pixels = (size_t)width * height;
     int r = ensureScratch(c, d.records, d.capacity, history ? pixels : 0u, 4u); if (r) return r;   // (the filter's record scratch, and the event every call is ordered by)
+    TemporalClipLaunch clipped;
+    if (clip) { r = temporalClipLaunch(c, clip, pixels, history, b.out(T_OUT_CONFIDENCE), clipped); if (r) return r; }
     HIP_TRY(hipStreamWaitEvent(stream, d.done, 0));
     TemporalIn in = { b.in(T_COLOR), b.in(T_HALF), b.in(T_DEPTH), b.in(T_NORMAL), b.in(T_POSITION), b.in(T_ALBEDO), b.ids(T_ID), nullptr, nullptr, nullptr, nullptr };
     if (history)
@@ -118,15 +170,22 @@ static int launchTemporal(RtgpuContext* c, const RtTemporalParams* t, uint32_t w
     }
     const TemporalOut out = { b.out(T_OUT_A), b.out(T_OUT_B), b.out(T_OUT_LENGTH), b.out(T_OUT_MOTION), nullptr, nullptr, nullptr, nullptr, nullptr };
     launchTemporalKernel(in, out, width, height, temporalFrame(t, t->prevWorldToScreen, t->prevSampleOffset, history && b.has(T_ID) && b.has(T_PREV_ID)), stream,
-                         history && motion.given ? motion.objects : nullptr, motion.numObjects);   // (without history every pixel starts: the table has nothing to say)
+                         history && motion.given ? motion.objects : nullptr, motion.numObjects, clip ? &clipped : nullptr);   // (without history every pixel starts: the table has nothing to say)
     return recordDone(c, stream);
 }
 
 // the pure entries over planes (and a motion table) in device memory (onDevice), or in host memory: then staged, the table behind the planes
-static int temporalAccumulate(RtgpuContext* c, const RtTemporalParams* t, uint32_t width, uint32_t height, PlaneTable b, TemporalMotion motion, bool onDevice, void* streamHandle)
+// (clipped: the _clip entries, which need `clip`)
+static int temporalAccumulate(RtgpuContext* c, const RtTemporalParams* t, uint32_t width, uint32_t height, PlaneTable b, TemporalMotion motion, bool onDevice, void* streamHandle,
+                              bool clipped = false, const RtTemporalClip* clip = nullptr)
 {
     bool history = false;
     int r = checkTemporal(c, t, width, height, b, history, motion); if (r) return r;
+    if (clipped)
+    {
+        if (!clip) return fail(RTGPU_ERR_INVALID_ARGUMENT, "NULL clip");
+        r = checkTemporalClip(clip); if (r) return r;
+    }
     const size_t n = (size_t)width * height;
     if (onDevice && motion.given && ((uintptr_t)motion.objects & 15u)) return fail(RTGPU_ERR_INVALID_ARGUMENT, "the motion table must be 16-byte aligned device memory");
     if (onDevice) { r = checkDevicePlanes(b, n); if (r) return r; }
@@ -136,7 +195,7 @@ static int temporalAccumulate(RtgpuContext* c, const RtTemporalParams* t, uint32
     const void* table = motion.objects;
     if (!onDevice) { r = stagePlanes(c, b, n, device, &table, motion.given ? motion.numObjects * sizeof(RtObjectMotion) : 0u); if (r) return r; }
     motion.objects = (const RtObjectMotion*)table;
-    r = launchTemporal(c, t, width, height, device, history, stream, motion);
+    r = launchTemporal(c, t, width, height, device, history, stream, motion, clip);
     if (r || onDevice) return r;
     HIP_TRY(hipStreamSynchronize(stream));
     return copyPlanesBack(b, device, n);
@@ -179,6 +238,31 @@ RTGPU_API int rtgpu_temporal_accumulate_moving_async(RtgpuContext* c, const RtTe
                                                                   prevPosition, prevObjectId, outA, outB, outLength, outMotion), { objects, numObjects, true }, true, streamHandle);
 }
 
+// the _clip entries: a table, or NULL and 0 -- then no object moved
+static TemporalMotion clipMotion(const RtObjectMotion* objects, uint32_t numObjects) { return !objects && numObjects == 0u ? kNoMotion : TemporalMotion{ objects, numObjects, true }; }
+
+RTGPU_API int rtgpu_temporal_accumulate_clip(RtgpuContext* c, const RtTemporalParams* t, uint32_t width, uint32_t height, const float* color, const float* colorHalf, const float* depth,
+                                             const float* normal, const float* position, const float* albedo, const uint32_t* objectId, const float* prevA, const float* prevB,
+                                             const float* prevLength, const float* prevDepth, const float* prevNormal, const float* prevPosition, const uint32_t* prevObjectId,
+                                             float* outA, float* outB, float* outLength, float* outMotion, const RtObjectMotion* objects, uint32_t numObjects,
+                                             const RtTemporalClip* clip, float* outConfidence)
+{
+    return temporalAccumulate(c, t, width, height, temporalPlanes(color, colorHalf, depth, normal, position, albedo, objectId, prevA, prevB, prevLength, prevDepth, prevNormal,
+                                                                  prevPosition, prevObjectId, outA, outB, outLength, outMotion, outConfidence), clipMotion(objects, numObjects), false,
+                              nullptr, true, clip);
+}
+
+RTGPU_API int rtgpu_temporal_accumulate_clip_async(RtgpuContext* c, const RtTemporalParams* t, uint32_t width, uint32_t height, const float* color, const float* colorHalf,
+                                                   const float* depth, const float* normal, const float* position, const float* albedo, const uint32_t* objectId,
+                                                   const float* prevA, const float* prevB, const float* prevLength, const float* prevDepth, const float* prevNormal,
+                                                   const float* prevPosition, const uint32_t* prevObjectId, float* outA, float* outB, float* outLength, float* outMotion,
+                                                   const RtObjectMotion* objects, uint32_t numObjects, const RtTemporalClip* clip, float* outConfidence, void* streamHandle)
+{
+    return temporalAccumulate(c, t, width, height, temporalPlanes(color, colorHalf, depth, normal, position, albedo, objectId, prevA, prevB, prevLength, prevDepth, prevNormal,
+                                                                  prevPosition, prevObjectId, outA, outB, outLength, outMotion, outConfidence), clipMotion(objects, numObjects), true,
+                              streamHandle, true, clip);
+}
+
 RTGPU_API int rtgpu_temporal_reset(RtgpuContext* c)
 {
     if (!c) return fail(RTGPU_ERR_INVALID_ARGUMENT, "NULL context");
@@ -187,16 +271,21 @@ RTGPU_API int rtgpu_temporal_reset(RtgpuContext* c)
 }
 
 // rtgpu_denoise_temporal / rtgpu_denoise_temporal_async: outHost or outDevice (outVariance is memory of the same kind, written with `v` only)
+// clip (may be NULL: the call without) and outConfidence (optional, written with a clip only): memory of the result's kind
 static int denoiseTemporalFrame(RtgpuContext* c, const RtTemporalParams* t, const RtDenoiseVarParams* v, const RtPassParams* guideParams, float* outHost, float* outDevice,
-                                float* outVariance, void* streamHandle)
+                                float* outVariance, void* streamHandle, const RtTemporalClip* clip = nullptr, float* outConfidence = nullptr)
 {
     if (!c) return fail(RTGPU_ERR_INVALID_ARGUMENT, "NULL context");
     if (!t) return fail(RTGPU_ERR_INVALID_ARGUMENT, "NULL argument");
     int r = checkTemporalParams(t, false); if (r) return r;
     if (v) { r = checkDenoiseVarParams(v); if (r) return r; }
+    if (clip) { r = checkTemporalClip(clip); if (r) return r; }
+    if (!clip) outConfidence = nullptr;
+    const bool stagesConfidence = outConfidence && outHost;
     FrameStep f;
-    r = beginFrame(c, guideParams, outHost, outDevice, outVariance, v != nullptr, streamHandle, 5u, 7u, f); if (r) return r;   // its own planes: the accumulated pair 3 + 3 and its length 1
+    r = beginFrame(c, guideParams, outHost, outDevice, outVariance, v != nullptr, streamHandle, 5u, stagesConfidence ? 8u : 7u, f, outDevice ? outConfidence : nullptr); if (r) return r;   // its own planes: the accumulated pair 3 + 3, its length 1 (and the host entry's confidence 1)
     float* const dA = f.extra; float* const dB = dA + 3u * f.stride; float* const dLength = dB + 3u * f.stride;
+    float* const dConfidence = stagesConfidence ? dLength + f.stride : outConfidence;
     RtgpuContext::Temporal& h = c->temporal;
     if (h.capacity < f.pixels) h.have = false;
     r = ensureScratch(c, h.records, h.capacity, f.pixels, 8u); if (r) return r;   // two sets of four planes of records
@@ -217,7 +306,9 @@ static int denoiseTemporalFrame(RtgpuContext* c, const RtTemporalParams* t, cons
         HIP_TRY(rtMemcpy(h.motion, table.data(), table.size() * sizeof(RtObjectMotion), hipMemcpyHostToDevice));
         motion = h.motion;
     }
-    launchTemporalKernel(in, res, c->width, c->height, temporalFrame(t, h.worldToScreen, h.sampleOffset, h.have), f.stream, motion, (uint32_t)objects.size());
+    TemporalClipLaunch clipped;
+    if (clip) { r = temporalClipLaunch(c, clip, f.pixels, h.have, dConfidence, clipped); if (r) return r; }
+    launchTemporalKernel(in, res, c->width, c->height, temporalFrame(t, h.worldToScreen, h.sampleOffset, h.have), f.stream, motion, (uint32_t)objects.size(), clip ? &clipped : nullptr);
     r = recordDone(c, f.stream); if (r) return r;
     r = markSumRead(c, f.stream); if (r) return r;
     // this frame is the next call's history
@@ -233,7 +324,9 @@ static int denoiseTemporalFrame(RtgpuContext* c, const RtTemporalParams* t, cons
         plan.flags |= RT_DENOISE_INPUT_PREPARED; plan.colorScale = 1.0f;
         r = launchAtrous(c, plan, c->width, c->height, filterPlanes(dA, dB, f.depth, f.normal, f.position, f.albedo, f.out, f.variance), f.stream, false); if (r) return r;
     }
-    return finishFrame(c, f);
+    r = finishFrame(c, f); if (r) return r;
+    if (stagesConfidence) HIP_TRY(rtMemcpy(outConfidence, dConfidence, f.pixels * sizeof(float), hipMemcpyDeviceToHost));   // (behind finishFrame's wait for the stream)
+    return RTGPU_OK;
 }
 
 RTGPU_API int rtgpu_denoise_temporal(RtgpuContext* c, const RtTemporalParams* t, const RtDenoiseVarParams* v, const RtPassParams* guideParams, float* outRGB, float* outVariance)
@@ -245,4 +338,16 @@ RTGPU_API int rtgpu_denoise_temporal_async(RtgpuContext* c, const RtTemporalPara
                                            void* streamHandle)
 {
     return denoiseTemporalFrame(c, t, v, guideParams, nullptr, outRGB, outVariance, streamHandle);
+}
+
+RTGPU_API int rtgpu_denoise_temporal_clip(RtgpuContext* c, const RtTemporalParams* t, const RtDenoiseVarParams* v, const RtPassParams* guideParams, float* outRGB, float* outVariance,
+                                          const RtTemporalClip* clip, float* outConfidence)
+{
+    return denoiseTemporalFrame(c, t, v, guideParams, outRGB, nullptr, outVariance, nullptr, clip, outConfidence);
+}
+
+RTGPU_API int rtgpu_denoise_temporal_clip_async(RtgpuContext* c, const RtTemporalParams* t, const RtDenoiseVarParams* v, const RtPassParams* guideParams, float* outRGB, float* outVariance,
+                                                const RtTemporalClip* clip, float* outConfidence, void* streamHandle)
+{
+    return denoiseTemporalFrame(c, t, v, guideParams, nullptr, outRGB, outVariance, streamHandle, clip, outConfidence);
 }

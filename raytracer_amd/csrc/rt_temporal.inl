@@ -15,6 +15,10 @@
 //                     is served from the caches, mostly as a broadcast -- whose matrix takes position and normal to where that surface point was in the
 //                     previous frame.  Projection and the tap tests use the moved pair and the id the object had then; the stored history keeps this
 //                     frame's own.  An unmoved object selects its own position and normal: the bits of k_temporal<false>.
+//   k_temporal_moments<r>   history clipping: mean and gamma standard deviations of this frame's prepared colours over the (2r + 1)^2 window pixels on the pixel's
+//                     own surface, from an LDS tile; two 16-byte records per pixel
+//   k_temporal<., true>   the same kernel reading those records (coalesced): the reprojected A is clipped to mu +- g, B shifted along, the history length cut by how
+//                     far A was pulled.  A compile-time variant: the two instantiations without it are what they were.
 
 __global__ void __launch_bounds__(RT_BLOCK) k_temporal_pack(const float* __restrict__ prevA, const float* __restrict__ prevB, const float* __restrict__ prevLength,
                                                             const float* __restrict__ prevDepth, const float* __restrict__ prevNormal, const float* __restrict__ prevPosition,
@@ -38,7 +42,86 @@ RT_DEV float4 temporalRecord(const float4* __restrict__ src, uint32_t q)
     return make_float4(lanes.x, lanes.y, lanes.z, lanes.w);
 }
 
-template <bool kMoving> __global__ void RT_ATROUS_ATTR k_temporal RT_K_TEMPORAL_ARGS
+// The colour statistics of history clipping ("Clipping the history", include/rtgpu.h): per pixel the mean and gamma standard deviations of the prepared colours
+// over the window pixels that lie on the pixel's own surface.  A block stages its tile and a halo of kRadius into LDS as three 16-byte records -- {c.rgb, depth},
+// {N.xyz, id bits}, {P.xyz, valid} -- with the prepare step done once per staged pixel; a record outside the frame is invalid, which is how its window pixel is
+// skipped.  Each lane then walks its (2 kRadius + 1)^2 window row by row from LDS with no branch around a neighbour (selects, as atrousTap) and writes
+// {mu.rgb, cnt} and {g.rgb, 0}.  Consecutive lanes read consecutive 16-byte records: no bank conflicts.  The window's columns are unrolled, its rows are not:
+// with all 49 taps of radius 3 in one basic block the scheduler hoists every LDS load (218 VGPRs, two waves per SIMD) and the kernel takes twice as long
+// (profiles/temporal_clip_resources.txt); a row at a time it holds 50 VGPRs, and the 25.5 KB tile lets six blocks -- six waves per SIMD -- share a CU.
+template <int kRadius>
+__global__ void RT_TEMPORAL_MOMENTS_ATTR k_temporal_moments RT_K_TEMPORAL_MOMENTS_ARGS
+{
+    constexpr int32_t kTileW = RT_DENOISE_TILE_X + 2 * kRadius, kTileH = RT_DENOISE_TILE_Y + 2 * kRadius;
+    __shared__ float4 tileC[kTileH * kTileW], tileN[kTileH * kTileW], tileP[kTileH * kTileW];
+    const int32_t w = (int32_t)width, h = (int32_t)height;
+    const size_t pixels = (size_t)width * height;
+    const uint32_t blocksX = (width + RT_DENOISE_TILE_X - 1u) / RT_DENOISE_TILE_X, blockY = blockIdx.x / blocksX, blockX = blockIdx.x - blockY * blocksX;   // (as k_atrous numbers them)
+    const int32_t x0 = (int32_t)(blockX * RT_DENOISE_TILE_X), y0 = (int32_t)(blockY * RT_DENOISE_TILE_Y);
+    for (int32_t e = (int32_t)(threadIdx.y * RT_DENOISE_TILE_X + threadIdx.x); e < kTileH * kTileW; e += RT_DENOISE_TILE_X * RT_DENOISE_TILE_Y)
+    {
+        const int32_t ty = e / kTileW, tx = e - ty * kTileW;
+        const int32_t gx = x0 - kRadius + tx, gy = y0 - kRadius + ty;
+        const bool inside = gx >= 0 && gx < w && gy >= 0 && gy < h;
+        float4 c = make_float4(0.0f, 0.0f, 0.0f, 0.0f), n = c, ps = c;
+        if (inside)
+        {
+            const uint32_t g = (uint32_t)gy * width + (uint32_t)gx;
+            const float depth = in.depth[g];
+            const bool valid = (__float_as_uint(depth) & 0x7F800000u) != 0x7F800000u;
+            float ck[3];
+#pragma unroll
+            for (uint32_t k = 0; k < 3u; ++k)
+            {
+                ck[k] = in.color[3 * (size_t)g + k] * frame.colorScale;
+                if (in.albedo) ck[k] = ck[k] / denoiseAlbedoDivisor(in.albedo, pixels, g, k);
+            }
+            c = make_float4(ck[0], ck[1], ck[2], depth);
+            n = make_float4(in.normal[g], in.normal[pixels + g], in.normal[2 * pixels + g], __uint_as_float(in.objectId ? in.objectId[g] : 0u));
+            ps = make_float4(in.position[g], in.position[pixels + g], in.position[2 * pixels + g], valid ? 1.0f : 0.0f);
+        }
+        tileC[e] = c; tileN[e] = n; tileP[e] = ps;
+    }
+    __syncthreads();
+    const int32_t x = x0 + (int32_t)threadIdx.x, y = y0 + (int32_t)threadIdx.y;
+    if (x >= w || y >= h) return;
+    const uint32_t p = (uint32_t)y * width + (uint32_t)x;
+    const int32_t centre = ((int32_t)threadIdx.y + kRadius) * kTileW + (int32_t)threadIdx.x + kRadius;
+    const float4 cp = tileC[centre], np = tileN[centre], pp = tileP[centre];
+    const float limit = frame.planeTolerance * cp.w;
+    float cnt = 0.0f, s10 = 0.0f, s11 = 0.0f, s12 = 0.0f, s20 = 0.0f, s21 = 0.0f, s22 = 0.0f;
+#pragma unroll 1   // (see above)
+    for (int32_t dy = -kRadius; dy <= kRadius; ++dy)
+    {
+#pragma unroll
+        for (int32_t dx = -kRadius; dx <= kRadius; ++dx)
+        {
+            const int32_t q = centre + dy * kTileW + dx;
+            const float4 cq = tileC[q], nq = tileN[q], pq = tileP[q];
+            const float dpx = pq.x - pp.x, dpy = pq.y - pp.y, dpz = pq.z - pp.z;
+            const float cosine = (np.x * nq.x + np.y * nq.y) + np.z * nq.z;
+            const float offset = fabsf((np.x * dpx + np.y * dpy) + np.z * dpz);
+            const bool counts = pq.w != 0.0f && __float_as_uint(nq.w) == __float_as_uint(np.w) && cosine >= frame.normalThreshold && offset <= limit;
+            cnt = counts ? cnt + 1.0f : cnt;
+            s10 = counts ? s10 + cq.x : s10;
+            s11 = counts ? s11 + cq.y : s11;
+            s12 = counts ? s12 + cq.z : s12;
+            s20 = counts ? s20 + cq.x * cq.x : s20;
+            s21 = counts ? s21 + cq.y * cq.y : s21;
+            s22 = counts ? s22 + cq.z * cq.z : s22;
+        }
+    }
+    // (cnt == 0: not a number, and never read -- minCount is at least 1)
+    const float mu0 = s10 / cnt, mu1 = s11 / cnt, mu2 = s12 / cnt;
+    const float var0 = fmaxf(s20 / cnt - mu0 * mu0, 0.0f), var1 = fmaxf(s21 / cnt - mu1 * mu1, 0.0f), var2 = fmaxf(s22 / cnt - mu2 * mu2, 0.0f);
+    outMu[p] = make_float4(mu0, mu1, mu2, cnt);
+    outG[p] = make_float4(frame.gamma * sqrtf(var0), frame.gamma * sqrtf(var1), frame.gamma * sqrtf(var2), 0.0f);
+}
+template __global__ void RT_TEMPORAL_MOMENTS_ATTR k_temporal_moments<1> RT_K_TEMPORAL_MOMENTS_ARGS;
+template __global__ void RT_TEMPORAL_MOMENTS_ATTR k_temporal_moments<2> RT_K_TEMPORAL_MOMENTS_ARGS;
+template __global__ void RT_TEMPORAL_MOMENTS_ATTR k_temporal_moments<3> RT_K_TEMPORAL_MOMENTS_ARGS;
+
+template <bool kMoving, bool kClip> __global__ void RT_ATROUS_ATTR k_temporal RT_K_TEMPORAL_ARGS
 {
     // (blocks numbered row by row along grid.x, as k_atrous numbers them)
     const uint32_t blocksX = (width + RT_DENOISE_BLOCK_X - 1u) / RT_DENOISE_BLOCK_X, blockY = blockIdx.x / blocksX, blockX = blockIdx.x - blockY * blocksX;
@@ -67,8 +150,11 @@ template <bool kMoving> __global__ void RT_ATROUS_ATTR k_temporal RT_K_TEMPORAL_
         }
     }
     float a0 = c[0], a1 = c[1], a2 = c[2], b0 = b[0], b1 = b[1], b2 = b[2], length = 1.0f, motionX = 0.0f, motionY = 0.0f;   // a pixel that starts
+    [[maybe_unused]] float confidence = 1.0f;
     if (in.recA)   // (uniform: NULL without history)
     {
+        [[maybe_unused]] float4 mu, g;   // (k_temporal_moments' records of this pixel: two coalesced 16-byte loads, in flight beside the taps)
+        if constexpr (kClip) { mu = temporalRecord(frame.momentMu, p); g = temporalRecord(frame.momentG, p); }
         // where the pixel's surface point was in the previous frame (pm, nm) and the id its object had there: its own, unless objects moved
         float4 pm = pp, nm = np;
         uint32_t idThen = idP;
@@ -149,7 +235,22 @@ template <bool kMoving> __global__ void RT_ATROUS_ATTR k_temporal RT_K_TEMPORAL_
             // blend
             hA0 = hA0 / ks; hA1 = hA1 / ks; hA2 = hA2 / ks;
             hB0 = hB0 / ks; hB1 = hB1 / ks; hB2 = hB2 / ks;
-            const float n = fminf(ln / ks + 1.0f, frame.maxHistory);
+            float n;
+            if constexpr (kClip)
+            {
+                // clip A into mu +- g, shift B by what A moved, and cut the history length by how far that was against the box's width; a pixel whose
+                // window holds too few of its surface keeps every value (selects), and with e == 0 the factor is exactly 1: the bits of the call without
+                const bool clips = mu.w >= frame.minCount;
+                const float c0 = fminf(fmaxf(hA0, mu.x - g.x), mu.x + g.x), c1 = fminf(fmaxf(hA1, mu.y - g.y), mu.y + g.y), c2 = fminf(fmaxf(hA2, mu.z - g.z), mu.z + g.z);
+                const float s0 = c0 - hA0, s1 = c1 - hA1, s2 = c2 - hA2;
+                const float e = (fabsf(s0) + fabsf(s1)) + fabsf(s2);
+                const float wd = (g.x + g.y) + g.z;
+                hB0 = clips ? hB0 + s0 : hB0; hB1 = clips ? hB1 + s1 : hB1; hB2 = clips ? hB2 + s2 : hB2;
+                hA0 = clips ? c0 : hA0; hA1 = clips ? c1 : hA1; hA2 = clips ? c2 : hA2;
+                confidence = clips && e > 0.0f ? wd / (wd + e) : 1.0f;
+                n = fminf((ln / ks) * confidence + 1.0f, frame.maxHistory);
+            }
+            else n = fminf(ln / ks + 1.0f, frame.maxHistory);
             const float alpha = fmaxf(1.0f / n, frame.alphaMin);
             a0 = hA0 + alpha * (c[0] - hA0); a1 = hA1 + alpha * (c[1] - hA1); a2 = hA2 + alpha * (c[2] - hA2);
             b0 = hB0 + alpha * (b[0] - hB0); b1 = hB1 + alpha * (b[1] - hB1); b2 = hB2 + alpha * (b[2] - hB2);
@@ -161,6 +262,7 @@ template <bool kMoving> __global__ void RT_ATROUS_ATTR k_temporal RT_K_TEMPORAL_
     out.b[3 * (size_t)p + 0] = b0; out.b[3 * (size_t)p + 1] = b1; out.b[3 * (size_t)p + 2] = b2;
     out.length[p] = length;
     if (out.motion) { out.motion[p] = motionX; out.motion[pixels + p] = motionY; }
+    if constexpr (kClip) { if (frame.confidence) frame.confidence[p] = confidence; }
     if (out.recA)   // the context's next history: this frame's pair beside this frame's guides
     {
         out.recA[p] = make_float4(a0, a1, a2, length);
@@ -171,5 +273,7 @@ template <bool kMoving> __global__ void RT_ATROUS_ATTR k_temporal RT_K_TEMPORAL_
     if (out.image) { out.image[3 * (size_t)p + 0] = a0 * d[0]; out.image[3 * (size_t)p + 1] = a1 * d[1]; out.image[3 * (size_t)p + 2] = a2 * d[2]; }
 }
 
-template __global__ void RT_ATROUS_ATTR k_temporal<false>(const TemporalIn, const TemporalOut, uint32_t, uint32_t, const TemporalFrame);
-template __global__ void RT_ATROUS_ATTR k_temporal<true>(const TemporalIn, const TemporalOut, uint32_t, uint32_t, const TemporalFrameMoving);
+template __global__ void RT_ATROUS_ATTR k_temporal<false, false>(const TemporalIn, const TemporalOut, uint32_t, uint32_t, const TemporalFrame);
+template __global__ void RT_ATROUS_ATTR k_temporal<true, false>(const TemporalIn, const TemporalOut, uint32_t, uint32_t, const TemporalFrameMoving);
+template __global__ void RT_ATROUS_ATTR k_temporal<false, true>(const TemporalIn, const TemporalOut, uint32_t, uint32_t, const TemporalFrameClip<TemporalFrame>);
+template __global__ void RT_ATROUS_ATTR k_temporal<true, true>(const TemporalIn, const TemporalOut, uint32_t, uint32_t, const TemporalFrameClip<TemporalFrameMoving>);

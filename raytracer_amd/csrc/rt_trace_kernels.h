@@ -66,9 +66,19 @@ struct TemporalFrame { float colorScale, alphaMin, maxHistory, normalThreshold, 
 // k_temporal<true>, moving objects: the frame's constants and the motion table -- five float4 per object, RtObjectMotion's 80 bytes: the rows of m, then
 // {prevId, moved, 0, 0}.  The static instantiation takes TemporalFrame itself: its argument list is what it was before objects could move.
 struct TemporalFrameMoving : TemporalFrame { const float4* objects; uint32_t numObjects; };
-template <bool kMoving> struct TemporalFrameOf { typedef TemporalFrame type; };
-template <> struct TemporalFrameOf<true> { typedef TemporalFrameMoving type; };
-#define RT_K_TEMPORAL_ARGS (const TemporalIn in, const TemporalOut out, uint32_t width, uint32_t height, const typename TemporalFrameOf<kMoving>::type frame)
+// k_temporal<., true>, history clipping: behind either frame the two planes of moment records k_temporal_moments wrote -- {mu.rgb, cnt} and {g.rgb, 0} --, the
+// count a pixel needs to clip (RtTemporalClip::minCount, as a float: cnt is one) and the confidence plane (may be NULL).  The two instantiations without take the
+// argument lists they took before there was a clip.
+template <class Frame> struct TemporalFrameClip : Frame { const float4* momentMu; const float4* momentG; float* confidence; float minCount; };
+template <bool kMoving, bool kClip = false> struct TemporalFrameOf { typedef TemporalFrame type; };
+template <> struct TemporalFrameOf<true, false> { typedef TemporalFrameMoving type; };
+template <bool kMoving> struct TemporalFrameOf<kMoving, true> { typedef TemporalFrameClip<typename TemporalFrameOf<kMoving, false>::type> type; };
+#define RT_K_TEMPORAL_ARGS (const TemporalIn in, const TemporalOut out, uint32_t width, uint32_t height, const typename TemporalFrameOf<kMoving, kClip>::type frame)
+// k_temporal_moments<kRadius> (history clipping): k_atrous_tiled's block of 8 rows x 32 columns with a halo of kRadius, three 16-byte records per staged pixel
+// (at radius 3: 38 x 14 x 48 bytes = 25.5 KB of LDS); reads the current frame's planes of TemporalIn, writes the two moment records per pixel
+struct TemporalMomentsFrame { float colorScale, normalThreshold, planeTolerance, gamma; };
+#define RT_K_TEMPORAL_MOMENTS_ARGS (const TemporalIn in, uint32_t width, uint32_t height, const TemporalMomentsFrame frame, float4* __restrict__ outMu, float4* __restrict__ outG)
+#define RT_TEMPORAL_MOMENTS_ATTR __launch_bounds__(RT_DENOISE_TILE_X * RT_DENOISE_TILE_Y)
 
 #ifndef RT_DEVICE_KERNELS
 template <int kStack, bool kCount, bool kPerRay = false> __global__ void RT_TRACE_ATTR(kStack) k_trace RT_K_TRACE_ARGS;
@@ -121,6 +131,7 @@ __global__ void __launch_bounds__(RT_BLOCK) k_temporal_pack(const float* __restr
                                                             const float* __restrict__ prevDepth, const float* __restrict__ prevNormal, const float* __restrict__ prevPosition,
                                                             const uint32_t* __restrict__ prevObjectId, uint32_t pixels, float4* __restrict__ recA, float4* __restrict__ recB,
                                                             float4* __restrict__ recN, float4* __restrict__ recP);
-template <bool kMoving = false> __global__ void RT_ATROUS_ATTR k_temporal RT_K_TEMPORAL_ARGS;
+template <bool kMoving = false, bool kClip = false> __global__ void RT_ATROUS_ATTR k_temporal RT_K_TEMPORAL_ARGS;
+template <int kRadius> __global__ void RT_TEMPORAL_MOMENTS_ATTR k_temporal_moments RT_K_TEMPORAL_MOMENTS_ARGS;
 __global__ void __launch_bounds__(RT_MONSTER_BLOCK) k_trace_monster(const RtSceneDesc scene, const Paths paths, const uint32_t* __restrict__ queue, const uint32_t* __restrict__ queueCount);
 #endif

@@ -18,6 +18,10 @@ Worth: the relative MSE, mean((x - ref)^2 / (ref^2 + 0.01)), against a render of
 the last frame alone and (b) the temporal call after `--frames` frames; beside them the raw frame and the accumulated frame without the spatial filter.
 Prints one JSON line and, with --output, writes it to a file.
 
+--clip adds, per gamma of --clip-gammas at radius 3, minCount 9: `rel_mse` of the same sequence with the history clipped (Viewport.denoise(temporal=True,
+clip=...)) filtered and unfiltered, the share of the last frame's pixels whose confidence fell below 0.5 and below 1, and for the first gamma the times
+`temporal_call_clipped`, `temporal_unfiltered_clipped` and `accumulate_pure_clipped` beside their unclipped twins (k_temporal_moments + the clipping k_temporal).
+
 --diagnose adds `starts_by_the_model`: the NumPy model (tests/temporal_ref.py) over the guides of the last two frames, with the defaults and with one
 surface test relaxed at a time -- how many pixels start and why.
 
@@ -53,6 +57,8 @@ def main():
     ap.add_argument("--depth", type=int, default=8)
     ap.add_argument("--triangles", type=int, default=262144)
     ap.add_argument("--diagnose", action="store_true", help="also count, by the NumPy model on the last two frames' guides, why pixels start")
+    ap.add_argument("--clip", action="store_true", help="add the clipped columns: the same sequence with the history clipped, once per gamma")
+    ap.add_argument("--clip-gammas", default="1,2,4,8")
     ap.add_argument("--output", default=None)
     args = ap.parse_args()
     if args.frames < 2:
@@ -135,6 +141,26 @@ def main():
                           "hit_share": float(hit.float().mean()), "length_mean_of_hits": float(length.mean()),
                           "share_of_hits_that_started_in_the_last_frame": float((length == 1.0).float().mean()),
                           "share_of_hits_with_length_at_least_8": float((length >= 8.0).float().mean())}
+        # the same sequence with the history clipped, filtered and not
+        gammas = [float(g) for g in args.clip_gammas.split(",")] if args.clip else []
+        for gamma in gammas:
+            clip = dict(radius=3, gamma=gamma, min_count=9)
+            for variance, label in ((True, "b_temporal_clipped_gamma_%g"), (False, "temporal_unfiltered_clipped_gamma_%g")):
+                vp.reset_history()
+                for frame in range(args.frames):
+                    look(frame)
+                    vp.reset()
+                    vp.render(camera, passes=args.passes)
+                    image, confidence = vp.denoise(vp.next_pass_params(camera), temporal=True, variance=variance, device=True, clip=clip, return_confidence=True)
+                out["rel_mse"][label % gamma] = rel_mse(image.cpu().numpy())
+            out.setdefault("clip_confidence", {})["gamma_%g" % gamma] = {"share_below_0.5": float((confidence < 0.5).float().mean()), "share_below_1": float((confidence < 1.0).float().mean())}
+        if gammas:   # (leave the film and the history as the timed calls below expect them: the last frame, unclipped)
+            vp.reset_history()
+            look(last)
+            vp.reset()
+            vp.render(camera, passes=args.passes)
+            guide = vp.next_pass_params(camera)
+            vp.denoise(guide, temporal=True, variance=True, device=True)
         # times: the film holds the last frame; every timed temporal call sees a full history (the call before it stored one at the same camera)
         # (the five planes through the raw entry, into tensors made once: what the temporal call itself does, without the wrapper's id conversion)
         raw = [torch.empty((ra.AOV_PLANES[name][1], h, w), dtype=torch.float32 if ra.AOV_PLANES[name][2] is np.float32 else torch.int32, device=temporal.device) for name in names]
@@ -150,6 +176,13 @@ def main():
         camera_kw = dict(prev_world_to_screen=list(history_before.camera.worldToScreen), prev_sample_offset=tuple(history_before.sampleOffset))
         out["accumulate_pure"] = time_call(torch, lambda: ra.temporal_accumulate(color, color_half, history=first, **camera_kw, **kw), args.reps)
         out["accumulate_pure_start"] = time_call(torch, lambda: ra.temporal_accumulate(color, color_half, **kw), args.reps)
+        if gammas:
+            clip = dict(radius=3, gamma=gammas[0], min_count=9)
+            out["temporal_call_clipped"] = time_call(torch, lambda: vp.denoise(guide, temporal=True, variance=True, device=True, clip=clip), args.reps)
+            out["temporal_unfiltered_clipped"] = time_call(torch, lambda: vp.denoise(guide, temporal=True, variance=False, device=True, clip=clip), args.reps)
+            out["accumulate_pure_clipped"] = time_call(torch, lambda: ra.temporal_accumulate(color, color_half, history=first, clip=clip, **camera_kw, **kw), args.reps)
+            out["temporal_call_again"] = time_call(torch, lambda: vp.denoise(guide, temporal=True, variance=True, device=True), args.reps)
+            out["temporal_unfiltered_again"] = time_call(torch, lambda: vp.denoise(guide, temporal=True, variance=False, device=True), args.reps)
     # why pixels start, by the model (tests/temporal_ref.py) on the guides of the last two frames: the defaults, then one test relaxed at a time
     if args.diagnose:
         sys.path.insert(0, os.path.join(ROOT, "tests"))

@@ -17,6 +17,8 @@ over the whole frame and over the pixels of the orbiting objects alone, of
   a  this feature: update_scene() + Viewport.denoise(temporal=True) every frame, the history kept across the moves
   b  the history dropped at every move (what a caller had to do: every move was a new scene)
   c  rtgpu_denoise_var on the last frame alone
+  d  (--clip) a with the history clipped to each frame's local colour statistics (Viewport.denoise(temporal=True, clip=...)), once per gamma of --clip-gammas at
+     radius 3, minCount 9; beside each the share of the last frame's pixels whose confidence fell below 0.5 (where the history was pulled far) and below 1
 The history follows surfaces, not light: where a moved object's shadow was, and on a surface that turned towards or away from a light, it lags by what alphaMin
 allows.  Under the scene's sun (20 000 units through a one-degree cone) that lag dominates a RELATIVE error; --no-sun measures the same frames under the sky alone.
 Prints one JSON line and, with --output, writes it to a file.
@@ -65,6 +67,8 @@ def main():
     ap.add_argument("--depth", type=int, default=8)
     ap.add_argument("--triangles", type=int, default=262144)
     ap.add_argument("--no-sun", action="store_true", help="leave the directional light out: under the sky alone nothing casts a hard shadow that moves with the objects")
+    ap.add_argument("--clip", action="store_true", help="add the clipped columns: the same frames with the history clipped, once per gamma")
+    ap.add_argument("--clip-gammas", default="1,2,4,8")
     ap.add_argument("--output", default=None)
     args = ap.parse_args()
     import torch
@@ -139,7 +143,7 @@ def main():
     scale = np.float32(1.0 / args.passes)
     last = args.frames - 1
     with torch.cuda.stream(stream):
-        def chain(drop_history):
+        def chain(drop_history, clip=None):
             vp.reset_history()
             for frame in range(args.frames):
                 move_to(frame)
@@ -148,14 +152,21 @@ def main():
                 guide = vp.next_pass_params(camera)
                 if drop_history:
                     vp.reset_history()
-                image = vp.denoise(guide, temporal=True, variance=True, device=True)
+                if clip is None:
+                    image = vp.denoise(guide, temporal=True, variance=True, device=True)
+                else:
+                    image, confidence = vp.denoise(guide, temporal=True, variance=True, device=True, clip=clip, return_confidence=True)
             stream.synchronize()
-            return image.cpu().numpy(), guide
+            return (image.cpu().numpy(), guide) if clip is None else (image.cpu().numpy(), confidence.cpu().numpy())
         followed, guide = chain(False)
         alone = vp.denoise(guide, variance=True, device=True).cpu().numpy()
         raw = vp.sum_buffer() * scale
         planes = vp.render_aovs(guide, names, device=True)
         dropped, _ = chain(True)
+        clipped = {}
+        if args.clip:
+            for gamma in (float(g) for g in args.clip_gammas.split(",")):
+                clipped[gamma] = chain(False, clip=dict(radius=3, gamma=gamma, min_count=9))
         # the reference: the scene as it stands now, converged
         vp.reset()
         vp.render(camera, passes=args.reference_passes)
@@ -173,6 +184,11 @@ def main():
                           "c_denoise_var_last_frame_alone": rel_mse(alone)}
         out["rel_mse_on_orbiters"] = {"raw_frame": rel_mse(raw, on_orbiters), "a_update_and_temporal": rel_mse(followed, on_orbiters),
                                       "b_history_dropped_at_every_move": rel_mse(dropped, on_orbiters), "c_denoise_var_last_frame_alone": rel_mse(alone, on_orbiters)}
+
+        for gamma, (image, confidence) in clipped.items():
+            key = "d_clipped_gamma_%g" % gamma
+            out["rel_mse"][key], out["rel_mse_on_orbiters"][key] = rel_mse(image), rel_mse(image, on_orbiters)
+            out.setdefault("clip_confidence", {})[key] = {"share_below_0.5": float((confidence < 0.5).mean()), "share_below_1": float((confidence < 1.0).mean())}
 
         # ---- the kernel with and without the table: the raw _async entries on tensors made once ----------------------------------------------------------
         vp.reset()
