@@ -715,6 +715,77 @@ int rtgpu_render_aovs_async(RtgpuContext* ctx, const RtPassParams* params, const
                             void* stream);
 
 /* ---------------------------------------------------------------------------------------------
+ * Guide chains: the AOV planes at the first vertex of a pixel's path that is not a mirror or a pane of glass.  Inside a reflection the first
+ * hit is the wrong surface to steer a filter by: the mirror's normal, position and base colour are constant over the whole reflected scene.
+ * The chain call follows the pixel's path through such surfaces and evaluates the planes where it stops.
+ *   the path   For a pixel, the path RT_INTEGRATOR_PATH_TRACER_MIS would trace for it under `params`, whichever integrator the context has
+ *              selected: the same sampler draws in the same order.  At every surface vertex these are the next-event draws of the pass's
+ *              light-sampling mode (RT_LIGHT_SAMPLING_SINGLE: the light pick when the scene has more than one light, then three floats;
+ *              RT_LIGHT_SAMPLING_ALL: three floats per light; none in a scene without lights), the roulette draw from
+ *              minRussianRouletteDepth on, and the three BSDF draws.
+ *   passed     Vertex j (j = depth, from 0) is PASSED iff all of these hold:
+ *                - the path goes on from it: it is not the closing vertex (not a miss, not a finite light, not ended by maxRayDepth,
+ *                  roulette, a zero throughput or a missing BSDF event);
+ *                - its sampled event is specular (RtPathVertex::bsdfEvent & 48: specular reflection 16 or specular refraction 32);
+ *                - its material's bsdf is RT_BSDF_DIELECTRIC, RT_BSDF_ROUGH_DIELECTRIC, RT_BSDF_METAL or RT_BSDF_ROUGH_METAL;
+ *                - j < maxChain.
+ *              The (bsdf, roughness) pairs that can return a specular event at all: DIELECTRIC and METAL at any roughness; ROUGH_DIELECTRIC,
+ *              ROUGH_METAL, ROUGH_PLASTIC with an evaluated roughness < 0.005 (below it they sample as their smooth siblings); PLASTIC at any
+ *              roughness.  PLASTIC and ROUGH_PLASTIC are excluded on purpose: the coat samples a specular event with probability >= 0.25
+ *              at every vertex, and following it would salt a plastic floor with reflection guides pixel by pixel.
+ *   the guide  The GUIDE VERTEX is vertex k, the first one not passed.
+ *   planes     - the 15 non-cost planes of RtAovPlane (DEPTH .. MATERIAL) mean what they mean for rtgpu_render_aovs, evaluated at the guide
+ *                vertex with that vertex's own ray: a secondary ray is Ray(origin, direction) with the origin then moved by direction * 0.001f.
+ *                DEPTH is that ray's hit distance, +inf on a miss.  On a miss everything else is 0 except OBJECT_ID (RT_INVALID_OBJECT) and
+ *                MATERIAL (RT_NO_MATERIAL); on a finite light the geometry planes hold what Scene::EvaluateIntersection returns -- at
+ *                depth > 0 with the previous vertex's material still in IntersectionData::material, so that material's normal map (if any)
+ *                is applied to the light's frame, as the reference's path tracer does -- the material planes are 0 and MATERIAL is
+ *                RT_NO_MATERIAL.  BARYCENTRICS are non-zero on mesh triangles only.
+ *              - RT_AOV_CHAIN_LENGTH     1 u32  k
+ *              - RT_AOV_CHAIN_DISTANCE   1 f32  ((d_0 + d_1) + ...) + d_k, the hit distances of vertices 0..k summed left to right in f32;
+ *                                               +inf when the guide vertex is a miss
+ *              - RT_AOV_CHAIN_THROUGHPUT 3 f32  the path throughput on arrival at the guide vertex: 1 for k = 0, otherwise what vertex k - 1
+ *                                               leaves behind (BSDF value over pdf, roulette division included)
+ *              - the four cost planes (RT_AOV_BOX_TESTS .. RT_AOV_TRIANGLE_TESTS_PASSED) are refused: they describe one traversal.
+ *   bounds     params->maxRayDepth and minRussianRouletteDepth bound the chain as they bound the path.  A caller who wants chains that
+ *              roulette never cuts passes guide params with minRussianRouletteDepth >= maxChain.
+ *   identity   maxChain == 0 gives the bits of rtgpu_render_aovs on every common plane.
+ *   errors     those of rtgpu_render_aovs; chain NULL, maxChain > RT_AOV_CHAIN_MAX, non-zero flags, or a cost plane:
+ *              RTGPU_ERR_INVALID_ARGUMENT.  The chain plane ids lie behind RT_AOV_NUM_PLANES: rtgpu_render_aovs refuses them.
+ * Layout, stream, alignment, chunking (RTGPU_AOV_CHUNK), multi-device, shard and active-block rules are those of rtgpu_render_aovs[_async].
+ * The calls submit the passes queued on the device they answer on first, are not passes, and leave film, sum buffers, counters, kernel times,
+ * the photon state, the path recorder and the temporal history alone.  Arena and queues are their own, grown on use, freed with the context.
+ * A vertex whose material cannot pass, or whose depth is maxChain, stops before a draw is taken: a frame without mirrors and glass costs
+ * what the first-hit call costs plus one shading launch that evaluates the hit.
+ *
+ * rtgpu_set_guide_chain makes rtgpu_denoise[_async] and rtgpu_denoise_var[_async] render their DEPTH, NORMAL, POSITION and BASE_COLOR guides
+ * through the chain call: by definition the result is rtgpu_render_aovs_chain followed by the pure filter entry on the same planes.  NULL
+ * clears it (first hit, the default).  While a chain is set, rtgpu_denoise_temporal* and rtgpu_denoise_temporal_clip* answer
+ * RTGPU_ERR_UNSUPPORTED and leave the history as it was.
+ * Measured (one MI355X, Sponza-class 1920 x 1080, maxChain 3; tools/bench_aovs.py and tools/bench_denoise.py with --chain 3 --mirror): the four
+ * guide planes take 0.93 ms against the first-hit call's 0.57 where nothing is specular, 1.82 against 0.74 with a mirror and a glass sphere over a sixth of the frame.
+ * At 16 passes the plain filter's relative MSE inside the mirror is 0.187 with chain guides against 0.216 without; under the variance-guided filter chain guides
+ * measure worse (mirror 0.088 against 0.029, glass sphere 1.78 against 0.035).
+ * Scope: temporal reprojection through a chain needs the virtual motion of the mirrored point and is not provided.  On glass one pass's
+ * guides pick reflect or refract per pixel by the pass's own draw while the colour averages both; a deterministic choice is not provided.
+ * --------------------------------------------------------------------------------------------- */
+#define RT_AOV_CHAIN_MAX 16u
+typedef enum RtAovChainPlane {
+    RT_AOV_CHAIN_LENGTH = RT_AOV_NUM_PLANES,   /* 1 u32 */
+    RT_AOV_CHAIN_DISTANCE,                     /* 1 f32 */
+    RT_AOV_CHAIN_THROUGHPUT,                   /* 3 f32 */
+    RT_AOV_CHAIN_NUM_PLANES
+} RtAovChainPlane;
+typedef struct RtAovChain { uint32_t maxChain; /* 0 .. 16 vertices passed at most */ uint32_t flags; /* 0 */ uint32_t _pad[2]; } RtAovChain;   /* 16 bytes */
+/* Host pointers; synchronous. */
+int rtgpu_render_aovs_chain(RtgpuContext* ctx, const RtPassParams* params, const RtAovChain* chain, const uint32_t* planes, uint32_t numPlanes,
+                            void* const* outputs);
+/* Device pointers (16-byte aligned) on `stream`, as rtgpu_render_aovs_async. */
+int rtgpu_render_aovs_chain_async(RtgpuContext* ctx, const RtPassParams* params, const RtAovChain* chain, const uint32_t* planes,
+                                  uint32_t numPlanes, void* const* outputs, void* stream);
+int rtgpu_set_guide_chain(RtgpuContext* ctx, const RtAovChain* chain /* NULL: first hit, the default */);
+
+/* ---------------------------------------------------------------------------------------------
  * Denoise: an edge-avoiding a-trous wavelet filter (Dammertz et al. 2010) over a rendered frame, guided by the first-hit planes
  * rtgpu_render_aovs writes.  It is this library's own filter, defined here operation by operation; tests/denoise_ref.py is the same text in
  * NumPy float32 and the device is held to it bit for bit.

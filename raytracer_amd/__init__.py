@@ -45,6 +45,11 @@ def rtgpu_lib():
         _rtgpu = _load(RTGPU_LIB_PATH)
         _rtgpu.rtgpu_last_error.restype = C.c_char_p
         _rtgpu.rtgpu_abi_version.restype = C.c_uint32
+        # guide chains: (ctx, params, chain, planes, numPlanes, outputs[, stream])
+        chain_args = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p]
+        _rtgpu.rtgpu_render_aovs_chain.argtypes, _rtgpu.rtgpu_render_aovs_chain.restype = chain_args, C.c_int
+        _rtgpu.rtgpu_render_aovs_chain_async.argtypes, _rtgpu.rtgpu_render_aovs_chain_async.restype = chain_args + [C.c_void_p], C.c_int
+        _rtgpu.rtgpu_set_guide_chain.argtypes, _rtgpu.rtgpu_set_guide_chain.restype = [C.c_void_p, C.c_void_p], C.c_int
     return _rtgpu
 
 
@@ -225,6 +230,16 @@ AOV_PLANES = collections.OrderedDict(
         ("roughness", 1, np.float32), ("metalness", 1, np.float32), ("ior", 1, np.float32), ("object_id", 1, np.uint32),
         ("sub_object_id", 1, np.uint32), ("material", 1, np.uint32), ("box_tests", 1, np.uint32), ("box_tests_passed", 1, np.uint32),
         ("triangle_tests", 1, np.uint32), ("triangle_tests_passed", 1, np.uint32))))
+
+# RtAovChainPlane (include/rtgpu.h): the planes of render_aovs(chain=N) alone, behind AOV_PLANES' ids
+AOV_CHAIN_PLANES = collections.OrderedDict(
+    (name, (len(AOV_PLANES) + i, channels, dtype)) for i, (name, channels, dtype) in enumerate((
+        ("chain_length", 1, np.uint32), ("chain_distance", 1, np.float32), ("chain_throughput", 3, np.float32))))
+AOV_CHAIN_MAX = 16
+
+
+class RtAovChain(C.Structure):
+    _fields_ = [("maxChain", C.c_uint32), ("flags", C.c_uint32), ("_pad", C.c_uint32 * 2)]
 
 
 # ---- denoise (include/rtgpu.h: rtgpu_filter_atrous / rtgpu_denoise) --------------------------------------------------------------------------
@@ -1097,19 +1112,27 @@ class Viewport:
         return [(vertices[i, :min(int(infos[i, 0]), capacity)].copy(), int(infos[i, 1]), radiance[i].copy()) for i in range(n)]
 
     # ---- AOVs (include/rtgpu.h: rtgpu_render_aovs / rtgpu_render_aovs_async) -------------------------------------------------------------
-    def render_aovs(self, params, planes=("depth", "normal", "base_color"), device=False):
+    def render_aovs(self, params, planes=("depth", "normal", "base_color"), device=False, chain=None):
         """What the primary ray of every pixel finds, as raw planes from one call: `planes` names them (AOV_PLANES: first-hit geometry, the
         evaluated material, ids, and the box / triangle tests of the traversal).  Returns a dict name -> array, (H, W) for a one-channel plane and
         (C, H, W) otherwise, row y as in sum_buffer(); float planes are float32, id and cost planes uint32.  device=True: torch tensors on the
         renderer's ROCm device, produced on torch.cuda.current_stream() without a host copy (ids and costs int64, as trace_rays returns them).
         `params` is an RtPassParams from next_pass_params(): the rays are those the pass would trace (the same lens samples), the call renders
-        nothing and is not a pass.  A Camera is not accepted, for the reason record_paths gives."""
+        nothing and is not a pass.  A Camera is not accepted, for the reason record_paths gives.
+        chain=N (0..16, rtgpu_render_aovs_chain): the planes at the guide vertex of every pixel's path instead -- the first vertex that is not a
+        specular event of a mirror or glass material, at most N vertices in -- and the AOV_CHAIN_PLANES beside them; the cost planes have no chain
+        form.  chain=None is the first-hit call."""
         if not isinstance(params, RtPassParams):
             raise TypeError("render_aovs takes the RtPassParams of next_pass_params(camera), not %s" % type(params).__name__)
         names = [planes] if isinstance(planes, str) else list(planes)
+        known = AOV_PLANES if chain is None else collections.OrderedDict(list(AOV_PLANES.items()) + list(AOV_CHAIN_PLANES.items()))
         for name in names:
-            if name not in AOV_PLANES:
+            if name not in known:
+                if name in AOV_CHAIN_PLANES:
+                    raise ValueError("AOV plane %r needs chain=N" % (name,))
                 raise ValueError("unknown AOV plane %r (AOV_PLANES lists them)" % (name,))
+        if chain is not None:
+            chain_desc = RtAovChain(int(chain), 0)
         if not self.has_renderer:
             raise RuntimeError("render_aovs needs a renderer: call set_renderer first")
         ctx = self.device_context()
@@ -1117,26 +1140,45 @@ class Viewport:
             raise RuntimeError("the viewport's renderer has no device context or its scene could not be uploaded: %s" % (rtgpu_lib().rtgpu_last_error() or b"").decode())
         lib = rtgpu_lib()
         n = len(names)
-        ids = (C.c_uint32 * max(n, 1))(*[AOV_PLANES[name][0] for name in names])
+        ids = (C.c_uint32 * max(n, 1))(*[known[name][0] for name in names])
         h, w = self.height, self.width
-        shape = lambda name: (h, w) if AOV_PLANES[name][1] == 1 else (AOV_PLANES[name][1], h, w)   # noqa: E731
+        shape = lambda name: (h, w) if known[name][1] == 1 else (known[name][1], h, w)   # noqa: E731
         if not device:
-            out = collections.OrderedDict((name, np.zeros(shape(name), dtype=AOV_PLANES[name][2])) for name in names)
+            out = collections.OrderedDict((name, np.zeros(shape(name), dtype=known[name][2])) for name in names)
             ptrs = (C.c_void_p * max(n, 1))(*[out[name].ctypes.data for name in names])
-            r = lib.rtgpu_render_aovs(ctx, C.byref(params), ids, C.c_uint32(n), ptrs)
+            if chain is None:
+                r = lib.rtgpu_render_aovs(ctx, C.byref(params), ids, C.c_uint32(n), ptrs)
+            else:
+                r = lib.rtgpu_render_aovs_chain(ctx, C.byref(params), C.byref(chain_desc), ids, C.c_uint32(n), ptrs)
         else:
             import torch
             dev = torch.device("cuda", multi_info(ctx)["devices"][0])
-            raw = collections.OrderedDict((name, torch.empty(shape(name), dtype=torch.float32 if AOV_PLANES[name][2] is np.float32 else torch.int32, device=dev))
+            raw = collections.OrderedDict((name, torch.empty(shape(name), dtype=torch.float32 if known[name][2] is np.float32 else torch.int32, device=dev))
                                           for name in names)
             ptrs = (C.c_void_p * max(n, 1))(*[raw[name].data_ptr() for name in names])
-            r = _run_on_torch_stream(torch, self._query_streams, dev, raw.values(), lambda stream: lib.rtgpu_render_aovs_async(ctx, C.byref(params), ids, C.c_uint32(n), ptrs, stream))
+            if chain is None:
+                r = _run_on_torch_stream(torch, self._query_streams, dev, raw.values(), lambda stream: lib.rtgpu_render_aovs_async(ctx, C.byref(params), ids, C.c_uint32(n), ptrs, stream))
+            else:
+                r = _run_on_torch_stream(torch, self._query_streams, dev, raw.values(),
+                                         lambda stream: lib.rtgpu_render_aovs_chain_async(ctx, C.byref(params), C.byref(chain_desc), ids, C.c_uint32(n), ptrs, stream))
         if r != 0:
             err = (lib.rtgpu_last_error() or b"").decode()
             raise (ValueError if r == -1 else RuntimeError)("render_aovs failed (%d): %s" % (r, err))
         if device:
             out = collections.OrderedDict((name, t if t.dtype == torch.float32 else _u32(torch, t)) for name, t in raw.items())
         return out
+
+    def set_guide_chain(self, chain):
+        """chain=N (0..16): denoise() and denoise(variance=True) render their guides through render_aovs(chain=N) -- the surface seen in a mirror or through
+        glass steers the filter, not the mirror (rtgpu_set_guide_chain).  None: first hit, the default.  While a chain is set, denoise(temporal=True)
+        raises: reprojecting a reflection is not provided."""
+        ctx = self.device_context()
+        desc = RtAovChain(int(chain), 0) if chain is not None else None
+        if not ctx.value:
+            raise RuntimeError("set_guide_chain needs a renderer with a device context: call set_renderer first")
+        r = rtgpu_lib().rtgpu_set_guide_chain(ctx, C.byref(desc) if desc is not None else None)
+        if r != 0:
+            raise (ValueError if r == -1 else RuntimeError)("set_guide_chain failed (%d): %s" % (r, (rtgpu_lib().rtgpu_last_error() or b"").decode()))
 
     # ---- denoise (include/rtgpu.h: rtgpu_denoise / rtgpu_denoise_async, rtgpu_postprocess_from) ------------------------------------------------------
     def denoise(self, params, iterations=5, sigma_color=DENOISE_DEFAULTS["sigma_color"], sigma_normal=DENOISE_DEFAULTS["sigma_normal"],

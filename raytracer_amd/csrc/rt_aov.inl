@@ -4,6 +4,9 @@
 // turns that record into the planes the caller asked for.
 //   k_aov_pixels    slot i of the chunk = pixel firstPixel + i of the frame, row-major in sum-buffer coordinates (k_generate flips the film row)
 //   k_aov_resolve   Scene::EvaluateIntersection + Material::EvaluateShadingData of every hit -> channel-major planes
+//   k_aov_resolve_chain   the same body for rtgpu_render_aovs_chain: the slot holds its path's guide vertex (k_shade_chain, rt_shade_body.inl), whose depth and
+//                   previous material ride in the flags word of R_ORIGIN; it also writes the three chain planes.  The planes are resolved here, behind the
+//                   bounce loop, and not from inside the shade variant: slot i is pixel firstPixel + i, so the stores stay pixel-ordered and coalesced
 // Slot i of the arena is pixel firstPixel + i, so a wave's 64 stores to one channel of one plane are 256 consecutive bytes.
 
 __global__ void __launch_bounds__(RT_BLOCK) k_aov_pixels(uint32_t* __restrict__ slotPixel, uint32_t count, unsigned long long firstPixel, uint32_t width)
@@ -23,8 +26,10 @@ __global__ void __launch_bounds__(RT_BLOCK) k_aov_pixels(uint32_t* __restrict__ 
 
 // kLean: the scene class, as for the other shading kernels (rt_device_core.h): 0 = anything, 3 = anything without textures.
 // `mask` (bit = RtAovPlane) and the plane pointers are kernel arguments, so every `if (mask & ...)` below is a scalar branch.
-template <int kLean>
-__global__ void __launch_bounds__(RT_BLOCK) k_aov_resolve RT_K_AOV_RESOLVE_ARGS
+// kChain: the vertex is the slot's current one at whatever depth (false: the primary ray's); `plane`: AovOutputs::plane or AovChainOutputs::plane
+template <int kLean, bool kChain>
+__device__ __forceinline__ static void aovResolve(const RtSceneDesc& scene, const Paths& paths, uint32_t count, uint32_t mask, void* const* plane, size_t channelStride, size_t firstOut,
+                                                  const uint4* __restrict__ rayCounts)
 {
     const uint32_t i = blockIdx.x * RT_BLOCK + threadIdx.x;
     if (i >= count) return;
@@ -37,10 +42,14 @@ __global__ void __launch_bounds__(RT_BLOCK) k_aov_resolve RT_K_AOV_RESOLVE_ARGS
     for (int k = 0; k < 4; ++k) sd.intersection.frame.r[k] = zero4();
     sd.intersection.texCoord = zero4(); sd.intersection.material = RT_NO_MATERIAL;
     sd.mp.baseColor = zero4(); sd.mp.emission = zero4(); sd.mp.roughness = 0.0f; sd.mp.metalness = 0.0f; sd.mp.IoR = 0.0f;
+    // a chain's guide vertex: its depth, and the material of the vertex before it, which a finite light's evaluation still finds in IntersectionData::material
+    // (k_shade's rule, rt_shade_body.inl: that material's normal map is applied to the light's frame)
+    const uint32_t flags = kChain ? ubits(prec(paths, R_ORIGIN, i).w) : 0u;
     if (isHit && (mask & (RT_AOV_FRAME_PLANES | RT_AOV_MATERIAL_PLANES)) != 0u)
     {
         // the primary ray as k_generate left it (depth 0: no origin offset), the evaluation as DebugRenderer::RenderPixel and PathTracerMIS::RenderPixel run it
-        const Ray ray = makePathRay(prec(paths, R_ORIGIN, i), prec(paths, R_DIR, i), 0u);
+        const Ray ray = makePathRay(prec(paths, R_ORIGIN, i), prec(paths, R_DIR, i), kChain ? flags & 0xFFu : 0u);
+        if (kChain) sd.intersection.material = (flags >> 9) - 1u;   // 0 -> RT_NO_MATERIAL
         DiscardCounters cnt;
         if (hit.distance < FLT_MAX) sceneEvaluateIntersection<kLean>(scene, ray, hit, sd.intersection, cnt);
         // a finite light has no material (LightSceneObject::EvaluateIntersection leaves IntersectionData::material alone): its material planes stay 0
@@ -48,9 +57,9 @@ __global__ void __launch_bounds__(RT_BLOCK) k_aov_resolve RT_K_AOV_RESOLVE_ARGS
     }
 
     const size_t at = firstOut + i;
-    auto storeF = [&](uint32_t plane, uint32_t channel, float v) { ((float*)out.plane[plane])[(size_t)channel * channelStride + at] = v; };
-    auto storeU = [&](uint32_t plane, uint32_t v) { ((uint32_t*)out.plane[plane])[at] = v; };
-    auto store3 = [&](uint32_t plane, V4 v) { storeF(plane, 0u, v.x); storeF(plane, 1u, v.y); storeF(plane, 2u, v.z); };
+    auto storeF = [&](uint32_t id, uint32_t channel, float v) { ((float*)plane[id])[(size_t)channel * channelStride + at] = v; };
+    auto storeU = [&](uint32_t id, uint32_t v) { ((uint32_t*)plane[id])[at] = v; };
+    auto store3 = [&](uint32_t id, V4 v) { storeF(id, 0u, v.x); storeF(id, 1u, v.y); storeF(id, 2u, v.z); };
     if (mask & RT_AOV_BIT(RT_AOV_DEPTH)) storeF(RT_AOV_DEPTH, 0u, hit.distance);   // (+inf on a miss: the walks leave it in the record)
     if (mask & RT_AOV_BIT(RT_AOV_POSITION)) store3(RT_AOV_POSITION, sd.intersection.frame.r[3]);
     if (mask & RT_AOV_BIT(RT_AOV_NORMAL)) store3(RT_AOV_NORMAL, sd.intersection.frame.r[2]);
@@ -71,7 +80,14 @@ __global__ void __launch_bounds__(RT_BLOCK) k_aov_resolve RT_K_AOV_RESOLVE_ARGS
     if (mask & RT_AOV_BIT(RT_AOV_IOR)) storeF(RT_AOV_IOR, 0u, sd.mp.IoR);
     if (mask & RT_AOV_BIT(RT_AOV_OBJECT_ID)) storeU(RT_AOV_OBJECT_ID, hit.objectId);
     if (mask & RT_AOV_BIT(RT_AOV_SUB_OBJECT_ID)) storeU(RT_AOV_SUB_OBJECT_ID, isHit ? hit.subObjectId : 0u);
-    if (mask & RT_AOV_BIT(RT_AOV_MATERIAL)) storeU(RT_AOV_MATERIAL, sd.intersection.material);
+    if (mask & RT_AOV_BIT(RT_AOV_MATERIAL)) storeU(RT_AOV_MATERIAL, kChain && isLight ? RT_NO_MATERIAL : sd.intersection.material);
+    if (kChain)
+    {
+        if (mask & RT_AOV_BIT(RT_AOV_CHAIN_LENGTH)) storeU(RT_AOV_CHAIN_LENGTH, flags & 0xFFu);
+        // R_RESULT.x: the distances of the vertices passed, summed left to right by k_shade_chain (0 at depth 0)
+        if (mask & RT_AOV_BIT(RT_AOV_CHAIN_DISTANCE)) storeF(RT_AOV_CHAIN_DISTANCE, 0u, prec(paths, R_RESULT, i).x + hit.distance);
+        if (mask & RT_AOV_BIT(RT_AOV_CHAIN_THROUGHPUT)) { const float4 tp = prec(paths, R_TP, i); store3(RT_AOV_CHAIN_THROUGHPUT, V4(tp.x, tp.y, tp.z, 0.0f)); }
+    }
     if (rayCounts)
     {
         // the counting walk's record of this slot's ray (TravTuning::rayCounts): box tests, passed box tests, triangle tests, passed triangle tests
@@ -81,4 +97,16 @@ __global__ void __launch_bounds__(RT_BLOCK) k_aov_resolve RT_K_AOV_RESOLVE_ARGS
         if (mask & RT_AOV_BIT(RT_AOV_TRIANGLE_TESTS)) storeU(RT_AOV_TRIANGLE_TESTS, n.z);
         if (mask & RT_AOV_BIT(RT_AOV_TRIANGLE_TESTS_PASSED)) storeU(RT_AOV_TRIANGLE_TESTS_PASSED, n.w);
     }
+}
+
+template <int kLean>
+__global__ void __launch_bounds__(RT_BLOCK) k_aov_resolve RT_K_AOV_RESOLVE_ARGS
+{
+    aovResolve<kLean, false>(scene, paths, count, mask, out.plane, channelStride, firstOut, rayCounts);
+}
+
+template <int kLean>
+__global__ void __launch_bounds__(RT_BLOCK) k_aov_resolve_chain RT_K_AOV_RESOLVE_CHAIN_ARGS
+{
+    aovResolve<kLean, true>(scene, paths, count, mask, out.plane, channelStride, firstOut, nullptr);
 }

@@ -198,6 +198,7 @@ RTGPU_API void rtgpu_destroy(RtgpuContext* c)
     freeQuery(c);
     freeRecorder(c);
     freeAov(c);
+    freeChain(c);
     freeDenoise(c);
     freeScene(c); freeFilm(c);
     for (uint32_t i = 0; i < RT_MAX_LANES; ++i)

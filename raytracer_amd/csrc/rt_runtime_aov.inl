@@ -165,3 +165,187 @@ RTGPU_API int rtgpu_render_aovs_async(RtgpuContext* c, const RtPassParams* p, co
     HIP_TRY(hipEventRecord(c->aov.done, stream));
     return RTGPU_OK;
 }
+
+// ---- guide chains (include/rtgpu.h, rtgpu_render_aovs_chain; kernels: k_shade_chain, rt_shade_body.inl, and k_aov_resolve_chain, rt_aov.inl) ----------------------
+// The recorder's sequence (launchSlotBounces) over the chunking of the first-hit call: k_aov_pixels -> k_generate -> {trace with the walk the context renders with ->
+// k_shade_chain} per bounce -> k_aov_resolve_chain, all on the call's stream with device-side queue counts.  The last bounce, min(maxChain, maxRayDepth), is traced
+// and not shaded: every vertex at that depth stops, and a stop writes nothing.  So maxChain 0 launches what the first-hit call launches.
+static const uint32_t kAovChainChannels[RT_AOV_CHAIN_NUM_PLANES - RT_AOV_NUM_PLANES] = { 1, 1, 3 };
+static uint32_t aovChainChannels(uint32_t plane) { return plane < RT_AOV_NUM_PLANES ? kAovChannels[plane] : kAovChainChannels[plane - RT_AOV_NUM_PLANES]; }
+
+static int ensureChainArena(RtgpuContext* c, uint32_t pixels, uint32_t bounces, size_t stagedWordsPerPixel)
+{
+    RtgpuContext::Chain& a = c->chain;
+    BatchLane& l = a.lane;
+    if (!a.done) HIP_TRY(hipEventCreateWithFlags(&a.done, hipEventDisableTiming));
+    if (!a.counters) { HIP_TRY(hipMalloc((void**)&a.counters, 16 * sizeof(unsigned long long))); HIP_TRY(hipMemset(a.counters, 0, 16 * sizeof(unsigned long long))); }
+    if (!a.passDev) HIP_TRY(hipMalloc((void**)&a.passDev, sizeof(DevPass)));
+    if (!a.seedDev) HIP_TRY(hipMalloc((void**)&a.seedDev, (size_t)RTGPU_MAX_DIMENSIONS * sizeof(uint32_t)));
+    if (!a.ringHost)
+    {
+        HIP_TRY(hipHostMalloc((void**)&a.ringHost, RtgpuContext::Chain::kRing * kAovRingRecord, hipHostMallocDefault));
+        for (uint32_t i = 0; i < RtgpuContext::Chain::kRing; ++i) HIP_TRY(hipEventCreateWithFlags(&a.ringCopied[i], hipEventDisableTiming));
+    }
+    if (!l.paths.base || l.paths.capacity < pixels)
+    {
+        freeChainArena(c);   // (waits for the calls still using it)
+        devFree(a.staged); a.stagedWords = 0;
+        uint32_t cap = 65536u;   // in powers of two from 64 K, as the first-hit call's arena (`pixels` is a chunk at most)
+        while (cap < pixels) cap <<= 1;
+        { const int r = allocLanePaths(l, cap, 1u); if (r) return r; }   // k_shade_chain writes no next-event request
+        HIP_TRY(hipMalloc((void**)&a.slotPixel, (size_t)cap * sizeof(uint32_t)));
+    }
+    if (l.queueCountCapacity < bounces + 1u)
+    {
+        HIP_TRY(hipEventSynchronize(a.done));
+        devFree(l.queueCounts);
+        l.queueCountCapacity = bounces + 1u;
+        HIP_TRY(hipMalloc((void**)&l.queueCounts, laneCountBytes(l)));
+    }
+    const size_t stagedWords = stagedWordsPerPixel * l.paths.capacity;
+    if (a.stagedWords < stagedWords)
+    {
+        HIP_TRY(hipEventSynchronize(a.done));
+        devFree(a.staged); a.stagedWords = 0;
+        HIP_TRY(hipMalloc((void**)&a.staged, stagedWords * sizeof(uint32_t)));
+        a.stagedWords = stagedWords;
+    }
+    return RTGPU_OK;
+}
+
+// the launches of one chunk: pixels [firstPixel, firstPixel + n) of the frame (n <= the arena's capacity), on `stream`; lastDepth = min(maxChain, maxRayDepth)
+static int launchChainChunk(RtgpuContext* c, hipStream_t stream, unsigned long long firstPixel, uint32_t n, uint32_t maxChain, uint32_t lastDepth, uint32_t mask,
+                            const AovChainOutputs& out, size_t channelStride, size_t firstOut)
+{
+    RtgpuContext::Chain& a = c->chain;
+    BatchLane& l = a.lane;
+    const LaneCounts counts(l);
+    const dim3 block(RT_BLOCK), grid((n + RT_BLOCK - 1u) / RT_BLOCK);
+    HIP_TRY(hipMemsetAsync(l.queueCounts, 0, laneCountBytes(l), stream));
+    hipLaunchKernelGGL(k_aov_pixels, grid, block, 0, stream, a.slotPixel, n, firstPixel, c->width);
+    // one pass, so a pass holds all `n` slots: slot / slotsPerPass = 0 for every slot
+    hipLaunchKernelGGL(k_generate, grid, block, 0, stream, c->sceneDev, a.passDev, n, l.paths, a.slotPixel, n, l.queues[0], counts.pathCounts + 0, a.counters);
+    launchSlotBounces(c, stream, a.counters, l, counts, lastDepth, lastDepth, false, [&](uint32_t depth)
+    {
+        if (depth == lastDepth) return;   // every vertex of the last bounce stops
+        hipLaunchKernelGGL((k_shade_chain<false, false>), grid, block, 0, stream, c->sceneDev, a.passDev, n, l.paths, l.queues[depth & 1u], counts.pathCounts + depth,
+                           l.queues[(depth + 1u) & 1u], counts.pathCounts + depth + 1, (uint32_t*)nullptr, (uint32_t*)nullptr, a.counters, maxChain);
+    });
+    if (c->leanScene == 1 || c->leanScene == 3) hipLaunchKernelGGL((k_aov_resolve_chain<3>), grid, block, 0, stream, c->sceneDev, l.paths, n, mask, out, channelStride, firstOut);
+    else hipLaunchKernelGGL((k_aov_resolve_chain<0>), grid, block, 0, stream, c->sceneDev, l.paths, n, mask, out, channelStride, firstOut);
+    HIP_TRY(hipGetLastError());
+    return RTGPU_OK;
+}
+
+// argument rules shared by both entry points, in the order of checkAovs; `mask`: bit = requested plane (RtAovPlane, then RtAovChainPlane)
+static int checkAovsChain(RtgpuContext* c, const RtPassParams* p, const RtAovChain* chain, const uint32_t* planes, uint32_t numPlanes, void* const* outputs, uint32_t& mask)
+{
+    mask = 0u;
+    if (!c) return fail(RTGPU_ERR_INVALID_ARGUMENT, "NULL context");
+    if (!chain) return fail(RTGPU_ERR_INVALID_ARGUMENT, "NULL chain");
+    if (chain->maxChain > RT_AOV_CHAIN_MAX) return fail(RTGPU_ERR_INVALID_ARGUMENT, "maxChain must be 0..16");
+    if (chain->flags != 0u) return fail(RTGPU_ERR_INVALID_ARGUMENT, "RtAovChain::flags must be 0");
+    if (numPlanes == 0) return RTGPU_OK;
+    if (!p || !planes || !outputs) return fail(RTGPU_ERR_INVALID_ARGUMENT, "NULL argument");
+    for (uint32_t k = 0; k < numPlanes; ++k)
+    {
+        if (planes[k] >= RT_AOV_CHAIN_NUM_PLANES) return fail(RTGPU_ERR_INVALID_ARGUMENT, "plane " + std::to_string(k) + ": unknown plane " + std::to_string(planes[k]));
+        if (planes[k] < RT_AOV_NUM_PLANES && ((1u << planes[k]) & RT_AOV_COST_PLANES))
+            return fail(RTGPU_ERR_INVALID_ARGUMENT, "plane " + std::to_string(k) + ": the cost planes describe one traversal and have no chain form");
+        if (mask & (1u << planes[k])) return fail(RTGPU_ERR_INVALID_ARGUMENT, "plane " + std::to_string(k) + ": plane " + std::to_string(planes[k]) + " is requested twice");
+        if (!outputs[k]) return fail(RTGPU_ERR_INVALID_ARGUMENT, "plane " + std::to_string(k) + ": NULL output buffer");
+        mask |= 1u << planes[k];
+    }
+    return checkPass(c, p);
+}
+
+// what both entry points do before their chunk loop (beginAovs' steps on the chain's own state)
+static int beginAovsChain(RtgpuContext* c, const RtPassParams* p, hipStream_t stream, uint32_t lastDepth, size_t stagedWordsPerPixel, uint32_t& chunk)
+{
+    const size_t pixels = (size_t)c->width * c->height;
+    chunk = knobs::aovChunk();
+    if (chunk > pixels) chunk = (uint32_t)pixels;
+    int r = ensureChainArena(c, chunk, lastDepth + 1u, stagedWordsPerPixel); if (r) return r;
+    RtgpuContext::Chain& a = c->chain;
+    HIP_TRY(hipStreamWaitEvent(stream, a.done, 0));   // the arena is shared with the previous call, whatever its stream
+    const uint32_t ring = a.ringCursor; a.ringCursor = (a.ringCursor + 1u) % RtgpuContext::Chain::kRing;
+    HIP_TRY(hipEventSynchronize(a.ringCopied[ring]));   // (a fresh event is complete)
+    char* record = a.ringHost + (size_t)ring * kAovRingRecord;
+    DevPass pass;
+    makeDevPass(c, p, pass);
+    pass.seed = a.seedDev;
+    memcpy(record, &pass, sizeof(pass));
+    if (p->numDimensions) memcpy(record + sizeof(DevPass), p->seed, (size_t)p->numDimensions * sizeof(uint32_t));
+    HIP_TRY(hipMemcpyAsync(a.passDev, record, sizeof(DevPass), hipMemcpyHostToDevice, stream));
+    if (p->numDimensions) HIP_TRY(hipMemcpyAsync(a.seedDev, record + sizeof(DevPass), (size_t)p->numDimensions * sizeof(uint32_t), hipMemcpyHostToDevice, stream));
+    HIP_TRY(hipEventRecord(a.ringCopied[ring], stream));
+    return RTGPU_OK;
+}
+
+RTGPU_API int rtgpu_render_aovs_chain(RtgpuContext* c, const RtPassParams* p, const RtAovChain* chain, const uint32_t* planes, uint32_t numPlanes, void* const* outputs)
+{
+    uint32_t mask = 0u;
+    int r = checkAovsChain(c, p, chain, planes, numPlanes, outputs, mask); if (r) return r;
+    if (numPlanes == 0) return RTGPU_OK;
+    uint32_t firstChannel[RT_AOV_CHAIN_NUM_PLANES], channels = 0u;
+    for (uint32_t k = 0; k < numPlanes; ++k) { firstChannel[k] = channels; channels += aovChainChannels(planes[k]); }
+    r = flushBeforeAovs(c); if (r) return r;
+    const QueryUntimed untimed(c);   // timing measures the render passes
+    hipStream_t stream = c->lanes[0].stream;
+    const uint32_t lastDepth = chain->maxChain < p->maxRayDepth ? chain->maxChain : p->maxRayDepth;
+    uint32_t chunk = 0u;
+    r = beginAovsChain(c, p, stream, lastDepth, channels, chunk); if (r) return r;
+    RtgpuContext::Chain& a = c->chain;
+    const size_t pixels = (size_t)c->width * c->height, capacity = a.lane.paths.capacity;
+    AovChainOutputs out;
+    for (uint32_t id = 0; id < RT_AOV_CHAIN_NUM_PLANES; ++id) out.plane[id] = nullptr;
+    for (uint32_t k = 0; k < numPlanes; ++k) out.plane[planes[k]] = a.staged + (size_t)firstChannel[k] * capacity;
+    for (size_t first = 0; first < pixels; first += chunk)
+    {
+        const uint32_t n = pixels - first < chunk ? (uint32_t)(pixels - first) : chunk;
+        r = launchChainChunk(c, stream, first, n, chain->maxChain, lastDepth, mask, out, capacity, 0u); if (r) return r;
+        HIP_TRY(hipStreamSynchronize(stream));
+        for (uint32_t k = 0; k < numPlanes; ++k)
+            for (uint32_t ch = 0; ch < aovChainChannels(planes[k]); ++ch)
+                HIP_TRY(rtMemcpy((uint32_t*)outputs[k] + (size_t)ch * pixels + first, a.staged + (size_t)(firstChannel[k] + ch) * capacity, (size_t)n * sizeof(uint32_t), hipMemcpyDeviceToHost));
+    }
+    HIP_TRY(hipEventRecord(a.done, stream));
+    return RTGPU_OK;
+}
+
+RTGPU_API int rtgpu_render_aovs_chain_async(RtgpuContext* c, const RtPassParams* p, const RtAovChain* chain, const uint32_t* planes, uint32_t numPlanes, void* const* outputs,
+                                            void* streamHandle)
+{
+    uint32_t mask = 0u;
+    int r = checkAovsChain(c, p, chain, planes, numPlanes, outputs, mask); if (r) return r;
+    if (numPlanes == 0) return RTGPU_OK;
+    for (uint32_t k = 0; k < numPlanes; ++k)
+        if ((uintptr_t)outputs[k] & 15u) return fail(RTGPU_ERR_INVALID_ARGUMENT, "plane " + std::to_string(k) + ": the output must be a 16-byte aligned device buffer");
+    r = flushBeforeAovs(c); if (r) return r;
+    const QueryUntimed untimed(c);
+    hipStream_t stream = streamHandle ? (hipStream_t)streamHandle : c->lanes[0].stream;
+    const uint32_t lastDepth = chain->maxChain < p->maxRayDepth ? chain->maxChain : p->maxRayDepth;
+    uint32_t chunk = 0u;
+    r = beginAovsChain(c, p, stream, lastDepth, 0u, chunk); if (r) return r;
+    const size_t pixels = (size_t)c->width * c->height;
+    AovChainOutputs out;
+    for (uint32_t id = 0; id < RT_AOV_CHAIN_NUM_PLANES; ++id) out.plane[id] = nullptr;
+    for (uint32_t k = 0; k < numPlanes; ++k) out.plane[planes[k]] = outputs[k];
+    for (size_t first = 0; first < pixels; first += chunk)
+    {
+        const uint32_t n = pixels - first < chunk ? (uint32_t)(pixels - first) : chunk;
+        r = launchChainChunk(c, stream, first, n, chain->maxChain, lastDepth, mask, out, pixels, first); if (r) return r;   // the planes are written in place
+    }
+    HIP_TRY(hipEventRecord(c->chain.done, stream));
+    return RTGPU_OK;
+}
+
+RTGPU_API int rtgpu_set_guide_chain(RtgpuContext* c, const RtAovChain* chain)
+{
+    if (!c) return fail(RTGPU_ERR_INVALID_ARGUMENT, "NULL context");
+    if (chain && chain->maxChain > RT_AOV_CHAIN_MAX) return fail(RTGPU_ERR_INVALID_ARGUMENT, "maxChain must be 0..16");
+    if (chain && chain->flags != 0u) return fail(RTGPU_ERR_INVALID_ARGUMENT, "RtAovChain::flags must be 0");
+    c->chain.guide = chain != nullptr;
+    c->chain.guideMaxChain = chain ? chain->maxChain : 0u;
+    return RTGPU_OK;
+}

@@ -307,6 +307,21 @@ struct RtgpuContext
         hipEvent_t done = nullptr;                // recorded behind every call: the next one (whatever its stream) and a new arena wait for it
     } aov;
 
+    // guide chains (rtgpu_render_aovs_chain): the slot-per-pixel bounce loop over a chunk of the frame's pixels with k_shade_chain, then k_aov_resolve_chain; arena,
+    // queues, work counts, counters, pass constants and staging of its own -- never a lane's, the recorder's or the first-hit call's
+    struct Chain
+    {
+        BatchLane lane;                           // arena (one request record pair per slot, never written), queues and work counts as a batch lane holds them
+        uint32_t* slotPixel = nullptr;            // slot -> pixel of the chunk (k_aov_pixels)
+        uint32_t* staged = nullptr; size_t stagedWords = 0;   // rtgpu_render_aovs_chain's device copy of a chunk's planes
+        unsigned long long* counters = nullptr;   // 16 x u64, never read
+        DevPass* passDev = nullptr; uint32_t* seedDev = nullptr;   // the pass whose paths are followed
+        static const uint32_t kRing = 4;          // pass constants and seeds travel as the first-hit call's do (Aov::ringHost)
+        char* ringHost = nullptr; hipEvent_t ringCopied[kRing] = { nullptr, nullptr, nullptr, nullptr }; uint32_t ringCursor = 0;
+        hipEvent_t done = nullptr;                // recorded behind every call: the next one (whatever its stream), a new arena and a new scene wait for it
+        bool guide = false; uint32_t guideMaxChain = 0;   // rtgpu_set_guide_chain: the frame step (beginFrame) renders its guides through the chain call
+    } chain;
+
     // the a-trous filter (rtgpu_filter_atrous, rtgpu_denoise; rt_runtime_denoise.inl): scratch of its own, grown on use, freed with the context
     struct Denoise
     {
@@ -411,6 +426,7 @@ static void waitQueries(RtgpuContext* c)
 {
     if (c->query.done) (void)hipEventSynchronize(c->query.done);
     if (c->aov.done) (void)hipEventSynchronize(c->aov.done);   // (an asynchronous AOV call walks the scene as a query does)
+    if (c->chain.done) (void)hipEventSynchronize(c->chain.done);
 }
 // A freed walk arena for `want` rays, in powers of two from 64 K: a caller whose batches grow slowly does not reallocate with every call
 static int growWalkArena(WalkArena& w, uint32_t want)
@@ -458,6 +474,26 @@ static void freeAov(RtgpuContext* c)
     if (a.ringHost) (void)hipHostFree(a.ringHost);
     a.ringHost = nullptr;
     for (uint32_t i = 0; i < RtgpuContext::Aov::kRing; ++i) { if (a.ringCopied[i]) (void)hipEventDestroy(a.ringCopied[i]); a.ringCopied[i] = nullptr; }
+    if (a.done) (void)hipEventDestroy(a.done);
+    a.done = nullptr;
+}
+
+static void freeChainArena(RtgpuContext* c)
+{
+    RtgpuContext::Chain& a = c->chain;
+    if (a.done) (void)hipEventSynchronize(a.done);
+    freePaths(a.lane);
+    devFree(a.slotPixel);
+}
+static void freeChain(RtgpuContext* c)
+{
+    RtgpuContext::Chain& a = c->chain;
+    freeChainArena(c);
+    devFree(a.staged, a.lane.queueCounts, a.counters, a.passDev, a.seedDev);
+    a.stagedWords = 0; a.lane.queueCountCapacity = 0;
+    if (a.ringHost) (void)hipHostFree(a.ringHost);
+    a.ringHost = nullptr;
+    for (uint32_t i = 0; i < RtgpuContext::Chain::kRing; ++i) { if (a.ringCopied[i]) (void)hipEventDestroy(a.ringCopied[i]); a.ringCopied[i] = nullptr; }
     if (a.done) (void)hipEventDestroy(a.done);
     a.done = nullptr;
 }

@@ -232,7 +232,7 @@ struct FrameStep
 
 // The checks of a frame call behind those of its parameter blocks; then every queued pass is in the sum buffer, `stream` stands behind the previous call, and the first
 // `guides` of depth, normal, position, base colour and object id are rendered on it: the first hits of the primary rays `guideParams` generates, through the AOV path
-// (its arena, never a lane's).  outHost or outDevice; outVariance (optional) is memory of the same kind, written with writesVariance only; outPlane (optional, beside
+// (its arena, never a lane's) -- or, under rtgpu_set_guide_chain, the guide vertices of the paths it generates, through the chain call.  outHost or outDevice; outVariance (optional) is memory of the same kind, written with writesVariance only; outPlane (optional, beside
 // outDevice only): one more device output of a float per pixel, held to the same rules
 static int beginFrame(RtgpuContext* c, const RtPassParams* guideParams, float* outHost, float* outDevice, float* outVariance, bool writesVariance, void* streamHandle,
                       uint32_t guides, uint32_t extraFloatsPerPixel, FrameStep& f, float* outPlane = nullptr)
@@ -271,6 +271,12 @@ static int beginFrame(RtgpuContext* c, const RtPassParams* guideParams, float* o
     f.variance = f.varianceHost ? f.out + 3u * plane : outVariance;
     const uint32_t planes[5] = { RT_AOV_DEPTH, RT_AOV_NORMAL, RT_AOV_POSITION, RT_AOV_BASE_COLOR, RT_AOV_OBJECT_ID };
     void* const outputs[5] = { f.depth, f.normal, f.position, f.albedo, f.id };
+    if (c->chain.guide)
+    {
+        // rtgpu_set_guide_chain: the same planes at the guide vertex of every pixel's path
+        const RtAovChain chain = { c->chain.guideMaxChain, 0u, { 0u, 0u } };
+        return rtgpu_render_aovs_chain_async(c, guideParams, &chain, planes, guides, outputs, f.stream);
+    }
     return rtgpu_render_aovs_async(c, guideParams, planes, guides, outputs, f.stream);
 }
 

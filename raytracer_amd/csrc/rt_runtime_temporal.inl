@@ -280,6 +280,8 @@ static int denoiseTemporalFrame(RtgpuContext* c, const RtTemporalParams* t, cons
     int r = checkTemporalParams(t, false); if (r) return r;
     if (v) { r = checkDenoiseVarParams(v); if (r) return r; }
     if (clip) { r = checkTemporalClip(clip); if (r) return r; }
+    // (before anything is submitted or the history touched) reprojecting a reflection needs the virtual motion of the mirrored point
+    if (c->chain.guide) return fail(RTGPU_ERR_UNSUPPORTED, "temporal accumulation does not reproject through a guide chain: clear it with rtgpu_set_guide_chain(ctx, NULL)");
     if (!clip) outConfidence = nullptr;
     const bool stagesConfidence = outConfidence && outHost;
     FrameStep f;

@@ -1,7 +1,7 @@
 // rt_shade.hip -- the shading kernels of the library, a translation unit of their own: PathTracerMIS / PathTracer / Debug shading over
 // slot-per-pixel and dense path state (rt_shade.inl with rt_shade_body.inl, rt_dense.inl: two layouts around ONE set of vertex stages, the mis* functions
 // of rt_shade.inl), the bidirectional integrator's kernels (rt_vcm.inl) and the
-// resolve kernel of rtgpu_render_aovs (rt_aov.inl).  The host side
+// resolve kernels of rtgpu_render_aovs and rtgpu_render_aovs_chain (rt_aov.inl).  The host side
 // (rt_runtime.hip) launches them through the declarations of rt_shade_kernels.h.
 //
 // Why its own unit: it is compiled with -mllvm -simplifycfg-sink-common=false.  SimplifyCFG's common-code sinking merges the stores that
@@ -27,6 +27,7 @@ RT_K_SHADE_DENSE_INSTANCES(RT_X)
 RT_K_SHADE_INSTANCES(RT_X)
 #undef RT_X
 template __global__ void __launch_bounds__(RT_BLOCK) k_shade_record<false, false> RT_K_SHADE_RECORD_ARGS;
+template __global__ void __launch_bounds__(RT_BLOCK) k_shade_chain<false, false> RT_K_SHADE_CHAIN_ARGS;
 #define RT_X(C) template __global__ void __launch_bounds__(RT_BLOCK) k_vcm_emit<C> RT_K_VCM_EMIT_ARGS; \
                 template __global__ void __launch_bounds__(RT_BLOCK) k_vcm_light_shade<C> RT_K_VCM_LIGHT_SHADE_ARGS; \
                 template __global__ void __launch_bounds__(RT_BLOCK) k_lt_shade<C> RT_K_VCM_LIGHT_SHADE_ARGS; \
@@ -34,5 +35,8 @@ template __global__ void __launch_bounds__(RT_BLOCK) k_shade_record<false, false
 RT_VCM_CLASSES(RT_X)
 #undef RT_X
 #define RT_X(C) template __global__ void __launch_bounds__(RT_BLOCK) k_aov_resolve<C> RT_K_AOV_RESOLVE_ARGS;
+RT_AOV_CLASSES(RT_X)
+#undef RT_X
+#define RT_X(C) template __global__ void __launch_bounds__(RT_BLOCK) k_aov_resolve_chain<C> RT_K_AOV_RESOLVE_CHAIN_ARGS;
 RT_AOV_CLASSES(RT_X)
 #undef RT_X

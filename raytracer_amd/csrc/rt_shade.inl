@@ -187,13 +187,15 @@ RT_DEV void flushAppendBuffer(const uint32_t* buf, uint32_t& count, uint32_t& ba
 }
 
 #ifndef RT_SHADE_FUNCTIONS_ONLY   // (rt_tail.hip takes the functions above and none of the kernels below)
-// k_shade, and rtgpu_record_paths' k_shade_record: ONE body (rt_shade_body.inl), compiled twice.  The recording blocks are preprocessor blocks, so
-// k_shade is the token stream it was before the recorder existed.
+// k_shade, rtgpu_record_paths' k_shade_record and rtgpu_render_aovs_chain's k_shade_chain: ONE body (rt_shade_body.inl), compiled three times.  The
+// recording and chain blocks are preprocessor blocks, so k_shade is the token stream it was before the recorder and the chain existed.
 #define RT_SHADE_KERNEL k_shade
 #define RT_SHADE_RECORDING 0
+#define RT_SHADE_CHAIN 0
 #include "rt_shade_body.inl"
 #undef RT_SHADE_KERNEL
 #undef RT_SHADE_RECORDING
+#undef RT_SHADE_CHAIN
 
 // ---- path records (include/rtgpu.h, rtgpu_record_paths; host side: rt_runtime_paths.inl) ------------------------------------------------------
 // The reference's PathDebugData hook (Core/Rendering/PathDebugging.h:27-53, filled at PathTracerMIS.cpp:377-410).  A slot's records are `stride`
@@ -223,9 +225,20 @@ RT_DEV void storePathVertex(float4* __restrict__ records, uint32_t stride, uint3
 }
 #define RT_SHADE_KERNEL k_shade_record
 #define RT_SHADE_RECORDING 1
+#define RT_SHADE_CHAIN 0
 #include "rt_shade_body.inl"
 #undef RT_SHADE_KERNEL
 #undef RT_SHADE_RECORDING
+#undef RT_SHADE_CHAIN
+
+// ---- guide chains (include/rtgpu.h, rtgpu_render_aovs_chain; host side: rt_runtime_aov.inl; the resolve: k_aov_resolve_chain, rt_aov.inl) ------
+#define RT_SHADE_KERNEL k_shade_chain
+#define RT_SHADE_RECORDING 0
+#define RT_SHADE_CHAIN 1
+#include "rt_shade_body.inl"
+#undef RT_SHADE_KERNEL
+#undef RT_SHADE_RECORDING
+#undef RT_SHADE_CHAIN
 
 // The end of a recording: folds the next-event results of every path's last vertex into its radiance (what k_accumulate does before it adds the
 // pixel) and writes the slot's RtPathInfo {numVertices, terminationReason, radiance[3], 0, 0, 0} as two float4.

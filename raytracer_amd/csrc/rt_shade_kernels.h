@@ -18,6 +18,11 @@
 #define RT_K_SHADE_RECORD_ARGS (const RtSceneDesc scene, const DevPass* __restrict__ passes, uint32_t slotsPerPass, const Paths paths, const uint32_t* __restrict__ queueIn, \
                                 const uint32_t* __restrict__ countIn, uint32_t* __restrict__ queueOut, uint32_t* __restrict__ countOut, uint32_t* __restrict__ shadowQueue, \
                                 uint32_t* __restrict__ shadowCount, unsigned long long* counters, float4* __restrict__ records, uint32_t recordStride)
+// rtgpu_render_aovs_chain's variant of k_shade (rt_shade_body.inl): the same arguments (the two next-event arguments are not read), then RtAovChain::maxChain.
+// One instantiation, the scene class "anything"
+#define RT_K_SHADE_CHAIN_ARGS (const RtSceneDesc scene, const DevPass* __restrict__ passes, uint32_t slotsPerPass, const Paths paths, const uint32_t* __restrict__ queueIn, \
+                               const uint32_t* __restrict__ countIn, uint32_t* __restrict__ queueOut, uint32_t* __restrict__ countOut, uint32_t* __restrict__ shadowQueue, \
+                               uint32_t* __restrict__ shadowCount, unsigned long long* counters, uint32_t maxChain)
 
 // rtgpu_render_aovs (rt_aov.inl): where each requested plane goes (indexed by RtAovPlane; null: not requested).  Channel c of pixel slot i lands at word
 // c * channelStride + firstOut + i of its plane.  Two scene classes, as the bidirectional integrator's kernels have: 0 = anything, 3 = no textures
@@ -25,6 +30,9 @@ struct AovOutputs { void* plane[RT_AOV_NUM_PLANES]; };
 #define RT_K_AOV_RESOLVE_ARGS (const RtSceneDesc scene, const Paths paths, uint32_t count, uint32_t mask, const AovOutputs out, size_t channelStride, size_t firstOut, \
                                const uint4* __restrict__ rayCounts)
 #define RT_AOV_CLASSES(X) X(0) X(3)
+// rtgpu_render_aovs_chain: the same for the slot's guide vertex; plane[] is indexed by RtAovPlane and, behind RT_AOV_NUM_PLANES, RtAovChainPlane
+struct AovChainOutputs { void* plane[RT_AOV_CHAIN_NUM_PLANES]; };
+#define RT_K_AOV_RESOLVE_CHAIN_ARGS (const RtSceneDesc scene, const Paths paths, uint32_t count, uint32_t mask, const AovChainOutputs out, size_t channelStride, size_t firstOut)
 
 // The bidirectional integrator's kernels that evaluate textures (normal maps, textured material parameters, an environment map) come in two scene
 // classes, as k_shade_dense does: 0 = anything, 3 = a scene without textures (rtgpu_upload_scene decides: RtgpuContext::leanScene 1 or 3).
@@ -43,6 +51,8 @@ __global__ void __launch_bounds__(RT_BLOCK) k_shade(const RtSceneDesc scene, con
                                                     unsigned long long* counters);
 template <bool kLean, bool kPlain = false>
 __global__ void __launch_bounds__(RT_BLOCK) k_shade_record RT_K_SHADE_RECORD_ARGS;
+template <bool kLean, bool kPlain = false>
+__global__ void __launch_bounds__(RT_BLOCK) k_shade_chain RT_K_SHADE_CHAIN_ARGS;
 __global__ void __launch_bounds__(RT_BLOCK) k_paths_finish(const Paths paths, uint32_t numSlots, const DevPass* __restrict__ passes, const float4* __restrict__ records,
                                                            uint32_t recordStride, float4* __restrict__ infos, unsigned long long* counters);
 __global__ void __launch_bounds__(RT_BLOCK) k_debug_shade(const RtSceneDesc scene, const Paths paths, const uint32_t* __restrict__ queueIn, const uint32_t* __restrict__ countIn,
@@ -53,6 +63,8 @@ __global__ void __launch_bounds__(RT_BLOCK) k_accumulate(const Paths paths, uint
 __global__ void __launch_bounds__(RT_BLOCK) k_aov_pixels(uint32_t* __restrict__ slotPixel, uint32_t count, unsigned long long firstPixel, uint32_t width);
 template <int kLean>
 __global__ void __launch_bounds__(RT_BLOCK) k_aov_resolve RT_K_AOV_RESOLVE_ARGS;
+template <int kLean>
+__global__ void __launch_bounds__(RT_BLOCK) k_aov_resolve_chain RT_K_AOV_RESOLVE_CHAIN_ARGS;
 __global__ void __launch_bounds__(RT_BLOCK) k_generate_dense(const RtSceneDesc scene, const DevPass* __restrict__ passes, uint32_t slotsPerPass, const Paths paths,
                                                              const uint32_t* __restrict__ slotPixel, uint32_t numSlots, uint32_t shardCapacity, uint32_t* __restrict__ counts,
                                                              unsigned long long* counters);

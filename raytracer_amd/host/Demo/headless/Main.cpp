@@ -4,7 +4,8 @@
 // GetFrontBuffer) and writes the tone-mapped front buffer as a BMP.  The extra options are --passes, --depth, --output, --seed and
 // --debug-pixel X,Y (prints the path behind that pixel of pass 0, what the reference's Demo shows for a picked pixel: Demo_UserInterface.cpp:197-272),
 // --denoise [N] (the frame goes through N levels, default 5, of the a-trous filter before it is tone-mapped: rtgpu_denoise, rtgpu_postprocess_from)
-// and --denoise-variance [N] (the same through the variance-guided filter over the film's two sum buffers: rtgpu_denoise_var);
+// and --denoise-variance [N] (the same through the variance-guided filter over the film's two sum buffers: rtgpu_denoise_var),
+// --guide-chain N beside either (the filter's guides follow every pixel's path through up to N mirror and glass vertices: rtgpu_set_guide_chain);
 // the environment variable RTGPU_DEVICES ("0,1,2,3" / "all") spreads the frame over several GPUs (Core/Rendering/Renderer.h).
 #include "../Demo.h"
 #include "../SceneLoader.h"
@@ -73,11 +74,18 @@ static bool PrintPixelPath(IRenderer* renderer, const RtPassParams& params, uint
 }
 
 // The front buffer of the frame after `levels` levels of the a-trous filter (rtgpu_denoise guided by the first hits of one more pass's primary rays,
-// then the viewport's post-process over the filtered image).  `variance`: rtgpu_denoise_var, the variance-guided filter
-static bool DenoisedFrontBuffer(Viewport& viewport, const Camera& camera, IRenderer* renderer, uint32 levels, bool variance, Bitmap& front)
+// then the viewport's post-process over the filtered image).  `variance`: rtgpu_denoise_var, the variance-guided filter.  guideChain >= 0: the guides are
+// those of the paths' guide vertices (rtgpu_set_guide_chain)
+static bool DenoisedFrontBuffer(Viewport& viewport, const Camera& camera, IRenderer* renderer, uint32 levels, bool variance, int guideChain, Bitmap& front)
 {
     PathTracerMIS* pt = dynamic_cast<PathTracerMIS*>(renderer);
     if (!pt || !pt->UploadScene()) { fprintf(stderr, "--denoise: the renderer has no device context\n"); return false; }
+    if (guideChain >= 0)
+    {
+        RtAovChain chain; memset(&chain, 0, sizeof(chain));
+        chain.maxChain = (uint32)guideChain;
+        if (rtgpu_set_guide_chain(pt->GetDeviceContext(), &chain) != RTGPU_OK) { fprintf(stderr, "--guide-chain: %s\n", rtgpu_last_error()); return false; }
+    }
     const uint32 w = viewport.GetWidth(), h = viewport.GetHeight(), passes = viewport.GetProgress().passesFinished ? viewport.GetProgress().passesFinished : 1u;
     RtPassParams guide;
     if (!viewport.NextPassParams(camera, guide)) return false;
@@ -109,7 +117,7 @@ int main(int argc, char* argv[])
 {
     uint32 width = 1280, height = 720, passes = 64, depth = 20;
     bool debugPixel = false; uint32 debugX = 0, debugY = 0;
-    uint32 denoiseLevels = 0; bool denoiseVariance = false;
+    uint32 denoiseLevels = 0; bool denoiseVariance = false; int guideChain = -1;
     std::string scenePath, rendererName = "Path Tracer MIS", output = "out.bmp";
     unsigned long long seed = 0; bool haveSeed = false;
     for (int i = 1; i < argc; ++i)
@@ -133,8 +141,14 @@ int main(int argc, char* argv[])
             if (i + 1 < argc && argv[i + 1][0] >= '0' && argv[i + 1][0] <= '9') denoiseLevels = (uint32)atoi(argv[++i]);
             if (denoiseLevels < 1 || denoiseLevels > 8) { fprintf(stderr, "%s takes 1..8 levels\n", a.c_str()); return 2; }
         }
-        else { fprintf(stderr, "usage: rt_demo -s scene.json [--data dir/] [-w W] [-h H] [--passes N] [--depth D] [--renderer name] [--output out.bmp] [--seed N] [--debug-pixel X,Y] [--denoise [N]] [--denoise-variance [N]]\n"); return 2; }
+        else if (a == "--guide-chain")
+        {
+            guideChain = atoi(value("--guide-chain"));
+            if (guideChain < 0 || guideChain > (int)RT_AOV_CHAIN_MAX) { fprintf(stderr, "--guide-chain takes 0..%u vertices\n", RT_AOV_CHAIN_MAX); return 2; }
+        }
+        else { fprintf(stderr, "usage: rt_demo -s scene.json [--data dir/] [-w W] [-h H] [--passes N] [--depth D] [--renderer name] [--output out.bmp] [--seed N] [--debug-pixel X,Y] [--denoise [N]] [--denoise-variance [N]] [--guide-chain N]\n"); return 2; }
     }
+    if (guideChain >= 0 && !denoiseLevels) { fprintf(stderr, "--guide-chain steers the denoiser's guides: it needs --denoise or --denoise-variance\n"); return 2; }
     if (scenePath.empty()) { fprintf(stderr, "no scene given (-s scene.json)\n"); return 2; }
 
     Scene scene;
@@ -169,8 +183,9 @@ int main(int argc, char* argv[])
            (double)counters.numRays / seconds / 1.0e6, (unsigned long long)counters.numRays, (unsigned long long)counters.numShadowRays,
            (double)viewport.GetProgress().averageError);
     Bitmap denoised;
-    if (denoiseLevels && !DenoisedFrontBuffer(viewport, camera, renderer.get(), denoiseLevels, denoiseVariance, denoised)) return 1;
+    if (denoiseLevels && !DenoisedFrontBuffer(viewport, camera, renderer.get(), denoiseLevels, denoiseVariance, guideChain, denoised)) return 1;
     if (denoiseLevels) printf("denoised: %u levels of the %sa-trous filter\n", denoiseLevels, denoiseVariance ? "variance-guided " : "");
+    if (denoiseLevels && guideChain >= 0) printf("guides: chains of at most %d mirror and glass vertices\n", guideChain);
     if (!SaveBMP(output.c_str(), denoiseLevels ? denoised : viewport.GetFrontBuffer())) { fprintf(stderr, "cannot write %s\n", output.c_str()); return 1; }
     printf("wrote %s\n", output.c_str());
     return 0;

@@ -395,6 +395,17 @@ def sponza_class(aspect, target_triangles=262144, seed=7, textured=False, extra_
     return scene, camera
 
 
+def add_mirror_props(scene):
+    """What the stock Sponza-class scene lacks for the guide-chain tools (tools/bench_aovs.py, tools/bench_denoise.py --mirror): a smooth-metal rect across the nave,
+    facing sponza_class()'s camera, and a glass sphere beside it.  Rebuilds the scene."""
+    mirror = scene.add_material("metal", (0.95, 0.93, 0.9))
+    glass = scene.add_material("dielectric", (1.0, 1.0, 1.0))
+    scene.add_rect((3.0, 2.5), transform_from_euler((-3.0, 3.0, 0.0), (0.0, -90.0, 0.0)), mirror)
+    scene.add_sphere(1.2, transform_from_euler((-7.0, 1.2, 2.5)), glass)
+    scene.build()
+    return scene
+
+
 def box_mesh(half=1.0):
     """12-triangle box mesh with per-face normals / tangents / uvs (the fixture sketched, commented out, at
     Tests/RaytracingTests.cpp:68-239)."""

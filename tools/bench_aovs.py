@@ -8,7 +8,11 @@ Timing, after a warm-up (arena growth, code objects), `--reps` repetitions (medi
 its device work (AOVs: the call, then a synchronise of its stream; Debug: render, then rtgpu_synchronize), so the three compare like for like, launch and
 Python overhead included on every side.  The AOV calls also report `device_ms_median`: device events around the call on its stream, a second loop.
 
-  python tools/bench_aovs.py [--reps 20]"""
+--chain N: instead, the guide-chain call (rtgpu_render_aovs_chain_async through Viewport.render_aovs(chain=N, device=True)) beside the first-hit call of the
+same run and the same planes -- the denoiser's four guides, and every non-cost plane -- on the stock scene, which has no specular surface (every pixel stops at
+its first hit: the cost of the early stop), and with --mirror on the scene with a smooth-metal rect and a glass sphere added (scenes.add_mirror_props).
+
+  python tools/bench_aovs.py [--reps 20] [--chain 3 [--mirror]]"""
 import argparse
 import json
 import os
@@ -52,16 +56,47 @@ def summary(ms, pixels):
     return {"ms_median": med, "ms_min": float(ms.min()), "ms_max": float(ms.max()), "mpixels_per_s": pixels / med / 1e3}
 
 
+def chain_beside_first_hit(args, torch, ra, scenes):
+    w, h = args.width, args.height
+    out = {"width": w, "height": h, "reps": args.reps, "max_chain": args.chain, "max_ray_depth": 6}
+    guides = ("depth", "normal", "position", "base_color")
+    non_cost = tuple(n for n in ra.AOV_PLANES if not n.endswith(("tests", "tests_passed")))
+    stream = torch.cuda.Stream()
+    for label in ("stock", "mirror") if args.mirror else ("stock",):
+        scene, camera = scenes.sponza_class(w / h)
+        if label == "mirror":
+            scenes.add_mirror_props(scene)
+        vp = ra.Viewport(w, h, seed=1234, max_ray_depth=6, min_russian_roulette_depth=args.chain)   # (roulette never cuts a chain)
+        vp.set_renderer(scene)
+        p = vp.next_pass_params(camera)
+        res = {"triangles": int(scene.desc.contents.numTriangles)}
+        with torch.cuda.stream(stream):
+            length = vp.render_aovs(p, ("chain_length",), device=True, chain=args.chain)["chain_length"]
+            res["pixels_with_chain"] = int((length >= 1).sum().item())
+            for name, planes in (("guides", guides), ("all_non_cost", non_cost)):
+                first = lambda: vp.render_aovs(p, planes, device=True)   # noqa: E731
+                chain = lambda: vp.render_aovs(p, planes, device=True, chain=args.chain)   # noqa: E731
+                a, b = np.median(time_call(torch, first, args.reps)), np.median(time_call(torch, chain, args.reps))
+                res[name] = {"planes": len(planes), "first_hit_device_ms_median": float(a), "chain_device_ms_median": float(b), "chain_over_first_hit": float(b / a)}
+        out[label] = res
+    return out
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--reps", type=int, default=20)
     ap.add_argument("--width", type=int, default=1920)
     ap.add_argument("--height", type=int, default=1080)
+    ap.add_argument("--chain", type=int, default=None)
+    ap.add_argument("--mirror", action="store_true")
     args = ap.parse_args()
     import torch
     import raytracer_amd as ra
     from raytracer_amd import scenes
     w, h = args.width, args.height
+    if args.chain is not None:
+        print(json.dumps(chain_beside_first_hit(args, torch, ra, scenes)))
+        return
     scene, camera = scenes.sponza_class(w / h)
     vp = ra.Viewport(w, h, seed=1234, max_ray_depth=6)
     vp.set_renderer(scene)

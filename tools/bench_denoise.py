@@ -14,7 +14,13 @@ what the 25-tap gather achieves against the traffic a perfect cache would leave,
 
 The tiled / direct A/B: the same command under RTGPU_DENOISE_TILED=0 and =1 (the knob is read once per process), alternating.
 
-  python tools/bench_denoise.py [--reps 20] [--output profiles/denoise_bench_1080p.json]"""
+--chain N: instead, what guide chains (Viewport.set_guide_chain(N)) do to the filtered frame: for --passes passes, the relative mean squared error
+mean((x - r)^2 / (r^2 + 1e-2)) of the frame against the tool's converged render r (--converged passes of the same scene), over the pixels with
+chain_length >= 1 and over the rest, unfiltered, filtered with first-hit guides and filtered with chain guides (five levels, the wrappers' default sigmas, plain
+and variance-guided), and the time of one denoise call either way.  --mirror adds a smooth-metal rect and a glass sphere (scenes.add_mirror_props): the stock scene
+has no specular surface.
+
+  python tools/bench_denoise.py [--reps 20] [--output profiles/denoise_bench_1080p.json] [--chain 3 --mirror [--converged 1024]]"""
 import argparse
 import json
 import os
@@ -43,6 +49,49 @@ def time_call(torch, fn, reps):
     return {"ms_median": float(np.median(ms)), "ms_min": float(ms.min()), "ms_max": float(ms.max())}
 
 
+def chain_quality(args, torch, ra, scenes):
+    w, h = args.width, args.height
+    scene, camera = scenes.sponza_class(w / h, args.triangles)
+    if args.mirror:
+        scenes.add_mirror_props(scene)
+    vp = ra.Viewport(w, h, seed=1234, max_ray_depth=args.depth)
+    vp.set_renderer(scene)
+    vp.render(camera, passes=args.passes)
+    guide = vp.next_pass_params(camera)
+    # the guides' own params: the frame's, with roulette pushed behind the chain so that it never cuts one (include/rtgpu.h)
+    guide.minRussianRouletteDepth = max(int(guide.minRussianRouletteDepth), args.chain)
+    noisy = vp.sum_buffer() / np.float32(vp.passes_finished)
+    length = vp.render_aovs(guide, ("chain_length",), chain=args.chain)["chain_length"]
+    frames = {"unfiltered": noisy}
+    times = {}
+    stream = torch.cuda.Stream()
+    for label, chain in (("first_hit", None), ("chain", args.chain)):
+        vp.set_guide_chain(chain)
+        frames[label] = vp.denoise(guide)
+        frames[label + "_variance"] = vp.denoise(guide, variance=True)
+        with torch.cuda.stream(stream):
+            times[label] = time_call(torch, lambda: vp.denoise(guide, device=True), args.reps)
+    vp.set_guide_chain(None)
+    ref_vp = ra.Viewport(w, h, seed=4321, max_ray_depth=args.depth)
+    ref_vp.set_renderer(scene)
+    ref_vp.render(camera, passes=args.converged)
+    ref = ref_vp.sum_buffer() / np.float32(ref_vp.passes_finished)
+    inside = length >= 1
+    # the chain pixels by what the primary ray hit: a metal (the mirror: one event per vertex) or a dielectric (the sphere: reflect or refract by the pass's draw)
+    first_material = vp.render_aovs(guide, ("material",))["material"]
+    desc = scene.desc.contents
+    kind_of = np.array([desc.materials[m].bsdf for m in range(desc.numMaterials)] + [0], dtype=np.uint32)
+    first_kind = kind_of[np.minimum(first_material, desc.numMaterials)]
+    metal, glass = inside & (first_kind == ra.BSDF_NAMES.index("metal")), inside & (first_kind == ra.BSDF_NAMES.index("dielectric"))
+    rel = lambda x, mask: float(np.mean(((x[mask] - ref[mask]) ** 2) / (ref[mask] ** 2 + 1e-2)))   # noqa: E731
+    out = {"scene": "sponza_class" + ("+mirror_props" if args.mirror else ""), "width": w, "height": h, "passes": vp.passes_finished, "converged_passes": args.converged,
+           "max_chain": args.chain, "depth": args.depth, "pixels_with_chain": int(inside.sum()), "metal_pixels": int(metal.sum()), "glass_pixels": int(glass.sum()), "denoise_ms": times, "relative_mse": {}}
+    for label, x in frames.items():
+        out["relative_mse"][label] = {"chain_pixels": rel(x, inside) if inside.any() else None, "metal_pixels": rel(x, metal) if metal.any() else None,
+                                      "glass_pixels": rel(x, glass) if glass.any() else None, "other_pixels": rel(x, ~inside)}
+    return out
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--reps", type=int, default=20)
@@ -52,11 +101,21 @@ def main():
     ap.add_argument("--depth", type=int, default=8)
     ap.add_argument("--triangles", type=int, default=262144)
     ap.add_argument("--output", default=None)
+    ap.add_argument("--chain", type=int, default=None)
+    ap.add_argument("--mirror", action="store_true")
+    ap.add_argument("--converged", type=int, default=1024)
     args = ap.parse_args()
     import torch
     import raytracer_amd as ra
     from raytracer_amd import scenes
     w, h = args.width, args.height
+    if args.chain is not None:
+        line = json.dumps(chain_quality(args, torch, ra, scenes))
+        print(line)
+        if args.output:
+            with open(args.output, "w") as f:
+                f.write(line + "\n")
+        return
     scene, camera = scenes.sponza_class(w / h, args.triangles)
     vp = ra.Viewport(w, h, seed=1234, max_ray_depth=args.depth)
     vp.set_renderer(scene)
