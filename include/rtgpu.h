@@ -766,8 +766,10 @@ int rtgpu_render_aovs_async(RtgpuContext* ctx, const RtPassParams* params, const
  * guide planes take 0.93 ms against the first-hit call's 0.57 where nothing is specular, 1.82 against 0.74 with a mirror and a glass sphere over a sixth of the frame.
  * At 16 passes the plain filter's relative MSE inside the mirror is 0.187 with chain guides against 0.216 without; under the variance-guided filter chain guides
  * measure worse (mirror 0.088 against 0.029, glass sphere 1.78 against 0.035).
- * Scope: temporal reprojection through a chain needs the virtual motion of the mirrored point and is not provided.  On glass one pass's
- * guides pick reflect or refract per pixel by the pass's own draw while the colour averages both; a deterministic choice is not provided.
+ * Scope: temporal reprojection through a chain needs the virtual motion of the mirrored point: rtgpu_render_aovs_virtual and
+ * rtgpu_denoise_temporal_chain (below) provide it, taking their chain as an argument; the entries under rtgpu_set_guide_chain still refuse.  On glass one
+ * pass's guides pick reflect or refract per pixel by the pass's own draw while the colour averages both; a deterministic choice is not provided, so on glass
+ * per-pixel chain lengths differ from frame to frame and most glass pixels start in the chained temporal call.
  * --------------------------------------------------------------------------------------------- */
 #define RT_AOV_CHAIN_MAX 16u
 typedef enum RtAovChainPlane {
@@ -784,6 +786,31 @@ int rtgpu_render_aovs_chain(RtgpuContext* ctx, const RtPassParams* params, const
 int rtgpu_render_aovs_chain_async(RtgpuContext* ctx, const RtPassParams* params, const RtAovChain* chain, const uint32_t* planes,
                                   uint32_t numPlanes, void* const* outputs, void* stream);
 int rtgpu_set_guide_chain(RtgpuContext* ctx, const RtAovChain* chain /* NULL: first hit, the default */);
+
+/* ---------------------------------------------------------------------------------------------
+ * The virtual position: where the guide vertex of a chain appears to be.  A point seen through plane mirrors appears at its virtual image, which lies
+ * on the primary ray at the unfolded path length and does not depend on the camera: projected through another camera it lands on the pixel where that
+ * camera sees the same reflected surface point.  This is the point temporal accumulation reprojects inside a reflection (the next sections).
+ * rtgpu_render_aovs_virtual[_async] are rtgpu_render_aovs_chain[_async] in every respect -- arguments, rules, errors, and the bits of every plane the
+ * chain call knows -- and accept plane ids below RT_AOV_VIRTUAL_NUM_PLANES; the chain call keeps refusing RT_AOV_VIRTUAL_POSITION as unknown.
+ *   RT_AOV_VIRTUAL_POSITION  3 f32.  For a pixel let o and w be the origin and the direction of its primary ray as generated (RtPathVertex words 0..2 and
+ *              3..5 of vertex 0: lens sample and distortion included), k its RT_AOV_CHAIN_LENGTH and D its RT_AOV_CHAIN_DISTANCE.
+ *                - D == +inf (the guide vertex is a miss): 0, 0, 0, as POSITION is.
+ *                - k == 0: the words of the POSITION plane.
+ *                - otherwise, per channel c:   V_c = o_c + w_c * D   -- the multiply rounded, then the add rounded, never fused.
+ *   scope      exact for any number of plane mirrors.  Behind a curved mirror or a refraction it is an approximation of where the surface appears; the
+ *              per-tap surface test of temporal accumulation, run on the chain guides, is what catches the cases where it fails.
+ * --------------------------------------------------------------------------------------------- */
+typedef enum RtAovVirtualPlane {
+    RT_AOV_VIRTUAL_POSITION = RT_AOV_CHAIN_NUM_PLANES,   /* 3 f32 */
+    RT_AOV_VIRTUAL_NUM_PLANES
+} RtAovVirtualPlane;
+/* Host pointers; synchronous. */
+int rtgpu_render_aovs_virtual(RtgpuContext* ctx, const RtPassParams* params, const RtAovChain* chain, const uint32_t* planes, uint32_t numPlanes,
+                              void* const* outputs);
+/* Device pointers (16-byte aligned) on `stream`, as rtgpu_render_aovs_async. */
+int rtgpu_render_aovs_virtual_async(RtgpuContext* ctx, const RtPassParams* params, const RtAovChain* chain, const uint32_t* planes,
+                                    uint32_t numPlanes, void* const* outputs, void* stream);
 
 /* ---------------------------------------------------------------------------------------------
  * Denoise: an edge-avoiding a-trous wavelet filter (Dammertz et al. 2010) over a rendered frame, guided by the first-hit planes
@@ -1084,6 +1111,79 @@ int rtgpu_denoise_temporal_clip(RtgpuContext* ctx, const RtTemporalParams* param
                                 float* outRGB, float* outVariance, const RtTemporalClip* clip, float* outConfidence);
 int rtgpu_denoise_temporal_clip_async(RtgpuContext* ctx, const RtTemporalParams* params, const RtDenoiseVarParams* filter, const RtPassParams* guideParams,
                                       float* outRGB, float* outVariance, const RtTemporalClip* clip, float* outConfidence, void* stream);
+
+/* ---------------------------------------------------------------------------------------------
+ * Temporal accumulation over chain guides: reflections in the history.  With first-hit guides every pixel inside a mirror reprojects the mirror's own plane,
+ * which stands still while the reflected image slides under a moving camera; the surface tests pass (the same mirror, normal and id), and the history blends
+ * last frame's reflection into this frame's at the wrong place.  The remedy is the one ReBLUR and ReLAX use for specular motion: reproject the virtual image
+ * (RT_AOV_VIRTUAL_POSITION above), test the taps on the chain guides -- the reflected surface stands still in world space -- and keep histories of different
+ * chain lengths apart.  Everything not restated here is rtgpu_temporal_accumulate_clip; tests/temporal_chain_ref.py is the same text in NumPy float32.
+ *   inputs     normal, position, depth, albedo and objectId are chain guides, at the guide vertex (rtgpu_render_aovs_chain).  RtTemporalChain adds this frame's
+ *              virtualPosition 3 x H x W f32 (V), chainLength 1 x H x W u32 (k), chainDistance 1 x H x W f32 (D), and the previous frame's prevChainLength
+ *              1 x H x W u32, required exactly when a history is given.  Chain lengths are at most RT_AOV_CHAIN_MAX, as the chain call writes them; the planes are
+ *              not range-checked, and a length of 0xFFFFFFFF is undefined here (in the moments it reads as an invalid pixel).  clip may be NULL: no clipping, outConfidence is not written.  objects may be NULL
+ *              with numObjects == 0.
+ *   project    uses V_p in P_p's place; outMotion is therefore the virtual motion.
+ *   tolerance  planeTolerance * chainDistance_p replaces planeTolerance * depth_p, in the taps and in the moments: inside a reflection the last segment's
+ *              length is the wrong scale.  For k == 0 the two are the same word.
+ *   taps       a tap is taken iff the conditions of the call without hold -- over N_p, P_p and the ids of the guide planes -- and prevChainLength_q ==
+ *              chainLength_p: a surface seen directly and the same surface seen in a tinted mirror do not share a colour history.
+ *   moments    a window pixel counts iff the conditions of the call without hold (validity: chainDistance_q finite, which is depth_q finite) and
+ *              chainLength_q == chainLength_p.
+ *   moving     when objects != NULL a pixel with chainLength_p > 0 starts; a pixel with chainLength_p == 0 follows the moving rules unchanged: it projects
+ *              P' (made from P_p, not from V_p) and tests its taps against P' and N'.
+ *   the rest   validity, prepare, blend, clip, anti-lag and the outputs are unchanged.  What the caller keeps as the next history are the current guides and
+ *              chainLength.
+ *   identity   with chainLength and prevChainLength all zero, virtualPosition the words of position and chainDistance the words of depth, every output is the
+ *              words of rtgpu_temporal_accumulate_clip; with clip == NULL, of rtgpu_temporal_accumulate[_moving].
+ *   scope      plane mirrors, any number of them: exact.  Curved mirrors and refraction: V is an approximation, fenced by the tap tests -- where it fails the
+ *              pixel starts.  The virtual image of a scene in which something moved, possibly the mirror, is not followed: dropping the history there costs
+ *              noise, keeping it would ghost.  On glass a pass's guides pick reflect or refract per pixel by the pass's own draw, so per-pixel chain lengths
+ *              differ from frame to frame and most glass pixels start.
+ *   errors     those of rtgpu_temporal_accumulate_clip, except that clip == NULL is allowed; and RTGPU_ERR_INVALID_ARGUMENT for: chain NULL; any of its three
+ *              current planes NULL; prevChainLength given without a history, or missing beside one; the _async entry: any of these planes violating the
+ *              alignment or overlap rules.
+ * rtgpu_denoise_temporal_chain is by definition rtgpu_render_aovs_virtual -- the DEPTH, NORMAL, POSITION, BASE_COLOR, OBJECT_ID, CHAIN_LENGTH, CHAIN_DISTANCE
+ * and VIRTUAL_POSITION planes of guideParams under `chain` -- followed by the pure entry on the same planes and then the filter: the composition
+ * rtgpu_denoise_temporal_clip is, over chain planes.  It takes its chain from its argument: rtgpu_set_guide_chain does not affect it (and the entries without
+ * keep answering RTGPU_ERR_UNSUPPORTED while one is set).  With chain->maxChain == 0 its outputs are the words of rtgpu_denoise_temporal_clip.  The motion
+ * table is built as that call builds it and passed only when an update happened since the history was stored; pixels with k > 0 then start for that frame.
+ * The chain length travels in the free lane of the {P, .} history record -- the entries without write 0.0f there, which is k = 0 bit for bit -- so the
+ * history stays 128 bytes per pixel, and a history the entries without wrote is valid input here.  The other way round it is not: the context remembers that
+ * the stored history was written by this entry, and rtgpu_denoise_temporal[_clip][_async] then treat it as no history (every pixel starts) and overwrite it.
+ * Multi-device, shard, active-block, stream and "not a pass" rules are those of rtgpu_denoise_temporal_clip.
+ * Measured (one MI355X, one run; Sponza-class 1920 x 1080 with a mirror and a glass sphere, maxChain 3, 2 passes a frame, 16 frames of 0.25 degrees of yaw;
+ * tools/bench_temporal.py --chain 3 --mirror --clip): the mirror's pixels keep a mean history length of 15.6 (1 % start in the last frame), the
+ * glass sphere's 8.3 (20 % start).  The pure entry (timed as a call: pack and kernels) takes 0.158 ms against 0.148 for the entry without on the same planes (clipped 0.315 against
+ * 0.302), the whole call 2.65 ms against rtgpu_denoise_temporal's 1.48 (1.69 against 1.32 where nothing is specular): the guide render through the chain call.  By relative MSE the
+ * call does NOT beat the call with first-hit guides: inside the mirror 0.097 against 0.048 filtered (clipped 0.052 against 0.040; at 1 degree a frame 0.069 against
+ * 0.053), on the glass sphere 1.09 against 0.10.  The variance-guided filter over chain guides loses what the history gains (unfiltered and unclipped the mirror
+ * reads 0.19 against 0.43), and at two passes a frame the measure does not see the ghost the first-hit history drags along.
+ * --------------------------------------------------------------------------------------------- */
+typedef struct RtTemporalChain {   /* 32 bytes */
+    const float*    virtualPosition;   /* 3 x H x W: RT_AOV_VIRTUAL_POSITION */
+    const uint32_t* chainLength;       /* 1 x H x W: RT_AOV_CHAIN_LENGTH */
+    const float*    chainDistance;     /* 1 x H x W: RT_AOV_CHAIN_DISTANCE */
+    const uint32_t* prevChainLength;   /* 1 x H x W: the previous frame's chainLength; NULL exactly when there is no history */
+} RtTemporalChain;
+int rtgpu_temporal_accumulate_chain(RtgpuContext* ctx, const RtTemporalParams* params, uint32_t width, uint32_t height, const float* color,
+                                    const float* colorHalf, const float* depth, const float* normal, const float* position, const float* albedo,
+                                    const uint32_t* objectId, const float* prevA, const float* prevB, const float* prevLength, const float* prevDepth,
+                                    const float* prevNormal, const float* prevPosition, const uint32_t* prevObjectId, float* outA, float* outB,
+                                    float* outLength, float* outMotion, const RtObjectMotion* objects, uint32_t numObjects,
+                                    const RtTemporalClip* clip /* NULL: none */, float* outConfidence, const RtTemporalChain* chain);
+int rtgpu_temporal_accumulate_chain_async(RtgpuContext* ctx, const RtTemporalParams* params, uint32_t width, uint32_t height, const float* color,
+                                          const float* colorHalf, const float* depth, const float* normal, const float* position, const float* albedo,
+                                          const uint32_t* objectId, const float* prevA, const float* prevB, const float* prevLength,
+                                          const float* prevDepth, const float* prevNormal, const float* prevPosition, const uint32_t* prevObjectId,
+                                          float* outA, float* outB, float* outLength, float* outMotion, const RtObjectMotion* objects,
+                                          uint32_t numObjects, const RtTemporalClip* clip, float* outConfidence, const RtTemporalChain* chain, void* stream);
+int rtgpu_denoise_temporal_chain(RtgpuContext* ctx, const RtTemporalParams* params, const RtDenoiseVarParams* filter, const RtPassParams* guideParams,
+                                 const RtAovChain* chain, float* outRGB, float* outVariance, const RtTemporalClip* clip /* NULL: none */,
+                                 float* outConfidence);
+int rtgpu_denoise_temporal_chain_async(RtgpuContext* ctx, const RtTemporalParams* params, const RtDenoiseVarParams* filter,
+                                       const RtPassParams* guideParams, const RtAovChain* chain, float* outRGB, float* outVariance,
+                                       const RtTemporalClip* clip, float* outConfidence, void* stream);
 
 /* rtgpu_postprocess over a caller's image (host memory, height x width x 3 floats of the context's size) in place of the sum buffer -- a
  * denoised frame, say: the same kernels, the same restrictions, and the same bits for the same input. */

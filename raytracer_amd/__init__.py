@@ -50,6 +50,8 @@ def rtgpu_lib():
         _rtgpu.rtgpu_render_aovs_chain.argtypes, _rtgpu.rtgpu_render_aovs_chain.restype = chain_args, C.c_int
         _rtgpu.rtgpu_render_aovs_chain_async.argtypes, _rtgpu.rtgpu_render_aovs_chain_async.restype = chain_args + [C.c_void_p], C.c_int
         _rtgpu.rtgpu_set_guide_chain.argtypes, _rtgpu.rtgpu_set_guide_chain.restype = [C.c_void_p, C.c_void_p], C.c_int
+        _rtgpu.rtgpu_render_aovs_virtual.argtypes, _rtgpu.rtgpu_render_aovs_virtual.restype = chain_args, C.c_int
+        _rtgpu.rtgpu_render_aovs_virtual_async.argtypes, _rtgpu.rtgpu_render_aovs_virtual_async.restype = chain_args + [C.c_void_p], C.c_int
     return _rtgpu
 
 
@@ -236,6 +238,8 @@ AOV_CHAIN_PLANES = collections.OrderedDict(
     (name, (len(AOV_PLANES) + i, channels, dtype)) for i, (name, channels, dtype) in enumerate((
         ("chain_length", 1, np.uint32), ("chain_distance", 1, np.float32), ("chain_throughput", 3, np.float32))))
 AOV_CHAIN_MAX = 16
+# RtAovVirtualPlane (include/rtgpu.h): the plane of rtgpu_render_aovs_virtual alone, behind AOV_CHAIN_PLANES' ids
+AOV_VIRTUAL_PLANES = {"virtual_position": (22, 3, np.float32)}
 
 
 class RtAovChain(C.Structure):
@@ -323,7 +327,7 @@ _filter_streams = {}
 
 def _image_planes(planes, shapes):
     """The planes (a dict name -> array, "color" first) of atrous_filter / temporal_accumulate held to `shapes` (name -> the shapes allowed): float32 NumPy arrays,
-    or contiguous float32 tensors on the colour's ROCm device; a plane named *object_id holds uint32 words, or int32 / int64 in a tensor.  Returns the planes as the
+    or contiguous float32 tensors on the colour's ROCm device; a plane named *object_id or *chain_length holds uint32 words, or int32 / int64 in a tensor.  Returns the planes as the
     library reads them (contiguous arrays; int64 ids narrowed to int32), ptr(a name of theirs, an array or None), empty(shape) for an output of their kind, the device
     index (0 for NumPy arrays) and the torch module (None for NumPy arrays)."""
     torch = None
@@ -332,7 +336,7 @@ def _image_planes(planes, shapes):
         on_gpu = isinstance(planes["color"], torch.Tensor) and planes["color"].is_cuda
         device = planes["color"].device if on_gpu else None
     for name, a in list(planes.items()):
-        ids = name.endswith("object_id")
+        ids = name.endswith("object_id") or name.endswith("chain_length")
         if torch is None:
             ok = isinstance(a, np.ndarray) and a.dtype == (np.uint32 if ids else np.float32)
         elif not ids:
@@ -477,6 +481,13 @@ class RtTemporalClip(C.Structure):
 TEMPORAL_CLIP_DEFAULTS = dict(radius=3, gamma=1.0, min_count=9)
 
 
+class RtTemporalChain(C.Structure):
+    _fields_ = [("virtualPosition", C.c_void_p), ("chainLength", C.c_void_p), ("chainDistance", C.c_void_p), ("prevChainLength", C.c_void_p)]
+
+
+CHAIN_KEYS = ("virtual_position", "chain_length", "chain_distance")
+
+
 def temporal_clip(clip):
     """The RtTemporalClip of a wrapper's `clip` argument: None (no clip: None comes back), True (TEMPORAL_CLIP_DEFAULTS) or a dict with any of radius, gamma and
     min_count, the rest at their defaults.  The library checks the ranges."""
@@ -495,7 +506,7 @@ def temporal_clip(clip):
 def temporal_accumulate(color, color_half, depth, normal, position, albedo=None, object_id=None, history=None, prev_world_to_screen=None, prev_sample_offset=(0.0, 0.0),
                         alpha_min=TEMPORAL_DEFAULTS["alpha_min"], max_history=TEMPORAL_DEFAULTS["max_history"], normal_threshold=TEMPORAL_DEFAULTS["normal_threshold"],
                         plane_tolerance=TEMPORAL_DEFAULTS["plane_tolerance"], color_scale=1.0, demodulate=True, return_motion=False, ctx=None, object_motion=None,
-                        clip=None, return_confidence=False):
+                        clip=None, return_confidence=False, chain=None):
     """Temporal accumulation of include/rtgpu.h over a frame: color, color_half (H, W, 3) -- Viewport.sum_buffer(secondary=True) --, depth (H, W) or (1, H, W),
     normal, position, albedo (3, H, W) float32 and object_id (H, W) or (1, H, W) uint32 (optional) -- Viewport.render_aovs() --, as NumPy arrays or as
     contiguous torch tensors on a ROCm device (object_id: the int64 tensor render_aovs(device=True) returns, or int32 words), then on
@@ -509,10 +520,19 @@ def temporal_accumulate(color, color_half, depth, normal, position, albedo=None,
     moved at all; NumPy arrays whichever way the frame comes.  Both id planes are required with it.
     clip=True or a dict (temporal_clip): the reprojected history is clipped to this frame's local colour statistics and its length cut by how far it was pulled
     (rtgpu_temporal_accumulate_clip), with or without object_motion; return_confidence=True then appends the (H, W) confidence plane -- 1 where nothing clipped
-    -- to what is returned."""
+    -- to what is returned.
+    chain=dict(virtual_position=(3, H, W) float32, chain_length=(H, W) or (1, H, W) uint32 (or the int64 tensor render_aovs returns), chain_distance=(H, W) or
+    (1, H, W) float32) -- Viewport.render_aovs(chain=N) --: the guides are chain guides (rtgpu_temporal_accumulate_chain): the virtual position is reprojected,
+    the plane tolerance scales with the chain distance, and histories of different chain lengths stay apart; with object_motion a pixel with a chain starts.
+    With or without clip and object_motion.  The returned history then carries chain_length, which a history passed beside chain must have."""
     clip = temporal_clip(clip)
     if return_confidence and clip is None:
         raise ValueError("return_confidence=True needs clip")
+    if chain is not None:
+        if not isinstance(chain, dict) or set(chain) != set(CHAIN_KEYS):
+            raise ValueError("chain must be a dict with the keys virtual_position, chain_length and chain_distance")
+        if history is not None and history.get("chain_length") is None:
+            raise ValueError("chain needs a history with chain_length: one a call with chain returned")
     table = None
     if object_motion is not None:
         table = object_motion_table(object_motion)
@@ -535,6 +555,10 @@ def temporal_accumulate(color, color_half, depth, normal, position, albedo=None,
                 planes["prev_" + key] = history[key]
         if ("object_id" in planes) != ("prev_object_id" in planes):
             raise ValueError("the object test needs both id planes: give object_id and a history with one, or neither")
+        if chain is not None:
+            planes["prev_chain_length"] = history["chain_length"]
+    if chain is not None:
+        planes.update(chain)
     if getattr(color, "ndim", 0) != 3 or color.shape[2] != 3:
         raise ValueError("color must be an (H, W, 3) float32 array or tensor")
     h, w = int(color.shape[0]), int(color.shape[1])
@@ -542,7 +566,7 @@ def temporal_accumulate(color, color_half, depth, normal, position, albedo=None,
     # (in the order of the entry's arguments)
     shapes = dict(color=image, color_half=image, depth=one, normal=three, position=three, albedo=three, object_id=one, prev_a=image, prev_b=image, prev_length=one,
                   prev_depth=one, prev_normal=three, prev_position=three, prev_object_id=one)
-    planes, ptr, empty, index, torch = _image_planes(planes, shapes)
+    planes, ptr, empty, index, torch = _image_planes(planes, dict(shapes, virtual_position=three, chain_length=one, chain_distance=one, prev_chain_length=one))
     p = temporal_params(alpha_min, max_history, normal_threshold, plane_tolerance, color_scale, demodulate, prev_world_to_screen if history is not None else None,
                         prev_sample_offset)
     out = dict(a=empty((h, w, 3)), b=empty((h, w, 3)), length=empty((h, w)))
@@ -554,13 +578,19 @@ def temporal_accumulate(color, color_half, depth, normal, position, albedo=None,
         with torch.cuda.device(index):
             table = torch.from_numpy(table.view(np.int32)).to(color.device)   # (ordered on the current stream, which the side stream waits for)
     moving = [ptr(table), C.c_uint32(0 if table is None else table.shape[0])]
-    if clip is not None:
+    if chain is not None:
+        block = RtTemporalChain(*[ptr(name) for name in CHAIN_KEYS + ("prev_chain_length",)])
+        _image_call(torch, index, "temporal_accumulate", ctx, "rtgpu_temporal_accumulate_chain",
+                    args + moving + [C.byref(clip) if clip is not None else None, ptr(confidence), C.byref(block)], tensors + [table])
+    elif clip is not None:
         _image_call(torch, index, "temporal_accumulate", ctx, "rtgpu_temporal_accumulate_clip", args + moving + [C.byref(clip), ptr(confidence)], tensors + [table])
     elif table is None:
         _image_call(torch, index, "temporal_accumulate", ctx, "rtgpu_temporal_accumulate", args, tensors)
     else:
         _image_call(torch, index, "temporal_accumulate", ctx, "rtgpu_temporal_accumulate_moving", args + moving, tensors + [table])
     out.update(depth=planes["depth"], normal=planes["normal"], position=planes["position"], object_id=planes.get("object_id"))
+    if chain is not None:
+        out["chain_length"] = planes["chain_length"]
     extras = ((motion,) if return_motion else ()) + ((confidence,) if return_confidence else ())
     return (out,) + extras if extras else out
 
@@ -1121,18 +1151,21 @@ class Viewport:
         nothing and is not a pass.  A Camera is not accepted, for the reason record_paths gives.
         chain=N (0..16, rtgpu_render_aovs_chain): the planes at the guide vertex of every pixel's path instead -- the first vertex that is not a
         specular event of a mirror or glass material, at most N vertices in -- and the AOV_CHAIN_PLANES beside them; the cost planes have no chain
-        form.  chain=None is the first-hit call."""
+        form.  With chain=N the name "virtual_position" (AOV_VIRTUAL_PLANES, rtgpu_render_aovs_virtual) is accepted too: where the guide vertex
+        appears to be along the primary ray, the point temporal accumulation reprojects inside a reflection.  chain=None is the first-hit call."""
         if not isinstance(params, RtPassParams):
             raise TypeError("render_aovs takes the RtPassParams of next_pass_params(camera), not %s" % type(params).__name__)
         names = [planes] if isinstance(planes, str) else list(planes)
-        known = AOV_PLANES if chain is None else collections.OrderedDict(list(AOV_PLANES.items()) + list(AOV_CHAIN_PLANES.items()))
+        known = AOV_PLANES if chain is None else collections.OrderedDict(list(AOV_PLANES.items()) + list(AOV_CHAIN_PLANES.items()) + list(AOV_VIRTUAL_PLANES.items()))
         for name in names:
             if name not in known:
-                if name in AOV_CHAIN_PLANES:
+                if name in AOV_CHAIN_PLANES or name in AOV_VIRTUAL_PLANES:
                     raise ValueError("AOV plane %r needs chain=N" % (name,))
                 raise ValueError("unknown AOV plane %r (AOV_PLANES lists them)" % (name,))
         if chain is not None:
             chain_desc = RtAovChain(int(chain), 0)
+            # the virtual entry only where its plane is asked for
+            chain_entry = "rtgpu_render_aovs_virtual" if any(name in AOV_VIRTUAL_PLANES for name in names) else "rtgpu_render_aovs_chain"
         if not self.has_renderer:
             raise RuntimeError("render_aovs needs a renderer: call set_renderer first")
         ctx = self.device_context()
@@ -1149,7 +1182,7 @@ class Viewport:
             if chain is None:
                 r = lib.rtgpu_render_aovs(ctx, C.byref(params), ids, C.c_uint32(n), ptrs)
             else:
-                r = lib.rtgpu_render_aovs_chain(ctx, C.byref(params), C.byref(chain_desc), ids, C.c_uint32(n), ptrs)
+                r = getattr(lib, chain_entry)(ctx, C.byref(params), C.byref(chain_desc), ids, C.c_uint32(n), ptrs)
         else:
             import torch
             dev = torch.device("cuda", multi_info(ctx)["devices"][0])
@@ -1160,7 +1193,7 @@ class Viewport:
                 r = _run_on_torch_stream(torch, self._query_streams, dev, raw.values(), lambda stream: lib.rtgpu_render_aovs_async(ctx, C.byref(params), ids, C.c_uint32(n), ptrs, stream))
             else:
                 r = _run_on_torch_stream(torch, self._query_streams, dev, raw.values(),
-                                         lambda stream: lib.rtgpu_render_aovs_chain_async(ctx, C.byref(params), C.byref(chain_desc), ids, C.c_uint32(n), ptrs, stream))
+                                         lambda stream: getattr(lib, chain_entry + "_async")(ctx, C.byref(params), C.byref(chain_desc), ids, C.c_uint32(n), ptrs, stream))
         if r != 0:
             err = (lib.rtgpu_last_error() or b"").decode()
             raise (ValueError if r == -1 else RuntimeError)("render_aovs failed (%d): %s" % (r, err))
@@ -1171,7 +1204,7 @@ class Viewport:
     def set_guide_chain(self, chain):
         """chain=N (0..16): denoise() and denoise(variance=True) render their guides through render_aovs(chain=N) -- the surface seen in a mirror or through
         glass steers the filter, not the mirror (rtgpu_set_guide_chain).  None: first hit, the default.  While a chain is set, denoise(temporal=True)
-        raises: reprojecting a reflection is not provided."""
+        raises: the call that reprojects a reflection takes its chain as an argument, denoise(temporal=True, chain=N)."""
         ctx = self.device_context()
         desc = RtAovChain(int(chain), 0) if chain is not None else None
         if not ctx.value:
@@ -1185,7 +1218,7 @@ class Viewport:
                 sigma_plane=DENOISE_DEFAULTS["sigma_plane"], color_scale=None, demodulate=True, device=False, variance=False,
                 sigma_lum=DENOISE_VAR_DEFAULTS["sigma_lum"], variance_floor=DENOISE_VAR_DEFAULTS["variance_floor"], return_variance=False, temporal=False,
                 alpha_min=TEMPORAL_DEFAULTS["alpha_min"], max_history=TEMPORAL_DEFAULTS["max_history"], normal_threshold=TEMPORAL_DEFAULTS["normal_threshold"],
-                plane_tolerance=TEMPORAL_DEFAULTS["plane_tolerance"], clip=None, return_confidence=False):
+                plane_tolerance=TEMPORAL_DEFAULTS["plane_tolerance"], clip=None, return_confidence=False, chain=None):
         """The frame rendered so far through the a-trous filter of include/rtgpu.h, guided by the depth, normal, position and base-colour planes of the pass
         `params` (an RtPassParams from next_pass_params(), as render_aovs takes it): the (H, W, 3) float32 image, sum_buffer() * color_scale filtered.
         color_scale defaults to 1 / max(1, passes_finished).  device=True: a torch tensor on the renderer's ROCm device, produced on
@@ -1200,8 +1233,13 @@ class Viewport:
         or the history is looked up through the camera's old place.
         clip=True or a dict (temporal_clip), with temporal=True: the history is clipped to this frame's local colour statistics (rtgpu_denoise_temporal_clip) --
         the remedy for lighting that changed under a surface; clip=None is the call without, word for word.  return_confidence=True then appends the (H, W)
-        confidence plane to what is returned."""
+        confidence plane to what is returned.
+        chain=N (0..16), with temporal=True (rtgpu_denoise_temporal_chain): the guides are the chain guides render_aovs(chain=N) renders and the history is
+        reprojected through mirrors and glass by the virtual position; with or without clip.  The chain is this call's own: set_guide_chain does not affect it.
+        chain=None is the call without, word for word -- its refusal under set_guide_chain included."""
         clip = temporal_clip(clip)
+        if chain is not None and not temporal:
+            raise ValueError("chain needs temporal=True (set_guide_chain steers the calls without a history)")
         if clip is not None and not temporal:
             raise ValueError("clip needs temporal=True")
         if return_confidence and clip is None:
@@ -1239,7 +1277,11 @@ class Viewport:
         out, out_variance = empty(self.height, self.width, 3), empty(self.height, self.width) if return_variance else None
         out_confidence = empty(self.height, self.width) if return_confidence else None
         args = (ctx,) + leading + (C.byref(params), ptr(out)) + ((ptr(out_variance),) if temporal or variance else ())
-        if clip is not None:
+        if chain is not None:
+            chain_desc = RtAovChain(int(chain), 0)
+            entry, args = "rtgpu_denoise_temporal_chain", (ctx,) + leading + (C.byref(params), C.byref(chain_desc), ptr(out), ptr(out_variance),
+                                                                                C.byref(clip) if clip is not None else None, ptr(out_confidence))
+        elif clip is not None:
             entry, args = "rtgpu_denoise_temporal_clip", args + (C.byref(clip), ptr(out_confidence))
         if not device:
             r = getattr(lib, entry)(*args)

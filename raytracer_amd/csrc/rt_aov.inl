@@ -5,7 +5,7 @@
 //   k_aov_pixels    slot i of the chunk = pixel firstPixel + i of the frame, row-major in sum-buffer coordinates (k_generate flips the film row)
 //   k_aov_resolve   Scene::EvaluateIntersection + Material::EvaluateShadingData of every hit -> channel-major planes
 //   k_aov_resolve_chain   the same body for rtgpu_render_aovs_chain: the slot holds its path's guide vertex (k_shade_chain, rt_shade_body.inl), whose depth and
-//                   previous material ride in the flags word of R_ORIGIN; it also writes the three chain planes.  The planes are resolved here, behind the
+//                   previous material ride in the flags word of R_ORIGIN; it also writes the three chain planes and, for rtgpu_render_aovs_virtual, the virtual position.  The planes are resolved here, behind the
 //                   bounce loop, and not from inside the shade variant: slot i is pixel firstPixel + i, so the stores stay pixel-ordered and coalesced
 // Slot i of the arena is pixel firstPixel + i, so a wave's 64 stores to one channel of one plane are 256 consecutive bytes.
 
@@ -45,7 +45,8 @@ __device__ __forceinline__ static void aovResolve(const RtSceneDesc& scene, cons
     // a chain's guide vertex: its depth, and the material of the vertex before it, which a finite light's evaluation still finds in IntersectionData::material
     // (k_shade's rule, rt_shade_body.inl: that material's normal map is applied to the light's frame)
     const uint32_t flags = kChain ? ubits(prec(paths, R_ORIGIN, i).w) : 0u;
-    if (isHit && (mask & (RT_AOV_FRAME_PLANES | RT_AOV_MATERIAL_PLANES)) != 0u)
+    // (the virtual position of a pixel whose path passes nothing is its POSITION)
+    if (isHit && (mask & (RT_AOV_FRAME_PLANES | RT_AOV_MATERIAL_PLANES | (kChain ? RT_AOV_BIT(RT_AOV_VIRTUAL_POSITION) : 0u))) != 0u)
     {
         // the primary ray as k_generate left it (depth 0: no origin offset), the evaluation as DebugRenderer::RenderPixel and PathTracerMIS::RenderPixel run it
         const Ray ray = makePathRay(prec(paths, R_ORIGIN, i), prec(paths, R_DIR, i), kChain ? flags & 0xFFu : 0u);
@@ -87,6 +88,20 @@ __device__ __forceinline__ static void aovResolve(const RtSceneDesc& scene, cons
         // R_RESULT.x: the distances of the vertices passed, summed left to right by k_shade_chain (0 at depth 0)
         if (mask & RT_AOV_BIT(RT_AOV_CHAIN_DISTANCE)) storeF(RT_AOV_CHAIN_DISTANCE, 0u, prec(paths, R_RESULT, i).x + hit.distance);
         if (mask & RT_AOV_BIT(RT_AOV_CHAIN_THROUGHPUT)) { const float4 tp = prec(paths, R_TP, i); store3(RT_AOV_CHAIN_THROUGHPUT, V4(tp.x, tp.y, tp.z, 0.0f)); }
+        if (mask & RT_AOV_BIT(RT_AOV_VIRTUAL_POSITION))
+        {
+            // the point on the primary ray at the unfolded path length: o + w * D, a rounded multiply and a rounded add, spelled out (the library is built with
+            // -ffp-contract=off; the two intrinsics say the same where it counts).  o and w: what k_shade_chain left in R_SH_P / R_SH_TP when vertex 0 was passed; never written for k == 0, never read then
+            const float distance = prec(paths, R_RESULT, i).x + hit.distance;
+            V4 v = sd.intersection.frame.r[3];
+            if ((flags & 0xFFu) != 0u)
+            {
+                const float4 o = prec(paths, R_SH_P, i), w = prec(paths, R_SH_TP, i);
+                v = V4(__fadd_rn(o.x, __fmul_rn(w.x, distance)), __fadd_rn(o.y, __fmul_rn(w.y, distance)), __fadd_rn(o.z, __fmul_rn(w.z, distance)), 0.0f);
+            }
+            if ((ubits(distance) & 0x7FFFFFFFu) == 0x7F800000u) v = zero4();   // a miss
+            store3(RT_AOV_VIRTUAL_POSITION, v);
+        }
     }
     if (rayCounts)
     {

@@ -166,11 +166,11 @@ RTGPU_API int rtgpu_render_aovs_async(RtgpuContext* c, const RtPassParams* p, co
     return RTGPU_OK;
 }
 
-// ---- guide chains (include/rtgpu.h, rtgpu_render_aovs_chain; kernels: k_shade_chain, rt_shade_body.inl, and k_aov_resolve_chain, rt_aov.inl) ----------------------
+// ---- guide chains (include/rtgpu.h, rtgpu_render_aovs_chain and rtgpu_render_aovs_virtual; kernels: k_shade_chain, rt_shade_body.inl, and k_aov_resolve_chain, rt_aov.inl) ----------------------
 // The recorder's sequence (launchSlotBounces) over the chunking of the first-hit call: k_aov_pixels -> k_generate -> {trace with the walk the context renders with ->
 // k_shade_chain} per bounce -> k_aov_resolve_chain, all on the call's stream with device-side queue counts.  The last bounce, min(maxChain, maxRayDepth), is traced
 // and not shaded: every vertex at that depth stops, and a stop writes nothing.  So maxChain 0 launches what the first-hit call launches.
-static const uint32_t kAovChainChannels[RT_AOV_CHAIN_NUM_PLANES - RT_AOV_NUM_PLANES] = { 1, 1, 3 };
+static const uint32_t kAovChainChannels[RT_AOV_VIRTUAL_NUM_PLANES - RT_AOV_NUM_PLANES] = { 1, 1, 3, 3 };   // RtAovChainPlane, then RtAovVirtualPlane
 static uint32_t aovChainChannels(uint32_t plane) { return plane < RT_AOV_NUM_PLANES ? kAovChannels[plane] : kAovChainChannels[plane - RT_AOV_NUM_PLANES]; }
 
 static int ensureChainArena(RtgpuContext* c, uint32_t pixels, uint32_t bounces, size_t stagedWordsPerPixel)
@@ -237,8 +237,10 @@ static int launchChainChunk(RtgpuContext* c, hipStream_t stream, unsigned long l
     return RTGPU_OK;
 }
 
-// argument rules shared by both entry points, in the order of checkAovs; `mask`: bit = requested plane (RtAovPlane, then RtAovChainPlane)
-static int checkAovsChain(RtgpuContext* c, const RtPassParams* p, const RtAovChain* chain, const uint32_t* planes, uint32_t numPlanes, void* const* outputs, uint32_t& mask)
+// argument rules shared by the entry points, in the order of checkAovs; `mask`: bit = requested plane (RtAovPlane, then RtAovChainPlane, then RtAovVirtualPlane);
+// numKnown: RT_AOV_CHAIN_NUM_PLANES for the chain entries, RT_AOV_VIRTUAL_NUM_PLANES for rtgpu_render_aovs_virtual[_async]
+static int checkAovsChain(RtgpuContext* c, const RtPassParams* p, const RtAovChain* chain, const uint32_t* planes, uint32_t numPlanes, void* const* outputs, uint32_t& mask,
+                          uint32_t numKnown)
 {
     mask = 0u;
     if (!c) return fail(RTGPU_ERR_INVALID_ARGUMENT, "NULL context");
@@ -249,7 +251,7 @@ static int checkAovsChain(RtgpuContext* c, const RtPassParams* p, const RtAovCha
     if (!p || !planes || !outputs) return fail(RTGPU_ERR_INVALID_ARGUMENT, "NULL argument");
     for (uint32_t k = 0; k < numPlanes; ++k)
     {
-        if (planes[k] >= RT_AOV_CHAIN_NUM_PLANES) return fail(RTGPU_ERR_INVALID_ARGUMENT, "plane " + std::to_string(k) + ": unknown plane " + std::to_string(planes[k]));
+        if (planes[k] >= numKnown) return fail(RTGPU_ERR_INVALID_ARGUMENT, "plane " + std::to_string(k) + ": unknown plane " + std::to_string(planes[k]));
         if (planes[k] < RT_AOV_NUM_PLANES && ((1u << planes[k]) & RT_AOV_COST_PLANES))
             return fail(RTGPU_ERR_INVALID_ARGUMENT, "plane " + std::to_string(k) + ": the cost planes describe one traversal and have no chain form");
         if (mask & (1u << planes[k])) return fail(RTGPU_ERR_INVALID_ARGUMENT, "plane " + std::to_string(k) + ": plane " + std::to_string(planes[k]) + " is requested twice");
@@ -282,12 +284,13 @@ static int beginAovsChain(RtgpuContext* c, const RtPassParams* p, hipStream_t st
     return RTGPU_OK;
 }
 
-RTGPU_API int rtgpu_render_aovs_chain(RtgpuContext* c, const RtPassParams* p, const RtAovChain* chain, const uint32_t* planes, uint32_t numPlanes, void* const* outputs)
+// the host entries: rtgpu_render_aovs_chain and rtgpu_render_aovs_virtual, which knows one plane more
+static int renderAovsChain(RtgpuContext* c, const RtPassParams* p, const RtAovChain* chain, const uint32_t* planes, uint32_t numPlanes, void* const* outputs, uint32_t numKnown)
 {
     uint32_t mask = 0u;
-    int r = checkAovsChain(c, p, chain, planes, numPlanes, outputs, mask); if (r) return r;
+    int r = checkAovsChain(c, p, chain, planes, numPlanes, outputs, mask, numKnown); if (r) return r;
     if (numPlanes == 0) return RTGPU_OK;
-    uint32_t firstChannel[RT_AOV_CHAIN_NUM_PLANES], channels = 0u;
+    uint32_t firstChannel[RT_AOV_VIRTUAL_NUM_PLANES], channels = 0u;
     for (uint32_t k = 0; k < numPlanes; ++k) { firstChannel[k] = channels; channels += aovChainChannels(planes[k]); }
     r = flushBeforeAovs(c); if (r) return r;
     const QueryUntimed untimed(c);   // timing measures the render passes
@@ -298,7 +301,7 @@ RTGPU_API int rtgpu_render_aovs_chain(RtgpuContext* c, const RtPassParams* p, co
     RtgpuContext::Chain& a = c->chain;
     const size_t pixels = (size_t)c->width * c->height, capacity = a.lane.paths.capacity;
     AovChainOutputs out;
-    for (uint32_t id = 0; id < RT_AOV_CHAIN_NUM_PLANES; ++id) out.plane[id] = nullptr;
+    for (uint32_t id = 0; id < RT_AOV_VIRTUAL_NUM_PLANES; ++id) out.plane[id] = nullptr;
     for (uint32_t k = 0; k < numPlanes; ++k) out.plane[planes[k]] = a.staged + (size_t)firstChannel[k] * capacity;
     for (size_t first = 0; first < pixels; first += chunk)
     {
@@ -313,11 +316,22 @@ RTGPU_API int rtgpu_render_aovs_chain(RtgpuContext* c, const RtPassParams* p, co
     return RTGPU_OK;
 }
 
-RTGPU_API int rtgpu_render_aovs_chain_async(RtgpuContext* c, const RtPassParams* p, const RtAovChain* chain, const uint32_t* planes, uint32_t numPlanes, void* const* outputs,
-                                            void* streamHandle)
+RTGPU_API int rtgpu_render_aovs_chain(RtgpuContext* c, const RtPassParams* p, const RtAovChain* chain, const uint32_t* planes, uint32_t numPlanes, void* const* outputs)
+{
+    return renderAovsChain(c, p, chain, planes, numPlanes, outputs, RT_AOV_CHAIN_NUM_PLANES);
+}
+
+RTGPU_API int rtgpu_render_aovs_virtual(RtgpuContext* c, const RtPassParams* p, const RtAovChain* chain, const uint32_t* planes, uint32_t numPlanes, void* const* outputs)
+{
+    return renderAovsChain(c, p, chain, planes, numPlanes, outputs, RT_AOV_VIRTUAL_NUM_PLANES);
+}
+
+// the device entries
+static int renderAovsChainAsync(RtgpuContext* c, const RtPassParams* p, const RtAovChain* chain, const uint32_t* planes, uint32_t numPlanes, void* const* outputs,
+                                void* streamHandle, uint32_t numKnown)
 {
     uint32_t mask = 0u;
-    int r = checkAovsChain(c, p, chain, planes, numPlanes, outputs, mask); if (r) return r;
+    int r = checkAovsChain(c, p, chain, planes, numPlanes, outputs, mask, numKnown); if (r) return r;
     if (numPlanes == 0) return RTGPU_OK;
     for (uint32_t k = 0; k < numPlanes; ++k)
         if ((uintptr_t)outputs[k] & 15u) return fail(RTGPU_ERR_INVALID_ARGUMENT, "plane " + std::to_string(k) + ": the output must be a 16-byte aligned device buffer");
@@ -329,7 +343,7 @@ RTGPU_API int rtgpu_render_aovs_chain_async(RtgpuContext* c, const RtPassParams*
     r = beginAovsChain(c, p, stream, lastDepth, 0u, chunk); if (r) return r;
     const size_t pixels = (size_t)c->width * c->height;
     AovChainOutputs out;
-    for (uint32_t id = 0; id < RT_AOV_CHAIN_NUM_PLANES; ++id) out.plane[id] = nullptr;
+    for (uint32_t id = 0; id < RT_AOV_VIRTUAL_NUM_PLANES; ++id) out.plane[id] = nullptr;
     for (uint32_t k = 0; k < numPlanes; ++k) out.plane[planes[k]] = outputs[k];
     for (size_t first = 0; first < pixels; first += chunk)
     {
@@ -338,6 +352,18 @@ RTGPU_API int rtgpu_render_aovs_chain_async(RtgpuContext* c, const RtPassParams*
     }
     HIP_TRY(hipEventRecord(c->chain.done, stream));
     return RTGPU_OK;
+}
+
+RTGPU_API int rtgpu_render_aovs_chain_async(RtgpuContext* c, const RtPassParams* p, const RtAovChain* chain, const uint32_t* planes, uint32_t numPlanes, void* const* outputs,
+                                            void* streamHandle)
+{
+    return renderAovsChainAsync(c, p, chain, planes, numPlanes, outputs, streamHandle, RT_AOV_CHAIN_NUM_PLANES);
+}
+
+RTGPU_API int rtgpu_render_aovs_virtual_async(RtgpuContext* c, const RtPassParams* p, const RtAovChain* chain, const uint32_t* planes, uint32_t numPlanes, void* const* outputs,
+                                              void* streamHandle)
+{
+    return renderAovsChainAsync(c, p, chain, planes, numPlanes, outputs, streamHandle, RT_AOV_VIRTUAL_NUM_PLANES);
 }
 
 RTGPU_API int rtgpu_set_guide_chain(RtgpuContext* c, const RtAovChain* chain)

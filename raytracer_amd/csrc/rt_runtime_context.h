@@ -336,6 +336,7 @@ struct RtgpuContext
     {
         float4* records = nullptr; size_t capacity = 0;   // two sets of four planes of `capacity` 16-byte records: {A, length}, {B, id}, {N, valid}, {P, 0} (128 bytes per pixel)
         uint32_t current = 0; bool have = false;          // the set that holds the previous frame; false: no history (every pixel starts)
+        bool chained = false;                             // that frame was written by rtgpu_denoise_temporal_chain: the free lane of {P, .} holds chain lengths
         float worldToScreen[16] = {}, sampleOffset[2] = {};   // of the pass that frame's guides were rendered with
         // moving objects: per CURRENT object the id and transform it had when the history was stored (rtgpu_update_objects carries them through its
         // permutations and raises movedSince); the device copy of the RtObjectMotion table built from them

@@ -47,16 +47,28 @@ struct TemporalClipLaunch { const RtTemporalClip* clip; float4* moments; size_t 
 // motion: the device copy of an RtObjectMotion table (objects moved between the two frames: k_temporal<true>), or NULL: the static kernel, launched as ever.
 // clipped (or NULL): k_temporal_moments over this frame's planes first -- only with a history: without one nothing blends, and nothing is there to clip --, then
 // the clipping variant of either kernel
+// chain (or NULL): the planes are chain guides (rtgpu_temporal_accumulate_chain) -- the k_temporal_chain / k_temporal_moments_chain sibling of whichever kernel the
+// call without would launch, with this frame's chain planes behind its arguments
 static void launchTemporalKernel(const TemporalIn& in, const TemporalOut& out, uint32_t width, uint32_t height, const TemporalFrame& frame, hipStream_t stream,
-                                 const RtObjectMotion* motion = nullptr, uint32_t numObjects = 0u, const TemporalClipLaunch* clipped = nullptr)
+                                 const RtObjectMotion* motion = nullptr, uint32_t numObjects = 0u, const TemporalClipLaunch* clipped = nullptr, const TemporalChainPlanes* chain = nullptr)
 {
     const dim3 block(RT_DENOISE_BLOCK_X, RT_DENOISE_BLOCK_Y), grid(((width + RT_DENOISE_BLOCK_X - 1u) / RT_DENOISE_BLOCK_X) * ((height + RT_DENOISE_BLOCK_Y - 1u) / RT_DENOISE_BLOCK_Y));
-    if (!motion && !clipped) { hipLaunchKernelGGL(k_temporal<false>, grid, block, 0, stream, in, out, width, height, frame); return; }
+    if (!motion && !clipped)
+    {
+        if (chain) hipLaunchKernelGGL((k_temporal_chain<false, false>), grid, block, 0, stream, in, out, width, height, frame, *chain);
+        else hipLaunchKernelGGL(k_temporal<false>, grid, block, 0, stream, in, out, width, height, frame);
+        return;
+    }
     static_assert(sizeof(RtObjectMotion) == 5u * sizeof(float4), "k_temporal<true> reads a motion record as five float4");
     TemporalFrameMoving moving;
     static_cast<TemporalFrame&>(moving) = frame;
     moving.objects = reinterpret_cast<const float4*>(motion); moving.numObjects = numObjects;
-    if (!clipped) { hipLaunchKernelGGL(k_temporal<true>, grid, block, 0, stream, in, out, width, height, moving); return; }
+    if (!clipped)
+    {
+        if (chain) hipLaunchKernelGGL((k_temporal_chain<true, false>), grid, block, 0, stream, in, out, width, height, moving, *chain);
+        else hipLaunchKernelGGL(k_temporal<true>, grid, block, 0, stream, in, out, width, height, moving);
+        return;
+    }
     float4* const mu = clipped->moments; float4* const g = mu + clipped->capacity;
     if (in.recA)
     {
@@ -64,21 +76,26 @@ static void launchTemporalKernel(const TemporalIn& in, const TemporalOut& out, u
         const TemporalMomentsFrame moments = { frame.colorScale, frame.normalThreshold, frame.planeTolerance, clipped->clip->gamma };
         typedef void (*MomentsKernel) RT_K_TEMPORAL_MOMENTS_ARGS;
         static const MomentsKernel kernels[3] = { k_temporal_moments<1>, k_temporal_moments<2>, k_temporal_moments<3> };
-        hipLaunchKernelGGL(kernels[clipped->clip->radius - 1u], tiles, tile, 0, stream, in, width, height, moments, mu, g);
+        typedef void (*MomentsChainKernel) RT_K_TEMPORAL_MOMENTS_CHAIN_ARGS;
+        static const MomentsChainKernel chainKernels[3] = { k_temporal_moments_chain<1>, k_temporal_moments_chain<2>, k_temporal_moments_chain<3> };
+        if (chain) hipLaunchKernelGGL(chainKernels[clipped->clip->radius - 1u], tiles, tile, 0, stream, in, width, height, moments, mu, g, *chain);
+        else hipLaunchKernelGGL(kernels[clipped->clip->radius - 1u], tiles, tile, 0, stream, in, width, height, moments, mu, g);
     }
     if (!motion)
     {
         TemporalFrameClip<TemporalFrame> f;
         static_cast<TemporalFrame&>(f) = frame;
         f.momentMu = mu; f.momentG = g; f.confidence = clipped->confidence; f.minCount = (float)clipped->clip->minCount;
-        hipLaunchKernelGGL((k_temporal<false, true>), grid, block, 0, stream, in, out, width, height, f);
+        if (chain) hipLaunchKernelGGL((k_temporal_chain<false, true>), grid, block, 0, stream, in, out, width, height, f, *chain);
+        else hipLaunchKernelGGL((k_temporal<false, true>), grid, block, 0, stream, in, out, width, height, f);
     }
     else
     {
         TemporalFrameClip<TemporalFrameMoving> f;
         static_cast<TemporalFrameMoving&>(f) = moving;
         f.momentMu = mu; f.momentG = g; f.confidence = clipped->confidence; f.minCount = (float)clipped->clip->minCount;
-        hipLaunchKernelGGL((k_temporal<true, true>), grid, block, 0, stream, in, out, width, height, f);
+        if (chain) hipLaunchKernelGGL((k_temporal_chain<true, true>), grid, block, 0, stream, in, out, width, height, f, *chain);
+        else hipLaunchKernelGGL((k_temporal<true, true>), grid, block, 0, stream, in, out, width, height, f);
     }
 }
 
@@ -117,15 +134,19 @@ static void buildMotionTable(const std::vector<RtObject>& now, const std::vector
 }
 
 // the planes of the pure entries, in the order of their arguments
+// (the four planes of RtTemporalChain stand behind the other inputs: every input before the first output)
 enum { T_COLOR, T_HALF, T_DEPTH, T_NORMAL, T_POSITION, T_ALBEDO, T_ID, T_PREV_A, T_PREV_B, T_PREV_LENGTH, T_PREV_DEPTH, T_PREV_NORMAL, T_PREV_POSITION, T_PREV_ID,
-       T_OUT_A, T_OUT_B, T_OUT_LENGTH, T_OUT_MOTION, T_OUT_CONFIDENCE };
+       T_VIRTUAL_POSITION, T_CHAIN_LENGTH, T_CHAIN_DISTANCE, T_PREV_CHAIN_LENGTH, T_OUT_A, T_OUT_B, T_OUT_LENGTH, T_OUT_MOTION, T_OUT_CONFIDENCE };
 static PlaneTable temporalPlanes(const float* color, const float* colorHalf, const float* depth, const float* normal, const float* position, const float* albedo, const uint32_t* objectId,
                                  const float* prevA, const float* prevB, const float* prevLength, const float* prevDepth, const float* prevNormal, const float* prevPosition,
-                                 const uint32_t* prevObjectId, float* outA, float* outB, float* outLength, float* outMotion, float* outConfidence = nullptr)
+                                 const uint32_t* prevObjectId, float* outA, float* outB, float* outLength, float* outMotion, float* outConfidence = nullptr,
+                                 const RtTemporalChain* chain = nullptr)
 {
     return { { { color, 3u, false }, { colorHalf, 3u, false }, { depth, 1u, false }, { normal, 3u, false }, { position, 3u, false }, { albedo, 3u, false }, { objectId, 1u, false },
                { prevA, 3u, false }, { prevB, 3u, false }, { prevLength, 1u, false }, { prevDepth, 1u, false }, { prevNormal, 3u, false }, { prevPosition, 3u, false },
-               { prevObjectId, 1u, false }, { outA, 3u, true }, { outB, 3u, true }, { outLength, 1u, true }, { outMotion, 2u, true }, { outConfidence, 1u, true } }, 19u };
+               { prevObjectId, 1u, false }, { chain ? chain->virtualPosition : nullptr, 3u, false }, { chain ? chain->chainLength : nullptr, 1u, false },
+               { chain ? chain->chainDistance : nullptr, 1u, false }, { chain ? chain->prevChainLength : nullptr, 1u, false },
+               { outA, 3u, true }, { outB, 3u, true }, { outLength, 1u, true }, { outMotion, 2u, true }, { outConfidence, 1u, true } }, 23u };
 }
 
 // the motion table of the _moving entries (NULL, 0: the entries without)
@@ -152,7 +173,7 @@ static int checkTemporal(RtgpuContext* c, const RtTemporalParams* t, uint32_t wi
 
 // the launches of a pure call on `stream`; every plane is device memory
 static int launchTemporal(RtgpuContext* c, const RtTemporalParams* t, uint32_t width, uint32_t height, const PlaneTable& b, bool history, hipStream_t stream, const TemporalMotion& motion,
-                          const RtTemporalClip* clip)
+                          const RtTemporalClip* clip, bool chained)
 {
     RtgpuContext::Denoise& d = c->denoise;
     const size_t pixels = (size_t)width * height;
@@ -165,26 +186,36 @@ static int launchTemporal(RtgpuContext* c, const RtTemporalParams* t, uint32_t w
     {
         float4* const recA = d.records; float4* const recB = recA + d.capacity; float4* const recN = recB + d.capacity; float4* const recP = recN + d.capacity;
         hipLaunchKernelGGL(k_temporal_pack, dim3((uint32_t)((pixels + RT_BLOCK - 1u) / RT_BLOCK)), dim3(RT_BLOCK), 0, stream, b.in(T_PREV_A), b.in(T_PREV_B), b.in(T_PREV_LENGTH),
-                           b.in(T_PREV_DEPTH), b.in(T_PREV_NORMAL), b.in(T_PREV_POSITION), b.ids(T_PREV_ID), (uint32_t)pixels, recA, recB, recN, recP);
+                           b.in(T_PREV_DEPTH), b.in(T_PREV_NORMAL), b.in(T_PREV_POSITION), b.ids(T_PREV_ID), b.ids(T_PREV_CHAIN_LENGTH), (uint32_t)pixels, recA, recB, recN, recP);
         in.recA = recA; in.recB = recB; in.recN = recN; in.recP = recP;
     }
     const TemporalOut out = { b.out(T_OUT_A), b.out(T_OUT_B), b.out(T_OUT_LENGTH), b.out(T_OUT_MOTION), nullptr, nullptr, nullptr, nullptr, nullptr };
+    const TemporalChainPlanes chain = { b.in(T_VIRTUAL_POSITION), b.ids(T_CHAIN_LENGTH), b.in(T_CHAIN_DISTANCE) };
     launchTemporalKernel(in, out, width, height, temporalFrame(t, t->prevWorldToScreen, t->prevSampleOffset, history && b.has(T_ID) && b.has(T_PREV_ID)), stream,
-                         history && motion.given ? motion.objects : nullptr, motion.numObjects, clip ? &clipped : nullptr);   // (without history every pixel starts: the table has nothing to say)
+                         history && motion.given ? motion.objects : nullptr, motion.numObjects, clip ? &clipped : nullptr,   // (without history every pixel starts: the table has nothing to say)
+                         chained ? &chain : nullptr);
     return recordDone(c, stream);
 }
 
 // the pure entries over planes (and a motion table) in device memory (onDevice), or in host memory: then staged, the table behind the planes
 // (clipped: the _clip entries, which need `clip`)
+// (chained: the _chain entries, whose table holds the planes of their RtTemporalChain -- `chain` itself is only tested for NULL -- and whose clip is optional)
 static int temporalAccumulate(RtgpuContext* c, const RtTemporalParams* t, uint32_t width, uint32_t height, PlaneTable b, TemporalMotion motion, bool onDevice, void* streamHandle,
-                              bool clipped = false, const RtTemporalClip* clip = nullptr)
+                              bool clipped = false, const RtTemporalClip* clip = nullptr, bool chained = false, const RtTemporalChain* chain = nullptr)
 {
     bool history = false;
     int r = checkTemporal(c, t, width, height, b, history, motion); if (r) return r;
-    if (clipped)
+    if (clipped || clip)
     {
         if (!clip) return fail(RTGPU_ERR_INVALID_ARGUMENT, "NULL clip");
         r = checkTemporalClip(clip); if (r) return r;
+    }
+    if (!clip) b.planes[T_OUT_CONFIDENCE].ptr = nullptr;   // (not written: neither staged nor checked)
+    if (chained)
+    {
+        if (!chain) return fail(RTGPU_ERR_INVALID_ARGUMENT, "NULL chain");
+        if (!b.has(T_VIRTUAL_POSITION) || !b.has(T_CHAIN_LENGTH) || !b.has(T_CHAIN_DISTANCE)) return fail(RTGPU_ERR_INVALID_ARGUMENT, "the chain's virtualPosition, chainLength and chainDistance planes are required");
+        if (b.has(T_PREV_CHAIN_LENGTH) != history) return fail(RTGPU_ERR_INVALID_ARGUMENT, "prevChainLength goes with the previous frame's buffers: give it beside a history and only there");
     }
     const size_t n = (size_t)width * height;
     if (onDevice && motion.given && ((uintptr_t)motion.objects & 15u)) return fail(RTGPU_ERR_INVALID_ARGUMENT, "the motion table must be 16-byte aligned device memory");
@@ -195,7 +226,7 @@ static int temporalAccumulate(RtgpuContext* c, const RtTemporalParams* t, uint32
     const void* table = motion.objects;
     if (!onDevice) { r = stagePlanes(c, b, n, device, &table, motion.given ? motion.numObjects * sizeof(RtObjectMotion) : 0u); if (r) return r; }
     motion.objects = (const RtObjectMotion*)table;
-    r = launchTemporal(c, t, width, height, device, history, stream, motion, clip);
+    r = launchTemporal(c, t, width, height, device, history, stream, motion, clip, chained);
     if (r || onDevice) return r;
     HIP_TRY(hipStreamSynchronize(stream));
     return copyPlanesBack(b, device, n);
@@ -263,6 +294,30 @@ RTGPU_API int rtgpu_temporal_accumulate_clip_async(RtgpuContext* c, const RtTemp
                               streamHandle, true, clip);
 }
 
+// the _chain entries: chain guides, an optional clip
+RTGPU_API int rtgpu_temporal_accumulate_chain(RtgpuContext* c, const RtTemporalParams* t, uint32_t width, uint32_t height, const float* color, const float* colorHalf, const float* depth,
+                                              const float* normal, const float* position, const float* albedo, const uint32_t* objectId, const float* prevA, const float* prevB,
+                                              const float* prevLength, const float* prevDepth, const float* prevNormal, const float* prevPosition, const uint32_t* prevObjectId,
+                                              float* outA, float* outB, float* outLength, float* outMotion, const RtObjectMotion* objects, uint32_t numObjects,
+                                              const RtTemporalClip* clip, float* outConfidence, const RtTemporalChain* chain)
+{
+    return temporalAccumulate(c, t, width, height, temporalPlanes(color, colorHalf, depth, normal, position, albedo, objectId, prevA, prevB, prevLength, prevDepth, prevNormal,
+                                                                  prevPosition, prevObjectId, outA, outB, outLength, outMotion, outConfidence, chain), clipMotion(objects, numObjects), false,
+                              nullptr, false, clip, true, chain);
+}
+
+RTGPU_API int rtgpu_temporal_accumulate_chain_async(RtgpuContext* c, const RtTemporalParams* t, uint32_t width, uint32_t height, const float* color, const float* colorHalf,
+                                                    const float* depth, const float* normal, const float* position, const float* albedo, const uint32_t* objectId,
+                                                    const float* prevA, const float* prevB, const float* prevLength, const float* prevDepth, const float* prevNormal,
+                                                    const float* prevPosition, const uint32_t* prevObjectId, float* outA, float* outB, float* outLength, float* outMotion,
+                                                    const RtObjectMotion* objects, uint32_t numObjects, const RtTemporalClip* clip, float* outConfidence,
+                                                    const RtTemporalChain* chain, void* streamHandle)
+{
+    return temporalAccumulate(c, t, width, height, temporalPlanes(color, colorHalf, depth, normal, position, albedo, objectId, prevA, prevB, prevLength, prevDepth, prevNormal,
+                                                                  prevPosition, prevObjectId, outA, outB, outLength, outMotion, outConfidence, chain), clipMotion(objects, numObjects), true,
+                              streamHandle, false, clip, true, chain);
+}
+
 RTGPU_API int rtgpu_temporal_reset(RtgpuContext* c)
 {
     if (!c) return fail(RTGPU_ERR_INVALID_ARGUMENT, "NULL context");
@@ -272,8 +327,10 @@ RTGPU_API int rtgpu_temporal_reset(RtgpuContext* c)
 
 // rtgpu_denoise_temporal / rtgpu_denoise_temporal_async: outHost or outDevice (outVariance is memory of the same kind, written with `v` only)
 // clip (may be NULL: the call without) and outConfidence (optional, written with a clip only): memory of the result's kind
+// chained: rtgpu_denoise_temporal_chain[_async], whose guides are the chain guides of `chain` (its own argument, never rtgpu_set_guide_chain's) with the virtual position
 static int denoiseTemporalFrame(RtgpuContext* c, const RtTemporalParams* t, const RtDenoiseVarParams* v, const RtPassParams* guideParams, float* outHost, float* outDevice,
-                                float* outVariance, void* streamHandle, const RtTemporalClip* clip = nullptr, float* outConfidence = nullptr)
+                                float* outVariance, void* streamHandle, const RtTemporalClip* clip = nullptr, float* outConfidence = nullptr, bool chained = false,
+                                const RtAovChain* chain = nullptr)
 {
     if (!c) return fail(RTGPU_ERR_INVALID_ARGUMENT, "NULL context");
     if (!t) return fail(RTGPU_ERR_INVALID_ARGUMENT, "NULL argument");
@@ -281,15 +338,24 @@ static int denoiseTemporalFrame(RtgpuContext* c, const RtTemporalParams* t, cons
     if (v) { r = checkDenoiseVarParams(v); if (r) return r; }
     if (clip) { r = checkTemporalClip(clip); if (r) return r; }
     // (before anything is submitted or the history touched) reprojecting a reflection needs the virtual motion of the mirrored point
-    if (c->chain.guide) return fail(RTGPU_ERR_UNSUPPORTED, "temporal accumulation does not reproject through a guide chain: clear it with rtgpu_set_guide_chain(ctx, NULL)");
+    if (chained)
+    {
+        if (!chain) return fail(RTGPU_ERR_INVALID_ARGUMENT, "NULL chain");
+        if (chain->maxChain > RT_AOV_CHAIN_MAX) return fail(RTGPU_ERR_INVALID_ARGUMENT, "maxChain must be 0..16");
+        if (chain->flags != 0u) return fail(RTGPU_ERR_INVALID_ARGUMENT, "RtAovChain::flags must be 0");
+    }
+    else if (c->chain.guide) return fail(RTGPU_ERR_UNSUPPORTED, "temporal accumulation does not reproject through a guide chain: clear it with rtgpu_set_guide_chain(ctx, NULL), or call rtgpu_denoise_temporal_chain");
     if (!clip) outConfidence = nullptr;
     const bool stagesConfidence = outConfidence && outHost;
     FrameStep f;
-    r = beginFrame(c, guideParams, outHost, outDevice, outVariance, v != nullptr, streamHandle, 5u, stagesConfidence ? 8u : 7u, f, outDevice ? outConfidence : nullptr); if (r) return r;   // its own planes: the accumulated pair 3 + 3, its length 1 (and the host entry's confidence 1)
+    // its own planes: the accumulated pair 3 + 3, its length 1 (and the host entry's confidence 1; behind them the chained call's chain planes 1 + 1 + 3)
+    r = beginFrame(c, guideParams, outHost, outDevice, outVariance, v != nullptr, streamHandle, 5u, (stagesConfidence ? 8u : 7u) + (chained ? 5u : 0u), f, outDevice ? outConfidence : nullptr,
+                   chained ? chain : nullptr); if (r) return r;
     float* const dA = f.extra; float* const dB = dA + 3u * f.stride; float* const dLength = dB + 3u * f.stride;
     float* const dConfidence = stagesConfidence ? dLength + f.stride : outConfidence;
     RtgpuContext::Temporal& h = c->temporal;
     if (h.capacity < f.pixels) h.have = false;
+    if (!chained && h.chained) h.have = false;   // a history over chain guides holds chain lengths these entries never knew: to them it is no history, and they overwrite it
     r = ensureScratch(c, h.records, h.capacity, f.pixels, 8u); if (r) return r;   // two sets of four planes of records
     float4* const from = h.records + (size_t)h.current * 4u * h.capacity; float4* const to = h.records + (size_t)(h.current ^ 1u) * 4u * h.capacity;
     TemporalIn in = { c->sum, c->secondary, f.depth, f.normal, f.position, (t->flags & RT_DENOISE_DEMODULATE) ? f.albedo : nullptr, f.id, nullptr, nullptr, nullptr, nullptr };
@@ -310,11 +376,13 @@ static int denoiseTemporalFrame(RtgpuContext* c, const RtTemporalParams* t, cons
     }
     TemporalClipLaunch clipped;
     if (clip) { r = temporalClipLaunch(c, clip, f.pixels, h.have, dConfidence, clipped); if (r) return r; }
-    launchTemporalKernel(in, res, c->width, c->height, temporalFrame(t, h.worldToScreen, h.sampleOffset, h.have), f.stream, motion, (uint32_t)objects.size(), clip ? &clipped : nullptr);
+    const TemporalChainPlanes chainPlanes = { f.virtualPosition, f.chainLength, f.chainDistance };
+    launchTemporalKernel(in, res, c->width, c->height, temporalFrame(t, h.worldToScreen, h.sampleOffset, h.have), f.stream, motion, (uint32_t)objects.size(), clip ? &clipped : nullptr,
+                         chained ? &chainPlanes : nullptr);
     r = recordDone(c, f.stream); if (r) return r;
     r = markSumRead(c, f.stream); if (r) return r;
     // this frame is the next call's history
-    h.current ^= 1u; h.have = true;
+    h.current ^= 1u; h.have = true; h.chained = chained;
     h.movedSince = false;
     h.then.resize(objects.size());
     for (size_t o = 0; o < objects.size(); ++o) { h.then[o].id = (uint32_t)o; memcpy(h.then[o].transform, objects[o].transform, sizeof(h.then[o].transform)); }
@@ -352,4 +420,16 @@ RTGPU_API int rtgpu_denoise_temporal_clip_async(RtgpuContext* c, const RtTempora
                                                 const RtTemporalClip* clip, float* outConfidence, void* streamHandle)
 {
     return denoiseTemporalFrame(c, t, v, guideParams, nullptr, outRGB, outVariance, streamHandle, clip, outConfidence);
+}
+
+RTGPU_API int rtgpu_denoise_temporal_chain(RtgpuContext* c, const RtTemporalParams* t, const RtDenoiseVarParams* v, const RtPassParams* guideParams, const RtAovChain* chain, float* outRGB,
+                                           float* outVariance, const RtTemporalClip* clip, float* outConfidence)
+{
+    return denoiseTemporalFrame(c, t, v, guideParams, outRGB, nullptr, outVariance, nullptr, clip, outConfidence, true, chain);
+}
+
+RTGPU_API int rtgpu_denoise_temporal_chain_async(RtgpuContext* c, const RtTemporalParams* t, const RtDenoiseVarParams* v, const RtPassParams* guideParams, const RtAovChain* chain,
+                                                 float* outRGB, float* outVariance, const RtTemporalClip* clip, float* outConfidence, void* streamHandle)
+{
+    return denoiseTemporalFrame(c, t, v, guideParams, nullptr, outRGB, outVariance, streamHandle, clip, outConfidence, true, chain);
 }

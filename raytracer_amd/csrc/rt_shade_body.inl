@@ -9,7 +9,8 @@
 // holds that vertex's own R_ORIGIN / R_DIR / R_TP / R_HIT for k_aov_resolve_chain (misSampleBsdf's results go through locals here for that reason).
 // Early stop: a miss, a light, a material kind that cannot pass and a vertex at depth maxChain stop before a draw is taken -- what the draws would
 // decide no longer matters -- so a frame without mirrors and glass pays one evaluated intersection per pixel.  R_RESULT.x carries the sum of the hit
-// distances of the vertices passed so far (no radiance is kept there).
+// distances of the vertices passed so far (no radiance is kept there); R_SH_P / R_SH_TP, the next-event request's records, carry the primary ray of a path
+// whose vertex 0 may be passed, for RT_AOV_VIRTUAL_POSITION.
 //
 // The body of PathTracerMIS::RenderPixel's loop for one path vertex (PathTracerMIS.cpp:276-395).  What does not depend on where a path's records live
 // -- the lights a ray hits, Russian roulette, BSDF sampling with the packing of the next ray -- are the mis* stages of rt_shade.inl, which
@@ -131,6 +132,14 @@ __global__ void __launch_bounds__(RT_BLOCK) RT_SHADE_KERNEL(const RtSceneDesc sc
 #if RT_SHADE_CHAIN
                 // the early stop: this vertex cannot be passed whatever is drawn
                 if (depth >= maxChain || !(mat.bsdf == RT_BSDF_DIELECTRIC || mat.bsdf == RT_BSDF_ROUGH_DIELECTRIC || mat.bsdf == RT_BSDF_METAL || mat.bsdf == RT_BSDF_ROUGH_METAL)) break;
+                // vertex 0 may be passed: the primary ray as generated, for RT_AOV_VIRTUAL_POSITION (k_aov_resolve_chain reads it for k > 0 only).  The two records are
+                // the next-event request's, which this variant never writes.  Stored here, while the ray is live, and not where the vertex is known to be passed:
+                // carried across the BSDF sampling the six words cost 8 VGPRs and a wave per SIMD
+                if (depth == 0u)
+                {
+                    prec(paths, R_SH_P, slot) = f4(ray.origin.x, ray.origin.y, ray.origin.z, 0.0f);
+                    prec(paths, R_SH_TP, slot) = f4(ray.dir.x, ray.dir.y, ray.dir.z, 0.0f);
+                }
 #endif
                 materialEvaluateShadingData<kLean>(scene, mat, sd);
 

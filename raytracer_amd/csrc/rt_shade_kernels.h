@@ -30,8 +30,9 @@ struct AovOutputs { void* plane[RT_AOV_NUM_PLANES]; };
 #define RT_K_AOV_RESOLVE_ARGS (const RtSceneDesc scene, const Paths paths, uint32_t count, uint32_t mask, const AovOutputs out, size_t channelStride, size_t firstOut, \
                                const uint4* __restrict__ rayCounts)
 #define RT_AOV_CLASSES(X) X(0) X(3)
-// rtgpu_render_aovs_chain: the same for the slot's guide vertex; plane[] is indexed by RtAovPlane and, behind RT_AOV_NUM_PLANES, RtAovChainPlane
-struct AovChainOutputs { void* plane[RT_AOV_CHAIN_NUM_PLANES]; };
+// rtgpu_render_aovs_chain and rtgpu_render_aovs_virtual: the same for the slot's guide vertex; plane[] is indexed by RtAovPlane and, behind RT_AOV_NUM_PLANES,
+// RtAovChainPlane and RtAovVirtualPlane
+struct AovChainOutputs { void* plane[RT_AOV_VIRTUAL_NUM_PLANES]; };
 #define RT_K_AOV_RESOLVE_CHAIN_ARGS (const RtSceneDesc scene, const Paths paths, uint32_t count, uint32_t mask, const AovChainOutputs out, size_t channelStride, size_t firstOut)
 
 // The bidirectional integrator's kernels that evaluate textures (normal maps, textured material parameters, an environment map) come in two scene

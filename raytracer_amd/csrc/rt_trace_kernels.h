@@ -79,6 +79,14 @@ template <bool kMoving> struct TemporalFrameOf<kMoving, true> { typedef Temporal
 struct TemporalMomentsFrame { float colorScale, normalThreshold, planeTolerance, gamma; };
 #define RT_K_TEMPORAL_MOMENTS_ARGS (const TemporalIn in, uint32_t width, uint32_t height, const TemporalMomentsFrame frame, float4* __restrict__ outMu, float4* __restrict__ outG)
 #define RT_TEMPORAL_MOMENTS_ATTR __launch_bounds__(RT_DENOISE_TILE_X * RT_DENOISE_TILE_Y)
+// temporal accumulation over chain guides (rtgpu_temporal_accumulate_chain): k_temporal_chain and k_temporal_moments_chain are the second inclusions of
+// rt_temporal_body.inl and rt_temporal_moments_body.inl, under RT_TEMPORAL_CHAIN 1, and take this frame's three chain planes behind the arguments of their
+// siblings, which keep their own lists
+struct TemporalChainPlanes { const float* virtualPosition; const uint32_t* chainLength; const float* chainDistance; };
+#define RT_K_TEMPORAL_CHAIN_ARGS (const TemporalIn in, const TemporalOut out, uint32_t width, uint32_t height, const typename TemporalFrameOf<kMoving, kClip>::type frame, \
+                                  const TemporalChainPlanes chain)
+#define RT_K_TEMPORAL_MOMENTS_CHAIN_ARGS (const TemporalIn in, uint32_t width, uint32_t height, const TemporalMomentsFrame frame, float4* __restrict__ outMu, float4* __restrict__ outG, \
+                                          const TemporalChainPlanes chain)
 
 #ifndef RT_DEVICE_KERNELS
 template <int kStack, bool kCount, bool kPerRay = false> __global__ void RT_TRACE_ATTR(kStack) k_trace RT_K_TRACE_ARGS;
@@ -129,9 +137,11 @@ template <bool kLast, int kStep, bool kVar = false> __global__ void RT_ATROUS_TI
 // temporal accumulation (rt_temporal.inl)
 __global__ void __launch_bounds__(RT_BLOCK) k_temporal_pack(const float* __restrict__ prevA, const float* __restrict__ prevB, const float* __restrict__ prevLength,
                                                             const float* __restrict__ prevDepth, const float* __restrict__ prevNormal, const float* __restrict__ prevPosition,
-                                                            const uint32_t* __restrict__ prevObjectId, uint32_t pixels, float4* __restrict__ recA, float4* __restrict__ recB,
-                                                            float4* __restrict__ recN, float4* __restrict__ recP);
+                                                            const uint32_t* __restrict__ prevObjectId, const uint32_t* __restrict__ prevChainLength, uint32_t pixels,
+                                                            float4* __restrict__ recA, float4* __restrict__ recB, float4* __restrict__ recN, float4* __restrict__ recP);
 template <bool kMoving = false, bool kClip = false> __global__ void RT_ATROUS_ATTR k_temporal RT_K_TEMPORAL_ARGS;
 template <int kRadius> __global__ void RT_TEMPORAL_MOMENTS_ATTR k_temporal_moments RT_K_TEMPORAL_MOMENTS_ARGS;
+template <bool kMoving = false, bool kClip = false> __global__ void RT_ATROUS_ATTR k_temporal_chain RT_K_TEMPORAL_CHAIN_ARGS;
+template <int kRadius> __global__ void RT_TEMPORAL_MOMENTS_ATTR k_temporal_moments_chain RT_K_TEMPORAL_MOMENTS_CHAIN_ARGS;
 __global__ void __launch_bounds__(RT_MONSTER_BLOCK) k_trace_monster(const RtSceneDesc scene, const Paths paths, const uint32_t* __restrict__ queue, const uint32_t* __restrict__ queueCount);
 #endif

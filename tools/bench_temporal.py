@@ -25,7 +25,17 @@ clip=...)) filtered and unfiltered, the share of the last frame's pixels whose c
 --diagnose adds `starts_by_the_model`: the NumPy model (tests/temporal_ref.py) over the guides of the last two frames, with the defaults and with one
 surface test relaxed at a time -- how many pixels start and why.
 
-  python tools/bench_temporal.py [--reps 20] [--diagnose] [--output profiles/temporal_bench_1080p.json]"""
+--chain N [--mirror]: another report altogether -- reflections in the history (rtgpu_denoise_temporal_chain through Viewport.denoise(temporal=True, chain=N)).
+--mirror adds scenes.add_mirror_props, as tools/bench_denoise.py --mirror does.  Under the yawing camera, after --frames frames, for the pixels with a chain and
+for the rest separately: the relative MSE against the converged render of (a) denoise(temporal=True) with first-hit guides, (b) denoise(temporal=True, chain=N)
+and (c) denoise(variance=True) under set_guide_chain(N), no history; (a) and (b) also without the spatial filter (variance=False), and with the clip of --clip-gammas' first gamma when --clip is given; the mean
+history length inside the chain pixels, by the pure entry; and the times: the pure entry with a history over chain planes against the entry without on the
+same planes (k_temporal_pack + k_temporal[_chain], with the clip k_temporal_moments[_chain] in front), and the whole context call against
+rtgpu_denoise_temporal[_clip].  These are times of calls: no kernel is timed alone.  `clip_adds_to_pure_ms` is the clipped pure entry minus the unclipped one,
+with and without chain planes: the moments kernel and the clipping variant's extra work.  Without --mirror every k is 0: the kChain kernels' cost where they change nothing.
+
+  python tools/bench_temporal.py [--reps 20] [--diagnose] [--output profiles/temporal_bench_1080p.json]
+  python tools/bench_temporal.py --chain 3 --mirror --clip [--output profiles/temporal_chain_bench_1080p_mirror.json]"""
 import argparse
 import ctypes as C
 import json
@@ -45,6 +55,114 @@ HBM_PEAK = 8.0e12
 BYTES_PER_PIXEL = {"current planes": 68, "history records": 64, "planar results": 28, "new records": 64, "image (the unfiltered call, which is the one timed)": 12}
 
 
+def chain_report(args, torch, ra, scenes):
+    w, h = args.width, args.height
+    scene, camera = scenes.sponza_class(w / h, args.triangles)
+    if args.mirror:
+        scenes.add_mirror_props(scene)
+    translation, orientation = camera.settings["translation"], camera.settings["orientation_deg"]
+
+    def look(frame):
+        camera.set_transform(translation, (orientation[0], orientation[1] + args.yaw * frame, orientation[2]))
+        camera.set_perspective(camera.settings["aspect"], camera.settings["fov_rad"])
+    vp = ra.Viewport(w, h, seed=1234, max_ray_depth=args.depth)
+    vp.set_renderer(scene)
+    ctx = vp.device_context()
+    last = args.frames - 1
+    look(last)
+    vp.render(camera, passes=args.reference_passes)
+    reference = (vp.sum_buffer() / np.float32(args.reference_passes)).astype(np.float64)
+    out = {"scene": "sponza_class" + ("+mirror_props" if args.mirror else ""), "width": w, "height": h, "passes_per_frame": args.passes, "frames": args.frames,
+           "yaw_deg_per_frame": args.yaw, "reference_passes": args.reference_passes, "reps": args.reps, "max_chain": args.chain, "max_ray_depth": args.depth}
+    guides = ("depth", "normal", "position", "base_color", "object_id")
+    chain_guides = guides + ("chain_length", "chain_distance", "virtual_position")
+    clips = [("", None)] + ([("_clipped", dict(radius=3, gamma=float(args.clip_gammas.split(",")[0]), min_count=9))] if args.clip else [])
+    scale = float(np.float32(1.0 / args.passes))
+    stream = torch.cuda.Stream()
+    with torch.cuda.stream(stream):
+        def sequence(call):
+            """the frames the caller drives; call(guide params) per frame; returns the last one's result"""
+            vp.reset_history()
+            result = None
+            for frame in range(args.frames):
+                look(frame)
+                vp.reset()
+                vp.render(camera, passes=args.passes)
+                result = call(vp.next_pass_params(camera))
+            return result
+        images = {}
+        for suffix, clip in clips:
+            images["a_temporal_first_hit" + suffix] = sequence(lambda p: vp.denoise(p, temporal=True, variance=True, device=True, clip=clip))
+            images["b_temporal_chain" + suffix] = sequence(lambda p: vp.denoise(p, temporal=True, variance=True, device=True, clip=clip, chain=args.chain))
+            # the accumulated frames without the spatial filter: what the reprojection alone is worth, apart from what chain guides do to the filter
+            images["a_temporal_first_hit_unfiltered" + suffix] = sequence(lambda p: vp.denoise(p, temporal=True, variance=False, device=True, clip=clip))
+            images["b_temporal_chain_unfiltered" + suffix] = sequence(lambda p: vp.denoise(p, temporal=True, variance=False, device=True, clip=clip, chain=args.chain))
+        vp.set_guide_chain(args.chain)
+        images["c_variance_chain_guides_no_history"] = vp.denoise(vp.next_pass_params(camera), variance=True, device=True)
+        vp.set_guide_chain(None)
+        # the same sequence through the pure entry, which returns the history lengths
+        state = dict(history=None, previous=None)
+
+        def pure_step(p):
+            g = vp.render_aovs(p, chain_guides, device=True, chain=args.chain)
+            s = vp.sum_buffer(secondary=True)
+            kw = {} if state["previous"] is None else dict(prev_world_to_screen=list(state["previous"].camera.worldToScreen), prev_sample_offset=tuple(state["previous"].sampleOffset))
+            state["before"] = (state["history"], state["previous"])
+            state["history"] = ra.temporal_accumulate(torch.from_numpy(s[0]).cuda(), torch.from_numpy(s[1]).cuda(), g["depth"], g["normal"], g["position"], g["base_color"], g["object_id"],
+                                                      history=state["history"], color_scale=scale, ctx=ctx, chain={k: g[k] for k in ra.CHAIN_KEYS}, **kw)
+            state["previous"], state["planes"], state["sums"] = p, g, s
+            return state["history"]
+        pure = sequence(pure_step)
+        stream.synchronize()
+        g = state["planes"]
+        inside = (g["chain_length"] >= 1).cpu().numpy()
+        hit = torch.isfinite(g["depth"]).cpu().numpy()
+        length = pure["length"].cpu().numpy()
+        # the chain pixels by what the primary ray hit: a metal (the mirror: one event per vertex) or a dielectric (the sphere: reflect or refract by the pass's draw)
+        first_material = vp.render_aovs(state["previous"], ("material",))["material"]
+        desc = scene.desc.contents
+        kind_of = np.array([desc.materials[m].bsdf for m in range(desc.numMaterials)] + [0], dtype=np.uint32)
+        first_kind = kind_of[np.minimum(first_material, desc.numMaterials)]
+        metal, glass = inside & (first_kind == ra.BSDF_NAMES.index("metal")), inside & (first_kind == ra.BSDF_NAMES.index("dielectric"))
+        out["metal_pixels"] = {"share": float(metal.mean()), "length_mean": float(length[metal & hit].mean()) if (metal & hit).any() else None,
+                               "share_started_in_the_last_frame": float((length[metal & hit] == 1.0).mean()) if (metal & hit).any() else None}
+        out["glass_pixels"] = {"share": float(glass.mean()), "length_mean": float(length[glass & hit].mean()) if (glass & hit).any() else None,
+                               "share_started_in_the_last_frame": float((length[glass & hit] == 1.0).mean()) if (glass & hit).any() else None}
+        out["chain_pixels"] = {"share": float(inside.mean()), "share_with_a_surface_guide": float((inside & hit).mean()),
+                               "length_mean": float(length[inside & hit].mean()) if (inside & hit).any() else None,
+                               "share_started_in_the_last_frame": float((length[inside & hit] == 1.0).mean()) if (inside & hit).any() else None}
+        out["other_pixels"] = {"length_mean": float(length[~inside & hit].mean()), "share_started_in_the_last_frame": float((length[~inside & hit] == 1.0).mean())}
+        error = lambda image: (image.cpu().numpy().astype(np.float64) - reference) ** 2 / (reference ** 2 + 0.01)   # noqa: E731
+        out["rel_mse"] = {}
+        for name, image in images.items():
+            e = error(image).mean(axis=-1)
+            out["rel_mse"][name] = {"chain_pixels": float(e[inside].mean()) if inside.any() else None, "metal_pixels": float(e[metal].mean()) if metal.any() else None,
+                                    "glass_pixels": float(e[glass].mean()) if glass.any() else None, "other_pixels": float(e[~inside].mean()), "frame": float(e.mean())}
+        # times: the film holds the last frame and the pure sequence's history of the frame before it
+        history, previous = state["before"]
+        color, color_half = torch.from_numpy(state["sums"][0]).cuda(), torch.from_numpy(state["sums"][1]).cuda()
+        kw = dict(depth=g["depth"], normal=g["normal"], position=g["position"], albedo=g["base_color"], object_id=g["object_id"].to(torch.int32), color_scale=scale, ctx=ctx,
+                  prev_world_to_screen=list(previous.camera.worldToScreen), prev_sample_offset=tuple(previous.sampleOffset))
+        chain = {k: (g[k].to(torch.int32) if k == "chain_length" else g[k]) for k in ra.CHAIN_KEYS}
+        plain_history = {k: v for k, v in history.items() if k != "chain_length"}
+        guide = state["previous"]
+        for suffix, clip in clips:
+            out["accumulate_pure" + suffix] = time_call(torch, lambda: ra.temporal_accumulate(color, color_half, history=plain_history, clip=clip, **kw), args.reps)
+            out["accumulate_pure_chain" + suffix] = time_call(torch, lambda: ra.temporal_accumulate(color, color_half, history=history, clip=clip, chain=chain, **kw), args.reps)
+            out["temporal_call" + suffix] = time_call(torch, lambda: vp.denoise(guide, temporal=True, variance=True, device=True, clip=clip), args.reps)
+            out["temporal_call_chain" + suffix] = time_call(torch, lambda: vp.denoise(guide, temporal=True, variance=True, device=True, clip=clip, chain=args.chain), args.reps)
+        # what the clip adds to the pure entry: k_temporal_moments[_chain] and the clipping variant of k_temporal[_chain] in the unclipped one's place -- the nearest this
+        # tool comes to the kernels themselves; it times calls, never a kernel alone
+        if args.clip:
+            out["clip_adds_to_pure_ms"] = {"without_chain": out["accumulate_pure_clipped"]["ms_median"] - out["accumulate_pure"]["ms_median"],
+                                           "with_chain": out["accumulate_pure_chain_clipped"]["ms_median"] - out["accumulate_pure_chain"]["ms_median"]}
+    line = json.dumps(out)
+    print(line)
+    if args.output:
+        with open(args.output, "w") as f:
+            f.write(line + "\n")
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--reps", type=int, default=20)
@@ -59,13 +177,19 @@ def main():
     ap.add_argument("--diagnose", action="store_true", help="also count, by the NumPy model on the last two frames' guides, why pixels start")
     ap.add_argument("--clip", action="store_true", help="add the clipped columns: the same sequence with the history clipped, once per gamma")
     ap.add_argument("--clip-gammas", default="1,2,4,8")
+    ap.add_argument("--chain", type=int, default=None, help="the report on reflections in the history instead: denoise(temporal=True, chain=N) beside the calls that exist")
+    ap.add_argument("--mirror", action="store_true", help="with --chain: add a mirror and a glass sphere (scenes.add_mirror_props)")
     ap.add_argument("--output", default=None)
     args = ap.parse_args()
     if args.frames < 2:
         ap.error("--frames must be at least 2")
+    if args.mirror and args.chain is None:
+        ap.error("--mirror goes with --chain N")
     import torch
     import raytracer_amd as ra
     from raytracer_amd import scenes
+    if args.chain is not None:
+        return chain_report(args, torch, ra, scenes)
     w, h = args.width, args.height
     scene, camera = scenes.sponza_class(w / h, args.triangles)
     translation, orientation = camera.settings["translation"], camera.settings["orientation_deg"]
