@@ -374,7 +374,13 @@ void rtgpu_destroy(RtgpuContext* ctx);
 const char* rtgpu_last_error(void);
 uint32_t rtgpu_abi_version(void);
 
-/* --- scene: replaces Scene::BuildBVH's pointer graph; copies everything, host memory may be freed */
+/* --- scene: replaces Scene::BuildBVH's pointer graph; copies everything, host memory may be freed.
+ *     May be called again on a live context.  The passes queued before the call (either integrator's) are submitted first and render the old
+ *     scene.  A scene is checked before anything is freed: a refused one (RTGPU_ERR_INVALID_ARGUMENT / _UNSUPPORTED) leaves the old scene, its
+ *     photons and the history of rtgpu_denoise_temporal as they were.  An accepted one drops those photons and that history and the update
+ *     record of rtgpu_get_update_info, and picks walk and shading kernels anew (rtgpu_get_walk_info is that of a fresh context given the
+ *     scene); it keeps the film and the counters as they stand (rtgpu_reset is the caller's), the frame size, shard and active blocks, the
+ *     integrator and its settings, and rtgpu_set_guide_chain. */
 int rtgpu_upload_scene(RtgpuContext* ctx, const RtSceneDesc* scene);
 
 /* --- moving objects: what the reference's demo does when the selected object is dragged -- ISceneObject::SetTransform
@@ -413,7 +419,18 @@ int rtgpu_update_objects(RtgpuContext* ctx, const RtSceneUpdate* update);
 typedef struct RtUpdateInfo { uint64_t bytesUploaded; uint32_t numUpdates, topDepth; uint32_t walk; uint32_t _pad[3]; } RtUpdateInfo;   /* 32 bytes */
 int rtgpu_get_update_info(RtgpuContext* ctx, RtUpdateInfo* out);
 
-/* --- film: Viewport::Resize (Viewport.cpp:52-107) / Viewport::Reset (:120-138) ------------------*/
+/* --- film: Viewport::Resize (Viewport.cpp:52-107) / Viewport::Reset (:120-138) ------------------
+ * All three first submit every pass rtgpu_render_pass has queued -- the bidirectional integrator's batch included -- and wait for it: a queued
+ * pass renders the film it was queued for (and counts in rtgpu_get_counters), never the one behind the call.
+ *   rtgpu_resize     a new film of the given size, both sum buffers zero.  Drops the active blocks of rtgpu_set_active_blocks (the whole
+ *                    image is active again), the photons of RT_INTEGRATOR_VCM (the next pass merges nothing) and the history of
+ *                    rtgpu_denoise_temporal (the next such call starts every pixel), also when the size is the one the context has.
+ *                    Keeps the scene, the integrator and its settings, the shard, the counters, rtgpu_set_guide_chain, and whatever device
+ *                    memory still suffices.  A refused size (0, or above 65536) changes nothing.
+ *   rtgpu_set_shard  the same for a new ownership of the frame's tiles.
+ *   rtgpu_reset      zeroes both sum buffers, the counters and the kernel times.  Keeps everything else, the active blocks and the history of
+ *                    rtgpu_denoise_temporal included (a moving camera resets the film every frame); the bidirectional integrator starts over
+ *                    with the pass whose passIndex is 0. */
 int rtgpu_resize(RtgpuContext* ctx, uint32_t width, uint32_t height);
 int rtgpu_set_shard(RtgpuContext* ctx, RtgpuShard shard);
 int rtgpu_reset(RtgpuContext* ctx);
@@ -502,6 +519,8 @@ typedef struct RtVcmParams
     float    vertexMergingWeight[4];       /* mVertexMergingWeight     = 1 */
 } RtVcmParams;
 #define RT_VCM_MAX_PATH_LENGTH 16u
+/* Synchronises (the queued passes render with the integrator they were queued under) and drops the recorded photons, whatever the integrator;
+ * film, counters, active blocks, the history of rtgpu_denoise_temporal and rtgpu_set_guide_chain stay.  Refused settings change nothing. */
 int rtgpu_set_integrator(RtgpuContext* ctx, uint32_t integrator, const RtVcmParams* vcm /* NULL: defaults */);
 /* DebugRenderer::mRenderingMode; needs RT_INTEGRATOR_DEBUG.  Synchronises. */
 int rtgpu_set_debug_rendering_mode(RtgpuContext* ctx, uint32_t mode);

@@ -55,7 +55,15 @@ using namespace rtd;
 #include "rt_knobs.h"
 
 static int flushPending(RtgpuContext* c);
+static int vcmFlush(RtgpuContext* c);
 static void freeVcm(RtgpuContext* c);
+// Everything rtgpu_render_pass queued goes out: the bidirectional integrator's batch (rt_runtime_vcm.inl) and the PathTracerMIS batch.  Whatever replaces the film,
+// the slot table or the scene calls this first, so that a queued pass renders the state it was queued in.
+static int flushQueued(RtgpuContext* c)
+{
+    { const int r = vcmFlush(c); if (r) return r; }
+    return flushPending(c);
+}
 
 #include "rt_multi.inl"
 
@@ -296,7 +304,7 @@ RTGPU_API int rtgpu_resize(RtgpuContext* c, uint32_t width, uint32_t height)
     if (width == 0 || height == 0 || width > 65536u || height > 65536u) return fail(RTGPU_ERR_INVALID_ARGUMENT, "Invalid viewport size");
     RT_FAN_OUT(c, rtgpu_resize(peer, width, height));
     HIP_TRY(hipSetDevice(c->device));
-    { int fr = flushPending(c); if (fr) return fr; }
+    { int fr = flushQueued(c); if (fr) return fr; }
     HIP_TRY(syncLanes(c));
     c->width = width; c->height = height;
     return rebuildFilm(c);
@@ -308,7 +316,7 @@ RTGPU_API int rtgpu_set_shard(RtgpuContext* c, RtgpuShard shard)
     if (shard.worldSize == 0 || shard.rank >= shard.worldSize) return fail(RTGPU_ERR_INVALID_ARGUMENT, "invalid shard");
     if (!c->peers.empty() || c->isPeer) return fail(RTGPU_ERR_UNSUPPORTED, "a multi-device context shards the frame itself (rtgpu_create_multi)");
     HIP_TRY(hipSetDevice(c->device));
-    { int fr = flushPending(c); if (fr) return fr; }
+    { int fr = flushQueued(c); if (fr) return fr; }
     HIP_TRY(syncLanes(c));
     c->shard = shard;
     return rebuildFilm(c);
@@ -319,7 +327,7 @@ RTGPU_API int rtgpu_reset(RtgpuContext* c)
     if (!c) return fail(RTGPU_ERR_INVALID_ARGUMENT, "NULL context");
     RT_FAN_OUT(c, rtgpu_reset(peer));
     HIP_TRY(hipSetDevice(c->device));
-    { int fr = flushPending(c); if (fr) return fr; }
+    { int fr = flushQueued(c); if (fr) return fr; }
     HIP_TRY(syncLanes(c));
     waitDenoiseRead(c);
     if (c->sum)

@@ -26,10 +26,9 @@ RTGPU_API int rtgpu_upload_scene(RtgpuContext* c, const RtSceneDesc* s)
     RT_FAN_OUT(c, rtgpu_upload_scene(peer, s));   // the scene is replicated: every device traverses its own copy
     if (s->abiVersion != RTGPU_ABI_VERSION) return fail(RTGPU_ERR_INVALID_ARGUMENT, "RtSceneDesc::abiVersion mismatch");
     HIP_TRY(hipSetDevice(c->device));
-    { int fr = flushPending(c); if (fr) return fr; }
+    { int fr = flushQueued(c); if (fr) return fr; }
     HIP_TRY(syncLanes(c));
     waitQueries(c);   // an asynchronous ray query or AOV call may still walk the old scene
-    c->temporal.have = false;   // rtgpu_denoise_temporal's history shows the old scene
 
     // validation: indices in range, stacks deep enough
     if (s->numObjects > 1 && s->numTopNodes == 0) return fail(RTGPU_ERR_INVALID_ARGUMENT, "scene with more than one object needs a top-level BVH");
@@ -135,7 +134,8 @@ RTGPU_API int rtgpu_upload_scene(RtgpuContext* c, const RtSceneDesc* s)
     // prepare: the breadth-first mesh nodes, the shading records, the 4-wide trees, the scene class (RTGPU_NO_SIMPLE_TEXTURES=1: class 2 instead of 4)
     const PreparedScene p = prepareScene(*s, topDepth, maxMeshDepth, !knobs::noLean(), !knobs::noSimpleTextures());
 
-    // copy
+    // copy (nothing of the context has changed up to here: a refused scene leaves the old one, its photons and the temporal history as they were)
+    c->temporal.have = false;   // rtgpu_denoise_temporal's history shows the old scene
     freeScene(c);
     RtSceneDesc d = *s;
     int r;
@@ -213,7 +213,7 @@ RTGPU_API int rtgpu_update_objects(RtgpuContext* c, const RtSceneUpdate* u)
     if (u->abiVersion != RTGPU_ABI_VERSION) return fail(RTGPU_ERR_INVALID_ARGUMENT, "RtSceneUpdate::abiVersion mismatch");
     if (!c->sceneReady) return fail(RTGPU_ERR_NOT_READY, "rtgpu_upload_scene has not been called");
     HIP_TRY(hipSetDevice(c->device));
-    { int fr = flushPending(c); if (fr) return fr; }
+    { int fr = flushQueued(c); if (fr) return fr; }
     HIP_TRY(syncLanes(c));
     waitQueries(c);
     RtgpuContext::Updatable& up = c->updatable;
