@@ -416,8 +416,53 @@ typedef struct RtSceneUpdate
     const RtLight*  lights;         /* [numLights]   Scene::mLights order, or NULL: the lights are unchanged */
 } RtSceneUpdate;
 int rtgpu_update_objects(RtgpuContext* ctx, const RtSceneUpdate* update);
-typedef struct RtUpdateInfo { uint64_t bytesUploaded; uint32_t numUpdates, topDepth; uint32_t walk; uint32_t _pad[3]; } RtUpdateInfo;   /* 32 bytes */
+typedef struct RtUpdateInfo { uint64_t bytesUploaded; uint32_t numUpdates, topDepth; uint32_t walk; uint32_t _pad[3]; } RtUpdateInfo;   /* 32 bytes; _pad[0]: rtgpu_update_mesh calls so far (below) */
 int rtgpu_get_update_info(RtgpuContext* ctx, RtUpdateInfo* out);
+
+/* --- deforming meshes: a mesh whose vertices moved (a skinned character, cloth, an edited vertex) keeps its topology, so every table that depends on its
+ *     positions is a box or a triangle record.  rtgpu_update_mesh takes the new positions (12 bytes per vertex) and refits those tables ON THE DEVICE.
+ *   triangles  triangle t of the mesh, in the device's (leaf) order, with vertex indices i0, i1, i2: v0 = P[i0], edge1 = P[i1] - P[i0], edge2 = P[i2] - P[i0],
+ *              each lane one float subtraction (MeshShape::Initialize's arithmetic).  Its box is Box(P[i0], P[i1], P[i2]) of Math.h -- Min(a, Min(b, c))
+ *              with Min(a, b) = a < b ? a : b per lane, Max alike --, taken from the positions, never from v0 + edge.
+ *   boxes      a leaf takes the box of its first triangle, joined with those of its further ones in order (Box(box0, box1) = Min(box0.min, box1.min), ...);
+ *              an interior node takes Box(child0, child1).  Node 1, which the builder never writes, stays; childIndex and leaves are never written.
+ *   gates      the exact box of every leaf, where the 4-wide walks read it.
+ *   grid       the grid of the mesh's 4-wide level is the one an upload computes over the new root box (the root node is read back for it).
+ *   4-wide     every child slot is re-quantised from its binary node's new box by the upload's rule (in double, with the same push-out loops); its reference,
+ *              leaf count or empty mark is kept.  WHICH binary nodes share a 4-wide node is kept as uploaded: it was chosen by surface area then, any choice
+ *              returns the same hits, and a fresh upload of the same vertices may choose differently (and walk faster after a large deformation).
+ *   shading    with shading != NULL the three RtVertexShading of every triangle's record are rewritten; its material is kept.  NULL: normals, tangents and
+ *              texture coordinates stay.
+ *   errors     a NULL argument, an abiVersion mismatch, flags != 0, meshIndex out of range, numVertices different from the mesh's, a position that is not
+ *              finite or positions spanning more than a float holds: RTGPU_ERR_INVALID_ARGUMENT; a mesh whose uploaded tree is not an exact tree over all its
+ *              triangles (a shared or unreachable node, a leaf's triangles out of range, a triangle in no leaf or in two), or -- where the mesh has a 4-wide
+ *              level -- new positions whose box the 16-bit grid cannot hold with the half step of margin the walks rest on (base = min - 4 steps rounds back
+ *              onto min: a mesh far from its local origin for its size, or flat at a coordinate that is not zero; an upload leaves such a mesh to the binary
+ *              walk, an update keeps the walk and so refuses: upload the scene instead): RTGPU_ERR_UNSUPPORTED; before rtgpu_upload_scene: RTGPU_ERR_NOT_READY.  A mesh without
+ *              triangles: RTGPU_OK, nothing done.  Every check is made on the host first: a refused update leaves the device exactly as it was.
+ *   ordering   as rtgpu_update_objects: queued passes are submitted first and show the old mesh; lanes, ray queries and AOV calls are waited for.  A
+ *              multi-device context updates every peer (never run on two devices so far).
+ *   refreshes  the tables above; the level records of every object that uses the mesh (instances share one level: one refit serves all); the grid of a
+ *              single-mesh scene.  The photons of the bidirectional integrator are dropped.  The history of rtgpu_denoise_temporal is kept: pixels whose first
+ *              hit lies on an object of the mesh start anew (their object's prevId is 0xFFFFFFFF in the table the call builds), all others reproject as before.
+ *   keeps      topology, materials, textures, the scene class, the chosen walk, the top level and the object table: when the mesh's box changed, the caller
+ *              follows with rtgpu_update_objects and a top-level tree over the new boxes (rtgpu_read_mesh tells the new root box).
+ * rtgpu_get_update_info counts these calls in _pad[0]; bytesUploaded is that of the last update of either kind.
+ * rtgpu_read_mesh: the mesh's nodes as they stand on the device, in the CALLER's node order and with the caller's child indices (nodes[numNodes]), and its
+ * triangles (triangles[numTriangles]); either may be NULL.  rtgpu_read_wide_level: the 4-wide level that serves object objectIndex (object 0 of a
+ * single-mesh scene) -- its WideLevel-shaped record (64 bytes: node base, gate base, triangle base, valid, grid base / step / bound), its raw 16-byte node
+ * records and its gate records; nodeBytes / gateBytes are the buffers' sizes and must hold the level (info->pad[0] node records, info->pad[1] gate
+ * records; call with NULL buffers to learn them).  RTGPU_ERR_NOT_READY for an object without such a level.  Both synchronise, as rtgpu_read_sum does. */
+typedef struct RtMeshUpdate
+{
+    uint32_t abiVersion, meshIndex, numVertices, flags /* 0 */;
+    const float*           positions;   /* [numVertices][3], mesh-local, the order of the VertexBufferDesc the mesh was made from */
+    const RtVertexShading* shading;     /* [numVertices] or NULL: normals, tangents and texture coordinates stay */
+} RtMeshUpdate;
+int rtgpu_update_mesh(RtgpuContext* ctx, const RtMeshUpdate* update);
+typedef struct RtWideLevelInfo { uint32_t nodeBase, gateBase, triBase, valid; float base[3], step[3], bound[3]; uint32_t pad[3]; } RtWideLevelInfo;   /* 64 bytes */
+int rtgpu_read_mesh(RtgpuContext* ctx, uint32_t meshIndex, RtNode* nodes, RtTriangle* triangles);
+int rtgpu_read_wide_level(RtgpuContext* ctx, uint32_t objectIndex, RtWideLevelInfo* info, void* nodes, uint64_t nodeBytes, void* gates, uint64_t gateBytes);
 
 /* --- film: Viewport::Resize (Viewport.cpp:52-107) / Viewport::Reset (:120-138) ------------------
  * All three first submit every pass rtgpu_render_pass has queued -- the bidirectional integrator's batch included -- and wait for it: a queued

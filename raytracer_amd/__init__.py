@@ -131,12 +131,46 @@ class RtUpdateInfo(C.Structure):
     _fields_ = [("bytesUploaded", C.c_uint64), ("numUpdates", C.c_uint32), ("topDepth", C.c_uint32), ("walk", C.c_uint32), ("_pad", C.c_uint32 * 3)]
 
 
+class RtMeshUpdate(C.Structure):
+    _fields_ = [("abiVersion", C.c_uint32), ("meshIndex", C.c_uint32), ("numVertices", C.c_uint32), ("flags", C.c_uint32),
+                ("positions", C.POINTER(C.c_float)), ("shading", C.c_void_p)]
+
+
+class RtWideLevelInfo(C.Structure):
+    _fields_ = [("nodeBase", C.c_uint32), ("gateBase", C.c_uint32), ("triBase", C.c_uint32), ("valid", C.c_uint32), ("base", C.c_float * 3),
+                ("step", C.c_float * 3), ("bound", C.c_float * 3), ("pad", C.c_uint32 * 3)]
+
+
+def read_mesh(ctx, mesh_index, num_nodes, num_triangles):
+    """rtgpu_read_mesh: the mesh's nodes (caller's order, (num_nodes, 8) uint32 words) and triangles ((num_triangles, 9) float32) as they stand on the device."""
+    nodes = np.zeros((num_nodes, 8), dtype=np.uint32)
+    triangles = np.zeros((num_triangles, 9), dtype=np.float32)
+    if rtgpu_lib().rtgpu_read_mesh(ctx, C.c_uint32(mesh_index), nodes.ctypes.data_as(C.c_void_p), triangles.ctypes.data_as(C.c_void_p)) != 0:
+        raise RuntimeError("rtgpu_read_mesh failed: %s" % (rtgpu_lib().rtgpu_last_error() or b"").decode())
+    return nodes, triangles
+
+
+def read_wide_level(ctx, object_index):
+    """rtgpu_read_wide_level: (info dict with the grid, node records (n, 4) uint32, gate records (m, 4) float32) of the 4-wide level that serves the object."""
+    lib, info = rtgpu_lib(), RtWideLevelInfo()
+    if lib.rtgpu_read_wide_level(ctx, C.c_uint32(object_index), C.byref(info), None, C.c_uint64(0), None, C.c_uint64(0)) != 0:
+        raise RuntimeError("rtgpu_read_wide_level failed: %s" % (lib.rtgpu_last_error() or b"").decode())
+    nodes = np.zeros((info.pad[0], 4), dtype=np.uint32)
+    gates = np.zeros((info.pad[1], 4), dtype=np.float32)
+    if lib.rtgpu_read_wide_level(ctx, C.c_uint32(object_index), C.byref(info), nodes.ctypes.data_as(C.c_void_p), C.c_uint64(nodes.nbytes),
+                                 gates.ctypes.data_as(C.c_void_p), C.c_uint64(gates.nbytes)) != 0:
+        raise RuntimeError("rtgpu_read_wide_level failed: %s" % (lib.rtgpu_last_error() or b"").decode())
+    grid = dict(base=np.array(info.base[:], dtype=np.float32), step=np.array(info.step[:], dtype=np.float32), bound=np.array(info.bound[:], dtype=np.float32))
+    return dict(grid, nodeBase=int(info.nodeBase), gateBase=int(info.gateBase), triBase=int(info.triBase), valid=int(info.valid)), nodes, gates
+
+
 def update_info(ctx):
-    """rtgpu_get_update_info as a dict: what the last rtgpu_update_objects copied to the device, and the walk that serves the scene."""
+    """rtgpu_get_update_info as a dict: what the last rtgpu_update_objects / rtgpu_update_mesh copied to the device, how many of each there were, and the walk
+    that serves the scene."""
     info = RtUpdateInfo()
     if rtgpu_lib().rtgpu_get_update_info(ctx, C.byref(info)) != 0:
         raise RuntimeError("rtgpu_get_update_info failed")
-    return {"bytesUploaded": int(info.bytesUploaded), "numUpdates": int(info.numUpdates), "topDepth": int(info.topDepth),
+    return {"bytesUploaded": int(info.bytesUploaded), "numUpdates": int(info.numUpdates), "numMeshUpdates": int(info._pad[0]), "topDepth": int(info.topDepth),
             "walk": ["binary", "wide", "wide2"][info.walk]}
 
 
@@ -693,6 +727,12 @@ class Scene:
         self.calls.append(("mesh", dict(positions=pos, indices=idx, normals=nrm, tangents=tan, tex_coords=uv, material_indices=mi, materials=tuple(materials),
                                         transform=list(transform or _IDENTITY), material=int(default_material))))
 
+    def add_instance(self, object_index, transform=None, default_material=-1):
+        """A further object over the shape of the object_index-th add_* call: for a mesh, an instance that shares its triangles and its tree."""
+        if host_lib().rth_add_instance(self._h, C.c_uint32(object_index), transform or _IDENTITY, int(default_material)) != 0:
+            raise IndexError("object %r has no shape" % (object_index,))
+        self.calls.append(("instance", dict(object=int(object_index), transform=list(transform or _IDENTITY), material=int(default_material))))
+
     def add_area_light(self, shape, params, color, transform=None):
         kind = {"sphere": 0, "box": 1, "rect": 2, "plane": 2}[shape]
         p = list(params) + [0.0] * (4 - len(params))
@@ -785,7 +825,7 @@ class Scene:
         return self
 
     # ---- moving objects (ISceneObject::SetTransform + the top-level half of Scene::BuildBVH) ----------------------------------------
-    _OBJECT_CALLS = ("sphere", "box", "rect", "mesh", "area_light", "background_light", "directional_light", "point_light", "spot_light")
+    _OBJECT_CALLS = ("sphere", "box", "rect", "mesh", "instance", "area_light", "background_light", "directional_light", "point_light", "spot_light")
 
     def object_count(self):
         """Objects added so far, shapes and lights alike: the range of set_object_transform's index."""
@@ -798,6 +838,33 @@ class Scene:
         added = [args for kind, args in self.calls if kind in self._OBJECT_CALLS]
         if len(added) == self.object_count() and "transform" in added[index]:   # (objects of load_json are not in `calls`)
             added[index]["transform"] = list(transform)
+
+    def set_mesh_vertices(self, object_index, positions, normals=None, tangents=None):
+        """MeshShape::UpdateVertices of the mesh the object_index-th add_* call made: new positions (and optionally normals / tangents; None: they stay) for
+        the same vertices, in add_mesh's order.  The mesh keeps its topology and leaf order; its tree is refitted.  Takes effect with update(); Viewport.
+        update_scene() then refits the device's copy from the positions alone (rtgpu_update_mesh).  Instances made from the same arrays are separate meshes."""
+        pos = np.ascontiguousarray(positions, dtype=np.float32).reshape(-1, 3)
+        opt = [None if a is None else np.ascontiguousarray(a, dtype=np.float32).reshape(-1, 3) for a in (normals, tangents)]
+        if any(a is not None and a.shape != pos.shape for a in opt):
+            raise ValueError("per-vertex array has the wrong length")
+        ptr = [None if a is None else a.ctypes.data_as(C.POINTER(C.c_float)) for a in opt]
+        if host_lib().rth_scene_set_mesh_vertices(self._h, C.c_uint32(object_index), C.c_uint32(pos.shape[0]), pos.ctypes.data_as(C.POINTER(C.c_float)), ptr[0], ptr[1]) != 0:
+            raise ValueError("object %r is not a mesh of %d vertices" % (object_index, pos.shape[0]))
+        added = [args for kind, args in self.calls if kind in self._OBJECT_CALLS]
+        if len(added) == self.object_count() and "positions" in added[object_index]:
+            added[object_index]["positions"] = pos.copy()
+            for key, a in zip(("normals", "tangents"), opt):
+                if a is not None:
+                    added[object_index][key] = a.copy()
+
+    def mesh_update_descs(self):
+        """The RtMeshUpdates of the last update() (pointers into the scene, valid until the next build / update / set_mesh_vertices)."""
+        out = []
+        for i in range(int(host_lib().rth_scene_mesh_update_count(self._h))):
+            u = RtMeshUpdate()
+            host_lib().rth_scene_mesh_update_desc(self._h, C.c_uint32(i), C.byref(u))
+            out.append(u)
+        return out
 
     def update(self):
         """Scene::UpdateBVH: rebuilds the top-level tree over the objects' current boxes and rewrites the flat objects, top nodes and light
@@ -936,8 +1003,8 @@ class Viewport:
         host_lib().rth_viewport_reset(self._h)
 
     def update_scene(self):
-        """Viewport::UpdateScene: after Scene.update(), sends the moved objects and the rebuilt top level to the renderer's device
-        (rtgpu_update_objects) -- no triangle is uploaded again.  Passes queued before the call render the scene as it was.  The accumulated
+        """Viewport::UpdateScene: after Scene.update(), sends the new positions of every deformed mesh (Scene.set_mesh_vertices; rtgpu_update_mesh refits its
+        tables on the device), then the moved objects and the rebuilt top level (rtgpu_update_objects) -- no triangle is uploaded again.  Passes queued before the call render the scene as it was.  The accumulated
         frame is the caller's to reset()."""
         if host_lib().rth_viewport_update_scene(self._h) != 0:
             raise RuntimeError("Viewport::UpdateScene failed: %s" % (rtgpu_lib().rtgpu_last_error() or b"").decode())

@@ -718,6 +718,7 @@ RTGPU_API int rtgpu_postprocess(RtgpuContext* c, const RtPostprocessParams* p, u
 #include "rt_runtime_aov.inl"
 #include "rt_runtime_denoise.inl"
 #include "rt_runtime_temporal.inl"
+#include "rt_runtime_refit.inl"   // rtgpu_update_mesh: a deformed mesh's tables refitted on the device
 
 RTGPU_API int rtgpu_set_concurrency(RtgpuContext* c, uint32_t lanes)
 {

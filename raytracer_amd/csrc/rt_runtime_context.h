@@ -172,6 +172,16 @@ struct RtgpuContext
         uint32_t topWideNodeCapacity = 0;                             // 4-wide nodes the top level's slab behind the mesh levels holds
         uint64_t meshNodeBytes = 0, meshGateBytes = 0;                // the mesh levels' share of walkNodeBytes / walkLeafBoxBytes[RTGPU_WALK_WIDE2]
         RtUpdateInfo info = {};                                       // rtgpu_get_update_info
+        // rtgpu_update_mesh (rt_runtime_refit.inl): per mesh its plan and 4-wide level (rt_scene_prepare.h) and, from its first update on, the device copies
+        // of its triangles' vertex indices (leaf order) and of the positions; the device arrays live in sceneAllocs and go with the scene
+        struct Mesh
+        {
+            MeshRefitPlan plan; PreparedScene::MeshLevel level;
+            RtVertexIndices* indices = nullptr; float* positions = nullptr; RtVertexShading* shading = nullptr; uint32_t* levelFirst = nullptr;
+        };
+        std::vector<Mesh> meshes; std::vector<RtMesh> meshTable;
+        std::vector<RtVertexIndices> vertexIndices;                   // the caller's, as uploaded: every update takes the new root box from them before it writes; a mesh's first update copies its share to the device
+        const uint32_t* wide2SlotNode = nullptr; const uint32_t* wideSlotNode = nullptr;   // per 4-wide record the mesh node whose box it holds (PreparedScene), on the device
     } updatable;
 
     // film

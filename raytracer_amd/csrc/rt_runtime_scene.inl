@@ -184,6 +184,16 @@ RTGPU_API int rtgpu_upload_scene(RtgpuContext* c, const RtSceneDesc* s)
         c->walkNodeBytes[RTGPU_WALK_WIDE] = p.single.nodes.size() * sizeof(float4); c->walkLeafBoxBytes[RTGPU_WALK_WIDE] = p.singleGrid.gate.size() * sizeof(float4);
         copyGrid(c->wide, p.singleGrid.grid);
     }
+    {
+        // what rtgpu_update_mesh refits by (rt_runtime_refit.inl)
+        RtgpuContext::Updatable& up = c->updatable;
+        if (p.twoLevel.ok && (r = uploadArray(c, p.wide2SlotNode.data(), p.wide2SlotNode.size(), &up.wide2SlotNode))) return r;
+        if (p.single.ok && (r = uploadArray(c, p.wideSlotNode.data(), p.wideSlotNode.size(), &up.wideSlotNode))) return r;
+        up.meshTable.assign(s->meshes, s->meshes + s->numMeshes);
+        up.vertexIndices.assign(s->vertexIndices, s->vertexIndices + s->numTriangles);
+        up.meshes.resize(s->numMeshes);
+        for (uint32_t m = 0; m < s->numMeshes; ++m) { up.meshes[m].plan = p.refit[m]; up.meshes[m].level = p.meshLevels[m]; }
+    }
     c->sceneDev = d;
     c->walkNodeBytes[RTGPU_WALK_BINARY] = ((uint64_t)s->numTopNodes + s->numMeshNodes) * sizeof(RtNode); c->walkTriangleBytes = (uint64_t)s->numTriangles * sizeof(RtTriangle);
     c->numLights = s->numLights;

@@ -66,6 +66,23 @@ static SceneStatus checkStack(uint32_t topDepth, uint32_t maxMeshDepth)
 // Mesh trees go to the device in BREADTH-FIRST order (root at 0, node 1 unused, child pairs from 2 on as the reference lays them out, levels one after
 // the other): the same tree -- a node's childIndex is only a pointer -- with the top levels every ray walks through contiguous at the front, which
 // k_trace stages in LDS.  Leaves keep their triangle ranges.
+// oldIndex[new position] of one mesh tree (a tree of fewer than three nodes keeps its order)
+static std::vector<uint32_t> breadthFirstOrder(const RtNode* src, uint32_t numNodes)
+{
+    std::vector<uint32_t> oldIndex;
+    if (numNodes < 3u) { for (uint32_t k = 0; k < numNodes; ++k) oldIndex.push_back(k); return oldIndex; }
+    oldIndex.reserve(numNodes);
+    oldIndex.push_back(0u); oldIndex.push_back(1u);
+    for (size_t k = 0; k < oldIndex.size() && oldIndex.size() + 2u <= numNodes; ++k)
+    {
+        if (k == 1u) continue;
+        const RtNode& n = src[oldIndex[k]];
+        if ((n.leaves & 0x3FFFFFFFu) != 0u) continue;
+        oldIndex.push_back(n.childIndex); oldIndex.push_back(n.childIndex + 1u);
+    }
+    return oldIndex;
+}
+
 static std::vector<RtNode> reorderMeshNodes(const RtSceneDesc& s)
 {
     std::vector<RtNode> ordered(s.meshNodes, s.meshNodes + s.numMeshNodes);
@@ -75,15 +92,16 @@ static std::vector<RtNode> reorderMeshNodes(const RtSceneDesc& s)
         if (mesh.numNodes < 3u) continue;
         const RtNode* src = s.meshNodes + mesh.firstNode;
         RtNode* dst = ordered.data() + mesh.firstNode;
-        std::vector<uint32_t> oldIndex; oldIndex.reserve(mesh.numNodes);   // oldIndex[new position]
-        oldIndex.push_back(0u); oldIndex.push_back(1u);
-        for (size_t k = 0; k < oldIndex.size() && oldIndex.size() + 2u <= mesh.numNodes; ++k)
+        const std::vector<uint32_t> oldIndex = breadthFirstOrder(src, mesh.numNodes);
+        // (children are appended in the order the interior nodes are met: the k-th interior node's pair follows the pairs of those before it)
+        uint32_t next = 2u;
+        for (size_t k = 0; k < oldIndex.size() && next + 2u <= mesh.numNodes; ++k)
         {
             if (k == 1u) continue;
             const RtNode& n = src[oldIndex[k]];
             if ((n.leaves & 0x3FFFFFFFu) != 0u) continue;
-            dst[k] = n; dst[k].childIndex = (uint32_t)oldIndex.size();
-            oldIndex.push_back(n.childIndex); oldIndex.push_back(n.childIndex + 1u);
+            dst[k] = n; dst[k].childIndex = next;
+            next += 2u;
         }
         for (size_t k = 0; k < oldIndex.size(); ++k) if (k != 1u && (src[oldIndex[k]].leaves & 0x3FFFFFFFu) != 0u) dst[k] = src[oldIndex[k]];
     }
@@ -127,6 +145,16 @@ static bool wideGridOver(const float lo[3], const float hi[3], WideGrid& g)
     }
     return true;
 }
+// Whether records on the grid can hold boxes inside [lo, hi] with the half step the walks rest on: planes lie between base and base + 65535 step, so the box that
+// reaches lo needs base <= lo - step / 2 and the one that reaches hi the last plane >= hi + step / 2.  It fails where the float lo - 4 steps rounds back onto lo:
+// a box far from the origin for its size, or flat at a coordinate that is not zero.  Sufficient for every box inside [lo, hi] (wideQuantiseBox pushes a plane that
+// is not clamped a full step out).  The builders find the same by checking every record; a refit asks BEFORE it writes.
+static bool wideGridHolds(const WideGrid& g, const float lo[3], const float hi[3])
+{
+    for (int a = 0; a < 3; ++a)
+        if ((double)g.base[a] > (double)lo[a] - 0.5 * (double)g.step[a] || (double)g.base[a] + 65535.0 * (double)g.step[a] < (double)hi[a] + 0.5 * (double)g.step[a]) return false;
+    return true;
+}
 template <class T> static void copyGrid(T& to, const WideGrid& g) { memcpy(to.base, g.base, sizeof(g.base)); memcpy(to.step, g.step, sizeof(g.step)); memcpy(to.bound, g.bound, sizeof(g.bound)); }
 static float4 wideRecord(const uint32_t v[6], uint32_t ref)   // v: min.xyz, max.xyz on the grid
 {
@@ -167,8 +195,6 @@ static QuantBuild buildQuantBvh(const RtNode* nodes, uint32_t numNodes, uint32_t
     // plane(qv) as the device could see it at worst: the kernel folds base and step into the ray's constants, whose rounding is
     // covered by the one spare step; here the stored coordinate is pushed out until the plain float plane is a full step outside
     auto plane = [&](int a, uint32_t v) { return (double)g.base[a] + (double)v * (double)g.step[a]; };
-    auto qmin = [&](int a, float x) { long v = (long)floor(((double)x - (double)g.base[a]) / (double)g.step[a]) - 1; while (v > 0 && plane(a, (uint32_t)v) > (double)x - (double)g.step[a]) --v; return (uint32_t)(v < 0 ? 0 : v); };
-    auto qmax = [&](int a, float x) { long v = (long)ceil(((double)x - (double)g.base[a]) / (double)g.step[a]) + 1; while (v < 65535 && plane(a, (uint32_t)v) < (double)x + (double)g.step[a]) ++v; return (uint32_t)(v > 65535 ? 65535 : v); };
     q.pairs.assign(numNodes, make_float4(0.0f, 0.0f, 0.0f, 0.0f));
     q.gate.assign((size_t)2 * numTriangles, make_float4(0.0f, 0.0f, 0.0f, 0.0f));
     for (uint32_t n = 2u; n < numNodes; ++n)
@@ -178,10 +204,10 @@ static QuantBuild buildQuantBvh(const RtNode* nodes, uint32_t numNodes, uint32_t
         const uint32_t numLeaves = node.leaves & 0x3FFFFFFFu;
         if (numLeaves > 2u || node.childIndex > RT_NODE_CHILD_MASK) return q;   // the reference builds leaves of at most two triangles (BVHBuilder.h:16)
         uint32_t v[6];
+        for (int a = 0; a < 3; ++a) if (!(node.min[a] <= node.max[a])) return q;   // a NaN or an inverted box: fminf / fmaxf above passed over it
+        wideQuantiseBox(g.base, g.step, node.min, node.max, v);   // (rt_wide_format.h: the rule the device's refit shares)
         for (int a = 0; a < 3; ++a)
         {
-            if (!(node.min[a] <= node.max[a])) return q;   // a NaN or an inverted box: fminf / fmaxf above passed over it
-            v[a] = qmin(a, node.min[a]); v[3 + a] = qmax(a, node.max[a]);
             if (plane(a, v[a]) > (double)node.min[a] - 0.5 * (double)g.step[a] || plane(a, v[3 + a]) < (double)node.max[a] + 0.5 * (double)g.step[a]) return q;   // the grid has room by construction
         }
         q.pairs[n] = wideRecord(v, node.childIndex | (numLeaves << RT_NODE_LEAVES_SHIFT));
@@ -203,6 +229,7 @@ static QuantBuild buildQuantBvh(const RtNode* nodes, uint32_t numNodes, uint32_t
 struct WideBuild
 {
     std::vector<float4> nodes;
+    std::vector<uint32_t> slotNode;   // per record of `nodes`: the binary node it was copied from (the caller's index; 0xFFFFFFFF: an empty slot) -- what a refit re-quantises
     bool ok = false;
 };
 
@@ -257,6 +284,7 @@ static WideBuild buildWideBvh(const RtNode* nodes, uint32_t numNodes, const Quan
             }
             w.nodes[i * 4u + k] = rec;
         }
+    w.slotNode = std::move(children);
     w.ok = true;
     return w;
 }
@@ -265,6 +293,7 @@ static WideBuild buildWideBvh(const RtNode* nodes, uint32_t numNodes, const Quan
 struct WideLevelBuild
 {
     std::vector<float4> nodes, gate;   // gate: 2 float4 per primitive index
+    std::vector<uint32_t> slotNode;    // WideBuild::slotNode; a root that is a leaf: 0xFFFFFFFF throughout (its one record does not depend on the box)
     WideGrid grid;
     bool ok = false;
 };
@@ -281,7 +310,7 @@ static WideLevelBuild buildWideLevel(const RtNode* nodes, uint32_t numNodes, uin
         if (!q.ok) return out;
         WideBuild w = buildWideBvh(nodes, numNodes, q);
         if (!w.ok) return out;
-        out.nodes = std::move(w.nodes); out.gate = std::move(q.gate); out.grid = q.grid;
+        out.nodes = std::move(w.nodes); out.gate = std::move(q.gate); out.grid = q.grid; out.slotNode = std::move(w.slotNode);
         out.ok = true;
         return out;
     }
@@ -295,6 +324,7 @@ static WideLevelBuild buildWideLevel(const RtNode* nodes, uint32_t numNodes, uin
         if ((double)g.base[a] + (double)g.step[a] > (double)root.min[a] - (double)g.step[a] || (double)g.base[a] + 65534.0 * (double)g.step[a] < (double)root.max[a] + (double)g.step[a]) return out;
     out.nodes.assign(4u, make_float4(0.0f, 0.0f, 0.0f, __builtin_bit_cast(float, (uint32_t)RT_WIDE_EMPTY)));
     out.nodes[0] = wideRecord(v, root.childIndex | (rootLeaves << RT_NODE_LEAVES_SHIFT));
+    out.slotNode.assign(4u, 0xFFFFFFFFu);
     out.gate.assign((size_t)2 * numPrimitives, make_float4(0.0f, 0.0f, 0.0f, 0.0f));
     out.gate[2u * (size_t)root.childIndex] = make_float4(root.min[0], root.min[1], root.min[2], 0.0f);
     out.gate[2u * (size_t)root.childIndex + 1u] = make_float4(root.max[0], root.max[1], root.max[2], 0.0f);
@@ -319,6 +349,9 @@ struct TwoLevelBuild
 {
     std::vector<float4> nodes, gates;    // nodes: the mesh levels, the top level, zeros up to the end of the slab
     std::vector<WideLevel> levels;
+    std::vector<uint32_t> slotNode;      // per record of the MESH levels: WideLevelBuild::slotNode (mesh-relative, the caller's order)
+    struct MeshLevel { uint32_t meshIndex, nodeBase, numNodes, gateBase; };
+    std::vector<MeshLevel> meshLevels;   // the level each mesh got: first 4-wide node, their count, first gate record
     size_t meshNodes = 0, meshGates = 0; // float4s of the mesh levels: where the top level starts
     size_t usedNodes = 0;                // float4s up to the end of the top level as built
     uint32_t topNodeCapacity = 0;        // 4-wide nodes the slab holds
@@ -348,6 +381,8 @@ static TwoLevelBuild buildTwoLevel(const RtSceneDesc& s, uint32_t topDepth)
         const WideLevelBuild b = buildWideLevel(s.meshNodes + mesh.firstNode, mesh.numNodes, mesh.numTriangles, bvhDepth(s.meshNodes + mesh.firstNode, mesh.numNodes));
         if (!b.ok) return out;
         append(b, out.levels[o], mesh.firstTriangle);
+        out.slotNode.insert(out.slotNode.end(), b.slotNode.begin(), b.slotNode.end());
+        out.meshLevels.push_back({ obj.meshIndex, out.levels[o].nodeBase, (uint32_t)(b.nodes.size() / 4u), out.levels[o].gateBase });
         builtMesh[obj.meshIndex] = o;
     }
     out.meshNodes = out.nodes.size(); out.meshGates = out.gates.size();
@@ -378,6 +413,156 @@ static TopLevelRebuild rebuildTopLevel(const std::vector<WideLevel>& levels, con
     out.levels[numObjects] = levels[numObjects];
     out.top = buildTopLevel(topNodes, numTopNodes, numObjects, topDepth, slabNodes);
     if (out.top.ok) copyGrid(out.levels[numObjects], out.top.grid);
+    return out;
+}
+
+// ---- refitting a mesh whose vertices moved (rtgpu_update_mesh) ------------------------------------------------------------------------------------------
+// The reference's Box operations (Math.h): Min(a, b) = a < b ? a : b per lane, Box(a, b, c) = Min(a, Min(b, c)), Box(b0, b1) = Min(b0.min, b1.min); Max alike.
+// The fold order is part of the contract: it decides the sign of a zero.
+struct RefitBox { float min[3], max[3]; };
+static inline float refitMin(float a, float b) { return a < b ? a : b; }
+static inline float refitMax(float a, float b) { return a > b ? a : b; }
+static inline RefitBox refitTriangleBox(const float* a, const float* b, const float* c)
+{
+    RefitBox r;
+    for (int k = 0; k < 3; ++k) { r.min[k] = refitMin(a[k], refitMin(b[k], c[k])); r.max[k] = refitMax(a[k], refitMax(b[k], c[k])); }
+    return r;
+}
+static inline RefitBox refitJoin(const RefitBox& a, const RefitBox& b)
+{
+    RefitBox r;
+    for (int k = 0; k < 3; ++k) { r.min[k] = refitMin(a.min[k], b.min[k]); r.max[k] = refitMax(a.max[k], b.max[k]); }
+    return r;
+}
+
+// What a refit of one mesh needs beside its tables, made from the BREADTH-FIRST nodes at upload.  ok: the stored nodes are an exact tree laid out depth after
+// depth (every child pair behind its parent and claimed once, every leaf's triangles inside the mesh) -- what the refit kernels rely on for their bounds -- and
+// its leaves hold every triangle of the mesh once, so the new root box is the box of the positions the triangles refer to: the host knows it before the device does.
+struct MeshRefitPlan
+{
+    std::vector<uint32_t> order;        // order[breadth-first position] = the caller's node index (reorderMeshNodes' permutation)
+    std::vector<uint32_t> levelFirst;   // first breadth-first position of every depth, then the number of positions: depth d is [levelFirst[d], levelFirst[d + 1]) (node 1 lies in depth 0's range and is skipped)
+    bool ok = false;
+};
+static MeshRefitPlan planMeshRefit(const RtNode* callerNodes, const RtNode* ordered, uint32_t numNodes, uint32_t numTriangles)
+{
+    MeshRefitPlan p;
+    if (numNodes == 0u) return p;
+    p.order = breadthFirstOrder(callerNodes, numNodes);
+    if (numNodes < 3u) p.order.resize(1u);   // only a root that is a leaf can be walked
+    const uint32_t count = (uint32_t)p.order.size();
+    std::vector<uint32_t> depth(count, 0xFFFFFFFFu);
+    depth[0] = 0u;
+    uint32_t next = 2u, last = 0u;
+    std::vector<uint8_t> held(numTriangles, 0u);
+    p.levelFirst.push_back(0u);
+    for (uint32_t k = 0; k < count; ++k)
+    {
+        if (k == 1u) continue;
+        if (depth[k] == 0xFFFFFFFFu || depth[k] < last || depth[k] > 64u) return p;
+        if (depth[k] > last) { if (depth[k] != last + 1u) return p; p.levelFirst.push_back(k); last = depth[k]; }
+        const RtNode& n = ordered[k];
+        const uint32_t leaves = n.leaves & 0x3FFFFFFFu;
+        if (leaves != 0u)
+        {
+            if (leaves > RT_MAX_PACKED_LEAVES || (uint64_t)n.childIndex + leaves > numTriangles) return p;
+            for (uint32_t j = 0; j < leaves; ++j) { if (held[n.childIndex + j]) return p; held[n.childIndex + j] = 1u; }
+            continue;
+        }
+        if (n.childIndex != next || (uint64_t)next + 2u > count) return p;
+        depth[next] = depth[next + 1u] = depth[k] + 1u;
+        next += 2u;
+    }
+    if (next != (count < 2u ? 2u : count)) return p;
+    for (const uint8_t h : held) if (!h) return p;
+    p.levelFirst.push_back(count);
+    p.ok = true;
+    return p;
+}
+
+// The refit, pure: new nodes, triangles, gates, grid and 4-wide records of one mesh from its new positions.  `nodes` in any order with mesh-relative child
+// indices (the caller's or the breadth-first one); boxes are folded child0 then child1, a leaf's triangles first to last.  childIndex, leaves and node 1 are
+// kept.  slotNode[i] = the node record i of `wide` takes its box from (0xFFFFFFFF: the record is kept); its .w is kept.  gates: 2 per triangle, zero where no
+// leaf starts.  ok: every index was in range; gridOk: the new root box has a grid and every box fits it with the builder's margin (slotNode empty: not asked).
+struct MeshRefit
+{
+    std::vector<RtNode> nodes;
+    std::vector<RtTriangle> triangles;
+    std::vector<float4> gates, wide;
+    WideGrid grid;
+    bool ok = false, gridOk = false;
+};
+static MeshRefit refitMesh(const std::vector<RtNode>& nodes, const std::vector<RtVertexIndices>& indices, const float* positions, uint32_t numVertices,
+                           const std::vector<uint32_t>& slotNode, const std::vector<float4>& wide)
+{
+    MeshRefit out;
+    out.nodes = nodes; out.wide = wide;
+    const uint32_t numTriangles = (uint32_t)indices.size();
+    out.triangles.resize(numTriangles);
+    std::vector<RefitBox> triBox(numTriangles);
+    for (uint32_t t = 0; t < numTriangles; ++t)
+    {
+        const RtVertexIndices& idx = indices[t];
+        if (idx.i0 >= numVertices || idx.i1 >= numVertices || idx.i2 >= numVertices) return out;
+        const float* a = positions + 3u * (size_t)idx.i0; const float* b = positions + 3u * (size_t)idx.i1; const float* c = positions + 3u * (size_t)idx.i2;
+        RtTriangle& tri = out.triangles[t];
+        for (int k = 0; k < 3; ++k) { tri.v0[k] = a[k]; tri.edge1[k] = b[k] - a[k]; tri.edge2[k] = c[k] - a[k]; }
+        triBox[t] = refitTriangleBox(a, b, c);
+    }
+    out.gates.assign((size_t)2 * numTriangles, make_float4(0.0f, 0.0f, 0.0f, 0.0f));
+    if (nodes.empty() || numTriangles == 0u) { out.ok = true; return out; }
+    // post order from the root: a node is folded once both children are
+    std::vector<std::pair<uint32_t, bool>> stack;
+    stack.push_back({ 0u, false });
+    size_t visits = 0;
+    while (!stack.empty())
+    {
+        const auto [n, childrenDone] = stack.back(); stack.pop_back();
+        if (n >= out.nodes.size() || ++visits > 2u * out.nodes.size()) return out;
+        RtNode& node = out.nodes[n];
+        const uint32_t leaves = node.leaves & 0x3FFFFFFFu;
+        RefitBox box;
+        if (leaves != 0u)
+        {
+            if ((uint64_t)node.childIndex + leaves > numTriangles) return out;
+            box = triBox[node.childIndex];
+            for (uint32_t j = 1; j < leaves; ++j) box = refitJoin(box, triBox[node.childIndex + j]);
+            out.gates[2u * (size_t)node.childIndex] = make_float4(box.min[0], box.min[1], box.min[2], 0.0f);
+            out.gates[2u * (size_t)node.childIndex + 1u] = make_float4(box.max[0], box.max[1], box.max[2], 0.0f);
+        }
+        else if (!childrenDone)
+        {
+            stack.push_back({ n, true }); stack.push_back({ node.childIndex + 1u, false }); stack.push_back({ node.childIndex, false });
+            continue;
+        }
+        else
+        {
+            const RtNode& c0 = out.nodes[node.childIndex]; const RtNode& c1 = out.nodes[node.childIndex + 1u];
+            RefitBox b0, b1;
+            memcpy(b0.min, c0.min, 12); memcpy(b0.max, c0.max, 12); memcpy(b1.min, c1.min, 12); memcpy(b1.max, c1.max, 12);
+            box = refitJoin(b0, b1);
+        }
+        memcpy(node.min, box.min, 12); memcpy(node.max, box.max, 12);
+    }
+    out.ok = true;
+    if (slotNode.empty()) return out;
+    if (slotNode.size() != wide.size() || !wideGridOver(out.nodes[0].min, out.nodes[0].max, out.grid)) return out;
+    out.gridOk = wideGridHolds(out.grid, out.nodes[0].min, out.nodes[0].max);   // false: the records below are clamped and must not be walked (rtgpu_update_mesh refuses before it writes)
+    for (size_t i = 0; i < slotNode.size(); ++i)
+    {
+        if (slotNode[i] == 0xFFFFFFFFu) continue;
+        if (slotNode[i] >= out.nodes.size()) { out.ok = out.gridOk = false; return out; }
+        const RtNode& node = out.nodes[slotNode[i]];
+        uint32_t v[6];
+        wideQuantiseBox(out.grid.base, out.grid.step, node.min, node.max, v);
+        for (int a = 0; a < 3; ++a)
+        {
+            const double lo = (double)out.grid.base[a] + (double)v[a] * (double)out.grid.step[a], hi = (double)out.grid.base[a] + (double)v[3 + a] * (double)out.grid.step[a];
+            if (lo > (double)node.min[a] - 0.5 * (double)out.grid.step[a] || hi < (double)node.max[a] + 0.5 * (double)out.grid.step[a]) out.gridOk = false;
+        }
+        const float4 rec = wideRecord(v, 0u);
+        out.wide[i].x = rec.x; out.wide[i].y = rec.y; out.wide[i].z = rec.z;
+    }
     return out;
 }
 
@@ -420,7 +605,21 @@ struct PreparedScene
     QuantBuild singleGrid; WideBuild single;   // single.ok: a single-mesh scene (Scene::Traverse's one-object bypass) with its 4-wide tree
     int leanScene = 0;
     bool axisParallelSun = false;
+    // what rtgpu_update_mesh needs (new beside the tables above, which are what they were): per mesh its plan and where its 4-wide level lies; per record of
+    // twoLevel.nodes' mesh levels / of single.nodes the node of `meshNodes` (a global, breadth-first index) whose box it holds, 0xFFFFFFFF: none
+    struct MeshLevel { uint32_t nodeBase = 0, numNodes = 0, gateBase = 0; bool have = false; };
+    std::vector<MeshRefitPlan> refit;
+    std::vector<MeshLevel> meshLevels;
+    std::vector<uint32_t> wide2SlotNode, wideSlotNode;
 };
+
+// WideBuild::slotNode of one mesh (the caller's node order, mesh-relative) as indices into the scene's breadth-first mesh nodes
+static void appendSlotNodes(std::vector<uint32_t>& to, const std::vector<uint32_t>& slotNode, const MeshRefitPlan& plan, const RtMesh& mesh)
+{
+    std::vector<uint32_t> position(mesh.numNodes, 0xFFFFFFFFu);   // the caller's index -> breadth-first position
+    for (size_t k = 0; k < plan.order.size(); ++k) if (plan.order[k] < mesh.numNodes) position[plan.order[k]] = (uint32_t)k;
+    for (const uint32_t n : slotNode) to.push_back(n < mesh.numNodes && position[n] != 0xFFFFFFFFu && plan.ok ? mesh.firstNode + position[n] : 0xFFFFFFFFu);
+}
 
 static PreparedScene prepareScene(const RtSceneDesc& s, uint32_t topDepth, uint32_t maxMeshDepth, bool allowLean, bool allowSimpleTextures)
 {
@@ -441,5 +640,26 @@ static PreparedScene prepareScene(const RtSceneDesc& s, uint32_t topDepth, uint3
     }
     p.leanScene = sceneClass(s, allowLean, allowSimpleTextures);
     p.axisParallelSun = hasAxisParallelSun(s.lights, s.numLights);
+    p.refit.resize(s.numMeshes); p.meshLevels.resize(s.numMeshes);
+    for (uint32_t m = 0; m < s.numMeshes; ++m)
+        p.refit[m] = planMeshRefit(s.meshNodes + s.meshes[m].firstNode, p.meshNodes.data() + s.meshes[m].firstNode, s.meshes[m].numNodes, s.meshes[m].numTriangles);
+    if (p.twoLevel.ok)
+    {
+        size_t record = 0;
+        for (const TwoLevelBuild::MeshLevel& l : p.twoLevel.meshLevels)   // in the order their records lie in twoLevel.nodes
+        {
+            const std::vector<uint32_t> slots(p.twoLevel.slotNode.begin() + record, p.twoLevel.slotNode.begin() + record + 4u * (size_t)l.numNodes);
+            appendSlotNodes(p.wide2SlotNode, slots, p.refit[l.meshIndex], s.meshes[l.meshIndex]);
+            p.meshLevels[l.meshIndex].nodeBase = l.nodeBase; p.meshLevels[l.meshIndex].numNodes = l.numNodes; p.meshLevels[l.meshIndex].gateBase = l.gateBase;
+            p.meshLevels[l.meshIndex].have = true;
+            record += 4u * (size_t)l.numNodes;
+        }
+    }
+    if (p.single.ok)
+    {
+        const uint32_t m = s.objects[0].meshIndex;
+        appendSlotNodes(p.wideSlotNode, p.single.slotNode, p.refit[m], s.meshes[m]);
+        p.meshLevels[m].nodeBase = 0u; p.meshLevels[m].numNodes = (uint32_t)(p.single.nodes.size() / 4u); p.meshLevels[m].gateBase = 0u; p.meshLevels[m].have = true;
+    }
     return p;
 }

@@ -18,6 +18,7 @@
 // A tree whose root is a leaf gets one node with that leaf as its only child.
 #pragma once
 
+#include <math.h>
 #include <stdint.h>
 #include "../../include/rtgpu.h"
 
@@ -36,6 +37,26 @@ static inline float4 make_float4(float x, float y, float z, float w) { return fl
 #define RT_WIDE_EMPTY 0xC0000000u    // leaf count 3 never occurs in the reference's trees (BVHBuilder.h:16): "no child"
 #define RT_QUANT_DONE 0xFFFFFFFFu   // cur: the ray is finished (same value as RT_LEVEL_EXHAUSTED: the mesh level has no node left)
 #define RT_QUANT_GRID 65535.0f
+
+// A box on a tree's grid: v = min.xyz, max.xyz, each the plane at least a full step outside the exact coordinate (in double, pushed out until it is), clamped to
+// 0 .. 65535.  One copy for the upload's builder (buildQuantBvh, rt_scene_prepare.h), the host's refit (refitMesh) and the device's (rt_runtime_refit.inl): -ffp-contract=off keeps the double arithmetic the same on both.
+#ifdef __HIPCC__
+#define RT_WIDE_HD __host__ __device__
+#else
+#define RT_WIDE_HD
+#endif
+RT_WIDE_HD static inline void wideQuantiseBox(const float base[3], const float step[3], const float lo[3], const float hi[3], uint32_t v[6])
+{
+    for (int a = 0; a < 3; ++a)
+    {
+        const double b = (double)base[a], s = (double)step[a], xlo = (double)lo[a], xhi = (double)hi[a];
+        long vmin = (long)floor((xlo - b) / s) - 1;
+        while (vmin > 0 && b + (double)(uint32_t)vmin * s > xlo - s) --vmin;
+        long vmax = (long)ceil((xhi - b) / s) + 1;
+        while (vmax < 65535 && b + (double)(uint32_t)vmax * s < xhi + s) ++vmax;
+        v[a] = (uint32_t)(vmin < 0 ? 0 : vmin); v[3 + a] = (uint32_t)(vmax > 65535 ? 65535 : vmax);
+    }
+}
 
 // the 4-wide tree of a single-mesh scene (k_trace_wide, k_trace_packet, k_tail)
 struct WideBvh

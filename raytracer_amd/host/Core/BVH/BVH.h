@@ -26,6 +26,7 @@ public:
     static_assert(sizeof(Node) == 32, "BVH node must be 32 bytes");
 
     const Node* GetNodes() const { return mNodes.data(); }
+    Node* GetNodes() { return mNodes.data(); }   // a refit rewrites boxes in place (MeshShape::UpdateVertices); the topology is the builder's
     uint32 GetNumNodes() const { return mNumNodes; }
 
 private:

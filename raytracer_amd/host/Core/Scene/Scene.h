@@ -28,6 +28,14 @@ public:
     // what rtgpu_update_objects takes after UpdateBVH; previousIndex relates the leaf order to the one before that UpdateBVH
     void GetUpdate(RtSceneUpdate& out) const;
     uint64 GetUpdateId() const { return mUpdateId; }   // UpdateBVH calls since the last BuildBVH
+    // Deforming meshes (mirror-only): MeshShape::UpdateVertices of the mesh the index-th AddObject call holds (numVertices must be the mesh's).  UpdateBVH then
+    // rewrites that mesh's flat nodes, triangles and vertex shading in place -- GetDesc() is the refit scene -- and lists it for the device:
+    // GetMeshUpdate(i) is what rtgpu_update_mesh takes for the i-th mesh the last UpdateBVH found changed, before that UpdateBVH's rtgpu_update_objects.
+    bool SetMeshVertices(uint32 index, uint32 numVertices, const math::Float3* positions, const math::Float3* normals, const math::Float3* tangents);
+    ShapePtr GetObjectShape(uint32 index) const;   // the shape of the index-th AddObject call (null: a light, or no such object): a second object may share it (an instance)
+    uint32 GetNumMeshUpdates() const { return (uint32)mDirtyMeshes.size(); }
+    void GetMeshUpdate(uint32 i, RtMeshUpdate& out) const;
+    bool ObjectsMovedInLastUpdate() const { return mObjectsMoved; }   // the last UpdateBVH changed a flat object, its place in the leaf order, or a light's matrices
 
     uint32 GetNumObjects() const { return (uint32)mAllObjects.size(); }
     const std::vector<const LightSceneObject*>& GetLights() const { return mLights; }
@@ -66,6 +74,11 @@ private:
     uint64 mBuildId = 0;
     std::vector<uint32> mPreviousIndex;
     uint64 mUpdateId = 0;
+    // per flat mesh its shape and the versions the flat arrays show; the flat meshes the last UpdateBVH rewrote (and whether their shading changed)
+    struct FlatMesh { const class MeshShape* shape; uint64 version, shadingVersion; };
+    std::vector<FlatMesh> mFlatMeshShapes;
+    std::vector<std::pair<uint32, bool>> mDirtyMeshes;
+    bool mObjectsMoved = false;
 };
 
 } // namespace rt

@@ -77,6 +77,15 @@ public:
     ~MeshShape() override;
     bool Initialize(const MeshDesc& desc);
 
+    // Deforming (mirror-only; the device's half is rtgpu_update_mesh).  New positions -- and optionally normals and tangents -- for the SAME vertices, in the
+    // order of the VertexBufferDesc the mesh was made from: the leaf order and the tree's topology stay, the triangles are recomputed with Initialize's
+    // arithmetic and every node's box is refitted with Math.h's Box operations (a leaf: its triangles' boxes joined in order; an interior node: Box(child0,
+    // child1)); the bounding box becomes the root's.  Scene::UpdateBVH picks the change up (GetVersion).
+    bool UpdateVertices(const math::Float3* positions, const math::Float3* normals, const math::Float3* tangents);
+    uint64 GetVersion() const { return mVersion; }                 // UpdateVertices calls so far
+    uint64 GetShadingVersion() const { return mShadingVersion; }   // the last of them that brought normals or tangents
+    const std::vector<math::Float3>& GetPositions() const { return mPositions; }   // of the last UpdateVertices (empty before the first)
+
     Kind GetKind() const override { return Kind::Mesh; }
     const math::Box GetBoundingBox() const override { return mBoundingBox; }
     void GetParams(float param[4], float param2[4]) const override;
@@ -94,6 +103,8 @@ private:
     std::vector<VertexIndices> mIndices;
     std::vector<VertexShading> mShading;
     std::vector<MaterialPtr> mMaterials;
+    std::vector<math::Float3> mPositions;
+    uint64 mVersion = 0, mShadingVersion = 0;
 };
 
 using MeshShapePtr = std::shared_ptr<MeshShape>;

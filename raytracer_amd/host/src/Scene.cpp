@@ -153,6 +153,53 @@ bool MeshShape::Initialize(const MeshDesc& desc)
     return true;
 }
 
+// post order: a node's box once both children have theirs
+static Box RefitNode(BVH::Node* nodes, uint32 index, const std::vector<Box>& triangleBoxes, uint32 depth)
+{
+    BVH::Node& node = nodes[index];
+    Box box = Box::Empty();
+    if (node.IsLeaf())
+    {
+        box = triangleBoxes[node.childIndex];
+        for (uint32 j = 1; j < node.numLeaves; ++j) box = Box(box, triangleBoxes[node.childIndex + j]);
+    }
+    else if (depth < BVH::MaxDepth)
+    {
+        const Box child0 = RefitNode(nodes, node.childIndex, triangleBoxes, depth + 1);
+        box = Box(child0, RefitNode(nodes, node.childIndex + 1, triangleBoxes, depth + 1));
+    }
+    node.min = box.min.ToFloat3(); node.max = box.max.ToFloat3();
+    return box;
+}
+
+bool MeshShape::UpdateVertices(const Float3* positions, const Float3* normals, const Float3* tangents)
+{
+    if (!positions) return false;
+    std::vector<Box> boxes(mTriangles.size());
+    for (size_t i = 0; i < mTriangles.size(); ++i)
+    {
+        const VertexIndices& idx = mIndices[i];
+        const Vector4 v0(positions[idx.i0]), v1(positions[idx.i1]), v2(positions[idx.i2]);
+        const Vector4 e1 = v1 - v0, e2 = v2 - v0;
+        Triangle& t = mTriangles[i];
+        t.v0[0] = v0.x; t.v0[1] = v0.y; t.v0[2] = v0.z;
+        t.edge1[0] = e1.x; t.edge1[1] = e1.y; t.edge1[2] = e1.z;
+        t.edge2[0] = e2.x; t.edge2[1] = e2.y; t.edge2[2] = e2.z;
+        boxes[i] = Box(v0, v1, v2);
+    }
+    if (mBVH.GetNumNodes() && !mTriangles.empty()) mBoundingBox = RefitNode(mBVH.GetNodes(), 0, boxes, 0);
+    mPositions.assign(positions, positions + mShading.size());
+    for (size_t i = 0; i < mShading.size(); ++i)
+    {
+        VertexShading& s = mShading[i];
+        if (normals) { s.normal[0] = normals[i].x; s.normal[1] = normals[i].y; s.normal[2] = normals[i].z; }
+        if (tangents) { s.tangent[0] = tangents[i].x; s.tangent[1] = tangents[i].y; s.tangent[2] = tangents[i].z; }
+    }
+    mVersion++;
+    if (normals || tangents) mShadingVersion = mVersion;
+    return true;
+}
+
 // ---------------------------------------------------------------------------------------------------
 // Lights
 // ---------------------------------------------------------------------------------------------------
@@ -281,6 +328,7 @@ bool Scene::Flatten()
     mFlatMaterials.clear(); mFlatMeshes.clear(); mFlatTriangles.clear(); mFlatVertexIndices.clear(); mFlatVertexShading.clear();
 
     mFlatTextures.clear(); mFlatTexels.clear();
+    mFlatMeshShapes.clear(); mDirtyMeshes.clear();
     bool texturesOk = true;
     std::map<const ITexture*, uint32> textureIds;
     std::function<uint32(const TexturePtr&)> internTexture = [&](const TexturePtr& t) -> uint32 {
@@ -342,6 +390,7 @@ bool Scene::Flatten()
         }
         const uint32 id = (uint32)mFlatMeshes.size();
         mFlatMeshes.push_back(flat);
+        mFlatMeshShapes.push_back({ mesh, mesh->GetVersion(), mesh->GetShadingVersion() });
         meshIds[mesh] = id;
         return id;
     };
@@ -463,6 +512,21 @@ bool Scene::UpdateBVH()
     for (const auto& object : mAllObjects)
         if (previous.count(object.get())) traceable.push_back(object.get());
     if (traceable.size() != mTraceableObjects.size()) return false;
+
+    // deformed meshes (MeshShape::UpdateVertices since the flat arrays were written): the same ranges, new boxes, triangles and vertex shading
+    mDirtyMeshes.clear();
+    for (uint32 id = 0; id < mFlatMeshShapes.size(); ++id)
+    {
+        FlatMesh& fm = mFlatMeshShapes[id];
+        if (fm.version == fm.shape->GetVersion()) continue;
+        const RtMesh& flat = mFlatMeshes[id];
+        if (flat.numNodes) memcpy(mFlatMeshNodes.data() + flat.firstNode, fm.shape->GetBVH().GetNodes(), sizeof(RtNode) * flat.numNodes);
+        if (flat.numTriangles) memcpy(mFlatTriangles.data() + flat.firstTriangle, fm.shape->GetTriangles().data(), sizeof(RtTriangle) * flat.numTriangles);
+        if (flat.numVertices) memcpy(mFlatVertexShading.data() + flat.firstVertex, fm.shape->GetVertexShading().data(), sizeof(RtVertexShading) * flat.numVertices);
+        mDirtyMeshes.push_back({ id, fm.shadingVersion != fm.shape->GetShadingVersion() });
+        fm.version = fm.shape->GetVersion(); fm.shadingVersion = fm.shape->GetShadingVersion();
+    }
+
     std::vector<Box> boxes;
     boxes.reserve(traceable.size());
     for (const ISceneObject* obj : traceable) boxes.push_back(obj->GetBoundingBox());
@@ -472,6 +536,7 @@ bool Scene::UpdateBVH()
     if (!builder.Build(boxes.data(), (uint32)traceable.size(), BvhBuildingParams(), newOrder)) return false;
 
     const std::vector<RtObject> oldFlat = mFlatObjects;
+    const std::vector<RtLight> oldLights = mFlatLights;
     mPreviousIndex.resize(traceable.size());
     for (uint32 i = 0; i < traceable.size(); ++i)
     {
@@ -488,6 +553,8 @@ bool Scene::UpdateBVH()
         mLights[i]->GetTransform().Store(mFlatLights[i].transform);
         mLights[i]->GetInverseTransform().Store(mFlatLights[i].invTransform);
     }
+    mObjectsMoved = oldLights.size() != mFlatLights.size() || (!oldLights.empty() && memcmp(oldLights.data(), mFlatLights.data(), sizeof(RtLight) * oldLights.size()) != 0);
+    for (uint32 i = 0; i < traceable.size(); ++i) mObjectsMoved = mObjectsMoved || mPreviousIndex[i] != i || memcmp(&oldFlat[i], &mFlatObjects[i], sizeof(RtObject)) != 0;
     mFlatTopNodes.clear();
     CopyNodes(mTraceableObjectsBVH, mFlatTopNodes);
     mDesc.numTopNodes = (uint32)mFlatTopNodes.size();
@@ -496,6 +563,33 @@ bool Scene::UpdateBVH()
     mDesc.lights = mFlatLights.data();
     mUpdateId++;
     return true;
+}
+
+bool Scene::SetMeshVertices(uint32 index, uint32 numVertices, const Float3* positions, const Float3* normals, const Float3* tangents)
+{
+    if (index >= mAllObjects.size() || mAllObjects[index]->GetType() != ISceneObject::Type::Shape) return false;
+    const ShapeSceneObject* object = static_cast<const ShapeSceneObject*>(mAllObjects[index].get());
+    if (object->GetShape()->GetKind() != IShape::Kind::Mesh) return false;
+    MeshShape* mesh = static_cast<MeshShape*>(object->GetShape().get());
+    if (numVertices != mesh->GetVertexShading().size()) return false;
+    return mesh->UpdateVertices(positions, normals, tangents);
+}
+
+ShapePtr Scene::GetObjectShape(uint32 index) const
+{
+    if (index >= mAllObjects.size() || mAllObjects[index]->GetType() != ISceneObject::Type::Shape) return nullptr;
+    return static_cast<const ShapeSceneObject*>(mAllObjects[index].get())->GetShape();
+}
+
+void Scene::GetMeshUpdate(uint32 i, RtMeshUpdate& out) const
+{
+    memset(&out, 0, sizeof(out));
+    out.abiVersion = RTGPU_ABI_VERSION;
+    out.meshIndex = mDirtyMeshes[i].first;
+    const RtMesh& flat = mFlatMeshes[out.meshIndex];
+    out.numVertices = flat.numVertices;
+    out.positions = reinterpret_cast<const float*>(mFlatMeshShapes[out.meshIndex].shape->GetPositions().data());
+    out.shading = mDirtyMeshes[i].second ? mFlatVertexShading.data() + flat.firstVertex : nullptr;
 }
 
 void Scene::GetUpdate(RtSceneUpdate& out) const

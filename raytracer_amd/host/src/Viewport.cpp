@@ -876,9 +876,22 @@ bool PathTracerMIS::EnsureSceneUploaded()
     if (mUploadedBuildId == mScene.GetBuildId() && mUploadedUpdateId + 1 == mScene.GetUpdateId())
     {
         // one Scene::UpdateBVH ahead of the device: its previousIndex relates exactly these two states
+        // deformed meshes first (each refitted on the device from its new positions), then the objects and the top level over the new boxes
+        for (uint32 i = 0; i < mScene.GetNumMeshUpdates(); ++i)
+        {
+            RtMeshUpdate meshUpdate;
+            mScene.GetMeshUpdate(i, meshUpdate);
+            if (rtgpu_update_mesh(mCtx, &meshUpdate) != RTGPU_OK)
+            {
+                fprintf(stderr, "[rt] ERROR: mesh update failed: %s\n", rtgpu_last_error());
+                return false;
+            }
+        }
         RtSceneUpdate update;
         mScene.GetUpdate(update);
-        if (rtgpu_update_objects(mCtx, &update) != RTGPU_OK)
+        // (a one-object scene has no top level: with a deformed mesh, the mesh update is all there is to send unless the object moved too)
+        const bool meshUpdateAlone = mScene.GetNumMeshUpdates() != 0 && update.numObjects == 1 && !mScene.ObjectsMovedInLastUpdate();
+        if (!meshUpdateAlone && rtgpu_update_objects(mCtx, &update) != RTGPU_OK)
         {
             fprintf(stderr, "[rt] ERROR: scene update failed: %s\n", rtgpu_last_error());
             return false;

@@ -219,6 +219,14 @@ RTH_API int rth_add_mesh(void* sh, uint32_t numVertices, uint32_t numTriangles, 
     return AddShape(s, mesh, transform, defaultMaterial);
 }
 
+// a further object over the SHAPE of the addIndex-th object (an instance: the scene holds the mesh once, Scene::Flatten interns it by its shape)
+RTH_API int rth_add_instance(void* sh, uint32_t addIndex, const float transform[16], int defaultMaterial)
+{
+    SceneHandle* s = static_cast<SceneHandle*>(sh);
+    const ShapePtr shape = s->scene.GetObjectShape(addIndex);
+    return shape ? AddShape(s, shape, transform, defaultMaterial) : -1;
+}
+
 static int AddLight(SceneHandle* s, LightPtr light, const float* transform)
 {
     LightSceneObjectPtr obj = std::make_unique<LightSceneObject>(std::move(light));
@@ -325,6 +333,22 @@ RTH_API int rth_scene_object_set_transform(void* sh, uint32_t addIndex, const fl
 RTH_API int rth_scene_update(void* sh) { return static_cast<SceneHandle*>(sh)->scene.UpdateBVH() ? 0 : -1; }
 // the RtSceneUpdate of the last rth_scene_update (pointers into the scene, valid until the next build or update)
 RTH_API void rth_scene_update_desc(void* sh, RtSceneUpdate* out) { static_cast<SceneHandle*>(sh)->scene.GetUpdate(*out); }
+// deforming meshes: MeshShape::UpdateVertices of the addIndex-th object's mesh (normals / tangents may be NULL: they stay); takes effect with rth_scene_update.
+// -1: no such mesh object, or another vertex count
+RTH_API int rth_scene_set_mesh_vertices(void* sh, uint32_t addIndex, uint32_t numVertices, const float* positions, const float* normals, const float* tangents)
+{
+    return positions && static_cast<SceneHandle*>(sh)->scene.SetMeshVertices(addIndex, numVertices, reinterpret_cast<const Float3*>(positions),
+                                                                              reinterpret_cast<const Float3*>(normals), reinterpret_cast<const Float3*>(tangents)) ? 0 : -1;
+}
+// the RtMeshUpdates of the last rth_scene_update (pointers into the scene, valid until the next build, update or rth_scene_set_mesh_vertices)
+RTH_API uint32_t rth_scene_mesh_update_count(void* sh) { return static_cast<SceneHandle*>(sh)->scene.GetNumMeshUpdates(); }
+RTH_API int rth_scene_mesh_update_desc(void* sh, uint32_t i, RtMeshUpdate* out)
+{
+    Scene& scene = static_cast<SceneHandle*>(sh)->scene;
+    if (i >= scene.GetNumMeshUpdates()) return -1;
+    scene.GetMeshUpdate(i, *out);
+    return 0;
+}
 
 // ---- camera -----------------------------------------------------------------------------------------
 RTH_API void* rth_camera_create() { return new Camera(); }

@@ -23,7 +23,18 @@ The history follows surfaces, not light: where a moved object's shadow was, and 
 allows.  Under the scene's sun (20 000 units through a one-degree cone) that lag dominates a RELATIVE error; --no-sun measures the same frames under the sky alone.
 Prints one JSON line and, with --output, writes it to a file.
 
-  python tools/bench_update.py [--reps 20] [--output profiles/update_bench_1080p.json]"""
+  python tools/bench_update.py [--reps 20] [--output profiles/update_bench_1080p.json]
+
+--deform: cost and worth of DEFORMING the mesh between frames instead (rtgpu_update_mesh).  The Sponza-class mesh alone (a single-mesh scene, bench.py's) under a
+travelling sine: every vertex is displaced along y by amplitude * sin(2 pi (x + z) / wavelength + phase), amplitude = `--amplitude` times the largest extent of
+the mesh's box (default 0.002: 6 cm on the 30 m hall), the wave one tenth of that extent long, the phase advanced by 0.4 rad per frame.  Times:
+  host_update            Scene.set_mesh_vertices() + Scene.update(): the mirror's own refit (host wall time)
+  update_mesh            Viewport.update_scene() -> rtgpu_update_mesh (host wall time; the call synchronises) and `bytes_uploaded` by it
+  upload_scene           rtgpu_upload_scene of the same deformed scene in the same run: the only way to do this before
+  pass_ms                ms per pass (wall, `--bench-passes` passes, synchronised) on the REFIT tree and on the same vertices built and uploaded AFRESH, at the
+                         amplitude and at four times it: the price of the kept topology and the kept collapse
+  rel_mse                after `--frames` frames against `--reference-passes` passes of the last frame's mesh: the history kept across the updates (every pixel of
+                         the deformed mesh starts anew at each, by design: there are no motion vectors for deforming surfaces) and dropped at every update"""
 import argparse
 import ctypes as C
 import json
@@ -55,6 +66,110 @@ def wall(fn, reps):
     return {"ms_median": float(np.median(ms)), "ms_min": float(ms.min()), "ms_max": float(ms.max())}
 
 
+def deform_main(args):
+    import raytracer_amd as ra
+    from raytracer_amd import scenes
+    w, h = args.width, args.height
+    pos, idx, nrm, tan, uv, mat = scenes.sponza_class_mesh(args.triangles, 7, refine=True)
+    pos = np.ascontiguousarray(pos, dtype=np.float32).reshape(-1, 3)
+    extent = float((pos.max(axis=0) - pos.min(axis=0)).max())
+    blue_noise = ra.load_blue_noise()
+
+    def wave(frame, amplitude):
+        p = pos.astype(np.float64)
+        p[:, 1] += amplitude * extent * np.sin(2.0 * math.pi * (p[:, 0] + p[:, 2]) / (0.1 * extent) + 0.4 * frame)
+        return p.astype(np.float32)
+
+    def build(positions):
+        scene = ra.Scene()
+        mats = [scene.add_material("diffuse", c) for _, c in scenes.SPONZA_MATERIALS]
+        scene.add_mesh(positions, idx, nrm, tan, uv, mat, mats)
+        scene.add_background_light((1.0, 1.5, 2.0))
+        if not args.no_sun:
+            scene.add_directional_light((20000.0, 19000.0, 18000.0), np.float32(1.0) / np.float32(180.0) * np.float32(3.14159265359),
+                                        ra.transform_from_euler((0.0, 0.0, 0.0), scenes.SPONZA_LIGHT_ORIENTATION))
+        scene.build()
+        scene.desc.contents.blueNoise = blue_noise.ctypes.data
+        vp = ra.Viewport(w, h, seed=1234, max_ray_depth=args.depth)
+        vp.set_renderer(scene)
+        return scene, vp
+    camera = ra.Camera((-12.5, 2.2, 0.6), (4.0, 82.0, 0.0), w / h, 65.0)
+    scene, vp = build(pos)
+    lib, ctx = ra.rtgpu_lib(), vp.device_context()
+    vp.render(camera, passes=1)
+    assert lib.rtgpu_synchronize(ctx) == 0
+    out = {"scene": "sponza_class, deforming", "triangles": int(scene.desc.contents.numTriangles), "vertices": int(len(pos)), "width": w, "height": h,
+           "amplitude_share_of_extent": args.amplitude, "extent": extent, "passes_per_frame": args.passes, "frames": args.frames, "sun": not args.no_sun,
+           "reference_passes": args.reference_passes, "reps": args.reps}
+
+    def deform_to(frame, amplitude):
+        scene.set_mesh_vertices(0, wave(frame, amplitude))
+        scene.update()
+        vp.update_scene()
+    for frame in range(3):
+        deform_to(frame, args.amplitude)
+    host, device = [], []
+    for frame in range(3, 3 + args.reps):
+        new = wave(frame, args.amplitude)
+        t0 = time.perf_counter(); scene.set_mesh_vertices(0, new); scene.update(); t1 = time.perf_counter(); vp.update_scene(); t2 = time.perf_counter()
+        host.append(1e3 * (t1 - t0)); device.append(1e3 * (t2 - t1))
+    stats = lambda ms: {"ms_median": float(np.median(ms)), "ms_min": float(min(ms)), "ms_max": float(max(ms))}   # noqa: E731
+    out["host_update"], out["update_mesh"] = stats(host), stats(device)
+    info = ra.update_info(ctx)
+    out["bytes_uploaded"], out["walk"], out["mesh_updates"] = info["bytesUploaded"], info["walk"], info["numMeshUpdates"]
+
+    def pass_ms(viewport):
+        context = viewport.device_context()
+        viewport.reset(); viewport.render(camera, passes=2); assert lib.rtgpu_synchronize(context) == 0
+        ms = []
+        for _ in range(3):
+            viewport.reset()
+            t0 = time.perf_counter(); viewport.render(camera, passes=args.bench_passes); assert lib.rtgpu_synchronize(context) == 0
+            ms.append(1e3 * (time.perf_counter() - t0) / args.bench_passes)
+        return float(np.median(ms))
+    out["pass_ms"] = {}
+    for factor in (1.0, 4.0):
+        deform_to(7, factor * args.amplitude)
+        refit = pass_ms(vp)
+        fresh_scene, fresh_vp = build(wave(7, factor * args.amplitude))
+        out["pass_ms"]["amplitude_x%g" % factor] = {"refit_tree": refit, "uploaded_afresh": pass_ms(fresh_vp)}
+        del fresh_vp, fresh_scene
+    deform_to(0, 0.0)
+    out["pass_ms"]["undeformed"] = pass_ms(vp)
+    # the upload of the same deformed scene, in the same run (after the timings above: an upload chooses the collapse anew)
+    deform_to(7, args.amplitude)
+    upload = lambda: lib.rtgpu_upload_scene(ctx, scene.desc)   # noqa: E731
+    assert upload() == 0
+    out["upload_scene"] = wall(upload, max(3, args.reps // 4))
+    out["update_share_of_upload"] = out["update_mesh"]["ms_median"] / out["upload_scene"]["ms_median"]
+
+    # ---- worth: the history kept across the updates against dropped at each ------------------------------------------------------------------------------
+    def chain(drop_history):
+        vp.reset_history()
+        for frame in range(args.frames):
+            deform_to(frame, args.amplitude)
+            vp.reset()
+            vp.render(camera, passes=args.passes)
+            guide = vp.next_pass_params(camera)
+            if drop_history:
+                vp.reset_history()
+            image = vp.denoise(guide, temporal=True, variance=True)
+        return np.asarray(image)
+    kept = chain(False)
+    raw = vp.sum_buffer() * np.float32(1.0 / args.passes)
+    dropped = chain(True)
+    vp.reset()
+    vp.render(camera, passes=args.reference_passes)
+    reference = (vp.sum_buffer() / np.float32(args.reference_passes)).astype(np.float64)
+    rel_mse = lambda image: float(((image.astype(np.float64) - reference) ** 2 / (reference ** 2 + 0.01)).mean())   # noqa: E731
+    out["rel_mse"] = {"raw_frame": rel_mse(raw), "history_kept": rel_mse(kept), "history_dropped_at_every_update": rel_mse(dropped)}
+    line = json.dumps(out)
+    print(line)
+    if args.output:
+        with open(args.output, "w") as f:
+            f.write(line + "\n")
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--reps", type=int, default=20)
@@ -70,7 +185,12 @@ def main():
     ap.add_argument("--clip", action="store_true", help="add the clipped columns: the same frames with the history clipped, once per gamma")
     ap.add_argument("--clip-gammas", default="1,2,4,8")
     ap.add_argument("--output", default=None)
+    ap.add_argument("--deform", action="store_true", help="measure rtgpu_update_mesh instead: the Sponza-class mesh under a travelling sine (see above)")
+    ap.add_argument("--amplitude", type=float, default=0.002, help="--deform: the wave's amplitude as a share of the mesh's largest extent")
+    ap.add_argument("--bench-passes", type=int, default=16, help="--deform: passes per timing of a pass")
     args = ap.parse_args()
+    if args.deform:
+        return deform_main(args)
     import torch
     import raytracer_amd as ra
     from raytracer_amd import scenes
