@@ -443,8 +443,10 @@ int rtgpu_get_update_info(RtgpuContext* ctx, RtUpdateInfo* out);
  *   ordering   as rtgpu_update_objects: queued passes are submitted first and show the old mesh; lanes, ray queries and AOV calls are waited for.  A
  *              multi-device context updates every peer (never run on two devices so far).
  *   refreshes  the tables above; the level records of every object that uses the mesh (instances share one level: one refit serves all); the grid of a
- *              single-mesh scene.  The photons of the bidirectional integrator are dropped.  The history of rtgpu_denoise_temporal is kept: pixels whose first
- *              hit lies on an object of the mesh start anew (their object's prevId is 0xFFFFFFFF in the table the call builds), all others reproject as before.
+ *              single-mesh scene.  The photons of the bidirectional integrator are dropped.  The history of rtgpu_denoise_temporal is kept: under
+ *              rtgpu_set_deform_tracking pixels whose first hit lies on an object of the mesh are followed through the triangle records the mesh had ("Temporal
+ *              accumulation that follows deforming meshes", below); without it they start anew (their object's prevId is 0xFFFFFFFF in the table the call
+ *              builds).  All others reproject as before.
  *   keeps      topology, materials, textures, the scene class, the chosen walk, the top level and the object table: when the mesh's box changed, the caller
  *              follows with rtgpu_update_objects and a top-level tree over the new boxes (rtgpu_read_mesh tells the new root box).
  * rtgpu_get_update_info counts these calls in _pad[0]; bytesUploaded is that of the last update of either kind.
@@ -1248,6 +1250,69 @@ int rtgpu_denoise_temporal_chain(RtgpuContext* ctx, const RtTemporalParams* para
 int rtgpu_denoise_temporal_chain_async(RtgpuContext* ctx, const RtTemporalParams* params, const RtDenoiseVarParams* filter,
                                        const RtPassParams* guideParams, const RtAovChain* chain, float* outRGB, float* outVariance,
                                        const RtTemporalClip* clip, float* outConfidence, void* stream);
+
+/* ---------------------------------------------------------------------------------------------
+ * Temporal accumulation that follows deforming meshes.  rtgpu_update_mesh moves a mesh's vertices; a pixel's surface point then was somewhere else in the
+ * previous frame, and no matrix says where.  The pixel itself does: the AOV call gives the triangle its first hit lies on (RT_AOV_SUB_OBJECT_ID, relative to
+ * the mesh, in the order of the mesh's triangle records) and the hit's barycentrics (RT_AOV_BARYCENTRICS), and v0 + u edge1 + v edge2 of the record that
+ * triangle had a frame ago is where the same surface point was, in the mesh's local space.  A record of the motion table with moved == RT_MOTION_DEFORMED
+ * marks an object whose mesh was deformed: its m takes the mesh-LOCAL position the point had then to the world position it had then (the object's transform
+ * of that time, word for word), _pad[0] is the first record of its mesh in prevTriangles and _pad[1] its triangle count; prevId is as before.  Records with
+ * moved 0 or 1 follow the rules of rtgpu_temporal_accumulate_moving, bit for bit.  Everything not restated here is rtgpu_temporal_accumulate_moving and
+ * rtgpu_temporal_accumulate_clip (clip may be NULL: no clipping, outConfidence is not written); tests/temporal_deform_ref.py is the same text in NumPy float32.
+ *   per pixel  with a valid hit, o = objectId_p < numObjects and moved[o] == RT_MOTION_DEFORMED: t = subObjectId_p, (u, v) = barycentrics_p.  The pixel starts
+ *              unless t < _pad[1] and _pad[0] + t < numPrevTriangles, the sum taken without 32-bit wrap-around: neither the table nor the triangle array is ever
+ *              read out of range, whatever the planes or a device-resident table hold.  Otherwise, with T = prevTriangles[_pad[0] + t], for lanes k = 0 .. 2
+ *                  L_k = T.edge1_k * u + T.v0_k;  L_k = T.edge2_k * v + L_k
+ *              and for lanes j = 0 .. 2
+ *                  P'_j = L.x * m[0][j] + m[3][j];  P'_j = L.y * m[1][j] + P'_j;  P'_j = L.z * m[2][j] + P'_j
+ *              every multiply and add rounded on its own.  N' = N_p: the shading normal is not carried back.
+ *   project, taps, blend, clip, outputs   unchanged: P' is projected, a tap is taken iff prevObjectId_q == prevId[o] and it passes the two surface tests against
+ *              P' and N'; what the caller keeps as the next history are the CURRENT N, P and ids.  The moments of a clip never use the moved pair.
+ *   identity   with no record of moved == RT_MOTION_DEFORMED every output is the words of rtgpu_temporal_accumulate_clip; with clip == NULL, of
+ *              rtgpu_temporal_accumulate_moving.
+ *   scope      deformations that keep the topology.  The turn the deformation gives the normal is left to normalThreshold, and so is a rigid move of the same
+ *              object between the same two frames: its position is followed exactly (m is the transform of then), its normal is not turned back.  Lighting that
+ *              changed with the shape is not reprojected (clip it).  Not followed inside reflections: the _chain entries have no such variant.
+ *   errors     those of rtgpu_temporal_accumulate_clip, except that clip == NULL is allowed; and RTGPU_ERR_INVALID_ARGUMENT for: deform NULL or objects NULL;
+ *              either plane NULL; prevTriangles NULL with numPrevTriangles > 0; _pad != 0; the host entry: a record with moved > RT_MOTION_DEFORMED, or a
+ *              deformed record with _pad[0] + _pad[1] > numPrevTriangles; the _async entry (which cannot read a device table: there the kernel's range test
+ *              alone stands): either plane violating the alignment or overlap rules, prevTriangles not 4-byte aligned.
+ * The table, the planes and prevTriangles are host memory for the synchronous entry and device memory for the _async one (deform itself is host memory).
+ *
+ * rtgpu_set_deform_tracking(ctx, 1) lets rtgpu_denoise_temporal[_clip][_async] follow rtgpu_update_mesh; off (the default) nothing changes, no launch and no
+ * byte.  With it on, an accepted rtgpu_update_mesh of a mesh that has not been updated since the history was stored copies the mesh's triangle records, device
+ * to device on the update's stream and before its first kernel, into a snapshot array over the scene's triangle numbering (36 bytes per triangle of the scene,
+ * allocated with the first snapshot, freed with the scene); further updates of that mesh before the next temporal call leave the snapshot alone -- it shows
+ * the mesh as the history saw it.  The mesh's objects keep the id they had and are marked deformed.  The next rtgpu_denoise_temporal[_clip][_async] then
+ * renders SUB_OBJECT_ID and BARYCENTRICS beside its five guide planes and is by definition the pure entry above on those planes, the snapshot (numPrevTriangles
+ * = the scene's triangle count) and the table of rtgpu_denoise_temporal with, for every marked object, moved = RT_MOTION_DEFORMED, m = the words of the
+ * transform the object had when the history was stored, _pad = { RtMesh::firstTriangle, RtMesh::numTriangles } and prevId as rtgpu_update_objects carried it.
+ * Storing a history invalidates every snapshot; rtgpu_upload_scene drops them with the history; a refused update takes none.  A mesh updated while tracking
+ * was off, or before a history existed, has no snapshot: its objects get prevId = 0xFFFFFFFF as ever.  Without a marked object the calls launch what they
+ * launched before, with the same arguments.  rtgpu_denoise_temporal_chain ignores tracking: there a deformed mesh's pixels start.  A multi-device context sets
+ * every peer (never run on two devices so far).
+ * --------------------------------------------------------------------------------------------- */
+#define RT_MOTION_DEFORMED 2u      /* RtObjectMotion::moved */
+typedef struct RtTemporalDeform {  /* 32 bytes */
+    const uint32_t*   subObjectId;    /* 1 x H x W: this frame's RT_AOV_SUB_OBJECT_ID */
+    const float*      barycentrics;   /* 2 x H x W: this frame's RT_AOV_BARYCENTRICS  */
+    const RtTriangle* prevTriangles;  /* [numPrevTriangles]: the records as they were when the history was stored */
+    uint32_t numPrevTriangles, _pad;
+} RtTemporalDeform;
+int rtgpu_temporal_accumulate_deform(RtgpuContext* ctx, const RtTemporalParams* params, uint32_t width, uint32_t height, const float* color,
+                                     const float* colorHalf, const float* depth, const float* normal, const float* position, const float* albedo,
+                                     const uint32_t* objectId, const float* prevA, const float* prevB, const float* prevLength, const float* prevDepth,
+                                     const float* prevNormal, const float* prevPosition, const uint32_t* prevObjectId, float* outA, float* outB,
+                                     float* outLength, float* outMotion, const RtObjectMotion* objects, uint32_t numObjects,
+                                     const RtTemporalClip* clip /* NULL: none */, float* outConfidence, const RtTemporalDeform* deform);
+int rtgpu_temporal_accumulate_deform_async(RtgpuContext* ctx, const RtTemporalParams* params, uint32_t width, uint32_t height, const float* color,
+                                           const float* colorHalf, const float* depth, const float* normal, const float* position, const float* albedo,
+                                           const uint32_t* objectId, const float* prevA, const float* prevB, const float* prevLength,
+                                           const float* prevDepth, const float* prevNormal, const float* prevPosition, const uint32_t* prevObjectId,
+                                           float* outA, float* outB, float* outLength, float* outMotion, const RtObjectMotion* objects,
+                                           uint32_t numObjects, const RtTemporalClip* clip, float* outConfidence, const RtTemporalDeform* deform, void* stream);
+int rtgpu_set_deform_tracking(RtgpuContext* ctx, int enable);
 
 /* rtgpu_postprocess over a caller's image (host memory, height x width x 3 floats of the context's size) in place of the sum buffer -- a
  * denoised frame, say: the same kernels, the same restrictions, and the same bits for the same input. */

@@ -492,8 +492,12 @@ class RtObjectMotion(C.Structure):
     _fields_ = [("m", C.c_float * 16), ("prevId", C.c_uint32), ("moved", C.c_uint32), ("_pad", C.c_uint32 * 2)]
 
 
-def object_motion_table(object_motion):
-    """(matrices (n, 4, 4), prev_ids (n,), moved (n,)) as the (n, 20) word array of RtObjectMotion records"""
+RT_MOTION_DEFORMED = 2
+
+
+def object_motion_table(object_motion, deform=None):
+    """(matrices (n, 4, 4), prev_ids (n,), moved (n,)) as the (n, 20) word array of RtObjectMotion records.  deform (temporal_accumulate's): moved goes in as it
+    is -- RT_MOTION_DEFORMED marks a deformed object -- and first_triangle, num_triangles (n,) fill the last two words."""
     matrices, prev_ids, moved = object_motion
     m = np.ascontiguousarray(matrices, dtype=np.float32).reshape(-1, 16)
     ids, flags = np.asarray(prev_ids).reshape(-1), np.asarray(moved).reshape(-1)
@@ -503,6 +507,11 @@ def object_motion_table(object_motion):
     table[:, :16] = m.view(np.uint32)
     table[:, 16] = ids.astype(np.uint32)
     table[:, 17] = (flags != 0).astype(np.uint32)
+    if deform is not None:
+        first, count = np.asarray(deform["first_triangle"]).reshape(-1), np.asarray(deform["num_triangles"]).reshape(-1)
+        if first.shape != ids.shape or count.shape != ids.shape:
+            raise ValueError("deform's first_triangle and num_triangles must hold one value per record of object_motion")
+        table[:, 17], table[:, 18], table[:, 19] = flags.astype(np.uint32), first.astype(np.uint32), count.astype(np.uint32)
     return table
 
 
@@ -520,6 +529,13 @@ class RtTemporalChain(C.Structure):
 
 
 CHAIN_KEYS = ("virtual_position", "chain_length", "chain_distance")
+
+
+class RtTemporalDeform(C.Structure):
+    _fields_ = [("subObjectId", C.c_void_p), ("barycentrics", C.c_void_p), ("prevTriangles", C.c_void_p), ("numPrevTriangles", C.c_uint32), ("_pad", C.c_uint32)]
+
+
+DEFORM_KEYS = ("sub_object_id", "barycentrics", "prev_triangles", "first_triangle", "num_triangles")
 
 
 def temporal_clip(clip):
@@ -540,7 +556,7 @@ def temporal_clip(clip):
 def temporal_accumulate(color, color_half, depth, normal, position, albedo=None, object_id=None, history=None, prev_world_to_screen=None, prev_sample_offset=(0.0, 0.0),
                         alpha_min=TEMPORAL_DEFAULTS["alpha_min"], max_history=TEMPORAL_DEFAULTS["max_history"], normal_threshold=TEMPORAL_DEFAULTS["normal_threshold"],
                         plane_tolerance=TEMPORAL_DEFAULTS["plane_tolerance"], color_scale=1.0, demodulate=True, return_motion=False, ctx=None, object_motion=None,
-                        clip=None, return_confidence=False, chain=None):
+                        clip=None, return_confidence=False, chain=None, deform=None):
     """Temporal accumulation of include/rtgpu.h over a frame: color, color_half (H, W, 3) -- Viewport.sum_buffer(secondary=True) --, depth (H, W) or (1, H, W),
     normal, position, albedo (3, H, W) float32 and object_id (H, W) or (1, H, W) uint32 (optional) -- Viewport.render_aovs() --, as NumPy arrays or as
     contiguous torch tensors on a ROCm device (object_id: the int64 tensor render_aovs(device=True) returns, or int32 words), then on
@@ -558,8 +574,18 @@ def temporal_accumulate(color, color_half, depth, normal, position, albedo=None,
     chain=dict(virtual_position=(3, H, W) float32, chain_length=(H, W) or (1, H, W) uint32 (or the int64 tensor render_aovs returns), chain_distance=(H, W) or
     (1, H, W) float32) -- Viewport.render_aovs(chain=N) --: the guides are chain guides (rtgpu_temporal_accumulate_chain): the virtual position is reprojected,
     the plane tolerance scales with the chain distance, and histories of different chain lengths stay apart; with object_motion a pixel with a chain starts.
-    With or without clip and object_motion.  The returned history then carries chain_length, which a history passed beside chain must have."""
+    With or without clip and object_motion.  The returned history then carries chain_length, which a history passed beside chain must have.
+    deform=dict(sub_object_id=(H, W) or (1, H, W) uint32 (or the int64 tensor render_aovs returns), barycentrics=(2, H, W) float32 -- this frame's
+    Viewport.render_aovs() planes --, prev_triangles=(T, 9) float32: the triangle records deformed meshes had when the history was stored (read_mesh; a NumPy
+    array, or beside tensors also a tensor), first_triangle=(n,), num_triangles=(n,)) beside an object_motion whose `moved` may hold RT_MOTION_DEFORMED: a deformed
+    object's pixels are followed through their triangle's old record (rtgpu_temporal_accumulate_deform).  For such a record the matrix is the object's transform
+    of then and first_triangle / num_triangles its mesh's range of prev_triangles.  With or without clip; not with chain."""
     clip = temporal_clip(clip)
+    if deform is not None:
+        if not isinstance(deform, dict) or set(deform) != set(DEFORM_KEYS):
+            raise ValueError("deform must be a dict with the keys " + ", ".join(DEFORM_KEYS))
+        if chain is not None or object_motion is None:
+            raise ValueError("deform goes with object_motion and without chain")
     if return_confidence and clip is None:
         raise ValueError("return_confidence=True needs clip")
     if chain is not None:
@@ -569,7 +595,7 @@ def temporal_accumulate(color, color_half, depth, normal, position, albedo=None,
             raise ValueError("chain needs a history with chain_length: one a call with chain returned")
     table = None
     if object_motion is not None:
-        table = object_motion_table(object_motion)
+        table = object_motion_table(object_motion, deform)
         if object_id is None or (history is not None and history.get("object_id") is None):
             raise ValueError("object_motion follows objects by their ids: it needs object_id and a history with one")
     planes = dict(color=color, color_half=color_half, depth=depth, normal=normal, position=position)
@@ -593,6 +619,8 @@ def temporal_accumulate(color, color_half, depth, normal, position, albedo=None,
             planes["prev_chain_length"] = history["chain_length"]
     if chain is not None:
         planes.update(chain)
+    if deform is not None:
+        planes.update(sub_object_id=deform["sub_object_id"], barycentrics=deform["barycentrics"])
     if getattr(color, "ndim", 0) != 3 or color.shape[2] != 3:
         raise ValueError("color must be an (H, W, 3) float32 array or tensor")
     h, w = int(color.shape[0]), int(color.shape[1])
@@ -600,7 +628,8 @@ def temporal_accumulate(color, color_half, depth, normal, position, albedo=None,
     # (in the order of the entry's arguments)
     shapes = dict(color=image, color_half=image, depth=one, normal=three, position=three, albedo=three, object_id=one, prev_a=image, prev_b=image, prev_length=one,
                   prev_depth=one, prev_normal=three, prev_position=three, prev_object_id=one)
-    planes, ptr, empty, index, torch = _image_planes(planes, dict(shapes, virtual_position=three, chain_length=one, chain_distance=one, prev_chain_length=one))
+    planes, ptr, empty, index, torch = _image_planes(planes, dict(shapes, virtual_position=three, chain_length=one, chain_distance=one, prev_chain_length=one,
+                                                                 sub_object_id=one, barycentrics=((2, h, w),)))
     p = temporal_params(alpha_min, max_history, normal_threshold, plane_tolerance, color_scale, demodulate, prev_world_to_screen if history is not None else None,
                         prev_sample_offset)
     out = dict(a=empty((h, w, 3)), b=empty((h, w, 3)), length=empty((h, w)))
@@ -612,7 +641,21 @@ def temporal_accumulate(color, color_half, depth, normal, position, albedo=None,
         with torch.cuda.device(index):
             table = torch.from_numpy(table.view(np.int32)).to(color.device)   # (ordered on the current stream, which the side stream waits for)
     moving = [ptr(table), C.c_uint32(0 if table is None else table.shape[0])]
-    if chain is not None:
+    if deform is not None:
+        triangles = deform["prev_triangles"]
+        if torch is None or isinstance(triangles, np.ndarray):
+            triangles = np.ascontiguousarray(triangles, dtype=np.float32)
+            if torch is not None:
+                with torch.cuda.device(index):
+                    triangles = torch.from_numpy(triangles).to(color.device)
+        elif not (isinstance(triangles, torch.Tensor) and triangles.dtype == torch.float32 and triangles.device == color.device and triangles.is_contiguous()):
+            raise ValueError("prev_triangles must be a float32 NumPy array or a contiguous float32 tensor on the colour's ROCm device")
+        if triangles.ndim != 2 or triangles.shape[1] != 9:
+            raise ValueError("prev_triangles must have the shape (T, 9)")
+        block = RtTemporalDeform(ptr("sub_object_id"), ptr("barycentrics"), ptr(triangles) if triangles.shape[0] else None, int(triangles.shape[0]), 0)
+        _image_call(torch, index, "temporal_accumulate", ctx, "rtgpu_temporal_accumulate_deform",
+                    args + moving + [C.byref(clip) if clip is not None else None, ptr(confidence), C.byref(block)], tensors + [table, triangles])
+    elif chain is not None:
         block = RtTemporalChain(*[ptr(name) for name in CHAIN_KEYS + ("prev_chain_length",)])
         _image_call(torch, index, "temporal_accumulate", ctx, "rtgpu_temporal_accumulate_chain",
                     args + moving + [C.byref(clip) if clip is not None else None, ptr(confidence), C.byref(block)], tensors + [table])
@@ -934,6 +977,7 @@ class Viewport:
         self.width, self.height = int(width), int(height)
         self._scene = None
         self.has_renderer = False
+        self._track_deformation = False
         self._query_streams, self._denoise_streams = {}, {}   # the side streams of _run_on_torch_stream: ray queries and AOVs, denoise
         if host_lib().rth_viewport_set_params(self._h, C.c_uint32(dimensions), int(bool(use_blue_noise)), C.c_float(anti_aliasing_spread),
                                               C.c_uint32(max_ray_depth), C.c_uint32(min_russian_roulette_depth), int(bool(light_sampling_all))) != 0:
@@ -968,6 +1012,8 @@ class Viewport:
             err = rtgpu_lib().rtgpu_last_error()
             raise RuntimeError("CreateRenderer(%r) failed (%d): %s" % (name, r, err.decode() if err else ""))
         self.has_renderer = True
+        if self._track_deformation:
+            self.track_deformation(True)
         if intersection_counters:
             rtgpu_lib().rtgpu_set_intersection_counters(self.device_context(), 1)
         self.reset()
@@ -1001,6 +1047,15 @@ class Viewport:
 
     def reset(self):
         host_lib().rth_viewport_reset(self._h)
+
+    def track_deformation(self, enable=True):
+        """rtgpu_set_deform_tracking: denoise(temporal=True) follows meshes deformed through Scene.set_mesh_vertices / update_scene() -- pixels on them keep
+        their history, reprojected through the triangle records the mesh had a frame ago -- at the price of a device copy of those records per deformed mesh
+        and frame and two more guide planes.  Off by default: such pixels then start.  A call before the device context exists is remembered and applied
+        when set_renderer makes it."""
+        self._track_deformation = bool(enable)
+        if self.has_renderer and rtgpu_lib().rtgpu_set_deform_tracking(self.device_context(), C.c_int(int(self._track_deformation))) != 0:
+            raise RuntimeError("rtgpu_set_deform_tracking failed: %s" % (rtgpu_lib().rtgpu_last_error() or b"").decode())
 
     def update_scene(self):
         """Viewport::UpdateScene: after Scene.update(), sends the new positions of every deformed mesh (Scene.set_mesh_vertices; rtgpu_update_mesh refits its
@@ -1303,7 +1358,8 @@ class Viewport:
         confidence plane to what is returned.
         chain=N (0..16), with temporal=True (rtgpu_denoise_temporal_chain): the guides are the chain guides render_aovs(chain=N) renders and the history is
         reprojected through mirrors and glass by the virtual position; with or without clip.  The chain is this call's own: set_guide_chain does not affect it.
-        chain=None is the call without, word for word -- its refusal under set_guide_chain included."""
+        chain=None is the call without, word for word -- its refusal under set_guide_chain included.
+        After track_deformation() the call (without chain) follows meshes deformed since the last such call: their pixels keep their history."""
         clip = temporal_clip(clip)
         if chain is not None and not temporal:
             raise ValueError("chain needs temporal=True (set_guide_chain steers the calls without a history)")

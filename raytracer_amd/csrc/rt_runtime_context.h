@@ -182,6 +182,10 @@ struct RtgpuContext
         std::vector<Mesh> meshes; std::vector<RtMesh> meshTable;
         std::vector<RtVertexIndices> vertexIndices;                   // the caller's, as uploaded: every update takes the new root box from them before it writes; a mesh's first update copies its share to the device
         const uint32_t* wide2SlotNode = nullptr; const uint32_t* wideSlotNode = nullptr;   // per 4-wide record the mesh node whose box it holds (PreparedScene), on the device
+        // rtgpu_set_deform_tracking: the triangle records deformed meshes had when the temporal history was stored -- one device array over the scene's triangle
+        // numbering, made with the first snapshot, in sceneAllocs -- and per mesh what happened since that history: 0 untouched, 1 its range of the array holds
+        // its snapshot, 2 it was updated without one (its pixels start)
+        RtTriangle* deformSnapshot = nullptr; std::vector<uint8_t> deformState;
     } updatable;
 
     // film
@@ -350,8 +354,10 @@ struct RtgpuContext
         float worldToScreen[16] = {}, sampleOffset[2] = {};   // of the pass that frame's guides were rendered with
         // moving objects: per CURRENT object the id and transform it had when the history was stored (rtgpu_update_objects carries them through its
         // permutations and raises movedSince); the device copy of the RtObjectMotion table built from them
-        struct Then { uint32_t id; float transform[16]; };
+        // (deformed: the object's mesh was deformed under a snapshot since then -- its id stays, and the call follows the deformation)
+        struct Then { uint32_t id; float transform[16]; uint32_t deformed; };
         std::vector<Then> then; bool movedSince = false;
+        bool trackDeform = false;                         // rtgpu_set_deform_tracking
         RtObjectMotion* motion = nullptr; size_t motionCapacity = 0;
         // history clipping: two planes of `momentsCapacity` 16-byte records, {mu.rgb, cnt} and {g.rgb, 0} (32 bytes per pixel), of the clipped calls, pure or not
         float4* moments = nullptr; size_t momentsCapacity = 0;

@@ -54,7 +54,7 @@ template <class T> static int ensureScratch(RtgpuContext* c, T*& buffer, size_t&
 struct Plane { const void* ptr; uint32_t floatsPerPixel; bool output; };
 struct PlaneTable
 {
-    Plane planes[23]; uint32_t count;
+    Plane planes[25]; uint32_t count;
     bool has(uint32_t k) const { return planes[k].ptr != nullptr; }
     const float* in(uint32_t k) const { return (const float*)planes[k].ptr; }
     const uint32_t* ids(uint32_t k) const { return (const uint32_t*)planes[k].ptr; }
@@ -229,6 +229,7 @@ struct FrameStep
     hipStream_t stream; size_t pixels, stride;
     float* depth; float* normal; float* position; float* albedo; uint32_t* id; float* extra; float* out; float* variance; float* outHost; float* varianceHost;
     uint32_t* chainLength; float* chainDistance; float* virtualPosition;   // (virtualChain only: the last five floats per pixel of `extra`)
+    uint32_t* subObjectId; float* barycentrics;                            // (deformPlanes only: the last three floats per pixel of `extra`)
 };
 
 // The checks of a frame call behind those of its parameter blocks; then every queued pass is in the sum buffer, `stream` stands behind the previous call, and the first
@@ -236,9 +237,10 @@ struct FrameStep
 // (its arena, never a lane's) -- or, under rtgpu_set_guide_chain, the guide vertices of the paths it generates, through the chain call.  outHost or outDevice; outVariance (optional) is memory of the same kind, written with writesVariance only; outPlane (optional, beside
 // outDevice only): one more device output of a float per pixel, held to the same rules.  virtualChain (rtgpu_denoise_temporal_chain; or NULL): the guides are rendered
 // through rtgpu_render_aovs_virtual_async with this chain, whatever rtgpu_set_guide_chain says, and CHAIN_LENGTH, CHAIN_DISTANCE and VIRTUAL_POSITION beside them
-// into the last five floats per pixel of the caller's `extra` planes
+// into the last five floats per pixel of the caller's `extra` planes.  deformPlanes (a temporal call that follows a deformed mesh; never beside a chain): SUB_OBJECT_ID
+// and BARYCENTRICS are rendered beside the guides, into the last three floats per pixel of `extra`
 static int beginFrame(RtgpuContext* c, const RtPassParams* guideParams, float* outHost, float* outDevice, float* outVariance, bool writesVariance, void* streamHandle,
-                      uint32_t guides, uint32_t extraFloatsPerPixel, FrameStep& f, float* outPlane = nullptr, const RtAovChain* virtualChain = nullptr)
+                      uint32_t guides, uint32_t extraFloatsPerPixel, FrameStep& f, float* outPlane = nullptr, const RtAovChain* virtualChain = nullptr, bool deformPlanes = false)
 {
     if (!guideParams || (!outHost && !outDevice)) return fail(RTGPU_ERR_INVALID_ARGUMENT, "NULL argument");
     if (outDevice && (((uintptr_t)outDevice | (uintptr_t)outVariance | (uintptr_t)outPlane) & 15u)) return fail(RTGPU_ERR_INVALID_ARGUMENT, "the output must be a 16-byte aligned device buffer");
@@ -275,6 +277,7 @@ static int beginFrame(RtgpuContext* c, const RtPassParams* guideParams, float* o
     const uint32_t planes[5] = { RT_AOV_DEPTH, RT_AOV_NORMAL, RT_AOV_POSITION, RT_AOV_BASE_COLOR, RT_AOV_OBJECT_ID };
     void* const outputs[5] = { f.depth, f.normal, f.position, f.albedo, f.id };
     f.chainLength = nullptr; f.chainDistance = nullptr; f.virtualPosition = nullptr;
+    f.subObjectId = nullptr; f.barycentrics = nullptr;
     if (virtualChain)
     {
         f.chainLength = (uint32_t*)(f.extra + (extraFloatsPerPixel - 5u) * plane); f.chainDistance = (float*)f.chainLength + plane; f.virtualPosition = f.chainDistance + plane;
@@ -287,6 +290,13 @@ static int beginFrame(RtgpuContext* c, const RtPassParams* guideParams, float* o
         // rtgpu_set_guide_chain: the same planes at the guide vertex of every pixel's path
         const RtAovChain chain = { c->chain.guideMaxChain, 0u, { 0u, 0u } };
         return rtgpu_render_aovs_chain_async(c, guideParams, &chain, planes, guides, outputs, f.stream);
+    }
+    if (deformPlanes)
+    {
+        f.subObjectId = (uint32_t*)(f.extra + (extraFloatsPerPixel - 3u) * plane); f.barycentrics = (float*)f.subObjectId + plane;
+        const uint32_t deformAovs[7] = { RT_AOV_DEPTH, RT_AOV_NORMAL, RT_AOV_POSITION, RT_AOV_BASE_COLOR, RT_AOV_OBJECT_ID, RT_AOV_SUB_OBJECT_ID, RT_AOV_BARYCENTRICS };
+        void* const deformOutputs[7] = { f.depth, f.normal, f.position, f.albedo, f.id, f.subObjectId, f.barycentrics };
+        return rtgpu_render_aovs_async(c, guideParams, deformAovs, 7u, deformOutputs, f.stream);
     }
     return rtgpu_render_aovs_async(c, guideParams, planes, guides, outputs, f.stream);
 }

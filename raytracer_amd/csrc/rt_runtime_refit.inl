@@ -192,6 +192,20 @@ RTGPU_API int rtgpu_update_mesh(RtgpuContext* c, const RtMeshUpdate* u)
     TriangleShading* const shading = reinterpret_cast<TriangleShading*>(const_cast<RtVertexIndices*>(c->sceneDev.vertexIndices)) + mesh.firstTriangle;
     const hipStream_t stream = c->lanes[0].stream;
     auto blocks = [](uint32_t n) { return dim3((n + RT_REFIT_BLOCK - 1u) / RT_REFIT_BLOCK); };
+    // rtgpu_set_deform_tracking: the records as the temporal history saw them, kept before the first kernel overwrites them -- once per mesh and history: a
+    // second update before the next temporal call leaves the snapshot alone.  (Every check has passed: a refused update takes none.)
+    const bool haveHistory = c->temporal.have && c->temporal.then.size() == up.objects.size();
+    if (up.deformState.size() != up.meshTable.size()) up.deformState.assign(up.meshTable.size(), (uint8_t)0u);
+    uint8_t& deformState = up.deformState[u->meshIndex];
+    if (!haveHistory) deformState = 0u;
+    else if (!c->temporal.trackDeform) deformState = 2u;
+    else if (deformState == 0u)
+    {
+        if ((r = refitBuffer(c, up.deformSnapshot, c->sceneDev.numTriangles))) return r;
+        if (c->denoise.done) HIP_TRY(hipEventSynchronize(c->denoise.done));   // (the temporal call that followed the last deformation may still read the array, on a stream of the caller's)
+        HIP_TRY(hipMemcpyAsync(up.deformSnapshot + mesh.firstTriangle, triangles, (size_t)mesh.numTriangles * sizeof(RtTriangle), hipMemcpyDeviceToDevice, stream));
+        deformState = 1u;
+    }
     hipLaunchKernelGGL(k_refit_triangles, blocks(mesh.numTriangles), dim3(RT_REFIT_BLOCK), 0, stream, state.indices, state.positions, u->shading ? state.shading : nullptr,
                        triangles, shading, mesh.numTriangles);
     hipLaunchKernelGGL(k_refit_leaves, blocks(numPositions), dim3(RT_REFIT_BLOCK), 0, stream, nodes, numPositions, state.indices, state.positions, gate);
@@ -229,11 +243,16 @@ RTGPU_API int rtgpu_update_mesh(RtgpuContext* c, const RtMeshUpdate* u)
     }
     if (haveWide && !twoLevel) copyGrid(c->wide, grid);
     c->vcm.havePhotons = false;   // photons of the mesh as it was
-    if (c->temporal.have && c->temporal.then.size() == up.objects.size())
+    if (haveHistory)
     {
-        // rtgpu_denoise_temporal's history stays; no tap of it matches an object of this mesh any more: those pixels start
+        // rtgpu_denoise_temporal's history stays.  Under a snapshot the objects of this mesh keep the id they had and are marked: the next call follows the
+        // deformation.  Otherwise no tap of the history matches an object of this mesh any more: those pixels start
         for (size_t o = 0; o < up.objects.size(); ++o)
-            if (up.objects[o].objectKind == RT_OBJECT_SHAPE && up.objects[o].shapeKind == RT_SHAPE_MESH && up.objects[o].meshIndex == u->meshIndex) c->temporal.then[o].id = 0xFFFFFFFFu;
+            if (up.objects[o].objectKind == RT_OBJECT_SHAPE && up.objects[o].shapeKind == RT_SHAPE_MESH && up.objects[o].meshIndex == u->meshIndex)
+            {
+                if (deformState == 1u) c->temporal.then[o].deformed = 1u;
+                else { c->temporal.then[o].id = 0xFFFFFFFFu; c->temporal.then[o].deformed = 0u; }
+            }
         c->temporal.movedSince = true;
     }
     else c->temporal.have = false;

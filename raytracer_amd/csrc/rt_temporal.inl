@@ -19,6 +19,12 @@
 //                     own surface, from an LDS tile; two 16-byte records per pixel
 //   k_temporal<., true>   the same kernel reading those records (coalesced): the reprojected A is clipped to mu +- g, B shifted along, the history length cut by how
 //                     far A was pulled.  A compile-time variant: the two instantiations without it are what they were.
+//   k_temporal<true, ., true>   a mesh was deformed between the two frames (rtgpu_temporal_accumulate_deform): three coalesced plane words more per pixel -- the
+//                     triangle the first hit lies on and its barycentrics -- and, for lanes on a deformed object, one 36-byte gather (nine dwords: the record is
+//                     4-byte aligned) of the triangle as it was when the history was stored.  v0 + u edge1 + v edge2 of that record, through the object's
+//                     transform of then, is where the surface point was; the normal is not carried back.  A triangle id outside the record's range, or a range
+//                     outside the array, starts the pixel before anything is read.  A compile-time variant of the moving kernels only: the four
+//                     instantiations without it are what they were.
 //   k_temporal_chain, k_temporal_moments_chain<r>   rtgpu_temporal_accumulate_chain: the same two bodies over chain guides (rt_temporal_body.inl and
 //                     rt_temporal_moments_body.inl, each compiled a second time under RT_TEMPORAL_CHAIN) -- the virtual position is projected, the plane tolerance scales with the chain distance, a tap or a window pixel
 //                     of another chain length is dropped; the chain length rides in the free lane of the {P.xyz, .} history record
@@ -71,7 +77,7 @@ template __global__ void RT_TEMPORAL_MOMENTS_ATTR k_temporal_moments_chain<2> RT
 template __global__ void RT_TEMPORAL_MOMENTS_ATTR k_temporal_moments_chain<3> RT_K_TEMPORAL_MOMENTS_CHAIN_ARGS;
 
 // k_temporal and k_temporal_chain: ONE body (rt_temporal_body.inl), compiled twice, as k_shade's is.  The chain blocks are preprocessor blocks, so k_temporal
-// is the token stream it was and its four instantiations are the code they were.
+// is the token stream it was and its four instantiations are the code they were.  k_temporal alone has the third template argument (kDeform).
 #define RT_TEMPORAL_KERNEL k_temporal
 #define RT_TEMPORAL_CHAIN 0
 #include "rt_temporal_body.inl"
@@ -83,10 +89,12 @@ template __global__ void RT_TEMPORAL_MOMENTS_ATTR k_temporal_moments_chain<3> RT
 #undef RT_TEMPORAL_KERNEL
 #undef RT_TEMPORAL_CHAIN
 
-template __global__ void RT_ATROUS_ATTR k_temporal<false, false>(const TemporalIn, const TemporalOut, uint32_t, uint32_t, const TemporalFrame);
-template __global__ void RT_ATROUS_ATTR k_temporal<true, false>(const TemporalIn, const TemporalOut, uint32_t, uint32_t, const TemporalFrameMoving);
-template __global__ void RT_ATROUS_ATTR k_temporal<false, true>(const TemporalIn, const TemporalOut, uint32_t, uint32_t, const TemporalFrameClip<TemporalFrame>);
-template __global__ void RT_ATROUS_ATTR k_temporal<true, true>(const TemporalIn, const TemporalOut, uint32_t, uint32_t, const TemporalFrameClip<TemporalFrameMoving>);
+template __global__ void RT_ATROUS_ATTR k_temporal<false, false, false>(const TemporalIn, const TemporalOut, uint32_t, uint32_t, const TemporalFrame);
+template __global__ void RT_ATROUS_ATTR k_temporal<true, false, false>(const TemporalIn, const TemporalOut, uint32_t, uint32_t, const TemporalFrameMoving);
+template __global__ void RT_ATROUS_ATTR k_temporal<false, true, false>(const TemporalIn, const TemporalOut, uint32_t, uint32_t, const TemporalFrameClip<TemporalFrame>);
+template __global__ void RT_ATROUS_ATTR k_temporal<true, true, false>(const TemporalIn, const TemporalOut, uint32_t, uint32_t, const TemporalFrameClip<TemporalFrameMoving>);
+template __global__ void RT_ATROUS_ATTR k_temporal<true, false, true>(const TemporalIn, const TemporalOut, uint32_t, uint32_t, const TemporalFrameDeform);
+template __global__ void RT_ATROUS_ATTR k_temporal<true, true, true>(const TemporalIn, const TemporalOut, uint32_t, uint32_t, const TemporalFrameClip<TemporalFrameDeform>);
 template __global__ void RT_ATROUS_ATTR k_temporal_chain<false, false>(const TemporalIn, const TemporalOut, uint32_t, uint32_t, const TemporalFrame, const TemporalChainPlanes);
 template __global__ void RT_ATROUS_ATTR k_temporal_chain<true, false>(const TemporalIn, const TemporalOut, uint32_t, uint32_t, const TemporalFrameMoving, const TemporalChainPlanes);
 template __global__ void RT_ATROUS_ATTR k_temporal_chain<false, true>(const TemporalIn, const TemporalOut, uint32_t, uint32_t, const TemporalFrameClip<TemporalFrame>, const TemporalChainPlanes);

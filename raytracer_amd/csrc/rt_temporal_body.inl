@@ -3,13 +3,18 @@
 // plane loads more (the chain length, the chain distance and -- static frames only -- the virtual position), one integer compare per tap against the chain
 // length in the free lane of the {P.xyz, .} history record, and that lane written for the next frame.  With objects moved a pixel with a chain starts, so the
 // moving variant projects the moved first-hit pair as ever and never loads the virtual position.
-template <bool kMoving, bool kClip> __global__ void RT_ATROUS_ATTR RT_TEMPORAL_KERNEL
+// k_temporal's third argument, kDeform (moving variants only; k_temporal_chain has none: a pixel with a chain starts when anything moved): an object whose
+// motion record says RT_MOTION_DEFORMED takes its point of then from the triangle record its mesh had then.
 #if RT_TEMPORAL_CHAIN
-    RT_K_TEMPORAL_CHAIN_ARGS
+template <bool kMoving, bool kClip> __global__ void RT_ATROUS_ATTR RT_TEMPORAL_KERNEL RT_K_TEMPORAL_CHAIN_ARGS
 #else
-    RT_K_TEMPORAL_ARGS
+template <bool kMoving, bool kClip, bool kDeform> __global__ void RT_ATROUS_ATTR RT_TEMPORAL_KERNEL RT_K_TEMPORAL_ARGS
 #endif
 {
+#if RT_TEMPORAL_CHAIN
+    constexpr bool kDeform = false;
+#endif
+    static_assert(kMoving || !kDeform, "a deformed mesh is followed through the motion table");
     // (blocks numbered row by row along grid.x, as k_atrous numbers them)
     const uint32_t blocksX = (width + RT_DENOISE_BLOCK_X - 1u) / RT_DENOISE_BLOCK_X, blockY = blockIdx.x / blocksX, blockX = blockIdx.x - blockY * blocksX;
     const int32_t x = (int32_t)(blockX * RT_DENOISE_BLOCK_X + threadIdx.x), y = (int32_t)(blockY * RT_DENOISE_BLOCK_Y + threadIdx.y);
@@ -60,20 +65,45 @@ template <bool kMoving, bool kClip> __global__ void RT_ATROUS_ATTR RT_TEMPORAL_K
             const float4 tail = temporalRecord(record, 4u);
             const bool moved = __float_as_uint(tail.y) != 0u;
             idThen = __float_as_uint(tail.x);
+            // the point the matrix takes: the pixel's own position, or -- on a deformed mesh -- where the old triangle record puts its barycentrics
+            float4 from = pp;
+            [[maybe_unused]] bool deformed = false;
+            if constexpr (kDeform)
+            {
+                deformed = known && __float_as_uint(tail.y) == RT_MOTION_DEFORMED;
+                const uint32_t first = __float_as_uint(tail.z), count = __float_as_uint(tail.w), t = frame.subObjectId[p];
+                const float bu = frame.barycentrics[p], bv = frame.barycentrics[pixels + p];
+                // (in 64 bits: first + t cannot wrap; a lane outside either range starts, and loads nothing)
+                const bool inRange = t < count && (uint64_t)first + t < (uint64_t)frame.numPrevTriangles;
+                known = known && (!deformed || inRange);
+                if (deformed && inRange)
+                {
+                    const float* const tri = frame.prevTriangles + 9u * ((size_t)first + t);   // {v0, edge1, edge2}: nine dword loads
+                    float l[3];
+#pragma unroll
+                    for (uint32_t k = 0; k < 3u; ++k)
+                    {
+                        l[k] = tri[3u + k] * bu + tri[k];
+                        l[k] = tri[6u + k] * bv + l[k];
+                    }
+                    from = make_float4(l[0], l[1], l[2], 0.0f);
+                }
+            }
             const float rows[3][4] = { { r0.x, r1.x, r2.x, r3.x }, { r0.y, r1.y, r2.y, r3.y }, { r0.z, r1.z, r2.z, r3.z } };   // [lane j] = m[0][j], m[1][j], m[2][j], m[3][j]
             float pj[3], nj[3];
 #pragma unroll
             for (uint32_t j = 0; j < 3u; ++j)
             {
-                pj[j] = pp.x * rows[j][0] + rows[j][3];
-                pj[j] = pp.y * rows[j][1] + pj[j];
-                pj[j] = pp.z * rows[j][2] + pj[j];
+                pj[j] = from.x * rows[j][0] + rows[j][3];
+                pj[j] = from.y * rows[j][1] + pj[j];
+                pj[j] = from.z * rows[j][2] + pj[j];
                 nj[j] = np.x * rows[j][0];
                 nj[j] = np.y * rows[j][1] + nj[j];
                 nj[j] = np.z * rows[j][2] + nj[j];
             }
             pm = make_float4(moved ? pj[0] : pp.x, moved ? pj[1] : pp.y, moved ? pj[2] : pp.z, 0.0f);
-            nm = make_float4(moved ? nj[0] : np.x, moved ? nj[1] : np.y, moved ? nj[2] : np.z, np.w);
+            const bool turned = moved && !deformed;   // (a deformed surface keeps this frame's normal: normalThreshold takes what the deformation turned it by)
+            nm = make_float4(turned ? nj[0] : np.x, turned ? nj[1] : np.y, turned ? nj[2] : np.z, np.w);
         }
         // project: transformPoint's operations, lane by lane
 #if RT_TEMPORAL_CHAIN

@@ -70,10 +70,15 @@ struct TemporalFrameMoving : TemporalFrame { const float4* objects; uint32_t num
 // count a pixel needs to clip (RtTemporalClip::minCount, as a float: cnt is one) and the confidence plane (may be NULL).  The two instantiations without take the
 // argument lists they took before there was a clip.
 template <class Frame> struct TemporalFrameClip : Frame { const float4* momentMu; const float4* momentG; float* confidence; float minCount; };
-template <bool kMoving, bool kClip = false> struct TemporalFrameOf { typedef TemporalFrame type; };
-template <> struct TemporalFrameOf<true, false> { typedef TemporalFrameMoving type; };
-template <bool kMoving> struct TemporalFrameOf<kMoving, true> { typedef TemporalFrameClip<typename TemporalFrameOf<kMoving, false>::type> type; };
-#define RT_K_TEMPORAL_ARGS (const TemporalIn in, const TemporalOut out, uint32_t width, uint32_t height, const typename TemporalFrameOf<kMoving, kClip>::type frame)
+// k_temporal<true, ., true>, deforming meshes (rtgpu_temporal_accumulate_deform): behind the moving frame this frame's triangle and barycentric planes and the
+// triangle records the meshes had when the history was stored -- nine floats each, RtTriangle's 36 bytes.  A record of the motion table with moved ==
+// RT_MOTION_DEFORMED names its mesh's range of them in its last two words.  The four instantiations without take the argument lists they took before.
+struct TemporalFrameDeform : TemporalFrameMoving { const uint32_t* subObjectId; const float* barycentrics; const float* prevTriangles; uint32_t numPrevTriangles; };
+template <bool kMoving, bool kClip = false, bool kDeform = false> struct TemporalFrameOf { typedef TemporalFrame type; };
+template <> struct TemporalFrameOf<true, false, false> { typedef TemporalFrameMoving type; };
+template <> struct TemporalFrameOf<true, false, true> { typedef TemporalFrameDeform type; };
+template <bool kMoving, bool kDeform> struct TemporalFrameOf<kMoving, true, kDeform> { typedef TemporalFrameClip<typename TemporalFrameOf<kMoving, false, kDeform>::type> type; };
+#define RT_K_TEMPORAL_ARGS (const TemporalIn in, const TemporalOut out, uint32_t width, uint32_t height, const typename TemporalFrameOf<kMoving, kClip, kDeform>::type frame)
 // k_temporal_moments<kRadius> (history clipping): k_atrous_tiled's block of 8 rows x 32 columns with a halo of kRadius, three 16-byte records per staged pixel
 // (at radius 3: 38 x 14 x 48 bytes = 25.5 KB of LDS); reads the current frame's planes of TemporalIn, writes the two moment records per pixel
 struct TemporalMomentsFrame { float colorScale, normalThreshold, planeTolerance, gamma; };
@@ -139,7 +144,7 @@ __global__ void __launch_bounds__(RT_BLOCK) k_temporal_pack(const float* __restr
                                                             const float* __restrict__ prevDepth, const float* __restrict__ prevNormal, const float* __restrict__ prevPosition,
                                                             const uint32_t* __restrict__ prevObjectId, const uint32_t* __restrict__ prevChainLength, uint32_t pixels,
                                                             float4* __restrict__ recA, float4* __restrict__ recB, float4* __restrict__ recN, float4* __restrict__ recP);
-template <bool kMoving = false, bool kClip = false> __global__ void RT_ATROUS_ATTR k_temporal RT_K_TEMPORAL_ARGS;
+template <bool kMoving = false, bool kClip = false, bool kDeform = false> __global__ void RT_ATROUS_ATTR k_temporal RT_K_TEMPORAL_ARGS;
 template <int kRadius> __global__ void RT_TEMPORAL_MOMENTS_ATTR k_temporal_moments RT_K_TEMPORAL_MOMENTS_ARGS;
 template <bool kMoving = false, bool kClip = false> __global__ void RT_ATROUS_ATTR k_temporal_chain RT_K_TEMPORAL_CHAIN_ARGS;
 template <int kRadius> __global__ void RT_TEMPORAL_MOMENTS_ATTR k_temporal_moments_chain RT_K_TEMPORAL_MOMENTS_CHAIN_ARGS;

@@ -34,7 +34,15 @@ the mesh's box (default 0.002: 6 cm on the 30 m hall), the wave one tenth of tha
   pass_ms                ms per pass (wall, `--bench-passes` passes, synchronised) on the REFIT tree and on the same vertices built and uploaded AFRESH, at the
                          amplitude and at four times it: the price of the kept topology and the kept collapse
   rel_mse                after `--frames` frames against `--reference-passes` passes of the last frame's mesh: the history kept across the updates (every pixel of
-                         the deformed mesh starts anew at each, by design: there are no motion vectors for deforming surfaces) and dropped at every update"""
+                         the deformed mesh starts anew at each: tracking is off) and dropped at every update
+--deform --track: what following the deformation costs and buys (rtgpu_set_deform_tracking, Viewport.track_deformation).  Both sides of every comparison in this run:
+  rel_mse                at the amplitude and at four times it, each against its own reference: `history_tracked` beside the two figures above
+  update_mesh_tracked    rtgpu_update_mesh with the snapshot copy against `update_mesh_untracked`: a temporal call between the updates in both (only the first
+                         update after a history takes a snapshot), host wall time of Viewport.update_scene()
+  denoise_temporal       the whole call after an update, Viewport.denoise(temporal=True, variance=True, device=True) synchronised (host wall time): tracked -- two
+                         guide planes more and k_temporal<true, false, true> -- against untracked
+  k_temporal_moving / k_temporal_deform   the pure _async entries on the same device planes and a one-record table (device events): k_temporal_pack +
+                         k_temporal<true> against k_temporal_pack + k_temporal<true, false, true> with the mesh's old triangle records"""
 import argparse
 import ctypes as C
 import json
@@ -64,6 +72,69 @@ def wall(fn, reps):
         ms.append(1e3 * (time.perf_counter() - t0))
     ms = np.array(ms)
     return {"ms_median": float(np.median(ms)), "ms_min": float(ms.min()), "ms_max": float(ms.max())}
+
+
+def track_costs(args, ra, lib, ctx, scene, vp, camera, wave, out):
+    """--deform --track: the update with and without the snapshot copy, the whole temporal call with and without the two planes, the kernel with and without the gather"""
+    import torch
+    w, h = args.width, args.height
+    stats = lambda ms: {"ms_median": float(np.median(ms)), "ms_min": float(min(ms)), "ms_max": float(max(ms))}   # noqa: E731
+    stream = torch.cuda.Stream()
+    with torch.cuda.stream(stream):
+        for track in (False, True, False, True):      # interleaved: both see the same clocks; the second round is the one kept
+            vp.track_deformation(track)
+            vp.reset_history()
+            update, call = [], []
+            for frame in range(2 + args.reps):
+                vp.reset()
+                vp.render(camera, passes=args.passes)
+                guide = vp.next_pass_params(camera)
+                torch.cuda.synchronize()
+                t0 = time.perf_counter(); vp.denoise(guide, temporal=True, variance=True, device=True); torch.cuda.synchronize(); t1 = time.perf_counter()
+                scene.set_mesh_vertices(0, wave(20 + frame, args.amplitude)); scene.update()
+                t2 = time.perf_counter(); vp.update_scene(); t3 = time.perf_counter()
+                if frame >= 2:      # (the first call has no history, the second builds the scratch)
+                    call.append(1e3 * (t1 - t0)); update.append(1e3 * (t3 - t2))
+            key = "tracked" if track else "untracked"
+            out["update_mesh_" + key], out["denoise_temporal_" + key] = stats(update), stats(call)
+        vp.track_deformation(False)
+        # the pure entries on planes made once: the mesh one step on, its records of a step ago, a one-record table
+        d = scene.desc.contents
+        triangles = torch.from_numpy(ra.read_mesh(ctx, 0, int(d.meshes[0].numNodes), int(d.meshes[0].numTriangles))[1]).cuda()
+        scene.set_mesh_vertices(0, wave(60, args.amplitude)); scene.update(); vp.update_scene()
+        vp.reset()
+        vp.render(camera, passes=args.passes)
+        guide = vp.next_pass_params(camera)
+        sums = vp.sum_buffer(secondary=True)
+        planes = vp.render_aovs(guide, ("depth", "normal", "position", "base_color", "object_id", "sub_object_id", "barycentrics"), device=True)
+        scale = 1.0 / args.passes
+        t = dict(color=torch.from_numpy(sums[0]).cuda(), color_half=torch.from_numpy(sums[1]).cuda(), depth=planes["depth"], normal=planes["normal"], position=planes["position"],
+                 albedo=planes["base_color"], object_id=planes["object_id"].to(torch.int32))
+        first = ra.temporal_accumulate(t["color"], t["color_half"], t["depth"], t["normal"], t["position"], t["albedo"], t["object_id"], color_scale=scale, ctx=ctx)
+        t.update(prev_a=first["a"], prev_b=first["b"], prev_length=first["length"], prev_depth=t["depth"], prev_normal=t["normal"], prev_position=t["position"],
+                 prev_object_id=t["object_id"])
+        outputs = [torch.empty((h, w, 3), dtype=torch.float32, device="cuda"), torch.empty((h, w, 3), dtype=torch.float32, device="cuda"),
+                   torch.empty((h, w), dtype=torch.float32, device="cuda"), torch.empty((2, h, w), dtype=torch.float32, device="cuda")]
+        p = ra.temporal_params(color_scale=scale, prev_world_to_screen=list(guide.camera.worldToScreen), prev_sample_offset=tuple(guide.sampleOffset))
+        pointers = [C.c_void_p(t[name].data_ptr()) for name in NAMES] + [C.c_void_p(o.data_ptr()) for o in outputs]
+        n = int(d.numObjects)
+        transform = np.array([[d.objects[i].transform[k] for k in range(16)] for i in range(n)], dtype=np.float32).reshape(n, 4, 4)
+        rigid = torch.from_numpy(ra.object_motion_table((transform, np.arange(n), np.ones(n))).view(np.int32)).cuda()      # (moved = 1: the matrix is used)
+        deformed = torch.from_numpy(ra.object_motion_table((transform, np.arange(n), np.full(n, ra.RT_MOTION_DEFORMED)),
+                                                           dict(first_triangle=np.zeros(n), num_triangles=np.full(n, triangles.shape[0]))).view(np.int32)).cuda()
+        sub, bary = planes["sub_object_id"].to(torch.int32), planes["barycentrics"]
+        block = ra.RtTemporalDeform(sub.data_ptr(), bary.data_ptr(), triangles.data_ptr(), int(triangles.shape[0]), 0)
+        handle = C.c_void_p(stream.cuda_stream)
+        head = [ctx, C.byref(p), C.c_uint32(w), C.c_uint32(h)] + pointers
+        moving = lambda: lib.rtgpu_temporal_accumulate_moving_async(*(head + [C.c_void_p(rigid.data_ptr()), C.c_uint32(n), handle]))   # noqa: E731
+        deform = lambda: lib.rtgpu_temporal_accumulate_deform_async(*(head + [C.c_void_p(deformed.data_ptr()), C.c_uint32(n), None, None, C.byref(block), handle]))   # noqa: E731
+        assert moving() == 0 and deform() == 0, lib.rtgpu_last_error()
+        out["k_temporal_moving"] = time_call(torch, moving, args.reps)
+        out["k_temporal_deform"] = time_call(torch, deform, args.reps)
+        out["k_temporal_moving_again"] = time_call(torch, moving, args.reps)
+        assert deform() == 0
+        torch.cuda.synchronize()
+        out["history_length_mean_with_the_triangles"] = float(outputs[2].cpu().numpy().mean())
 
 
 def deform_main(args):
@@ -143,26 +214,38 @@ def deform_main(args):
     out["upload_scene"] = wall(upload, max(3, args.reps // 4))
     out["update_share_of_upload"] = out["update_mesh"]["ms_median"] / out["upload_scene"]["ms_median"]
 
-    # ---- worth: the history kept across the updates against dropped at each ------------------------------------------------------------------------------
-    def chain(drop_history):
+    # ---- worth: the history kept across the updates against dropped at each (and, with --track, followed through them) ------------------------------------
+    def chain(drop_history, amplitude, track=False):
+        vp.track_deformation(track)
         vp.reset_history()
         for frame in range(args.frames):
-            deform_to(frame, args.amplitude)
+            deform_to(frame, amplitude)
             vp.reset()
             vp.render(camera, passes=args.passes)
             guide = vp.next_pass_params(camera)
             if drop_history:
                 vp.reset_history()
             image = vp.denoise(guide, temporal=True, variance=True)
+        vp.track_deformation(False)
         return np.asarray(image)
-    kept = chain(False)
-    raw = vp.sum_buffer() * np.float32(1.0 / args.passes)
-    dropped = chain(True)
-    vp.reset()
-    vp.render(camera, passes=args.reference_passes)
-    reference = (vp.sum_buffer() / np.float32(args.reference_passes)).astype(np.float64)
-    rel_mse = lambda image: float(((image.astype(np.float64) - reference) ** 2 / (reference ** 2 + 0.01)).mean())   # noqa: E731
-    out["rel_mse"] = {"raw_frame": rel_mse(raw), "history_kept": rel_mse(kept), "history_dropped_at_every_update": rel_mse(dropped)}
+
+    def worth(amplitude):
+        kept = chain(False, amplitude)
+        raw = vp.sum_buffer() * np.float32(1.0 / args.passes)
+        dropped = chain(True, amplitude)
+        tracked = chain(False, amplitude, track=True) if args.track else None
+        vp.reset()
+        vp.render(camera, passes=args.reference_passes)
+        reference = (vp.sum_buffer() / np.float32(args.reference_passes)).astype(np.float64)
+        rel_mse = lambda image: float(((image.astype(np.float64) - reference) ** 2 / (reference ** 2 + 0.01)).mean())   # noqa: E731
+        figures = {"raw_frame": rel_mse(raw), "history_kept": rel_mse(kept), "history_dropped_at_every_update": rel_mse(dropped)}
+        if tracked is not None:
+            figures["history_tracked"] = rel_mse(tracked)
+        return figures
+    out["rel_mse"] = worth(args.amplitude)
+    if args.track:
+        out["rel_mse_amplitude_x4"] = worth(4.0 * args.amplitude)
+        track_costs(args, ra, lib, ctx, scene, vp, camera, wave, out)
     line = json.dumps(out)
     print(line)
     if args.output:
@@ -188,6 +271,7 @@ def main():
     ap.add_argument("--deform", action="store_true", help="measure rtgpu_update_mesh instead: the Sponza-class mesh under a travelling sine (see above)")
     ap.add_argument("--amplitude", type=float, default=0.002, help="--deform: the wave's amplitude as a share of the mesh's largest extent")
     ap.add_argument("--bench-passes", type=int, default=16, help="--deform: passes per timing of a pass")
+    ap.add_argument("--track", action="store_true", help="--deform: also with the deformation followed (Viewport.track_deformation), at the amplitude and four times it, and what following costs")
     args = ap.parse_args()
     if args.deform:
         return deform_main(args)

@@ -11,6 +11,10 @@ unbundled (clang-offload-bundler), and every function symbol is listed with its 
   same code*   the same size and, instruction for instruction, the same disassembly once the 32-bit literals of `s_add_u32 / s_addc_u32 sN, sN, literal` are masked:
                pc-relative offsets of a kernel whose distance to the unit's constant tables moved because other kernels grew
   DIFFERS, new, gone   (a kernel whose argument list changed is `gone` under its old mangled name and `new` under the other)
+A kernel that is `gone` and one that is `new` under the same name and template arguments are one kernel whose mangled name moved -- a type of its argument list was
+renamed, or, for k_temporal, the defaulted third template argument (kDeform) was added behind the two it had: a trailing `false` of k_temporal<a, b, false> is
+dropped, as tools/kernel_resources_diff.py drops k_trace's --: they are compared as one, and the state carries a `~` (same bytes~: the renamed kernel holds the
+parent's bytes).
 
   python tools/kernel_code_diff.py --parent <a git worktree of the parent commit> [--root <this tree>]"""
 import argparse
@@ -59,6 +63,12 @@ def listing(elf, name, llvm):
     return [re.sub(r"^(s_addc?_u32 (s\d+), \2, )0x[0-9a-f]{6,8}$", r"\1<pc-relative>", line) for line in lines]
 
 
+def plain_name(demangled):
+    """name and template arguments: what identifies a kernel whatever its argument list is spelled as"""
+    name = re.sub(r"\(.*$", "", demangled)
+    return re.sub(r"(k_temporal<(?:true|false), (?:true|false)), false>", r"\1>", name)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--parent", required=True, help="the tree to compare against, e.g. a `git worktree` of the parent commit")
@@ -73,18 +83,30 @@ def main():
             now_elf = code_object(args.root, unit, extra, tmp, "this", args.hipcc, args.llvm_bin)
             then, now = functions(then_elf, args.llvm_bin), functions(now_elf, args.llvm_bin)
             names = sorted(set(then) | set(now))
-            for name, plain in zip(names, run(["c++filt"] + names).splitlines()):
-                a, b = then.get(name), now.get(name)
+            plain = dict(zip(names, (plain_name(p) for p in run(["c++filt"] + names).splitlines())))
+            # a kernel gone under one mangled name and new under another, with the same name and template arguments: one kernel, renamed
+            gone, new = [n for n in names if n not in now], [n for n in names if n not in then]
+            renamed = {}
+            for n in gone:
+                twins = [m for m in new if plain[m] == plain[n]]
+                if len(twins) == 1 and sum(plain[g] == plain[n] for g in gone) == 1:
+                    renamed[n] = twins[0]
+            for name in names:
+                if name in renamed.values():
+                    continue
+                other = renamed.get(name, name)
+                a, b = then.get(name), now.get(other)
                 state = "new" if a is None else "gone" if b is None else "same bytes" if a == b else "DIFFERS"
-                if state == "DIFFERS" and a[0] == b[0] and listing(then_elf, name, args.llvm_bin) == listing(now_elf, name, args.llvm_bin):
+                if state == "DIFFERS" and a[0] == b[0] and listing(then_elf, name, args.llvm_bin) == listing(now_elf, other, args.llvm_bin):
                     state = "same code*"
-                rows.append((unit, a[0] if a else "-", b[0] if b else "-", state, re.sub(r"\(.*$", "", plain)))
+                rows.append((unit, a[0] if a else "-", b[0] if b else "-", state + ("~" if other != name else ""), plain[name]))
     print("%-9s %8s %8s  %-10s %s" % ("unit", "parent", "this", "code", "kernel"))
     for row in rows:
         print("%-9s %8s %8s  %-10s %s" % row)
-    count = lambda state: sum(r[3] == state for r in rows)   # noqa: E731
-    print("# %d functions hold the parent's bytes, %d its instructions with other pc-relative offsets (*); %d differ, %d new, %d gone" % (
-        count("same bytes"), count("same code*"), count("DIFFERS"), count("new"), count("gone")))
+    renamed = sum(r[3].endswith("~") for r in rows)
+    count = lambda state: sum(r[3].rstrip("~") == state for r in rows)   # noqa: E731
+    print("# %d functions hold the parent's bytes, %d its instructions with other pc-relative offsets (*); %d differ, %d new, %d gone; %d of them under another mangled name (~)" % (
+        count("same bytes"), count("same code*"), count("DIFFERS"), count("new"), count("gone"), renamed))
 
 
 if __name__ == "__main__":

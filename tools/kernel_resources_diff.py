@@ -9,7 +9,7 @@ Each translation unit of raytracer_amd/csrc is compiled as __graft_entry__.build
 
 and the remarks become one line per kernel: unit, SGPRs, VGPRs, AGPRs, scratch bytes per lane, SGPR / VGPR spills, waves per SIMD, LDS bytes per block, demangled
 name.  A trailing `false` template argument of k_trace is dropped from the name, so that tables from before and after k_trace<kStack, kCount> gained its
-defaulted third argument line up.
+defaulted third argument line up; and of k_temporal<kMoving, kClip, kDeform> alike.
 
   python tools/kernel_resources_diff.py                         > table.txt     # this tree (--root DIR: another checkout, e.g. a `git worktree` of the parent commit)
   python tools/kernel_resources_diff.py --against parent.txt                    # this tree's table, then what differs from parent.txt"""
@@ -50,6 +50,7 @@ def table_of(root, hipcc):
             names = subprocess.run(["c++filt"] + list(kernels), capture_output=True, text=True).stdout.splitlines()
             for mangled, name in zip(kernels, names):
                 name = re.sub(r"(k_trace<\d+, (?:true|false)), false>", r"\1>", name)
+                name = re.sub(r"(k_temporal<(?:true|false), (?:true|false)), false>", r"\1>", name)   # (and of k_temporal<kMoving, kClip, kDeform>)
                 name = re.sub(r"\(.*$", "", name)   # the argument list adds nothing: a kernel's name and template arguments identify it
                 rows.append("%-11s %5s %5s %5s %7s %6s %6s %5s %6s  %s" % ((unit,) + tuple(kernels[mangled].get(f, "?") for f in FIELDS) + (name,)))
     return sorted(rows, key=lambda r: (r.split()[0], r.split(None, 9)[9]))
