@@ -462,6 +462,46 @@ typedef struct RtMeshUpdate
     const RtVertexShading* shading;     /* [numVertices] or NULL: normals, tangents and texture coordinates stay */
 } RtMeshUpdate;
 int rtgpu_update_mesh(RtgpuContext* ctx, const RtMeshUpdate* update);
+/* --- deforming meshes from device memory: what moves the vertices (skinning, cloth, a morph) usually runs on the same device.  rtgpu_update_mesh_device is
+ *     rtgpu_update_mesh on arrays that are there already: no host copy of the positions, and the two checks that walk them are made by a kernel.
+ *   semantics  exactly rtgpu_update_mesh's on the same values: the same tables bit for bit, the same ordering (queued passes first; lanes, ray queries and AOV
+ *              calls waited for), the same effects on the photons, on the history of rtgpu_denoise_temporal and on the snapshot of
+ *              rtgpu_set_deform_tracking, and the same count in RtUpdateInfo::_pad[0].  The two entries share one body from "the positions are in the mesh's
+ *              device buffer" on.  bytesUploaded counts what crossed between host and device: the vertex indices and depth offsets with a mesh's first
+ *              update, the root node read back and the level table of a two-level scene -- never the arrays.
+ *   arrays     tight float3 arrays of numVertices entries in device memory of the context's device.  normals / tangents: either may be NULL, and then that
+ *              half of every vertex record keeps what it holds; texture coordinates are never re-sent (a kernel rewrites the first 24 bytes -- or the 12
+ *              given -- of each of the three 32-byte vertex records of a triangle, and leaves texCoord, the material and the padding alone).
+ *   stream     the stream the caller produced the arrays on; NULL: the context's own.  The call orders itself behind that stream with an event, copies the
+ *              arrays device to device into the mesh's own buffers and refits on the context's stream, as rtgpu_update_mesh does.  It returns synchronised
+ *              (it reads the root box back anyway): the caller may overwrite or free the arrays on return.
+ *   checks     before anything is launched, every given pointer is held to hipPointerGetAttributes and hipMemGetAddressRange: memory of the context's device,
+ *              4-byte aligned, whose allocation holds 12 * numVertices bytes from the pointer on -- else RTGPU_ERR_INVALID_ARGUMENT: no kernel reads past an
+ *              allocation.  Then one read-only kernel (k_refit_check) tells whether any of the 3 * numVertices floats is not finite and folds the box over the
+ *              positions the triangles REFER to (a vertex no triangle uses does not count, as on the host), by atomic minimum and maximum over
+ *              order-preserving keys of the floats: exact whatever the order of the blocks.  The host reads those 32 bytes and decides as rtgpu_update_mesh
+ *              does, with the same statuses and messages; the box can differ from the host loop's only in the sign of a zero bound, which no decision
+ *              depends on.  With a mesh's first update its vertex indices go to the device BEFORE the check (the kernel gathers through them): a private
+ *              array that no walk reads, so "a refused update leaves the device exactly as it was" holds for everything a pass, a query or a read-back can see.
+ *   errors     rtgpu_update_mesh's, and: a pointer that fails the checks above: RTGPU_ERR_INVALID_ARGUMENT; a multi-device context (the arrays live on one
+ *              device): RTGPU_ERR_UNSUPPORTED -- rtgpu_update_mesh serves it.
+ *   outBox     (may be NULL) min.xyz, max.xyz of the REFITTED ROOT NODE, read back after the refit -- the floats the host mirror's fold produces, bit for bit,
+ *              zero signs included, never the check's box: what a top level over the new boxes is built from (rtgpu_update_objects follows, as above).
+ *              Untouched where nothing was refitted (a mesh without triangles). */
+typedef struct RtMeshUpdateDevice
+{
+    uint32_t abiVersion, meshIndex, numVertices, flags /* 0 */;
+    const float* positions;   /* device, [numVertices][3] tight */
+    const float* normals;     /* device, [numVertices][3] or NULL: stay */
+    const float* tangents;    /* device, [numVertices][3] or NULL: stay */
+} RtMeshUpdateDevice;
+int rtgpu_update_mesh_device(RtgpuContext* ctx, const RtMeshUpdateDevice* update, void* stream, float outBox[6]);
+/* The check alone, for tests and measurements: k_refit_check over `positions` (device, [numVertices][3], held to the pointer checks above) and the triangles of
+ * mesh meshIndex, on `stream` (NULL: the context's own), into outRecord -- 32 bytes of device memory of the context's device: uint32 lo[3], hi[3] (keys of the box
+ * over the referenced positions: key = bits ^ 0xFFFFFFFF for a negative float, bits | 0x80000000 otherwise; 0xFFFFFFFF / 0 where the mesh has no triangle),
+ * nonFinite (blocks that met a float that is not finite), pad.  Asynchronous: it returns when the two launches are queued and writes no scene table.  The
+ * mesh's vertex indices go to the device with the first call for a mesh, as with its first update. */
+int rtgpu_refit_check_async(RtgpuContext* ctx, uint32_t meshIndex, uint32_t numVertices, const float* positions, void* outRecord, void* stream);
 typedef struct RtWideLevelInfo { uint32_t nodeBase, gateBase, triBase, valid; float base[3], step[3], bound[3]; uint32_t pad[3]; } RtWideLevelInfo;   /* 64 bytes */
 int rtgpu_read_mesh(RtgpuContext* ctx, uint32_t meshIndex, RtNode* nodes, RtTriangle* triangles);
 int rtgpu_read_wide_level(RtgpuContext* ctx, uint32_t objectIndex, RtWideLevelInfo* info, void* nodes, uint64_t nodeBytes, void* gates, uint64_t gateBytes);

@@ -136,6 +136,44 @@ class RtMeshUpdate(C.Structure):
                 ("positions", C.POINTER(C.c_float)), ("shading", C.c_void_p)]
 
 
+class RtMeshUpdateDevice(C.Structure):
+    _fields_ = [("abiVersion", C.c_uint32), ("meshIndex", C.c_uint32), ("numVertices", C.c_uint32), ("flags", C.c_uint32),
+                ("positions", C.c_void_p), ("normals", C.c_void_p), ("tangents", C.c_void_p)]
+
+
+def update_mesh_device(ctx, mesh_index, num_vertices, positions, normals=None, tangents=None, stream=None):
+    """rtgpu_update_mesh_device, the thin call: the arrays are DEVICE addresses (ints, or None), `stream` a HIP stream handle (None: the context's own).
+    Returns (status, box): the library's status as it is and the refitted root box as a (2, 3) float32 array (min, max) -- zeros where the call refused."""
+    u = RtMeshUpdateDevice(3, int(mesh_index), int(num_vertices), 0, positions, normals, tangents)
+    box = np.zeros((2, 3), dtype=np.float32)
+    lib = rtgpu_lib()
+    lib.rtgpu_update_mesh_device.argtypes, lib.rtgpu_update_mesh_device.restype = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p], C.c_int
+    status = lib.rtgpu_update_mesh_device(ctx, C.byref(u), stream, box.ctypes.data_as(C.c_void_p))
+    return int(status), box
+
+
+def refit_check(ctx, mesh_index, positions, stream=None, record=None):
+    """rtgpu_refit_check_async, the check of rtgpu_update_mesh_device alone: `positions` a contiguous float32 (V, 3) tensor on the context's device.  With
+    `record` (an int32 tensor of 8 words on that device) the call is left asynchronous on `stream` and returns the status; without, it is waited for and
+    returns dict(lo, hi: the box over the positions the mesh's triangles refer to, float32, from the record's keys; non_finite: bool)."""
+    import torch
+    lib = rtgpu_lib()
+    lib.rtgpu_refit_check_async.argtypes = [C.c_void_p, C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p]
+    lib.rtgpu_refit_check_async.restype = C.c_int
+    out = record if record is not None else torch.empty(8, dtype=torch.int32, device=positions.device)
+    if stream is None and record is None:
+        stream = C.c_void_p(torch.cuda.current_stream(positions.device).cuda_stream)
+    r = lib.rtgpu_refit_check_async(ctx, int(mesh_index), int(positions.shape[0]), positions.data_ptr(), out.data_ptr(), stream)
+    if record is not None:
+        return int(r)
+    if r != 0:
+        raise (ValueError if r == -1 else RuntimeError)("rtgpu_refit_check_async failed (%d): %s" % (r, (lib.rtgpu_last_error() or b"").decode()))
+    torch.cuda.current_stream(positions.device).synchronize()
+    keys = out.cpu().numpy().view(np.uint32)
+    unkey = np.where(keys[:6] & 0x80000000, keys[:6] & 0x7FFFFFFF, ~keys[:6]).astype(np.uint32).view(np.float32)
+    return dict(lo=unkey[0:3].copy(), hi=unkey[3:6].copy(), non_finite=bool(keys[6]))
+
+
 class RtWideLevelInfo(C.Structure):
     _fields_ = [("nodeBase", C.c_uint32), ("gateBase", C.c_uint32), ("triBase", C.c_uint32), ("valid", C.c_uint32), ("base", C.c_float * 3),
                 ("step", C.c_float * 3), ("bound", C.c_float * 3), ("pad", C.c_uint32 * 3)]
@@ -863,6 +901,9 @@ class Scene:
 
     def build(self):
         if host_lib().rth_scene_build(self._h) != 0:
+            if any(self.mesh_on_device(i) for i in range(self.object_count())):
+                raise RuntimeError("Scene::BuildBVH refused: a mesh was deformed on the device (Viewport.update_mesh_device) and the scene's copy of it is "
+                                   "stale; give it vertices with set_mesh_vertices first")
             raise RuntimeError("Scene::BuildBVH failed")
         self.built = True
         return self
@@ -900,6 +941,26 @@ class Scene:
                 if a is not None:
                     added[object_index][key] = a.copy()
 
+    def set_mesh_bounds(self, object_index, lo, hi):
+        """Scene::SetMeshBounds: the mesh of the object_index-th add_* call was deformed ON THE DEVICE (Viewport.update_mesh_device, which calls this) and
+        (lo, hi) is its refitted root box.  update() then builds the top level over it and sends the objects alone.  The mesh is device-owned from here on
+        (mesh_on_device): the scene's positions, triangles and tree of it -- `desc`'s share and `calls` -- are stale until set_mesh_vertices gives the scene
+        the word again; until then build() and a whole upload (a second viewport, two update() calls without an update_scene() between them) refuse."""
+        box = _f(list(lo) + list(hi), 6)
+        if host_lib().rth_scene_set_mesh_bounds(self._h, C.c_uint32(object_index), box) != 0:
+            raise ValueError("object %r is not a mesh" % (object_index,))
+
+    def mesh_on_device(self, object_index):
+        """True while the mesh of the object_index-th add_* call is device-owned: deformed by Viewport.update_mesh_device and not given vertices since."""
+        return bool(host_lib().rth_scene_mesh_on_device(self._h, C.c_uint32(object_index)))
+
+    def object_mesh(self, object_index):
+        """(flat mesh index, vertex count) of the mesh the object_index-th add_* call made, as of the last build()."""
+        mi, nv = C.c_uint32(), C.c_uint32()
+        if host_lib().rth_scene_object_mesh(self._h, C.c_uint32(object_index), C.byref(mi), C.byref(nv)) != 0:
+            raise ValueError("object %r is not a mesh of the built scene" % (object_index,))
+        return int(mi.value), int(nv.value)
+
     def mesh_update_descs(self):
         """The RtMeshUpdates of the last update() (pointers into the scene, valid until the next build / update / set_mesh_vertices)."""
         out = []
@@ -924,7 +985,8 @@ class Scene:
 
     @property
     def desc(self):
-        """Pointer to the flat RtSceneDesc (valid until the scene is rebuilt / destroyed)."""
+        """Pointer to the flat RtSceneDesc (valid until the scene is rebuilt / destroyed).  Stale for a mesh while mesh_on_device() says so: its nodes,
+        triangles and vertex shading are those of the last vertices the scene itself was given."""
         return host_lib().rth_scene_desc(self._h)
 
 
@@ -1056,6 +1118,42 @@ class Viewport:
         self._track_deformation = bool(enable)
         if self.has_renderer and rtgpu_lib().rtgpu_set_deform_tracking(self.device_context(), C.c_int(int(self._track_deformation))) != 0:
             raise RuntimeError("rtgpu_set_deform_tracking failed: %s" % (rtgpu_lib().rtgpu_last_error() or b"").decode())
+
+    def update_mesh_device(self, object_index, positions, normals=None, tangents=None):
+        """rtgpu_update_mesh_device: deforms the mesh of the scene's object_index-th add_* call from tensors that are on the device already -- contiguous
+        float32 (V, 3) tensors on the renderer's ROCm device, V the mesh's vertex count; normals / tangents None: they stay.  No host copy: the call runs behind
+        torch.cuda.current_stream(), refits the mesh's tables on the device and returns synchronised, so the tensors may be overwritten at once.  The
+        scene must be uploaded and in step (no update() the device has not seen).  The scene learns the new box alone (Scene.set_mesh_bounds: the mesh is
+        device-owned from here on); where there is a top level the caller follows with scene.update(); vp.update_scene(), exactly as after any move -- a
+        one-object scene needs nothing more.  Returns (lo, hi), the refitted root box, as float32 NumPy arrays."""
+        import torch
+        scene = self._scene
+        if not self.has_renderer or scene is None:
+            raise RuntimeError("update_mesh_device needs a renderer: call set_renderer first")
+        mesh_index, num_vertices = scene.object_mesh(object_index)
+        for name, t in (("positions", positions), ("normals", normals), ("tangents", tangents)):
+            if t is None and name != "positions":
+                continue
+            if not isinstance(t, torch.Tensor) or t.dtype != torch.float32 or t.dim() != 2 or tuple(t.shape) != (num_vertices, 3):
+                raise ValueError("%s must be a (%d, 3) float32 tensor" % (name, num_vertices))
+            if not t.is_cuda or t.device != positions.device:
+                raise ValueError("%s must live on the renderer's ROCm device" % name)
+            if not t.is_contiguous():
+                raise ValueError("%s must be contiguous" % name)
+        ctx = self.device_context()
+        if not ctx.value or not host_lib().rth_viewport_scene_in_step(self._h):
+            raise RuntimeError("update_mesh_device needs the scene on the device and in step: call update_scene() first (after the scene's last update())")
+        device = positions.device
+        if (device.index if device.index is not None else torch.cuda.current_device()) != multi_info(ctx)["devices"][0]:
+            raise ValueError("the tensors must live on the renderer's device (cuda:%d)" % multi_info(ctx)["devices"][0])
+        ptr = lambda t: None if t is None else t.data_ptr()   # noqa: E731
+        status, box = _run_on_torch_stream(torch, self._query_streams, device, (positions, normals, tangents), lambda stream: update_mesh_device(
+            ctx, mesh_index, num_vertices, ptr(positions), ptr(normals), ptr(tangents), stream))
+        if status != 0:
+            err = (rtgpu_lib().rtgpu_last_error() or b"").decode()
+            raise (ValueError if status == -1 else RuntimeError)("rtgpu_update_mesh_device failed (%d): %s" % (status, err))
+        scene.set_mesh_bounds(object_index, box[0], box[1])
+        return box[0].copy(), box[1].copy()
 
     def update_scene(self):
         """Viewport::UpdateScene: after Scene.update(), sends the new positions of every deformed mesh (Scene.set_mesh_vertices; rtgpu_update_mesh refits its

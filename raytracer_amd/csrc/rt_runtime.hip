@@ -47,6 +47,7 @@
 using namespace rtd;
 
 #include "rt_scene_prepare.h"
+#include "rt_refit_keys.h"
 #include "rt_trace_kernels.h"
 #include "rt_shade_kernels.h"
 #include "rt_tail_kernels.h"
@@ -221,6 +222,7 @@ RTGPU_API void rtgpu_destroy(RtgpuContext* c)
     if (c->seedRingHost) (void)hipHostFree(c->seedRingHost);
     if (c->passRingHost) (void)hipHostFree(c->passRingHost);
     for (int i = 0; i < RT_SEED_RING; ++i) if (c->seedEvents[i]) (void)hipEventDestroy(c->seedEvents[i]);
+    if (c->refitOrder) (void)hipEventDestroy(c->refitOrder);
     for (auto& t : c->pendingTimed) { (void)hipEventDestroy(t.a); (void)hipEventDestroy(t.b); }
     for (hipEvent_t e : c->eventPool) (void)hipEventDestroy(e);
     for (uint32_t i = 0; i < RT_MAX_LANES; ++i) if (c->lanes[i].stream) { (void)hipStreamSynchronize(c->lanes[i].stream); releaseStream(c->device, c->lanes[i].stream); }

@@ -173,11 +173,13 @@ struct RtgpuContext
         uint64_t meshNodeBytes = 0, meshGateBytes = 0;                // the mesh levels' share of walkNodeBytes / walkLeafBoxBytes[RTGPU_WALK_WIDE2]
         RtUpdateInfo info = {};                                       // rtgpu_get_update_info
         // rtgpu_update_mesh (rt_runtime_refit.inl): per mesh its plan and 4-wide level (rt_scene_prepare.h) and, from its first update on, the device copies
-        // of its triangles' vertex indices (leaf order) and of the positions; the device arrays live in sceneAllocs and go with the scene
+        // of its triangles' vertex indices (leaf order) and of the positions (rtgpu_update_mesh_device: of the normals and tangents it was given too); the device
+        // arrays live in sceneAllocs and go with the scene
         struct Mesh
         {
             MeshRefitPlan plan; PreparedScene::MeshLevel level;
             RtVertexIndices* indices = nullptr; float* positions = nullptr; RtVertexShading* shading = nullptr; uint32_t* levelFirst = nullptr;
+            float* normals = nullptr; float* tangents = nullptr;
         };
         std::vector<Mesh> meshes; std::vector<RtMesh> meshTable;
         std::vector<RtVertexIndices> vertexIndices;                   // the caller's, as uploaded: every update takes the new root box from them before it writes; a mesh's first update copies its share to the device
@@ -186,7 +188,9 @@ struct RtgpuContext
         // numbering, made with the first snapshot, in sceneAllocs -- and per mesh what happened since that history: 0 untouched, 1 its range of the array holds
         // its snapshot, 2 it was updated without one (its pixels start)
         RtTriangle* deformSnapshot = nullptr; std::vector<uint8_t> deformState;
+        RefitCheckRecord* refitCheck = nullptr;                       // what k_refit_check found (rtgpu_update_mesh_device), in sceneAllocs
     } updatable;
+    hipEvent_t refitOrder = nullptr;   // rtgpu_update_mesh_device: puts the refit's stream behind the caller's
 
     // film
     uint32_t width = 0, height = 0;

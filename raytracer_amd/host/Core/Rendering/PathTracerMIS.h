@@ -35,6 +35,8 @@ public:
     // after Scene::UpdateBVH: sends the moved objects and the new top level alone (rtgpu_update_objects); a scene that was never uploaded, was rebuilt, or
     // was updated more than once since this renderer saw it goes up whole instead
     bool UpdateScene() { return EnsureSceneUploaded(); }
+    // the device holds the scene as it stands: uploaded, and no Scene::UpdateBVH since (what a deformation on the device, rtgpu_update_mesh_device, starts from)
+    bool SceneInStep() const { return mCtx && mUploadedBuildId == mScene.GetBuildId() && mUploadedUpdateId == mScene.GetUpdateId(); }
 
 protected:
     // wholeFrameOnOneDevice: integrators that splat over the frame (Light Tracer, VCM) ignore SetRendererDevices

@@ -32,6 +32,17 @@ public:
     // rewrites that mesh's flat nodes, triangles and vertex shading in place -- GetDesc() is the refit scene -- and lists it for the device:
     // GetMeshUpdate(i) is what rtgpu_update_mesh takes for the i-th mesh the last UpdateBVH found changed, before that UpdateBVH's rtgpu_update_objects.
     bool SetMeshVertices(uint32 index, uint32 numVertices, const math::Float3* positions, const math::Float3* normals, const math::Float3* tangents);
+    // Deforming meshes ON THE DEVICE (rtgpu_update_mesh_device): the mirror learns the new bounding box alone -- the refitted root's, as the call returned it.
+    // SetMeshBounds sets the box of the mesh the index-th AddObject call holds; the next UpdateBVH builds the top level over it and counts every object over
+    // the mesh as moved, WITHOUT listing the mesh in GetMeshUpdate (the device has its tables: the objects alone are sent).  The mesh is then device-owned
+    // (MeshOnDevice): the mirror's positions, triangles and tree, and GetDesc()'s share of them, are stale until SetMeshVertices gives the mirror the word
+    // again.  While any mesh is device-owned (AnyMeshOnDevice) BuildBVH refuses, and so does a renderer asked to upload the scene whole: either would
+    // put the stale mesh back.
+    bool SetMeshBounds(uint32 index, const math::Float3& min, const math::Float3& max);
+    bool MeshOnDevice(uint32 index) const;
+    bool AnyMeshOnDevice() const;
+    // the flat mesh (GetDesc().meshes) the index-th AddObject call's mesh became at the last BuildBVH, and its vertex count: what rtgpu_update_mesh_device names
+    bool GetObjectMesh(uint32 index, uint32* outMeshIndex, uint32* outNumVertices) const;
     ShapePtr GetObjectShape(uint32 index) const;   // the shape of the index-th AddObject call (null: a light, or no such object): a second object may share it (an instance)
     uint32 GetNumMeshUpdates() const { return (uint32)mDirtyMeshes.size(); }
     void GetMeshUpdate(uint32 i, RtMeshUpdate& out) const;
@@ -75,7 +86,7 @@ private:
     std::vector<uint32> mPreviousIndex;
     uint64 mUpdateId = 0;
     // per flat mesh its shape and the versions the flat arrays show; the flat meshes the last UpdateBVH rewrote (and whether their shading changed)
-    struct FlatMesh { const class MeshShape* shape; uint64 version, shadingVersion; };
+    struct FlatMesh { const class MeshShape* shape; uint64 version, shadingVersion, boundsVersion; };
     std::vector<FlatMesh> mFlatMeshShapes;
     std::vector<std::pair<uint32, bool>> mDirtyMeshes;
     bool mObjectsMoved = false;

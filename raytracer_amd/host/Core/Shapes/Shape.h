@@ -85,6 +85,12 @@ public:
     uint64 GetVersion() const { return mVersion; }                 // UpdateVertices calls so far
     uint64 GetShadingVersion() const { return mShadingVersion; }   // the last of them that brought normals or tangents
     const std::vector<math::Float3>& GetPositions() const { return mPositions; }   // of the last UpdateVertices (empty before the first)
+    // The mesh was deformed ON THE DEVICE (rtgpu_update_mesh_device): only its new bounding box, the refitted root's, comes back.  The mesh is then
+    // device-owned: positions, triangles and tree of the mirror no longer describe the device, until UpdateVertices gives the mirror the word again (and then
+    // sends its normals and tangents too: the device's may be newer).  GetVersion stays: nothing is to be sent.
+    void SetDeviceBounds(const math::Box& box) { mBoundingBox = box; mOnDevice = true; mBoundsVersion++; }
+    bool IsOnDevice() const { return mOnDevice; }
+    uint64 GetBoundsVersion() const { return mBoundsVersion; }     // SetDeviceBounds calls so far
 
     Kind GetKind() const override { return Kind::Mesh; }
     const math::Box GetBoundingBox() const override { return mBoundingBox; }
@@ -104,7 +110,8 @@ private:
     std::vector<VertexShading> mShading;
     std::vector<MaterialPtr> mMaterials;
     std::vector<math::Float3> mPositions;
-    uint64 mVersion = 0, mShadingVersion = 0;
+    uint64 mVersion = 0, mShadingVersion = 0, mBoundsVersion = 0;
+    bool mOnDevice = false;
 };
 
 using MeshShapePtr = std::shared_ptr<MeshShape>;

@@ -196,7 +196,8 @@ bool MeshShape::UpdateVertices(const Float3* positions, const Float3* normals, c
         if (tangents) { s.tangent[0] = tangents[i].x; s.tangent[1] = tangents[i].y; s.tangent[2] = tangents[i].z; }
     }
     mVersion++;
-    if (normals || tangents) mShadingVersion = mVersion;
+    if (normals || tangents || mOnDevice) mShadingVersion = mVersion;   // (after a deformation on the device the mirror's normals and tangents go along: the device's may be newer)
+    mOnDevice = false;
     return true;
 }
 
@@ -267,6 +268,11 @@ void Scene::AddObject(SceneObjectPtr object)
 
 bool Scene::BuildBVH()
 {
+    if (AnyMeshOnDevice())
+    {
+        fprintf(stderr, "[rt] ERROR: a mesh was deformed on the device (Scene::SetMeshBounds): the scene's copy of it is stale and cannot be built or uploaded again; give it vertices with SetMeshVertices first\n");
+        return false;
+    }
     // classification: finite lights and shapes are traceable, infinite lights are "global"
     mTraceableObjects.clear(); mLights.clear(); mGlobalLights.clear();
     for (const auto& object : mAllObjects)
@@ -390,7 +396,7 @@ bool Scene::Flatten()
         }
         const uint32 id = (uint32)mFlatMeshes.size();
         mFlatMeshes.push_back(flat);
-        mFlatMeshShapes.push_back({ mesh, mesh->GetVersion(), mesh->GetShadingVersion() });
+        mFlatMeshShapes.push_back({ mesh, mesh->GetVersion(), mesh->GetShadingVersion(), mesh->GetBoundsVersion() });
         meshIds[mesh] = id;
         return id;
     };
@@ -514,10 +520,13 @@ bool Scene::UpdateBVH()
     if (traceable.size() != mTraceableObjects.size()) return false;
 
     // deformed meshes (MeshShape::UpdateVertices since the flat arrays were written): the same ranges, new boxes, triangles and vertex shading
+    // (a mesh deformed on the device, SetMeshBounds, is not among them: the device has its tables; its new box moves every object over it)
     mDirtyMeshes.clear();
+    bool boundsMoved = false;
     for (uint32 id = 0; id < mFlatMeshShapes.size(); ++id)
     {
         FlatMesh& fm = mFlatMeshShapes[id];
+        if (fm.boundsVersion != fm.shape->GetBoundsVersion()) { boundsMoved = true; fm.boundsVersion = fm.shape->GetBoundsVersion(); }
         if (fm.version == fm.shape->GetVersion()) continue;
         const RtMesh& flat = mFlatMeshes[id];
         if (flat.numNodes) memcpy(mFlatMeshNodes.data() + flat.firstNode, fm.shape->GetBVH().GetNodes(), sizeof(RtNode) * flat.numNodes);
@@ -553,7 +562,7 @@ bool Scene::UpdateBVH()
         mLights[i]->GetTransform().Store(mFlatLights[i].transform);
         mLights[i]->GetInverseTransform().Store(mFlatLights[i].invTransform);
     }
-    mObjectsMoved = oldLights.size() != mFlatLights.size() || (!oldLights.empty() && memcmp(oldLights.data(), mFlatLights.data(), sizeof(RtLight) * oldLights.size()) != 0);
+    mObjectsMoved = boundsMoved || oldLights.size() != mFlatLights.size() || (!oldLights.empty() && memcmp(oldLights.data(), mFlatLights.data(), sizeof(RtLight) * oldLights.size()) != 0);
     for (uint32 i = 0; i < traceable.size(); ++i) mObjectsMoved = mObjectsMoved || mPreviousIndex[i] != i || memcmp(&oldFlat[i], &mFlatObjects[i], sizeof(RtObject)) != 0;
     mFlatTopNodes.clear();
     CopyNodes(mTraceableObjectsBVH, mFlatTopNodes);
@@ -573,6 +582,40 @@ bool Scene::SetMeshVertices(uint32 index, uint32 numVertices, const Float3* posi
     MeshShape* mesh = static_cast<MeshShape*>(object->GetShape().get());
     if (numVertices != mesh->GetVertexShading().size()) return false;
     return mesh->UpdateVertices(positions, normals, tangents);
+}
+
+bool Scene::SetMeshBounds(uint32 index, const Float3& min, const Float3& max)
+{
+    const ShapePtr shape = GetObjectShape(index);
+    if (!shape || shape->GetKind() != IShape::Kind::Mesh) return false;
+    static_cast<MeshShape*>(shape.get())->SetDeviceBounds(Box(Vector4(min), Vector4(max)));
+    return true;
+}
+
+bool Scene::MeshOnDevice(uint32 index) const
+{
+    const ShapePtr shape = GetObjectShape(index);
+    return shape && shape->GetKind() == IShape::Kind::Mesh && static_cast<const MeshShape*>(shape.get())->IsOnDevice();
+}
+
+bool Scene::GetObjectMesh(uint32 index, uint32* outMeshIndex, uint32* outNumVertices) const
+{
+    const ShapePtr shape = GetObjectShape(index);
+    for (uint32 id = 0; shape && id < mFlatMeshShapes.size(); ++id)
+        if (mFlatMeshShapes[id].shape == shape.get())
+        {
+            if (outMeshIndex) *outMeshIndex = id;
+            if (outNumVertices) *outNumVertices = mFlatMeshes[id].numVertices;
+            return true;
+        }
+    return false;
+}
+
+bool Scene::AnyMeshOnDevice() const
+{
+    for (uint32 i = 0; i < mAllObjects.size(); ++i)
+        if (MeshOnDevice(i)) return true;
+    return false;
 }
 
 ShapePtr Scene::GetObjectShape(uint32 index) const

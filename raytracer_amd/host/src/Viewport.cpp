@@ -899,6 +899,12 @@ bool PathTracerMIS::EnsureSceneUploaded()
         mUploadedUpdateId = mScene.GetUpdateId();
         return true;
     }
+    if (mScene.AnyMeshOnDevice())
+    {
+        // (a whole upload would put the mirror's stale copy of that mesh back: never quietly)
+        fprintf(stderr, "[rt] ERROR: the scene must be uploaded whole (it was rebuilt, or is more than one update ahead of the device), but a mesh of it was deformed on the device and the scene's copy is stale: give it vertices with SetMeshVertices first\n");
+        return false;
+    }
     RtSceneDesc desc = mScene.GetDesc();
     desc.blueNoise = mBlueNoise.empty() ? nullptr : mBlueNoise.data();
     if (rtgpu_upload_scene(mCtx, &desc) != RTGPU_OK)

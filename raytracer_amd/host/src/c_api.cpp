@@ -350,6 +350,19 @@ RTH_API int rth_scene_mesh_update_desc(void* sh, uint32_t i, RtMeshUpdate* out)
     return 0;
 }
 
+// deforming meshes on the device: Scene::SetMeshBounds of the addIndex-th object's mesh with the box rtgpu_update_mesh_device returned (min.xyz, max.xyz);
+// -1: no such mesh object.  rth_scene_mesh_on_device: 1 while the mirror's copy of that object's mesh is stale (0 also for what is no mesh)
+RTH_API int rth_scene_set_mesh_bounds(void* sh, uint32_t addIndex, const float box[6])
+{
+    return box && static_cast<SceneHandle*>(sh)->scene.SetMeshBounds(addIndex, Float3(box[0], box[1], box[2]), Float3(box[3], box[4], box[5])) ? 0 : -1;
+}
+RTH_API int rth_scene_mesh_on_device(void* sh, uint32_t addIndex) { return static_cast<SceneHandle*>(sh)->scene.MeshOnDevice(addIndex) ? 1 : 0; }
+// the flat mesh index of the addIndex-th object's mesh and its vertex count, as of the last rth_scene_build; -1: no such mesh object
+RTH_API int rth_scene_object_mesh(void* sh, uint32_t addIndex, uint32_t* outMeshIndex, uint32_t* outNumVertices)
+{
+    return static_cast<SceneHandle*>(sh)->scene.GetObjectMesh(addIndex, outMeshIndex, outNumVertices) ? 0 : -1;
+}
+
 // ---- camera -----------------------------------------------------------------------------------------
 RTH_API void* rth_camera_create() { return new Camera(); }
 RTH_API void rth_camera_destroy(void* c) { delete static_cast<Camera*>(c); }
@@ -407,6 +420,12 @@ RTH_API int rth_viewport_upload_scene(void* v)
 {
     PathTracerMIS* r = dynamic_cast<PathTracerMIS*>(static_cast<ViewportHandle*>(v)->renderer.get());
     return r && r->UploadScene() ? 0 : -1;
+}
+// 1: the renderer's device holds the scene as it stands (uploaded, no rth_scene_update since)
+RTH_API int rth_viewport_scene_in_step(void* v)
+{
+    PathTracerMIS* r = dynamic_cast<PathTracerMIS*>(static_cast<ViewportHandle*>(v)->renderer.get());
+    return r && r->SceneInStep() ? 1 : 0;
 }
 RTH_API int rth_viewport_update_scene(void* v) { return static_cast<ViewportHandle*>(v)->viewport.UpdateScene() ? 0 : -1; }
 // the devices of renderers created afterwards (SetRendererDevices); n == 0: back to one device

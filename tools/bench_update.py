@@ -42,7 +42,16 @@ the mesh's box (default 0.002: 6 cm on the 30 m hall), the wave one tenth of tha
   denoise_temporal       the whole call after an update, Viewport.denoise(temporal=True, variance=True, device=True) synchronised (host wall time): tracked -- two
                          guide planes more and k_temporal<true, false, true> -- against untracked
   k_temporal_moving / k_temporal_deform   the pure _async entries on the same device planes and a one-record table (device events): k_temporal_pack +
-                         k_temporal<true> against k_temporal_pack + k_temporal<true, false, true> with the mesh's old triangle records"""
+                         k_temporal<true> against k_temporal_pack + k_temporal<true, false, true> with the mesh's old triangle records
+--deform --device: deforming from positions that are on the device already (rtgpu_update_mesh_device, Viewport.update_mesh_device), in the same run and
+interleaved with its yardstick.  Every row: median, min, max and `spread` = max - min over `--reps`:
+  entry_host / entry_device      rtgpu_update_mesh on host positions against rtgpu_update_mesh_device on the same positions in a device tensor, alternating
+                         call by call (host wall time; both return synchronised).  `device_entry_below_host_entry_by_more_than_its_spread` is the one
+                         condition under which "faster" may be written
+  k_refit_check          the check alone (rtgpu_refit_check_async: init + k_refit_check; device events)
+  route_host / route_device      from a device-resident tensor to an updated scene: .cpu().numpy() -> set_mesh_vertices -> update -> update_scene against
+                         update_mesh_device -> update -> update_scene (host wall time), in alternating blocks; the second round is kept
+  pass_ms_by_route       ms per pass on the tables either route refitted from the same positions: the same bits, so one timing of each"""
 import argparse
 import ctypes as C
 import json
@@ -137,6 +146,64 @@ def track_costs(args, ra, lib, ctx, scene, vp, camera, wave, out):
         out["history_length_mean_with_the_triangles"] = float(outputs[2].cpu().numpy().mean())
 
 
+def device_costs(args, ra, lib, ctx, scene, vp, wave, pass_ms, out):
+    """--deform --device: the device entry beside the host entry on the same positions, the check alone, the two whole routes, a pass after either"""
+    import torch
+
+    def stats(ms):
+        return {"ms_median": float(np.median(ms)), "ms_min": float(min(ms)), "ms_max": float(max(ms)), "spread": float(max(ms) - min(ms))}
+    count = len(wave(0, args.amplitude))
+    frames = [np.ascontiguousarray(wave(30 + k, args.amplitude)) for k in range(4)]
+    tensors = [torch.from_numpy(f).cuda() for f in frames]
+    torch.cuda.synchronize()
+    # the two entries, call by call on the same positions (the mirror is not told: this part measures the C calls alone, as README's figures do)
+    host, device, bytes_host, bytes_device = [], [], 0, 0
+    for rep in range(2 + args.reps):
+        f, t = frames[rep % 4], tensors[rep % 4]
+        u = ra.RtMeshUpdate(3, 0, count, 0, f.ctypes.data_as(C.POINTER(C.c_float)), None)
+        t0 = time.perf_counter(); r = lib.rtgpu_update_mesh(ctx, C.byref(u)); t1 = time.perf_counter()
+        assert r == 0, lib.rtgpu_last_error()
+        bytes_host = ra.update_info(ctx)["bytesUploaded"]
+        t2 = time.perf_counter(); r, box = ra.update_mesh_device(ctx, 0, count, t.data_ptr()); t3 = time.perf_counter()
+        assert r == 0, lib.rtgpu_last_error()
+        bytes_device = ra.update_info(ctx)["bytesUploaded"]
+        if rep >= 2:
+            host.append(1e3 * (t1 - t0)); device.append(1e3 * (t3 - t2))
+    out["entry_host"], out["entry_device"] = dict(stats(host), bytes_uploaded=bytes_host), dict(stats(device), bytes_uploaded=bytes_device)
+    out["device_entry_below_host_entry_by_more_than_its_spread"] = bool(out["entry_device"]["ms_median"] < out["entry_host"]["ms_median"] - out["entry_host"]["spread"])
+    # the check alone, on a stream of torch's
+    stream = torch.cuda.Stream()
+    record = torch.empty(8, dtype=torch.int32, device="cuda")
+    with torch.cuda.stream(stream):
+        check = lambda: ra.refit_check(ctx, 0, tensors[0], C.c_void_p(stream.cuda_stream), record)   # noqa: E731
+        assert check() == 0, lib.rtgpu_last_error()
+        out["k_refit_check"] = dict(time_call(torch, check, args.reps), bytes_read=int(12 * count + 16 * scene.desc.contents.numTriangles + 36 * scene.desc.contents.numTriangles))
+    out["k_refit_check"]["spread"] = out["k_refit_check"]["ms_max"] - out["k_refit_check"]["ms_min"]
+
+    # the two whole routes from a device-resident tensor, in alternating blocks (a host-route call after a device-route call also takes the mesh back, with
+    # its normals and tangents: the first calls of a block are not kept)
+    def route_host(t):
+        scene.set_mesh_vertices(0, t.cpu().numpy()); scene.update(); vp.update_scene()
+
+    def route_device(t):
+        vp.update_mesh_device(0, t); scene.update(); vp.update_scene()
+    scene.set_mesh_vertices(0, frames[0]); scene.update(); vp.update_scene()      # (the mirror in step with the device again)
+    for name, route in (("route_host", route_host), ("route_device", route_device)) * 2:
+        ms = []
+        for rep in range(2 + args.reps):
+            t = tensors[rep % 4]
+            t0 = time.perf_counter(); route(t); t1 = time.perf_counter()
+            if rep >= 2:
+                ms.append(1e3 * (t1 - t0))
+        out[name] = stats(ms)
+    out["device_route_below_host_route_by_more_than_its_spread"] = bool(out["route_device"]["ms_median"] < out["route_host"]["ms_median"] - out["route_host"]["spread"])
+    # a pass on the tables of either route, the same positions
+    route_device(tensors[1])
+    by_device = pass_ms(vp)
+    route_host(tensors[1])
+    out["pass_ms_by_route"] = {"device": by_device, "host": pass_ms(vp)}
+
+
 def deform_main(args):
     import raytracer_amd as ra
     from raytracer_amd import scenes
@@ -198,6 +265,8 @@ def deform_main(args):
             t0 = time.perf_counter(); viewport.render(camera, passes=args.bench_passes); assert lib.rtgpu_synchronize(context) == 0
             ms.append(1e3 * (time.perf_counter() - t0) / args.bench_passes)
         return float(np.median(ms))
+    if args.device:
+        device_costs(args, ra, lib, ctx, scene, vp, wave, pass_ms, out)
     out["pass_ms"] = {}
     for factor in (1.0, 4.0):
         deform_to(7, factor * args.amplitude)
@@ -271,6 +340,7 @@ def main():
     ap.add_argument("--deform", action="store_true", help="measure rtgpu_update_mesh instead: the Sponza-class mesh under a travelling sine (see above)")
     ap.add_argument("--amplitude", type=float, default=0.002, help="--deform: the wave's amplitude as a share of the mesh's largest extent")
     ap.add_argument("--bench-passes", type=int, default=16, help="--deform: passes per timing of a pass")
+    ap.add_argument("--device", action="store_true", help="--deform: also rtgpu_update_mesh_device on positions that are on the device already, beside rtgpu_update_mesh in the same run")
     ap.add_argument("--track", action="store_true", help="--deform: also with the deformation followed (Viewport.track_deformation), at the amplitude and four times it, and what following costs")
     args = ap.parse_args()
     if args.deform:
