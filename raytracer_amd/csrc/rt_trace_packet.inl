@@ -146,7 +146,7 @@ __global__ void __launch_bounds__(RT_BLOCK) k_trace_packet(const RtSceneDesc sce
                             float nearD;
                             const bool pass = intersectBoxRayNoNaN(gateRay, __uint_as_float(gmin.x), __uint_as_float(gmin.y), __uint_as_float(gmin.z),
                                                                    __uint_as_float(gmax.x), __uint_as_float(gmax.y), __uint_as_float(gmax.z), nearD);
-                            if (candidate && pass) wideAcceptPair(paths, slot, 0u, firstTri, t0, u0, v0_, t1, u1, v1, lo, best, second);
+                            if (candidate && pass) wideAcceptPair(paths, slot, 0u, firstTri, t0, u0, v0_, t1, u1, v1, lo, nearD, tol, best, second);
                         }
                     }
                     // (else: an unused child slot whose corner point a ray happened to meet)

@@ -181,13 +181,14 @@ RT_DEV void traceWideLoop(const RtSceneDesc& scene, const WideBvh& bvh, const Pa
                     gateRay.origin = ray.origin; gateRay.dir = ray.dir;
                     gateRay.invDir = V4(park[0], park[RT_BLOCK], park[2 * RT_BLOCK], 0.0f);
                     gateRay.originDivDir = V4(park[3 * RT_BLOCK], park[4 * RT_BLOCK], park[5 * RT_BLOCK], 0.0f);
-                    const bool pass = wideLeafGate(bvh.gate, first, gateRay, shadow, best);
+                    float entry;
+                    const bool pass = wideLeafGate(bvh.gate, first, gateRay, shadow, best, entry);
                     if (pass)
                     {
                         if (shadow) { if (lo < best) occluded = true; }
                         else
                         {
-                            const bool wrote = wideAcceptPair(paths, slot, 0u, first, t0, u0, v0_, t1, u1, v1, lo, best, second);
+                            const bool wrote = wideAcceptPair(paths, slot, 0u, first, t0, u0, v0_, t1, u1, v1, lo, entry, tol, best, second);
                             if (kDiag && wrote) diagHitWrites++;
                         }
                     }

@@ -177,13 +177,14 @@ __global__ void __launch_bounds__(RT_BLOCK) __attribute__((amdgpu_waves_per_eu(k
                     const float lo = wideLeafPair(scene.triangles + level.triBase, cur, ray, t0, u0, v0_, t1, u1, v1);
                     if (lo < best + tol)
                     {
-                        const bool pass = wideLeafGate(wide.gate + level.gateBase, first, makeRayUnsafe3(ray.origin, ray.dir), shadow, best);   // (the ray rebuilt, not parked: this walk's LDS holds the world terms)
+                        float entry;
+                        const bool pass = wideLeafGate(wide.gate + level.gateBase, first, makeRayUnsafe3(ray.origin, ray.dir), shadow, best, entry);   // (the ray rebuilt, not parked: this walk's LDS holds the world terms)
                         if (pass)
                         {
                             if (shadow) { if (lo < best) occluded = true; }
                             else
                             {
-                                wideAcceptPair(paths, slot, objectId, first, t0, u0, v0_, t1, u1, v1, lo, best, second);
+                                wideAcceptPair(paths, slot, objectId, first, t0, u0, v0_, t1, u1, v1, lo, entry, tol, best, second);
                             }
                         }
                     }

@@ -26,3 +26,15 @@
 // need no runner-up: occlusion is an OR over the same candidate set (their leaf gate includes the reference's entry-distance test
 // against the fixed ray length).  The reference's box / triangle test counters belong to its own walk: with the intersection
 // counters on, k_trace runs alone.
+//
+// Hits in front of their box.  The argument above lets the running hit distance cull a candidate only where two candidates lie within the rounding of a SLAB test
+// of each other.  It took for granted that a triangle's hit distance is not smaller than its leaf box's entry distance.  Exact arithmetic says so; the triangle
+// test's own rounding does not: its error grows with 1 / cos of the angle between ray and triangle plane, and a ray 0.14 degrees off a sheet had t = 0.9755346 on
+// a triangle whose leaf box it enters at 0.975574 -- 4e-5 apart, tol was 3.4e-6.  The reference's walk, with the neighbouring triangle's hit (0.97554296) found
+// first, culls that leaf (entry >= best) and reports the neighbour; found in the other order it reports the nearer hit.  So a candidate with lo < entry - tol
+// (entry: the exact box's entry distance, which the leaf gate computes anyway) is one whose fate depends on the reference's order: wideAcceptPair makes it its own
+// runner-up, and a ray that ends with it is retraced.  Down to entry - tol the existing rule covers it (a hit that culls it lies within tol of it and is its
+// runner-up).  NOT covered: the mirror case -- the walk culls such a leaf by its conservative entry (>= best + 2 tol) and never tests the triangle, while the
+// reference, meeting it first, reports it.  That needs the two walks to visit the two leaves in opposite orders with the nearer box holding the farther hit; no
+// constructed input has shown it (tests/test_gpu_wide_margins.py), DESIGN_PARITY.md "Margins" keeps it as an open finding.  Any-hit rays are not concerned: their
+// candidate set does not depend on a running distance.

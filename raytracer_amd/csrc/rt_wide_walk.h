@@ -157,20 +157,23 @@ RT_DEV float wideLeafPair(const RtTriangle* tris, uint32_t leaf, const Ray& ray,
 }
 // Such a hit counts only if the ray passes the leaf's exact box (gate[2 first], gate[2 first + 1]), as in the reference's walk -- any-hit rays: with
 // its entry-distance test against the fixed ray length.  `gateRay`: the quotients transformRayUnsafe built, which the caller has parked or rebuilds.
-RT_DEV bool wideLeafGate(const float4* gate, uint32_t first, const Ray& gateRay, bool shadow, float best)
+// `entry`: the exact box's entry distance as the reference's walk computes it (what its own culling compares with the running hit distance).
+RT_DEV bool wideLeafGate(const float4* gate, uint32_t first, const Ray& gateRay, bool shadow, float best, float& entry)
 {
     const float4 gmin = gate[2u * first], gmax = gate[2u * first + 1u];
-    float nearD;
-    return intersectBoxRayNoNaN(gateRay, gmin.x, gmin.y, gmin.z, gmax.x, gmax.y, gmax.z, nearD) && (!shadow || nearD < best);
+    return intersectBoxRayNoNaN(gateRay, gmin.x, gmin.y, gmin.z, gmax.x, gmax.y, gmax.z, entry) && (!shadow || entry < best);
 }
 // A candidate pair of a closest-hit ray behind its leaf's exact box: the running minimum, the runner-up and -- written through -- the HitPoint of
 // the path in `slot` (an exact tie is retraced anyway).  True: a hit record was written.  (k_trace_packet calls this behind its scalar loads.)
+// `entry`, `tol`: the leaf's exact entry distance (wideLeafGate) and the ray's tolerance.  A hit that lies more than tol IN FRONT of its own leaf box is one
+// the reference's walk finds or culls depending on its order (rt_wide_grid.inl, "Hits in front of their box"): it becomes its own runner-up, so the ray is
+// retraced if it ends with this hit.
 RT_DEV bool wideAcceptPair(const Paths& paths, uint32_t slot, uint32_t objectId, uint32_t first, float t0, float u0, float v0, float t1, float u1, float v1,
-                           float lo, float& best, float& second)
+                           float lo, float entry, float tol, float& best, float& second)
 {
     const float hi = fmaxf(t0, t1);
     if (!(lo < best)) { second = fminf(second, lo); return false; }
-    second = fminf(best, hi);
+    second = lo < entry - tol ? lo : fminf(best, hi);
     best = lo;
     const bool firstWins = t0 <= t1;
     prec(paths, R_HIT, slot) = f4(fbits(objectId), fbits(first + (firstWins ? 0u : 1u)), lo, firstWins ? u0 : u1);
