@@ -511,7 +511,8 @@ int rtgpu_read_wide_level(RtgpuContext* ctx, uint32_t objectIndex, RtWideLevelIn
  * pass renders the film it was queued for (and counts in rtgpu_get_counters), never the one behind the call.
  *   rtgpu_resize     a new film of the given size, both sum buffers zero.  Drops the active blocks of rtgpu_set_active_blocks (the whole
  *                    image is active again), the photons of RT_INTEGRATOR_VCM (the next pass merges nothing) and the history of
- *                    rtgpu_denoise_temporal (the next such call starts every pixel), also when the size is the one the context has.
+ *                    rtgpu_denoise_temporal (the next such call starts every pixel), also when the size is the one the context has.  It alone
+ *                    drops the ray source of rtgpu_set_ray_source too (the camera renders again); rtgpu_set_shard and rtgpu_reset keep it.
  *                    Keeps the scene, the integrator and its settings, the shard, the counters, rtgpu_set_guide_chain, and whatever device
  *                    memory still suffices.  A refused size (0, or above 65536) changes nothing.
  *   rtgpu_set_shard  the same for a new ownership of the frame's tiles.
@@ -917,6 +918,56 @@ int rtgpu_render_aovs_virtual(RtgpuContext* ctx, const RtPassParams* params, con
 /* Device pointers (16-byte aligned) on `stream`, as rtgpu_render_aovs_async. */
 int rtgpu_render_aovs_virtual_async(RtgpuContext* ctx, const RtPassParams* params, const RtAovChain* chain, const uint32_t* planes,
                                     uint32_t numPlanes, void* const* outputs, void* stream);
+
+/* ---------------------------------------------------------------------------------------------
+ * The ray source: passes along caller-supplied primary rays.  Every image starts at Camera::GenerateRay (Core/Scene/Camera.cpp:81-118), a perspective
+ * camera with a thin lens and barrel distortion.  A ray source replaces it at the source: a per-pixel table of primary rays -- an orthographic view, a
+ * panorama, a calibrated lens, the rays that leave a lightmap texel -- from which rtgpu_render_pass and every call that follows a pass's primary rays
+ * start.  Nothing behind the primary ray changes: the path records hold an origin and an unnormalised direction whoever wrote them.
+ *   table      width * height entries of 32 bytes in sum-buffer coordinates, row-major (as in RtBlock and the AOV planes; the film row flips inside):
+ *              entry y * width + x is the primary ray of pixel (x, y).  RtPrimaryRay has RtQueryRay's layout, so one buffer serves this call and
+ *              rtgpu_trace_rays; words 3 and 7 are never read.  The direction need not be unit length: it goes into the path's direction record as
+ *              given and Ray() normalises it wherever a ray is built -- rtgpu_trace_rays' rule, and the state in which the camera's direction is
+ *              stored.  No origin offset is applied.
+ *   while set  rtgpu_render_pass under RT_INTEGRATOR_PATH_TRACER_MIS, _PATH_TRACER and _DEBUG takes every pixel's primary ray from the table.
+ *              RtPassParams::camera and sampleOffset are not read (nor checked).  The sampler and the per-pixel generator start as
+ *              ResetPixel(x, y) with the pass's rngKey leaves them: a table ray is the ray of a camera that draws nothing.  All else of the pass is what
+ *              it was: seeds, passIndex and the secondary sum, depth, roulette, light sampling, the counters (numPrimaryRays included), shards, active
+ *              blocks, batching over lanes, both path-state layouts and the fused tail.
+ *   followers  every call documented as generating "the primary ray rtgpu_render_pass would generate" does so under a source too: rtgpu_render_aovs*, the
+ *              chain and virtual-position variants, rtgpu_record_paths -- hence rtgpu_denoise and rtgpu_denoise_var, whose guides the AOV call renders.
+ *              The rtgpu_denoise_temporal* entries refuse with RTGPU_ERR_UNSUPPORTED, as under a guide chain: a table has no worldToScreen to reproject
+ *              through (the pure rtgpu_temporal_accumulate* entries take planes and are untouched).  A pass under RT_INTEGRATOR_VCM or _LIGHT_TRACER
+ *              while a source is set: RTGPU_ERR_UNSUPPORTED (they splat through Camera::WorldToFilm).
+ *   setting    the queued passes are submitted first and render what they were queued for; lanes, ray queries and AOV calls are waited for, as in
+ *              rtgpu_update_objects.  The table is copied into memory of the context (the caller may free or overwrite it on return; both entries return
+ *              synchronised), and the COPY is checked by one read-only kernel (k_ray_source_check) before the source is replaced: an entry is degenerate
+ *              if a word of its origin or direction is not finite or its direction's squared length is 0 or not finite -- the degenerate-ray rule of
+ *              the ray queries.  A degenerate entry: RTGPU_ERR_INVALID_ARGUMENT, and the previous source, or the camera, stays exactly as it was; nothing
+ *              degenerate ever reaches a walk.
+ *   errors     count != width * height: RTGPU_ERR_INVALID_ARGUMENT; before rtgpu_resize: RTGPU_ERR_NOT_READY; rays == NULL with count == 0 clears the
+ *              source (the camera renders again), rays == NULL with any other count: RTGPU_ERR_INVALID_ARGUMENT.
+ *   _device    `rays` is device memory, held to hipPointerGetAttributes and hipMemGetAddressRange as rtgpu_update_mesh_device holds its arrays (memory of
+ *              the context's device, 4-byte aligned, whose allocation holds 32 * count bytes from the pointer on -- else RTGPU_ERR_INVALID_ARGUMENT); the
+ *              call orders itself behind `stream` (NULL: the context's own) with an event and copies device to device.  A multi-device context:
+ *              RTGPU_ERR_UNSUPPORTED -- rtgpu_set_ray_source serves it and replicates the table to every device.
+ *   keeps      rtgpu_upload_scene, the update calls, rtgpu_reset, rtgpu_set_shard, rtgpu_set_active_blocks and rtgpu_set_integrator keep the source.
+ *   drops      rtgpu_resize, also when the size is the one the context has (like the active blocks): a table is a frame's.
+ *   rtgpu_get_ray_source   outCount = the entries of the source, 0: the camera.
+ * Exporting the camera's rays: rtgpu_read_camera_rays[_async] write, for every pixel of the frame, what the generate kernel would store for `params` -- the
+ * origin and the unnormalised direction, in the table's layout and order, words 3 and 7 zero.  Not a pass: film, counters and queued passes are untouched;
+ * a multi-device context answers on its first device.  It is where a caller starts who wants the camera's rays with a lens model of their own on top, and
+ * what makes the source checkable bit for bit: a table exported from a camera renders that camera's frame.  A camera that draws from the sampler (dofEnable,
+ * or barrelDistortionVariableFactor != 0): RTGPU_ERR_UNSUPPORTED -- a table cannot carry the draws the camera took.  The export writes the camera's rays
+ * whether or not a source is set.  Before rtgpu_resize: RTGPU_ERR_NOT_READY.  The _async entry takes device memory (16-byte aligned, held to the pointer
+ * checks above) on `stream` (NULL: the context's own) and returns without synchronising.
+ * --------------------------------------------------------------------------------------------- */
+typedef struct RtPrimaryRay { float origin[3]; float _pad0; float direction[3]; float _pad1; } RtPrimaryRay;   /* 32 bytes */
+int rtgpu_set_ray_source(RtgpuContext* ctx, const RtPrimaryRay* rays, uint64_t count);                        /* host pointer */
+int rtgpu_set_ray_source_device(RtgpuContext* ctx, const RtPrimaryRay* rays, uint64_t count, void* stream);   /* device pointer */
+int rtgpu_get_ray_source(RtgpuContext* ctx, uint64_t* outCount);                                              /* 0: the camera */
+int rtgpu_read_camera_rays(RtgpuContext* ctx, const RtPassParams* params, RtPrimaryRay* out);                        /* host; synchronous */
+int rtgpu_read_camera_rays_async(RtgpuContext* ctx, const RtPassParams* params, RtPrimaryRay* out, void* stream);    /* device */
 
 /* ---------------------------------------------------------------------------------------------
  * Denoise: an edge-avoiding a-trous wavelet filter (Dammertz et al. 2010) over a rendered frame, guided by the first-hit planes

@@ -29,7 +29,7 @@
 // rt_runtime_scene.inl (rtgpu_upload_scene, rtgpu_update_objects: the copies of what rt_scene_prepare.h checks and builds on the host), rt_runtime_render.inl (arena sizing, traversal launchers, batch submission), rt_runtime_vcm.inl (bidirectional
 // integrator, Light Tracer), rt_runtime_kat.inl (known-answer hooks, rtgpu_evaluate_textures), rt_runtime_query.inl (batched ray queries), rt_runtime_paths.inl (path records),
 // rt_runtime_aov.inl (AOVs), rt_runtime_denoise.inl (the a-trous filter, rtgpu_denoise, rtgpu_postprocess_from),
-// rt_runtime_temporal.inl (temporal accumulation).
+// rt_runtime_temporal.inl (temporal accumulation), rt_runtime_raysource.inl (the ray source: passes along a caller's primary rays).
 //
 // Compile: hipcc --offload-arch=gfx950 -O3 -ffp-contract=off
 #include "rt_trace_common.h"
@@ -209,6 +209,7 @@ RTGPU_API void rtgpu_destroy(RtgpuContext* c)
     freeAov(c);
     freeChain(c);
     freeDenoise(c);
+    freeRaySource(c);
     freeScene(c); freeFilm(c);
     for (uint32_t i = 0; i < RT_MAX_LANES; ++i)
     {
@@ -308,6 +309,9 @@ RTGPU_API int rtgpu_resize(RtgpuContext* c, uint32_t width, uint32_t height)
     HIP_TRY(hipSetDevice(c->device));
     { int fr = flushQueued(c); if (fr) return fr; }
     HIP_TRY(syncLanes(c));
+    // a ray source is a frame's: the camera renders again, also when the size is the one the context has (an asynchronous AOV call may still read the table)
+    // (both buffers are sized for the old frame: the one a refused table was copied into goes too)
+    if (c->raySource.table || c->raySource.incoming) { waitQueries(c); dropRaySource(c); }
     c->width = width; c->height = height;
     return rebuildFilm(c);
 }
@@ -414,7 +418,7 @@ static int checkPass(const RtgpuContext* c, const RtPassParams* p)
     if (p->numDimensions > RTGPU_MAX_DIMENSIONS) return fail(RTGPU_ERR_INVALID_ARGUMENT, "numDimensions exceeds RTGPU_MAX_DIMENSIONS");
     if (p->numDimensions > 0 && !p->seed) return fail(RTGPU_ERR_INVALID_ARGUMENT, "seed is NULL");
     if (p->maxRayDepth >= 255u) return fail(RTGPU_ERR_INVALID_ARGUMENT, "maxRayDepth must be < 255");
-    if (p->camera.dofEnable && p->camera.bokehShape > 2u) return fail(RTGPU_ERR_UNSUPPORTED, "bokeh shapes: circle, hexagon, square (NGon is a TODO in the reference, texture-shaped bokeh is not implemented)");
+    if (!c->raySource.table && p->camera.dofEnable && p->camera.bokehShape > 2u) return fail(RTGPU_ERR_UNSUPPORTED, "bokeh shapes: circle, hexagon, square (NGon is a TODO in the reference, texture-shaped bokeh is not implemented)");
     return RTGPU_OK;
 }
 // the device's per-pass constants; `seed` is assigned where the pass is submitted
@@ -434,6 +438,9 @@ static void makeDevPass(const RtgpuContext* c, const RtPassParams* p, DevPass& p
     memcpy(pass.bsdfSamplingWeight, p->bsdfSamplingWeight, 16);
     pass.rngKey[0] = p->rngKey[0]; pass.rngKey[1] = p->rngKey[1];
     pass.width = c->width; pass.height = c->height;
+    // under a ray source the table is the camera: the pass carries one that draws nothing -- dense shading re-runs it at bounce 0 only to restore the
+    // sampler (rt_dense.inl), which then stays as the table kernels left it -- and the caller's camera and sample offset are never read
+    if (c->raySource.table) { memset(&pass.camera, 0, sizeof(pass.camera)); pass.sampleOffset[0] = 0.0f; pass.sampleOffset[1] = 0.0f; }
 }
 
 RTGPU_API int rtgpu_render_pass(RtgpuContext* c, const RtPassParams* p)
@@ -721,6 +728,7 @@ RTGPU_API int rtgpu_postprocess(RtgpuContext* c, const RtPostprocessParams* p, u
 #include "rt_runtime_denoise.inl"
 #include "rt_runtime_temporal.inl"
 #include "rt_runtime_refit.inl"   // rtgpu_update_mesh: a deformed mesh's tables refitted on the device
+#include "rt_runtime_raysource.inl"   // rtgpu_set_ray_source: primary rays from a table of the caller's
 
 RTGPU_API int rtgpu_set_concurrency(RtgpuContext* c, uint32_t lanes)
 {

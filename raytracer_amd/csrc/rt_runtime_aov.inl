@@ -51,7 +51,7 @@ static int launchAovChunk(RtgpuContext* c, hipStream_t stream, unsigned long lon
     HIP_TRY(hipMemsetAsync(w.counts, 0, QC_WORDS * sizeof(uint32_t), stream));
     hipLaunchKernelGGL(k_aov_pixels, grid, block, 0, stream, a.slotPixel, n, firstPixel, c->width);
     // one pass, so a pass holds all `n` slots: slot / slotsPerPass = 0 for every slot
-    hipLaunchKernelGGL(k_generate, grid, block, 0, stream, c->sceneDev, a.passDev, n, w.paths, a.slotPixel, n, w.queue, w.counts + QC_QUEUE, w.counters);
+    launchGenerate(c, grid, stream, a.passDev, n, w.paths, a.slotPixel, n, w.queue, w.counts + QC_QUEUE, w.counters);   // (the camera's rays, or the ray source's)
     // a cost plane takes the counting binary walk; otherwise the walk the context renders with, as the ray queries take it (launchArenaWalk, rt_runtime_query.inl)
     launchArenaWalk(c, stream, w, true, useWide(c) && !cost, cost ? a.rayCounts : nullptr);
     const uint4* rayCounts = cost ? a.rayCounts : nullptr;
@@ -224,7 +224,7 @@ static int launchChainChunk(RtgpuContext* c, hipStream_t stream, unsigned long l
     HIP_TRY(hipMemsetAsync(l.queueCounts, 0, laneCountBytes(l), stream));
     hipLaunchKernelGGL(k_aov_pixels, grid, block, 0, stream, a.slotPixel, n, firstPixel, c->width);
     // one pass, so a pass holds all `n` slots: slot / slotsPerPass = 0 for every slot
-    hipLaunchKernelGGL(k_generate, grid, block, 0, stream, c->sceneDev, a.passDev, n, l.paths, a.slotPixel, n, l.queues[0], counts.pathCounts + 0, a.counters);
+    launchGenerate(c, grid, stream, a.passDev, n, l.paths, a.slotPixel, n, l.queues[0], counts.pathCounts + 0, a.counters);
     launchSlotBounces(c, stream, a.counters, l, counts, lastDepth, lastDepth, false, [&](uint32_t depth)
     {
         if (depth == lastDepth) return;   // every vertex of the last bounce stops

@@ -367,6 +367,18 @@ struct RtgpuContext
         float4* moments = nullptr; size_t momentsCapacity = 0;
     } temporal;
 
+    // the ray source (rtgpu_set_ray_source; rt_runtime_raysource.inl): the table the generate kernels read in place of the camera, and the buffer the next
+    // table is copied into and checked in before the two change places -- a refused table never becomes the source, and a caller who sets a table per
+    // pass (anti-aliasing) allocates twice, not per call.  Both hold width * height entries of two float4 and go with the film's size (rtgpu_resize).
+    struct RaySource
+    {
+        float4* table = nullptr;                  // null: the camera
+        float4* incoming = nullptr;
+        uint32_t* degenerate = nullptr;           // what k_ray_source_check counted
+        float4* exported = nullptr; size_t exportedEntries = 0;   // rtgpu_read_camera_rays' device copy
+        hipEvent_t order = nullptr;               // rtgpu_set_ray_source_device: puts the copy behind the caller's stream
+    } raySource;
+
     // timing
     bool timing = false;
     struct Timed { int kc; hipEvent_t a, b; };
@@ -535,6 +547,36 @@ static void freeDenoise(RtgpuContext* c)
     if (d.done) (void)hipEventDestroy(d.done);
     if (d.sumRead) (void)hipEventDestroy(d.sumRead);
     d.done = nullptr; d.sumRead = nullptr; d.sumReadPending = false;
+}
+
+// A caller's device array of `bytes` bytes, before any kernel or copy reads or writes it (rtgpu_update_mesh_device, rtgpu_set_ray_source_device,
+// rtgpu_read_camera_rays_async): aligned to alignMask + 1 bytes, device memory of the context's device, inside one allocation to its last byte.  `unit` names
+// what the allocation must hold ("12 bytes per vertex").
+static int callerDeviceArray(const RtgpuContext* c, const void* p, size_t bytes, uintptr_t alignMask, const char* name, const char* unit)
+{
+    const std::string what(name);
+    if ((uintptr_t)p & alignMask) return fail(RTGPU_ERR_INVALID_ARGUMENT, what + " is not aligned to " + (alignMask == 3u ? std::string("a float") : std::to_string(alignMask + 1u) + " bytes"));
+    hipPointerAttribute_t attributes;
+    memset(&attributes, 0, sizeof(attributes));
+    if (hipPointerGetAttributes(&attributes, p) != hipSuccess) { (void)hipGetLastError(); return fail(RTGPU_ERR_INVALID_ARGUMENT, what + " is not a device pointer"); }
+    if (attributes.type != hipMemoryTypeDevice || attributes.device != c->device) return fail(RTGPU_ERR_INVALID_ARGUMENT, what + " is not memory of the context's device");
+    hipDeviceptr_t base = nullptr; size_t size = 0;
+    if (hipMemGetAddressRange(&base, &size, (hipDeviceptr_t)p) != hipSuccess) { (void)hipGetLastError(); return fail(RTGPU_ERR_INVALID_ARGUMENT, what + " lies in no device allocation"); }
+    const uintptr_t begin = (uintptr_t)base, at = (uintptr_t)p;
+    if (at < begin || at - begin > size || size - (at - begin) < bytes) return fail(RTGPU_ERR_INVALID_ARGUMENT, what + ": its allocation ends before " + unit + " do");
+    return RTGPU_OK;
+}
+
+// the ray source's tables (the caller has waited for whatever reads them): the camera renders again
+static void dropRaySource(RtgpuContext* c) { devFree(c->raySource.table, c->raySource.incoming); }
+static void freeRaySource(RtgpuContext* c)
+{
+    RtgpuContext::RaySource& s = c->raySource;
+    dropRaySource(c);
+    devFree(s.degenerate, s.exported);
+    s.exportedEntries = 0;
+    if (s.order) (void)hipEventDestroy(s.order);
+    s.order = nullptr;
 }
 
 static void freeRecorder(RtgpuContext* c)

@@ -51,7 +51,7 @@ static int launchRecordChunk(RtgpuContext* c, hipStream_t stream, uint32_t n, ui
     const dim3 block(RT_BLOCK), grid((n + RT_BLOCK - 1u) / RT_BLOCK);
     HIP_TRY(hipMemsetAsync(l.queueCounts, 0, laneCountBytes(l), stream));
     // one pass, so a pass holds all `n` slots: slot / slotsPerPass = 0 for every slot
-    hipLaunchKernelGGL(k_generate, grid, block, 0, stream, c->sceneDev, rec.passDev, n, l.paths, rec.slotPixel, n, l.queues[0], counts.pathCounts + 0, rec.counters);
+    launchGenerate(c, grid, stream, rec.passDev, n, l.paths, rec.slotPixel, n, l.queues[0], counts.pathCounts + 0, rec.counters);   // (the camera's rays, or the ray source's)
     launchSlotBounces(c, stream, rec.counters, l, counts, maxRayDepth, maxRayDepth + 1u, c->numLights != 0, [&](uint32_t depth)
     {
         hipLaunchKernelGGL((k_shade_record<false, false>), grid, block, 0, stream, c->sceneDev, rec.passDev, n, l.paths, l.queues[depth & 1u], counts.pathCounts + depth,

@@ -378,17 +378,7 @@ RTGPU_API int rtgpu_update_mesh(RtgpuContext* c, const RtMeshUpdate* u)
 // a caller's device array of `bytes` bytes: device memory of the context's device, inside one allocation to its last byte -- no kernel reads past one
 static int refitDeviceArray(const RtgpuContext* c, const float* p, size_t bytes, const char* name)
 {
-    const std::string what(name);
-    if ((uintptr_t)p & 3u) return fail(RTGPU_ERR_INVALID_ARGUMENT, what + " is not aligned to a float");
-    hipPointerAttribute_t attributes;
-    memset(&attributes, 0, sizeof(attributes));
-    if (hipPointerGetAttributes(&attributes, p) != hipSuccess) { (void)hipGetLastError(); return fail(RTGPU_ERR_INVALID_ARGUMENT, what + " is not a device pointer"); }
-    if (attributes.type != hipMemoryTypeDevice || attributes.device != c->device) return fail(RTGPU_ERR_INVALID_ARGUMENT, what + " is not memory of the context's device");
-    hipDeviceptr_t base = nullptr; size_t size = 0;
-    if (hipMemGetAddressRange(&base, &size, (hipDeviceptr_t)p) != hipSuccess) { (void)hipGetLastError(); return fail(RTGPU_ERR_INVALID_ARGUMENT, what + " lies in no device allocation"); }
-    const uintptr_t begin = (uintptr_t)base, at = (uintptr_t)p;
-    if (at < begin || at - begin > size || size - (at - begin) < bytes) return fail(RTGPU_ERR_INVALID_ARGUMENT, what + ": its allocation ends before 12 bytes per vertex do");
-    return RTGPU_OK;
+    return callerDeviceArray(c, p, bytes, 3u, name, "12 bytes per vertex");
 }
 
 // k_refit_check over `numVertices` positions and the mesh's triangles (none: the finite check alone) into `out`, on `stream`

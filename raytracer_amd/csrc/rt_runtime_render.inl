@@ -237,7 +237,9 @@ static int submitDenseBatch(RtgpuContext* c, BatchLane& l, const LaneCounts& cou
     HIP_TRY(hipMemsetAsync(l.denseCounts, 0, (size_t)plane * (l.queueCountCapacity + 1u) * sizeof(uint32_t), l.stream));
     {
         LaunchTimer t(c, l.stream, KC_GENERATE);
-        hipLaunchKernelGGL(k_generate_dense, grid, block, 0, l.stream, c->sceneDev, passesDev, c->numSlots, l.paths, c->slotPixel, totalSlots, shardCapacity, l.denseCounts, c->counters);
+        if (c->raySource.table)
+            hipLaunchKernelGGL(k_generate_dense_rays, grid, block, 0, l.stream, c->sceneDev, passesDev, c->numSlots, l.paths, c->slotPixel, totalSlots, shardCapacity, l.denseCounts, c->counters, c->raySource.table);
+        else hipLaunchKernelGGL(k_generate_dense, grid, block, 0, l.stream, c->sceneDev, passesDev, c->numSlots, l.paths, c->slotPixel, totalSlots, shardCapacity, l.denseCounts, c->counters);
     }
     const bool haveNee = c->numLights != 0 && !c->plainPathTracer;
     // The fused tail (rt_tail.hip): from bounce `tailDepth` on, one persistent launch takes the batch's remaining paths to their end.  Single-mesh
@@ -303,6 +305,15 @@ static void launchSlotBounces(RtgpuContext* c, hipStream_t stream, unsigned long
     }
 }
 
+// k_generate of a slot-per-pixel sequence (a batch lane's, the recorder's, the AOV calls'): from the camera, or from the ray source where one is set
+static void launchGenerate(RtgpuContext* c, dim3 grid, hipStream_t stream, const DevPass* passesDev, uint32_t slotsPerPass, const Paths& paths, const uint32_t* slotPixel,
+                           uint32_t totalSlots, uint32_t* queue, uint32_t* queueCount, unsigned long long* counters)
+{
+    if (c->raySource.table)
+        hipLaunchKernelGGL(k_generate_rays, grid, dim3(RT_BLOCK), 0, stream, c->sceneDev, passesDev, slotsPerPass, paths, slotPixel, totalSlots, queue, queueCount, counters, c->raySource.table);
+    else hipLaunchKernelGGL(k_generate, grid, dim3(RT_BLOCK), 0, stream, c->sceneDev, passesDev, slotsPerPass, paths, slotPixel, totalSlots, queue, queueCount, counters);
+}
+
 #define RT_LAUNCH_SHADE(...) hipLaunchKernelGGL((k_shade<__VA_ARGS__>), grid, block, 0, l.stream, c->sceneDev, passesDev, c->numSlots, l.paths, l.queues[depth & 1u], counts.pathCounts + depth, \
                                              l.queues[(depth + 1u) & 1u], counts.pathCounts + depth + 1, l.shadowQueues[depth & 1u], counts.shadowCounts + depth, c->counters)
 
@@ -312,7 +323,7 @@ static void submitSlotBatch(RtgpuContext* c, BatchLane& l, const LaneCounts& cou
     const dim3 block(RT_BLOCK);
     {
         LaunchTimer t(c, l.stream, KC_GENERATE);
-        hipLaunchKernelGGL(k_generate, grid, block, 0, l.stream, c->sceneDev, passesDev, c->numSlots, l.paths, c->slotPixel, totalSlots, l.queues[0], counts.pathCounts + 0, c->counters);
+        launchGenerate(c, grid, l.stream, passesDev, c->numSlots, l.paths, c->slotPixel, totalSlots, l.queues[0], counts.pathCounts + 0, c->counters);
     }
     launchSlotBounces(c, l.stream, c->counters, l, counts, maxRayDepth, c->debugMode >= 0 ? 0u : maxRayDepth + 1u, c->numLights != 0 && !c->plainPathTracer, [&](uint32_t depth)
     {

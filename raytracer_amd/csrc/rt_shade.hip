@@ -40,3 +40,7 @@ RT_AOV_CLASSES(RT_X)
 #define RT_X(C) template __global__ void __launch_bounds__(RT_BLOCK) k_aov_resolve_chain<C> RT_K_AOV_RESOLVE_CHAIN_ARGS;
 RT_AOV_CLASSES(RT_X)
 #undef RT_X
+
+// (behind everything else: the kernels above keep their places in the code object) k_generate_dense fed from a table of rays, rtgpu_set_ray_source
+#define RT_RAYSOURCE_DENSE 1
+#include "rt_raysource.inl"

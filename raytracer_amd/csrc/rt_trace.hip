@@ -12,6 +12,7 @@
 //   rt_query.inl          batched ray queries around the walks above (rtgpu_trace_rays)
 //   rt_denoise.inl        the a-trous filter (rtgpu_filter_atrous, rtgpu_denoise)
 //   rt_temporal.inl       temporal accumulation (rtgpu_temporal_accumulate, rtgpu_denoise_temporal)
+//   rt_raysource.inl      the ray source: k_generate fed from a table of rays, the table's check, the camera's rays written out (rtgpu_set_ray_source)
 // The host side (rt_runtime.hip) launches them through the declarations of rt_trace_kernels.h.
 //
 // Compile: hipcc --offload-arch=gfx950 -O3 -ffp-contract=off
@@ -54,3 +55,4 @@ RT_K_TRACE_PER_RAY_INSTANCES(RT_X)
 // (behind everything else, for the same reason)
 #include "rt_denoise.inl"
 #include "rt_temporal.inl"
+#include "rt_raysource.inl"

@@ -148,5 +148,12 @@ template <bool kMoving = false, bool kClip = false, bool kDeform = false> __glob
 template <int kRadius> __global__ void RT_TEMPORAL_MOMENTS_ATTR k_temporal_moments RT_K_TEMPORAL_MOMENTS_ARGS;
 template <bool kMoving = false, bool kClip = false> __global__ void RT_ATROUS_ATTR k_temporal_chain RT_K_TEMPORAL_CHAIN_ARGS;
 template <int kRadius> __global__ void RT_TEMPORAL_MOMENTS_ATTR k_temporal_moments_chain RT_K_TEMPORAL_MOMENTS_CHAIN_ARGS;
+// the ray source (rt_raysource.inl): k_generate's arguments and the table behind them; the table's check; the camera's rays in the table's layout
+__global__ void __launch_bounds__(RT_BLOCK) k_generate_rays(const RtSceneDesc scene, const DevPass* __restrict__ passes, uint32_t slotsPerPass,
+                                                            const Paths paths, const uint32_t* __restrict__ slotPixel, uint32_t numSlots,
+                                                            uint32_t* __restrict__ queue, uint32_t* __restrict__ queueCount,
+                                                            unsigned long long* counters, const float4* __restrict__ rays);
+__global__ void __launch_bounds__(RT_BLOCK) k_ray_source_check(const float4* __restrict__ rays, uint32_t count, uint32_t* __restrict__ outDegenerate);
+__global__ void __launch_bounds__(RT_BLOCK) k_camera_rays(const RtCamera camera, float sampleOffsetX, float sampleOffsetY, uint32_t width, uint32_t height, float4* __restrict__ out);
 __global__ void __launch_bounds__(RT_MONSTER_BLOCK) k_trace_monster(const RtSceneDesc scene, const Paths paths, const uint32_t* __restrict__ queue, const uint32_t* __restrict__ queueCount);
 #endif

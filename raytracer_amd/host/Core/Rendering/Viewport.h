@@ -58,6 +58,10 @@ public:
     // Extension (the reference has no seed API): re-seed the Viewport's generators.
     void SetSeed(uint64 seed);
     void ClearAccumulation();   // sums, progress, counters, block list start over; the sample sequence goes on
+    // Extension (rtgpu_set_ray_source): the passes that follow start at the caller's primary rays -- width * height entries, entry y * width + x the ray of
+    // pixel (x, y) of the sum buffer -- instead of the camera's, whose part of Render()'s constants is then not read.  nullptr with count 0: the camera
+    // again.  The table is copied.  Resize and SetRenderer drop it (a table is a frame's, and it lives in the renderer's device context).
+    bool SetRaySource(const RtPrimaryRay* rays, size_t count);
 
     // The per-pass constants Render() would use next; advances the Halton sequence and the generator
     // exactly like Render().  Exposed so parity tests can feed identical constants to the CPU oracle.

@@ -6,6 +6,9 @@
 // --denoise [N] (the frame goes through N levels, default 5, of the a-trous filter before it is tone-mapped: rtgpu_denoise, rtgpu_postprocess_from)
 // and --denoise-variance [N] (the same through the variance-guided filter over the film's two sum buffers: rtgpu_denoise_var),
 // --guide-chain N beside either (the filter's guides follow every pixel's path through up to N mirror and glass vertices: rtgpu_set_guide_chain);
+// --projection orthographic|panorama|fisheye (the frame is rendered along a table of primary rays built here from the scene file's camera transform, in
+// place of the perspective camera: Viewport::SetRaySource; --projection-size S: the orthographic picture is 2 S world units wide, --projection-fov D: the
+// fisheye's image circle spans D degrees; --denoise and --denoise-variance work with it: their guides follow the table);
 // the environment variable RTGPU_DEVICES ("0,1,2,3" / "all") spreads the frame over several GPUs (Core/Rendering/Renderer.h).
 #include "../Demo.h"
 #include "../SceneLoader.h"
@@ -113,6 +116,49 @@ static bool DenoisedFrontBuffer(Viewport& viewport, const Camera& camera, IRende
     return true;
 }
 
+// The table of --projection: one primary ray per pixel, row 0 the top of the picture, from the camera's transform (rows: right, up, forward, position).
+// orthographic: parallel rays along forward, the picture 2 * size wide; panorama: equirectangular, the centre column looks forward and the rows sweep from
+// straight up to straight down; fisheye: equidistant, fovDegrees across the circle inscribed in the shorter side, the axis ray outside it.
+static std::vector<RtPrimaryRay> ProjectionTable(const std::string& projection, const RtCamera& camera, uint32 width, uint32 height, double size, double fovDegrees)
+{
+    const double pi = 3.14159265358979323846;
+    const float* m = camera.localToWorld;
+    const double right[3] = { m[0], m[1], m[2] }, up[3] = { m[4], m[5], m[6] }, forward[3] = { m[8], m[9], m[10] }, position[3] = { m[12], m[13], m[14] };
+    std::vector<RtPrimaryRay> table((size_t)width * height);
+    const double shorter = width < height ? width : height;
+    for (uint32 y = 0; y < height; ++y)
+        for (uint32 x = 0; x < width; ++x)
+        {
+            const double u = (x + 0.5) / width, v = (height - 1u - y + 0.5) / height;   // film coordinates: v up
+            double o[3] = { position[0], position[1], position[2] }, d[3];
+            double cr = 0.0, cu = 0.0, cf = 1.0;   // the direction's coordinates along right, up, forward
+            if (projection == "orthographic")
+            {
+                const double px = (2.0 * u - 1.0) * size, py = (2.0 * v - 1.0) * size * height / width;
+                for (int k = 0; k < 3; ++k) o[k] += px * right[k] + py * up[k];
+            }
+            else if (projection == "panorama")
+            {
+                const double azimuth = (u - 0.5) * 2.0 * pi, elevation = (v - 0.5) * pi;
+                cf = cos(elevation) * cos(azimuth); cr = cos(elevation) * sin(azimuth); cu = sin(elevation);
+            }
+            else   // fisheye
+            {
+                const double px = (2.0 * u - 1.0) * width / shorter, py = (2.0 * v - 1.0) * height / shorter, r = sqrt(px * px + py * py);
+                if (r > 0.0 && r <= 1.0)
+                {
+                    const double theta = r * 0.5 * fovDegrees * pi / 180.0;
+                    cf = cos(theta); cr = sin(theta) * px / r; cu = sin(theta) * py / r;
+                }
+            }
+            for (int k = 0; k < 3; ++k) d[k] = cr * right[k] + cu * up[k] + cf * forward[k];
+            RtPrimaryRay& ray = table[(size_t)y * width + x];
+            memset(&ray, 0, sizeof(ray));
+            for (int k = 0; k < 3; ++k) { ray.origin[k] = (float)o[k]; ray.direction[k] = (float)d[k]; }
+        }
+    return table;
+}
+
 int main(int argc, char* argv[])
 {
     uint32 width = 1280, height = 720, passes = 64, depth = 20;
@@ -120,6 +166,7 @@ int main(int argc, char* argv[])
     uint32 denoiseLevels = 0; bool denoiseVariance = false; int guideChain = -1;
     std::string scenePath, rendererName = "Path Tracer MIS", output = "out.bmp";
     unsigned long long seed = 0; bool haveSeed = false;
+    std::string projection; double projectionSize = 5.0, projectionFov = 180.0;
     for (int i = 1; i < argc; ++i)
     {
         const std::string a = argv[i];
@@ -146,7 +193,14 @@ int main(int argc, char* argv[])
             guideChain = atoi(value("--guide-chain"));
             if (guideChain < 0 || guideChain > (int)RT_AOV_CHAIN_MAX) { fprintf(stderr, "--guide-chain takes 0..%u vertices\n", RT_AOV_CHAIN_MAX); return 2; }
         }
-        else { fprintf(stderr, "usage: rt_demo -s scene.json [--data dir/] [-w W] [-h H] [--passes N] [--depth D] [--renderer name] [--output out.bmp] [--seed N] [--debug-pixel X,Y] [--denoise [N]] [--denoise-variance [N]] [--guide-chain N]\n"); return 2; }
+        else if (a == "--projection")
+        {
+            projection = value("--projection");
+            if (projection != "orthographic" && projection != "panorama" && projection != "fisheye") { fprintf(stderr, "--projection takes orthographic, panorama or fisheye\n"); return 2; }
+        }
+        else if (a == "--projection-size") { projectionSize = atof(value("--projection-size")); if (!(projectionSize > 0.0)) { fprintf(stderr, "--projection-size takes a positive half width\n"); return 2; } }
+        else if (a == "--projection-fov") { projectionFov = atof(value("--projection-fov")); if (!(projectionFov > 0.0 && projectionFov <= 360.0)) { fprintf(stderr, "--projection-fov takes 0..360 degrees\n"); return 2; } }
+        else { fprintf(stderr, "usage: rt_demo -s scene.json [--data dir/] [-w W] [-h H] [--passes N] [--depth D] [--renderer name] [--output out.bmp] [--seed N] [--debug-pixel X,Y] [--denoise [N]] [--denoise-variance [N]] [--guide-chain N] [--projection orthographic|panorama|fisheye] [--projection-size S] [--projection-fov DEGREES]\n"); return 2; }
     }
     if (guideChain >= 0 && !denoiseLevels) { fprintf(stderr, "--guide-chain steers the denoiser's guides: it needs --denoise or --denoise-variance\n"); return 2; }
     if (scenePath.empty()) { fprintf(stderr, "no scene given (-s scene.json)\n"); return 2; }
@@ -166,6 +220,14 @@ int main(int argc, char* argv[])
     if (!renderer) { fprintf(stderr, "renderer '%s' is not available (no GPU?)\n", rendererName.c_str()); return 1; }
     if (!viewport.SetRenderer(renderer)) return 1;
     viewport.Reset();
+    if (!projection.empty())
+    {
+        RtCamera desc;
+        if (!camera.GetDesc(desc)) return 1;
+        const std::vector<RtPrimaryRay> table = ProjectionTable(projection, desc, width, height, projectionSize, projectionFov);
+        if (!viewport.SetRaySource(table.data(), table.size())) return 1;
+        printf("projection: %s, %zu primary rays from the scene's camera transform\n", projection.c_str(), table.size());
+    }
 
     const auto t0 = std::chrono::steady_clock::now();
     uint32 rendered = 0;

@@ -534,6 +534,18 @@ bool Viewport::UpdateScene()
     return renderer && renderer->UpdateScene();
 }
 
+bool Viewport::SetRaySource(const RtPrimaryRay* rays, size_t count)
+{
+    PathTracerMIS* renderer = dynamic_cast<PathTracerMIS*>(mRenderer.get());
+    if (!renderer || !renderer->GetDeviceContext()) return false;
+    if (rtgpu_set_ray_source(renderer->GetDeviceContext(), rays, (uint64_t)count) != RTGPU_OK)
+    {
+        fprintf(stderr, "[rt] ERROR: cannot set the ray source: %s\n", rtgpu_last_error());
+        return false;
+    }
+    return true;
+}
+
 bool Viewport::SetRenderingParams(const RenderingParams& params)
 {
     if (params.maxRayDepth >= 255u || params.antiAliasingSpread < 0.0f) return false;
