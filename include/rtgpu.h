@@ -1424,11 +1424,20 @@ int rtgpu_postprocess_from(RtgpuContext* ctx, const RtPostprocessParams* params,
  *   rtgpu_kat_mesh    MeshShape::Traverse / Traverse_Shadow / EvaluateIntersection (Core/Shapes/MeshShape.cpp:134-328) through the
  *                     traversal state machine of the path tracer, on the uploaded scene's single mesh object: rays = n * {origin[3],
  *                     direction[3], tmax}, out = n * 19 words {objectId (7 on a hit), triangle, distance, u, v, anyHit, tangent[4],
- *                     normal[4], texCoord[4], material}. */
+ *                     normal[4], texCoord[4], material}.
+ *   rtgpu_kat_postprocess  the per-pixel body of Viewport::PostProcessTile (the function rtgpu_postprocess's kernels call) on n records, each with
+ *                     its own params, at pixel (0, 0), without bloom: rgb = n * 3 sum-buffer floats, outBGR = n words 0x00RRGGBB,
+ *                     outToneMapped (n * 3, may be NULL) = the floats Vector4::ToBGR quantises, dithering included.  colorScale is computed
+ *                     on the host as rtgpu_postprocess does.  An unknown tone mapper or numPasses = 0 in any record: INVALID_ARGUMENT.
+ *   rtgpu_kat_blur    Bitmap::GaussianBlur(sigma, 8) in place on a tight float3 image in host memory: the window plan and the two kernel
+ *                     launches of rtgpu_postprocess's bloom levels.  Needs no rtgpu_resize.  Refused as there (RTGPU_ERR_UNSUPPORTED, the
+ *                     image untouched) unless width is a multiple of 4 and both sizes are <= 4096 and > 2 * wu + 1 for this sigma's window. */
 int rtgpu_kat(RtgpuContext* ctx, uint32_t func, const float* in, uint32_t inStride, float* out, uint32_t outStride, uint32_t n);
 int rtgpu_kat_sampler(RtgpuContext* ctx, const uint16_t* blueNoise, const uint32_t* in, uint32_t inStride, uint32_t count, uint32_t n,
                       uint32_t* outInts, float* outFloats);
 int rtgpu_kat_mesh(RtgpuContext* ctx, const float* rays, uint32_t n, uint32_t* out);
+int rtgpu_kat_postprocess(RtgpuContext* ctx, const RtPostprocessParams* params, const float* rgb, uint32_t n, uint32_t* outBGR, float* outToneMapped);
+int rtgpu_kat_blur(RtgpuContext* ctx, float* rgbHost, uint32_t width, uint32_t height, float sigma);
 
 /* --- measurement hooks (bench.py) ---------------------------------------------------------------
  * Per-kernel-class GPU time in milliseconds accumulated since rtgpu_reset, measured with HIP events

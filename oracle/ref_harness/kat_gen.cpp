@@ -1086,6 +1086,31 @@ static void genObjMesh()
 // linked here) composed from the reference's own functions in the same order -- Vector4 ops, FastLog / FastExp
 // (Transcendental.cpp), ToneMap (ColorHelpers.h), Vector4::ToBGR -- without bloom and without dithering.
 // File "postprocess_kat.bin": u32 count; records: RtPostprocessParams, f32 raw[3], u32 bgr, f32 toneMapped[3].
+// Viewport::PostProcessTile up to the colour that enters ToneMap
+static Vector4 postprocessBeforeToneMap(const RtPostprocessParams& P, const PostprocessParams& params, const Float3& raw)
+{
+    const Vector4 colorScale = params.colorFilter * powf(2.0f, params.exposure);
+    const float pixelScaling = 1.0f / (float)P.numPasses;
+    Vector4 rgbColor(raw);   // Vector4_Load_Float3_Unsafe(mSum.GetPixelRef<Float3>(x, y)): the w lane (the next pixel) never reaches ToBGR
+    rgbColor *= pixelScaling;
+    const float grayscale = Vector4::Dot3(rgbColor, Vector4(0.2126f, 0.7152f, 0.0722f));
+    rgbColor = Vector4::Max(Vector4::Zero(), Vector4::Lerp(Vector4(grayscale), rgbColor, params.saturation));
+    rgbColor = FastExp(FastLog(rgbColor) * params.contrast);
+    rgbColor *= colorScale;
+    return rgbColor;
+}
+// one record: the per-pixel body of Viewport::PostProcessTile on `raw`, appended as { RtPostprocessParams, raw[3], bgr, toneMapped[3] }
+static void pushPostprocessRecord(std::vector<uint32_t>& out, const RtPostprocessParams& P, const PostprocessParams& params, const Float3& raw)
+{
+    const Vector4 toneMapped = ToneMap(postprocessBeforeToneMap(P, params, raw), params.tonemapper);
+    const uint32_t bgr = toneMapped.ToBGR();
+
+    uint32_t pw[sizeof(P) / 4]; memcpy(pw, &P, sizeof(P));
+    for (uint32_t w : pw) out.push_back(w);
+    out.push_back(fbits(raw.x)); out.push_back(fbits(raw.y)); out.push_back(fbits(raw.z));
+    out.push_back(bgr & 0x00FFFFFFu);
+    out.push_back(fbits(toneMapped.x)); out.push_back(fbits(toneMapped.y)); out.push_back(fbits(toneMapped.z));
+}
 static void genPostprocess()
 {
     Lcg g(110);
@@ -1110,25 +1135,96 @@ static void genPostprocess()
         switch (i % 7) { case 0: scale = 0.0f; break; case 1: scale = 1.0e-4f; break; case 2: scale = 50.0f; break; case 3: scale = 1.0e4f; break; default: break; }
         const Float3 raw(g.range(0.0f, 2.0f) * scale * numPasses, g.range(0.0f, 2.0f) * scale * numPasses, g.range(0.0f, 2.0f) * scale * numPasses);
 
-        // Viewport::PostProcessTile
-        const Vector4 colorScale = params.colorFilter * powf(2.0f, params.exposure);
-        const float pixelScaling = 1.0f / (float)numPasses;
-        Vector4 rgbColor(raw);   // Vector4_Load_Float3_Unsafe(mSum.GetPixelRef<Float3>(x, y)): the w lane (the next pixel) never reaches ToBGR
-        rgbColor *= pixelScaling;
-        const float grayscale = Vector4::Dot3(rgbColor, Vector4(0.2126f, 0.7152f, 0.0722f));
-        rgbColor = Vector4::Max(Vector4::Zero(), Vector4::Lerp(Vector4(grayscale), rgbColor, params.saturation));
-        rgbColor = FastExp(FastLog(rgbColor) * params.contrast);
-        rgbColor *= colorScale;
-        const Vector4 toneMapped = ToneMap(rgbColor, params.tonemapper);
-        const uint32_t bgr = toneMapped.ToBGR();
-
-        uint32_t pw[sizeof(P) / 4]; memcpy(pw, &P, sizeof(P));
-        for (uint32_t w : pw) out.push_back(w);
-        out.push_back(fbits(raw.x)); out.push_back(fbits(raw.y)); out.push_back(fbits(raw.z));
-        out.push_back(bgr & 0x00FFFFFFu);
-        out.push_back(fbits(toneMapped.x)); out.push_back(fbits(toneMapped.y)); out.push_back(fbits(toneMapped.z));
+        pushPostprocessRecord(out, P, params, raw);
     }
     writeRaw("postprocess_kat.bin", out.data(), out.size() * 4);
+}
+
+// The same records at the edges of the float range ("postprocess_edges_kat.bin", the layout of postprocess_kat.bin): channel values from
+// kPostSpecials, parameters from the corners of their ranges.
+//   records [0, 2016)     56 pixel patterns x 4 tone mappers x 9 parameter picks: pattern p < 14 = special p in all three channels,
+//                         pattern 14 + 3 s + k = special s in channel k among two ordinary values; colorFilter = 1
+//   records [2016, 4096)  a seeded mix: each channel a special with probability 1/2, random colorFilter, parameters drawn from the same sets
+// Saturation {0, 1, 1.5}, contrast {0.4, 1, 1.6}, exposure {-30, 0, 30}, numPasses {1, 300}.
+static const uint32_t kPostSpecials[14] = {
+    0x00000000u /* +0 */, 0x80000000u /* -0 */, 0x00000001u /* smallest denormal */, 0x00800000u /* FLT_MIN */, 0x1E3CE508u /* 1e-20 */,
+    0x3F800000u /* 1 */, 0x477FE000u /* 65504 */, 0x60AD78ECu /* 1e20 */, 0x7F7FFFFFu /* FLT_MAX */, 0x7F800000u /* +inf */,
+    0xFF800000u /* -inf */, 0x7FC00000u /* NaN */, 0xBF800000u /* -1 */, 0xE0AD78ECu /* -1e20 */ };
+// Inputs of the two operators that go through Vector4::FastReciprocal (_mm_rcp_ps, a vendor-specific 12-bit seed, refined by one Newton step)
+// on which that seed decides the 8-bit result, so that no restatement with an exact 1 / v can be held to it (tests/golden/README.md):
+//   Hejl-Burgess-Dawson, a finite channel c >= 2^16: the operator tends to 1 - 0.19 / c and is not saturated, so 255 * v sits within the refined
+//     reciprocal's error of the step from 254 to 255;
+//   ACES, a finite denominator |t2| >= 2^63 (c >= 1.9e9; Hejl-Burgess-Dawson's lies inside its class above): rcp * rcp of the Newton step is
+//     denormal and loses the bits that correct the seed; beyond 2^126 the seed itself underflows to 0 and the reference's result is 0.
+static bool approximateReciprocalDecides(const Vector4& color, uint32_t tonemapper)
+{
+    const Vector4 t1 = Vector4::MulAndAdd(color, Vector4(2.43f), Vector4(0.59f));      // ToneMap, ColorHelpers.h:113-123
+    const Vector4 t2 = Vector4::MulAndAdd(color, t1, Vector4(0.14f));
+    for (int k = 0; k < 3; ++k)
+    {
+        const float c = color[k], d = fabsf(t2[k]);
+        if (tonemapper == 2u && c >= 65536.0f && c <= FLT_MAX) return true;
+        if (tonemapper == 3u && d >= 9223372036854775808.0f && d <= FLT_MAX) return true;
+    }
+    return false;
+}
+static void genPostprocessEdges()
+{
+    Lcg g(111);
+    std::vector<uint32_t> out;
+    uint32_t numMoved = 0;
+    const uint32_t numStructured = 56u * 4u * 9u, N = 4096;
+    static const float saturations[3] = { 0.0f, 1.0f, 1.5f }, contrasts[3] = { 0.4f, 1.0f, 1.6f }, exposures[3] = { -30.0f, 0.0f, 30.0f };
+    static const uint32_t passes[2] = { 1u, 300u };
+    out.push_back(N);
+    for (uint32_t i = 0; i < N; ++i)
+    {
+        RtPostprocessParams P; memset(&P, 0, sizeof(P));
+        PostprocessParams params;
+        uint32_t combo, tonemapper;
+        float raw[3];
+        if (i < numStructured)
+        {
+            const uint32_t pattern = i / 36u, pick = i % 9u;
+            tonemapper = (i / 9u) % 4u;
+            combo = (pattern * 9u + pick) % 54u;
+            params.colorFilter = Vector4(1.0f, 1.0f, 1.0f, 1.0f);
+            const uint32_t numPasses = passes[(combo / 27u) % 2u];
+            for (uint32_t k = 0; k < 3; ++k)
+            {
+                const float ordinary = g.range(0.0f, 2.0f) * numPasses;
+                if (pattern < 14u) raw[k] = bitsf(kPostSpecials[pattern]);
+                else raw[k] = ((pattern - 14u) % 3u == k) ? bitsf(kPostSpecials[(pattern - 14u) / 3u]) : ordinary;
+            }
+        }
+        else
+        {
+            tonemapper = i % 4u;
+            combo = g.u32() % 54u;
+            params.colorFilter = Vector4(g.range(0.2f, 1.5f), g.range(0.2f, 1.5f), g.range(0.2f, 1.5f), 1.0f);
+            const uint32_t numPasses = passes[(combo / 27u) % 2u];
+            for (uint32_t k = 0; k < 3; ++k)
+            {
+                const uint32_t pickSpecial = g.u32() % 28u;
+                const float ordinary = g.range(0.0f, 2.0f) * numPasses;
+                raw[k] = pickSpecial < 14u ? bitsf(kPostSpecials[pickSpecial]) : ordinary;
+            }
+        }
+        params.saturation = saturations[combo % 3u]; params.contrast = contrasts[(combo / 3u) % 3u]; params.exposure = exposures[(combo / 9u) % 3u];
+        params.tonemapper = (Tonemapper)tonemapper;
+        memcpy(P.colorFilter, &params.colorFilter, 16);
+        P.exposure = params.exposure; P.contrast = params.contrast; P.saturation = params.saturation;
+        P.ditheringStrength = 0.0f; P.bloomFactor = 0.0f; P.tonemapper = tonemapper; P.numPasses = passes[(combo / 27u) % 2u];
+        if (tonemapper >= 2u && approximateReciprocalDecides(postprocessBeforeToneMap(P, params, Float3(raw[0], raw[1], raw[2])), tonemapper))
+        {
+            // not dropped: the same pixel and parameters under the exact operator two below (Clamped for Hejl-Burgess-Dawson, Reinhard for ACES)
+            tonemapper -= 2u; numMoved++;
+            params.tonemapper = (Tonemapper)tonemapper; P.tonemapper = tonemapper;
+        }
+        pushPostprocessRecord(out, P, params, Float3(raw[0], raw[1], raw[2]));
+    }
+    printf("postprocess_edges_kat.bin: %u records moved from an approximate operator to an exact one\n", numMoved);
+    writeRaw("postprocess_edges_kat.bin", out.data(), out.size() * 4);
 }
 
 // =====================================================================================================
@@ -1395,6 +1491,46 @@ static void genBloom()
     writeRaw("bloom_kat.bin", out.data(), out.size() * 4);
 }
 
+// The blur at the edges of what it admits and on input that is not finite ("bloom_edges_kat.bin").  bloom_kat.bin's layout with two changes
+// that NaN asks for: the 64-bit sum is taken over the words that are not NaN, and a u32 count of the NaN words follows it.
+//   { magic 'BLOE', count } then per case { width, height, numLevels, lattice step, sigma0 bits, edit } followed, per level, by
+//   { sum lo, sum hi, NaN words } and the pixels of the lattice.  edit: 0 = bloomInput as it is; 1 / 2 = the float at index
+//   kBloomEditIndex set to +inf / NaN; 3 = the float at kBloomEdgeIndex set to FLT_MAX; 4 = every float negated.
+static const uint32_t kBloomEditIndex = 3u * (17u * 64u + 20u) + 1u;   // pixel (20, 17), green, of the 64 x 48 image
+static const uint32_t kBloomEdgeIndex = 3u * (17u * 64u + 0u) + 1u;    // pixel (0, 17), green: a line's first value enters its running sum radius + 1 times, so FLT_MAX there overflows it
+static void genBloomEdges()
+{
+    std::vector<uint32_t> out;
+    struct Case { uint32_t w, h, levels, step; float sigma0; uint32_t edit; };
+    const Case cases[] = { { 8, 8, 1, 1, 1.3f, 0 }, { 8, 300, 1, 1, 1.3f, 0 }, { 300, 8, 1, 1, 1.3f, 0 }, { 196, 196, 5, 4, 2.0f, 0 },
+                           { 64, 48, 1, 1, 2.0f, 1 }, { 64, 48, 1, 1, 2.0f, 2 }, { 64, 48, 1, 1, 2.0f, 3 }, { 64, 48, 1, 1, 2.0f, 4 } };
+    out.push_back(0x454F4C42u); out.push_back((uint32_t)(sizeof(cases) / sizeof(cases[0])));
+    for (const Case& c : cases)
+    {
+        Bitmap img("bloom");
+        Bitmap::InitData id; id.width = c.w; id.height = c.h; id.format = Bitmap::Format::R32G32B32_Float;
+        if (!img.Init(id)) { fprintf(stderr, "Bitmap::Init failed\n"); exit(1); }
+        float* data = reinterpret_cast<float*>(img.GetData());
+        for (uint32_t i = 0; i < c.w * c.h * 3; ++i) data[i] = c.edit == 4u ? -bloomInput(i) : bloomInput(i);
+        if (c.edit == 1u || c.edit == 2u) data[kBloomEditIndex] = bitsf(c.edit == 1u ? 0x7F800000u : 0x7FC00000u);
+        if (c.edit == 3u) data[kBloomEdgeIndex] = FLT_MAX;
+        out.push_back(c.w); out.push_back(c.h); out.push_back(c.levels); out.push_back(c.step); out.push_back(fbits(c.sigma0)); out.push_back(c.edit);
+        float blurSigma = c.sigma0;
+        for (uint32_t level = 0; level < c.levels; ++level)
+        {
+            if (!img.GaussianBlur(blurSigma, 8)) { fprintf(stderr, "GaussianBlur failed\n"); exit(1); }
+            blurSigma *= 2.5f;
+            uint64_t sum = 0; uint32_t nans = 0;
+            for (uint32_t i = 0; i < c.w * c.h * 3; ++i) { if (data[i] != data[i]) nans++; else sum += fbits(data[i]); }
+            out.push_back((uint32_t)sum); out.push_back((uint32_t)(sum >> 32)); out.push_back(nans);
+            for (uint32_t y = 0; y < c.h; y += c.step)
+                for (uint32_t x = 0; x < c.w; x += c.step)
+                    for (int k = 0; k < 3; ++k) out.push_back(fbits(data[3 * (y * c.w + x) + k]));
+        }
+    }
+    writeRaw("bloom_edges_kat.bin", out.data(), out.size() * 4);
+}
+
 // HSVtoRGB (Core/Color/ColorHelpers.h:133-156) as DebugRenderer's TriangleID mode drives it (DebugRenderer.cpp:98-106):
 // in = { objectId, subObjectId } -> hash -> hue, saturation -> rgb
 static void genDebug()
@@ -1501,10 +1637,12 @@ int main(int argc, char** argv)
     genTextures();
     genObjMesh();
     genPostprocess();
+    genPostprocessEdges();
     genBidirLights();
     genBidirBsdf();
     genBidirCameraFilm();
     genBloom();
+    genBloomEdges();
     genDebug();
     genDds();
     genBmp();

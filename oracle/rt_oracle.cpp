@@ -510,6 +510,19 @@ void rto_postprocess(const float* sumRGB, uint32_t width, uint32_t height, const
         }
 }
 
+// the per-pixel body alone over n records, each with its own params, at pixel (0, 0): the 8-bit word and (outToneMapped != NULL) the three
+// floats Vector4::ToBGR quantises -- what postprocess_kat.bin / postprocess_edges_kat.bin carry
+void rto_postprocess_records(const RtPostprocessParams* params, const float* rgb, uint32_t n, uint32_t* outBGR, float* outToneMapped)
+{
+    for (uint32_t i = 0; i < n; ++i)
+    {
+        const RtPostprocessParams& p = params[i];
+        const float exposureScale = powf(2.0f, p.exposure);
+        const float colorScale[3] = { p.colorFilter[0] * exposureScale, p.colorFilter[1] * exposureScale, p.colorFilter[2] * exposureScale };
+        outBGR[i] = postProcessPixel(rgb[3 * (size_t)i], rgb[3 * (size_t)i + 1], rgb[3 * (size_t)i + 2], 0, 0, p, colorScale, outToneMapped ? outToneMapped + 3 * (size_t)i : nullptr);
+    }
+}
+
 // ---- bloom -------------------------------------------------------------------------------------------------------
 // BoxBlur_Internal, Core/Utils/Bitmap.cpp:880-914 (one colour channel; the reference runs the four lanes of a Vector4 in lockstep)
 static void boxBlurInternal(float* targetLine, const float* srcLine, const uint32_t radius, const uint32_t width)
@@ -518,11 +531,12 @@ static void boxBlurInternal(float* targetLine, const float* srcLine, const uint3
     const float* srcLineBegin = srcLine; const float* srcLineEnd = srcLine;
     const float firstValue = srcLine[0];
     const float lastValue = srcLine[width - 1];
-    float val = firstValue * (float)(radius + 1);
-    for (uint32_t j = 0; j < radius; j++) val = val + *(srcLineBegin++);
-    for (uint32_t j = 0; j <= radius; j++) { val = val + (*(srcLineBegin++) - firstValue); *(targetLine++) = val * factor; }
-    for (uint32_t j = radius + 1; j < width - radius; j++) { val = val + (*(srcLineBegin++) - *(srcLineEnd++)); *(targetLine++) = val * factor; }
-    for (uint32_t j = width - radius; j < width; j++) { val = val + (lastValue - *(srcLineEnd++)); *(targetLine++) = val * factor; }
+    // (the sse* forms: inf - inf in the running sum is SSE's NaN, sign included -- the tone mapper's FastLog reads a NaN's bits, rto_math.h)
+    float val = sseMul(firstValue, (float)(radius + 1));
+    for (uint32_t j = 0; j < radius; j++) val = sseAdd(val, *(srcLineBegin++));
+    for (uint32_t j = 0; j <= radius; j++) { val = sseAdd(val, sseSub(*(srcLineBegin++), firstValue)); *(targetLine++) = sseMul(val, factor); }
+    for (uint32_t j = radius + 1; j < width - radius; j++) { val = sseAdd(val, sseSub(*(srcLineBegin++), *(srcLineEnd++))); *(targetLine++) = sseMul(val, factor); }
+    for (uint32_t j = width - radius; j < width; j++) { val = sseAdd(val, sseSub(lastValue, *(srcLineEnd++))); *(targetLine++) = sseMul(val, factor); }
 }
 // Bitmap::GaussianBlur, :917-1020, on a tight float3 image.  Lines are processed per channel; the line buffers are as long as the
 // reference's (4096) so that a window wider than the line reads the same kind of stale entries -- callers keep to sizes where it does not.
@@ -594,10 +608,10 @@ int rto_postprocess_bloom(const float* sumRGB, uint32_t width, uint32_t height, 
             float rgb[3];
             for (int k = 0; k < 3; ++k)
             {
-                const float v = sumRGB[3 * i + k] * (1.0f - params->bloomFactor);
+                const float v = sseMul(sumRGB[3 * i + k], 1.0f - params->bloomFactor);
                 float bloomColor = 0.0f;
-                for (int l = 0; l < 5; ++l) bloomColor = fmaf(blurred[l][3 * i + k], bloomWeights[l], bloomColor);
-                rgb[k] = fmaf(bloomColor, params->bloomFactor, v);
+                for (int l = 0; l < 5; ++l) bloomColor = sseMulAdd(blurred[l][3 * i + k], bloomWeights[l], bloomColor);
+                rgb[k] = sseMulAdd(bloomColor, params->bloomFactor, v);
             }
             out[i] = postProcessPixel(rgb[0], rgb[1], rgb[2], x, y, *params, colorScale);
         }

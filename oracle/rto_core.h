@@ -1933,23 +1933,36 @@ static inline float ditherNoise(uint32_t x, uint32_t y, uint32_t channel, uint32
     float f; memcpy(&f, &bits, 4);
     return f - 3.0f;
 }
-// one pixel: r, g, b = sum-buffer value; returns 0x00RRGGBB (Vector4::ToBGR, Vector4ImplSSE.h:89-110)
-static inline uint32_t postProcessPixel(float r, float g, float b, uint32_t x, uint32_t y, const RtPostprocessParams& p, const float colorScale[3])
+// one channel up to the float Vector4::ToBGR quantises: c = the pixel's channel times 1 / numPasses, grayscale = the pixel's luminance
+static inline float postProcessChannel(float c, float grayscale, int k, uint32_t x, uint32_t y, const RtPostprocessParams& p, const float colorScale[3])
+{
+    // saturation: Max(0, Lerp(grayscale, rgb, saturation)), Lerp = MulAndAdd(v2 - v1, w, v1)
+    // (the sse* forms: a NaN keeps the bits SSE gives it, which FastLog below reads as a number)
+    float v = sseMax(0.0f, sseMulAdd(sseSub(c, grayscale), p.saturation, grayscale));
+    v = fastExpVec(fastLogVec(v) * p.contrast);                       // contrast
+    v = v * colorScale[k];                                            // exposure: colorScale = colorFilter * powf(2, exposure), computed on the host (Viewport.cpp:453)
+    v = toneMap(v, p.tonemapper);
+    if (p.ditheringStrength != 0.0f) v = fmaf(ditherNoise(x, y, (uint32_t)k, p.ditherSeed), p.ditheringStrength, v);
+    return v;
+}
+// _mm_cvttps_epi32: truncation; NaN and everything outside [-2^31, 2^31) give INT_MIN (the "integer indefinite"), so an overflowing
+// channel comes out black like a NaN one (postprocess_edges_kat.bin).  A plain cast is undefined in C++ for those inputs.
+static inline int32_t cvttToInt(float v)
+{
+    return (v >= -2147483648.0f && v < 2147483648.0f) ? (int32_t)v : (int32_t)0x80000000;
+}
+// one pixel: r, g, b = sum-buffer value; returns 0x00RRGGBB (Vector4::ToBGR, Vector4ImplSSE.h:89-110).  toneMapped (may be null): the three floats before ToBGR
+static inline uint32_t postProcessPixel(float r, float g, float b, uint32_t x, uint32_t y, const RtPostprocessParams& p, const float colorScale[3], float* toneMapped = nullptr)
 {
     const float pixelScaling = 1.0f / (float)p.numPasses;
-    float c[3] = { r * pixelScaling, g * pixelScaling, b * pixelScaling };
-    // saturation: Max(0, Lerp(grayscale, rgb, saturation)), Lerp = MulAndAdd(v2 - v1, w, v1)
-    const float grayscale = (c[0] * 0.2126f + c[1] * 0.7152f) + (c[2] * 0.0722f + 0.0f);
+    float c[3] = { sseMul(r, pixelScaling), sseMul(g, pixelScaling), sseMul(b, pixelScaling) };
+    const float grayscale = sseAdd(sseAdd(sseMul(c[0], 0.2126f), sseMul(c[1], 0.7152f)), sseAdd(sseMul(c[2], 0.0722f), 0.0f));   // Dot3: (x + y) + (z + 0)
     uint32_t out = 0;
     for (int k = 0; k < 3; ++k)
     {
-        float v = sseMax(0.0f, fmaf(c[k] - grayscale, p.saturation, grayscale));
-        v = fastExpVec(fastLogVec(v) * p.contrast);                       // contrast
-        v = v * colorScale[k];                                            // exposure: colorScale = colorFilter * powf(2, exposure), computed on the host (Viewport.cpp:453)
-        v = toneMap(v, p.tonemapper);
-        if (p.ditheringStrength != 0.0f) v = fmaf(ditherNoise(x, y, (uint32_t)k, p.ditherSeed), p.ditheringStrength, v);
-        const float scaled = v * 255.0f;
-        int32_t q = (scaled != scaled) ? (int32_t)0x80000000 : (int32_t)scaled;   // cvttps2dq (NaN -> INT_MIN); values here are far from overflow
+        const float v = postProcessChannel(c[k], grayscale, k, x, y, p, colorScale);
+        if (toneMapped) toneMapped[k] = v;
+        int32_t q = cvttToInt(v * 255.0f);
         q = q < 0 ? 0 : (q > 255 ? 255 : q);
         out |= (uint32_t)q << (16 - 8 * k);                              // r << 16 | g << 8 | b
     }

@@ -73,6 +73,22 @@ static inline float sseMin(float a, float b) { return a < b ? a : b; }
 static inline float sseMax(float a, float b) { return a > b ? a : b; }
 static inline V4 min4(V4 a, V4 b) { return V4(sseMin(a.x, b.x), sseMin(a.y, b.y), sseMin(a.z, b.z), sseMin(a.w, b.w)); }
 static inline V4 max4(V4 a, V4 b) { return V4(sseMax(a.x, b.x), sseMax(a.y, b.y), sseMax(a.z, b.z), sseMax(a.w, b.w)); }
+// SSE's NaN results, for the places where a NaN's BITS are read afterwards (post-processing: FastLog takes a NaN's sign and payload for a number, so
+// the sign decides between a white and a black pixel).  An operand that is NaN comes back quieted with its sign, the first one if several are; an
+// invalid operation on numbers (inf - inf, 0 * inf) gives the "real indefinite" 0xFFC00000.  Stated in integer logic so that neither the host's
+// floating-point unit nor the compiler's choice of operand order decides.  Results that are not NaN pass through untouched.
+static inline float sseNan(float result, float a, float b, float c)
+{
+    if (result == result) return result;
+    const float first = (a != a) ? a : ((b != b) ? b : c);
+    uint32_t bits = 0xFFC00000u;
+    if (first != first) { memcpy(&bits, &first, 4); bits |= 0x00400000u; }
+    float r; memcpy(&r, &bits, 4); return r;
+}
+static inline float sseAdd(float a, float b) { return sseNan(a + b, a, b, 0.0f); }
+static inline float sseSub(float a, float b) { return sseNan(a - b, a, b, 0.0f); }
+static inline float sseMul(float a, float b) { return sseNan(a * b, a, b, 0.0f); }
+static inline float sseMulAdd(float a, float b, float c) { return sseNan(fmaf(a, b, c), a, b, c); }
 static inline float absf(float v) { uint32_t u; memcpy(&u, &v, 4); u &= 0x7fffffffu; memcpy(&v, &u, 4); return v; }
 static inline V4 abs4(V4 a) { return V4(absf(a.x), absf(a.y), absf(a.z), absf(a.w)); }     // Vector4ImplSSE.h:398-401
 

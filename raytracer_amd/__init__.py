@@ -58,6 +58,9 @@ def rtgpu_lib():
         _rtgpu.rtgpu_get_ray_source.argtypes, _rtgpu.rtgpu_get_ray_source.restype = [C.c_void_p, C.POINTER(C.c_uint64)], C.c_int
         _rtgpu.rtgpu_read_camera_rays.argtypes, _rtgpu.rtgpu_read_camera_rays.restype = [C.c_void_p, C.c_void_p, C.c_void_p], C.c_int
         _rtgpu.rtgpu_read_camera_rays_async.argtypes, _rtgpu.rtgpu_read_camera_rays_async.restype = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p], C.c_int
+        # known-answer hooks of post-processing: (ctx, params[n], rgb[n * 3], n, outBGR[n], outToneMapped[n * 3] or NULL), (ctx, rgb in place, width, height, sigma)
+        _rtgpu.rtgpu_kat_postprocess.argtypes, _rtgpu.rtgpu_kat_postprocess.restype = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p], C.c_int
+        _rtgpu.rtgpu_kat_blur.argtypes, _rtgpu.rtgpu_kat_blur.restype = [C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32, C.c_float], C.c_int
     return _rtgpu
 
 

@@ -62,6 +62,20 @@ RT_DEV float sseMin(float a, float b) { return a < b ? a : b; }
 RT_DEV float sseMax(float a, float b) { return a > b ? a : b; }
 RT_DEV V4 min4(V4 a, V4 b) { return V4(sseMin(a.x, b.x), sseMin(a.y, b.y), sseMin(a.z, b.z), sseMin(a.w, b.w)); }
 RT_DEV V4 max4(V4 a, V4 b) { return V4(sseMax(a.x, b.x), sseMax(a.y, b.y), sseMax(a.z, b.z), sseMax(a.w, b.w)); }
+// SSE's NaN results, for the places where a NaN's BITS are read afterwards (post-processing: FastLog takes a NaN's sign and payload for a number, so
+// the sign decides between a white and a black pixel).  An operand that is NaN comes back quieted with its sign, the first one if several are; an
+// invalid operation on numbers (inf - inf, 0 * inf) gives the "real indefinite" 0xFFC00000.  The GPU's own results differ in both: its default NaN
+// is 0x7FC00000, and a source negation (a - b is a + -b) reaches a NaN operand's sign.  Results that are not NaN pass through untouched.
+RT_DEV float sseNan(float result, float a, float b, float c)
+{
+    if (result == result) return result;
+    const float first = (a != a) ? a : ((b != b) ? b : c);
+    return (first != first) ? __uint_as_float(__float_as_uint(first) | 0x00400000u) : __uint_as_float(0xFFC00000u);
+}
+RT_DEV float sseAdd(float a, float b) { return sseNan(a + b, a, b, 0.0f); }
+RT_DEV float sseSub(float a, float b) { return sseNan(a - b, a, b, 0.0f); }
+RT_DEV float sseMul(float a, float b) { return sseNan(a * b, a, b, 0.0f); }
+RT_DEV float sseMulAdd(float a, float b, float c) { return sseNan(__fmaf_rn(a, b, c), a, b, c); }
 RT_DEV float absf(float v) { return __uint_as_float(__float_as_uint(v) & 0x7fffffffu); }
 RT_DEV V4 abs4(V4 a) { return V4(absf(a.x), absf(a.y), absf(a.z), absf(a.w)); }     // Vector4ImplSSE.h:398-401
 

@@ -9,6 +9,17 @@ __global__ void __launch_bounds__(RT_BLOCK) k_postprocess(const float* __restric
     front[i] = postProcessPixel(sum[3 * (size_t)i + 0], sum[3 * (size_t)i + 1], sum[3 * (size_t)i + 2], x, y, params, colorScale.c);
 }
 
+// rtgpu_kat_postprocess: postProcessPixel on n records, each with its own parameters, at pixel (0, 0); toneMapped = the floats ToBGR quantises
+__global__ void __launch_bounds__(64) k_kat_postprocess(const RtPostprocessParams* __restrict__ params, const PostScale* __restrict__ colorScales, const float* __restrict__ rgb,
+                                                        uint32_t n, uint32_t* __restrict__ outBGR, float* __restrict__ outToneMapped)
+{
+    const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    float toneMapped[3];
+    outBGR[i] = postProcessPixel(rgb[3 * (size_t)i + 0], rgb[3 * (size_t)i + 1], rgb[3 * (size_t)i + 2], 0u, 0u, params[i], colorScales[i].c, toneMapped);
+    for (int k = 0; k < 3; ++k) outToneMapped[3 * (size_t)i + k] = toneMapped[k];
+}
+
 // ---- bloom: Bitmap::GaussianBlur (Core/Utils/Bitmap.cpp:880-1020) ---------------------------------------------------------
 // n box blurs per line, each a running sum in the reference's order (BoxBlur_Internal, :880-914), so a line is sequential;
 // one thread per (line, colour channel).  The two line buffers live in global scratch, element-major (element e of
@@ -18,11 +29,12 @@ RT_DEV void boxBlurLine(float* __restrict__ dst, const float* __restrict__ src, 
     const float factor = 1.0f / (float)(2u * radius + 1u);
     uint32_t b = 0, e = 0, t = 0;
     const float firstValue = src[0], lastValue = src[(size_t)(width - 1u) * stride];
-    float val = firstValue * (float)(radius + 1u);
-    for (uint32_t j = 0; j < radius; j++) val = val + src[(size_t)(b++) * stride];
-    for (uint32_t j = 0; j <= radius; j++) { val = val + (src[(size_t)(b++) * stride] - firstValue); dst[(size_t)(t++) * stride] = val * factor; }
-    for (uint32_t j = radius + 1u; j < width - radius; j++) { val = val + (src[(size_t)(b++) * stride] - src[(size_t)(e++) * stride]); dst[(size_t)(t++) * stride] = val * factor; }
-    for (uint32_t j = width - radius; j < width; j++) { val = val + (lastValue - src[(size_t)(e++) * stride]); dst[(size_t)(t++) * stride] = val * factor; }
+    // (the sse* forms: inf - inf in the running sum is SSE's NaN, sign included -- the tone mapper's FastLog reads a NaN's bits, rt_device_math.h)
+    float val = sseMul(firstValue, (float)(radius + 1u));
+    for (uint32_t j = 0; j < radius; j++) val = sseAdd(val, src[(size_t)(b++) * stride]);
+    for (uint32_t j = 0; j <= radius; j++) { val = sseAdd(val, sseSub(src[(size_t)(b++) * stride], firstValue)); dst[(size_t)(t++) * stride] = sseMul(val, factor); }
+    for (uint32_t j = radius + 1u; j < width - radius; j++) { val = sseAdd(val, sseSub(src[(size_t)(b++) * stride], src[(size_t)(e++) * stride])); dst[(size_t)(t++) * stride] = sseMul(val, factor); }
+    for (uint32_t j = width - radius; j < width; j++) { val = sseAdd(val, sseSub(lastValue, src[(size_t)(e++) * stride])); dst[(size_t)(t++) * stride] = sseMul(val, factor); }
 }
 __global__ void __launch_bounds__(RT_BLOCK) k_blur_lines(float* __restrict__ image, uint32_t width, uint32_t height, uint32_t vertical, const BlurPlan plan,
                                                          float* __restrict__ lineA, float* __restrict__ lineB)
@@ -61,10 +73,10 @@ __global__ void __launch_bounds__(RT_BLOCK) k_postprocess_bloom(const float* __r
     float rgb[3];
     for (int k = 0; k < 3; ++k)
     {
-        float v = sum[3 * (size_t)i + k] * (1.0f - params.bloomFactor);
+        float v = sseMul(sum[3 * (size_t)i + k], 1.0f - params.bloomFactor);
         float bloomColor = 0.0f;
-        for (int l = 0; l < 5; ++l) bloomColor = __fmaf_rn(blurred.level[l][3 * (size_t)i + k], bloomWeights[l], bloomColor);
-        rgb[k] = __fmaf_rn(bloomColor, params.bloomFactor, v);
+        for (int l = 0; l < 5; ++l) bloomColor = sseMulAdd(blurred.level[l][3 * (size_t)i + k], bloomWeights[l], bloomColor);
+        rgb[k] = sseMulAdd(bloomColor, params.bloomFactor, v);
     }
     front[i] = postProcessPixel(rgb[0], rgb[1], rgb[2], x, y, params, colorScale.c);
 }

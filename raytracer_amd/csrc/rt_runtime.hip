@@ -644,29 +644,49 @@ RTGPU_API int rtgpu_set_active_blocks(RtgpuContext* c, uint32_t numBlocks, const
     return rebuildSlots(c);
 }
 
+// colorScale = colorFilter * 2^exposure on the host like the reference (Viewport.cpp:453)
+static PostScale postScale(const RtPostprocessParams* p)
+{
+    const float exposureScale = powf(2.0f, p->exposure);
+    return { { p->colorFilter[0] * exposureScale, p->colorFilter[1] * exposureScale, p->colorFilter[2] * exposureScale } };
+}
+
+// Bitmap::GaussianBlur(sigma, 8) on a width x height image: its window plan (Bitmap.cpp:935-946), or the refusal.  The reference's blur works on
+// 4 columns at a time and on 4096-entry line buffers without bounds checks (Bitmap.cpp:925-931, :941, :978-990): sizes it would read or write
+// out of bounds for are refused here
+static int blurPlanFor(float sigma, uint32_t width, uint32_t height, BlurPlan* plan)
+{
+    if (width > 4096u || height > 4096u || (width % 4u) != 0u) return fail(RTGPU_ERR_UNSUPPORTED, "bloom: width must be a multiple of 4 and both sizes <= 4096 (Bitmap::GaussianBlur)");
+    const uint32_t n = 8u;
+    float wIdeal = sqrtf((12.0f * sigma * sigma / n) + 1.0f);
+    uint32_t wl = (uint32_t)floorf(wIdeal);
+    if (wl % 2u == 0u) wl--;
+    const uint32_t wu = wl + 2u;
+    const float mIdeal = (12.0f * sigma * sigma - n * wl * wl - 4.0f * n * wl - 3.0f * n) / (-4.0f * wl - 4.0f);
+    plan->n = n; plan->wl = wl; plan->wu = wu; plan->m = roundf(mIdeal);
+    if (width <= 2u * wu + 1u || height <= 2u * wu + 1u) return fail(RTGPU_ERR_UNSUPPORTED, "bloom: the image is not larger than the blur window (2 * wu + 1 pixels; 195 for the widest of a frame's five levels)");
+    return RTGPU_OK;
+}
+// the blur itself, in place on a device image: rows, then columns.  lines: 2 * width * height * 3 floats of scratch
+static void blurImage(hipStream_t stream, float* img, uint32_t width, uint32_t height, const BlurPlan& plan, float* lines)
+{
+    const size_t pixels = (size_t)width * height;
+    hipLaunchKernelGGL(k_blur_lines, dim3((height * 3u + RT_BLOCK - 1) / RT_BLOCK), dim3(RT_BLOCK), 0, stream, img, width, height, 0u, plan, lines, lines + pixels * 3);
+    hipLaunchKernelGGL(k_blur_lines, dim3((width * 3u + RT_BLOCK - 1) / RT_BLOCK), dim3(RT_BLOCK), 0, stream, img, width, height, 1u, plan, lines, lines + pixels * 3);
+}
+
 // rtgpu_postprocess (rgbHost == nullptr: the sum buffer) and rtgpu_postprocess_from (a caller's image of the context's size, rt_runtime_denoise.inl)
 static int postprocessImage(RtgpuContext* c, const RtPostprocessParams* p, const float* rgbHost, uint32_t* frontBufferBGRA)
 {
     if (!c->sum) return fail(RTGPU_ERR_NOT_READY, "rtgpu_resize has not been called");
-    // bloom: the reference's blur works on 4 columns at a time and on 4096-entry line buffers without bounds checks
-    // (Bitmap.cpp:925-931, :941, :978-990): sizes it would read or write out of bounds for are refused here
     const bool bloom = p->bloomFactor > 0.0f;
     BlurPlan plans[5];
     if (bloom)
     {
-        if (c->width > 4096u || c->height > 4096u || (c->width % 4u) != 0u) return fail(RTGPU_ERR_UNSUPPORTED, "bloom: width must be a multiple of 4 and both sizes <= 4096 (Bitmap::GaussianBlur)");
         float blurSigma = 2.0f;   // Viewport.cpp:438-444
         for (int l = 0; l < 5; ++l)
         {
-            const uint32_t n = 8u;
-            const float sigma = blurSigma;
-            float wIdeal = sqrtf((12.0f * sigma * sigma / n) + 1.0f);   // Bitmap.cpp:935-946
-            uint32_t wl = (uint32_t)floorf(wIdeal);
-            if (wl % 2u == 0u) wl--;
-            const uint32_t wu = wl + 2u;
-            const float mIdeal = (12.0f * sigma * sigma - n * wl * wl - 4.0f * n * wl - 3.0f * n) / (-4.0f * wl - 4.0f);
-            plans[l].n = n; plans[l].wl = wl; plans[l].wu = wu; plans[l].m = roundf(mIdeal);
-            if (c->width <= 2u * wu + 1u || c->height <= 2u * wu + 1u) return fail(RTGPU_ERR_UNSUPPORTED, "bloom: the image is smaller than the widest blur window (2 * 97 + 1 pixels)");
+            const int pr = blurPlanFor(blurSigma, c->width, c->height, &plans[l]); if (pr) return pr;
             blurSigma *= 2.5f;
         }
     }
@@ -685,8 +705,7 @@ static int postprocessImage(RtgpuContext* c, const RtPostprocessParams* p, const
     }
     const float* image = rgbHost ? dImage : c->sum;
     { const hipError_t fe = hipMalloc((void**)&dFront, pixels * sizeof(uint32_t)); if (fe != hipSuccess) { devFree(dImage); HIP_TRY(fe); } }
-    const float exposureScale = powf(2.0f, p->exposure);   // colorScale on the host like the reference (Viewport.cpp:453)
-    const PostScale scale = { { p->colorFilter[0] * exposureScale, p->colorFilter[1] * exposureScale, p->colorFilter[2] * exposureScale } };
+    const PostScale scale = postScale(p);
     hipStream_t stream = c->lanes[0].stream;
     hipError_t e = hipSuccess;
     float* dBlur = nullptr; float* dLines = nullptr;
@@ -703,8 +722,7 @@ static int postprocessImage(RtgpuContext* c, const RtPostprocessParams* p, const
             levels.level[l] = img;
             e = hipMemcpyAsync(img, l == 0 ? image : dBlur + (size_t)(l - 1) * pixels * 3, pixels * 3 * sizeof(float), hipMemcpyDeviceToDevice, stream);
             if (e != hipSuccess) break;
-            hipLaunchKernelGGL(k_blur_lines, dim3((c->height * 3u + RT_BLOCK - 1) / RT_BLOCK), dim3(RT_BLOCK), 0, stream, img, c->width, c->height, 0u, plans[l], dLines, dLines + pixels * 3);
-            hipLaunchKernelGGL(k_blur_lines, dim3((c->width * 3u + RT_BLOCK - 1) / RT_BLOCK), dim3(RT_BLOCK), 0, stream, img, c->width, c->height, 1u, plans[l], dLines, dLines + pixels * 3);
+            blurImage(stream, img, c->width, c->height, plans[l], dLines);
         }
         if (e == hipSuccess) hipLaunchKernelGGL(k_postprocess_bloom, dim3((uint32_t)((pixels + RT_BLOCK - 1) / RT_BLOCK)), dim3(RT_BLOCK), 0, stream, image, levels, dFront, c->width, c->height, *p, scale);
     }

@@ -85,6 +85,64 @@ RTGPU_API int rtgpu_kat_mesh(RtgpuContext* c, const float* rays, uint32_t n, uin
     });
 }
 
+RTGPU_API int rtgpu_kat_postprocess(RtgpuContext* c, const RtPostprocessParams* params, const float* rgb, uint32_t n, uint32_t* outBGR, float* outToneMapped)
+{
+    if (!c || (n && (!params || !rgb || !outBGR))) return fail(RTGPU_ERR_INVALID_ARGUMENT, "NULL argument");
+    if (n == 0) return RTGPU_OK;
+    std::vector<PostScale> scales(n);
+    for (uint32_t i = 0; i < n; ++i)
+    {
+        if (params[i].tonemapper > RT_TONEMAPPER_ACES) return fail(RTGPU_ERR_INVALID_ARGUMENT, "unknown tonemapper");
+        if (params[i].numPasses == 0) return fail(RTGPU_ERR_INVALID_ARGUMENT, "numPasses must be > 0");
+        scales[i] = postScale(&params[i]);
+    }
+    HIP_TRY(hipSetDevice(c->device));
+    RtPostprocessParams* dParams = nullptr; PostScale* dScales = nullptr; float* dRgb = nullptr; uint32_t* dBGR = nullptr; float* dTone = nullptr;
+    hipError_t e = hipMalloc((void**)&dParams, (size_t)n * sizeof(RtPostprocessParams));
+    if (e == hipSuccess) e = hipMalloc((void**)&dScales, (size_t)n * sizeof(PostScale));
+    if (e == hipSuccess) e = hipMalloc((void**)&dRgb, (size_t)n * 3 * sizeof(float));
+    if (e == hipSuccess) e = hipMalloc((void**)&dBGR, (size_t)n * sizeof(uint32_t));
+    if (e == hipSuccess) e = hipMalloc((void**)&dTone, (size_t)n * 3 * sizeof(float));
+    if (e == hipSuccess) e = rtMemcpy(dParams, params, (size_t)n * sizeof(RtPostprocessParams), hipMemcpyHostToDevice);
+    if (e == hipSuccess) e = rtMemcpy(dScales, scales.data(), (size_t)n * sizeof(PostScale), hipMemcpyHostToDevice);
+    if (e == hipSuccess) e = rtMemcpy(dRgb, rgb, (size_t)n * 3 * sizeof(float), hipMemcpyHostToDevice);
+    if (e == hipSuccess)
+    {
+        hipLaunchKernelGGL(k_kat_postprocess, dim3((n + 63u) / 64u), dim3(64), 0, c->lanes[0].stream, dParams, dScales, dRgb, n, dBGR, dTone);
+        e = hipGetLastError();
+        if (e == hipSuccess) e = hipStreamSynchronize(c->lanes[0].stream);
+    }
+    if (e == hipSuccess) e = rtMemcpy(outBGR, dBGR, (size_t)n * sizeof(uint32_t), hipMemcpyDeviceToHost);
+    if (e == hipSuccess && outToneMapped) e = rtMemcpy(outToneMapped, dTone, (size_t)n * 3 * sizeof(float), hipMemcpyDeviceToHost);
+    devFree(dParams, dScales, dRgb, dBGR, dTone);
+    if (e != hipSuccess) return fail(RTGPU_ERR_DEVICE, std::string("rtgpu_kat_postprocess: ") + hipGetErrorString(e));
+    return RTGPU_OK;
+}
+
+RTGPU_API int rtgpu_kat_blur(RtgpuContext* c, float* rgbHost, uint32_t width, uint32_t height, float sigma)
+{
+    if (!c || !rgbHost) return fail(RTGPU_ERR_INVALID_ARGUMENT, "NULL argument");
+    if (width == 0 || height == 0 || !(sigma > 0.0f)) return fail(RTGPU_ERR_INVALID_ARGUMENT, "rtgpu_kat_blur: empty image or sigma not positive");
+    BlurPlan plan;
+    { const int pr = blurPlanFor(sigma, width, height, &plan); if (pr) return pr; }
+    HIP_TRY(hipSetDevice(c->device));
+    const size_t bytes = (size_t)width * height * 3 * sizeof(float);
+    float* dImage = nullptr; float* dLines = nullptr;
+    hipError_t e = hipMalloc((void**)&dImage, bytes);
+    if (e == hipSuccess) e = hipMalloc((void**)&dLines, bytes * 2);
+    if (e == hipSuccess) e = rtMemcpy(dImage, rgbHost, bytes, hipMemcpyHostToDevice);
+    if (e == hipSuccess)
+    {
+        blurImage(c->lanes[0].stream, dImage, width, height, plan, dLines);
+        e = hipGetLastError();
+        if (e == hipSuccess) e = hipStreamSynchronize(c->lanes[0].stream);
+    }
+    if (e == hipSuccess) e = rtMemcpy(rgbHost, dImage, bytes, hipMemcpyDeviceToHost);
+    devFree(dImage, dLines);
+    if (e != hipSuccess) return fail(RTGPU_ERR_DEVICE, std::string("rtgpu_kat_blur: ") + hipGetErrorString(e));
+    return RTGPU_OK;
+}
+
 RTGPU_API int rtgpu_evaluate_textures(RtgpuContext* c, uint32_t count, const uint32_t* textureIndex, const float* uv, float* out)
 {
     if (!c || (count && (!textureIndex || !uv || !out))) return fail(RTGPU_ERR_INVALID_ARGUMENT, "NULL argument");

@@ -104,6 +104,8 @@ __global__ void __launch_bounds__(RT_BLOCK) k_generate(const RtSceneDesc scene, 
                                                        unsigned long long* counters);
 __global__ void __launch_bounds__(RT_BLOCK) k_postprocess(const float* __restrict__ sum, uint32_t* __restrict__ front, uint32_t width, uint32_t height,
                                                           const RtPostprocessParams params, const PostScale colorScale);
+__global__ void __launch_bounds__(64) k_kat_postprocess(const RtPostprocessParams* __restrict__ params, const PostScale* __restrict__ colorScales, const float* __restrict__ rgb,
+                                                        uint32_t n, uint32_t* __restrict__ outBGR, float* __restrict__ outToneMapped);
 __global__ void __launch_bounds__(RT_BLOCK) k_blur_lines(float* __restrict__ image, uint32_t width, uint32_t height, uint32_t vertical, const BlurPlan plan,
                                                          float* __restrict__ lineA, float* __restrict__ lineB);
 __global__ void __launch_bounds__(RT_BLOCK) k_postprocess_bloom(const float* __restrict__ sum, const BloomLevels blurred, uint32_t* __restrict__ front, uint32_t width, uint32_t height,

@@ -19,6 +19,94 @@ def bit_mismatch(expected, got):
     return ~((e.view(np.uint32) == g.view(np.uint32)) | (np.isnan(e) & np.isnan(g)))
 
 
+POSTPROCESS_FILES = ("postprocess_kat.bin", "postprocess_edges_kat.bin")
+BLOOM_FILES = ("bloom_kat.bin", "bloom_edges_kat.bin")
+# the channel values postprocess_edges_kat.bin is drawn from (kat_gen.cpp kPostSpecials): +0, -0, the smallest denormal, FLT_MIN, 1e-20, 1, 65504,
+# 1e20, FLT_MAX, +inf, -inf, NaN, -1, -1e20
+POST_SPECIALS = np.array([0x00000000, 0x80000000, 0x00000001, 0x00800000, 0x1E3CE508, 0x3F800000, 0x477FE000, 0x60AD78EC, 0x7F7FFFFF, 0x7F800000,
+                          0xFF800000, 0x7FC00000, 0xBF800000, 0xE0AD78EC], dtype=np.uint32).view(np.float32)
+
+
+def load_postprocess(name):
+    """postprocess_kat.bin / postprocess_edges_kat.bin (kat_gen.cpp genPostprocess / genPostprocessEdges): a structured array of
+    { params (the bytes of an RtPostprocessParams), raw[3], bgr, toneMapped[3] }."""
+    import ctypes as C
+    import raytracer_amd as ra
+    raw = np.fromfile(os.path.join(GOLDEN, name), dtype=np.uint8)
+    n = int(raw[:4].view(np.uint32)[0])
+    rec = np.dtype([("params", np.uint8, C.sizeof(ra.RtPostprocessParams)), ("raw", np.float32, 3), ("bgr", np.uint32), ("toneMapped", np.float32, 3)])
+    assert raw.size == 4 + n * rec.itemsize, name
+    return raw[4:].view(rec)
+
+
+def postprocess_arrays(recs):
+    """(an RtPostprocessParams array, the raw pixels as a contiguous (n, 3) float32 array) of load_postprocess's records"""
+    import raytracer_amd as ra
+    params = (ra.RtPostprocessParams * len(recs)).from_buffer_copy(np.ascontiguousarray(recs["params"]).tobytes())
+    return params, np.ascontiguousarray(recs["raw"], dtype=np.float32)
+
+
+def bloom_input(count):
+    """kat_gen.cpp::bloomInput for i in [0, count)"""
+    i = np.arange(count, dtype=np.uint64)
+    h = (i * np.uint64(2654435761) + np.uint64(0x9E3779B9)) & np.uint64(0xFFFFFFFF)
+    h ^= h >> np.uint64(15); h = (h * np.uint64(2246822519)) & np.uint64(0xFFFFFFFF)
+    h ^= h >> np.uint64(13); h = (h * np.uint64(3266489917)) & np.uint64(0xFFFFFFFF)
+    h ^= h >> np.uint64(16)
+    base = (h >> np.uint64(8)).astype(np.float32) * np.float32(1.0 / 16777216.0)
+    return np.where((h & np.uint64(0x3F)) == 0, base * np.float32(400.0), base * np.float32(2.0)).astype(np.float32)
+
+
+BLOOM_EDIT_INDEX = 3 * (17 * 64 + 20) + 1   # kat_gen.cpp kBloomEditIndex: pixel (20, 17), green, of the 64 x 48 cases (+inf, NaN)
+BLOOM_EDGE_INDEX = 3 * (17 * 64 + 0) + 1    # kat_gen.cpp kBloomEdgeIndex: pixel (0, 17), green (FLT_MAX: a line's first value is summed radius + 1 times)
+
+
+def load_bloom(name):
+    """bloom_kat.bin / bloom_edges_kat.bin (kat_gen.cpp genBloom / genBloomEdges) as a list of cases: dict(w, h, step, sigma0, edit, image = the
+    input, levels = [dict(sum = the 64-bit sum of the words that are not NaN, nans = the number of NaN words or None where the file does not carry
+    it (bloom_kat.bin: no NaN in it), lattice = the expected uint32 words at x % step == 0, y % step == 0)])"""
+    raw = np.fromfile(os.path.join(GOLDEN, name), dtype=np.uint32)
+    edges = {0x4D4F4C42: False, 0x454F4C42: True}[int(raw[0])]
+    off, cases = 2, []
+    for _ in range(int(raw[1])):
+        w, h, levels, step = (int(v) for v in raw[off:off + 4])
+        sigma0 = float(raw[off + 4:off + 5].view(np.float32)[0])
+        edit = int(raw[off + 5]) if edges else 0
+        off += 6 if edges else 5
+        image = bloom_input(w * h * 3)
+        if edit == 4:
+            image = -image
+        elif edit:
+            image[BLOOM_EDGE_INDEX if edit == 3 else BLOOM_EDIT_INDEX] = np.array([0x7F800000, 0x7FC00000, 0x7F7FFFFF], dtype=np.uint32).view(np.float32)[edit - 1]
+        out = []
+        for _level in range(levels):
+            total = int(raw[off]) | (int(raw[off + 1]) << 32)
+            nans = int(raw[off + 2]) if edges else None
+            off += 3 if edges else 2
+            count = len(range(0, h, step)) * len(range(0, w, step)) * 3
+            out.append(dict(sum=total, nans=nans, lattice=raw[off:off + count].reshape(len(range(0, h, step)), len(range(0, w, step)), 3)))
+            off += count
+        cases.append(dict(w=w, h=h, step=step, sigma0=sigma0, edit=edit, image=image.reshape(h, w, 3), levels=out))
+    assert off == raw.size, name
+    return cases
+
+
+def check_blur_level(img, level, step, what):
+    """One blurred level against the reference's: every lattice float (bit for bit; both NaN where the reference's is NaN), the number of NaN
+    words and the 64-bit sum of the others."""
+    lattice = img[::step, ::step, :]
+    want = level["lattice"].view(np.float32)
+    bad = bit_mismatch(want, lattice)
+    assert not bad.any(), "%s: %d lattice floats differ, first at %s" % (what, int(bad.sum()), np.argwhere(bad)[0])
+    words = img.view(np.uint32)
+    nan = np.isnan(img)
+    if level["nans"] is not None:
+        assert int(nan.sum()) == level["nans"], "%s: %d NaN words, the reference has %d" % (what, int(nan.sum()), level["nans"])
+    else:
+        assert not nan.any(), what
+    assert int(words[~nan].astype(np.uint64).sum()) & 0xFFFFFFFFFFFFFFFF == level["sum"], "%s: checksum" % what
+
+
 def load_texture_kat():
     """tests/golden/texture_kat.bin (layout: oracle/ref_harness/kat_gen.cpp genTextures).  Returns a dict with the
     RtTexture array, the texel blob (uint8) and the three record tables as structured numpy arrays."""

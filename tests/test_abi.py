@@ -27,6 +27,21 @@ def test_every_declared_symbol_is_exported(built):
     assert lib.rtgpu_abi_version() == 3
 
 
+def test_postprocess_hooks_are_declared_and_refuse_a_null_context(built):
+    """rtgpu_kat_postprocess / rtgpu_kat_blur: in the header, exported, given argument types by the package, and a NULL context is
+    refused before any device is touched"""
+    import raytracer_amd as ra
+    lib = ra.rtgpu_lib()
+    names = declared_functions()
+    for n in ("rtgpu_kat_postprocess", "rtgpu_kat_blur"):
+        assert n in names and hasattr(lib, n) and getattr(lib, n).argtypes is not None, n
+    p = ra.RtPostprocessParams(numPasses=1)
+    rgb, bgr = np.zeros(3 * 64, dtype=np.float32), np.zeros(64, dtype=np.uint32)
+    assert lib.rtgpu_kat_postprocess(None, C.byref(p), rgb.ctypes.data, 1, bgr.ctypes.data, None) == -1 and b"NULL" in lib.rtgpu_last_error()
+    assert lib.rtgpu_kat_blur(None, rgb.ctypes.data, 8, 8, 1.3) == -1 and b"NULL" in lib.rtgpu_last_error()
+    assert C.sizeof(ra.RtPostprocessParams) == 48   # the record layout of postprocess_kat.bin / postprocess_edges_kat.bin depends on it
+
+
 def test_struct_layouts_agree(built):
     import raytracer_amd as ra
     import oracle_lib

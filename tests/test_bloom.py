@@ -47,6 +47,27 @@ def test_gaussian_blur_matches_the_reference(built):
     assert off == raw.size
 
 
+def test_gaussian_blur_matches_the_reference_at_the_edges(built):
+    """bloom_edges_kat.bin: the smallest images the blur's windows admit (8 x 8 at sigma 1.3, 196 x 196 over the frame's five levels), lines far
+    longer than there are lines, and input that is not finite -- one +inf, one NaN, one FLT_MAX (the running sum overflows), a negated image.
+    Every lattice float bit for bit (both NaN where the reference's is NaN), the number of NaN words, the checksum of the others."""
+    lib = oracle_lib.lib()
+    cases = kat_io.load_bloom("bloom_edges_kat.bin")
+    assert [(c["w"], c["h"], len(c["levels"]), c["edit"]) for c in cases] == [(8, 8, 1, 0), (8, 300, 1, 0), (300, 8, 1, 0), (196, 196, 5, 0), (64, 48, 1, 1), (64, 48, 1, 2),
+                                                                             (64, 48, 1, 3), (64, 48, 1, 4)]
+    for c in cases:
+        img, sigma = c["image"].copy(), c["sigma0"]
+        for number, level in enumerate(c["levels"]):
+            assert lib.rto_gaussian_blur(img.ctypes.data_as(C.POINTER(C.c_float)), C.c_uint32(c["w"]), C.c_uint32(c["h"]), C.c_float(sigma), C.c_uint32(8)) == 0
+            sigma = float(np.float32(sigma) * np.float32(2.5))
+            kat_io.check_blur_level(img, level, c["step"], "%dx%d edit %d level %d" % (c["w"], c["h"], c["edit"], number))
+    # what one pixel that is not finite does, in the reference's own numbers: inf - inf poisons the rest of its row, then every column of it
+    for edit in (1, 2, 3):
+        nans = cases[3 + edit]["levels"][0]["nans"]
+        assert 0 < nans < 64 * 48 * 3, (edit, nans)
+    assert cases[7]["levels"][0]["nans"] == 0
+
+
 @pytest.mark.gpu
 def test_front_buffer_with_bloom_matches_the_oracle(built):
     import raytracer_amd as ra

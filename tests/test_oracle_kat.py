@@ -118,37 +118,62 @@ def test_textures_on_the_shading_path_bit_exact(built):
         assert np.array_equal(got.view(np.uint32), rec["out"].view(np.uint32)), (rec["dir"], got, rec["out"])
 
 
-def _postprocess_records():
-    import ctypes as C
-    import raytracer_amd as ra
-    raw = np.fromfile(os.path.join(kat_io.GOLDEN, "postprocess_kat.bin"), dtype=np.uint8)
-    n = int(raw[:4].view(np.uint32)[0])
-    rec = np.dtype([("params", np.uint8, C.sizeof(ra.RtPostprocessParams)), ("raw", np.float32, 3), ("bgr", np.uint32), ("toneMapped", np.float32, 3)])
-    assert raw.size == 4 + n * rec.itemsize
-    return raw[4:].view(rec)
-
-
 def test_postprocess_matches_reference(built):
-    """Viewport::PostProcessTile composed from the reference's own functions (postprocess_kat.bin).  The Clamped and Reinhard
-    tone mappers are arithmetic only: the oracle's 8-bit output must be IDENTICAL.  Hejl-Burgess-Dawson and ACES go through
-    Vector4::FastReciprocal, whose seed is the vendor-specific _mm_rcp_ps (the oracle uses 1 / v): the refined reciprocal
-    agrees to ~2^-22, so a channel may land on the other side of an 8-bit boundary -- at most one LSB, in < 0.5 % of them."""
+    """Viewport::PostProcessTile composed from the reference's own functions: postprocess_kat.bin (rendered-frame ranges) and
+    postprocess_edges_kat.bin (zeros, denormals, huge values, infinities, NaN, negative channels; parameters at the corners of their ranges).
+    The Clamped and Reinhard tone mappers are arithmetic only: the floats Vector4::ToBGR quantises must be the reference's bit for bit (both
+    NaN where the reference's is NaN) and the 8-bit words IDENTICAL.  Hejl-Burgess-Dawson and ACES go through Vector4::FastReciprocal, whose
+    seed is the vendor-specific _mm_rcp_ps (the oracle uses 1 / v): the refined reciprocal agrees to ~2^-22, so a channel may land on the
+    other side of an 8-bit boundary -- at most one LSB, in < 0.5 % of them.  The inputs on which that seed decides more than this are kept
+    out of those two operators' records by the generator (tests/golden/README.md names them); no record is skipped here."""
     import ctypes as C
-    import raytracer_amd as ra
-    recs = _postprocess_records()
     o = oracle_lib.lib()
-    out = (C.c_uint32 * 1)()
-    exact_bad = 0; approx_off = 0; approx_total = 0
-    for r in recs:
-        p = ra.RtPostprocessParams.from_buffer_copy(r["params"].tobytes())
-        px = (C.c_float * 3)(*r["raw"])
-        o.rto_postprocess(px, C.c_uint32(1), C.c_uint32(1), C.byref(p), out)
-        got, exp = int(out[0]), int(r["bgr"])
-        if p.tonemapper in (0, 1):
-            exact_bad += got != exp
-        else:
-            d = [abs(((got >> s) & 255) - ((exp >> s) & 255)) for s in (0, 8, 16)]
-            assert max(d) <= 1, (got, exp)
-            approx_off += sum(d); approx_total += 3
-    assert exact_bad == 0
-    assert approx_off <= 0.005 * approx_total, (approx_off, approx_total)
+    for name in kat_io.POSTPROCESS_FILES:
+        recs = kat_io.load_postprocess(name)
+        params, rgb = kat_io.postprocess_arrays(recs)
+        n = len(recs)
+        assert n == 4096
+        bgr = np.zeros(n, dtype=np.uint32)
+        tone = np.zeros((n, 3), dtype=np.float32)
+        o.rto_postprocess_records(params, rgb.ctypes.data_as(C.c_void_p), C.c_uint32(n), bgr.ctypes.data_as(C.c_void_p), tone.ctypes.data_as(C.c_void_p))
+        # the records entry and the whole-image entry are the same function
+        for i in range(0, n, 97):
+            one = (C.c_uint32 * 1)()
+            o.rto_postprocess(rgb[i].ctypes.data_as(C.c_void_p), C.c_uint32(1), C.c_uint32(1), C.byref(params[i]), one)
+            assert int(one[0]) == int(bgr[i]), (name, i)
+        tonemapper = np.array([p.tonemapper for p in params])
+        exact = tonemapper <= 1
+        assert exact.sum() >= n // 2 and (tonemapper == 2).sum() >= n // 8 and (tonemapper == 3).sum() >= n // 8, name
+        bad = kat_io.bit_mismatch(recs["toneMapped"], tone)
+        assert not bad[exact].any(), "%s: %d tone-mapped floats of the exact operators differ, first record %d" % (name, int(bad[exact].sum()), int(np.nonzero(bad.any(axis=1) & exact)[0][0]))
+        assert np.array_equal(bgr[exact], recs["bgr"][exact]), "%s: record %d" % (name, int(np.nonzero((bgr != recs["bgr"]) & exact)[0][0]))
+        d = np.stack([np.abs(((bgr[~exact] >> s) & 255).astype(np.int64) - ((recs["bgr"][~exact] >> s) & 255).astype(np.int64)) for s in (0, 8, 16)], axis=1)
+        print("%s: approximate operators: %d of %d channels off by one, largest difference %d" % (name, int((d == 1).sum()), d.size, int(d.max())))
+        assert d.max() <= 1, (name, int(np.nonzero(~exact)[0][np.argmax(d.max(axis=1))]))
+        assert d.sum() <= 0.005 * d.size, (name, int(d.sum()), d.size)
+        # where the reference's float of an approximate operator is NaN (an infinite or NaN channel), so is the oracle's: no seed is involved
+        assert np.array_equal(np.isnan(tone), np.isnan(recs["toneMapped"])), name
+
+
+def test_postprocess_edge_fixture_covers_what_it_claims():
+    """postprocess_edges_kat.bin: every special value in every channel position under every operator that keeps it, every parameter corner,
+    and NaN / black results among the expected outputs (the NaN -> INT_MIN -> 0 conversion of Vector4::ToBGR)."""
+    recs = kat_io.load_postprocess("postprocess_edges_kat.bin")
+    params, rgb = kat_io.postprocess_arrays(recs)
+    bits = rgb.view(np.uint32)
+    tonemapper = np.array([p.tonemapper for p in params])
+    for special in kat_io.POST_SPECIALS.view(np.uint32):
+        for k in range(3):
+            for t in (0, 1):
+                assert ((bits[:, k] == special) & (tonemapper == t)).any(), (hex(int(special)), k, t)
+    for special in kat_io.POST_SPECIALS[[0, 1, 2, 3, 4, 5, 9, 10, 11, 12, 13]].view(np.uint32):   # (not 65504, 1e20, FLT_MAX under exposure +30: the documented class)
+        for t in (2, 3):
+            assert ((bits == special).any(axis=1) & (tonemapper == t)).any(), (hex(int(special)), t)
+    for field, values in (("saturation", (0.0, 1.0, 1.5)), ("contrast", (0.4, 1.0, 1.6)), ("exposure", (-30.0, 0.0, 30.0)), ("numPasses", (1, 300))):
+        got = np.array([getattr(p, field) for p in params])
+        for t in range(4):
+            assert set(np.unique(got[tonemapper == t]).tolist()) == set(np.float32(v).item() if isinstance(v, float) else v for v in values), (field, t)
+    nan = np.isnan(recs["toneMapped"])
+    assert nan.any(axis=1).sum() > 200
+    for k, shift in enumerate((16, 8, 0)):
+        assert (((recs["bgr"] >> shift) & 255)[nan[:, k]] == 0).all()     # a NaN channel comes out black
