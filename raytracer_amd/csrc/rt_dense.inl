@@ -87,14 +87,63 @@ RT_DEV void denseResolvePending(const Paths& in, uint32_t slot, uint32_t numRequ
     resultColor = mulAdd(V4(tp.x, tp.y, tp.z, 0.0f), accumulated, resultColor);
 }
 
+// What k_shade_dense copies to LDS in front of its first vertex (rt_device_state.h: RT_STAGE_*): the scene's small tables and the seed rows of the batch's passes
+struct DenseStageTables
+{
+    RtObject objects[RT_STAGE_MAX_OBJECTS];
+    RtMesh meshes[RT_STAGE_MAX_MESHES];
+    RtMaterial materials[RT_STAGE_MAX_MATERIALS];
+    RtLight lights[RT_STAGE_MAX_LIGHTS];
+    uint32_t globalLights[RT_STAGE_MAX_LIGHTS];
+    uint32_t seeds[RT_STAGE_SEED_WORDS];   // row p: pass p of the batch, stageSeedRow(numDimensions) words
+};
+// all threads of the block; `bytes` is a multiple of 16 and both ends are 16-byte aligned
+RT_DEV void denseStageCopy(void* dst, const void* src, uint32_t bytes)
+{
+    const uint4* __restrict__ s = (const uint4*)src;
+    uint4* d = (uint4*)dst;
+    for (uint32_t k = threadIdx.x; k < bytes / 16u; k += RT_BLOCK) d[k] = s[k];
+}
+// The block's copy of the tables (the host checked them against the capacities: denseStageMask) and, `seeds`, of the seed rows, made per launch from the
+// device tables, so that rtgpu_update_objects and scene uploads need nothing extra.  All threads of the block; the caller synchronises.
+RT_DEV void denseStageLoad(DenseStageTables& t, const RtSceneDesc& scene, const DevPass* __restrict__ passes, uint32_t numPasses, uint32_t numDims, bool seeds)
+{
+    denseStageCopy(t.objects, scene.objects, scene.numObjects * (uint32_t)sizeof(RtObject));
+    denseStageCopy(t.meshes, scene.meshes, scene.numMeshes * (uint32_t)sizeof(RtMesh));
+    denseStageCopy(t.materials, scene.materials, scene.numMaterials * (uint32_t)sizeof(RtMaterial));
+    denseStageCopy(t.lights, scene.lights, scene.numLights * (uint32_t)sizeof(RtLight));
+    if (threadIdx.x < scene.numGlobalLights) t.globalLights[threadIdx.x] = scene.globalLights[threadIdx.x];
+    if (seeds)
+    {
+        // the ring rows are RTGPU_MAX_DIMENSIONS words apart: only the words the samplers read are copied (a row's tail up to the next multiple of four rides along)
+        const uint32_t quads = stageSeedRow(numDims) / 4u;
+        for (uint32_t k = threadIdx.x; k < numPasses * quads; k += RT_BLOCK)
+        {
+            const uint32_t p = k / quads, q = k - p * quads;
+            ((uint4*)t.seeds)[k] = ((const uint4*)passes[p].seed)[q];
+        }
+    }
+}
+
+// The seed row of pass `row` of the batch: the staged copy (kStage 2) or the ring's row in memory
+template <int kStage>
+RT_DEV const uint32_t* denseSeedRow(const DevPass* __restrict__ passes, uint32_t row, const uint32_t* stagedSeeds, uint32_t seedRow)
+{
+    if (kStage == 2) return stagedSeeds + row * seedRow;
+    return passes[row].seed;
+}
+
 // The body of PathTracerMIS::RenderPixel's loop for one path vertex (PathTracerMIS.cpp:276-395) over the records of arena `in` at `slot`;
 // kPlain: PathTracer::RenderPixel (Core/Rendering/PathTracer.cpp:73-171).  `stage` = four LDS rows of RT_BLOCK float4 (the next-event request
 // waits there, see k_shade_dense).
-template <int kLean, bool kPlain, bool kAll>
+// kStage says where the launch-uniform tables are, at compile time, so that a staged table is LDS to the compiler and a table in memory is addressed as it
+// always was: 0 in memory, all of them; 1 `scene`'s objects, meshes, materials, lights and global lights are the block's LDS copies, the seed rows are in
+// memory; 2 the seed rows too (`stagedSeeds`, rows `seedRow` words apart).  k_tail runs kStage 0.
+template <int kLean, bool kPlain, bool kAll, int kStage = 0>
 __device__ __forceinline__ static void denseShadeVertex(const RtSceneDesc& scene, const DevPass* __restrict__ passes, uint32_t slotsPerPass, const DevPass& pass, const Paths& in,
                                                         uint32_t slot, bool zombie, V4 lightSamplingWeight, V4 bsdfSamplingWeight, float lightPickProbability,
                                                         float4 (*stage)[RT_BLOCK], float4* __restrict__ home, Counters& cnt, DenseVertex& v,
-                                                        const uint32_t* __restrict__ primarySlotPixel = nullptr)
+                                                        const uint32_t* __restrict__ primarySlotPixel = nullptr, const uint32_t* stagedSeeds = nullptr, uint32_t seedRow = 0u)
 {
     // Bounce 0 (primarySlotPixel != null): k_generate_dense stores only what depends on the camera sample -- origin and direction.  The other five
     // records of a fresh path are functions of its slot (radiance 0 | pixel, throughput 1, home = slot, the sampler and the per-pixel generator as
@@ -159,14 +208,14 @@ __device__ __forceinline__ static void denseShadeVertex(const RtSceneDesc& scene
                 // the sampler and the per-pixel generator as Camera::GenerateRay left them: reset as k_generate_dense does and let the camera draw again
                 const DevPass& own = passes[homeIndex / slotsPerPass];
                 const uint32_t x = pix & 0xFFFFu, y = pix >> 16;
-                sampler.seed = own.seed; sampler.numDims = own.numDimensions; sampler.blueNoiseLayers = own.blueNoiseLayers; sampler.blueNoise = scene.blueNoise;
+                sampler.seed = denseSeedRow<kStage>(passes, homeIndex / slotsPerPass, stagedSeeds, seedRow); sampler.numDims = own.numDimensions; sampler.blueNoiseLayers = own.blueNoiseLayers; sampler.blueNoise = scene.blueNoise;
                 sampler.resetPixel(x, y, own.rngKey[0], own.rngKey[1]);
                 const float invW = 1.0f / (float)(int32_t)own.width, invH = 1.0f / (float)(int32_t)own.height;
                 const V4 coords(((float)(int32_t)x + own.sampleOffset[0]) * invW, ((float)(int32_t)(own.height - 1u - y) + own.sampleOffset[1]) * invH, 0.0f, 0.0f);
                 V4 cameraOrigin, cameraDirection;
                 cameraGenerateRayParts(own.camera, coords, sampler, cameraOrigin, cameraDirection);
             }
-            else { if (!kEarlyRng) rRng = ldStream(prec(in, R_RNG, slot)); loadSampler(sampler, pix, rSampler, rRng, pass, scene.blueNoise); sampler.seed = passes[homeIndex / slotsPerPass].seed; }
+            else { if (!kEarlyRng) rRng = ldStream(prec(in, R_RNG, slot)); loadSampler(sampler, pix, rSampler, rRng, pass, scene.blueNoise); sampler.seed = denseSeedRow<kStage>(passes, homeIndex / slotsPerPass, stagedSeeds, seedRow); }
 
             // SampleLights (next event estimation), PathTracerMIS.cpp:125-155
             if (!kPlain && kAll && scene.numLights != 0)
@@ -226,7 +275,12 @@ __device__ __forceinline__ static void denseShadeVertex(const RtSceneDesc& scene
 // The 2 x numLights request records of a vertex cannot wait in registers or LDS for its output slot, so they are written to the vertex's OWN
 // slot of the input arena first -- its previous requests were folded in at the top of the iteration, the space is free -- and copied to the
 // output slot once the block has allocated it (the copy reads what the same lane just wrote: L2 hits).
-template <int kLean, bool kPlain = false, bool kAll = false>
+//
+// kStage: where the launch-uniform tables behind a vertex's records are (denseShadeVertex), chosen by the host per launch (denseStageMask).  One kernel per
+// place, not one kernel with three copies of the vertex: the copies' live ranges add up at the branch (the lean class 116 -> 125 VGPRs, scratch gained in two of
+// the register-capped classes), while a kernel with one vertex keeps every class within its waves and its scratch (profiles/shade_tables_resources_diff.txt),
+// and kStage 0 is the kernel as it was, without the tables' LDS.
+template <int kLean, bool kPlain = false, bool kAll = false, int kStage = 0>
 __global__ void RT_SHADE_DENSE_ATTR(kLean, kAll) k_shade_dense(const RtSceneDesc scene, const DevPass* __restrict__ passes, uint32_t slotsPerPass, const Paths in, const Paths out,
                                                           const DenseCounts dense, uint32_t* __restrict__ shadowQueue, uint32_t* __restrict__ shadowCount,
                                                           float4* __restrict__ home, unsigned long long* counters)
@@ -239,14 +293,20 @@ __global__ void RT_SHADE_DENSE_ATTR(kLean, kAll) k_shade_dense(const RtSceneDesc
     __shared__ uint32_t sShadowCount, sShadowBase;
     __shared__ uint32_t sLive, sZombies, sLiveBase, sZombieBase;
     __shared__ uint32_t sLivePrefix[RT_DENSE_SHARDS + 1u], sZombiePrefix[RT_DENSE_SHARDS + 1u];
+    // the launch-uniform tables behind a vertex's records (rt_device_state.h, RT_STAGE_*): an LDS read in the vertex's dependent chain where a trip to L2 was
+    __shared__ __attribute__((aligned(16))) DenseStageTables sTables;
     if (threadIdx.x == 0) { sShadowCount = 0; sLive = 0; sZombies = 0; }
     denseLoadPrefix(dense.in, sLivePrefix);
     denseLoadZombiePrefix(dense.in, dense.shardCapacity, dense.errorFlags, sZombiePrefix);
+    const DevPass pass = passes[0];   // the structural parameters are those of every pass of the batch
+    if (kStage != 0) denseStageLoad(sTables, scene, passes, dense.numPasses, pass.numDimensions, kStage == 2);
     __syncthreads();
+    RtSceneDesc staged = scene;
+    if (kStage != 0) { staged.objects = sTables.objects; staged.meshes = sTables.meshes; staged.materials = sTables.materials; staged.lights = sTables.lights; staged.globalLights = sTables.globalLights; }
+    const uint32_t seedRow = stageSeedRow(pass.numDimensions);
     Counters cnt; zeroCounters(cnt);
     const uint32_t numLive = sLivePrefix[RT_DENSE_SHARDS], count = numLive + sZombiePrefix[RT_DENSE_SHARDS];
     const uint32_t stride = gridDim.x * blockDim.x;
-    const DevPass pass = passes[0];   // the structural parameters are those of every pass of the batch
     const V4 lightSamplingWeight = load4(pass.lightSamplingWeight), bsdfSamplingWeight = load4(pass.bsdfSamplingWeight);
     const float lightPickProbability = kAll ? 1.0f : 1.0f / (float)(scene.numLights ? scene.numLights : 1u);   // GetLightPickingProbability, PathTracerMIS.cpp:157-172
 
@@ -263,8 +323,8 @@ __global__ void RT_SHADE_DENSE_ATTR(kLean, kAll) k_shade_dense(const RtSceneDesc
             bool zombie;
             const uint32_t slot = denseVertexSlot(sLivePrefix, sZombiePrefix, numLive, dense.shardCapacity, i, zombie);
             inSlot = slot;
-            denseShadeVertex<kLean, kPlain, kAll>(scene, passes, slotsPerPass, pass, in, slot, zombie, lightSamplingWeight, bsdfSamplingWeight, lightPickProbability, sStage, home, cnt, v,
-                                                  dense.primarySlotPixel);
+            denseShadeVertex<kLean, kPlain, kAll, kStage>(staged, passes, slotsPerPass, pass, in, slot, zombie, lightSamplingWeight, bsdfSamplingWeight, lightPickProbability, sStage, home, cnt, v,
+                                                          dense.primarySlotPixel, kStage == 2 ? sTables.seeds : nullptr, seedRow);
         }
         uint32_t outcome = v.outcome;
 

@@ -172,7 +172,23 @@ struct DenseCounts
     uint32_t shardCapacity;
     uint32_t* errorFlags;   // host-visible words of the context (RtgpuContext::deviceFlags): [0] != 0 = a region of the arena overflowed
     const uint32_t* primarySlotPixel;   // bounce 0 of a batch whose k_generate_dense stored origin and direction only: the slot -> pixel table; else null
+    uint32_t stage;         // RT_STAGE_* bits: what this launch copies to LDS (the host decides: denseStageMask); 0: everything from memory
+    uint32_t numPasses;     // passes of the batch (the seed rows a block stages)
 };
+
+// ---- launch-uniform tables of k_shade_dense in LDS (rt_dense.inl) ----
+// A vertex reads its object, mesh, material and light records and the seed row of its pass from tables of a few hundred bytes that are the same for every lane
+// of the launch; each such read was a trip to L2 of its own in the vertex's dependent chain.  A block copies them in front of its first vertex where they fit
+// these capacities: the scene's tables as a group, and with them the seed rows where those fit too.
+#define RT_STAGE_TABLES 1u    // scene.objects, meshes, materials, lights and globalLights
+#define RT_STAGE_SEEDS  2u    // the seed rows of the batch's passes, numDimensions words each (rounded up to four); only together with RT_STAGE_TABLES
+#define RT_STAGE_MAX_OBJECTS   8u
+#define RT_STAGE_MAX_MESHES    8u
+#define RT_STAGE_MAX_MATERIALS 32u
+#define RT_STAGE_MAX_LIGHTS    8u
+#define RT_STAGE_SEED_WORDS    2048u   // 8 KB: 24 passes of 64 dimensions take 6 KB
+static_assert(sizeof(RtObject) % 16 == 0 && sizeof(RtMesh) % 16 == 0 && sizeof(RtMaterial) % 16 == 0 && sizeof(RtLight) % 16 == 0, "the staged tables are copied in 16-byte words");
+__host__ __device__ __forceinline__ static uint32_t stageSeedRow(uint32_t numDims) { return (numDims + 3u) & ~3u; }   // words between two staged seed rows
 
 // prefix sums of the 16 region counts into LDS (prefix[16] = total); all threads of the block call it
 RT_DEV void denseLoadPrefix(const uint32_t* __restrict__ counts, uint32_t* sPrefix)

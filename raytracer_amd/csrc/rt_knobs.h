@@ -65,6 +65,8 @@ RT_KNOB_ONCE(bool, denoiseTiled, envInt("RTGPU_DENOISE_TILED", 1) != 0)         
 static inline uint32_t wideDrainAbort() { return (uint32_t)envInt("RTGPU_WIDE_DRAIN_ABORT", 0); }   // test hook; 0: off
 static inline uint32_t wideDiagMode() { return (uint32_t)envInt("RTGPU_WIDE_DIAG", 0); }
 static inline bool packets() { return envInt("RTGPU_PACKET", 1) != 0; }
+// every launch of k_shade_dense: the launch-uniform tables (objects, meshes, materials, lights, seed rows) from LDS copies; 0: everything from memory; same bits either way
+static inline bool shadeStage() { return envInt("RTGPU_SHADE_STAGE", 1) != 0; }
 // every rtgpu_render_aovs: pixels per chunk, 1 .. 4 M (the tests run a small frame in several chunks)
 static inline uint32_t aovChunk() { const int v = envInt("RTGPU_AOV_CHUNK", 1 << 22); return v < 1 ? 1u : (v > (1 << 22) ? (1u << 22) : (uint32_t)v); }
 // every rtgpu_upload_scene

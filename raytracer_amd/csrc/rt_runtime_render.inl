@@ -221,15 +221,30 @@ static uint32_t tailDepthFor(const RtgpuContext* c, uint32_t maxRayDepth, bool d
 }
 
 // The scene-class ladders of the shading kernels and of the fused tail (rt_shade_kernels.h, rt_tail_kernels.h): kLean class, plain path tracer, all lights
-#define RT_LAUNCH_SHADE_DENSE(L, P, A) hipLaunchKernelGGL((k_shade_dense<L, P, A>), grid, block, 0, l.stream, c->sceneDev, passesDev, c->numSlots, in, out, dc, \
-                                                     l.shadowQueues[depth & 1u], counts.shadowCounts + depth, l.home, c->counters)
+#define RT_LAUNCH_SHADE_DENSE_STAGE(L, P, A, S) hipLaunchKernelGGL((k_shade_dense<L, P, A, S>), grid, block, 0, l.stream, c->sceneDev, passesDev, c->numSlots, in, out, dc, \
+                                                              l.shadowQueues[depth & 1u], counts.shadowCounts + depth, l.home, c->counters)
+#define RT_LAUNCH_SHADE_DENSE(L, P, A) do { if (stage & RT_STAGE_SEEDS) RT_LAUNCH_SHADE_DENSE_STAGE(L, P, A, 2); else if (stage & RT_STAGE_TABLES) RT_LAUNCH_SHADE_DENSE_STAGE(L, P, A, 1); \
+                                         else RT_LAUNCH_SHADE_DENSE_STAGE(L, P, A, 0); } while (0)
 #define RT_LAUNCH_TAIL(L, P) hipLaunchKernelGGL((k_tail<L, P>), tailGrid, block, 0, l.stream, c->sceneDev, c->wide, passesDev, c->numSlots, in, args, l.home, c->counters)
+
+// What a launch of k_shade_dense reads from LDS copies (RT_STAGE_*, rt_device_state.h): the scene's small tables where every one of them fits its capacity,
+// and then the batch's seed rows where they fit theirs; decided per launch from the scene's counts and the batch -- nothing is cached, so scene updates and
+// uploads need no extra work.  RTGPU_SHADE_STAGE=0: nothing.
+static uint32_t denseStageMask(const RtgpuContext* c, uint32_t numPasses, uint32_t numDimensions)
+{
+    if (!knobs::shadeStage()) return 0u;   // (read per launch: the tests switch it)
+    const RtSceneDesc& d = c->sceneDev;
+    if (d.numObjects > RT_STAGE_MAX_OBJECTS || d.numMeshes > RT_STAGE_MAX_MESHES || d.numMaterials > RT_STAGE_MAX_MATERIALS || d.numLights > RT_STAGE_MAX_LIGHTS ||
+        d.numGlobalLights > RT_STAGE_MAX_LIGHTS) return 0u;
+    return (size_t)numPasses * stageSeedRow(numDimensions) <= RT_STAGE_SEED_WORDS ? RT_STAGE_TABLES | RT_STAGE_SEEDS : RT_STAGE_TABLES;
+}
 
 // The bounces of a batch with DENSE path state (rt_dense.inl): one next-event request per vertex (LightSamplingStrategy::Single, or none: "Path Tracer"),
 // or one per light under LightSamplingStrategy::All with a handful of lights (the benchmark scene has two): `denseAll`
-static int submitDenseBatch(RtgpuContext* c, BatchLane& l, const LaneCounts& counts, const DevPass* passesDev, uint32_t totalSlots, uint32_t maxRayDepth, bool denseAll, dim3 grid)
+static int submitDenseBatch(RtgpuContext* c, BatchLane& l, const LaneCounts& counts, const DevPass* passesDev, uint32_t totalSlots, uint32_t maxRayDepth, bool denseAll, dim3 grid, uint32_t numDimensions)
 {
     const dim3 block(RT_BLOCK);
+    const uint32_t numPasses = totalSlots / (c->numSlots ? c->numSlots : 1u), stage = denseStageMask(c, numPasses, numDimensions);
     const uint32_t shardCapacity = (totalSlots + RT_DENSE_SHARDS - 1u) / RT_DENSE_SHARDS + 65536u;
     const uint32_t plane = 2u * RT_DENSE_SHARDS;
     // a fresh path's records: only origin and direction are stored, bounce 0's shade rebuilds the rest from the slot (rt_dense.inl)
@@ -273,7 +288,7 @@ static int submitDenseBatch(RtgpuContext* c, BatchLane& l, const LaneCounts& cou
         }
         // bounce `depth`: shades the live paths; folds the visibility results of the previous bounce's zombies in (the last round does only that)
         const DenseCounts dc = { l.denseCounts + (size_t)plane * depth, l.denseCounts + (size_t)plane * (depth + 1u), shardCapacity, c->deviceFlags,
-                                 depth == 0u ? c->slotPixel : nullptr };
+                                 depth == 0u ? c->slotPixel : nullptr, stage, numPasses };
         LaunchTimer t(c, l.stream, KC_SHADE);
         if (c->plainPathTracer) RT_LAUNCH_SHADE_DENSE(0, true, false);
         else if (denseAll) { if (c->leanScene == 1) RT_LAUNCH_SHADE_DENSE(1, false, true); else if (c->leanScene == 2) RT_LAUNCH_SHADE_DENSE(2, false, true); else if (c->leanScene == 4) RT_LAUNCH_SHADE_DENSE(4, false, true); else RT_LAUNCH_SHADE_DENSE(0, false, true); }
@@ -283,6 +298,7 @@ static int submitDenseBatch(RtgpuContext* c, BatchLane& l, const LaneCounts& cou
     return RTGPU_OK;
 }
 #undef RT_LAUNCH_SHADE_DENSE
+#undef RT_LAUNCH_SHADE_DENSE_STAGE
 #undef RT_LAUNCH_TAIL
 
 // The bounces of a slot-per-pixel sequence on lane `l` (a batch lane or the recorder's), after its k_generate.  Bounce k: trace {closest-hit rays of bounce k,
@@ -400,7 +416,7 @@ static int flushBatch(RtgpuContext* c, uint32_t maxPasses)
     HIP_TRY(hipMemsetAsync(l.queueCounts, 0, laneCountBytes(l), l.stream));
     const bool dense = c->denseAllowed && c->debugMode < 0 && maxLights <= RT_DENSE_MAX_LIGHTS && l.paths2.base != nullptr;
     const bool denseAll = dense && first.lightSamplingStrategy == RT_LIGHT_SAMPLING_ALL && !c->plainPathTracer;
-    if (dense) { r = submitDenseBatch(c, l, counts, passesDev, totalSlots, first.maxRayDepth, denseAll, grid); if (r) return r; }
+    if (dense) { r = submitDenseBatch(c, l, counts, passesDev, totalSlots, first.maxRayDepth, denseAll, grid, first.numDimensions); if (r) return r; }
     else submitSlotBatch(c, l, counts, passesDev, totalSlots, first.maxRayDepth, grid);
 
     // the film is summed in pass order: this batch's accumulate runs after the previous batch's

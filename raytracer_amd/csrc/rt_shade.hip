@@ -20,7 +20,9 @@
 #include "rt_aov.inl"
 
 // the instantiations the host side launches (the lists are in rt_shade_kernels.h)
-#define RT_X(L, P, A) template __global__ void RT_SHADE_DENSE_ATTR(L, A) k_shade_dense<L, P, A> RT_K_SHADE_DENSE_ARGS;
+#define RT_X(L, P, A) template __global__ void RT_SHADE_DENSE_ATTR(L, A) k_shade_dense<L, P, A, 0> RT_K_SHADE_DENSE_ARGS; \
+                      template __global__ void RT_SHADE_DENSE_ATTR(L, A) k_shade_dense<L, P, A, 1> RT_K_SHADE_DENSE_ARGS; \
+                      template __global__ void RT_SHADE_DENSE_ATTR(L, A) k_shade_dense<L, P, A, 2> RT_K_SHADE_DENSE_ARGS;
 RT_K_SHADE_DENSE_INSTANCES(RT_X)
 #undef RT_X
 #define RT_X(L, P) template __global__ void __launch_bounds__(RT_BLOCK) k_shade<L, P> RT_K_SHADE_ARGS;

@@ -3,7 +3,8 @@
 #include "rt_vcm_state.h"
 
 // one list of k_shade_dense's instantiations -- X(scene class, plain path tracer, LightSamplingStrategy::All) -- for the explicit instantiations in
-// rt_shade.hip; the launch ladder of flushBatch (rt_runtime.hip) picks among exactly these
+// rt_shade.hip; the launch ladder of flushBatch (rt_runtime.hip) picks among exactly these.  Each comes three times, kStage 0 / 1 / 2: where the launch-uniform
+// tables are read from (rt_dense.inl)
 #define RT_SHADE_DENSE_ATTR(kLean, kAll) __launch_bounds__(RT_BLOCK) __attribute__((amdgpu_waves_per_eu(RT_SHADE_MIN_WAVES(kLean, kAll), RT_SHADE_MIN_WAVES(kLean, kAll) > 1 ? RT_SHADE_MIN_WAVES(kLean, kAll) : 10)))
 #define RT_K_SHADE_DENSE_ARGS (const RtSceneDesc scene, const DevPass* __restrict__ passes, uint32_t slotsPerPass, const Paths in, const Paths out, const DenseCounts dense, \
                                uint32_t* __restrict__ shadowQueue, uint32_t* __restrict__ shadowCount, float4* __restrict__ home, unsigned long long* counters)
@@ -73,7 +74,7 @@ __global__ void __launch_bounds__(RT_BLOCK) k_generate_dense(const RtSceneDesc s
 __global__ void __launch_bounds__(RT_BLOCK) k_generate_dense_rays(const RtSceneDesc scene, const DevPass* __restrict__ passes, uint32_t slotsPerPass, const Paths paths,
                                                                   const uint32_t* __restrict__ slotPixel, uint32_t numSlots, uint32_t shardCapacity, uint32_t* __restrict__ counts,
                                                                   unsigned long long* counters, const float4* __restrict__ rays);
-template <int kLean, bool kPlain = false, bool kAll = false>
+template <int kLean, bool kPlain = false, bool kAll = false, int kStage = 0>
 __global__ void RT_SHADE_DENSE_ATTR(kLean, kAll) k_shade_dense RT_K_SHADE_DENSE_ARGS;
 __global__ void __launch_bounds__(RT_BLOCK) k_accumulate_home(const float4* __restrict__ home, const uint32_t* __restrict__ slotPixel, uint32_t slotsPerPass, uint32_t numPasses,
                                                               float* __restrict__ sum, float* __restrict__ secondary, uint32_t width, const DevPass* __restrict__ passes);
