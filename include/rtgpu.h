@@ -512,7 +512,8 @@ int rtgpu_read_wide_level(RtgpuContext* ctx, uint32_t objectIndex, RtWideLevelIn
  *   rtgpu_resize     a new film of the given size, both sum buffers zero.  Drops the active blocks of rtgpu_set_active_blocks (the whole
  *                    image is active again), the photons of RT_INTEGRATOR_VCM (the next pass merges nothing) and the history of
  *                    rtgpu_denoise_temporal (the next such call starts every pixel), also when the size is the one the context has.  It alone
- *                    drops the ray source of rtgpu_set_ray_source too (the camera renders again); rtgpu_set_shard and rtgpu_reset keep it.
+ *                    drops the ray source of rtgpu_set_ray_source or the lens source of rtgpu_set_lens_source too (the camera renders again); rtgpu_set_shard
+ *                    and rtgpu_reset keep it.
  *                    Keeps the scene, the integrator and its settings, the shard, the counters, rtgpu_set_guide_chain, and whatever device
  *                    memory still suffices.  A refused size (0, or above 65536) changes nothing.
  *   rtgpu_set_shard  the same for a new ownership of the frame's tiles.
@@ -946,7 +947,7 @@ int rtgpu_render_aovs_virtual_async(RtgpuContext* ctx, const RtPassParams* param
  *              the ray queries.  A degenerate entry: RTGPU_ERR_INVALID_ARGUMENT, and the previous source, or the camera, stays exactly as it was; nothing
  *              degenerate ever reaches a walk.
  *   errors     count != width * height: RTGPU_ERR_INVALID_ARGUMENT; before rtgpu_resize: RTGPU_ERR_NOT_READY; rays == NULL with count == 0 clears the
- *              source (the camera renders again), rays == NULL with any other count: RTGPU_ERR_INVALID_ARGUMENT.
+ *              source, also a lens source (the camera renders again), rays == NULL with any other count: RTGPU_ERR_INVALID_ARGUMENT.
  *   _device    `rays` is device memory, held to hipPointerGetAttributes and hipMemGetAddressRange as rtgpu_update_mesh_device holds its arrays (memory of
  *              the context's device, 4-byte aligned, whose allocation holds 32 * count bytes from the pointer on -- else RTGPU_ERR_INVALID_ARGUMENT); the
  *              call orders itself behind `stream` (NULL: the context's own) with an event and copies device to device.  A multi-device context:
@@ -968,6 +969,85 @@ int rtgpu_set_ray_source_device(RtgpuContext* ctx, const RtPrimaryRay* rays, uin
 int rtgpu_get_ray_source(RtgpuContext* ctx, uint64_t* outCount);                                              /* 0: the camera */
 int rtgpu_read_camera_rays(RtgpuContext* ctx, const RtPassParams* params, RtPrimaryRay* out);                        /* host; synchronous */
 int rtgpu_read_camera_rays_async(RtgpuContext* ctx, const RtPassParams* params, RtPrimaryRay* out, void* stream);    /* device */
+
+/* ---------------------------------------------------------------------------------------------
+ * The lens source: a table of RECIPES for a pass's primary ray.  A ray source holds one finished ray per pixel, so a new sub-pixel offset per pass means a
+ * new table per pass (and every set call ends the batch in flight), and a thin lens, whose sample must come from the pass's sampler on the device, cannot be
+ * expressed at all.  A lens source holds, per pixel, the ray, its footprint -- its first-order change per unit of RtPassParams::sampleOffset -- and a thin
+ * lens; the generate kernels apply the pass's offset and take the lens sample from the pass's sampler exactly as Camera::GenerateRay does.  One table then
+ * serves every pass of a batch, jittered and defocused.  It is a second setting beside the ray source, whose contract is untouched: one context holds one
+ * source, setting either kind replaces the other, and rtgpu_set_ray_source(ctx, NULL, 0) clears both.
+ *   entry      RtLensRay, 128 bytes, eight float4; entry y * width + x is sum-buffer pixel (x, y), the plain table's indexing and row order:
+ *                quad 0   origin.xyz                          w: aperture
+ *                quad 1   direction.xyz (not normalised)      w: focalDistance
+ *                quad 2,3 dOrigin/dsx, dOrigin/dsy            w: not interpreted
+ *                quad 4,5 dDirection/dsx, dDirection/dsy      w: not interpreted
+ *                quad 6,7 lensU, lensV (the lens plane's axes; the library does not normalise them)   w: not interpreted
+ *              sx, sy are RtPassParams::sampleOffset[0], [1] as the caller passes them.
+ *   a pass's ray, operation by operation (tests/lens_source_ref.py is the same text in float32 NumPy; the jitter step is reproducible bit for bit):
+ *     1 jitter if sx == 0 and sy == 0: origin and direction are the stored words, untouched (a -0.0 component survives: it decides the sign of 1 / dir).
+ *              Otherwise, for each of the six components v of origin and direction with its derivatives dvdsx, dvdsy:
+ *                  v' = fadd(fadd(v, fmul(sx, dvdsx)), fmul(sy, dvdsy))
+ *              every fmul and fadd an IEEE float32 operation rounded to nearest even on its own; nothing is contracted into a fused multiply-add.
+ *     2 lens   only if the source was set with lens = 1.  EVERY pixel draws sampler.getFloat() twice, whatever its aperture (as the camera does under
+ *              dofEnable), u1 then u2, and runs the dofEnable branch of Camera::GenerateRay (Camera.cpp:104-114) -- the camera kernels' branch, operation
+ *              for operation -- on the jittered ray:
+ *                  focusPoint = fma(direction, focalDistance, origin)
+ *                  bokeh      = bokehShape 0: the circle of SamplingHelpers::GetCircle(u1, u2); 1: (u1 * -1 + u2 * 0.5, u1 * 0 + u2 * 0.8660254) (the hexagon's
+ *                               first rhombus); 2: (2 u1 - 1, 2 u2 - 1)
+ *                  p          = bokeh * aperture
+ *                  origin     = fma(p.y, lensV, fma(p.x, lensU, origin))
+ *                  direction  = focusPoint - origin
+ *              with lensU, lensV in the places of the camera transform's rows 0 and 1.  With lens = 0 nothing is drawn: the sampler starts as under the
+ *              ray source.
+ *     3 guard  the final ray is held to the degenerate-ray rule of the ray queries (a word of the origin not finite; the direction's squared length 0 or
+ *              not finite) -- jitter may cancel a direction, focalDistance and the lens offset may cancel.  A degenerate final ray is replaced by the
+ *              entry's stored origin and direction, which the set call checked; the draws stay taken.  No degenerate ray reaches a walk, whatever the offsets.
+ *   while set  as under the ray source (passes under RT_INTEGRATOR_PATH_TRACER_MIS, _PATH_TRACER and _DEBUG, the followers rtgpu_render_aovs*, the chain and
+ *              virtual variants, rtgpu_record_paths, rtgpu_denoise and rtgpu_denoise_var; the same refusals: rtgpu_denoise_temporal*, RT_INTEGRATOR_VCM and
+ *              _LIGHT_TRACER answer RTGPU_ERR_UNSUPPORTED), except that sampleOffset IS read: a sampleOffset that is not finite: RTGPU_ERR_INVALID_ARGUMENT.
+ *              RtPassParams::camera is still neither read nor checked.
+ *   setting    the ray source's life cycle: queued passes are submitted first, lanes, queries and AOV calls are waited for, the table is copied into the
+ *              context's second buffer (128 * width * height bytes each, allocated once per frame size, dropped by rtgpu_resize and with the context) and
+ *              checked there by one read-only kernel (k_lens_source_check) before it replaces anything.  An entry is refused, RTGPU_ERR_INVALID_ARGUMENT,
+ *              if an interpreted word is not finite (the xyz of all eight quads, aperture, focalDistance), if its stored ray is degenerate by the rule above,
+ *              or if, with lens = 1, its focalDistance is not > 0.  The uninterpreted w lanes are never tested.  A refused table leaves the previous
+ *              source -- plain, lens, or the camera -- exactly as it was.  RtLensSourceParams::lens above 1 or bokehShape above 2, a NULL argument, count !=
+ *              width * height: RTGPU_ERR_INVALID_ARGUMENT; before rtgpu_resize: RTGPU_ERR_NOT_READY.
+ *   _device    as rtgpu_set_ray_source_device: device memory of the context's device, 4-byte aligned, whose allocation holds 128 * count bytes from the
+ *              pointer on; ordered behind `stream`; a multi-device context: RTGPU_ERR_UNSUPPORTED (the host entry replicates the table to every device).
+ *   keeps / drops   as the ray source: only rtgpu_resize drops it.  rtgpu_get_ray_source counts the entries of a source of either kind;
+ *              rtgpu_get_ray_source_kind: 0 the camera, 1 a ray source, 2 a lens source.
+ * rtgpu_read_lens_source_rays[_async] write, for every pixel, the final origin and direction a pass with `params` would start from under the lens source
+ * that is set -- the jitter by params->sampleOffset, the lens draws of params' sampler and the guard included -- in RtPrimaryRay's layout, words 3 and 7 zero.
+ * Not a pass: nothing is walked, film, counters and queued passes are untouched.  It is what makes the definition above checkable on its own.  No lens
+ * source set: RTGPU_ERR_NOT_READY; so is a source with lens = 1 under params->useBlueNoise before rtgpu_upload_scene (the draws take the scene's blue noise).
+ * rtgpu_read_camera_footprints[_async] export a camera as a lens table: origin and pinhole direction as Camera::GenerateRay
+ * computes them at params->sampleOffset, dDirection/dsx = r[0] * (2 / width * aspectRatio * tanHalfFoV), dDirection/dsy = r[1] * (2 / height * tanHalfFoV)
+ * (r: the rows of localToWorld; film rows run bottom-up, so d/dsy has the camera's sign), dOrigin = 0, aperture and focalDistance the camera's, lensU = r[0],
+ * lensV = r[1], every uninterpreted w zero.  A camera with dofEnable is accepted -- set the table with lens = 1 and its bokehShape and a pass at the
+ * export's offset renders that camera's frame bit for bit; barrelDistortionVariableFactor != 0: RTGPU_ERR_UNSUPPORTED.  The _async entries take device memory
+ * (16-byte aligned, held to the pointer checks above) on `stream` (NULL: the context's own) and return without synchronising.
+ * --------------------------------------------------------------------------------------------- */
+typedef struct RtLensRay
+{
+    float origin[3];     float aperture;
+    float direction[3];  float focalDistance;
+    float dOriginDsx[3];    float _pad2;
+    float dOriginDsy[3];    float _pad3;
+    float dDirectionDsx[3]; float _pad4;
+    float dDirectionDsy[3]; float _pad5;
+    float lensU[3];      float _pad6;
+    float lensV[3];      float _pad7;
+} RtLensRay;   /* 128 bytes */
+typedef struct RtLensSourceParams { uint32_t lens; uint32_t bokehShape; } RtLensSourceParams;   /* lens: 0 / 1; bokehShape: 0 circle, 1 hexagon, 2 square */
+int rtgpu_set_lens_source(RtgpuContext* ctx, const RtLensRay* rays, uint64_t count, const RtLensSourceParams* params);                        /* host pointer */
+int rtgpu_set_lens_source_device(RtgpuContext* ctx, const RtLensRay* rays, uint64_t count, const RtLensSourceParams* params, void* stream);   /* device pointer */
+int rtgpu_get_ray_source_kind(RtgpuContext* ctx, uint32_t* outKind);                                                                          /* 0 camera, 1 ray source, 2 lens source */
+int rtgpu_read_lens_source_rays(RtgpuContext* ctx, const RtPassParams* params, RtPrimaryRay* out);                       /* host; synchronous */
+int rtgpu_read_lens_source_rays_async(RtgpuContext* ctx, const RtPassParams* params, RtPrimaryRay* out, void* stream);   /* device */
+int rtgpu_read_camera_footprints(RtgpuContext* ctx, const RtPassParams* params, RtLensRay* out);                         /* host; synchronous */
+int rtgpu_read_camera_footprints_async(RtgpuContext* ctx, const RtPassParams* params, RtLensRay* out, void* stream);     /* device */
 
 /* ---------------------------------------------------------------------------------------------
  * Denoise: an edge-avoiding a-trous wavelet filter (Dammertz et al. 2010) over a rendered frame, guided by the first-hit planes

@@ -58,6 +58,13 @@ def rtgpu_lib():
         _rtgpu.rtgpu_get_ray_source.argtypes, _rtgpu.rtgpu_get_ray_source.restype = [C.c_void_p, C.POINTER(C.c_uint64)], C.c_int
         _rtgpu.rtgpu_read_camera_rays.argtypes, _rtgpu.rtgpu_read_camera_rays.restype = [C.c_void_p, C.c_void_p, C.c_void_p], C.c_int
         _rtgpu.rtgpu_read_camera_rays_async.argtypes, _rtgpu.rtgpu_read_camera_rays_async.restype = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p], C.c_int
+        # the lens source: (ctx, rays, count, params[, stream]), (ctx, outKind), (ctx, params, out[, stream])
+        _rtgpu.rtgpu_set_lens_source.argtypes, _rtgpu.rtgpu_set_lens_source.restype = [C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p], C.c_int
+        _rtgpu.rtgpu_set_lens_source_device.argtypes, _rtgpu.rtgpu_set_lens_source_device.restype = [C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p], C.c_int
+        _rtgpu.rtgpu_get_ray_source_kind.argtypes, _rtgpu.rtgpu_get_ray_source_kind.restype = [C.c_void_p, C.POINTER(C.c_uint32)], C.c_int
+        for name in ("rtgpu_read_lens_source_rays", "rtgpu_read_camera_footprints"):
+            getattr(_rtgpu, name).argtypes, getattr(_rtgpu, name).restype = [C.c_void_p, C.c_void_p, C.c_void_p], C.c_int
+            getattr(_rtgpu, name + "_async").argtypes, getattr(_rtgpu, name + "_async").restype = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p], C.c_int
         # known-answer hooks of post-processing: (ctx, params[n], rgb[n * 3], n, outBGR[n], outToneMapped[n * 3] or NULL), (ctx, rgb in place, width, height, sigma)
         _rtgpu.rtgpu_kat_postprocess.argtypes, _rtgpu.rtgpu_kat_postprocess.restype = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p], C.c_int
         _rtgpu.rtgpu_kat_blur.argtypes, _rtgpu.rtgpu_kat_blur.restype = [C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32, C.c_float], C.c_int
@@ -288,6 +295,18 @@ class RtQueryRay(C.Structure):
 class RtPrimaryRay(C.Structure):
     """an entry of a ray source (Viewport.set_ray_source): RtQueryRay's layout, words 3 and 7 never read"""
     _fields_ = [("origin", C.c_float * 3), ("_pad0", C.c_float), ("direction", C.c_float * 3), ("_pad1", C.c_float)]
+
+
+class RtLensRay(C.Structure):
+    """an entry of a lens source (Viewport.set_lens_source): 128 bytes, eight quads; the pads of quads 2..7 are never read"""
+    _fields_ = [("origin", C.c_float * 3), ("aperture", C.c_float), ("direction", C.c_float * 3), ("focalDistance", C.c_float),
+                ("dOriginDsx", C.c_float * 3), ("_pad2", C.c_float), ("dOriginDsy", C.c_float * 3), ("_pad3", C.c_float),
+                ("dDirectionDsx", C.c_float * 3), ("_pad4", C.c_float), ("dDirectionDsy", C.c_float * 3), ("_pad5", C.c_float),
+                ("lensU", C.c_float * 3), ("_pad6", C.c_float), ("lensV", C.c_float * 3), ("_pad7", C.c_float)]
+
+
+class RtLensSourceParams(C.Structure):
+    _fields_ = [("lens", C.c_uint32), ("bokehShape", C.c_uint32)]
 
 
 class RtQueryHit(C.Structure):
@@ -1353,7 +1372,7 @@ class Viewport:
         arrays, origins and directions -- what the builders of raytracer_amd.rays return.  Directions need not be unit length; no origin offset is applied.
         Torch tensors on the renderer's ROCm device go in without a host copy, behind torch.cuda.current_stream().  The table is copied: the arrays may be
         changed at once (set a new table between passes for anti-aliasing; every set call ends the batch in flight: 6.05 ms per pass with a table per pass against
-        2.32 ms on the 1080p Sponza-class frame).  A table with a ray that is not finite
+        2.32 ms on the 1080p Sponza-class frame, DESIGN.md section 5 -- set_lens_source takes ONE table for all passes instead).  A table with a ray that is not finite
         or has a zero direction raises ValueError and leaves the previous source in place.  None clears the source: the camera renders again.  A resize
         drops the source; the camera and sample offset of the pass constants are not read while one is set; denoise(temporal=True), "VCM" and
         "Light Tracer" passes raise."""
@@ -1436,6 +1455,88 @@ class Viewport:
             err = (lib.rtgpu_last_error() or b"").decode()
             raise (ValueError if r == -1 else RuntimeError)("camera_rays failed (%d): %s" % (r, err))
         return out
+
+    # ---- the lens source (include/rtgpu.h: rtgpu_set_lens_source / rtgpu_read_lens_source_rays / rtgpu_read_camera_footprints) ---------------------
+    def set_lens_source(self, table, lens=False, bokeh_shape=0):
+        """Passes along a table of lens rays (rtgpu_set_lens_source): pixel (x, y) of every following pass -- and of render_aovs, record_paths, denoise() and
+        denoise(variance=True) -- starts at the ray table[y, x] describes FOR THAT PASS: the stored ray moved by the pass's sample offset along the
+        entry's footprint and, with lens=True, through the entry's thin lens, its sample drawn from the pass's sampler as the camera draws it.  One table
+        serves every pass: anti-aliasing and depth of field under a source cost no set call.  `table`: an (H, W, 32) float32 array of RtLensRay entries
+        {origin xyz, aperture, direction xyz, focalDistance, dOrigin/dsx, -, dOrigin/dsy, -, dDirection/dsx, -, dDirection/dsy, -, lensU, -, lensV, -} -- what
+        raytracer_amd.rays.footprints and camera_footprints() return -- or a torch tensor on the renderer's ROCm device, taken without a host copy behind
+        torch.cuda.current_stream().  bokeh_shape: 0 circle, 1 hexagon, 2 square.  The table is copied.  A table with a word that is not finite, a zero
+        direction or, under lens=True, a focalDistance that is not > 0 raises ValueError and leaves the previous source (plain, lens or the camera) in
+        place.  It replaces a ray source and is replaced by one; set_ray_source(None) clears it; a resize drops it.  The camera of the pass constants is
+        not read while it is set, their sample offset is; denoise(temporal=True), "VCM" and "Light Tracer" passes raise."""
+        lib = rtgpu_lib()
+        ctx = self._ray_source_context("set_lens_source")
+        h, w = self.height, self.width
+        params = RtLensSourceParams(1 if lens else 0, int(bokeh_shape))
+        if type(table).__module__.split(".")[0] == "torch":
+            import torch
+            if not isinstance(table, torch.Tensor) or table.dtype != torch.float32 or tuple(table.shape) != (h, w, 32):
+                raise ValueError("the lens table must be an (H, W, 32) float32 tensor of the viewport's size")
+            if not table.is_cuda:
+                raise ValueError("the tensor must live on the renderer's ROCm device")
+            device = table.device
+            if (device.index if device.index is not None else torch.cuda.current_device()) != multi_info(ctx)["devices"][0]:
+                raise ValueError("the tensor must live on the renderer's device (cuda:%d)" % multi_info(ctx)["devices"][0])
+            table = table.contiguous()
+            r = _run_on_torch_stream(torch, self._query_streams, device, (table,), lambda stream: lib.rtgpu_set_lens_source_device(
+                ctx, C.c_void_p(table.data_ptr()), C.c_uint64(h * w), C.byref(params), stream))
+        else:
+            if not isinstance(table, np.ndarray) or table.dtype != np.float32 or table.shape != (h, w, 32):
+                raise ValueError("the lens table must be an (H, W, 32) float32 NumPy array of the viewport's size (or a torch tensor)")
+            table = np.ascontiguousarray(table)
+            r = lib.rtgpu_set_lens_source(ctx, table.ctypes.data_as(C.c_void_p), C.c_uint64(h * w), C.byref(params))
+        if r != 0:
+            err = (lib.rtgpu_last_error() or b"").decode()
+            raise (ValueError if r == -1 else RuntimeError)("set_lens_source failed (%d): %s" % (r, err))
+
+    def ray_source_kind(self):
+        """What the passes start from (rtgpu_get_ray_source_kind): 0 the camera, 1 a ray source, 2 a lens source."""
+        kind = C.c_uint32(0)
+        if not self.has_renderer or not self.device_context().value:
+            return 0
+        if rtgpu_lib().rtgpu_get_ray_source_kind(self.device_context(), C.byref(kind)) != 0:
+            raise RuntimeError("rtgpu_get_ray_source_kind failed: %s" % (rtgpu_lib().rtgpu_last_error() or b"").decode())
+        return int(kind.value)
+
+    def _lens_export(self, what, entry, words, params, device):
+        if not isinstance(params, RtPassParams):
+            raise TypeError("%s takes the RtPassParams of next_pass_params(camera), not %s" % (what, type(params).__name__))
+        lib = rtgpu_lib()
+        ctx = self._ray_source_context(what)
+        if not device:
+            out = np.zeros((self.height, self.width, words), dtype=np.float32)
+            r = getattr(lib, entry)(ctx, C.byref(params), out.ctypes.data_as(C.c_void_p))
+        else:
+            import torch
+            dev = torch.device("cuda", multi_info(ctx)["devices"][0])
+            out = torch.empty((self.height, self.width, words), dtype=torch.float32, device=dev)
+            r = _run_on_torch_stream(torch, self._query_streams, dev, (out,), lambda stream: getattr(lib, entry + "_async")(
+                ctx, C.byref(params), C.c_void_p(out.data_ptr()), stream))
+        if r != 0:
+            err = (lib.rtgpu_last_error() or b"").decode()
+            raise (ValueError if r == -1 else RuntimeError)("%s failed (%d): %s" % (what, r, err))
+        return out
+
+    def camera_footprints(self, params, device=False):
+        """The camera of the pass `params` as a lens table (rtgpu_read_camera_footprints): an (H, W, 32) float32 array of RtLensRay entries -- the camera's
+        origin and pinhole direction at params.sampleOffset, the direction's analytic change per unit sample offset, the camera's aperture, focal distance
+        and lens axes -- or, device=True, a torch tensor on the renderer's ROCm device written on torch.cuda.current_stream().  Not a pass.  A camera
+        with depth of field is accepted: set the table with lens=True and the camera's bokeh shape and a pass at the export's offset renders the camera's
+        own frame bit for bit.  A variable barrel factor raises."""
+        return self._lens_export("camera_footprints", "rtgpu_read_camera_footprints", 32, params, device)
+
+    def lens_source_rays(self, params, device=False):
+        """The primary rays a pass with `params` would start from under the lens source that is set (rtgpu_read_lens_source_rays): jitter by
+        params.sampleOffset, the lens draws of the pass's sampler and the degenerate-ray guard included, as an (H, W, 8) float32 array in set_ray_source's
+        layout {origin xyz, 0, direction xyz (not normalised), 0}; device=True: a torch tensor.  Not a pass: nothing is walked."""
+        ctx = self._ray_source_context("lens_source_rays")
+        if host_lib().rth_viewport_upload_scene(self._h) != 0:   # (the lens draws take the scene's blue noise, as a pass's do)
+            raise RuntimeError("the viewport's scene could not be uploaded: %s" % (rtgpu_lib().rtgpu_last_error() or b"").decode())
+        return self._lens_export("lens_source_rays", "rtgpu_read_lens_source_rays", 8, params, device)
 
     # ---- path records (include/rtgpu.h: rtgpu_record_paths) ------------------------------------------------------------------------------
     def record_paths(self, params, pixels, max_vertices=None):

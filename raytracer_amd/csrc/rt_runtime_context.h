@@ -377,6 +377,14 @@ struct RtgpuContext
         uint32_t* degenerate = nullptr;           // what k_ray_source_check counted
         float4* exported = nullptr; size_t exportedEntries = 0;   // rtgpu_read_camera_rays' device copy
         hipEvent_t order = nullptr;               // rtgpu_set_ray_source_device: puts the copy behind the caller's stream
+        // the lens source (rtgpu_set_lens_source): the same pair of buffers for entries of eight float4 (RtLensRay).  One context holds one source: at most
+        // one of `table` and `lensTable` is set, and setting either kind hands the other's buffer back to its `incoming`.
+        float4* lensTable = nullptr;              // null: the plain table, or the camera
+        float4* lensIncoming = nullptr;
+        uint32_t lens = 0u, bokehShape = 0u;      // RtLensSourceParams of lensTable
+        hipEvent_t lensRead = nullptr;            // behind the last rtgpu_read_lens_source_rays_async on a caller's stream: it reads lensTable
+        float4* lensExported = nullptr; size_t lensExportedBytes = 0;   // the device copy of rtgpu_read_lens_source_rays and rtgpu_read_camera_footprints
+        bool any() const { return table || lensTable; }   // a source of either kind: the camera is not read
     } raySource;
 
     // timing
@@ -568,15 +576,18 @@ static int callerDeviceArray(const RtgpuContext* c, const void* p, size_t bytes,
 }
 
 // the ray source's tables (the caller has waited for whatever reads them): the camera renders again
-static void dropRaySource(RtgpuContext* c) { devFree(c->raySource.table, c->raySource.incoming); }
+static void waitLensExport(RtgpuContext* c) { if (c->raySource.lensRead) (void)hipEventSynchronize(c->raySource.lensRead); }
+static void dropRaySource(RtgpuContext* c) { waitLensExport(c); devFree(c->raySource.table, c->raySource.incoming, c->raySource.lensTable, c->raySource.lensIncoming); }
 static void freeRaySource(RtgpuContext* c)
 {
     RtgpuContext::RaySource& s = c->raySource;
     dropRaySource(c);
-    devFree(s.degenerate, s.exported);
-    s.exportedEntries = 0;
+    devFree(s.degenerate, s.exported, s.lensExported);
+    s.exportedEntries = 0; s.lensExportedBytes = 0;
     if (s.order) (void)hipEventDestroy(s.order);
     s.order = nullptr;
+    if (s.lensRead) (void)hipEventDestroy(s.lensRead);
+    s.lensRead = nullptr;
 }
 
 static void freeRecorder(RtgpuContext* c)

@@ -15,6 +15,14 @@ static int raySourceBuffers(RtgpuContext* c, size_t entries)
     return RTGPU_OK;
 }
 
+// The other kind's table after a set call succeeded (everything that read it has been waited for): it becomes that kind's spare buffer, or goes.
+static void raySourceRetire(float4*& table, float4*& incoming)
+{
+    if (!table) return;
+    if (!incoming) { incoming = table; table = nullptr; }
+    else devFree(table);
+}
+
 // k_ray_source_check over raySource.incoming on `stream`, read back; then the swap, or the refusal that leaves the source as it was
 static int raySourceCheckAndSwap(RtgpuContext* c, uint32_t entries, hipStream_t stream)
 {
@@ -31,11 +39,12 @@ static int raySourceCheckAndSwap(RtgpuContext* c, uint32_t entries, hipStream_t 
         return fail(RTGPU_ERR_INVALID_ARGUMENT, std::to_string(degenerate) + " entries of the table are degenerate rays (an origin or direction word that is not finite, a zero direction)");
     float4* const previous = s.table;
     s.table = s.incoming; s.incoming = previous;
+    raySourceRetire(s.lensTable, s.lensIncoming);   // one context holds one source: a lens source ends here
     return RTGPU_OK;
 }
 
 // what both entries check and wait for before the copy; `clear`: the call clears the source and is done
-static int raySourceBegin(RtgpuContext* c, const RtPrimaryRay* rays, uint64_t count, bool& clear)
+static int raySourceBegin(RtgpuContext* c, const void* rays, uint64_t count, bool& clear)
 {
     clear = false;
     if (!rays && count != 0u) return fail(RTGPU_ERR_INVALID_ARGUMENT, "rays is NULL");
@@ -46,6 +55,7 @@ static int raySourceBegin(RtgpuContext* c, const RtPrimaryRay* rays, uint64_t co
     { int fr = flushQueued(c); if (fr) return fr; }   // the queued passes render the source they were queued under
     HIP_TRY(syncLanes(c));
     waitQueries(c);                                   // (AOV calls on a caller's stream read the table too)
+    waitLensExport(c);                                // (and rtgpu_read_lens_source_rays_async reads a lens table)
     if (!rays) { dropRaySource(c); clear = true; }
     return RTGPU_OK;
 }
@@ -87,7 +97,7 @@ RTGPU_API int rtgpu_set_ray_source_device(RtgpuContext* c, const RtPrimaryRay* r
 RTGPU_API int rtgpu_get_ray_source(RtgpuContext* c, uint64_t* outCount)
 {
     if (!c || !outCount) return fail(RTGPU_ERR_INVALID_ARGUMENT, "NULL argument");
-    *outCount = c->raySource.table ? (uint64_t)c->width * c->height : 0u;
+    *outCount = c->raySource.any() ? (uint64_t)c->width * c->height : 0u;   // (a source of either kind: rtgpu_get_ray_source_kind tells them apart)
     return RTGPU_OK;
 }
 

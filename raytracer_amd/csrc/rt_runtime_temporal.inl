@@ -431,7 +431,7 @@ static int denoiseTemporalFrame(RtgpuContext* c, const RtTemporalParams* t, cons
     int r = checkTemporalParams(t, false); if (r) return r;
     if (v) { r = checkDenoiseVarParams(v); if (r) return r; }
     if (clip) { r = checkTemporalClip(clip); if (r) return r; }
-    if (c->raySource.table) return fail(RTGPU_ERR_UNSUPPORTED, "temporal accumulation reprojects through the camera's worldToScreen, and a ray source has none: clear it, or call rtgpu_temporal_accumulate on planes of your own");
+    if (c->raySource.any()) return fail(RTGPU_ERR_UNSUPPORTED, "temporal accumulation reprojects through the camera's worldToScreen, and a ray source has none: clear it, or call rtgpu_temporal_accumulate on planes of your own");
     // (before anything is submitted or the history touched) reprojecting a reflection needs the virtual motion of the mirrored point
     if (chained)
     {

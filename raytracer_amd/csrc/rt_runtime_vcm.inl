@@ -297,7 +297,7 @@ static int vcmRenderPass(RtgpuContext* c, const RtPassParams* p)
 {
     RtgpuContext::Vcm& v = c->vcm;
     if (const int r = vcmRefusals(c)) return r;
-    if (c->raySource.table) return fail(RTGPU_ERR_UNSUPPORTED, "VCM splats through Camera::WorldToFilm: clear the ray source (rtgpu_set_ray_source(ctx, NULL, 0))");
+    if (c->raySource.any()) return fail(RTGPU_ERR_UNSUPPORTED, "VCM splats through Camera::WorldToFilm: clear the ray source (rtgpu_set_ray_source(ctx, NULL, 0))");
     if (p->passIndex == 0u && !v.pending.empty()) { const int r = vcmFlush(c); if (r) return r; }   // a restart begins its own batch
     if (v.pending.empty())
     {
@@ -324,7 +324,7 @@ static int lightTracerRenderPass(RtgpuContext* c, const RtPassParams* p)
 {
     RtgpuContext::Vcm& v = c->vcm;
     if (const int r = refusePartialFrame(c, "the Light Tracer")) return r;
-    if (c->raySource.table) return fail(RTGPU_ERR_UNSUPPORTED, "the Light Tracer splats through Camera::WorldToFilm: clear the ray source (rtgpu_set_ray_source(ctx, NULL, 0))");
+    if (c->raySource.any()) return fail(RTGPU_ERR_UNSUPPORTED, "the Light Tracer splats through Camera::WorldToFilm: clear the ray source (rtgpu_set_ray_source(ctx, NULL, 0))");
     if (p->maxRayDepth + 2u > RT_VCM_COUNT_PLANE) return fail(RTGPU_ERR_UNSUPPORTED, "Light Tracer: maxRayDepth must be <= 18");
     { int r = flushPending(c); if (r) return r; }
     HIP_TRY(syncLanes(c));

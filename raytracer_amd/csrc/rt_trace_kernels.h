@@ -157,5 +157,16 @@ __global__ void __launch_bounds__(RT_BLOCK) k_generate_rays(const RtSceneDesc sc
                                                             unsigned long long* counters, const float4* __restrict__ rays);
 __global__ void __launch_bounds__(RT_BLOCK) k_ray_source_check(const float4* __restrict__ rays, uint32_t count, uint32_t* __restrict__ outDegenerate);
 __global__ void __launch_bounds__(RT_BLOCK) k_camera_rays(const RtCamera camera, float sampleOffsetX, float sampleOffsetY, uint32_t width, uint32_t height, float4* __restrict__ out);
+// the lens source (rt_lenssource.inl): k_generate behind a table of lens rays; the table's check; the rays of a pass and the camera's footprints written out
+__global__ void __launch_bounds__(RT_BLOCK) k_generate_lens(const RtSceneDesc scene, const DevPass* __restrict__ passes, uint32_t slotsPerPass,
+                                                            const Paths paths, const uint32_t* __restrict__ slotPixel, uint32_t numSlots,
+                                                            uint32_t* __restrict__ queue, uint32_t* __restrict__ queueCount,
+                                                            unsigned long long* counters, const float4* __restrict__ table, uint32_t lens, uint32_t bokehShape);
+__global__ void __launch_bounds__(RT_BLOCK) k_lens_source_check(const float4* __restrict__ table, uint32_t count, uint32_t lens, uint32_t* __restrict__ outRefused);
+__global__ void __launch_bounds__(RT_BLOCK) k_lens_source_rays(const float4* __restrict__ table, uint32_t width, uint32_t height, float sx, float sy, uint32_t lens,
+                                                               uint32_t bokehShape, uint32_t seed0, uint32_t seed1, uint32_t numDims, uint32_t blueNoiseLayers,
+                                                               const uint16_t* __restrict__ blueNoise, unsigned long long rngKey0, unsigned long long rngKey1,
+                                                               float4* __restrict__ out);
+__global__ void __launch_bounds__(RT_BLOCK) k_camera_footprints(const RtCamera camera, float sampleOffsetX, float sampleOffsetY, uint32_t width, uint32_t height, float4* __restrict__ out);
 __global__ void __launch_bounds__(RT_MONSTER_BLOCK) k_trace_monster(const RtSceneDesc scene, const Paths paths, const uint32_t* __restrict__ queue, const uint32_t* __restrict__ queueCount);
 #endif

@@ -62,6 +62,10 @@ public:
     // pixel (x, y) of the sum buffer -- instead of the camera's, whose part of Render()'s constants is then not read.  nullptr with count 0: the camera
     // again.  The table is copied.  Resize and SetRenderer drop it (a table is a frame's, and it lives in the renderer's device context).
     bool SetRaySource(const RtPrimaryRay* rays, size_t count);
+    // Extension (rtgpu_set_lens_source): the same with a table of lens rays -- each entry a ray, its change per unit of the pass's sample offset and a thin
+    // lens -- so that Render()'s anti-aliasing offsets and, with params.lens, depth of field apply to the caller's rays pass after pass without a new
+    // table.  Of Render()'s constants the sample offset is then read, the camera is not.  Replaces a ray source; SetRaySource(nullptr, 0) clears it.
+    bool SetLensSource(const RtLensRay* rays, size_t count, const RtLensSourceParams& params);
 
     // The per-pass constants Render() would use next; advances the Halton sequence and the generator
     // exactly like Render().  Exposed so parity tests can feed identical constants to the CPU oracle.

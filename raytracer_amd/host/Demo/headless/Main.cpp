@@ -7,8 +7,9 @@
 // and --denoise-variance [N] (the same through the variance-guided filter over the film's two sum buffers: rtgpu_denoise_var),
 // --guide-chain N beside either (the filter's guides follow every pixel's path through up to N mirror and glass vertices: rtgpu_set_guide_chain);
 // --projection orthographic|panorama|fisheye (the frame is rendered along a table of primary rays built here from the scene file's camera transform, in
-// place of the perspective camera: Viewport::SetRaySource; --projection-size S: the orthographic picture is 2 S world units wide, --projection-fov D: the
-// fisheye's image circle spans D degrees; --denoise and --denoise-variance work with it: their guides follow the table);
+// place of the perspective camera: Viewport::SetLensSource, so the viewport's anti-aliasing applies to it; --projection-size S: the orthographic picture is 2 S world units wide, --projection-fov D: the
+// fisheye's image circle spans D degrees; --aperture A --focal-distance F [--bokeh circle|hexagon|square]: the projection's rays pass a thin lens of radius A
+// focused F along each ray; --denoise and --denoise-variance work with it: their guides follow the table);
 // the environment variable RTGPU_DEVICES ("0,1,2,3" / "all") spreads the frame over several GPUs (Core/Rendering/Renderer.h).
 #include "../Demo.h"
 #include "../SceneLoader.h"
@@ -116,45 +117,73 @@ static bool DenoisedFrontBuffer(Viewport& viewport, const Camera& camera, IRende
     return true;
 }
 
-// The table of --projection: one primary ray per pixel, row 0 the top of the picture, from the camera's transform (rows: right, up, forward, position).
-// orthographic: parallel rays along forward, the picture 2 * size wide; panorama: equirectangular, the centre column looks forward and the rows sweep from
-// straight up to straight down; fisheye: equidistant, fovDegrees across the circle inscribed in the shorter side, the axis ray outside it.
-static std::vector<RtPrimaryRay> ProjectionTable(const std::string& projection, const RtCamera& camera, uint32 width, uint32 height, double size, double fovDegrees)
+// The table of --projection: one lens ray per pixel (RtLensRay), row 0 the top of the picture, from the camera's transform (rows: right, up, forward,
+// position).  orthographic: parallel rays along forward, the picture 2 * size wide; panorama: equirectangular, the centre column looks forward and the rows
+// sweep from straight up to straight down; fisheye: equidistant, fovDegrees across the circle inscribed in the shorter side, the axis ray outside it.
+// The stored ray is the projection's at the pixel's centre; its footprint -- what the viewport's anti-aliasing offset moves it by, per pixel of offset -- is
+// the projection's own central difference over the pixel ((ray at +1/2) - (ray at -1/2), x to the right, y up); the lens plane is spanned by U = up x d,
+// normalised, and V = d x U (orthographic: right and up; at a direction parallel to up: U = right), its aperture and focal distance the caller's.
+static std::vector<RtLensRay> ProjectionTable(const std::string& projection, const RtCamera& camera, uint32 width, uint32 height, double size, double fovDegrees,
+                                              double aperture, double focalDistance)
 {
     const double pi = 3.14159265358979323846;
     const float* m = camera.localToWorld;
     const double right[3] = { m[0], m[1], m[2] }, up[3] = { m[4], m[5], m[6] }, forward[3] = { m[8], m[9], m[10] }, position[3] = { m[12], m[13], m[14] };
-    std::vector<RtPrimaryRay> table((size_t)width * height);
+    std::vector<RtLensRay> table((size_t)width * height);
     const double shorter = width < height ? width : height;
+    // the projection's ray through pixel (x, y) at sample offset (sx, sy) from its centre
+    auto rayAt = [&](uint32 x, uint32 y, double sx, double sy, double o[3], double d[3])
+    {
+        const double u = (x + 0.5 + sx) / width, v = (height - 1u - y + 0.5 + sy) / height;   // film coordinates: v up
+        for (int k = 0; k < 3; ++k) o[k] = position[k];
+        double cr = 0.0, cu = 0.0, cf = 1.0;   // the direction's coordinates along right, up, forward
+        if (projection == "orthographic")
+        {
+            const double px = (2.0 * u - 1.0) * size, py = (2.0 * v - 1.0) * size * height / width;
+            for (int k = 0; k < 3; ++k) o[k] += px * right[k] + py * up[k];
+        }
+        else if (projection == "panorama")
+        {
+            const double azimuth = (u - 0.5) * 2.0 * pi, elevation = (v - 0.5) * pi;
+            cf = cos(elevation) * cos(azimuth); cr = cos(elevation) * sin(azimuth); cu = sin(elevation);
+        }
+        else   // fisheye
+        {
+            const double px = (2.0 * u - 1.0) * width / shorter, py = (2.0 * v - 1.0) * height / shorter, r = sqrt(px * px + py * py);
+            if (r > 0.0 && r <= 1.0)
+            {
+                const double theta = r * 0.5 * fovDegrees * pi / 180.0;
+                cf = cos(theta); cr = sin(theta) * px / r; cu = sin(theta) * py / r;
+            }
+        }
+        for (int k = 0; k < 3; ++k) d[k] = cr * right[k] + cu * up[k] + cf * forward[k];
+    };
+    auto cross = [](const double a[3], const double b[3], double out[3]) { out[0] = a[1] * b[2] - a[2] * b[1]; out[1] = a[2] * b[0] - a[0] * b[2]; out[2] = a[0] * b[1] - a[1] * b[0]; };
+    auto normalise = [](double a[3]) { const double l = sqrt(a[0] * a[0] + a[1] * a[1] + a[2] * a[2]); if (l > 0.0) for (int k = 0; k < 3; ++k) a[k] /= l; return l; };
     for (uint32 y = 0; y < height; ++y)
         for (uint32 x = 0; x < width; ++x)
         {
-            const double u = (x + 0.5) / width, v = (height - 1u - y + 0.5) / height;   // film coordinates: v up
-            double o[3] = { position[0], position[1], position[2] }, d[3];
-            double cr = 0.0, cu = 0.0, cf = 1.0;   // the direction's coordinates along right, up, forward
-            if (projection == "orthographic")
-            {
-                const double px = (2.0 * u - 1.0) * size, py = (2.0 * v - 1.0) * size * height / width;
-                for (int k = 0; k < 3; ++k) o[k] += px * right[k] + py * up[k];
-            }
-            else if (projection == "panorama")
-            {
-                const double azimuth = (u - 0.5) * 2.0 * pi, elevation = (v - 0.5) * pi;
-                cf = cos(elevation) * cos(azimuth); cr = cos(elevation) * sin(azimuth); cu = sin(elevation);
-            }
-            else   // fisheye
-            {
-                const double px = (2.0 * u - 1.0) * width / shorter, py = (2.0 * v - 1.0) * height / shorter, r = sqrt(px * px + py * py);
-                if (r > 0.0 && r <= 1.0)
-                {
-                    const double theta = r * 0.5 * fovDegrees * pi / 180.0;
-                    cf = cos(theta); cr = sin(theta) * px / r; cu = sin(theta) * py / r;
-                }
-            }
-            for (int k = 0; k < 3; ++k) d[k] = cr * right[k] + cu * up[k] + cf * forward[k];
-            RtPrimaryRay& ray = table[(size_t)y * width + x];
+            double o[3], d[3], op[3], dp[3], om[3], dm[3];
+            RtLensRay& ray = table[(size_t)y * width + x];
             memset(&ray, 0, sizeof(ray));
+            rayAt(x, y, 0.0, 0.0, o, d);
             for (int k = 0; k < 3; ++k) { ray.origin[k] = (float)o[k]; ray.direction[k] = (float)d[k]; }
+            rayAt(x, y, 0.5, 0.0, op, dp); rayAt(x, y, -0.5, 0.0, om, dm);
+            for (int k = 0; k < 3; ++k) { ray.dOriginDsx[k] = (float)(op[k] - om[k]); ray.dDirectionDsx[k] = (float)(dp[k] - dm[k]); }
+            rayAt(x, y, 0.0, 0.5, op, dp); rayAt(x, y, 0.0, -0.5, om, dm);
+            for (int k = 0; k < 3; ++k) { ray.dOriginDsy[k] = (float)(op[k] - om[k]); ray.dDirectionDsy[k] = (float)(dp[k] - dm[k]); }
+            double unit[3] = { d[0], d[1], d[2] }, lensU[3], lensV[3];
+            normalise(unit);
+            cross(up, unit, lensU);
+            if (normalise(lensU) < 1e-6)   // d along up: the right axis, its part along d removed
+            {
+                const double along = right[0] * unit[0] + right[1] * unit[1] + right[2] * unit[2];
+                for (int k = 0; k < 3; ++k) lensU[k] = right[k] - along * unit[k];
+                normalise(lensU);
+            }
+            cross(unit, lensU, lensV);
+            for (int k = 0; k < 3; ++k) { ray.lensU[k] = (float)lensU[k]; ray.lensV[k] = (float)lensV[k]; }
+            ray.aperture = (float)aperture; ray.focalDistance = (float)focalDistance;
         }
     return table;
 }
@@ -167,6 +196,7 @@ int main(int argc, char* argv[])
     std::string scenePath, rendererName = "Path Tracer MIS", output = "out.bmp";
     unsigned long long seed = 0; bool haveSeed = false;
     std::string projection; double projectionSize = 5.0, projectionFov = 180.0;
+    double lensAperture = 0.0, lensFocalDistance = 1.0; bool haveLens = false; uint32 lensBokeh = 0;
     for (int i = 1; i < argc; ++i)
     {
         const std::string a = argv[i];
@@ -200,9 +230,19 @@ int main(int argc, char* argv[])
         }
         else if (a == "--projection-size") { projectionSize = atof(value("--projection-size")); if (!(projectionSize > 0.0)) { fprintf(stderr, "--projection-size takes a positive half width\n"); return 2; } }
         else if (a == "--projection-fov") { projectionFov = atof(value("--projection-fov")); if (!(projectionFov > 0.0 && projectionFov <= 360.0)) { fprintf(stderr, "--projection-fov takes 0..360 degrees\n"); return 2; } }
-        else { fprintf(stderr, "usage: rt_demo -s scene.json [--data dir/] [-w W] [-h H] [--passes N] [--depth D] [--renderer name] [--output out.bmp] [--seed N] [--debug-pixel X,Y] [--denoise [N]] [--denoise-variance [N]] [--guide-chain N] [--projection orthographic|panorama|fisheye] [--projection-size S] [--projection-fov DEGREES]\n"); return 2; }
+        else if (a == "--aperture") { lensAperture = atof(value("--aperture")); haveLens = true; if (!(lensAperture >= 0.0)) { fprintf(stderr, "--aperture takes a lens radius >= 0\n"); return 2; } }
+        else if (a == "--focal-distance") { lensFocalDistance = atof(value("--focal-distance")); haveLens = true; if (!(lensFocalDistance > 0.0)) { fprintf(stderr, "--focal-distance takes a positive distance\n"); return 2; } }
+        else if (a == "--bokeh")
+        {
+            const std::string shape = value("--bokeh");
+            haveLens = true;
+            if (shape == "circle") lensBokeh = 0; else if (shape == "hexagon") lensBokeh = 1; else if (shape == "square") lensBokeh = 2;
+            else { fprintf(stderr, "--bokeh takes circle, hexagon or square\n"); return 2; }
+        }
+        else { fprintf(stderr, "usage: rt_demo -s scene.json [--data dir/] [-w W] [-h H] [--passes N] [--depth D] [--renderer name] [--output out.bmp] [--seed N] [--debug-pixel X,Y] [--denoise [N]] [--denoise-variance [N]] [--guide-chain N] [--projection orthographic|panorama|fisheye] [--projection-size S] [--projection-fov DEGREES] [--aperture A] [--focal-distance F] [--bokeh circle|hexagon|square]\n"); return 2; }
     }
     if (guideChain >= 0 && !denoiseLevels) { fprintf(stderr, "--guide-chain steers the denoiser's guides: it needs --denoise or --denoise-variance\n"); return 2; }
+    if (haveLens && projection.empty()) { fprintf(stderr, "--aperture, --focal-distance and --bokeh give a --projection its thin lens (the scene file sets the perspective camera's)\n"); return 2; }
     if (scenePath.empty()) { fprintf(stderr, "no scene given (-s scene.json)\n"); return 2; }
 
     Scene scene;
@@ -224,9 +264,12 @@ int main(int argc, char* argv[])
     {
         RtCamera desc;
         if (!camera.GetDesc(desc)) return 1;
-        const std::vector<RtPrimaryRay> table = ProjectionTable(projection, desc, width, height, projectionSize, projectionFov);
-        if (!viewport.SetRaySource(table.data(), table.size())) return 1;
+        // one lens table for the whole run: the viewport's anti-aliasing offsets and the lens draws are applied to it on the device, pass after pass
+        const std::vector<RtLensRay> table = ProjectionTable(projection, desc, width, height, projectionSize, projectionFov, lensAperture, lensFocalDistance);
+        const RtLensSourceParams lens = { haveLens ? 1u : 0u, lensBokeh };
+        if (!viewport.SetLensSource(table.data(), table.size(), lens)) return 1;
         printf("projection: %s, %zu primary rays from the scene's camera transform\n", projection.c_str(), table.size());
+        if (haveLens) printf("lens: aperture %g, focal distance %g, bokeh shape %u\n", lensAperture, lensFocalDistance, lensBokeh);
     }
 
     const auto t0 = std::chrono::steady_clock::now();

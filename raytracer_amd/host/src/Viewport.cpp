@@ -546,6 +546,18 @@ bool Viewport::SetRaySource(const RtPrimaryRay* rays, size_t count)
     return true;
 }
 
+bool Viewport::SetLensSource(const RtLensRay* rays, size_t count, const RtLensSourceParams& params)
+{
+    PathTracerMIS* renderer = dynamic_cast<PathTracerMIS*>(mRenderer.get());
+    if (!renderer || !renderer->GetDeviceContext()) return false;
+    if (rtgpu_set_lens_source(renderer->GetDeviceContext(), rays, (uint64_t)count, &params) != RTGPU_OK)
+    {
+        fprintf(stderr, "[rt] ERROR: cannot set the lens source: %s\n", rtgpu_last_error());
+        return false;
+    }
+    return true;
+}
+
 bool Viewport::SetRenderingParams(const RenderingParams& params)
 {
     if (params.maxRayDepth >= 255u || params.antiAliasingSpread < 0.0f) return false;

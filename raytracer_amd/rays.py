@@ -10,7 +10,9 @@ right, row 1 up, row 2 forward, row 3 is the position.  Anything np.asarray turn
 ``sample_offset = (sx, sy)`` moves the sample inside the pixel, in pixels, x to the right and y up, from the pixel's centre.  For anti-aliasing draw a new
 offset per pass and set the table again between passes; each set call ends the batch of passes in flight, so a pass then rides through the launch sequence
 alone: measured on the 1080p Sponza-class frame, 6.05 ms per pass with a table set before every pass against 2.32 ms from one table (DESIGN.md section 5,
-"Ray source").  Setting a table every few passes keeps most of the batching.
+"Ray source").  ``footprints`` below is the way around that: it turns a builder into a LENS table (Viewport.set_lens_source), which carries every ray's
+change per unit of the pass's sample offset -- and a thin lens -- so that one table serves every pass, jittered on the device (DESIGN.md section 5,
+"Lens source").
 """
 import numpy as np
 
@@ -137,3 +139,56 @@ def hemisphere_probe(points, normals, n, sample_offset=(0.0, 0.0), offset=1e-3):
     directions = directions / np.sqrt(np.einsum("...k,...k->...", directions, directions))[..., None]
     origins = np.broadcast_to((points + nz * float(offset))[:, None, :], directions.shape)
     return _out(origins, directions)
+
+
+def _lens_axes(directions, right, up):
+    """The lens plane of each direction: U = up x d, normalised, and V = d x U -- a unit pair perpendicular to d that turns into (right, up) where d is the
+    transform's forward axis.  Where d is parallel to up (the poles of a panorama: |up x d| < 1e-6) U is the right axis with its part along d removed."""
+    d = directions / np.sqrt(np.einsum("...k,...k->...", directions, directions))[..., None]
+    u = np.cross(np.broadcast_to(up, d.shape), d)
+    length = np.sqrt(np.einsum("...k,...k->...", u, u))
+    fallback = right - np.einsum("...k,k->...", d, right)[..., None] * d
+    u = np.where((length < 1e-6)[..., None], fallback, u)
+    u = u / np.sqrt(np.einsum("...k,...k->...", u, u))[..., None]
+    return u, np.cross(d, u)
+
+
+def footprints(builder, *args, aperture=0.0, focal_distance=1.0, **kw):
+    """A lens table for Viewport.set_lens_source from one of the builders above (orthographic, panorama, fisheye): ``footprints(panorama, w, h, transform)``
+    returns an (height, width, 32) float32 array of RtLensRay entries.
+      stored ray    the builder's ray at sample offset (0, 0)
+      derivatives   the builder's own central differences per unit offset, (builder(+1/2) - builder(-1/2)) along x and along y: exact for orthographic,
+                    whose rays are linear in the offset; for the angular builders the first-order footprint, whose direction at offset o (before it is
+                    normalised) is off the builder's by an angle of second order, below (|o| * theta)^2 with theta the angle between neighbouring pixels
+                    (a fisheye pixel whose samples straddle the image circle has no derivative: its footprint is the jump's difference)
+      lens axes     orthographic: the transform's right and up axes, normalised; panorama and fisheye: per pixel U = up x d normalised, V = d x U (at a
+                    direction parallel to up: U = right with its part along d removed) -- unit length and perpendicular to the stored direction
+      aperture, focal_distance   scalars or (height, width) arrays: the lens radius in world units and the distance along the (unit) direction at which the
+                    picture is sharp; they take effect when the table is set with lens=True
+    ``sample_offset`` is not accepted: the pass's offset is applied on the device."""
+    if builder not in (orthographic, panorama, fisheye):
+        raise ValueError("footprints takes orthographic, panorama or fisheye")
+    if "sample_offset" in kw:
+        raise ValueError("a lens table is built at offset 0: the pass's sample offset is applied on the device")
+    o0, d0 = builder(*args, sample_offset=(0.0, 0.0), **kw)
+    height, width = o0.shape[:2]
+    table = np.zeros((height, width, 32), dtype=np.float32)
+    table[..., 0:3], table[..., 4:7] = o0, d0
+    for axis, (ko, kd) in enumerate(((8, 16), (12, 20))):
+        plus = builder(*args, sample_offset=(0.5, 0.0) if axis == 0 else (0.0, 0.5), **kw)
+        minus = builder(*args, sample_offset=(-0.5, 0.0) if axis == 0 else (0.0, -0.5), **kw)
+        table[..., ko:ko + 3] = plus[0].astype(np.float64) - minus[0].astype(np.float64)
+        table[..., kd:kd + 3] = plus[1].astype(np.float64) - minus[1].astype(np.float64)
+    transform = kw["transform"] if "transform" in kw else args[2]
+    right, up, _, _ = _axes(transform)
+    if builder is orthographic:
+        lens_u = np.broadcast_to(right / np.sqrt(np.dot(right, right)), d0.shape)
+        lens_v = np.broadcast_to(up / np.sqrt(np.dot(up, up)), d0.shape)
+    else:
+        lens_u, lens_v = _lens_axes(d0.astype(np.float64), right, up)
+    table[..., 24:27], table[..., 28:31] = lens_u, lens_v
+    table[..., 3] = np.broadcast_to(np.asarray(aperture, dtype=np.float32), (height, width))
+    table[..., 7] = np.broadcast_to(np.asarray(focal_distance, dtype=np.float32), (height, width))
+    if not np.isfinite(table).all():
+        raise ValueError("the lens table is not finite")
+    return table

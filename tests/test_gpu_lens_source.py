@@ -1,0 +1,547 @@
+"""The lens source on the device (include/rtgpu.h: rtgpu_set_lens_source, rtgpu_read_lens_source_rays, rtgpu_read_camera_footprints; Viewport.set_lens_source /
+lens_source_rays / camera_footprints): passes, AOVs, path records and the denoisers along a table of rays with footprints and a thin lens.
+
+Bar: BIT-EQUAL words everywhere ("same": every word of sum and secondary sum, every counter).  The jitter step is defined operation by operation and
+tests/lens_source_ref.py performs the same float32 operations; the lens step is the camera's own code on the camera's own values; everything behind the
+primary ray is the code every pass runs.  There is no tolerance to state.  The CPU side: tests/test_lens_source_cpu.py."""
+import ctypes as C
+import os
+import subprocess
+
+import numpy as np
+import pytest
+
+import lens_source_ref as ref
+import oracle_lib
+import raytracer_amd as ra
+from raytracer_amd import scenes
+
+pytestmark = pytest.mark.gpu
+
+INVALID_ARGUMENT, NOT_READY, UNSUPPORTED = -1, -5, -6
+FIXTURES = {
+    "single_mesh": (lambda a: scenes.sponza_class(a, 6000), 96, 54, 6),
+    "two_level": (scenes.cornell_box, 64, 48, 4),
+}
+BLUE_NOISE = ra.load_blue_noise()   # kept alive: the scene descriptions point into it
+INTERPRETED = [k for k in range(32) if k < 8 or k % 4 != 3]   # every word but the w lanes of quads 2..7
+UNINTERPRETED = [11, 15, 19, 23, 27, 31]
+
+
+def words(a):
+    return np.ascontiguousarray(a).view(np.uint32)
+
+
+def same(a, b, what=""):
+    assert a.shape == b.shape, (what, a.shape, b.shape)
+    bad = np.argwhere(words(a) != words(b))
+    assert len(bad) == 0, "%s: %d of %d words differ, first at %r: %r against %r" % (what, len(bad), a.size, tuple(bad[0]), a[tuple(bad[0])], b[tuple(bad[0])])
+
+
+def viewport(scene, w, h, walk="default", seed=31, spread=0.0, **kw):
+    scene.desc.contents.blueNoise = BLUE_NOISE.ctypes.data   # (for the oracle: the mirror brings its own)
+    vp = ra.Viewport(w, h, seed=seed, anti_aliasing_spread=spread, **kw)
+    vp.set_renderer(scene, intersection_counters=(walk == "counting"))
+    return vp
+
+
+def copy_of(p):
+    q = ra.RtPassParams.from_buffer_copy(p)
+    q._seed_keepalive = p._seed_keepalive
+    return q
+
+
+def without_camera(p, offset=None):
+    """the pass constants with a camera no kernel could use and checkPass would refuse: under a lens source it is not read -- the sample offset is"""
+    q = copy_of(p)
+    for k in range(16):
+        q.camera.localToWorld[k] = float("nan")
+        q.camera.worldToScreen[k] = float("nan")
+    q.camera.aspectRatio = q.camera.tanHalfFoV = float("nan")
+    q.camera.dofEnable, q.camera.bokehShape = 1, 7
+    if offset is not None:
+        q.sampleOffset[0], q.sampleOffset[1] = offset
+    return q
+
+
+def at_offset(p, offset):
+    q = copy_of(p)
+    q.sampleOffset[0], q.sampleOffset[1] = offset
+    return q
+
+
+def offset_of(p):
+    return float(p.sampleOffset[0]), float(p.sampleOffset[1])
+
+
+def frame_of(vp):
+    return vp.sum_buffer(secondary=True) + (vp.counters(),)
+
+
+def same_frame(got, want, what=""):
+    same(got[0], want[0], what + " sum")
+    same(got[1], want[1], what + " secondary")
+    assert got[2] == want[2], (what, got[2], want[2])
+
+
+def pass_params(vp, camera, n):
+    params = [vp.next_pass_params(camera) for _ in range(n)]
+    for i, p in enumerate(params):
+        p.passIndex = i   # (drawn before any pass has finished: the viewport numbered them all 0)
+    return params
+
+
+def dof_camera(camera, shape, focal=3.0, aperture=0.08):
+    camera.set_dof(True, focal, aperture)
+    camera.set_lens(bokeh_shape=shape)
+    return camera
+
+
+# ---- 1. jitter against the plain source ----------------------------------------------------------------------------------------------------------------
+@pytest.mark.parametrize("no_dense", [False, True])
+@pytest.mark.parametrize("fixture", sorted(FIXTURES))
+def test_jitter_renders_what_the_models_plain_tables_render(built, monkeypatch, fixture, no_dense):
+    """the camera's lens table under three passes at spread 0.5, against a twin that sets, before every pass, the plain table the model computes from that
+    lens table and the pass's offset; default layout (k_generate_dense_lens) and RTGPU_NO_DENSE=1 (k_generate_lens)"""
+    if no_dense:
+        monkeypatch.setenv("RTGPU_NO_DENSE", "1")
+    make, w, h, depth = FIXTURES[fixture]
+    scene, camera = make(w / h)
+    a, b = (viewport(scene, w, h, spread=0.5, max_ray_depth=depth) for _ in range(2))
+    params = pass_params(a, camera, 3)
+    assert all(offset_of(p) != (0.0, 0.0) for p in params) and len({offset_of(p) for p in params}) == 3
+    table = a.camera_footprints(at_offset(params[0], (0.0, 0.0)))
+    assert table.shape == (h, w, 32) and np.isfinite(table).all() and table[..., 16:23].any() and not table[..., 8:15].any()
+    a.set_lens_source(table)
+    assert a.ray_source_kind() == 2 and a.ray_source() and b.ray_source_kind() == 0
+    for p in params:
+        a.render_pass_with(without_camera(p))
+        b.set_ray_source(ref.plain_table(table, *offset_of(p)))
+        b.render_pass_with(p)
+        a.sum_buffer(), b.sum_buffer()
+    got, want = frame_of(a), frame_of(b)
+    same_frame(got, want, fixture)
+    assert want[2]["numPrimaryRays"] == 3 * w * h and want[0].any()
+    # the jitter moved the rays: the unjittered table renders another frame
+    b.reset()
+    b.set_ray_source(ref.plain_table(table, 0.0, 0.0))
+    for p in params:
+        b.render_pass_with(p)
+    assert not np.array_equal(words(b.sum_buffer()), words(got[0]))
+
+
+def test_eight_queued_passes_form_a_batch_under_one_table(built, walk):
+    make, w, h, depth = FIXTURES["single_mesh"]
+    scene, camera = make(w / h)
+    a, b = (viewport(scene, w, h, walk, spread=0.5, max_ray_depth=depth) for _ in range(2))
+    params = pass_params(a, camera, 8)
+    table = a.camera_footprints(at_offset(params[0], (0.0, 0.0)))
+    a.set_lens_source(table)
+    for p in params:   # no synchronise in between: the passes queue up and go out as batches, each with its own offset
+        a.render_pass_with(without_camera(p))
+    for p in params:
+        b.set_ray_source(ref.plain_table(table, *offset_of(p)))
+        b.render_pass_with(p)
+    got, want = frame_of(a), frame_of(b)
+    same_frame(got, want, "batch")
+    assert got[2]["numPrimaryRays"] == 8 * w * h
+
+
+# ---- 2. offset zero passes through ---------------------------------------------------------------------------------------------------------------------
+def test_zero_offset_passes_the_stored_rays_through(built, walk):
+    make, w, h, depth = FIXTURES["single_mesh"]
+    scene, camera = make(w / h)
+    a, b = (viewport(scene, w, h, walk, max_ray_depth=depth) for _ in range(2))
+    params = pass_params(a, camera, 2)
+    assert offset_of(params[0]) == (0.0, 0.0)
+    rng = np.random.default_rng(5)
+    table = rng.uniform(-50.0, 50.0, size=(h, w, 32)).astype(np.float32)   # arbitrary finite derivatives, lens words and w lanes
+    stored = a.camera_rays(params[0])
+    stored[h // 2, w // 2, 5] = -0.0   # a -0.0 component: it decides the sign of 1 / dir
+    stored[3, 7, 4] = -0.0
+    table[..., 0:3], table[..., 4:7] = stored[..., 0:3], stored[..., 4:7]
+    a.set_lens_source(table)
+    b.set_ray_source(stored)
+    exported = a.lens_source_rays(params[0])
+    same(exported, stored, "the export at offset 0")   # (words 3 and 7: zero on both sides)
+    assert np.signbit(exported[h // 2, w // 2, 5]) and np.signbit(exported[3, 7, 4])
+    for p in params:
+        a.render_pass_with(without_camera(p, offset=(0.0, -0.0)))
+        b.render_pass_with(p)
+    same_frame(frame_of(a), frame_of(b), "offset 0")
+
+
+# ---- 3. the camera's lens ------------------------------------------------------------------------------------------------------------------------------
+@pytest.mark.parametrize("no_dense", [False, True])
+@pytest.mark.parametrize("shape", [0, 1, 2])
+@pytest.mark.parametrize("fixture", sorted(FIXTURES))
+def test_the_cameras_lens_table_renders_the_cameras_depth_of_field(built, monkeypatch, walk, fixture, shape, no_dense):
+    """a DOF camera's exported table with lens=1 renders the camera's own frame -- and the oracle's on the two-level fixture -- under both walks, the
+    stored-sampler path (RTGPU_NO_DENSE=1) and the dense re-run with the two draws; three passes: both parities of passIndex"""
+    if no_dense:
+        monkeypatch.setenv("RTGPU_NO_DENSE", "1")
+    make, w, h, depth = FIXTURES[fixture]
+    scene, camera = make(w / h)
+    dof_camera(camera, shape)
+    a, b = (viewport(scene, w, h, walk, max_ray_depth=depth) for _ in range(2))
+    params = pass_params(a, camera, 3)
+    assert params[0].camera.dofEnable == 1 and params[0].camera.bokehShape == shape and offset_of(params[0]) == (0.0, 0.0)
+    table = b.camera_footprints(params[0])
+    assert (table[..., 3] == np.float32(0.08)).all() and (table[..., 7] == np.float32(3.0)).all()
+    b.set_lens_source(table, lens=True, bokeh_shape=shape)
+    for p in params:
+        a.render_pass_with(p)
+        b.render_pass_with(without_camera(p))
+        a.sum_buffer(), b.sum_buffer()
+    want, got = frame_of(a), frame_of(b)
+    same_frame(got, want, "%s shape %d" % (fixture, shape))
+    assert want[0].any()
+    if fixture == "two_level":
+        o1, o2 = np.zeros((h, w, 3), dtype=np.float32), np.zeros((h, w, 3), dtype=np.float32)
+        for p in params:
+            oracle_lib.render_pass(scene.desc, p, w, h, o1, o2, threads=8)
+        same(got[0], o1, "oracle sum")
+        same(got[1], o2, "oracle secondary")
+    if shape == 0 and not no_dense and walk == "default":   # the lens did something: without it the table renders the pinhole's frame
+        b.reset()
+        b.set_lens_source(table, lens=False)
+        for p in params:
+            b.render_pass_with(p)
+        assert not np.array_equal(words(b.sum_buffer()), words(want[0]))
+
+
+# ---- 4. lens and jitter together -----------------------------------------------------------------------------------------------------------------------
+@pytest.mark.parametrize("no_dense", [False, True])
+def test_lens_and_jitter_together(built, monkeypatch, no_dense):
+    """table A under the passes' offsets against table B -- A with origins and directions pre-jittered by the model, set per pass -- at offset (0, 0); the same
+    lens settings on both"""
+    if no_dense:
+        monkeypatch.setenv("RTGPU_NO_DENSE", "1")
+    make, w, h, depth = FIXTURES["single_mesh"]
+    scene, camera = make(w / h)
+    dof_camera(camera, 1)
+    a, b = (viewport(scene, w, h, spread=0.5, max_ray_depth=depth) for _ in range(2))
+    params = pass_params(a, camera, 3)
+    table = a.camera_footprints(at_offset(params[0], (0.0, 0.0)))
+    a.set_lens_source(table, lens=True, bokeh_shape=1)
+    for p in params:
+        a.render_pass_with(without_camera(p))
+        b.set_lens_source(ref.prejittered(table, *offset_of(p)), lens=True, bokeh_shape=1)
+        b.render_pass_with(without_camera(p, offset=(0.0, 0.0)))
+        a.sum_buffer(), b.sum_buffer()
+    same_frame(frame_of(a), frame_of(b), "lens and jitter")
+    assert frame_of(a)[0].any()
+
+
+# ---- 5. the ray export ---------------------------------------------------------------------------------------------------------------------------------
+def test_the_export_is_the_model_and_the_guard_holds(built):
+    make, w, h, depth = FIXTURES["single_mesh"]
+    scene, camera = make(w / h)
+    a, b = (viewport(scene, w, h, max_ray_depth=depth) for _ in range(2))
+    params = pass_params(a, camera, 2)
+    rng = np.random.default_rng(11)
+    table = rng.uniform(-10.0, 10.0, size=(h, w, 32)).astype(np.float32)
+    cancel = (h // 3, w // 4)
+    table[cancel][4:7], table[cancel][16:19] = (1.0, 0.0, 0.0), (-1.0, 0.0, 0.0)   # direction + 1 * dDirection/dsx = 0
+    a.set_lens_source(table)
+    for offset in ((1.0, 0.0), (0.37, -1.21), (0.0, 0.0), (-2.0, 1.5)):
+        got = a.lens_source_rays(at_offset(params[0], offset))
+        same(got, ref.plain_table(table, *offset), "export at %r" % (offset,))
+    got = a.lens_source_rays(at_offset(params[0], (1.0, 0.0)))
+    raw_o, raw_d = ref.jitter(table, 1.0, 0.0)
+    assert not raw_d[cancel].any() and raw_o[cancel].tolist() != table[cancel][0:3].tolist()
+    same(got[cancel][0:3], table[cancel][0:3], "the cancelled entry's origin is the stored one")
+    same(got[cancel][4:7], table[cancel][4:7], "the cancelled entry's direction is the stored one")
+    # the same on the device: a tensor out, without a host copy
+    on_device = a.lens_source_rays(at_offset(params[0], (1.0, 0.0)), device=True)
+    same(on_device.cpu().numpy(), got, "device export")
+    # a frame from a table with a cancelling entry: the camera's footprints with origins that move too, one direction cancelled at offset (1, 0)
+    table = a.camera_footprints(params[0])
+    table[..., 8:11] = rng.uniform(-0.01, 0.01, size=(h, w, 3)).astype(np.float32)
+    table[..., 12:15] = rng.uniform(-0.01, 0.01, size=(h, w, 3)).astype(np.float32)
+    table[cancel][16:19] = -table[cancel][4:7]
+    a.set_lens_source(table)
+    exported = a.lens_source_rays(at_offset(params[0], (1.0, 0.0)))
+    same(exported, ref.plain_table(table, 1.0, 0.0), "export")
+    same(exported[cancel][4:7], table[cancel][4:7], "guarded")
+    b.set_ray_source(exported)
+    for p in params:
+        a.render_pass_with(without_camera(p, offset=(1.0, 0.0)))
+        b.render_pass_with(p)
+    same_frame(frame_of(a), frame_of(b), "frame of the exported rays")
+    assert np.isfinite(frame_of(a)[0]).all() and frame_of(a)[0].any()
+
+
+def test_the_export_takes_the_passes_lens_draws(built):
+    """with lens=1 the export is the ray the pass starts from, draws included: it is vertex 0 of the recorded path, and differs from pass to pass"""
+    make, w, h, depth = FIXTURES["two_level"]
+    scene, camera = make(w / h)
+    dof_camera(camera, 0)
+    vp = viewport(scene, w, h, max_ray_depth=depth)
+    params = pass_params(vp, camera, 2)
+    vp.set_lens_source(vp.camera_footprints(params[0]), lens=True, bokeh_shape=0)
+    rays = [vp.lens_source_rays(p) for p in params]
+    assert not np.array_equal(words(rays[0]), words(rays[1]))
+    pixels = [(0, 0), (w - 1, h - 1), (w // 2, h // 3), (5, 7)]
+    for p, r in zip(params, rays):
+        for (x, y), (vertices, _, _) in zip(pixels, vp.record_paths(p, pixels)):
+            same(vertices[0, 0:3], r[y, x, 0:3], "origin of pixel %d %d" % (x, y))
+
+
+# ---- 6. followers --------------------------------------------------------------------------------------------------------------------------------------
+def test_the_followers_follow_the_lens(built):
+    """render_aovs, record_paths and denoise under the DOF camera's lens table at offset (0, 0) equal the same calls under the DOF camera"""
+    make, w, h, depth = FIXTURES["single_mesh"]
+    scene, camera = make(w / h)
+    dof_camera(camera, 2)
+    a, b = (viewport(scene, w, h, max_ray_depth=depth) for _ in range(2))
+    params = pass_params(a, camera, 3)
+    b.set_lens_source(b.camera_footprints(params[0]), lens=True, bokeh_shape=2)
+    for p in params[:2]:
+        a.render_pass_with(p)
+        b.render_pass_with(without_camera(p))
+    same_frame(frame_of(b), frame_of(a), "frame")
+    want, got = a.render_aovs(params[2], ("depth", "position", "normal")), b.render_aovs(without_camera(params[2]), ("depth", "position", "normal"))
+    for name in ("depth", "position", "normal"):
+        same(got[name], want[name], name)
+    pinhole = copy_of(params[2])
+    pinhole.camera.dofEnable = 0
+    assert not np.array_equal(words(a.render_aovs(pinhole, ("depth",))["depth"]), words(want["depth"]))   # (the lens shows in the guides)
+    pixels = [(0, 0), (w - 1, h - 1), (w // 2, h // 3), (5, 7)]
+    for (wv, wn, wr), (gv, gn, gr) in zip(a.record_paths(params[2], pixels), b.record_paths(without_camera(params[2]), pixels)):
+        same(gv, wv, "vertices")
+        same(gr, wr, "radiance")
+        assert gn == wn
+    same(b.denoise(without_camera(params[2])), a.denoise(params[2]), "denoise")
+    same_frame(frame_of(b), frame_of(a), "not a pass")
+
+
+# ---- 7. refusals and state -----------------------------------------------------------------------------------------------------------------------------
+@pytest.mark.parametrize("previous", ["camera", "plain", "lens"])
+def test_a_refused_table_leaves_the_previous_source(built, previous):
+    import torch
+    lib = ra.rtgpu_lib()
+    make, w, h, depth = FIXTURES["two_level"]
+    scene, camera = make(w / h)
+    vp, twin = (viewport(scene, w, h, spread=0.5, max_ray_depth=depth) for _ in range(2))
+    params = pass_params(vp, camera, 2)
+    good = vp.camera_footprints(at_offset(params[0], (0.0, 0.0)))
+    good[..., 3], good[..., 7] = 0.05, 3.0
+    for v in (vp, twin):
+        if previous == "plain":
+            v.set_ray_source(v.camera_rays(at_offset(params[0], (0.0, 0.0)))[::-1].copy())
+        elif previous == "lens":
+            v.set_lens_source(good[:, ::-1].copy(), lens=True, bokeh_shape=1)
+    kind = {"camera": 0, "plain": 1, "lens": 2}[previous]
+    assert vp.ray_source_kind() == kind
+    ctx = vp.device_context()
+    # a word that is not finite in each interpreted lane, through the host entry; every fourth also through the device entry
+    for i, word in enumerate(INTERPRETED):
+        bad = good.copy()
+        bad[(7 * i) % h, (11 * i) % w, word] = (np.nan, np.inf, -np.inf)[i % 3]
+        with pytest.raises(ValueError, match="refused"):
+            vp.set_lens_source(bad)
+        if i % 4 == 0:
+            with pytest.raises(ValueError, match="refused"):
+                vp.set_lens_source(torch.from_numpy(bad).cuda(), lens=True)
+    # a zero stored direction (also one whose squared length underflows); focalDistance <= 0 under lens = 1 only
+    for value in (0.0, 1e-30):
+        bad = good.copy()
+        bad[h - 1, w - 1, 4:7] = value
+        with pytest.raises(ValueError, match="refused"):
+            vp.set_lens_source(bad)
+    for value in (0.0, -1.0):
+        bad = good.copy()
+        bad[0, 0, 7] = value
+        with pytest.raises(ValueError, match="focalDistance"):
+            vp.set_lens_source(bad, lens=True)
+    # counts, shapes, parameters, pointers
+    ptr = good.ctypes.data_as(C.c_void_p)
+    settings = ra.RtLensSourceParams(1, 0)
+    assert lib.rtgpu_set_lens_source(ctx, ptr, C.c_uint64(w * h - 1), C.byref(settings)) == INVALID_ARGUMENT
+    assert lib.rtgpu_set_lens_source(ctx, ptr, C.c_uint64(0), C.byref(settings)) == INVALID_ARGUMENT
+    assert lib.rtgpu_set_lens_source(ctx, None, C.c_uint64(w * h), C.byref(settings)) == INVALID_ARGUMENT
+    assert lib.rtgpu_set_lens_source(ctx, ptr, C.c_uint64(w * h), None) == INVALID_ARGUMENT
+    assert lib.rtgpu_set_lens_source(ctx, ptr, C.c_uint64(w * h), C.byref(ra.RtLensSourceParams(1, 3))) == INVALID_ARGUMENT and b"bokeh" in lib.rtgpu_last_error()
+    assert lib.rtgpu_set_lens_source(ctx, ptr, C.c_uint64(w * h), C.byref(ra.RtLensSourceParams(2, 0))) == INVALID_ARGUMENT
+    with pytest.raises(ValueError, match="bokeh"):
+        vp.set_lens_source(good, lens=True, bokeh_shape=3)
+    with pytest.raises(ValueError):
+        vp.set_lens_source(good[:-1])
+    assert lib.rtgpu_set_lens_source_device(ctx, ptr, C.c_uint64(w * h), C.byref(settings), None) == INVALID_ARGUMENT and b"device" in lib.rtgpu_last_error()
+    on_device = torch.from_numpy(good).cuda()
+    # a table one float short of 128 bytes per pixel before its ALLOCATION ends (torch carves tensors out of larger segments: the library can hold a pointer
+    # to the segment alone, whose end torch's snapshot tells)
+    at = on_device.data_ptr()
+    segment = next(s for s in torch.cuda.memory_snapshot() if s["address"] <= at < s["address"] + s["total_size"])
+    near_the_end = segment["address"] + segment["total_size"] - (128 * w * h - 4)
+    assert lib.rtgpu_set_lens_source_device(ctx, C.c_void_p(near_the_end), C.c_uint64(w * h), C.byref(settings), None) == INVALID_ARGUMENT
+    assert b"allocation" in lib.rtgpu_last_error(), lib.rtgpu_last_error()
+    assert lib.rtgpu_set_lens_source_device(ctx, C.c_void_p(on_device.data_ptr() + 2), C.c_uint64(w * h), C.byref(settings), None) == INVALID_ARGUMENT
+    out_of_line = torch.zeros(w * h * 32 + 8, dtype=torch.float32, device="cuda")
+    assert lib.rtgpu_read_camera_footprints_async(ctx, C.byref(params[0]), C.c_void_p(out_of_line.data_ptr() + 4), None) == INVALID_ARGUMENT and not out_of_line.any()
+    assert vp.ray_source_kind() == kind
+    # ... and the previous source renders the frame it rendered before
+    for p in params:
+        vp.render_pass_with(p)
+        twin.render_pass_with(p)
+    same_frame(frame_of(vp), frame_of(twin), "after refused tables over %s" % previous)
+    assert frame_of(vp)[0].any()
+
+
+def test_pass_time_refusals_and_calls_out_of_order(built):
+    lib = ra.rtgpu_lib()
+    make, w, h, depth = FIXTURES["two_level"]
+    scene, camera = make(w / h)
+    vp, twin = (viewport(scene, w, h, max_ray_depth=depth) for _ in range(2))
+    params = pass_params(vp, camera, 3)
+    good = vp.camera_footprints(params[0])
+    ctx = vp.device_context()
+    ptr = good.ctypes.data_as(C.c_void_p)
+    settings = ra.RtLensSourceParams(0, 0)
+    # no lens source: nothing to export; a variable barrel factor has no table
+    assert lib.rtgpu_read_lens_source_rays(ctx, C.byref(params[0]), ptr) == NOT_READY
+    barrel = copy_of(params[0])
+    barrel.camera.barrelDistortionVariableFactor = 0.1
+    assert lib.rtgpu_read_camera_footprints(ctx, C.byref(barrel), ptr) == UNSUPPORTED
+    # before rtgpu_resize
+    raw = C.c_void_p()
+    assert lib.rtgpu_create(0, C.byref(raw)) == 0
+    kind = C.c_uint32(7)
+    assert lib.rtgpu_set_lens_source(raw, ptr, C.c_uint64(w * h), C.byref(settings)) == NOT_READY
+    assert lib.rtgpu_get_ray_source_kind(raw, C.byref(kind)) == 0 and kind.value == 0
+    assert lib.rtgpu_read_camera_footprints(raw, C.byref(params[0]), ptr) == NOT_READY
+    assert lib.rtgpu_read_lens_source_rays(raw, C.byref(params[0]), ptr) == NOT_READY
+    lib.rtgpu_destroy(raw)
+    # garbage in the uninterpreted w lanes is accepted, and is never read
+    dirty = good.copy()
+    for i, word in enumerate(UNINTERPRETED):
+        dirty[..., word] = (np.nan, np.inf, -np.inf)[i % 3]
+    vp.set_lens_source(dirty, lens=True, bokeh_shape=1)
+    twin.set_lens_source(good, lens=True, bokeh_shape=1)
+    same(vp.lens_source_rays(params[1]), twin.lens_source_rays(params[1]), "the export, w lanes dirty")   # (uploads the scene: the pass-time checks below need one)
+    # a sample offset that is not finite: refused at pass time, under a lens source only; the camera is still not looked at
+    for value in (float("inf"), float("nan")):
+        for k in (0, 1):
+            bad = copy_of(params[0])
+            bad.sampleOffset[k] = value
+            assert lib.rtgpu_render_pass(ctx, C.byref(bad)) == INVALID_ARGUMENT and b"sampleOffset" in lib.rtgpu_last_error()
+            assert lib.rtgpu_read_lens_source_rays(ctx, C.byref(bad), ptr) == INVALID_ARGUMENT
+            with pytest.raises(ValueError, match="sampleOffset"):
+                vp.render_aovs(bad, ("depth",))
+    # the integrators that splat through the camera, and the reprojection
+    for integrator in (1, 4):
+        assert lib.rtgpu_set_integrator(ctx, C.c_uint32(integrator), None) == 0
+        assert lib.rtgpu_render_pass(ctx, C.byref(params[2])) == UNSUPPORTED and b"ray source" in lib.rtgpu_last_error()
+    assert lib.rtgpu_set_integrator(ctx, C.c_uint32(0), None) == 0
+    with pytest.raises(RuntimeError, match="ray source"):
+        vp.denoise(params[2], temporal=True)
+    for p in params[:2]:
+        vp.render_pass_with(without_camera(p))
+        twin.render_pass_with(p)
+    same_frame(frame_of(vp), frame_of(twin), "after the refusals, w lanes dirty")
+    assert frame_of(vp)[0].any()
+
+
+def test_one_context_holds_one_source_and_what_keeps_or_drops_it(built):
+    lib = ra.rtgpu_lib()
+    make, w, h, depth = FIXTURES["two_level"]
+    scene, camera = make(w / h)
+    a, b, fresh = (viewport(scene, w, h, spread=0.5, max_ray_depth=depth) for _ in range(3))
+    params = pass_params(a, camera, 4)
+    zero = at_offset(params[0], (0.0, 0.0))
+    lens = a.camera_footprints(zero)[:, ::-1].copy()
+    plain = a.camera_rays(zero)[::-1].copy()
+    ctx = b.device_context()
+    # setting one kind replaces the other, back and forth (the buffers change roles: nothing stale may be read)
+    for v in (a, b):
+        v.set_ray_source(plain)
+        assert v.ray_source_kind() == 1
+        v.set_lens_source(lens)
+        assert v.ray_source_kind() == 2 and v.ray_source()
+        v.set_ray_source(plain)
+        assert v.ray_source_kind() == 1
+        v.set_lens_source(lens * np.float32(2.0))
+        v.set_lens_source(lens)
+        assert v.ray_source_kind() == 2
+    # the calls of the state table that keep a source keep this one
+    b.render_pass_with(params[0])
+    b.reset()
+    assert b.ray_source_kind() == 2
+    b.set_shard(0, 1)
+    assert b.ray_source_kind() == 2
+    assert lib.rtgpu_set_integrator(ctx, C.c_uint32(2), None) == 0 and lib.rtgpu_set_integrator(ctx, C.c_uint32(0), None) == 0
+    assert lib.rtgpu_upload_scene(ctx, scene.desc) == 0
+    scene.update()
+    b.update_scene()   # rtgpu_update_objects
+    assert b.ray_source_kind() == 2
+    for p in params[:2]:
+        a.render_pass_with(p)
+        b.render_pass_with(p)
+    same(b.sum_buffer(), a.sum_buffer(), "after the calls that keep the source")
+    fresh.set_ray_source(ref.plain_table(lens, *offset_of(params[0])))
+    fresh.render_pass_with(params[0])
+    fresh.set_ray_source(ref.plain_table(lens, *offset_of(params[1])))
+    fresh.render_pass_with(params[1])
+    same(a.sum_buffer(), fresh.sum_buffer(), "the lens table after the plain one, not the plain one")
+    # clearing through the ray source's entry clears a lens source: the camera renders again
+    a.set_ray_source(None)
+    assert a.ray_source_kind() == 0 and not a.ray_source()
+    fresh.set_ray_source(None)
+    a.reset(), fresh.reset()
+    for p in params[2:]:
+        a.render_pass_with(p)
+        fresh.render_pass_with(p)
+    same(a.sum_buffer(), fresh.sum_buffer(), "cleared")
+    # a resize drops it, also to the size the context has
+    assert lib.rtgpu_resize(ctx, C.c_uint32(w), C.c_uint32(h)) == 0
+    assert b.ray_source_kind() == 0 and not b.ray_source()
+    for p in params[2:]:
+        b.render_pass_with(p)
+    same(b.sum_buffer(), fresh.sum_buffer(), "resized")
+    b.set_lens_source(lens)   # (its buffers went with the old frame: they come back)
+    assert b.ray_source_kind() == 2
+
+
+def test_a_multi_device_context(built):
+    import torch
+    w, h = 200, 136
+    scene, camera = scenes.cornell_box(w / h)
+    one = viewport(scene, w, h, spread=0.5, max_ray_depth=3)
+    params = pass_params(one, camera, 2)
+    dof_camera(camera, 1)
+    table = one.camera_footprints(at_offset(one.next_pass_params(camera), (0.0, 0.0)))[::-1].copy()
+    one.set_lens_source(table, lens=True, bokeh_shape=1)
+    many = ra.Viewport(w, h, seed=31, anti_aliasing_spread=0.5, max_ray_depth=3)
+    many.set_renderer(scene, devices=[0, 0])
+    many.set_lens_source(table, lens=True, bokeh_shape=1)   # the host entry replicates the table
+    for p in params:
+        one.render_pass_with(p)
+        many.render_pass_with(p)
+    same_frame(frame_of(many), frame_of(one), "two shards on one device")
+    with pytest.raises(RuntimeError, match="multi-device"):
+        many.set_lens_source(torch.from_numpy(table).cuda(), lens=True, bokeh_shape=1)
+    assert many.ray_source_kind() == 2
+
+
+# ---- 8. the headless demo ------------------------------------------------------------------------------------------------------------------------------
+def test_rt_demo_gives_a_projection_a_lens(built, tmp_path):
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    scene = os.path.join(root, "tests", "golden", "obj", "scene.json")
+    exe = os.path.join(root, "raytracer_amd", "lib", "rt_demo")
+    images = {}
+    for label, extra in (("sharp", []), ("lens", ["--aperture", "0.3", "--focal-distance", "4", "--bokeh", "hexagon"])):
+        path = str(tmp_path / (label + ".bmp"))
+        r = subprocess.run([exe, "-s", scene, "--data", os.path.dirname(scene) + "/", "--width", "64", "--height", "48", "--passes", "4", "--depth", "3", "--seed", "11",
+                            "--projection", "panorama"] + extra + ["--output", path], capture_output=True, text=True, timeout=120)
+        assert r.returncode == 0, r.stdout + r.stderr
+        assert "projection: panorama, 3072 primary rays" in r.stdout and "4 passes of 64x48" in r.stdout
+        assert ("lens: aperture 0.3, focal distance 4, bokeh shape 1" in r.stdout) == (label == "lens"), r.stdout
+        images[label] = open(path, "rb").read()
+    assert len(images["sharp"]) == len(images["lens"]) > 54 + 64 * 48 * 3 - 1
+    assert len(set(images["sharp"][54:])) > 8 and len(set(images["lens"][54:])) > 8   # frames, not blanks
+    assert images["sharp"] != images["lens"]
+    r = subprocess.run([exe, "-s", scene, "--aperture", "0.3"], capture_output=True, text=True, timeout=120)
+    assert r.returncode == 2 and "--projection" in r.stderr
+    r = subprocess.run([exe, "-s", scene, "--projection", "panorama", "--bokeh", "star"], capture_output=True, text=True, timeout=120)
+    assert r.returncode == 2 and "circle, hexagon or square" in r.stderr
