@@ -1376,52 +1376,60 @@ class Viewport:
         or has a zero direction raises ValueError and leaves the previous source in place.  None clears the source: the camera renders again.  A resize
         drops the source; the camera and sample offset of the pass constants are not read while one is set; denoise(temporal=True), "VCM" and
         "Light Tracer" passes raise."""
-        lib = rtgpu_lib()
         ctx = self._ray_source_context("set_ray_source")
         if rays is None:
             if directions is not None:
                 raise ValueError("directions without origins")
+            lib = rtgpu_lib()
             r = lib.rtgpu_set_ray_source(ctx, None, C.c_uint64(0))
             if r != 0:
                 raise RuntimeError("set_ray_source failed (%d): %s" % (r, (lib.rtgpu_last_error() or b"").decode()))
             return
-        h, w = self.height, self.width
-        torch = None
-        if type(rays).__module__.split(".")[0] == "torch" or (directions is not None and type(directions).__module__.split(".")[0] == "torch"):
-            import torch
-        parts = (rays,) if directions is None else (rays, directions)
-        shape = (h, w, 8) if directions is None else (h, w, 3)
-        what = "rays must be an (H, W, 8)" if directions is None else "origins and directions must be (H, W, 3)"
-        if torch is None:
-            for a in parts:
-                if not isinstance(a, np.ndarray) or a.dtype != np.float32 or a.shape != shape:
-                    raise ValueError("%s float32 NumPy array(s) of the viewport's size (or torch tensors)" % what)
-            if directions is None:
-                table = np.ascontiguousarray(rays)
-            else:
-                table = np.zeros((h, w, 8), dtype=np.float32)
-                table[:, :, 0:3], table[:, :, 4:7] = rays, directions
-            r = lib.rtgpu_set_ray_source(ctx, table.ctypes.data_as(C.c_void_p), C.c_uint64(h * w))
+        if directions is None:
+            parts, words, what = (rays,), 8, "rays must be an (H, W, 8)"
         else:
+            parts, words, what = (rays, directions), 3, "origins and directions must be (H, W, 3)"
+        self._set_source("set_ray_source", ctx, "rtgpu_set_ray_source", parts, words, what + " float32 NumPy array(s) of the viewport's size (or torch tensors)",
+                         what + " float32 tensor(s) of the viewport's size", "tensors")
+
+    def _set_source(self, what, ctx, entry, parts, words, wrong_arrays, wrong_tensors, noun, *settings):
+        """set_ray_source and set_lens_source behind their own arguments: `parts` -- one table, or origins and directions -- are (H, W, words) float32 NumPy
+        arrays, or torch tensors on the renderer's device (one of them a tensor: all are held to that), and go as one contiguous table to `entry`, tensors to
+        `entry`_device behind torch.cuda.current_stream(); `settings` are the entry's arguments behind the count.  A refusal (-1) raises ValueError."""
+        lib = rtgpu_lib()
+        h, w = self.height, self.width
+        shape, count = (h, w, words), C.c_uint64(h * w)
+        if any(type(a).__module__.split(".")[0] == "torch" for a in parts):
+            import torch
             for a in parts:
                 if not isinstance(a, torch.Tensor) or a.dtype != torch.float32 or tuple(a.shape) != shape:
-                    raise ValueError("%s float32 tensor(s) of the viewport's size" % what)
-                if not a.is_cuda or a.device != rays.device:
-                    raise ValueError("the tensors must live on the renderer's ROCm device")
-            device = rays.device
+                    raise ValueError(wrong_tensors)
+                if not a.is_cuda or a.device != parts[0].device:
+                    raise ValueError("the %s must live on the renderer's ROCm device" % noun)
+            device = parts[0].device
             if (device.index if device.index is not None else torch.cuda.current_device()) != multi_info(ctx)["devices"][0]:
-                raise ValueError("the tensors must live on the renderer's device (cuda:%d)" % multi_info(ctx)["devices"][0])
-            if directions is None:
-                table = rays.contiguous()
+                raise ValueError("the %s must live on the renderer's device (cuda:%d)" % (noun, multi_info(ctx)["devices"][0]))
+            if len(parts) == 1:
+                table = parts[0].contiguous()
             else:
                 table = torch.zeros((h, w, 8), dtype=torch.float32, device=device)
-                table[:, :, 0:3] = rays
-                table[:, :, 4:7] = directions
-            r = _run_on_torch_stream(torch, self._query_streams, device, (table,), lambda stream: lib.rtgpu_set_ray_source_device(
-                ctx, C.c_void_p(table.data_ptr()), C.c_uint64(h * w), stream))
+                table[:, :, 0:3] = parts[0]
+                table[:, :, 4:7] = parts[1]
+            r = _run_on_torch_stream(torch, self._query_streams, device, (table,), lambda stream: getattr(lib, entry + "_device")(
+                ctx, C.c_void_p(table.data_ptr()), count, *settings, stream))
+        else:
+            for a in parts:
+                if not isinstance(a, np.ndarray) or a.dtype != np.float32 or a.shape != shape:
+                    raise ValueError(wrong_arrays)
+            if len(parts) == 1:
+                table = np.ascontiguousarray(parts[0])
+            else:
+                table = np.zeros((h, w, 8), dtype=np.float32)
+                table[:, :, 0:3], table[:, :, 4:7] = parts
+            r = getattr(lib, entry)(ctx, table.ctypes.data_as(C.c_void_p), count, *settings)
         if r != 0:
             err = (lib.rtgpu_last_error() or b"").decode()
-            raise (ValueError if r == -1 else RuntimeError)("set_ray_source failed (%d): %s" % (r, err))
+            raise (ValueError if r == -1 else RuntimeError)("%s failed (%d): %s" % (what, r, err))
 
     def ray_source(self):
         """Whether a ray source is set (rtgpu_get_ray_source)."""
@@ -1438,23 +1446,7 @@ class Viewport:
         torch.cuda.current_stream().  Not a pass.  Set as the source they render the camera's frame bit for bit; they are also where a lens model of the
         caller's own starts.  A camera with depth of field or a variable barrel factor raises: a table cannot carry the lens draws.  Always the camera's
         rays, whether or not a source is set."""
-        if not isinstance(params, RtPassParams):
-            raise TypeError("camera_rays takes the RtPassParams of next_pass_params(camera), not %s" % type(params).__name__)
-        lib = rtgpu_lib()
-        ctx = self._ray_source_context("camera_rays")
-        if not device:
-            out = np.zeros((self.height, self.width, 8), dtype=np.float32)
-            r = lib.rtgpu_read_camera_rays(ctx, C.byref(params), out.ctypes.data_as(C.c_void_p))
-        else:
-            import torch
-            dev = torch.device("cuda", multi_info(ctx)["devices"][0])
-            out = torch.empty((self.height, self.width, 8), dtype=torch.float32, device=dev)
-            r = _run_on_torch_stream(torch, self._query_streams, dev, (out,), lambda stream: lib.rtgpu_read_camera_rays_async(
-                ctx, C.byref(params), C.c_void_p(out.data_ptr()), stream))
-        if r != 0:
-            err = (lib.rtgpu_last_error() or b"").decode()
-            raise (ValueError if r == -1 else RuntimeError)("camera_rays failed (%d): %s" % (r, err))
-        return out
+        return self._source_export("camera_rays", "rtgpu_read_camera_rays", 8, params, device)
 
     # ---- the lens source (include/rtgpu.h: rtgpu_set_lens_source / rtgpu_read_lens_source_rays / rtgpu_read_camera_footprints) ---------------------
     def set_lens_source(self, table, lens=False, bokeh_shape=0):
@@ -1468,30 +1460,11 @@ class Viewport:
         direction or, under lens=True, a focalDistance that is not > 0 raises ValueError and leaves the previous source (plain, lens or the camera) in
         place.  It replaces a ray source and is replaced by one; set_ray_source(None) clears it; a resize drops it.  The camera of the pass constants is
         not read while it is set, their sample offset is; denoise(temporal=True), "VCM" and "Light Tracer" passes raise."""
-        lib = rtgpu_lib()
         ctx = self._ray_source_context("set_lens_source")
-        h, w = self.height, self.width
         params = RtLensSourceParams(1 if lens else 0, int(bokeh_shape))
-        if type(table).__module__.split(".")[0] == "torch":
-            import torch
-            if not isinstance(table, torch.Tensor) or table.dtype != torch.float32 or tuple(table.shape) != (h, w, 32):
-                raise ValueError("the lens table must be an (H, W, 32) float32 tensor of the viewport's size")
-            if not table.is_cuda:
-                raise ValueError("the tensor must live on the renderer's ROCm device")
-            device = table.device
-            if (device.index if device.index is not None else torch.cuda.current_device()) != multi_info(ctx)["devices"][0]:
-                raise ValueError("the tensor must live on the renderer's device (cuda:%d)" % multi_info(ctx)["devices"][0])
-            table = table.contiguous()
-            r = _run_on_torch_stream(torch, self._query_streams, device, (table,), lambda stream: lib.rtgpu_set_lens_source_device(
-                ctx, C.c_void_p(table.data_ptr()), C.c_uint64(h * w), C.byref(params), stream))
-        else:
-            if not isinstance(table, np.ndarray) or table.dtype != np.float32 or table.shape != (h, w, 32):
-                raise ValueError("the lens table must be an (H, W, 32) float32 NumPy array of the viewport's size (or a torch tensor)")
-            table = np.ascontiguousarray(table)
-            r = lib.rtgpu_set_lens_source(ctx, table.ctypes.data_as(C.c_void_p), C.c_uint64(h * w), C.byref(params))
-        if r != 0:
-            err = (lib.rtgpu_last_error() or b"").decode()
-            raise (ValueError if r == -1 else RuntimeError)("set_lens_source failed (%d): %s" % (r, err))
+        self._set_source("set_lens_source", ctx, "rtgpu_set_lens_source", (table,), 32,
+                         "the lens table must be an (H, W, 32) float32 NumPy array of the viewport's size (or a torch tensor)",
+                         "the lens table must be an (H, W, 32) float32 tensor of the viewport's size", "tensor", C.byref(params))
 
     def ray_source_kind(self):
         """What the passes start from (rtgpu_get_ray_source_kind): 0 the camera, 1 a ray source, 2 a lens source."""
@@ -1502,7 +1475,7 @@ class Viewport:
             raise RuntimeError("rtgpu_get_ray_source_kind failed: %s" % (rtgpu_lib().rtgpu_last_error() or b"").decode())
         return int(kind.value)
 
-    def _lens_export(self, what, entry, words, params, device):
+    def _source_export(self, what, entry, words, params, device):
         if not isinstance(params, RtPassParams):
             raise TypeError("%s takes the RtPassParams of next_pass_params(camera), not %s" % (what, type(params).__name__))
         lib = rtgpu_lib()
@@ -1527,7 +1500,7 @@ class Viewport:
         and lens axes -- or, device=True, a torch tensor on the renderer's ROCm device written on torch.cuda.current_stream().  Not a pass.  A camera
         with depth of field is accepted: set the table with lens=True and the camera's bokeh shape and a pass at the export's offset renders the camera's
         own frame bit for bit.  A variable barrel factor raises."""
-        return self._lens_export("camera_footprints", "rtgpu_read_camera_footprints", 32, params, device)
+        return self._source_export("camera_footprints", "rtgpu_read_camera_footprints", 32, params, device)
 
     def lens_source_rays(self, params, device=False):
         """The primary rays a pass with `params` would start from under the lens source that is set (rtgpu_read_lens_source_rays): jitter by
@@ -1536,7 +1509,7 @@ class Viewport:
         ctx = self._ray_source_context("lens_source_rays")
         if host_lib().rth_viewport_upload_scene(self._h) != 0:   # (the lens draws take the scene's blue noise, as a pass's do)
             raise RuntimeError("the viewport's scene could not be uploaded: %s" % (rtgpu_lib().rtgpu_last_error() or b"").decode())
-        return self._lens_export("lens_source_rays", "rtgpu_read_lens_source_rays", 8, params, device)
+        return self._source_export("lens_source_rays", "rtgpu_read_lens_source_rays", 8, params, device)
 
     # ---- path records (include/rtgpu.h: rtgpu_record_paths) ------------------------------------------------------------------------------
     def record_paths(self, params, pixels, max_vertices=None):

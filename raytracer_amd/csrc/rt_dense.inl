@@ -18,36 +18,13 @@
 // misHitLight, misRoulette, misSampleBsdf, computeLightSample: rt_shade.inl) and keeps only what the layout decides -- record loads and stores, the pending
 // request's resolution, next-event staging, zombies and home[].  The images are bit-identical.
 #ifndef RT_SHADE_FUNCTIONS_ONLY
-// k_generate for dense state: slot i = home i; the regions of the first arena are simply filled one after the other
+// k_generate for dense state (generatePaths, rt_device_state.h): slot i = home i; the regions of the first arena are simply filled one after the other
 __global__ void __launch_bounds__(RT_BLOCK) k_generate_dense(const RtSceneDesc scene, const DevPass* __restrict__ passes, uint32_t slotsPerPass, const Paths paths,
                                                              const uint32_t* __restrict__ slotPixel, uint32_t numSlots, uint32_t shardCapacity, uint32_t* __restrict__ counts,
                                                              unsigned long long* counters)
 {
-    const uint32_t stride = gridDim.x * blockDim.x;
-    for (uint32_t slot = blockIdx.x * blockDim.x + threadIdx.x; slot < numSlots; slot += stride)
-    {
-        const uint32_t passInBatch = slot / slotsPerPass;
-        const DevPass& pass = passes[passInBatch];
-        const uint32_t pix = slotPixel[slot - passInBatch * slotsPerPass];
-        const uint32_t x = pix & 0xFFFFu, y = pix >> 16;
-        const uint32_t realY = pass.height - 1u - y;
-        const float invW = 1.0f / (float)(int32_t)pass.width, invH = 1.0f / (float)(int32_t)pass.height;
-        const V4 coords(((float)(int32_t)x + pass.sampleOffset[0]) * invW, ((float)(int32_t)realY + pass.sampleOffset[1]) * invH, 0.0f, 0.0f);
-        Sampler sampler;
-        sampler.seed = pass.seed; sampler.numDims = pass.numDimensions; sampler.blueNoiseLayers = pass.blueNoiseLayers; sampler.blueNoise = scene.blueNoise;
-        sampler.resetPixel(x, y, pass.rngKey[0], pass.rngKey[1]);
-        V4 origin, direction;
-        cameraGenerateRayParts(pass.camera, coords, sampler, origin, direction);
-        stStream(prec(paths, R_ORIGIN, slot), f4(origin.x, origin.y, origin.z, fbits(0x100u)));   // depth 0, lastSpecular = true (PathTracerMIS.h:29-34)
-        stStream(prec(paths, R_DIR, slot), f4(direction.x, direction.y, direction.z, 1.0f));        // lastPdfW = 1
-        // (the five other records of a fresh path are functions of its slot: bounce 0's shade rebuilds them, see denseShadeVertex)
-    }
-    if (blockIdx.x == 0 && threadIdx.x < RT_DENSE_SHARDS)
-    {
-        const uint32_t first = threadIdx.x * shardCapacity;
-        counts[threadIdx.x] = first >= numSlots ? 0u : (numSlots - first < shardCapacity ? numSlots - first : shardCapacity);
-        if (threadIdx.x == 0) atomicAdd(&counters[C_PRIMARY], (unsigned long long)numSlots);
-    }
+    generatePaths<true>(RT_GRID_STRIDE, scene.blueNoise, passes, slotsPerPass, paths, slotPixel, numSlots, nullptr, CameraRayOf());
+    generateShardCounts(counts, shardCapacity, counters, numSlots);
 }
 
 #endif   // RT_SHADE_FUNCTIONS_ONLY

@@ -152,6 +152,84 @@ RT_DEV Hit unpackHit(const float4& rHit, float v)
     return hit;
 }
 
+// ---- the generate kernels (k_generate*: rt_generate.inl, rt_dense.inl, rt_raysource.inl): one body around "the ray of this pixel" ----
+// film coordinates of pixel (x, y) at a sample offset: invSize = VECTOR_ONE2 / FromIntegers(w, h, 1, 1); coords = (FromIntegers(x, realY) + sampleOffset) * invSize
+// (the export kernels' -- k_camera_rays, k_camera_footprints; generatePaths writes the same three lines out: through this function one packed multiply of
+// k_generate and of k_generate_dense comes out with its operands exchanged, and the two are held to the bytes they had)
+RT_DEV V4 filmCoords(uint32_t x, uint32_t y, uint32_t width, uint32_t height, float sampleOffsetX, float sampleOffsetY)
+{
+    const uint32_t realY = height - 1u - y;
+    const float invW = 1.0f / (float)(int32_t)width, invH = 1.0f / (float)(int32_t)height;
+    return V4(((float)(int32_t)x + sampleOffsetX) * invW, ((float)(int32_t)realY + sampleOffsetY) * invH, 0.0f, 0.0f);
+}
+// Viewport::RenderTile's per-pixel prologue for every slot of a batch, the ray `rayOf(pass, pix, coords, sampler, origin, direction)` gives pixel pix
+// (x | y << 16) -- it draws from the sampler, reset for the pixel, what the ray takes; `coords` are the pixel's film coordinates where RayOf::kFromFilm says
+// the ray starts from the film, else zero -- and the records of a fresh path in the arena's layout:
+//   slot per pixel (kDense false)   all of them, and the slot in `queue`
+//   dense (kDense true)             origin and direction only, streamed: the five other records of a fresh path are functions of its slot, which bounce 0's
+//                                   shade rebuilds (denseShadeVertex)
+// (the grid-stride loop's ends are the kernel's to compute, RT_GRID_STRIDE: blockDim.x read in a device function compiles to another load, and k_generate and
+// k_generate_dense are held to the code they had)
+#define RT_GRID_STRIDE blockIdx.x * blockDim.x + threadIdx.x, gridDim.x * blockDim.x
+template <bool kDense, class RayOf>
+RT_DEV void generatePaths(uint32_t firstSlot, uint32_t stride, const uint16_t* blueNoise, const DevPass* __restrict__ passes, uint32_t slotsPerPass, const Paths& paths, const uint32_t* __restrict__ slotPixel,
+                          uint32_t numSlots, uint32_t* __restrict__ queue, RayOf rayOf)
+{
+    for (uint32_t slot = firstSlot; slot < numSlots; slot += stride)
+    {
+        // several passes ride in one batch: slot = passInBatch * slotsPerPass + pixelSlot
+        const uint32_t passInBatch = slot / slotsPerPass;
+        const DevPass& pass = passes[passInBatch];
+        const uint32_t pix = slotPixel[slot - passInBatch * slotsPerPass];
+        const uint32_t x = pix & 0xFFFFu, y = pix >> 16;
+        V4 coords = zero4();
+        if (RayOf::kFromFilm)   // (ahead of the sampler, where the camera kernels had it; a table's kernels keep their loads where they were)
+        {
+            const uint32_t realY = pass.height - 1u - y;
+            const float invW = 1.0f / (float)(int32_t)pass.width, invH = 1.0f / (float)(int32_t)pass.height;
+            coords = V4(((float)(int32_t)x + pass.sampleOffset[0]) * invW, ((float)(int32_t)realY + pass.sampleOffset[1]) * invH, 0.0f, 0.0f);
+        }
+        Sampler sampler;
+        sampler.seed = pass.seed; sampler.numDims = pass.numDimensions; sampler.blueNoiseLayers = pass.blueNoiseLayers; sampler.blueNoise = blueNoise;
+        sampler.resetPixel(x, y, pass.rngKey[0], pass.rngKey[1]);
+        // Camera::GenerateRay up to (not including) the Ray constructor, which trace/shade re-run from origin+direction
+        V4 origin, direction;
+        rayOf(pass, pix, coords, sampler, origin, direction);
+        if (kDense)
+        {
+            stStream(prec(paths, R_ORIGIN, slot), f4(origin.x, origin.y, origin.z, fbits(0x100u)));   // depth 0, lastSpecular = true (PathTracerMIS.h:29-34)
+            stStream(prec(paths, R_DIR, slot), f4(direction.x, direction.y, direction.z, 1.0f));        // lastPdfW = 1
+        }
+        else
+        {
+            prec(paths, R_ORIGIN, slot) = f4(origin.x, origin.y, origin.z, fbits(0x100u));
+            prec(paths, R_DIR, slot) = f4(direction.x, direction.y, direction.z, 1.0f);
+            prec(paths, R_TP, slot) = f4(1.0f, 1.0f, 1.0f, 1.0f);
+            prec(paths, R_RESULT, slot) = f4(0.0f, 0.0f, 0.0f, fbits(pix));
+            storeSampler(sampler, paths, slot, 0.0f, 0u);
+            queue[slot] = slot;
+        }
+    }
+}
+// the camera as `rayOf` (k_generate, k_generate_dense)
+struct CameraRayOf
+{
+    static constexpr bool kFromFilm = true;
+    __device__ __forceinline__ void operator()(const DevPass& pass, uint32_t, V4 coords, Sampler& sampler, V4& origin, V4& direction) const
+    {
+        cameraGenerateRayParts(pass.camera, coords, sampler, origin, direction);
+    }
+};
+// block 0's epilogue, slot per pixel: every slot is queued
+RT_DEV void generateQueueCount(uint32_t* __restrict__ queueCount, unsigned long long* counters, uint32_t numSlots)
+{
+    if (blockIdx.x == 0 && threadIdx.x == 0)
+    {
+        *queueCount = numSlots;
+        atomicAdd(&counters[C_PRIMARY], (unsigned long long)numSlots);
+    }
+}
+
 // The path's current ray exactly as the reference holds it: Ray(origin, direction) -- which normalises and
 // computes invDir / originDivDir from the UN-offset origin -- and then origin += dir * 0.001f for
 // secondary rays, leaving originDivDir stale (PathTracerMIS.cpp:392-393).
@@ -189,6 +267,17 @@ struct DenseCounts
 #define RT_STAGE_SEED_WORDS    2048u   // 8 KB: 24 passes of 64 dimensions take 6 KB
 static_assert(sizeof(RtObject) % 16 == 0 && sizeof(RtMesh) % 16 == 0 && sizeof(RtMaterial) % 16 == 0 && sizeof(RtLight) % 16 == 0, "the staged tables are copied in 16-byte words");
 __host__ __device__ __forceinline__ static uint32_t stageSeedRow(uint32_t numDims) { return (numDims + 3u) & ~3u; }   // words between two staged seed rows
+
+// block 0's epilogue of the dense generate kernels: slot i = home i, so the regions of the first arena are simply filled one after the other
+RT_DEV void generateShardCounts(uint32_t* __restrict__ counts, uint32_t shardCapacity, unsigned long long* counters, uint32_t numSlots)
+{
+    if (blockIdx.x == 0 && threadIdx.x < RT_DENSE_SHARDS)
+    {
+        const uint32_t first = threadIdx.x * shardCapacity;
+        counts[threadIdx.x] = first >= numSlots ? 0u : (numSlots - first < shardCapacity ? numSlots - first : shardCapacity);
+        if (threadIdx.x == 0) atomicAdd(&counters[C_PRIMARY], (unsigned long long)numSlots);
+    }
+}
 
 // prefix sums of the 16 region counts into LDS (prefix[16] = total); all threads of the block call it
 RT_DEV void denseLoadPrefix(const uint32_t* __restrict__ counts, uint32_t* sPrefix)

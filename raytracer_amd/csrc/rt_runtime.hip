@@ -29,8 +29,8 @@
 // rt_runtime_scene.inl (rtgpu_upload_scene, rtgpu_update_objects: the copies of what rt_scene_prepare.h checks and builds on the host), rt_runtime_render.inl (arena sizing, traversal launchers, batch submission), rt_runtime_vcm.inl (bidirectional
 // integrator, Light Tracer), rt_runtime_kat.inl (known-answer hooks, rtgpu_evaluate_textures), rt_runtime_query.inl (batched ray queries), rt_runtime_paths.inl (path records),
 // rt_runtime_aov.inl (AOVs), rt_runtime_denoise.inl (the a-trous filter, rtgpu_denoise, rtgpu_postprocess_from),
-// rt_runtime_temporal.inl (temporal accumulation), rt_runtime_raysource.inl (the ray source: passes along a caller's primary rays),
-// rt_runtime_lenssource.inl (the lens source: a table of rays with footprints and a thin lens).
+// rt_runtime_temporal.inl (temporal accumulation), rt_runtime_raysource.inl (the primary-ray sources: passes along a caller's table of rays, or of rays
+// with footprints and a thin lens).
 //
 // Compile: hipcc --offload-arch=gfx950 -O3 -ffp-contract=off
 #include "rt_trace_common.h"
@@ -312,7 +312,7 @@ RTGPU_API int rtgpu_resize(RtgpuContext* c, uint32_t width, uint32_t height)
     HIP_TRY(syncLanes(c));
     // a ray source is a frame's: the camera renders again, also when the size is the one the context has (an asynchronous AOV call may still read the table)
     // (both buffers are sized for the old frame: the one a refused table was copied into goes too)
-    if (c->raySource.any() || c->raySource.incoming || c->raySource.lensIncoming) { waitQueries(c); dropRaySource(c); }
+    if (c->raySource.table || c->raySource.incoming) { waitQueries(c); dropRaySource(c); }
     c->width = width; c->height = height;
     return rebuildFilm(c);
 }
@@ -421,7 +421,7 @@ static int checkPass(const RtgpuContext* c, const RtPassParams* p)
     if (p->maxRayDepth >= 255u) return fail(RTGPU_ERR_INVALID_ARGUMENT, "maxRayDepth must be < 255");
     if (!c->raySource.any() && p->camera.dofEnable && p->camera.bokehShape > 2u) return fail(RTGPU_ERR_UNSUPPORTED, "bokeh shapes: circle, hexagon, square (NGon is a TODO in the reference, texture-shaped bokeh is not implemented)");
     // (a lens source applies the pass's sample offset to its footprints: it is the one word of the caller's camera and offset that is read)
-    if (c->raySource.lensTable && !(std::isfinite(p->sampleOffset[0]) && std::isfinite(p->sampleOffset[1])))
+    if (c->raySource.kind == 2u && !(std::isfinite(p->sampleOffset[0]) && std::isfinite(p->sampleOffset[1])))
         return fail(RTGPU_ERR_INVALID_ARGUMENT, "sampleOffset is not finite (a lens source applies it to every ray's footprint)");
     return RTGPU_OK;
 }
@@ -444,10 +444,10 @@ static void makeDevPass(const RtgpuContext* c, const RtPassParams* p, DevPass& p
     pass.width = c->width; pass.height = c->height;
     // under a ray source the table is the camera: the pass carries one that draws nothing -- dense shading re-runs it at bounce 0 only to restore the
     // sampler (rt_dense.inl), which then stays as the table kernels left it -- and the caller's camera and sample offset are never read
-    if (c->raySource.table) { memset(&pass.camera, 0, sizeof(pass.camera)); pass.sampleOffset[0] = 0.0f; pass.sampleOffset[1] = 0.0f; }
+    if (c->raySource.kind == 1u) { memset(&pass.camera, 0, sizeof(pass.camera)); pass.sampleOffset[0] = 0.0f; pass.sampleOffset[1] = 0.0f; }
     // under a lens source the pass keeps its sample offset (the lens kernels jitter by it) and carries a zeroed camera with the SOURCE's lens: the dense
     // re-run then takes the two draws the lens kernel took -- or none -- and discards its ray
-    if (c->raySource.lensTable)
+    if (c->raySource.kind == 2u)
     {
         memset(&pass.camera, 0, sizeof(pass.camera));
         pass.camera.dofEnable = c->raySource.lens; pass.camera.bokehShape = c->raySource.bokehShape;
@@ -757,8 +757,7 @@ RTGPU_API int rtgpu_postprocess(RtgpuContext* c, const RtPostprocessParams* p, u
 #include "rt_runtime_denoise.inl"
 #include "rt_runtime_temporal.inl"
 #include "rt_runtime_refit.inl"   // rtgpu_update_mesh: a deformed mesh's tables refitted on the device
-#include "rt_runtime_raysource.inl"   // rtgpu_set_ray_source: primary rays from a table of the caller's
-#include "rt_runtime_lenssource.inl"  // rtgpu_set_lens_source: the same with footprints, jitter and a thin lens
+#include "rt_runtime_raysource.inl"   // rtgpu_set_ray_source, rtgpu_set_lens_source: primary rays from a table of the caller's
 
 RTGPU_API int rtgpu_set_concurrency(RtgpuContext* c, uint32_t lanes)
 {

@@ -367,24 +367,21 @@ struct RtgpuContext
         float4* moments = nullptr; size_t momentsCapacity = 0;
     } temporal;
 
-    // the ray source (rtgpu_set_ray_source; rt_runtime_raysource.inl): the table the generate kernels read in place of the camera, and the buffer the next
-    // table is copied into and checked in before the two change places -- a refused table never becomes the source, and a caller who sets a table per
-    // pass (anti-aliasing) allocates twice, not per call.  Both hold width * height entries of two float4 and go with the film's size (rtgpu_resize).
+    // where a pass's primary rays come from (rtgpu_set_ray_source, rtgpu_set_lens_source; rt_runtime_raysource.inl): the camera, or the table the generate
+    // kernels read in its place.  One context holds one source.  `incoming` is the buffer the next table of either kind is copied into and checked in before
+    // the two change places -- a refused table never becomes the source, and a caller who sets a table per pass (anti-aliasing) allocates twice, not per
+    // call.  Both hold width * height entries and go with the film's size (rtgpu_resize).
     struct RaySource
     {
-        float4* table = nullptr;                  // null: the camera
-        float4* incoming = nullptr;
-        uint32_t* degenerate = nullptr;           // what k_ray_source_check counted
-        float4* exported = nullptr; size_t exportedEntries = 0;   // rtgpu_read_camera_rays' device copy
-        hipEvent_t order = nullptr;               // rtgpu_set_ray_source_device: puts the copy behind the caller's stream
-        // the lens source (rtgpu_set_lens_source): the same pair of buffers for entries of eight float4 (RtLensRay).  One context holds one source: at most
-        // one of `table` and `lensTable` is set, and setting either kind hands the other's buffer back to its `incoming`.
-        float4* lensTable = nullptr;              // null: the plain table, or the camera
-        float4* lensIncoming = nullptr;
-        uint32_t lens = 0u, bokehShape = 0u;      // RtLensSourceParams of lensTable
-        hipEvent_t lensRead = nullptr;            // behind the last rtgpu_read_lens_source_rays_async on a caller's stream: it reads lensTable
-        float4* lensExported = nullptr; size_t lensExportedBytes = 0;   // the device copy of rtgpu_read_lens_source_rays and rtgpu_read_camera_footprints
-        bool any() const { return table || lensTable; }   // a source of either kind: the camera is not read
+        uint32_t kind = 0u;                       // 0 the camera, 1 a plain table (RtPrimaryRay), 2 a lens table (RtLensRay): rtgpu_get_ray_source_kind's values
+        float4* table = nullptr; size_t tableBytes = 0;         // null under kind 0
+        float4* incoming = nullptr; size_t incomingBytes = 0;
+        uint32_t* degenerate = nullptr;           // what the kind's check kernel counted
+        float4* exported = nullptr; size_t exportedBytes = 0;   // the device copy the synchronous exports read back from (rtgpu_read_camera_rays, ...)
+        hipEvent_t order = nullptr;               // the _device set entries: puts the copy behind the caller's stream
+        uint32_t lens = 0u, bokehShape = 0u;      // RtLensSourceParams of a lens table
+        hipEvent_t lensRead = nullptr;            // behind the last rtgpu_read_lens_source_rays_async on a caller's stream: it reads the lens table
+        bool any() const { return kind != 0u; }   // a source of either kind: the camera is not read
     } raySource;
 
     // timing
@@ -577,13 +574,19 @@ static int callerDeviceArray(const RtgpuContext* c, const void* p, size_t bytes,
 
 // the ray source's tables (the caller has waited for whatever reads them): the camera renders again
 static void waitLensExport(RtgpuContext* c) { if (c->raySource.lensRead) (void)hipEventSynchronize(c->raySource.lensRead); }
-static void dropRaySource(RtgpuContext* c) { waitLensExport(c); devFree(c->raySource.table, c->raySource.incoming, c->raySource.lensTable, c->raySource.lensIncoming); }
+static void dropRaySource(RtgpuContext* c)
+{
+    RtgpuContext::RaySource& s = c->raySource;
+    waitLensExport(c);
+    devFree(s.table, s.incoming);
+    s.kind = 0u; s.tableBytes = 0; s.incomingBytes = 0;
+}
 static void freeRaySource(RtgpuContext* c)
 {
     RtgpuContext::RaySource& s = c->raySource;
     dropRaySource(c);
-    devFree(s.degenerate, s.exported, s.lensExported);
-    s.exportedEntries = 0; s.lensExportedBytes = 0;
+    devFree(s.degenerate, s.exported);
+    s.exportedBytes = 0;
     if (s.order) (void)hipEventDestroy(s.order);
     s.order = nullptr;
     if (s.lensRead) (void)hipEventDestroy(s.lensRead);

@@ -252,9 +252,9 @@ static int submitDenseBatch(RtgpuContext* c, BatchLane& l, const LaneCounts& cou
     HIP_TRY(hipMemsetAsync(l.denseCounts, 0, (size_t)plane * (l.queueCountCapacity + 1u) * sizeof(uint32_t), l.stream));
     {
         LaunchTimer t(c, l.stream, KC_GENERATE);
-        if (c->raySource.lensTable)
-            hipLaunchKernelGGL(k_generate_dense_lens, grid, block, 0, l.stream, c->sceneDev, passesDev, c->numSlots, l.paths, c->slotPixel, totalSlots, shardCapacity, l.denseCounts, c->counters, c->raySource.lensTable, c->raySource.lens, c->raySource.bokehShape);
-        else if (c->raySource.table)
+        if (c->raySource.kind == 2u)
+            hipLaunchKernelGGL(k_generate_dense_lens, grid, block, 0, l.stream, c->sceneDev, passesDev, c->numSlots, l.paths, c->slotPixel, totalSlots, shardCapacity, l.denseCounts, c->counters, c->raySource.table, c->raySource.lens, c->raySource.bokehShape);
+        else if (c->raySource.kind == 1u)
             hipLaunchKernelGGL(k_generate_dense_rays, grid, block, 0, l.stream, c->sceneDev, passesDev, c->numSlots, l.paths, c->slotPixel, totalSlots, shardCapacity, l.denseCounts, c->counters, c->raySource.table);
         else hipLaunchKernelGGL(k_generate_dense, grid, block, 0, l.stream, c->sceneDev, passesDev, c->numSlots, l.paths, c->slotPixel, totalSlots, shardCapacity, l.denseCounts, c->counters);
     }
@@ -327,9 +327,9 @@ static void launchSlotBounces(RtgpuContext* c, hipStream_t stream, unsigned long
 static void launchGenerate(RtgpuContext* c, dim3 grid, hipStream_t stream, const DevPass* passesDev, uint32_t slotsPerPass, const Paths& paths, const uint32_t* slotPixel,
                            uint32_t totalSlots, uint32_t* queue, uint32_t* queueCount, unsigned long long* counters)
 {
-    if (c->raySource.lensTable)
-        hipLaunchKernelGGL(k_generate_lens, grid, dim3(RT_BLOCK), 0, stream, c->sceneDev, passesDev, slotsPerPass, paths, slotPixel, totalSlots, queue, queueCount, counters, c->raySource.lensTable, c->raySource.lens, c->raySource.bokehShape);
-    else if (c->raySource.table)
+    if (c->raySource.kind == 2u)
+        hipLaunchKernelGGL(k_generate_lens, grid, dim3(RT_BLOCK), 0, stream, c->sceneDev, passesDev, slotsPerPass, paths, slotPixel, totalSlots, queue, queueCount, counters, c->raySource.table, c->raySource.lens, c->raySource.bokehShape);
+    else if (c->raySource.kind == 1u)
         hipLaunchKernelGGL(k_generate_rays, grid, dim3(RT_BLOCK), 0, stream, c->sceneDev, passesDev, slotsPerPass, paths, slotPixel, totalSlots, queue, queueCount, counters, c->raySource.table);
     else hipLaunchKernelGGL(k_generate, grid, dim3(RT_BLOCK), 0, stream, c->sceneDev, passesDev, slotsPerPass, paths, slotPixel, totalSlots, queue, queueCount, counters);
 }

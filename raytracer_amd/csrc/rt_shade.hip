@@ -43,9 +43,7 @@ RT_AOV_CLASSES(RT_X)
 RT_AOV_CLASSES(RT_X)
 #undef RT_X
 
-// (behind everything else: the kernels above keep their places in the code object) k_generate_dense fed from a table of rays, rtgpu_set_ray_source
+// (behind everything else: the kernels above keep their places in the code object) k_generate_dense fed from a table of rays, rtgpu_set_ray_source, and from a
+// table of lens rays, rtgpu_set_lens_source
 #define RT_RAYSOURCE_DENSE 1
 #include "rt_raysource.inl"
-// (and from a table of lens rays, rtgpu_set_lens_source)
-#define RT_LENSSOURCE_DENSE 1
-#include "rt_lenssource.inl"

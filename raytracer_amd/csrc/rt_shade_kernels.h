@@ -74,7 +74,7 @@ __global__ void __launch_bounds__(RT_BLOCK) k_generate_dense(const RtSceneDesc s
 __global__ void __launch_bounds__(RT_BLOCK) k_generate_dense_rays(const RtSceneDesc scene, const DevPass* __restrict__ passes, uint32_t slotsPerPass, const Paths paths,
                                                                   const uint32_t* __restrict__ slotPixel, uint32_t numSlots, uint32_t shardCapacity, uint32_t* __restrict__ counts,
                                                                   unsigned long long* counters, const float4* __restrict__ rays);
-// (rt_lenssource.inl: the same behind a table of lens rays, rtgpu_set_lens_source)
+// (the same behind a table of lens rays, rtgpu_set_lens_source)
 __global__ void __launch_bounds__(RT_BLOCK) k_generate_dense_lens(const RtSceneDesc scene, const DevPass* __restrict__ passes, uint32_t slotsPerPass, const Paths paths,
                                                                   const uint32_t* __restrict__ slotPixel, uint32_t numSlots, uint32_t shardCapacity, uint32_t* __restrict__ counts,
                                                                   unsigned long long* counters, const float4* __restrict__ table, uint32_t lens, uint32_t bokehShape);

@@ -12,8 +12,8 @@
 //   rt_query.inl          batched ray queries around the walks above (rtgpu_trace_rays)
 //   rt_denoise.inl        the a-trous filter (rtgpu_filter_atrous, rtgpu_denoise)
 //   rt_temporal.inl       temporal accumulation (rtgpu_temporal_accumulate, rtgpu_denoise_temporal)
-//   rt_raysource.inl      the ray source: k_generate fed from a table of rays, the table's check, the camera's rays written out (rtgpu_set_ray_source)
-//   rt_lenssource.inl     the lens source: k_generate fed from a table of rays with footprints and a thin lens, its check and exports (rtgpu_set_lens_source)
+//   rt_raysource.inl      the primary-ray sources: k_generate fed from a table of rays (rtgpu_set_ray_source) or of rays with footprints and a thin lens
+//                         (rtgpu_set_lens_source), the tables' checks, the camera's rays and footprints and a lens table's rays written out
 // The host side (rt_runtime.hip) launches them through the declarations of rt_trace_kernels.h.
 //
 // Compile: hipcc --offload-arch=gfx950 -O3 -ffp-contract=off
@@ -57,4 +57,3 @@ RT_K_TRACE_PER_RAY_INSTANCES(RT_X)
 #include "rt_denoise.inl"
 #include "rt_temporal.inl"
 #include "rt_raysource.inl"
-#include "rt_lenssource.inl"

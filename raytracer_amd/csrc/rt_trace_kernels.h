@@ -157,7 +157,7 @@ __global__ void __launch_bounds__(RT_BLOCK) k_generate_rays(const RtSceneDesc sc
                                                             unsigned long long* counters, const float4* __restrict__ rays);
 __global__ void __launch_bounds__(RT_BLOCK) k_ray_source_check(const float4* __restrict__ rays, uint32_t count, uint32_t* __restrict__ outDegenerate);
 __global__ void __launch_bounds__(RT_BLOCK) k_camera_rays(const RtCamera camera, float sampleOffsetX, float sampleOffsetY, uint32_t width, uint32_t height, float4* __restrict__ out);
-// the lens source (rt_lenssource.inl): k_generate behind a table of lens rays; the table's check; the rays of a pass and the camera's footprints written out
+// the lens source (rt_raysource.inl): k_generate behind a table of lens rays; the table's check; the rays of a pass and the camera's footprints written out
 __global__ void __launch_bounds__(RT_BLOCK) k_generate_lens(const RtSceneDesc scene, const DevPass* __restrict__ passes, uint32_t slotsPerPass,
                                                             const Paths paths, const uint32_t* __restrict__ slotPixel, uint32_t numSlots,
                                                             uint32_t* __restrict__ queue, uint32_t* __restrict__ queueCount,

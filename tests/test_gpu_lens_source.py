@@ -501,6 +501,14 @@ def test_one_context_holds_one_source_and_what_keeps_or_drops_it(built):
     same(b.sum_buffer(), fresh.sum_buffer(), "resized")
     b.set_lens_source(lens)   # (its buffers went with the old frame: they come back)
     assert b.ray_source_kind() == 2
+    # the exports of one context share one device copy, sized in bytes: it grows from 32 to 128 bytes per pixel and is reused at 32 (b has exported nothing yet)
+    b.set_ray_source(None)
+    for entry in ("camera_rays", "camera_footprints", "camera_rays"):
+        same(getattr(b, entry)(params[0]), getattr(viewport(scene, w, h, spread=0.5, max_ray_depth=depth), entry)(params[0]), entry + " on a context that has exported before")
+    other = viewport(scene, w, h, spread=0.5, max_ray_depth=depth)
+    for v in (b, other):
+        v.set_lens_source(lens)
+    same(b.lens_source_rays(params[1]), other.lens_source_rays(params[1]), "lens_source_rays on a context that has exported before")
 
 
 def test_a_multi_device_context(built):
