@@ -1621,6 +1621,8 @@ static void genBmp()
     writeRaw("bmp_kat.bin", out.data(), out.size() * 4);
 }
 
+#include "kat_edges.inl"
+
 int main(int argc, char** argv)
 {
     if (argc > 1) gOutDir = argv[1];
@@ -1646,6 +1648,7 @@ int main(int argc, char** argv)
     genDebug();
     genDds();
     genBmp();
+    genEdges();
     printf("done\n");
     return 0;
 }

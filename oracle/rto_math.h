@@ -244,7 +244,9 @@ static inline Ray transformRayUnsafe(const M4& m, const Ray& ray)   // Matrix4.h
 }
 
 // ---- transcendental approximations, Core/Math/Transcendental.cpp ---------------------------------
-static inline int32_t cvtRN(float f) { return (int32_t)lrintf(f); }   // _mm_cvtps_epi32, default rounding mode
+// _mm_cvtps_epi32, default rounding mode.  NaN and everything outside [-2^31, 2^31) give INT_MIN (the "integer indefinite"); a cast of lrintf's
+// 64-bit result wraps instead (tests/golden/edges, DESIGN_PARITY.md)
+static inline int32_t cvtRN(float f) { return fabsf(f) < 2147483648.0f ? (int32_t)lrintf(f) : (int32_t)0x80000000; }
 // vector Sin, one lane (Transcendental.cpp:51-76): round-to-nearest range reduction, fused Horner
 static inline float sinLane(float a)
 {

@@ -221,7 +221,9 @@ RT_DEV Ray transformRayUnsafe(const M4& m, const Ray& ray)   // Matrix4.h:245-25
 }
 
 // ---- transcendental approximations, Core/Math/Transcendental.cpp ---------------------------------
-RT_DEV int32_t cvtRN(float f) { return __float2int_rn(f); }   // _mm_cvtps_epi32, default rounding mode
+// _mm_cvtps_epi32, default rounding mode.  NaN and everything outside [-2^31, 2^31) give INT_MIN (the "integer indefinite") where the device's
+// conversion saturates (NaN -> 0, +big -> INT_MAX): Sin of a quotient beyond int32, a NaN film position (tests/golden/edges, DESIGN_PARITY.md)
+RT_DEV int32_t cvtRN(float f) { return fabsf(f) < 2147483648.0f ? __float2int_rn(f) : (int32_t)0x80000000; }
 // vector Sin, one lane (Transcendental.cpp:51-76): round-to-nearest range reduction, fused Horner
 RT_DEV float sinLane(float a)
 {

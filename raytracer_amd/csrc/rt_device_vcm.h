@@ -74,7 +74,7 @@ RT_DEV bool filmSplatPixel(V4 pos, uint32_t width, uint32_t height, V4 u, uint32
         if (u.y < fracY) iy++;
     }
     const int32_t x = ix;
-    const int32_t y = (int32_t)(height - 1u) - (int32_t)filmCoords.y;
+    const int32_t y = (int32_t)((height - 1u) - (uint32_t)cvttToInt(filmCoords.y));   // int32(float): INT_MIN for NaN and out of range, wrapping subtraction
     if ((uint32_t)x < width && (uint32_t)y < height) { outX = (uint32_t)x; outY = (uint32_t)y; return true; }
     return false;
 }

@@ -36,6 +36,36 @@ def all_lights_scene(aspect):
     return s, cam
 
 
+def edge_materials_scene(aspect):
+    """Materials and lights on the branch boundaries tests/golden/edges pins per function, for the shading kernels' own compilation of them:
+    roughness exactly SpecularEventRoughnessTreshold = 0.005 (the rough lobe) and its lower neighbour (the specular fall-back) on a rough
+    metal, a rough dielectric and a rough plastic; a dielectric with IoR = 1; a metal with IoR = 0, K = 0; a sphere light of radius 0.01 at
+    distance > 9 from every surface (cosThetaMax > 0.999999: the FLT_MAX pdf branch of SphereShape::Sample); a rect light coplanar with the
+    back wall (cosNormalDir = 0 from the wall, grazing from the floor next to it)."""
+    s = ra.Scene()
+    threshold = np.float32(0.005)
+    below = np.nextafter(threshold, np.float32(0.0))
+    white = s.add_material("diffuse", (0.8, 0.8, 0.8))
+    kinds = [("roughMetal", dict(roughness=float(threshold), ior=0.2, k=3.0)), ("roughMetal", dict(roughness=float(below), ior=0.2, k=3.0)),
+             ("roughDielectric", dict(roughness=float(threshold))), ("roughDielectric", dict(roughness=float(below))),
+             ("roughPlastic", dict(roughness=float(threshold))), ("roughPlastic", dict(roughness=float(below))),
+             ("dielectric", dict(ior=1.0)), ("metal", dict(ior=0.0, k=0.0))]
+    for i, (bsdf, args) in enumerate(kinds):
+        m = s.add_material(bsdf, (0.9, 0.7, 0.5) if i % 2 else (0.5, 0.7, 0.9), **args)
+        x, z = -3.0 + 2.0 * (i % 4), -1.0 + 2.0 * (i // 4)
+        if i % 3 == 2:
+            s.add_box((0.6, 0.6, 0.6), ra.transform_from_euler((x, -1.4, z), (0.0, 20.0, 0.0)), m)
+        else:
+            s.add_sphere(0.6, ra.transform_from_euler((x, -1.4, z)), m)
+    s.add_rect((6.0, 6.0), ra.transform_from_euler((0.0, -2.0, 0.0), (-90.0, 0.0, 0.0)), white)        # floor
+    s.add_rect((6.0, 4.0), ra.transform_from_euler((0.0, 2.0, -3.0), (0.0, 0.0, 0.0)), white)          # back wall, facing +z
+    s.add_area_light("rect", [2.0, 1.0], (6.0, 5.0, 4.0), ra.transform_from_euler((0.0, 1.0, -3.0), (0.0, 0.0, 0.0)))   # in the wall's plane
+    s.add_area_light("sphere", [0.01], (4.0e5, 4.0e5, 3.0e5), ra.transform_from_euler((1.0, 9.0, 2.0)))
+    s.build()
+    cam = ra.Camera((0.3, 1.5, 8.0), (14.0, 180.0, 0.0), aspect, 50.0)
+    return s, cam
+
+
 def mesh_scene(aspect, triangles=20000, with_analytic=True):
     """Sponza-class mesh (small) + a few analytic instances so that both BVH levels are exercised."""
     pos, idx, nrm, tan, uv, mat = scenes.sponza_class_mesh(triangles, seed=5)

@@ -79,6 +79,19 @@ def test_every_light_and_bsdf_all_strategy(built, walk):
     assert_identical(*run_both(scene, camera, w, h, walk=walk, passes=3, max_ray_depth=6, dimensions=128, light_sampling_all=True))
 
 
+def test_edge_materials_and_lights_bit_exact(built, walk):
+    """The branches tests/golden/edges pins through the KAT hook (compiled into the traversal translation unit), as the SHADING kernels
+    compile them: roughness at SpecularEventRoughnessTreshold and one ulp below on the three rough BSDFs that fall back to a specular event,
+    a dielectric with IoR = 1, a metal with IoR = 0 and K = 0, a sphere light on its FLT_MAX pdf branch and a rect light coplanar with a wall
+    (scene_zoo.edge_materials_scene).  Sum buffers and counters bit for bit against the oracle; the default strategy (Single) picks one of
+    the two lights per vertex, so both are sampled across the frame."""
+    w, h = 48, 32
+    scene, camera = scene_zoo.edge_materials_scene(w / h)
+    out = run_both(scene, camera, w, h, walk=walk, passes=3, max_ray_depth=6)
+    assert_identical(*out)
+    assert out[2]["numShadowRays"] > 0 and out[2]["numRays"] > 3 * w * h
+
+
 def test_single_strategy_many_lights_and_dimension_overflow(built, walk):
     """Single strategy with 8 lights (per-pixel fallback generator picks the light) and only 16 Halton
     dimensions (samples past them come from the fallback generator, GenericSampler.cpp:106-109)."""
