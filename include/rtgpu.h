@@ -1543,6 +1543,37 @@ typedef struct RtWalkInfo
 } RtWalkInfo;
 int rtgpu_get_walk_info(RtgpuContext* ctx, RtWalkInfo* out);
 
+/* Beam lists: while a frame accumulates under a still pinhole camera, the camera rays of a dense batch over a single-mesh scene take their leaves from
+ * per-tile lists (a tile = 64 consecutive slots of the slot table = one 8 x 8 pixel block) built once, with the second batch the camera serves, in place of
+ * walking the tree on every pass.  Results do not depend on it, bit for bit.  RTGPU_BEAM_LISTS=0 turns it off.
+ *   rtgpu_set_beam_margin    m, in pixels: a pass whose |sampleOffset| exceeds m on an axis walks the tree.  The lists hold every leaf a ray of the tile can
+ *                            pass at offsets within m, so a larger m serves more passes from longer lists.  Default 1.5 (3 x the default
+ *                            antiAliasingSpread: sampleOffset is normal with that deviation); a renderer with another spread sets 3 x its own.
+ *   rtgpu_get_beam_list_info synchronises, then reports (of the first device of a multi-device context):
+ *       builds               build launches since the context was created (a camera that changes with every batch never causes one)
+ *       allocations          builds that took new device arrays (numTiles x capacity x 8 bytes and numTiles x 4): a build behind idle lanes rewrites the
+ *                            arrays the context has, so a caller who synchronises between rebuilds allocates once
+ *       retiredArrays        arrays of earlier builds that launches in flight could still read when the call was made (before it synchronised, which
+ *                            frees them, as every synchronising call does); never more than 4
+ *       valid                lists exist for the last batch's camera; capacity, numTiles, margin: theirs
+ *       packetsScanned / packetsWalkedOffset / packetsWalkedNoList   packets (waves of 64 camera rays) of launches that had lists: served from their
+ *                            tile's list, walked because their pass's offset exceeds the margin, walked because their tile has no list (more leaves than
+ *                            the capacity) or the packet straddles two tiles (a slot table whose length is no multiple of 64)
+ *   rtgpu_read_beam_lists    the lists themselves: counts[numTiles] (0xFFFFFFFF: no list) and entries[numTiles * capacity] as {leaf reference, bits of dmin}
+ *                            pairs, ascending; fromHost != 0: not the device's arrays but what the pure host builder makes of the same tree, slot table and
+ *                            key (the reference the build kernel is tested against).  RTGPU_ERR_NOT_READY without valid lists. */
+typedef struct RtBeamListInfo
+{
+    uint64_t builds, packetsScanned, packetsWalkedOffset, packetsWalkedNoList;
+    uint32_t valid, capacity, numTiles;
+    float    margin;
+    uint64_t allocations;
+    uint32_t retiredArrays, reserved;
+} RtBeamListInfo;
+int rtgpu_set_beam_margin(RtgpuContext* ctx, float pixels);
+int rtgpu_get_beam_list_info(RtgpuContext* ctx, RtBeamListInfo* out);
+int rtgpu_read_beam_lists(RtgpuContext* ctx, int fromHost, uint32_t* counts, uint32_t* entries);
+
 /* How a multi-device context (rtgpu_create_multi) exchanges the peers' tiles at read-back, and why -- so that a first run on a real multi-GPU node
  * explains itself (the reference has no counterpart: its only fan-out is Core/Utils/ThreadPool.cpp:57-117 under Viewport.cpp:244-262).
  *   gatherMode    0 one device (nothing to gather), 1 a kernel on the first device reads the peers' sum buffers in place (peer access over xGMI),

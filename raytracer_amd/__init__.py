@@ -68,6 +68,10 @@ def rtgpu_lib():
         # known-answer hooks of post-processing: (ctx, params[n], rgb[n * 3], n, outBGR[n], outToneMapped[n * 3] or NULL), (ctx, rgb in place, width, height, sigma)
         _rtgpu.rtgpu_kat_postprocess.argtypes, _rtgpu.rtgpu_kat_postprocess.restype = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p], C.c_int
         _rtgpu.rtgpu_kat_blur.argtypes, _rtgpu.rtgpu_kat_blur.restype = [C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32, C.c_float], C.c_int
+        # beam lists: (ctx, pixels), (ctx, outInfo), (ctx, fromHost, counts, entries)
+        _rtgpu.rtgpu_set_beam_margin.argtypes, _rtgpu.rtgpu_set_beam_margin.restype = [C.c_void_p, C.c_float], C.c_int
+        _rtgpu.rtgpu_get_beam_list_info.argtypes, _rtgpu.rtgpu_get_beam_list_info.restype = [C.c_void_p, C.c_void_p], C.c_int
+        _rtgpu.rtgpu_read_beam_lists.argtypes, _rtgpu.rtgpu_read_beam_lists.restype = [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p], C.c_int
     return _rtgpu
 
 
@@ -249,6 +253,12 @@ class RtMultiInfo(C.Structure):
     _fields_ = [("numDevices", C.c_uint32), ("gatherMode", C.c_uint32), ("gatherReason", C.c_uint32), ("reasonDevice", C.c_int32), ("reasonError", C.c_int32),
                 ("devices", C.c_int32 * 16), ("peerAccess", C.c_uint32 * 16), ("reserved", C.c_uint32), ("gathers", C.c_uint64),
                 ("lastGatherMs", C.c_double), ("totalGatherMs", C.c_double)]
+
+
+class RtBeamListInfo(C.Structure):
+    _fields_ = [("builds", C.c_uint64), ("packetsScanned", C.c_uint64), ("packetsWalkedOffset", C.c_uint64), ("packetsWalkedNoList", C.c_uint64),
+                ("valid", C.c_uint32), ("capacity", C.c_uint32), ("numTiles", C.c_uint32), ("margin", C.c_float),
+                ("allocations", C.c_uint64), ("retiredArrays", C.c_uint32), ("reserved", C.c_uint32)]
 
 
 def multi_info(ctx):
@@ -1265,6 +1275,28 @@ class Viewport:
                 d["numRetracedRays"] = int(raw.numRetracedRays)
                 d["numUntrustedRays"], d["numStackOverflowRays"], d["diag2"] = int(raw._reserved[0]), int(raw._reserved[1]), int(raw._reserved[2])
         return d
+
+    # ---- beam lists (include/rtgpu.h: a still camera's per-tile leaf lists) ----------------------------------------------------------------
+    def set_beam_margin(self, pixels):
+        if rtgpu_lib().rtgpu_set_beam_margin(self.device_context(), float(pixels)) != 0:
+            raise RuntimeError(rtgpu_lib().rtgpu_last_error().decode())
+
+    def beam_list_info(self):
+        """rtgpu_get_beam_list_info as a dict (synchronises): builds, packetsScanned, packetsWalkedOffset, packetsWalkedNoList, valid, capacity, numTiles, margin, allocations, retiredArrays."""
+        info = RtBeamListInfo()
+        if rtgpu_lib().rtgpu_get_beam_list_info(self.device_context(), C.byref(info)) != 0:
+            raise RuntimeError(rtgpu_lib().rtgpu_last_error().decode())
+        return {name: getattr(info, name) for name, _ in RtBeamListInfo._fields_}
+
+    def beam_lists(self, from_host=False):
+        """The valid lists as (counts[numTiles], entries[numTiles, capacity, 2] = {leaf reference, bits of dmin}); `from_host`: the pure host builder's for the
+        same key instead of the device's arrays."""
+        info = self.beam_list_info()
+        counts = np.zeros(max(1, info["numTiles"]), dtype=np.uint32)
+        entries = np.zeros((max(1, info["numTiles"]), max(1, info["capacity"]), 2), dtype=np.uint32)
+        if rtgpu_lib().rtgpu_read_beam_lists(self.device_context(), int(bool(from_host)), counts.ctypes.data_as(C.c_void_p), entries.ctypes.data_as(C.c_void_p)) != 0:
+            raise RuntimeError(rtgpu_lib().rtgpu_last_error().decode())
+        return counts, entries
 
     # ---- batched ray queries (include/rtgpu.h: rtgpu_trace_rays / rtgpu_trace_rays_async) -----------------------------------------------
     def trace_rays(self, origins, directions, max_distance=float("inf"), surfaces=False):

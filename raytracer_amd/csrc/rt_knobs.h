@@ -65,6 +65,10 @@ RT_KNOB_ONCE(bool, denoiseTiled, envInt("RTGPU_DENOISE_TILED", 1) != 0)         
 static inline uint32_t wideDrainAbort() { return (uint32_t)envInt("RTGPU_WIDE_DRAIN_ABORT", 0); }   // test hook; 0: off
 static inline uint32_t wideDiagMode() { return (uint32_t)envInt("RTGPU_WIDE_DIAG", 0); }
 static inline bool packets() { return envInt("RTGPU_PACKET", 1) != 0; }
+// every dense batch: a still camera's packets take their leaves from per-tile lists (rt_beam_lists.h; beamListsFor); 0: they walk.  Same bits either way
+static inline bool beamLists() { return envInt("RTGPU_BEAM_LISTS", 1) != 0; }
+// test hook: entries a tile's list may hold, 1 .. RT_BEAM_MAX_CAPACITY (a tile with more leaves has no list and walks)
+static inline uint32_t beamListCap() { const int v = envInt("RTGPU_BEAM_LIST_CAP", (int)RT_BEAM_MAX_CAPACITY); return v < 1 ? 1u : (v > (int)RT_BEAM_MAX_CAPACITY ? RT_BEAM_MAX_CAPACITY : (uint32_t)v); }
 // every launch of k_shade_dense: the launch-uniform tables (objects, meshes, materials, lights, seed rows) from LDS copies; 0: everything from memory; same bits either way
 static inline bool shadeStage() { return envInt("RTGPU_SHADE_STAGE", 1) != 0; }
 // every rtgpu_render_aovs: pixels per chunk, 1 .. 4 M (the tests run a small frame in several chunks)

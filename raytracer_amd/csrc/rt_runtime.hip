@@ -212,6 +212,9 @@ RTGPU_API void rtgpu_destroy(RtgpuContext* c)
     freeDenoise(c);
     freeRaySource(c);
     freeScene(c); freeFilm(c);
+    beamFreeRetired(c);
+    devFree(c->beam.entries, c->beam.counts, c->beam.stats);
+    if (c->beam.built) (void)hipEventDestroy(c->beam.built);
     for (uint32_t i = 0; i < RT_MAX_LANES; ++i)
     {
         freePaths(c->lanes[i]);
@@ -261,6 +264,7 @@ static std::vector<uint32_t> buildSlotTable(uint32_t width, uint32_t height, Rtg
 static int rebuildSlots(RtgpuContext* c)
 {
     devFree(c->slotPixel);
+    beamInvalidate(c); beamFreeRetired(c);   // beam lists are per tile of the table that goes (like it, nothing in flight reads them here)
     const std::vector<uint32_t> slots = buildSlotTable(c->width, c->height, c->shard, c->activeMask);
     c->numSlots = (uint32_t)slots.size();
     // launches of a batch should stay large enough to fill 256 CUs: a 1/8 shard of a 1080p frame batches 16 passes
@@ -794,6 +798,58 @@ RTGPU_API int rtgpu_get_walk_info(RtgpuContext* c, RtWalkInfo* out)
     const uint32_t kernel = !useWide(c) ? RTGPU_WALK_BINARY : (c->wide.nodes ? RTGPU_WALK_WIDE : RTGPU_WALK_WIDE2);
     out->kernel = kernel; out->reserved = 0u;
     out->nodeBytes = c->walkNodeBytes[kernel]; out->leafBoxBytes = c->walkLeafBoxBytes[kernel]; out->triangleBytes = c->walkTriangleBytes;
+    return RTGPU_OK;
+}
+
+// ---- beam lists (rt_beam_lists.h; the policy is beamListsFor, rt_runtime_render.inl) ----
+RTGPU_API int rtgpu_set_beam_margin(RtgpuContext* c, float pixels)
+{
+    if (!c) return fail(RTGPU_ERR_INVALID_ARGUMENT, "NULL context");
+    if (!(pixels >= 0.0f) || !(pixels <= 64.0f)) return fail(RTGPU_ERR_INVALID_ARGUMENT, "the beam margin is 0 .. 64 pixels");
+    RT_FAN_OUT(c, rtgpu_set_beam_margin(peer, pixels));
+    c->beam.margin = pixels;   // (part of the lists' key: the next still batch builds for it)
+    return RTGPU_OK;
+}
+
+RTGPU_API int rtgpu_get_beam_list_info(RtgpuContext* c, RtBeamListInfo* out)
+{
+    if (!c || !out) return fail(RTGPU_ERR_INVALID_ARGUMENT, "NULL argument");
+    { int fr = flushQueued(c); if (fr) return fr; }   // (a queued batch may build)
+    const uint32_t retiredArrays = (uint32_t)c->beam.retired.size();   // before the lanes go idle, which frees them
+    int r = rtgpu_synchronize(c); if (r) return r;
+    const RtgpuContext::Beam& b = c->beam;
+    unsigned long long stats[3] = { 0ull, 0ull, 0ull };
+    if (b.stats) HIP_TRY(rtMemcpy(stats, b.stats, sizeof(stats), hipMemcpyDeviceToHost));
+    out->allocations = b.allocations; out->retiredArrays = retiredArrays; out->reserved = 0u;
+    out->builds = b.builds; out->packetsScanned = stats[0]; out->packetsWalkedOffset = stats[1]; out->packetsWalkedNoList = stats[2];
+    out->valid = b.valid ? 1u : 0u; out->capacity = b.valid ? b.capacity : 0u; out->numTiles = b.valid ? b.numTiles : 0u; out->margin = b.valid ? b.builtMargin : b.margin;
+    return RTGPU_OK;
+}
+
+RTGPU_API int rtgpu_read_beam_lists(RtgpuContext* c, int fromHost, uint32_t* counts, uint32_t* entries)
+{
+    if (!c || !counts || !entries) return fail(RTGPU_ERR_INVALID_ARGUMENT, "NULL argument");
+    int r = rtgpu_synchronize(c); if (r) return r;
+    const RtgpuContext::Beam& b = c->beam;
+    if (!b.valid || !c->wide.nodes || c->updatable.objects.size() != 1u) return fail(RTGPU_ERR_NOT_READY, "no valid beam lists");
+    if (!fromHost)
+    {
+        HIP_TRY(rtMemcpy(counts, b.counts, (size_t)b.numTiles * sizeof(uint32_t), hipMemcpyDeviceToHost));
+        HIP_TRY(rtMemcpy(entries, b.entries, (size_t)b.numTiles * b.capacity * sizeof(BeamEntry), hipMemcpyDeviceToHost));
+        return RTGPU_OK;
+    }
+    std::vector<float4> nodes((size_t)c->wide.numNodes * 4u), gate((size_t)(c->walkLeafBoxBytes[RTGPU_WALK_WIDE] / sizeof(float4)));
+    std::vector<uint32_t> slots(c->numSlots);
+    HIP_TRY(rtMemcpy(nodes.data(), c->wide.nodes, nodes.size() * sizeof(float4), hipMemcpyDeviceToHost));
+    HIP_TRY(rtMemcpy(gate.data(), c->wide.gate, gate.size() * sizeof(float4), hipMemcpyDeviceToHost));
+    HIP_TRY(rtMemcpy(slots.data(), c->slotPixel, slots.size() * sizeof(uint32_t), hipMemcpyDeviceToHost));
+    BeamCamera local;
+    float lo[3], hi[3];
+    beamTreeBounds(c->wide.base, c->wide.step, lo, hi);
+    if (!beamCameraFor(b.camera, c->updatable.objects[0].invTransform, b.width, b.height, b.builtMargin, lo, hi, local)) return fail(RTGPU_ERR_NOT_READY, "no valid beam lists");
+    const BeamListsHost h = buildBeamLists(nodes.data(), gate.data(), c->wide.base, c->wide.step, slots.data(), c->numSlots, local, b.capacity);
+    memcpy(counts, h.counts.data(), h.counts.size() * sizeof(uint32_t));
+    memcpy(entries, h.entries.data(), h.entries.size() * sizeof(BeamEntry));
     return RTGPU_OK;
 }
 

@@ -110,6 +110,7 @@ struct TraceStep
     bool mayTraceUndecidedRaysItself = true;   // a 4-wide walk may trace what it does not decide in its own blocks (launchTraceWide's policy decides whether it does)
     uint32_t bounce = 0u;                      // for the policies that depend on it (the block-local second walk, the packet walk of camera rays)
     uint4* rayCounts = nullptr;                // binary walk only: every closest-hit ray's own test counts (TravTuning::rayCounts); makes the walk a counting one
+    BeamLists beam = {};                       // bounce 0 of a dense batch from a still camera: the lists k_trace_packet may scan (entries == nullptr: none)
 };
 
 // LaneCounts names the first six; eight are allocated and zeroed: 32 bytes per bounce are a multiple of 16 at any depth, which the runtime's memset fills with
@@ -384,6 +385,27 @@ struct RtgpuContext
         bool any() const { return kind != 0u; }   // a source of either kind: the camera is not read
     } raySource;
 
+    // beam lists (rt_beam_lists.h; the policy: beamListsFor, rt_runtime_render.inl): a still camera's per-tile leaf lists, which k_trace_packet scans in place of
+    // its walk.  They belong to ONE combination of camera, frame size, slot table (so shard and active blocks), geometry, margin and capacity: the first, the last
+    // two and the size are compared by beamListsFor; whatever replaces one of the others calls beamInvalidate.  A launch in flight may read the arrays: while one
+    // may (`inFlight`), a rebuild takes new arrays and retires these; retired arrays are freed wherever the lanes go idle (syncLanes: every synchronising call,
+    // reset, upload, update, resize), and a caller who never synchronises holds at most RT_BEAM_MAX_RETIRED of them.  Behind idle lanes a rebuild of the same
+    // size rewrites the arrays in place: an animation that deforms its mesh every frame, or a viewer that reads back between camera moves, allocates once.
+    struct Beam
+    {
+        BeamEntry* entries = nullptr; uint32_t* counts = nullptr;
+        uint32_t capacity = 0, numTiles = 0;
+        bool valid = false;
+        RtCamera camera = {}; uint32_t width = 0, height = 0; float builtMargin = 0.0f;   // what `entries` were built for
+        hipEvent_t built = nullptr; int builtLane = -1; uint32_t lanesWaited = 0u;        // behind the build kernel; the lanes (bits) that wait for it already
+        bool haveLast = false; RtCamera lastCamera = {};   // the camera of the previous batch: a build needs two batches from one camera
+        float margin = 1.5f;                               // m in pixels: rtgpu_set_beam_margin (the host mirror sets 3 x antiAliasingSpread)
+        unsigned long long* stats = nullptr;               // device, BeamLists::stats
+        uint64_t builds = 0, allocations = 0;              // build launches; those of them that took new arrays (the others rewrote idle ones in place)
+        bool inFlight = false;                             // a launch submitted since the lanes were last idle (syncLanes) may read `entries`
+        std::vector<void*> retired;                        // at most RT_BEAM_MAX_RETIRED arrays: beamListsFor lets the lanes go idle before it retires more
+    } beam;
+
     // timing
     bool timing = false;
     struct Timed { int kc; hipEvent_t a, b; };
@@ -405,8 +427,18 @@ static void freeScene(RtgpuContext* c)
     c->sceneReady = false;
 }
 
+// the beam lists no longer describe what the next batch renders (scene, geometry, slot table, ray source): the next still camera builds anew
+static void beamInvalidate(RtgpuContext* c) { c->beam.valid = false; c->beam.haveLast = false; }
+// only where no launch is in flight (the callers have synchronised the lanes)
+static void beamFreeRetired(RtgpuContext* c)
+{
+    for (void* p : c->beam.retired) (void)hipFree(p);
+    c->beam.retired.clear();
+}
+
 static void freeFilm(RtgpuContext* c)
 {
+    beamInvalidate(c);   // the slot table goes
     devFree(c->sum, c->secondary, c->slotPixel);
     c->numSlots = 0;
 }
@@ -422,6 +454,8 @@ static hipError_t syncLanes(RtgpuContext* c)
     hipError_t first = hipSuccess;
     for (uint32_t i = 0; i < RT_MAX_LANES; ++i)
         if (c->lanes[i].stream) { const hipError_t e = hipStreamSynchronize(c->lanes[i].stream); if (first == hipSuccess) first = e; }
+    // every lane is idle: no launch reads beam-list arrays any more -- the retired ones go, and the ones in use may be rewritten in place (beamListsFor)
+    if (first == hipSuccess) { beamFreeRetired(c); c->beam.inFlight = false; }
     return first;
 }
 

@@ -40,6 +40,7 @@ static int raySourceBegin(RtgpuContext* c, const void* rays, uint64_t count, boo
     HIP_TRY(syncLanes(c));
     waitQueries(c);                                   // (AOV calls on a caller's stream read the table too)
     waitLensExport(c);                                // (and rtgpu_read_lens_source_rays_async reads a lens table)
+    beamInvalidate(c);                                // (beam lists are the camera's: a source of either kind renders without them, and the camera after it builds anew)
     if (!rays) { dropRaySource(c); clear = true; }
     return RTGPU_OK;
 }

@@ -231,6 +231,9 @@ static int refitTables(RtgpuContext* c, uint32_t meshIndex, const RefitSource& s
     const bool twoLevel = !up.levels.empty(), haveWide = refitHaveWide(c, state);
     const bool fromDevice = src.devPositions != nullptr;
     const hipStream_t stream = c->lanes[0].stream;
+    // beam lists hold the leaf boxes as they were: invalid from here on, BEFORE anything is rewritten -- an error return further down leaves tables half
+    // refitted, and stale lists would change primary hits silently
+    beamInvalidate(c);
 
     // device state of the mesh (first update) and the new positions
     int r;

@@ -156,7 +156,7 @@ static void launchTraceWide(RtgpuContext* c, const TraceStep& s)
     const bool packets = knobs::packets();   // (read per launch: the tests switch it)
     if (packets && !diag && s.bounce == 0u && s.denseCounts != nullptr && s.shadowQueue == nullptr && s.queue == nullptr)
     {
-        hipLaunchKernelGGL(k_trace_packet, dim3(c->numCUs * knobs::packetBlocksPerCU()), block, 0, s.stream, c->sceneDev, c->wide, s.paths, s.cursor, s.counters, tune);
+        hipLaunchKernelGGL(k_trace_packet, dim3(c->numCUs * knobs::packetBlocksPerCU()), block, 0, s.stream, c->sceneDev, c->wide, s.paths, s.cursor, s.counters, tune, s.beam);
         return;
     }
     if (diag) tune.localExact = knobs::wideDiagMode();   // 2: stack-depth histogram instead of the visit counts (tools/wide_diag.py)
@@ -220,6 +220,80 @@ static uint32_t tailDepthFor(const RtgpuContext* c, uint32_t maxRayDepth, bool d
     return depth > maxRayDepth + 1u ? 0u : depth;
 }
 
+// Beam lists for the packet launch of a dense batch on lane `l` (rt_beam_lists.h; k_trace_packet's front end): `out.entries` stays null where the batch walks.
+// Lists exist for: a single-mesh scene served by k_trace_wide on the 24-entry stack class, packets on, intersection counters off, a mesh object with a rigid
+// transform, a pinhole camera (no depth of field, no barrel distortion: beamCameraFor) and no ray or lens source; every pass of the batch from ONE camera.
+// Key: camera bytes, frame size, margin m, capacity -- compared here; slot table (so shard, active blocks), geometry, object transform, source: whoever
+// replaces one calls beamInvalidate.
+// Build trigger: a batch that finds the camera of the PREVIOUS batch unchanged and no valid lists builds them, on its lane's stream in front of its packet
+// launch, followed by an event the other lanes wait for before their first packet launch that reads the lists.  A camera that moves every frame never pays for
+// a build (tests/test_gpu_beam_lists.py holds builds at 0 for a camera that changes with every batch; tools/bench_temporal.py's frames turn the camera in the same
+// way and are expected to build only in the tool's still reference render -- not measured); a frame that accumulates pays once, with its second batch.
+// Break-even (profiles/beam_lists_kernel_stats_serial.txt, the full-HD benchmark frame): the build is 128 us once, a scanned pass saves about 57 us of the
+// packet launch: paid back within 3 passes.
+// Arrays a launch in flight may read are never rewritten or freed, and a context holds a bounded number of them (RtgpuContext::Beam).
+static int beamListsFor(RtgpuContext* c, BatchLane& l, int laneIndex, const DevPass* passesHost, const DevPass* passesDev, uint32_t numPasses, BeamLists& out)
+{
+    RtgpuContext::Beam& b = c->beam;
+    const bool served = knobs::beamLists() && knobs::packets() && !knobs::wideDiag() && c->wide.nodes != nullptr && useWide(c) && stackClassOf(c) == 24u &&
+                        !c->raySource.any() && c->sceneDev.numObjects == 1u && c->updatable.objects.size() == 1u && c->numSlots != 0u;
+    bool oneCamera = served;
+    for (uint32_t i = 0; oneCamera && i < numPasses; ++i)
+        oneCamera = memcmp(&passesHost[i].camera, &passesHost[0].camera, sizeof(RtCamera)) == 0 && passesHost[i].width == c->width && passesHost[i].height == c->height;
+    if (!oneCamera) { b.haveLast = false; return RTGPU_OK; }
+    const RtCamera& camera = passesHost[0].camera;
+    const bool still = b.haveLast && memcmp(&b.lastCamera, &camera, sizeof(RtCamera)) == 0;
+    b.lastCamera = camera; b.haveLast = true;
+    const uint32_t capacity = knobs::beamListCap();
+    const bool keyed = b.valid && memcmp(&b.camera, &camera, sizeof(RtCamera)) == 0 && b.width == c->width && b.height == c->height && b.builtMargin == b.margin && b.capacity == capacity;
+    if (!keyed)
+    {
+        b.valid = false;
+        if (!still) return RTGPU_OK;
+        BeamCamera local;
+        float lo[3], hi[3];
+        beamTreeBounds(c->wide.base, c->wide.step, lo, hi);
+        if (!beamCameraFor(camera, c->updatable.objects[0].invTransform, c->width, c->height, b.margin, lo, hi, local)) return RTGPU_OK;
+        const uint32_t numTiles = (c->numSlots + 63u) / 64u;
+        // where the arrays come from: behind idle lanes the ones the context has are rewritten in place (same size) or freed; while a launch may read them
+        // they are retired and new ones taken -- after the lanes went idle (syncLanes frees what is retired) if that would exceed RT_BEAM_MAX_RETIRED
+        if (b.inFlight && b.entries && b.retired.size() + 2u > RT_BEAM_MAX_RETIRED) HIP_TRY(syncLanes(c));
+        if (b.inFlight)
+        {
+            if (b.entries) b.retired.push_back(b.entries);
+            if (b.counts) b.retired.push_back(b.counts);
+            b.entries = nullptr; b.counts = nullptr;
+        }
+        else if (b.entries && (b.numTiles != numTiles || b.capacity != capacity)) devFree(b.entries, b.counts);
+        if (!b.entries || !b.counts)
+        {
+            devFree(b.entries, b.counts);
+            HIP_TRY(hipMalloc((void**)&b.entries, (size_t)numTiles * capacity * sizeof(BeamEntry)));
+            HIP_TRY(hipMalloc((void**)&b.counts, (size_t)numTiles * sizeof(uint32_t)));
+            b.allocations++;
+        }
+        if (!b.stats)
+        {
+            HIP_TRY(hipMalloc((void**)&b.stats, 3 * sizeof(unsigned long long)));
+            HIP_TRY(hipMemsetAsync(b.stats, 0, 3 * sizeof(unsigned long long), l.stream));
+        }
+        if (!b.built) HIP_TRY(hipEventCreateWithFlags(&b.built, hipEventDisableTiming));
+        hipLaunchKernelGGL(k_beam_lists_build, dim3(numTiles), dim3(64), 0, l.stream, c->wide, c->slotPixel, c->numSlots, local, capacity, b.entries, b.counts);
+        HIP_TRY(hipGetLastError());
+        HIP_TRY(hipEventRecord(b.built, l.stream));
+        b.capacity = capacity; b.numTiles = numTiles; b.camera = camera; b.width = c->width; b.height = c->height; b.builtMargin = b.margin;
+        b.builtLane = laneIndex; b.lanesWaited = 1u << laneIndex; b.valid = true; b.builds++;
+    }
+    else if (!(b.lanesWaited & (1u << laneIndex)))
+    {
+        HIP_TRY(hipStreamWaitEvent(l.stream, b.built, 0));
+        b.lanesWaited |= 1u << laneIndex;
+    }
+    b.inFlight = true;
+    out.entries = b.entries; out.counts = b.counts; out.capacity = b.capacity; out.slotsPerPass = c->numSlots; out.margin = b.builtMargin; out.passes = passesDev; out.stats = b.stats;
+    return RTGPU_OK;
+}
+
 // The scene-class ladders of the shading kernels and of the fused tail (rt_shade_kernels.h, rt_tail_kernels.h): kLean class, plain path tracer, all lights
 #define RT_LAUNCH_SHADE_DENSE_STAGE(L, P, A, S) hipLaunchKernelGGL((k_shade_dense<L, P, A, S>), grid, block, 0, l.stream, c->sceneDev, passesDev, c->numSlots, in, out, dc, \
                                                               l.shadowQueues[depth & 1u], counts.shadowCounts + depth, l.home, c->counters)
@@ -241,7 +315,8 @@ static uint32_t denseStageMask(const RtgpuContext* c, uint32_t numPasses, uint32
 
 // The bounces of a batch with DENSE path state (rt_dense.inl): one next-event request per vertex (LightSamplingStrategy::Single, or none: "Path Tracer"),
 // or one per light under LightSamplingStrategy::All with a handful of lights (the benchmark scene has two): `denseAll`
-static int submitDenseBatch(RtgpuContext* c, BatchLane& l, const LaneCounts& counts, const DevPass* passesDev, uint32_t totalSlots, uint32_t maxRayDepth, bool denseAll, dim3 grid, uint32_t numDimensions)
+static int submitDenseBatch(RtgpuContext* c, BatchLane& l, const LaneCounts& counts, const DevPass* passesDev, uint32_t totalSlots, uint32_t maxRayDepth, bool denseAll, dim3 grid, uint32_t numDimensions,
+                            const BeamLists& beam)
 {
     const dim3 block(RT_BLOCK);
     const uint32_t numPasses = totalSlots / (c->numSlots ? c->numSlots : 1u), stage = denseStageMask(c, numPasses, numDimensions);
@@ -286,6 +361,7 @@ static int submitDenseBatch(RtgpuContext* c, BatchLane& l, const LaneCounts& cou
             counts.queuesOf(s, depth, false, haveShadow);   // (the closest-hit rays are the arena's live paths: no queue)
             counts.handOverOf(s, depth);
             s.denseCounts = haveClosest ? l.denseCounts + (size_t)plane * depth : nullptr; s.denseShardCapacity = shardCapacity; s.bounce = depth;
+            if (depth == 0u) s.beam = beam;
             launchTraceStep(c, s, useWide(c));
         }
         // bounce `depth`: shades the live paths; folds the visibility results of the previous bounce's zombies in (the last round does only that)
@@ -420,7 +496,12 @@ static int flushBatch(RtgpuContext* c, uint32_t maxPasses)
     HIP_TRY(hipMemsetAsync(l.queueCounts, 0, laneCountBytes(l), l.stream));
     const bool dense = c->denseAllowed && c->debugMode < 0 && maxLights <= RT_DENSE_MAX_LIGHTS && l.paths2.base != nullptr;
     const bool denseAll = dense && first.lightSamplingStrategy == RT_LIGHT_SAMPLING_ALL && !c->plainPathTracer;
-    if (dense) { r = submitDenseBatch(c, l, counts, passesDev, totalSlots, first.maxRayDepth, denseAll, grid, first.numDimensions); if (r) return r; }
+    if (dense)
+    {
+        BeamLists beam = {};
+        r = beamListsFor(c, l, laneIndex, c->passRingHost + firstSlot, passesDev, numPasses, beam); if (r) return r;
+        r = submitDenseBatch(c, l, counts, passesDev, totalSlots, first.maxRayDepth, denseAll, grid, first.numDimensions, beam); if (r) return r;
+    }
     else submitSlotBatch(c, l, counts, passesDev, totalSlots, first.maxRayDepth, grid);
 
     // the film is summed in pass order: this batch's accumulate runs after the previous batch's

@@ -136,6 +136,7 @@ RTGPU_API int rtgpu_upload_scene(RtgpuContext* c, const RtSceneDesc* s)
 
     // copy (nothing of the context has changed up to here: a refused scene leaves the old one, its photons and the temporal history as they were)
     c->temporal.have = false;   // rtgpu_denoise_temporal's history shows the old scene
+    beamInvalidate(c); beamFreeRetired(c);   // beam lists hold the old tree's leaves (the lanes are idle)
     freeScene(c);
     RtSceneDesc d = *s;
     int r;
@@ -281,6 +282,7 @@ RTGPU_API int rtgpu_update_objects(RtgpuContext* c, const RtSceneUpdate* u)
     if (u->lights) { up.lights.assign(u->lights, u->lights + u->numLights); c->axisParallelSun = hasAxisParallelSun(u->lights, u->numLights); }
     c->traversalStackNeed = topDepth + up.maxMeshDepth;
     c->vcm.havePhotons = false;   // photons of the scene as it was
+    beamInvalidate(c); beamFreeRetired(c);   // (and beam lists in the mesh object's frame as it was; the lanes are idle)
     if (c->temporal.have && c->temporal.then.size() == n)
     {
         // rtgpu_denoise_temporal's history stays: current object i is the one that was previousIndex[i], and carries that one's id and transform of then

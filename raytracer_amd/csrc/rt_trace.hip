@@ -5,6 +5,7 @@
 //   rt_wide_walk.h        the device parts the 4-wide walks share: slab test, hand-over lists, request ray, fold, interior step, mesh leaf (pair, gate, acceptance), finish, tallies
 //   rt_trace_wide.inl     k_trace_wide (4-wide tree of a single-mesh scene; the rays it does not decide go through the reference's walk in the same launch)
 //   rt_trace_packet.inl   k_trace_packet (the camera rays of a dense batch: one wave walks the 4-wide tree for an 8 x 8 pixel block, the node is uniform)
+//   rt_beam_lists.inl     k_beam_lists_build (a still camera's per-tile leaf lists, which k_trace_packet scans in place of its walk; rt_beam_lists.h)
 //   rt_trace_wide2.inl    k_trace_wide2 (4-wide top-level tree over 4-wide mesh trees)
 //   rt_generate.inl       k_generate (camera rays, slot-per-pixel pipeline)
 //   rt_post.inl           post-process, bloom, block errors, texture evaluation
@@ -33,6 +34,7 @@ using namespace rtd;
 #include "rt_wide_walk.h"
 #include "rt_trace_wide.inl"
 #include "rt_trace_packet.inl"
+#include "rt_beam_lists.inl"
 #include "rt_trace_wide2.inl"
 #include "rt_kat.inl"
 #include "rt_query.inl"

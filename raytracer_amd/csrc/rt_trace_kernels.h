@@ -2,6 +2,7 @@
 // (rt_runtime.hip), and the argument structs both sides share.  rt_trace.hip includes it for the structs only (RT_DEVICE_KERNELS).
 #pragma once
 #include "rt_trace_common.h"
+#include "rt_beam_lists.h"
 
 // known-answer hooks (rt_kat.inl): function ids = the ids the fixtures of tests/golden/*.kat carry in their headers (tests/golden/README.md)
 enum
@@ -97,7 +98,10 @@ struct TemporalChainPlanes { const float* virtualPosition; const uint32_t* chain
 template <int kStack, bool kCount, bool kPerRay = false> __global__ void RT_TRACE_ATTR(kStack) k_trace RT_K_TRACE_ARGS;
 template <int kStack, bool kDiag = false, bool kLocalExact = false> __global__ void RT_TRACE_ATTR(kStack) k_trace_wide RT_K_TRACE_WIDE_ARGS;
 template <int kStack> __global__ void RT_TRACE_ATTR(kStack) k_trace_wide2 RT_K_TRACE_WIDE2_ARGS;
-__global__ void __launch_bounds__(RT_BLOCK) k_trace_packet(const RtSceneDesc scene, const WideBvh bvh, const Paths paths, uint32_t* __restrict__ cursor, unsigned long long* counters, const WideTuning tune);
+__global__ void __launch_bounds__(RT_BLOCK) k_trace_packet(const RtSceneDesc scene, const WideBvh bvh, const Paths paths, uint32_t* __restrict__ cursor, unsigned long long* counters, const WideTuning tune,
+                                                           const BeamLists beam);
+__global__ void __launch_bounds__(64) k_beam_lists_build(const WideBvh bvh, const uint32_t* __restrict__ slotPixel, uint32_t numSlots, const BeamCamera cam, uint32_t capacity,
+                                                         BeamEntry* __restrict__ entries, uint32_t* __restrict__ counts);
 __global__ void __launch_bounds__(RT_BLOCK) k_generate(const RtSceneDesc scene, const DevPass* __restrict__ passes, uint32_t slotsPerPass,
                                                        const Paths paths, const uint32_t* __restrict__ slotPixel, uint32_t numSlots,
                                                        uint32_t* __restrict__ queue, uint32_t* __restrict__ queueCount,

@@ -14,6 +14,20 @@
 // a leaf's triangles count for a lane only behind the leaf's exact box and the `lo < best + tol` test, every candidate has the reference's (t, u, v), the
 // runner-up is tracked per lane, and a lane whose runner-up is within tol of its best -- or whose ray is not trusted (zero direction component, far origin)
 // -- goes to the exact queue for the reference's own walk (the k_trace launch behind this one).  Any-hit rays never come here (bounce 0 has none).
+//
+// Front end: a still camera's BEAM LISTS (rt_wide_format.h, rt_beam_lists.h).  While a frame accumulates, camera, scene and slot -> pixel table stay what they
+// are and a packet's rays differ from pass to pass by the pass's sub-pixel sampleOffset only: the ~20 interior steps find the same few leaves again.  Where the
+// launch has lists, the packet's pass has |sampleOffset| <= m on both axes and its tile has a list, the packet takes its leaves from the list, nearest first, and
+// runs the LEAF step below on each -- refill and finish are the walk's; otherwise it walks exactly as before.  Same loop, another source of `cur`.
+// Exactness, in rt_wide_grid.inl's terms:
+//   * a lane sees a SUPERSET of the leaves whose exact box its ray passes (the list holds every leaf whose exact box ANY ray of the tile can pass at any offset
+//     within m: rt_beam_lists.h, "Membership"), in another order (ascending dmin for the whole tile instead of its own entry distances);
+//   * a triangle counts only behind its leaf's exact box and the `lo < best + tol` test, with the reference's (t, u, v): the leaf step is the walk's, line by line;
+//   * the cut `dmin >= best + 2 tol` -- per lane: skip the entry; for every lane: leave the list, which ascends in dmin while best only falls -- is the interior
+//     step's `n < limit` with another conservative lower bound of the same exact entry distance (there: the entry into a stored box around the exact one; here:
+//     the eye's distance to the exact box, less a relative margin);
+//   * runner-ups within tol, hits in front of their box and untrusted rays go to the re-trace launch as before.
+// numRetracedRays may therefore differ from the walk's (another order finds other runner-ups); the sum buffers and the reference's counters do not.
 
 #ifdef RT_DEVICE_KERNELS
 #define RT_PACKET_CLAIM 4u            // packets a wave claims per atomic (1: +1 ms per launch in atomics; 16: uneven tails; profiles/r04_packet_ab.txt)
@@ -27,7 +41,12 @@ RT_DEV float packetPlaneLo(uint32_t w) { float f; asm("v_cvt_f32_u32_sdwa %0, %1
 RT_DEV float packetPlaneHi(uint32_t w) { float f; asm("v_cvt_f32_u32_sdwa %0, %1 dst_sel:DWORD dst_unused:UNUSED_PAD src0_sel:WORD_1" : "=v"(f) : "s"(w)); return f; }
 #define RT_PACKET_CE(ka, ra, kb, rb) { if (ka > kb) { const uint32_t tk_ = ka, tr_ = ra; ka = kb; ra = rb; kb = tk_; rb = tr_; } }
 
-__global__ void __launch_bounds__(RT_BLOCK) k_trace_packet(const RtSceneDesc scene, const WideBvh bvh, const Paths paths, uint32_t* __restrict__ cursor, unsigned long long* counters, const WideTuning tune)
+typedef uint32_t PacketU2 __attribute__((ext_vector_type(2)));
+typedef const __attribute__((address_space(4))) PacketU2* PacketConst2;
+typedef const __attribute__((address_space(4))) uint32_t* PacketConst1;
+
+__global__ void __launch_bounds__(RT_BLOCK) k_trace_packet(const RtSceneDesc scene, const WideBvh bvh, const Paths paths, uint32_t* __restrict__ cursor, unsigned long long* counters, const WideTuning tune,
+                                                           const BeamLists beam)
 {
     __shared__ uint32_t sDensePrefix[RT_DENSE_SHARDS + 1u];
     __shared__ uint32_t sTally[4];
@@ -44,6 +63,9 @@ __global__ void __launch_bounds__(RT_BLOCK) k_trace_packet(const RtSceneDesc sce
     const float inf = __uint_as_float(0x7f800000u);
     uint32_t numRetraced = 0, numUntrusted = 0, numOverflow = 0;
     const WideLocal noLists = { nullptr, nullptr, nullptr, nullptr, 0u };   // what the packets do not decide goes to the launch's exact queue
+    const PacketConst2 beamEntries = (PacketConst2)(uintptr_t)beam.entries;
+    const PacketConst1 beamCounts = (PacketConst1)(uintptr_t)beam.counts;
+    uint32_t numScanned = 0, numWalkedOffset = 0, numWalkedNoList = 0;   // packets, wave-uniform (BeamLists::stats)
 
     for (;;)
     {
@@ -80,6 +102,24 @@ __global__ void __launch_bounds__(RT_BLOCK) k_trace_packet(const RtSceneDesc sce
                     act = true;
                 }
             }
+            // ---- the front end: this packet's leaves from its tile's list (above), or the walk.  Wave-uniform. ----
+            // At bounce 0 the regions of the arena are filled one after the other (generateShardCounts), so slot == idx: the packet's paths are the slots
+            // first .. first + 63 = pixel slots pixelSlot .. of pass `pass` of the batch, and a tile is 64 consecutive pixel slots from a multiple of 64 on.
+            uint32_t listCount = RT_BEAM_NO_LIST, listBase = 0u;
+            if (beamEntries != nullptr)
+            {
+                const uint32_t pass = first / beam.slotsPerPass, pixelSlot = first - pass * beam.slotsPerPass;
+                const uint32_t here = count - first < 64u ? count - first : 64u;
+                const PacketConstF offset = (PacketConstF)((uintptr_t)beam.passes + (size_t)pass * sizeof(DevPass) + offsetof(DevPass, sampleOffset));
+                if (!(fabsf(offset[0]) <= beam.margin && fabsf(offset[1]) <= beam.margin)) numWalkedOffset++;
+                else
+                {
+                    // (a packet that straddles two tiles or two passes -- a slot table whose length is no multiple of 64 -- has no list of its own)
+                    if ((pixelSlot & 63u) == 0u && pixelSlot + here <= beam.slotsPerPass) { listCount = beamCounts[pixelSlot >> 6]; listBase = (pixelSlot >> 6) * beam.capacity; }
+                    if (listCount == RT_BEAM_NO_LIST) numWalkedNoList++; else numScanned++;
+                }
+            }
+            const bool scan = listCount != RT_BEAM_NO_LIST;
             bool overflow = false;
             if (__ballot(act) != 0ull)
             {
@@ -87,7 +127,9 @@ __global__ void __launch_bounds__(RT_BLOCK) k_trace_packet(const RtSceneDesc sce
                 const Ray gateRay = makeRayUnsafe3(ray.origin, ray.dir);   // = the ray transformRayUnsafe built
                 // ---- the shared walk: cur, sp and the stack are wave-uniform ----
                 uint32_t stackLo = 0u, stackHi = 0u;   // entry e < 64 in lane e of stackLo, else in lane e - 64 of stackHi
-                uint32_t sp = 0u, cur = 0u;            // node 0 holds the children of the binary tree's root
+                uint32_t sp = 0u, cur = scan ? RT_WIDE_EMPTY : 0u;   // node 0 holds the children of the binary tree's root; a scan starts with nothing in hand and "pops" its first entry
+                uint32_t listAt = 0u;                  // scan: the next entry
+                float dminCur = 0.0f;                  // scan: the entry's dmin (wave-uniform); the walk: 0, which excludes no lane
                 for (;;)
                 {
                     bool pop = true;
@@ -139,7 +181,7 @@ __global__ void __launch_bounds__(RT_BLOCK) k_trace_packet(const RtSceneDesc sce
                             if (!intersectTriangleRay(ray, nv0, ne1, ne2, u1, v1, t1)) t1 = inf;
                         }
                         const float lo = fminf(t0, t1);
-                        const bool candidate = act && lo < best + tol;
+                        const bool candidate = act && lo < best + tol && dminCur < best + (tol + tol);   // (scan: a lane whose limit the entry lies behind skips it)
                         if (__ballot(candidate) != 0ull)
                         {
                             const PacketU4 gmin = gates[2u * firstTri], gmax = gates[2u * firstTri + 1u];
@@ -150,7 +192,17 @@ __global__ void __launch_bounds__(RT_BLOCK) k_trace_packet(const RtSceneDesc sce
                         }
                     }
                     // (else: an unused child slot whose corner point a ray happened to meet)
-                    if (pop)
+                    if (scan)
+                    {
+                        // ---- the list: entries ascend in dmin and hits only shorten the rays, so the first entry no lane's limit reaches ends the scan ----
+                        if (listAt == listCount) break;
+                        const PacketU2 entry = beamEntries[listBase + listAt];
+                        ++listAt;
+                        dminCur = __uint_as_float(entry.y);
+                        if (__ballot(act && dminCur < best + (tol + tol)) == 0ull) break;
+                        cur = entry.x;
+                    }
+                    else if (pop)
                     {
                         if (sp == 0u) break;
                         --sp;
@@ -163,6 +215,12 @@ __global__ void __launch_bounds__(RT_BLOCK) k_trace_packet(const RtSceneDesc sce
         }
     }
     wideFlushTallies<14u>(sTally, true, true, 0u, numRetraced, numUntrusted, numOverflow, true, counters);   // tallies per LANE (every lane adds), sTally cleared above; no any-hit rays here
+    if (beamEntries != nullptr && lane == 0u)   // the packets' ways, per wave (rtgpu_get_beam_list_info)
+    {
+        if (numScanned) atomicAdd(beam.stats + 0, (unsigned long long)numScanned);
+        if (numWalkedOffset) atomicAdd(beam.stats + 1, (unsigned long long)numWalkedOffset);
+        if (numWalkedNoList) atomicAdd(beam.stats + 2, (unsigned long long)numWalkedNoList);
+    }
 }
 #undef RT_PACKET_CE
 #endif   // RT_DEVICE_KERNELS

@@ -67,6 +67,25 @@ struct WideBvh
     float base[3], step[3], bound[3];   // the grid; bound: the largest |coordinate| a plane of it has, which bounds a slab term of the fold (rt_wide_walk.h)
 };
 
+// Beam lists (rt_beam_lists.h builds them, host and device; k_trace_packet scans them): per TILE = 64 consecutive slots of the slot -> pixel table (one wave of
+// k_trace_packet) the leaves of the tree above whose exact box a camera ray of the tile's pixels can pass at any sample offset of at most `margin` pixels per
+// axis, nearest first.  Tile t: counts[t] entries at entries[t * capacity ..], each {the leaf's reference as the node records hold it, bits of dmin}, ascending
+// in (dmin, reference); dmin: a lower bound of the ray parameter at which a unit-direction ray from the eye can enter the leaf's exact box.
+// counts[t] == RT_BEAM_NO_LIST: the tile has none (more leaves than the capacity, or the builder's stack ran out) and walks the tree.
+#define RT_BEAM_NO_LIST 0xFFFFFFFFu
+#define RT_BEAM_MAX_CAPACITY 64u     // one entry per lane of the building wave
+struct BeamEntry { uint32_t leaf; uint32_t dminBits; };
+struct BeamLists
+{
+    const BeamEntry* entries;    // nullptr: the launch has no lists
+    const uint32_t* counts;
+    uint32_t capacity;           // entries per tile, <= RT_BEAM_MAX_CAPACITY
+    uint32_t slotsPerPass;       // the slot -> pixel table's length: slot = pass in batch * slotsPerPass + pixel slot
+    float margin;                // m, in pixels: a pass whose |sampleOffset| exceeds it on an axis walks
+    const void* passes;          // the batch's DevPass records (their sampleOffset)
+    unsigned long long* stats;   // [0] packets served from lists, [1] packets that walked for their pass's offset, [2] packets that walked for "no list"
+};
+
 // two-level scenes (k_trace_wide2): one node array and one gate array for all levels
 struct WideLevel   // 64 bytes
 {

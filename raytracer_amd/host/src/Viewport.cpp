@@ -518,10 +518,19 @@ void Viewport::ClearAccumulation()
     if (mRenderer) { mRenderer->Reset(); mRenderer->SetActiveBlocks({}); }
 }
 
+// The sample offsets are normal with deviation antiAliasingSpread: the device's beam lists (rtgpu_set_beam_margin) serve the passes within three deviations,
+// 99.5 % of them, and the others walk.
+static void PushBeamMargin(IRenderer* renderer, float antiAliasingSpread)
+{
+    PathTracerMIS* pt = dynamic_cast<PathTracerMIS*>(renderer);
+    if (pt && pt->GetDeviceContext()) (void)rtgpu_set_beam_margin(pt->GetDeviceContext(), fminf(3.0f * antiAliasingSpread, 64.0f));
+}
+
 bool Viewport::SetRenderer(const RendererPtr& renderer)
 {
     PinSumBuffers(false);
     mRenderer = renderer;
+    PushBeamMargin(mRenderer.get(), mParams.antiAliasingSpread);
     if (mRenderer && mWidth && mHeight) return mRenderer->Resize(mWidth, mHeight);
     return true;
 }
@@ -563,6 +572,7 @@ bool Viewport::SetRenderingParams(const RenderingParams& params)
     if (params.maxRayDepth >= 255u || params.antiAliasingSpread < 0.0f) return false;
     if (params.samplingParams.dimensions > HaltonSequence::MaxDimensions) return false;
     mParams = params;
+    PushBeamMargin(mRenderer.get(), mParams.antiAliasingSpread);
     return true;
 }
 

@@ -217,6 +217,7 @@ def main():
            "render_pass_ms": {"median": float(np.median(per_pass)), "min": float(min(per_pass)), "max": float(max(per_pass)), "passes_per_batch": 20}}
     rel_mse = lambda image: float(np.mean((image.astype(np.float64) - reference) ** 2 / (reference.astype(np.float64) ** 2 + 0.01)))   # noqa: E731
     names = ("depth", "normal", "position", "base_color", "object_id")
+    builds_still = vp.beam_list_info()["builds"]   # the reference render and the timed batches above: one camera, so its beam lists are built (include/rtgpu.h)
     stream = torch.cuda.Stream()   # (the null stream would send the calls through the wrappers' side stream)
     with torch.cuda.stream(stream):
         # the sequence the caller drives
@@ -233,6 +234,8 @@ def main():
             temporal = vp.denoise(guide, temporal=True, variance=True, device=True)
             previous = guide
         stream.synchronize()
+        # a camera that turns with every frame must never pay for a build of beam lists: the sequence adds none
+        out["beam_list_builds"] = {"still_reference_and_timed_batches": int(builds_still), "in_the_turning_sequence": int(vp.beam_list_info()["builds"] - builds_still)}
         sums = vp.sum_buffer(secondary=True)
         scale = np.float32(1.0 / args.passes)
         alone = vp.denoise(guide, variance=True, device=True)

@@ -40,16 +40,26 @@ def main():
     nodes.tofile(os.path.join(out, "nodes.bin")); triangles.astype(np.float32).tofile(os.path.join(out, "tris.bin"))
     vp = ra.Viewport(w, h, seed=20260928, max_ray_depth=depth)
     rays = []
+    pixels = []   # of the primary rays, in their order in rays.bin (beam_lists_model.cpp: which tile a recorded ray belongs to)
     for p_index in range(2):
         p = vp.next_pass_params(camera)
+        if p_index == 0:
+            # the pinhole camera and the frame, for beam_lists_model.cpp: width, height, antiAliasingSpread, aspectRatio, tanHalfFoV, localToWorld (16, row major)
+            cam = p.camera
+            with open(os.path.join(out, "camera.txt"), "w") as f:
+                f.write("%d %d %.9g %.9g %.9g\n" % (w, h, 0.5, cam.aspectRatio, cam.tanHalfFoV))   # 0.5: ra.Viewport's default anti_aliasing_spread
+                f.write(" ".join("%.9g" % x for x in cam.localToWorld[:]) + "\n")
         for y in range(stride // 2 + p_index, h, stride):
             for x in range(stride // 2 + 3 * p_index, w, stride):
                 v = oracle_lib.render_pixel_paths(scene.desc, p, w, h, x, y)
+                if len(v):
+                    pixels.append((x, y))
                 for k in range(len(v)):
                     # origin, direction, hit distance, bounce, hit point, shading normal
                     rays.append(np.concatenate([v[k, 0:6], v[k, 8:9], [float(k)], v[k, 11:14], v[k, 14:17]]))
     rays = np.array(rays, dtype=np.float32)
     rays.tofile(os.path.join(out, "rays.bin"))
+    np.array(pixels, dtype=np.int32).tofile(os.path.join(out, "pixels.bin"))
     with open(os.path.join(out, "meta.txt"), "w") as f:
         f.write("%d %d %d %.9g %.9g %.9g\n" % (len(nodes), len(triangles), len(rays), sun[0], sun[1], sun[2]))
     print("nodes %d, triangles %d, rays %d (%.2f per path), sun %s -> %s" % (len(nodes), len(triangles), len(rays), len(rays) / max(1, np.count_nonzero(rays[:, 7] == 0)), sun, out))
